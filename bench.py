@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the hypergraph message-passing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extras] [--no-kernel-events]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, config, final loss;
+gradient_exchange when N > 1).  Everything else below (roofline and per-kernel figures, the untimed extra passes, the CPU baseline) is measured
+only with --full; there the --no-* switches leave parts of it out.  --dump-outputs DIR writes what the last timed step computed as .npy files
+(dump_outputs below).
 
 Metric (BASELINE.json / SURVEY.md §8 d1): hyperedges aggregated per second = E * L * steps / wall time, where one
 "hyperedge aggregated" is one hyperedge taken through one layer's node->hyperedge and hyperedge->node phases.
@@ -80,6 +85,10 @@ def parse():
     ap.add_argument('--order', type=int, default=3)
     ap.add_argument('--dim', type=int, default=0, help='embedding width instead of the config\'s (the reference\'s default is --emb 32, Helpers/GlobalSettings.py:30)')
     ap.add_argument('--layer', default='ihgnn', choices=['ihgnn', 'hgcn'])
+    ap.add_argument('--full', action='store_true', help='measure more than the headline: roofline and per-kernel figures (HIP events around the roofline kernel inside '
+                                                        'the timed region), the untimed extra passes and the CPU baseline (each can be left out with its --no-* switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write the loss and the parameters the last timed step left as DIR/<name>.npy (float32; '
+                                                          'tables above 1 MiB as a fixed sample of their rows, under 64 MB in all)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-scale', type=float, default=0.125, help='fraction of the workload the CPU baseline runs on (C3: ~3 s per oracle step on 32 threads; 7 steps)')
     ap.add_argument('--no-kernel-events', action='store_true', help='do not bracket kernels with HIP events')
@@ -93,7 +102,41 @@ def parse():
                     help='gradient exchange for --gpus > 1: auto (ihgnn_amd.distributed.choose_gradient_sync: cotangent wherever the fused batch tail runs) | cotangent: all-gather of '
                          'the batch rows\' cotangents, propagation backward on the union, no dense exchange | one flat all-reduce | per-bucket all-reduces from a side stream | '
                          'reduce-scatter + sharded Adam + all-gather')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what the headline needs: no HIP events in the timed region, no extra passes after it, no CPU baseline
+        args.no_cpu_baseline = args.no_extras = args.no_kernel_events = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 56 << 20        # --dump-outputs: the arrays of all files together (under 64 MB with the .npy headers)
+DUMP_WHOLE_BYTES = 1 << 20         # a parameter up to this size is written whole, a larger one as a sample of its rows
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step - its loss and every parameter as Adam left it - as float32
+    DIR/loss.npy and DIR/param.<name>.npy.  The parameters above DUMP_WHOLE_BYTES share what is left of DUMP_LIMIT_BYTES equally, each written as the rows
+    a generator of fixed seed picks (sorted): the same rows in every run and every build at the same shapes."""
+    import numpy as np
+    import torch
+    params = [(name, p.detach()) for name, p in model.named_parameters()]
+    whole = [(name, p) for name, p in params if 4 * p.numel() <= DUMP_WHOLE_BYTES]
+    sampled = [(name, p) for name, p in params if 4 * p.numel() > DUMP_WHOLE_BYTES]
+    share = (DUMP_LIMIT_BYTES - 4 - sum(4 * p.numel() for _, p in whole)) // max(len(sampled), 1)
+    arrays = {'loss': loss.detach().reshape(1)}
+    arrays.update((f'param.{name}', p) for name, p in whole)
+    for name, p in sampled:
+        rows = p.shape[0]
+        keep = min(rows, share // (4 * max(p[0].numel(), 1)))
+        pick = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays[f'param.{name}'] = p[torch.from_numpy(pick).to(p.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    assert total <= DUMP_LIMIT_BYTES, total
 
 
 def launch_ranks(args) -> int:
@@ -422,6 +465,8 @@ def main():
     profiler.stop()
     kernels = profiler.summary() if not args.no_kernel_events else {}
     final_loss = float(last.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)         # before the extra passes below step the model again
 
     table, table_steps, restricted_elapsed, fwd_elapsed, stress, eval_stats, f32_elapsed, k5_alone = {}, min(args.steps, 5), None, None, None, None, None, None
     dense_cot_elapsed = None
@@ -555,8 +600,11 @@ def main():
     k5_compulsory = touched * row + Er * row + 12 * Er        # every touched node row once + the [E,d] store + the ids
     k5_algorithmic = Er * (16 * dim + 12)                      # 3 ids + 3 row reads + 1 row write per hyperedge (row of the launch)
     pmc = None                                                 # HBM bytes per launch from the committed PMC passes (profiles/), newest round first
-    rounds = sorted((d for d in os.listdir(os.path.join(REPO, 'profiles')) if d.startswith('r') and d[1:].isdigit()), key=lambda d: -int(d[1:]))
-    for pmc_file in [os.path.join(REPO, 'profiles', r, f'pmc_traffic_{args.config}.json') for r in rounds] + [os.path.join(REPO, 'profiles', 'r1', 'pmc_traffic.json')]:
+    pmc_files = []                                             # (--full only: the roofline objects and step_bytes quote them)
+    if args.full:
+        rounds = sorted((d for d in os.listdir(os.path.join(REPO, 'profiles')) if d.startswith('r') and d[1:].isdigit()), key=lambda d: -int(d[1:]))
+        pmc_files = [os.path.join(REPO, 'profiles', r, f'pmc_traffic_{args.config}.json') for r in rounds] + [os.path.join(REPO, 'profiles', 'r1', 'pmc_traffic.json')]
+    for pmc_file in pmc_files:
         if os.path.exists(pmc_file):
             cand = json.load(open(pmc_file))
             if (cand.get('workload'), cand.get('dim'), cand.get('edges')) == (args.config, dim, E) and cand.get('rows', E) == Er:
@@ -757,20 +805,21 @@ def main():
                                            'is a cache rate (it may exceed the HBM peak; frac_algorithmic is null then): target_met is the STRICTER reading - compulsory bytes '
                                            '(every row once) / time >= 0.40 of 8 TB/s.  The HBM-resident reading of the same kernel is roofline_gather_stress')
         out['roofline_node_to_hyperedge'] = k5_outside
-    # SURVEY §8 d3's byte model against what the step really moves: the model prices the reference's two-phase formulation (K5 + K7 per layer, training ~ 3 x forward);
-    # the build's re-associations (two-hop fusion, node-level form of the interactive layer) move fewer bytes for the same result, so model / time can exceed the HBM peak
-    d3_fwd = (16 * dim + 12 + 12 * dim + 12) * E * layers + (4 * dim + 8) * N_public * layers      # (the reference formulation: every interaction a hyperedge, every node a row)
-    step_s = elapsed / args.steps
-    measured = measured_src = None
-    if pmc is not None and pmc.get('step_l2_miss_bytes'):
-        measured = int(pmc['step_l2_miss_bytes'])
-        measured_src = f'NOT measured in this run: every kernel of one training step of the committed in-situ counter pass {pmc_name} (commit {pmc.get("commit", "unrecorded")})'
-    out['step_bytes'] = dict(model_d3_forward=d3_fwd, model_d3_training=3 * d3_fwd, model_d3_gbs=round(3 * d3_fwd / step_s / 1e9, 1),
-                             model_d3_frac_of_hbm_peak=round(3 * d3_fwd / step_s / 1e9 / HBM_PEAK_GBS, 3), measured_l2_miss=measured,
-                             measured_l2_miss_gbs=round(measured / step_s / 1e9, 1) if measured else None, measured_source=measured_src, ms=round(1e3 * step_s, 4),
-                             note='model_d3 = SURVEY §8 d3 algorithmic bytes of the REFERENCE formulation ((16 d + 12) + (12 d + 12) per hyperedge-layer + (4 d + 8) per node-layer forward, '
-                                  'training = 3 x); a model rate above the HBM peak is not skipped work: the step computes the same function with fewer bytes (DESIGN.md section 4); '
-                                  'measured_l2_miss = FETCH_SIZE (doubled) + WRITE_SIZE at the L2 <-> fabric boundary, Infinity-Cache hits included')
+    if args.full:
+        # SURVEY §8 d3's byte model against what the step really moves: the model prices the reference's two-phase formulation (K5 + K7 per layer, training ~ 3 x forward);
+        # the build's re-associations (two-hop fusion, node-level form of the interactive layer) move fewer bytes for the same result, so model / time can exceed the HBM peak
+        d3_fwd = (16 * dim + 12 + 12 * dim + 12) * E * layers + (4 * dim + 8) * N_public * layers      # (the reference formulation: every interaction a hyperedge, every node a row)
+        step_s = elapsed / args.steps
+        measured = measured_src = None
+        if pmc is not None and pmc.get('step_l2_miss_bytes'):
+            measured = int(pmc['step_l2_miss_bytes'])
+            measured_src = f'NOT measured in this run: every kernel of one training step of the committed in-situ counter pass {pmc_name} (commit {pmc.get("commit", "unrecorded")})'
+        out['step_bytes'] = dict(model_d3_forward=d3_fwd, model_d3_training=3 * d3_fwd, model_d3_gbs=round(3 * d3_fwd / step_s / 1e9, 1),
+                                 model_d3_frac_of_hbm_peak=round(3 * d3_fwd / step_s / 1e9 / HBM_PEAK_GBS, 3), measured_l2_miss=measured,
+                                 measured_l2_miss_gbs=round(measured / step_s / 1e9, 1) if measured else None, measured_source=measured_src, ms=round(1e3 * step_s, 4),
+                                 note='model_d3 = SURVEY §8 d3 algorithmic bytes of the REFERENCE formulation ((16 d + 12) + (12 d + 12) per hyperedge-layer + (4 d + 8) per node-layer forward, '
+                                      'training = 3 x); a model rate above the HBM peak is not skipped work: the step computes the same function with fewer bytes (DESIGN.md section 4); '
+                                      'measured_l2_miss = FETCH_SIZE (doubled) + WRITE_SIZE at the L2 <-> fabric boundary, Infinity-Cache hits included')
     if stress is not None:
         out['roofline_gather_stress'] = stress
     if eval_stats is not None:

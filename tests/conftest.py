@@ -65,12 +65,16 @@ def state_digest(tensors):
 
 
 def f8_gradient_error(z, tag, name, grad):
-    """max relative deviation of a parameter gradient from what F8 keeps of it (full, or every 4th row + row/col sums)."""
+    """max relative deviation of a parameter gradient from what F8 keeps of it (full, or every 4th row + row/col sums; a gradient whose sums cancel
+    is kept whole in ``tests/golden/f8_whole_gradients.npz`` and compared whole)."""
     g = np.asarray(grad, np.float64)
     pre = f'{tag}.grad.{name}.'
 
     def rel(a, b):
         return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+    whole = np.load(os.path.join(GOLDEN, 'f8_whole_gradients.npz'))
+    if pre + 'full' in whole.files:
+        return rel(g, whole[pre + 'full'].astype(np.float64))
     if pre + 'full' in z.files:
         return rel(g, z[pre + 'full'].astype(np.float64))
     return max(rel(g[::4], z[pre + 'rows4'].astype(np.float64)), rel(g.sum(1), z[pre + 'rowsum']), rel(g.sum(0), z[pre + 'colsum']))

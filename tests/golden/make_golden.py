@@ -18,6 +18,7 @@ import json
 import os
 import random
 import sys
+import tempfile
 import types
 
 import numpy as np
@@ -399,10 +400,11 @@ def make_f7():
 F8_CASES = (('d128_o3', 3, 3, 128, 801), ('d128_o2', 3, 2, 128, 802), ('d256_o3', 2, 3, 256, 803))
 
 
-def make_f8(ds):
+def make_f8(ds, whole_only=False):
+    """F8 -> f8_wide_models.npz, and the digested gradients whose sums cancel, whole -> f8_whole_gradients.npz (only that file: ``whole_only``)."""
     sys.path.insert(0, HERE)
-    from seeded_weights import big_gradient_digest, seeded_state
-    out = {}
+    from seeded_weights import big_gradient_digest, digest_sums_cancel, seeded_state
+    out, whole = {}, {}
     for tag, L, order, d, seed in F8_CASES:
         seed_all(seed)
         m = RawGnn(CPU, ds, d, IHGNNLayer, L, order, False, HemPredictionLayer, 0.5)
@@ -419,6 +421,8 @@ def make_f8(ds):
         for n, p in m.named_parameters():
             for part, v in big_gradient_digest(p.grad.numpy()).items():
                 out[f'{tag}.grad.{n}.{part}'] = v
+            if digest_sums_cancel(p.grad.numpy()):
+                whole[f'{tag}.grad.{n}.full'] = p.grad.numpy().astype(np.float32)
         with torch.no_grad():
             m.save_features_for_test()
             out[f'{tag}.features'] = m._saved_output_feature.numpy().copy()
@@ -428,7 +432,9 @@ def make_f8(ds):
         out.update({f'{tag}.u': u.numpy(), f'{tag}.q': q.numpy(), f'{tag}.i': i.numpy(), f'{tag}.flags': flags.numpy(),
                     f'{tag}.scores': scores.detach().numpy(), f'{tag}.loss': np.float64(loss.item()),
                     f'{tag}.cfg': np.array([L, order, d, seed], np.int64)})
-    np.savez(os.path.join(HERE, 'f8_wide_models.npz'), **out)
+    if not whole_only:
+        np.savez(os.path.join(HERE, 'f8_wide_models.npz'), **out)
+    np.savez_compressed(os.path.join(HERE, 'f8_whole_gradients.npz'), **whole)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -586,9 +592,9 @@ if __name__ == '__main__':
     if sys.argv[1:] == ['f9']:
         make_f9()
         sys.exit(0)
-    if sys.argv[1:] == ['f8']:                       # add the wide-model fixture without rewriting the others
+    if sys.argv[1:] in (['f8'], ['f8_whole']):      # add the wide-model fixture (f8_whole: only its whole gradients) without rewriting the others
         w = small_workload()
-        make_f8(load_dataset(synth.write_files(w, os.path.join('/tmp', 'ihgnn_golden_small'))))
+        make_f8(load_dataset(synth.write_files(w, os.path.join(tempfile.gettempdir(), 'ihgnn_golden_small'))), whole_only=sys.argv[1:] == ['f8_whole'])
         sys.exit(0)
     ds_tiny = make_f1()
     ds_small, _ = make_f2(ds_tiny)

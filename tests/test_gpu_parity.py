@@ -2949,7 +2949,7 @@ def test_bench_launches_its_own_ranks(sync):
     `gradient_exchange` object names the mode that ran (`auto` resolves to the cotangent exchange for a model on the fused batch tail), the rank count, the bytes a rank
     hands over and receives per step, and every rank's own step time and exposed exchange time."""
     import json
-    r = _run(['bench.py', '--gpus', '2', '--device', '0', '--backend', 'gloo', '--config', 'C1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-extras', '--sync', sync])
+    r = _run(['bench.py', '--full', '--gpus', '2', '--device', '0', '--backend', 'gloo', '--config', 'C1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-extras', '--sync', sync])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['config']['parallelism'] == 'dp2' and line['value'] > 0

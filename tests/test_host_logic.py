@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import GOLDEN, REPO
 from ihgnn_amd import synth
 from ihgnn_amd.Dataset import GraphDataset, TestSearchLogDataLoader
 from ihgnn_amd.Helpers.ArgsParser import parse_args
@@ -661,3 +661,46 @@ def test_user_reduced_member_lists_in_chunks_are_cut_where_the_user_changes():
     parts = heavy.member_csr_qi_chunks(4)
     users = heavy.i3_host[:, 0]
     assert all(users[e1 - 1] != users[e1] for _, e1, _, _ in parts[:-1]) and sum(e1 - e0 for e0, e1, _, _ in parts) == heavy.edge_count
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench', os.path.join(REPO, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_measures_the_headline_only(monkeypatch):
+    """``bench.py`` without ``--full`` leaves out every pass beside the headline; ``--full`` keeps them, each switch of its own still honoured."""
+    bench = _bench_module()
+    monkeypatch.setattr('sys.argv', ['bench.py', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.full, a.steps, a.warmup, a.no_cpu_baseline, a.no_extras, a.no_kernel_events, a.dump_outputs) == (False, 7, 2, True, True, True, None)
+    monkeypatch.setattr('sys.argv', ['bench.py', '--full', '--no-extras', '--dump-outputs', 'out'])
+    a = bench.parse()
+    assert (a.full, a.no_cpu_baseline, a.no_extras, a.no_kernel_events, a.dump_outputs) == (True, False, True, False, 'out')
+
+
+def test_bench_dump_outputs_is_float32_bounded_and_the_same_rows_every_run(tmp_path):
+    """``--dump-outputs``: the loss and every parameter as float32 .npy; small parameters whole, large tables as the same sample of rows in every run, under 64 MB in all."""
+    bench = _bench_module()
+    m = torch.nn.Module()
+    m.users = torch.nn.Parameter(torch.randn(230_001, 128))
+    m.items = torch.nn.Parameter(torch.randn(120_001, 128))
+    m.bias = torch.nn.Parameter(torch.randn(3_000_000))
+    m.w = torch.nn.Parameter(torch.randn(7, 64, 64))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(0.25), m)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['loss.npy', 'param.bias.npy', 'param.items.npy', 'param.users.npy', 'param.w.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) < 64_000_000
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'param.w.npy'), m.w.detach().numpy())
+    users = np.load(tmp_path / 'a' / 'param.users.npy')
+    assert 0 < users.shape[0] < 230_001 and users.shape[1] == 128
+    rows = {r.tobytes() for r in m.users.detach().numpy()}
+    assert all(r.tobytes() in rows for r in users)                 # whole rows of the table
+    assert np.load(tmp_path / 'a' / 'loss.npy').tolist() == [0.25]

@@ -41,7 +41,7 @@ def main():
         for lst, us in zip(per_role, k7):
             if us is not None:
                 lst.append(us)
-    out = dict(command='rocprofv3 --kernel-trace --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline',
+    out = dict(command='rocprofv3 --kernel-trace --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline',
                kernel='node_segment_sum_kernel<4, 32>', steps=steps,
                note='launches longer than 100 us, by position in the training step, steps with every layer over all rows (the small launches of the same kernel are the bag means and the batch tail)',
                roles={name: dict(avg_us=round(sum(v) / len(v), 1), min_us=round(min(v), 1), max_us=round(max(v), 1), launches=len(v)) for name, v in zip(ROLES, per_role) if v})

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the profile artefacts of a round on the GPU box (run through gpurun from the repo root):
 #   tools/profile_round.sh <tag> [config]   -> gpurun_out/<tag>/...      (config: C3 by default; C5: fewer steps, every counter pass over bench.py itself)
-# 1. rocprofv3 --kernel-trace --stats of the default bench (10 steps)      2. the default bench line, unprofiled
+# 1. rocprofv3 --kernel-trace --stats of bench.py --full (10 steps)      2. the bench.py --full line, unprofiled
 # 3. PMC passes (separate runs): FETCH_SIZE, WRITE_SIZE over 3 bench steps and over K5 / K7 launched alone (tools/kbench.py); SQ_VALU_MFMA_BUSY_CYCLES + GRBM_GUI_ACTIVE over the interact kernels
 set -u
 TAG=${1:-prof}
@@ -10,9 +10,9 @@ OUT=gpurun_out/$TAG
 if [ "$CONFIG" = "C5" ]; then STEPS="--steps 3 --warmup 1"; PSTEPS="--steps 2 --warmup 1"; else STEPS="--steps 10 --warmup 3"; PSTEPS="--steps 3 --warmup 2"; fi
 mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --config $CONFIG $STEPS --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
-if [ "$CONFIG" = "C3" ]; then python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-else python3 bench.py --config $CONFIG $STEPS --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err; fi
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --full --config $CONFIG $STEPS --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
+if [ "$CONFIG" = "C3" ]; then python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+else python3 bench.py --full --config $CONFIG $STEPS --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err; fi
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -- python3 bench.py --config $CONFIG $PSTEPS --no-cpu-baseline --no-extras --no-kernel-events > $OUT/pmc_$c.json 2> $OUT/pmc_$c.log
 done

@@ -3,8 +3,8 @@
 # union the propagation backward runs on), with the per-kernel table; and the layout's collapses forced on at C3, where `auto` leaves them off.  Output: gpurun_out/r6/probe/
 export TMPDIR=/tmp
 O=gpurun_out/r6/probe; mkdir -p $O
-for k in 1 8; do python bench.py --union-of-ranks $k --no-cpu-baseline > $O/table_C3_union$k.json 2> $O/table_C3_union$k.err; done
-for k in 1 8; do python bench.py --config C5 --union-of-ranks $k --steps 3 --warmup 1 --no-cpu-baseline > $O/table_C5_union$k.json 2> $O/table_C5_union$k.err; done
+for k in 1 8; do python bench.py --full --union-of-ranks $k --no-cpu-baseline > $O/table_C3_union$k.json 2> $O/table_C3_union$k.err; done
+for k in 1 8; do python bench.py --full --config C5 --union-of-ranks $k --steps 3 --warmup 1 --no-cpu-baseline > $O/table_C5_union$k.json 2> $O/table_C5_union$k.err; done
 python - <<'PY'
 import json
 for c in ('C3','C5'):
