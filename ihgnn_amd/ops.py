@@ -1307,8 +1307,8 @@ class TailGradients:
         (addressed by ``rows_upper`` where the layout's numbering differs from the public one)."""
         rows = self._rows_of(upper)
         if self.leader is None:
-            if upper and self.rows_upper is not None:
-                raise _lib.IhgnnHipError('a compact layout needs the combined row gradients (batches of at most 32,768 rows)')
+            # (beyond one combine launch: the scatter in row chunks; a negative row - an isolated node above layer 0, a rank's own non-leader duplicate after the
+            #  exchange - is skipped by the kernel like every other row that takes no part)
             _scatter_rows(self.rowgrad, col0, width, rows, dense, tail, tail_offset)
             return
         lib = _lib.load()

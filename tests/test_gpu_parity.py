@@ -2726,16 +2726,35 @@ def test_last_layer_backward_skips_the_zero_rows_of_its_cotangent(monkeypatch):
     assert torch.equal(x.grad, want)
 
 
-def test_recorded_training_step_equals_the_eager_step():
+def test_recorded_training_step_equals_the_eager_step(monkeypatch):
     """``CapturedTrainingStep`` (forward + backward + Adam recorded as one hipGraph, the Adam scalars read from device memory) replayed four
     times - with a learning-rate change in between - against the same four eager steps: same losses, same parameters, same Adam state."""
-    from ihgnn_amd import synth
+    _recorded_step_equals_the_eager_step(100, False, monkeypatch)
+
+
+def test_recorded_training_step_equals_the_eager_step_beyond_one_scatter_launch(monkeypatch):
+    """The same at 33,000 batch rows (beyond one scatter launch: the chunked scatter is recorded) over a compact layout with multiplicities (config C5's kind)."""
+    _recorded_step_equals_the_eager_step(1000, True, monkeypatch)
+
+
+def _recorded_step_equals_the_eager_step(positives, collapsed, monkeypatch):
+    from ihgnn_amd import layout as layout_mod, synth
     from ihgnn_amd.Dataset import GraphDataset
     from ihgnn_amd.captured_step import CapturedTrainingStep
     from ihgnn_amd.optim import Adam
     w = synth.draw(300, 40, 200, 50, 4000, seed=21)
-    ds = GraphDataset.from_arrays(w.user_count, w.query_count, w.item_count, w.vocab_size, w.bag_words, w.bag_offsets, w.triples, device=dev())
-    batches = list(ds.sample_batches(100, 4, seed=5))
+    triples = w.triples
+    if collapsed:
+        monkeypatch.setattr(layout_mod, 'COMPACT_NODES', '1')
+        monkeypatch.setattr(layout_mod, 'EDGE_MULTIPLICITY', '1')
+        g = np.random.default_rng(4)
+        live = [g.choice(n, n // 3, replace=False) for n in (300, 40, 200)]           # two thirds of every type in no hyperedge; half of the triples repeated
+        base = np.stack([g.choice(live[k], 3000) for k in range(3)], 1)
+        triples = np.concatenate([base, base[:1500]])
+    ds = GraphDataset.from_arrays(w.user_count, w.query_count, w.item_count, w.vocab_size, w.bag_words, w.bag_offsets, triples, device=dev())
+    assert ds.hypergraph.layout.compact == collapsed and (ds.hypergraph.layout.edge_weight is not None) == collapsed
+    batches = list(ds.sample_batches(positives, 4, seed=5))
+    assert (3 * batches[0][0].shape[0] > SCATTER_LIMIT) == collapsed
 
     def run(recorded):
         torch.manual_seed(7)
@@ -2890,6 +2909,223 @@ def test_recorded_step_refuses_what_it_cannot_replay(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------
+# batch tails beyond one scatter launch (ihg_batch_scatter_max_rows() = 32,768 rows): no combine, no leaders, every tap through ops._scatter_rows in row
+# chunks - model-level gradients against the float64 oracle, at the limit and above it, over every layout
+# ---------------------------------------------------------------------------------------------
+SCATTER_LIMIT = 32768    # rows of one ihg_batch_scatter_add / ihg_batch_combine launch (ihg_batch_scatter_max_rows(), ops.SCATTER_CHUNK_ROWS)
+BIG_UQI = (500, 24, 420)
+BIG_TABLES = ('embeddings.embedding_user.weight', 'embeddings.embedding_item.weight', 'embeddings.embedding_bag_vocabulary.weight', 'prediction_layer.items_bias')
+_BIG_GRAPH = {}
+
+
+def _big_tail_graph():
+    """Users / queries / items 500 / 24 / 420, about a third of every type in a hyperedge (the rest isolated) and half of the triples written twice: a compact
+    layout has isolated nodes to leave out, a layout with multiplicities repeated triples to collapse.  -> ``{w: its query bags, triples, live: ids per type, g: the float64 oracle graph}`` (built once)."""
+    if not _BIG_GRAPH:
+        from ihgnn_amd import synth
+        from oracle import ihgnn_ref as ref
+        U, Q, I = BIG_UQI
+        rng = np.random.default_rng(77)
+        live = tuple(np.sort(rng.choice(n, k, replace=False)) for n, k in ((U, 170), (Q, 15), (I, 150)))
+        base = np.stack([rng.choice(live[t], 5000) for t in range(3)], 1)
+        triples = np.concatenate([base, base[:2500]])
+        w = synth.draw(U, Q, I, 40, 10, seed=3)                          # (only its query bags are used)
+        _BIG_GRAPH.update(w=w, triples=triples, live=live, g=ref.HyperGraph(triples, U, Q, I).to(torch.float64))
+    return _BIG_GRAPH
+
+
+def _big_tail_dataset(layout, monkeypatch):
+    from ihgnn_amd import layout as layout_mod
+    from ihgnn_amd.Dataset import GraphDataset
+    big = _big_tail_graph()
+    compact, mult = {'plain': ('0', '0'), 'mult': ('0', '1'), 'compact': ('1', '0'), 'compact_mult': ('1', '1')}[layout]
+    monkeypatch.setattr(layout_mod, 'COMPACT_NODES', compact)
+    monkeypatch.setattr(layout_mod, 'EDGE_MULTIPLICITY', mult)
+    w = big['w']
+    ds = GraphDataset.from_arrays(*BIG_UQI, w.vocab_size, w.bag_words, w.bag_offsets, big['triples'], device=dev())
+    lay = ds.hypergraph.layout
+    assert lay.compact == (compact == '1') and (lay.edge_weight is not None) == (mult == '1')
+    return ds
+
+
+def _stress_batch(n, seed):
+    """``n`` samples that stress the row scatter: a user and a query repeated hundreds of times each (far more than the 16 members one trip of the kernel loads),
+    two hot items, isolated nodes in every third (two thirds of every type are isolated), the nodes of compact ids 0 and N' - 1 (the first live user, the last live
+    item) and, at every chunk boundary (row 32,768 k), the same hot node on both sides.  -> ((u, q, i, y) on the device, [the global node row of every destination that straddles a boundary])."""
+    big = _big_tail_graph()
+    U, Q, I = BIG_UQI
+    live_u, live_q, live_i = big['live']
+    rng = np.random.default_rng(seed)
+    ids = [rng.integers(0, U, n), rng.integers(0, Q, n), rng.integers(0, I, n)]
+    hot = (live_u[3], live_q[2], live_i[5])
+    ids[0][::29] = hot[0]
+    ids[1][::17] = hot[1]
+    ids[2][::41] = hot[2]
+    ids[2][7::53] = live_i[9]
+    ids[0][1], ids[2][1] = live_u[0], live_i[-1]
+    spanning = []
+    for b in range(SCATTER_LIMIT, 3 * n, SCATTER_LIMIT):
+        third, k = divmod(b, n)
+        assert k >= 1                                    # (rows b - 1 and b in the same third: node types never share a destination)
+        ids[third][k - 1] = ids[third][k] = hot[third]
+        spanning.append((0, U, U + Q)[third] + int(hot[third]))
+    y = (rng.random(n) < 0.1).astype(np.float32)
+    return tuple(torch.from_numpy(x).to(dev()) for x in ids) + (torch.from_numpy(y).to(dev()),), spanning
+
+
+def _float64_step(oracle, batch):
+    """Loss and every parameter's gradient of the float64 oracle on ``batch``, and the gradient of its feature matrix ``[N, D]`` (the batch tail's cotangent)."""
+    u, q, i, y = (t.cpu() for t in batch)
+    held = {}
+    propagate = type(oracle).propagate
+
+    def keep(self=oracle):
+        f = propagate(self)
+        f.retain_grad()
+        held['F'] = f
+        return f
+    oracle.propagate = keep
+    try:
+        oracle.zero_grad(set_to_none=True)
+        loss = torch.nn.BCEWithLogitsLoss()(oracle(u, q, i), y.double())
+        loss.backward()
+    finally:
+        del oracle.propagate
+    return loss.item(), oracle.reference_grads(), held['F'].grad
+
+
+def _check_tail_gradients(tag, got_loss, got, want_loss, want, compact_rows=None):
+    """The bars of every case: loss 1e-5, every gradient RTOL, tables and items_bias per row ROW_RTOL, the oracle's exact-zero rows exactly zero, and (compact
+    layouts) the named rows at their own magnitude.  Prints the measured errors."""
+    assert set(got) == set(want)
+    err = {'loss': rel(got_loss, want_loss)}
+    assert err['loss'] <= 1e-5, (tag, err)
+    worst = (0.0, None)
+    for k in want:
+        e = rel(got[k], want[k])
+        worst = max(worst, (e, k))
+        assert e <= RTOL, (tag, k, e)
+    err['grad'] = worst
+    worst_row = (0.0, None)
+    for k in BIG_TABLES:
+        e = row_rel(got[k], want[k])
+        worst_row = max(worst_row, (e, k))
+        assert e <= ROW_RTOL, (tag, k, e)
+        g, wv = got[k].detach().cpu().double(), want[k]
+        zero = (wv.reshape(wv.shape[0], -1) == 0).all(1)
+        assert not bool(zero.any()) or float(g[zero].abs().max()) == 0.0, (tag, k, 'a row the float64 gradient leaves at zero')
+    err['row'] = worst_row
+    if compact_rows:
+        err['own'] = 0.0
+        for k, r in compact_rows:
+            assert float(want[k][r].abs().max()) > 0, (tag, k, r)
+            e = row_rel(got[k][r:r + 1], want[k][r:r + 1], floor=0)
+            err['own'] = max(err['own'], e)
+            assert e <= ROW_RTOL, (tag, k, r, e)
+    print(f'tail beyond one scatter launch {tag}: loss {err["loss"]:.2e}, grad {err["grad"][0]:.2e} ({err["grad"][1]}), row {err["row"][0]:.2e} ({err["row"][1]})'
+          + (f', compact rows 0 / last {err["own"]:.2e}' if compact_rows else '') + f'   (bars 1e-5 / {RTOL:.0e} / {ROW_RTOL:.0e})')
+
+
+def _tail_beyond_one_launch(kind, layers, order, dim, samples, layout, restrict, monkeypatch):
+    from ihgnn_amd import _lib, ops, profiler
+    from ihgnn_amd.optim import Adam
+    from oracle import ihgnn_ref as ref
+    assert ops.SCATTER_CHUNK_ROWS == SCATTER_LIMIT == int(_lib.load().ihg_batch_scatter_max_rows())
+    big = _big_tail_graph()
+    U, Q, I = BIG_UQI
+    ds = _big_tail_dataset(layout, monkeypatch)
+    lay = ds.hypergraph.layout
+    torch.manual_seed(dim + layers)
+    m = build_model(ds, kind, layers, order, dim)
+    m.batch_rows_only_last_layer = restrict
+    w = big['w']
+    oracle = ref.OracleRawGnn(big['g'], torch.from_numpy(w.bag_words + 1), torch.from_numpy(w.bag_offsets), w.vocab_size, dim, kind, layers, order, dtype=torch.float64)
+    oracle.load_reference_state({k: v.detach().cpu().numpy() for k, v in m.state_dict().items()})
+    rows = 3 * samples
+    above = rows > SCATTER_LIMIT
+    compact_rows = None
+    if lay.compact:
+        first, last = int(lay.active_nodes[0]), int(lay.active_nodes[-1])
+        assert first == int(big['live'][0][0]) and last == U + Q + int(big['live'][2][-1])
+        compact_rows = [('embeddings.embedding_user.weight', first + 1), ('embeddings.embedding_item.weight', last - U - Q + 1), ('prediction_layer.items_bias', last - U - Q)]
+    opt = Adam(m.parameters(), 1e-3, weight_decay=0)
+    for step in range(2):
+        batch, spanning = _stress_batch(samples, 100 * step + dim + samples)
+        if lay.compact:
+            public = torch.cat([batch[0], batch[1] + U, batch[2] + U + Q])
+            isolated = (lay.node_map[public] < 0).view(3, samples).any(1)
+            assert bool(isolated.all()), 'isolated nodes in every third of the batch'
+        want_loss, want, want_f = _float64_step(oracle, batch)
+        assert len(spanning) == (rows - 1) // SCATTER_LIMIT
+        for node in spanning:
+            assert float(want_f[node].abs().max()) > 0, 'a destination on both sides of a chunk boundary with a non-zero float64 gradient'
+        m.zero_grad(set_to_none=True)
+        profiler.start(only={'batch_combine', 'batch_scatter_add'})
+        loss = m.bce_loss(*batch)
+        loss.backward()
+        profiler.stop()
+        launches = {k: v['launches'] for k, v in profiler.summary().items()}
+        got = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
+        tag = f'{kind} L{layers} o{order} d{dim} {layout} rows {rows} restrict {restrict} step {step + 1}'
+        _check_tail_gradients(tag, loss.item(), got, want_loss, want, compact_rows)
+        if above:
+            chunks = -(-rows // SCATTER_LIMIT)
+            assert 'batch_combine' not in launches and launches.get('batch_scatter_add', 0) >= chunks * (len(m.gnns) + 2), launches
+            m.zero_grad(set_to_none=True)
+            m.bce_loss(*batch).backward()                # the same step again from the same state: bitwise the same gradients (no float atomics)
+            for k, p in m.named_parameters():
+                assert torch.equal(p.grad, got[k]), (tag, k, 'not bitwise repeatable')
+        else:
+            assert launches.get('batch_combine', 0) >= 1 and 'batch_scatter_add' not in launches, launches
+        if step == 0:
+            opt.step()
+            oracle.load_reference_state({k: v.detach().cpu().double().numpy() for k, v in m.state_dict().items()})
+
+
+@pytest.mark.parametrize('restrict', [True, False])
+@pytest.mark.parametrize('layout', ['plain', 'mult', 'compact', 'compact_mult'])
+@pytest.mark.parametrize('samples', [10922, 10923, 22000])
+@pytest.mark.parametrize('dim', [128, 32])
+def test_batch_tail_beyond_one_scatter_launch(dim, samples, layout, restrict, monkeypatch):
+    """IHGNN 2 layers / order 3: one training step's loss and EVERY parameter gradient against the float64 oracle, then one Adam step and the next step's gradients
+    the same way, at 32,766 batch rows (the combine path: the control), 32,769 (one row over the limit: two scatter chunks) and 66,000 (three) - every layout,
+    the restricted and the full last layer.  Above the limit no combine runs and every tap goes through the chunked scatter (a destination that straddles a chunk
+    boundary, the items_bias column, the -1 rows of isolated nodes above layer 0), bitwise repeatable."""
+    _tail_beyond_one_launch('ihgnn', 2, 3, dim, samples, layout, restrict, monkeypatch)
+
+
+@pytest.mark.parametrize('layout', ['plain', 'compact_mult'])
+@pytest.mark.parametrize('kind,layers,order,dim', [('ihgnn', 1, 3, 64), ('ihgnn', 2, 3, 256), ('ihgnn', 2, 3, 96), ('hgcn', 2, 1, 64)])
+def test_batch_tail_beyond_one_scatter_launch_other_models(kind, layers, order, dim, layout, monkeypatch):
+    """The same at 32,769 rows for one layer, the widest tiled width through the two-hop form (``FIRST_ORDER_TWO_HOP_BYTES = 0``), a padded width (96 -> 128) and HGCN."""
+    from ihgnn_amd import ops
+    if dim == 256:
+        monkeypatch.setattr(ops, 'FIRST_ORDER_TWO_HOP_BYTES', 0)
+    _tail_beyond_one_launch(kind, layers, order, dim, 10923, layout, True, monkeypatch)
+
+
+def test_driver_with_batches_beyond_one_scatter_launch(tmp_path, monkeypatch):
+    """``python -m ihgnn_amd.Main`` for one epoch over the files of ``test_driver_over_a_graph_whose_layout_collapses`` (a compact layout with multiplicities) with
+    batches of 1,000 positives = 33,000 batch rows: the eager training step takes the chunked scatter on every tap and the run ends with finite metrics."""
+    from ihgnn_amd import layout as layout_mod, synth
+    from ihgnn_amd import Main as driver
+    from ihgnn_amd.Helpers.GlobalSettings import Gs
+    monkeypatch.setattr(layout_mod, 'COMPACT_NODES', 'auto')
+    monkeypatch.setattr(layout_mod, 'EDGE_MULTIPLICITY', 'auto')
+    assert 3 * 1000 * (1 + Gs.random_negative_sample_size + Gs.non_random_negative_sample_size) > SCATTER_LIMIT
+    w = synth.draw(40000, 2000, 30000, 50, 33000, seed=4, eval_logs=40)
+    w.triples = np.concatenate([w.triples, w.triples])
+    synth.write_files(w, str(tmp_path / 'Data' / 'Synth' / 'Sparse'))
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(Gs, 'batch_size', 1000)
+    hist = driver.main(['--ds', 'Synth/Sparse/', '--gnn', 'IHGNN', '--gnns', '2', '--fo', '3', '--emb', '32', '--ec', '1', '--est', '1', '--etf', '1', '--seed', '5',
+                        '--record_step', 'off'])
+    (_, metrics), = list(hist.iter_epoch_test())
+    for v in (metrics.NDCG_at10, metrics.HitRatio_at10):
+        assert np.isfinite(v) and 0.0 <= v <= 1.0
+
+
+# ---------------------------------------------------------------------------------------------
 # multi-rank path on one GPU (SURVEY §8 e1): the HIP model, N ranks == 1 rank on the union batch; bench.py launches itself
 # ---------------------------------------------------------------------------------------------
 def _run(cmd, timeout=600):
@@ -2931,6 +3167,15 @@ def test_eight_ranks_exchange_cotangents_of_a_union_beyond_one_combine_instance(
     combine kernel, what eight ranks of 1,100 rows (26,400) run on an 8-GPU node - and the replicas must stay bitwise identical and equal the one-rank run on all 5,600 rows."""
     r = _run(['tools/two_rank_check.py', '--ranks', '8', '--sync', 'cotangent', '--device', '0', '--backend', 'gloo', '--batch', '700'])
     assert r.returncode == 0 and 'OK' in r.stdout and 'DIVERGED' not in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize('batch,collapsed', [(5500, False), (5500, True), (11000, True)])
+def test_two_ranks_with_a_union_beyond_one_scatter_launch(batch, collapsed):
+    """Two ranks under the cotangent exchange whose union has more rows than one scatter launch takes (2 x 3 x 5,500 = 33,000; at 11,000 per rank every rank alone is
+    over it, skips its own combine and marks every row a leader): the union - the -1 rows of a rank's own non-leader duplicates, the items_bias column - goes through
+    the chunked scatter, over the every-node-a-row and the compact layout with multiplicities, and equals the one-rank run on the whole batch."""
+    r = _run(['tools/two_rank_check.py', '--ranks', '2', '--sync', 'cotangent', '--device', '0', '--backend', 'gloo', '--batch', str(batch)] + (['--collapsed'] if collapsed else []))
+    assert r.returncode == 0 and '-> OK' in r.stdout and 'DIVERGED' not in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 @pytest.mark.parametrize('sync', ['flat', 'bucketed', 'sharded', 'cotangent'])
