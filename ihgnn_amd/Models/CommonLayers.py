@@ -5,8 +5,10 @@ order 1 / 2 / 3; column blocks u, q, i, uq, qi, iu, uqi) but never builds the ``
 
 * the three first-order blocks are applied per NODE, before the gather (users only ever meet block u, queries
   block q, items block i): ``P = [H_users W_u^T + c ; H_queries W_q^T ; H_items W_i^T]`` - ``N*d*d`` flops
-  instead of ``E*3*d*d`` - and the hyperedge value is the gather-sum ``P[u] + P[q] + P[i]`` (HIP kernel K5);
-* the product blocks (orders 2, 3) are contracted inside the fused HIP kernel ``ihg_interact_fwd``.
+  instead of ``E*3*d*d`` - and the hyperedge value gathers ``P[u] + P[q] + P[i]``: HIP kernel K5 at order 1
+  (``ops.edge_gather_sum``), the fused HIP kernel ``ihg_interact_fwd`` at orders 2 and 3, which also contracts the
+  product blocks (``ops.interact``);
+* ``to_nodes``, what ``IHGNNLayer`` runs, takes orders 2 and 3 on to the nodes as ONE autograd node (``ops.interact_layer``).
 """
 from typing import Optional
 
@@ -54,10 +56,7 @@ class FeatureInteractor(nn.Module):
         repeated (user, query, item) triples once (``layout.edge_weight``; ``layout.file_to_edge`` maps an interaction to its row) - the reference's ``[E, d]`` in file order
         is ``out[layout.file_to_edge]``.  ``node_features`` has one row per node of the layout (``layout.node_count``: without the isolated nodes where it is compact)."""
         layout = self.dataset.hypergraph.layout
-        w, b = self._operands(node_features)
-        if self.max_order > 1 and ops.interact_from_nodes_supported(node_features, w):
-            return ops.interact_from_nodes(node_features, w, b, layout, self.max_order)
         hoisted = self.first_order(node_features)
         if self.max_order == 1:
             return ops.edge_gather_sum(hoisted, layout)
-        return ops.interact(node_features, hoisted, w, layout, self.max_order)
+        return ops.interact(node_features, hoisted, self._operands(node_features)[0], layout, self.max_order)

@@ -1892,6 +1892,25 @@ constexpr int kPipeGrid = 256;          // wave-specialised and strip kernels: o
 // tile ranges of the user-reduced member-gradient kernels (two boundary-table entries each): one per workgroup at d = 64 / 128, one per wave at d = 32 (narrow.hip)
 inline int64_t boundary_ranges(int dim) { return dim == 128 || dim == 64 || dim == 256 ? kPipeGrid : (dim == kNarrowDim ? kNarrowMemberRanges : 0); }
 
+// The backward's workspace in the order ihg_interact_bwd_workspace_bytes sizes it: packed weights, weight slabs, the boundary runs of the user-reduced form
+// (values, then their users), the planes of the split / narrow member kernels.
+struct BwdWorkspace {
+    float* wq;
+    float* slabs;
+    float* bnd_val;
+    int32_t* bnd_user;
+    void* planes;
+};
+inline BwdWorkspace carve_bwd_workspace(void* workspace, int dim, int order) {
+    BwdWorkspace ws;
+    ws.wq = static_cast<float*>(workspace);
+    ws.slabs = ws.wq + packed_weight_floats(dim, order);
+    ws.bnd_val = ws.slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order);
+    ws.bnd_user = reinterpret_cast<int32_t*>(ws.bnd_val + 2LL * boundary_ranges(dim) * dim);
+    ws.planes = ws.bnd_user + 2LL * boundary_ranges(dim);
+    return ws;
+}
+
 // Persistent grid of a plain (one role) tiling: as many workgroups as are resident at once - a larger grid runs in rounds, and
 // the workgroups of the last round start when the others have already walked their whole share of the tiles.
 template <typename Kernel>
@@ -2180,16 +2199,12 @@ int ihg_interact_bwd_user_reduced(const float* h, int64_t ld_h, const int32_t* i
     if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd_user_reduced: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nblk = order == 3 ? 4 : 3;
-    float* wq = static_cast<float*>(workspace);
-    float* slabs = wq + packed_weight_floats(dim, order);
-    float* bnd_val = slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order);
-    int32_t* bnd_user = reinterpret_cast<int32_t*>(bnd_val + 2LL * boundary_ranges(dim) * dim);
-    void* planes = bnd_user + 2LL * boundary_ranges(dim);
+    const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
     const int pack_items = (dim / 16) * nblk * (dim / 16) * kWave;
     hipLaunchKernelGGL(pack_weights_strip_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
-                       static_cast<float*>(nullptr), wq);
-    if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, wq, dout, ld_dout, g2, slabs, dw, ld_dw, n_edges, s, dh, ld_dh, bnd_val, bnd_user, w, ld_w, planes);
-    else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, wq, dout, ld_dout, g2, slabs, dw, ld_dw, n_edges, s, dh, ld_dh, bnd_val, bnd_user, w, ld_w, planes);
+                       static_cast<float*>(nullptr), ws.wq);
+    if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes);
+    else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes);
     return check_launch("ihg_interact_bwd_user_reduced");
 }
 
@@ -2210,15 +2225,11 @@ int ihg_interact_bwd_user_reduced_planes(const float* h, int64_t ld_h, const int
         return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced_planes: rows must be 16-byte aligned");
     if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd_user_reduced_planes: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    float* wq = static_cast<float*>(workspace);
-    float* slabs = wq + packed_weight_floats(dim, order);
-    float* bnd_val = slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order);
-    int32_t* bnd_user = reinterpret_cast<int32_t*>(bnd_val + 2LL * boundary_ranges(dim) * dim);
-    void* planes = bnd_user + 2LL * boundary_ranges(dim);
+    const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
     int entries = 0;
-    launch_members_split(dim, order, h, ld_h, i3, w, ld_w, planes, static_cast<const float*>(planes_rows), dim, g2, n_edges, dh, ld_dh, bnd_val, bnd_user, &entries, s, nullptr,
-                         nullptr, 0, inv_scale);
-    hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, s, bnd_val, bnd_user, entries, dim, dh, ld_dh);
+    launch_members_split(dim, order, h, ld_h, i3, w, ld_w, ws.planes, static_cast<const float*>(planes_rows), dim, g2, n_edges, dh, ld_dh, ws.bnd_val, ws.bnd_user, &entries, s,
+                         nullptr, nullptr, 0, inv_scale);
+    hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, s, ws.bnd_val, ws.bnd_user, entries, dim, dh, ld_dh);
     return check_launch("ihg_interact_bwd_user_reduced_planes");
 }
 
@@ -2245,16 +2256,14 @@ int ihg_interact_bwd_gathered(const float* h, int64_t ld_h, const int32_t* i3, c
     if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd_gathered: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nblk = order == 3 ? 4 : 3;
-    float* wq = static_cast<float*>(workspace);                          // (the fp32 fragment image of w is not needed by the split kernels)
-    float* slabs = wq + packed_weight_floats(dim, order);
-    float* bnd_val = slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order);
-    int32_t* bnd_user = reinterpret_cast<int32_t*>(bnd_val + 2LL * boundary_ranges(dim) * dim);
-    void* planes = bnd_user + 2LL * boundary_ranges(dim);
+    const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);  // (the fp32 fragment image of w, ws.wq, is not needed by the split kernels)
     if (dim == kNarrowDim ? (!narrow_members_ok(dim, order, g2, ld_h, ld_dy, dy) || (dw != nullptr && ld_dout <= 0))
                           : (!split_members_ok(dim, order, g2, ld_h, ld_dy, dy, true) || (dw != nullptr && !split_weight_ok(dim, order, ld_h, ld_dout, dout))))
         return fail(IHG_ERR_INVALID, "ihg_interact_bwd_gathered: the kernels do not take these strides / alignments");
-    if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, wq, dy, ld_dy, g2, slabs, dw, ld_dw, n_edges, s, dh, ld_dh, bnd_val, bnd_user, w, ld_w, planes, dy_scale, dout, ld_dout);
-    else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, wq, dy, ld_dy, g2, slabs, dw, ld_dw, n_edges, s, dh, ld_dh, bnd_val, bnd_user, w, ld_w, planes, dy_scale, dout, ld_dout);
+    if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, ws.wq, dy, ld_dy, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes, dy_scale,
+                                               dout, ld_dout);
+    else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, ws.wq, dy, ld_dy, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes, dy_scale,
+                                     dout, ld_dout);
     return check_launch("ihg_interact_bwd_gathered");
 }
 
@@ -2273,20 +2282,18 @@ int ihg_interact_bwd(const float* h, int64_t ld_h, const int32_t* i3, const floa
     if (tiled) {
         if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd: workspace too small");
         const int nblk = order == 3 ? 4 : 3;
-        float* wq = static_cast<float*>(workspace);
-        float* slabs = wq + packed_weight_floats(dim, order);
+        const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
         const int pack_items = (dim / 32) * nblk * (dim / 8) * kWave;
         if (strip_bwd_ok(dim, g, ld_h))
             hipLaunchKernelGGL(pack_weights_strip_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
-                               static_cast<float*>(nullptr), wq);
+                               static_cast<float*>(nullptr), ws.wq);
         else
             hipLaunchKernelGGL(pack_weights_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
-                               static_cast<float*>(nullptr), wq);
+                               static_cast<float*>(nullptr), ws.wq);
         // the bf16 planes of the split contraction sit behind the boundary table (only d = 128 has either)
-        void* planes = split_plane_floats(dim, order) == 0 ? nullptr :
-                       static_cast<void*>(slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order) + 2LL * boundary_ranges(dim) * dim + 2LL * boundary_ranges(dim));
-        if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, wq, dout, ld_dout, g, slabs, dw, ld_dw, n_edges, s, nullptr, 0, nullptr, nullptr, w, ld_w, planes);
-        else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, wq, dout, ld_dout, g, slabs, dw, ld_dw, n_edges, s, nullptr, 0, nullptr, nullptr, w, ld_w, planes);
+        void* planes = split_plane_floats(dim, order) == 0 ? nullptr : ws.planes;
+        if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g, ws.slabs, dw, ld_dw, n_edges, s, nullptr, 0, nullptr, nullptr, w, ld_w, planes);
+        else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g, ws.slabs, dw, ld_dw, n_edges, s, nullptr, 0, nullptr, nullptr, w, ld_w, planes);
         return check_launch("ihg_interact_bwd");
     }
     if (n_edges > 0) {

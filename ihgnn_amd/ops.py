@@ -156,13 +156,18 @@ class _EdgeGatherSum(torch.autograd.Function):
         return node_segment_sum_raw(grad_out, ctx.layout.node_csr, None, scale, mode, role='k7.edges_to_nodes_bwd_of_k5'), None, None, None
 
 
+def _edges_to_nodes(src: Tensor, layout: IncidenceLayout, out_scale: Optional[Tensor], rows: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """K7's hyperedge -> node pass ``out_scale * H src`` over ``layout.node_csr``."""
+    mode = _lib.SCALE_NONE if out_scale is None else _lib.SCALE_MULTIPLY
+    # layout.edge_weight (duplicate triples collapsed): a row stands for m_e hyperedges of the reference's incidence and enters the sum m_e times
+    return node_segment_sum_raw(src, layout.node_csr, layout.edge_weight, out_scale, mode, rows=rows, role='k7.edges_to_nodes', out=out)
+
+
 class _NodeSegmentSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src: Tensor, layout: IncidenceLayout, out_scale: Optional[Tensor], rows: Optional[Tensor], out: Optional[Tensor]) -> Tensor:
         ctx.layout, ctx.out_scale = layout, out_scale
-        mode = _lib.SCALE_NONE if out_scale is None else _lib.SCALE_MULTIPLY
-        # layout.edge_weight (duplicate triples collapsed): a row stands for m_e hyperedges of the reference's incidence and enters the sum m_e times
-        return node_segment_sum_raw(src, layout.node_csr, layout.edge_weight, out_scale, mode, rows=rows, role='k7.edges_to_nodes', out=_check_out(out, src))
+        return _edges_to_nodes(src, layout, out_scale, rows, _check_out(out, src))
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
@@ -435,13 +440,6 @@ def node_linear_supported(x: Tensor, w: Tensor) -> bool:
     d = int(x.shape[1])
     return (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.stride(-1) == 1 and w.stride(-1) == 1
             and int(w.shape[0]) == d and int(w.shape[1]) >= d)
-
-
-def node_linear_tiled(x: Tensor, w: Tensor) -> bool:
-    """The MFMA row-GEMM form applies (what the fused one-node interactive path builds on)."""
-    d = int(x.shape[1])
-    return (node_linear_supported(x, w) and d in (32, 64, 128, 256) and x.stride(0) % 4 == 0 and w.stride(0) % 4 == 0
-            and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
 
 
 def _type_begin(layout: IncidenceLayout):
@@ -789,6 +787,9 @@ NODE_LEVEL_WEIGHT = _os.environ.get('IHG_NODE_LEVEL_WEIGHT', '1') != '0'
 # the first-order gradient d P = H H^T (scale * dy): a scatter of the stored [E, d] cotangents - or, for tables beyond this many bytes, the two-hop operator on dy
 # (at C3 the scatter wins, 8.74 against 8.81 ms per step; at C5 the 51 GB table's scatter reads HBM at random and the two-hop form wins, 22 against 32 ms)
 FIRST_ORDER_TWO_HOP_BYTES = int(_os.environ.get('IHG_FIRST_ORDER_TWO_HOP_BYTES', 8 << 30))     # where the member-gradient kernel does not form the hyperedges' cotangents itself: [E, d] tables larger than this take the two-hop form
+# the hyperedges' cotangents of the interactive layer's backward written by K5 as the member-gradient kernel's operand (two fp16 planes per row + the row's inverse scale)
+# where nothing else reads them (d = 256 beyond FIRST_ORDER_TWO_HOP_BYTES: config C5); IHG_COTANGENT_PLANES=0: fp32 rows, scaled and split by every column part of the kernel
+COTANGENT_PLANES = _os.environ.get('IHG_COTANGENT_PLANES', '1') != '0'
 
 
 def _node_level_forward_ok(h: Tensor, w: Tensor, bias: Optional[Tensor], out: Optional[Tensor], dim: int, order: int) -> bool:
@@ -802,8 +803,6 @@ def _node_level_forward_ok(h: Tensor, w: Tensor, bias: Optional[Tensor], out: Op
 NODE_TABLES = _os.environ.get('IHG_NODE_TABLES', '1') != '0'
 
 
-
-
 def _user_reduced_ok(h: Tensor, w: Tensor, grad_out: Tensor, layout: IncidenceLayout, order: int) -> bool:
     """The interactive backward can run ``ihg_interact_bwd_user_reduced`` on these operands."""
     lib = _lib.load()
@@ -812,175 +811,209 @@ def _user_reduced_ok(h: Tensor, w: Tensor, grad_out: Tensor, layout: IncidenceLa
                 and _ld(w) % 4 == 0 and _ld(grad_out) % 4 == 0 and grad_out.data_ptr() % 16 == 0)
 
 
-def _zero_isolated_users(dh: Tensor, layout: IncidenceLayout) -> None:
-    """Users without hyperedges are not written by the user-reduced kernels: their rows of ``dh`` are zeroed here (an index fill of those
-    rows; a fill of the whole user block is 118 MB at C3)."""
-    idx = layout.users_without_hyperedges()
-    if idx.numel():
-        _lib.check(_lib.load().ihg_zero_rows(_ptr(dh), _ld(dh), int(dh.shape[1]), _ptr(idx), int(idx.numel()), _stream()), 'ihg_zero_rows')
+def _first_order_rows(h: Tensor, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout) -> Tensor:
+    """``[N, d]`` first-order blocks per node: the typed row GEMM with ``w``'s blocks u / q / i, the bias on the users (``ihg_node_linear_fwd``, bias mask ``0b001``)."""
+    lib = _lib.load()
+    dim = int(h.shape[1])
+    p = torch.empty(h.shape[0], dim, dtype=torch.float32, device=h.device)
+    ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
+    with profiler.kernel('node_linear_fwd', h.shape[0], dim):
+        _lib.check(lib.ihg_node_linear_fwd(_ptr(h), _ld(h), _ptr(w), int(w.stride(0)), dim, _ptr(bias), 0b001, 0, _type_begin(layout),
+                                           _ptr(p), _ld(p), _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd')
+    return p
 
 
-# the hyperedges' cotangents of the interactive layer's backward written by K5 as the member-gradient kernel's operand (two fp16 planes per row + the row's inverse scale)
-# where nothing else reads them (d = 256 beyond FIRST_ORDER_TWO_HOP_BYTES: config C5); IHG_COTANGENT_PLANES=0: fp32 rows, scaled and split by every column part of the kernel
-COTANGENT_PLANES = _os.environ.get('IHG_COTANGENT_PLANES', '1') != '0'
+def _interact_rows(h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, order: int) -> Tensor:
+    """``[E, d]`` hyperedge rows (``ihg_interact_fwd``): the first-order part gathered from ``p``, the products of ``h``'s member rows contracted with ``w``."""
+    lib = _lib.load()
+    dim = int(h.shape[1])
+    out = torch.empty(layout.edge_count, dim, dtype=torch.float32, device=h.device)
+    ws = _workspace(int(lib.ihg_interact_fwd_workspace_bytes(layout.edge_count, dim, order)), h.device)
+    with profiler.kernel('interact_fwd', layout.edge_count, dim):
+        _lib.check(lib.ihg_interact_fwd(_ptr(h), _ld(h), _ptr(p), _ld(p), _ptr(layout.i3), _ptr(w), _ld(w), order,
+                                        _ptr(out), _ld(out), _ptr(ws), ws.numel() * 4, layout.edge_count, dim, _stream()), 'ihg_interact_fwd')
+    return out
+
+
+def _first_order_backward(dp: Tensor, h: Tensor, w: Tensor, layout: IncidenceLayout, dw: Tensor, dh: Tensor, has_bias: bool) -> Optional[Tensor]:
+    """The first-order blocks' gradients from ``dp`` (``ihg_node_linear_bwd_weight``): weights into ``dw``'s blocks u / q / i, the input gradient ADDED onto ``dh`` - by
+    the kernel (``dx_accumulate``: no separate ``[N, d]`` add) where it can.  Returns the bias gradient (``None`` without a bias)."""
+    lib = _lib.load()
+    dim = int(h.shape[1])
+    dbias = torch.empty(dim, dtype=torch.float32, device=h.device) if has_bias else None
+    ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
+    accumulate = bool(lib.ihg_node_linear_bwd_accumulates(dim, _ld(dp), _ld(h), _ld(dh))) and h.data_ptr() % 16 == 0 and dh.data_ptr() % 16 == 0 and dp.data_ptr() % 16 == 0
+    dx = dh if accumulate else torch.empty_like(dh)
+    with profiler.kernel('node_linear_bwd', h.shape[0], dim):
+        _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(dp), _ld(dp), _ptr(h), _ld(h), _type_begin(layout), _ptr(dw), int(dw.stride(0)), dim,
+                                                  _ptr(dbias), 0b001, 0, _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx), 1 if accumulate else 0,
+                                                  _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
+    if not accumulate:
+        dh.add_(dx)
+    return dbias
+
+
+def _member_gradients(h: Tensor, layout: IncidenceLayout, order: int, dw: Optional[Tensor], user_reduced: bool, launch) -> Tensor:
+    """The member gradients of the interactive backward scattered to nodes (returned), the product blocks' weight gradients into ``dw`` (its columns from ``3 d`` on;
+    ``None``: not wanted).  ``launch(e0, e1, g, dh, dw_part, ws)`` runs the member-gradient kernel on hyperedges ``e0:e1`` into ``dw_part`` and the member buffer ``g``:
+    ``[n, 3 d]``, or ``[n, 2 d]`` with ``user_reduced`` (hyperedges numbered by user: the kernel sums the user slot on chip and writes ``dh[users]`` itself).  Beyond
+    ``MEMBER_BUFFER_LIMIT_BYTES`` hyperedge chunks, each with its own member lists (user-reduced: cut where the user changes), the K7 passes after the first
+    adding onto ``dh`` inside the kernel: same sums, associated chunk by chunk."""
+    lib = _lib.load()
+    n_edges, dim = layout.edge_count, int(h.shape[1])
+    slots = 2 if user_reduced else 3
+    n_chunks = max(1, -(-(n_edges * slots * dim * 4) // MEMBER_BUFFER_LIMIT_BYTES))
+    if user_reduced:
+        parts = [(0, n_edges) + layout.member_csr_qi()] if n_chunks == 1 else layout.member_csr_qi_chunks(n_chunks)
+        dh = torch.empty(layout.node_count, dim, dtype=torch.float32, device=h.device)
+        idx = layout.users_without_hyperedges()          # not written by the user-reduced kernels: an index fill of their rows (a fill of the user block is 118 MB at C3)
+        if idx.numel():
+            _lib.check(lib.ihg_zero_rows(_ptr(dh), _ld(dh), dim, _ptr(idx), int(idx.numel()), _stream()), 'ihg_zero_rows')
+    else:                                                # (node v, hyperedge e) reads row 3 (e - e0) + type(v)
+        parts = [(0, n_edges, layout.member_csr)] if n_chunks == 1 else layout.member_csr_chunks(n_chunks)
+        parts = [part + (None,) for part in parts]
+        dh = None
+    for index, (e0, e1, csr, csr_rows) in enumerate(parts):
+        g = torch.empty(e1 - e0, slots * dim, dtype=torch.float32, device=h.device)
+        dw_part = dw if index == 0 or dw is None else torch.empty_like(dw)
+        ws = _workspace(int(lib.ihg_interact_bwd_workspace_bytes(e1 - e0, dim, order)), h.device)
+        with profiler.kernel('interact_bwd', e1 - e0, dim):
+            launch(e0, e1, g, dh, dw_part, ws)
+        if index > 0 and dw is not None:
+            dw[:, 3 * dim:].add_(dw_part[:, 3 * dim:])
+        dh = node_segment_sum_raw(g.view(slots * (e1 - e0), dim), csr, out=dh, rows=csr_rows, role='k7.member_gradients', accumulate=index > 0, read_once=True)
+        del g
+    return dh
 
 
 def _interact_backward(h: Tensor, w: Tensor, grad_out: Tensor, layout: IncidenceLayout, order: int, dw: Optional[Tensor], inv_scale: Optional[Tensor] = None) -> Tensor:
-    """Product-block weight gradient into ``dw`` (its columns from ``3 d`` on; ``None``: not wanted - the caller has it from the node-level
-    kernel) and the member gradients scattered to nodes (returned).  One pass when the ``[E, 3, d]`` buffer fits ``MEMBER_BUFFER_LIMIT_BYTES``, otherwise hyperedge chunks, each with
-    its own member lists (``IncidenceLayout.member_csr_chunks``): same sums, associated chunk by chunk.  ``inv_scale`` (``[E]``): ``grad_out`` holds fp16 planes
-    (``ihg_edge_gather_sum_planes``), not fp32 rows; the caller has checked ``_cotangent_planes_ok``."""
+    """``_member_gradients`` from the hyperedges' cotangents ``grad_out`` (``[E, d]``; with ``inv_scale`` (``[E]``): fp16 planes written by
+    ``ihg_edge_gather_sum_planes``, read by the user-reduced kernel only)."""
+    lib = _lib.load()
+    dim = int(h.shape[1])
+    reduced = _user_reduced_ok(h, w, grad_out, layout, order)
+    if inv_scale is not None and (dw is not None or not reduced):
+        raise RuntimeError('cotangent planes are read by the user-reduced member-gradient kernel only')
+    def launch(e0, e1, g, dh, dw_part, ws):
+        n, go, i3, ld_dw = e1 - e0, grad_out[e0:e1], layout.i3[e0:e1], _ld(dw_part) if dw_part is not None else 0
+        if inv_scale is not None:
+            _lib.check(lib.ihg_interact_bwd_user_reduced_planes(_ptr(h), _ld(h), _ptr(i3), _ptr(w), _ld(w), order, _ptr(go), _ptr(inv_scale[e0:e1]),
+                                                                _ptr(g), _ptr(dh), dim, _ptr(ws), ws.numel() * 4, n, dim, _stream()), 'ihg_interact_bwd_user_reduced_planes')
+        elif reduced:
+            _lib.check(lib.ihg_interact_bwd_user_reduced(_ptr(h), _ld(h), _ptr(i3), _ptr(w), _ld(w), order, _ptr(go), _ld(grad_out), _ptr(g),
+                                                         _ptr(dh), dim, _ptr(dw_part), ld_dw, _ptr(ws), ws.numel() * 4, n, dim, _stream()), 'ihg_interact_bwd_user_reduced')
+        else:
+            _lib.check(lib.ihg_interact_bwd(_ptr(h), _ld(h), _ptr(i3), _ptr(w), _ld(w), order, _ptr(go), _ld(grad_out),
+                                            _ptr(g), _ptr(dw_part), ld_dw, _ptr(ws), ws.numel() * 4, n, dim, _stream()), 'ihg_interact_bwd')
+    return _member_gradients(h, layout, order, dw, reduced, launch)
+
+
+def _gathered_backward_ok(h: Tensor, w: Tensor, dy: Tensor, layout: IncidenceLayout, order: int) -> bool:
+    # (the gathering kernel forms sum_m scale[m] dy[m] itself and has no per-hyperedge factor: a layout with multiplicities takes the K5 + member-kernel sequence)
+    dim = int(h.shape[1])
+    return (layout.edge_weight is None and layout.edge_count * 3 * dim * 4 <= MEMBER_BUFFER_LIMIT_BYTES and _user_reduced_ok(h, w, dy, layout, order)
+            and bool(_lib.load().ihg_interact_bwd_gathered_supported(dim, order, _ld(h), _ld(dy))))
+
+
+def _interact_to_nodes_backward(h: Tensor, w: Tensor, dy: Tensor, layout: IncidenceLayout, order: int, out_scale: Optional[Tensor], dw: Tensor,
+                                sums: Optional[Tensor] = None):
+    """``(d h, d p)`` of ``y = out_scale * H interact(h, p, w)`` from ``dy``, the product blocks' weight gradients into ``dw`` (from node-level data where the forward
+    left the pair sums ``sums``).  The member-gradient kernel gathers the three ``dy`` rows of a hyperedge itself where it can (``ihg_interact_bwd_gathered``: no
+    node -> hyperedge launch); otherwise K5 forms the hyperedges' cotangents for ``_interact_backward``."""
     lib = _lib.load()
     n_edges, dim = layout.edge_count, int(h.shape[1])
-    if inv_scale is not None and (dw is not None or not _user_reduced_ok(h, w, grad_out, layout, order)):
-        raise RuntimeError('cotangent planes are read by the user-reduced member-gradient kernel only')
-    if _user_reduced_ok(h, w, grad_out, layout, order):
-        # hyperedges are numbered by user: the kernel sums the user slot on chip and writes dh[users] itself; only the query and item
-        # slots go through the member buffer ([E, 2, d]) and the K7 pass.  Beyond MEMBER_BUFFER_LIMIT_BYTES the buffer is produced in hyperedge chunks
-        # cut where the user changes: every launch writes the rows of its own users, the K7 passes after the first add onto the query and item rows.
-        n_chunks = max(1, -(-(n_edges * 2 * dim * 4) // MEMBER_BUFFER_LIMIT_BYTES))
-        if n_chunks == 1:
-            csr_qi, qi_rows = layout.member_csr_qi()
-            parts = [(0, n_edges, csr_qi, qi_rows)]
+    # the product blocks' weight gradients from node-level data (N rows, no gathers) where the forward left the pair sums
+    node_weight = (sums is not None and NODE_LEVEL_WEIGHT and dy.data_ptr() % 16 == 0 and _ld(dw) % 4 == 0 and h.data_ptr() % 16 == 0
+                   and bool(lib.ihg_node_interact_bwd_weight_supported(dim, order, _ld(h), _ld(sums), _ld(dy))))
+    if node_weight:
+        ws_w = _workspace(int(lib.ihg_node_interact_bwd_weight_workspace_bytes(dim, order)), h.device)
+        with profiler.kernel('node_interact_bwd_weight', layout.node_count, dim):
+            _lib.check(lib.ihg_node_interact_bwd_weight(_ptr(h), _ld(h), _ptr(sums), _ld(sums), _ptr(dy), _ld(dy), _ptr(out_scale), order, _type_begin(layout),
+                                                        _ptr(dw), _ld(dw), _ptr(ws_w), ws_w.numel() * 4, dim, _stream()), 'ihg_node_interact_bwd_weight')
+    if _gathered_backward_ok(h, w, dy, layout, order):
+        # with the weight gradients taken at node level nobody but the first-order scatter would read the hyperedges' cotangents: then that gradient is
+        # the two-hop operator applied to the node-level cotangent and the [E, d] rows are not stored at all.  (Round 3 measured the opposite order - 8.81 against
+        # 8.74 ms per C3 step; since the member-gradient kernel became bound by its memory traffic the 1.1 GB it no longer writes are worth more than the two-hop
+        # launch costs over the scatter: C3 7.89 -> 7.78 ms, C2 1.92 -> 1.87, C4 10.59 -> 10.45; member kernel 1,426-1,467 -> 1,188 us, first-order gradient 672-681 -> 823-833)
+        keep_dout = not node_weight
+        dout = torch.empty(n_edges, dim, dtype=torch.float32, device=h.device) if keep_dout else None
+        def launch(e0, e1, g2, dh, dw_part, ws):             # (one launch: _gathered_backward_ok keeps even the [E, 3, d] buffer within MEMBER_BUFFER_LIMIT_BYTES)
+            _lib.check(lib.ihg_interact_bwd_gathered(_ptr(h), _ld(h), _ptr(layout.i3), _ptr(w), _ld(w), order, _ptr(dy), _ld(dy), _ptr(out_scale),
+                                                     _ptr(dout), dim, _ptr(g2), _ptr(dh), dim, _ptr(dw_part), _ld(dw), _ptr(ws), ws.numel() * 4,
+                                                     n_edges, dim, _stream()), 'ihg_interact_bwd_gathered')
+        dh = _member_gradients(h, layout, order, None if node_weight else dw, True, launch)
+        return dh, (node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient') if keep_dout else _two_hop_first_order_gradient(dy, layout, out_scale))
+    two_hop_first = n_edges * dim * 4 > FIRST_ORDER_TWO_HOP_BYTES
+    inv = None
+    if (COTANGENT_PLANES and node_weight and two_hop_first and dy.data_ptr() % 16 == 0 and bool(lib.ihg_edge_gather_sum_planes_supported(dim, _ld(dy)))
+            and bool(lib.ihg_interact_bwd_user_reduced_planes_supported(dim, order, _ld(h)))):
+        # only the member-gradient kernel reads the hyperedges' cotangents here: K5 writes them as that kernel's operand (same bytes per row), scaled and split once
+        # instead of once per column part of the kernel
+        dout = torch.empty(n_edges, dim, dtype=torch.float32, device=h.device)
+        if _user_reduced_ok(h, w, dout, layout, order):
+            inv = torch.empty(n_edges, dtype=torch.float32, device=h.device)
+            with profiler.kernel('edge_gather_sum', n_edges, dim):
+                _lib.check(lib.ihg_edge_gather_sum_planes(_ptr(dy), _ld(dy), _ptr(layout.i3), _ptr(out_scale), _ptr(layout.edge_weight), _ptr(dout), _ptr(inv), n_edges,
+                                                          dim, _stream()), 'ihg_edge_gather_sum_planes')
         else:
-            parts = layout.member_csr_qi_chunks(n_chunks)
-        dh = torch.empty(layout.node_count, dim, dtype=torch.float32, device=h.device)
-        _zero_isolated_users(dh, layout)
-        for index, (e0, e1, csr_qi, qi_rows) in enumerate(parts):
-            n = e1 - e0
-            g2 = torch.empty(n, 2 * dim, dtype=torch.float32, device=h.device)
-            dw_part = dw if index == 0 or dw is None else torch.empty_like(dw)
-            ws = _workspace(int(lib.ihg_interact_bwd_workspace_bytes(n, dim, order)), h.device)
-            go = grad_out[e0:e1]
-            with profiler.kernel('interact_bwd', n, dim):
-                if inv_scale is not None:
-                    _lib.check(lib.ihg_interact_bwd_user_reduced_planes(_ptr(h), _ld(h), _ptr(layout.i3[e0:e1]), _ptr(w), _ld(w), order, _ptr(go), _ptr(inv_scale[e0:e1]),
-                                                                        _ptr(g2), _ptr(dh), dim, _ptr(ws), ws.numel() * 4, n, dim, _stream()),
-                               'ihg_interact_bwd_user_reduced_planes')
-                else:
-                    _lib.check(lib.ihg_interact_bwd_user_reduced(_ptr(h), _ld(h), _ptr(layout.i3[e0:e1]), _ptr(w), _ld(w), order, _ptr(go), _ld(grad_out), _ptr(g2),
-                                                                 _ptr(dh), dim, _ptr(dw_part), _ld(dw_part) if dw_part is not None else 0, _ptr(ws), ws.numel() * 4, n, dim,
-                                                                 _stream()),
-                               'ihg_interact_bwd_user_reduced')
-            if index > 0 and dw is not None:
-                dw[:, 3 * dim:].add_(dw_part[:, 3 * dim:])
-            node_segment_sum_raw(g2.view(2 * n, dim), csr_qi, out=dh, rows=qi_rows, role='k7.member_gradients', accumulate=index > 0, read_once=True)
-            del g2
-        return dh
-    n_chunks = max(1, -(-(n_edges * 3 * dim * 4) // MEMBER_BUFFER_LIMIT_BYTES))
-    if n_chunks == 1:
-        parts = [(0, n_edges, layout.member_csr)]
+            del dout
+    if inv is None:
+        dout = edge_gather_sum_raw(dy, layout.i3, out_scale, None, 1.0, edge_scale=layout.edge_weight)      # (x m_e: the cotangent of all copies of the row)
+    if two_hop_first:
+        # a [E, d] table far beyond the caches (config C5: 51 GB): its scatter reads HBM at random, the two-hop operator on the node-level
+        # cotangent (10 GB) gathers twice the rows and is still the shorter launch (22 against 32 ms)
+        dp = _two_hop_first_order_gradient(dy, layout, out_scale)
     else:
-        parts = layout.member_csr_chunks(n_chunks)
-    dh = None
-    for index, (e0, e1, csr) in enumerate(parts):
-        n = e1 - e0
-        g = torch.empty(n, 3 * dim, dtype=torch.float32, device=h.device)
-        dw_part = dw if index == 0 or dw is None else torch.empty_like(dw)
-        ws = _workspace(int(lib.ihg_interact_bwd_workspace_bytes(n, dim, order)), h.device)
-        go = grad_out[e0:e1]
-        with profiler.kernel('interact_bwd', n, dim):
-            _lib.check(lib.ihg_interact_bwd(_ptr(h), _ld(h), _ptr(layout.i3[e0:e1]), _ptr(w), _ld(w), order, _ptr(go), _ld(grad_out),
-                                            _ptr(g), _ptr(dw_part), _ld(dw_part) if dw_part is not None else 0, _ptr(ws), ws.numel() * 4, n, dim, _stream()),
-                       'ihg_interact_bwd')
-        if index > 0 and dw is not None:
-            dw[:, 3 * dim:].add_(dw_part[:, 3 * dim:])
-        # (node v, hyperedge e) reads row 3 (e - e0) + type(v); the chunks after the first ADD onto dh inside the kernel (no [N, d] add pass)
-        dh = node_segment_sum_raw(g.view(3 * n, dim), csr, role='k7.member_gradients', out=dh, accumulate=dh is not None, read_once=True)
-        del g
-    return dh
+        # the scatter of dout goes first: K5 has just written it, so most of its rows are still in the Infinity Cache for these random
+        # reads; the interact kernels read it as a stream and do not care
+        dp = node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient')
+    dh = _interact_backward(h, w, dout, layout, order, None if node_weight else dw, inv_scale=inv)
+    return dh, dp
 
 
 class _Interact(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, order: int) -> Tensor:
-        lib = _lib.load()
-        h, p = _rows(h, 'h'), _rows(p, 'p')
-        w = _rows(w, 'w')
-        dim = int(h.shape[1])
-        out = torch.empty(layout.edge_count, dim, dtype=torch.float32, device=h.device)
-        ws = _workspace(int(lib.ihg_interact_fwd_workspace_bytes(layout.edge_count, dim, order)), h.device)
-        with profiler.kernel('interact_fwd', layout.edge_count, dim):
-            _lib.check(lib.ihg_interact_fwd(_ptr(h), _ld(h), _ptr(p), _ld(p), _ptr(layout.i3), _ptr(w), _ld(w), order,
-                                            _ptr(out), _ld(out), _ptr(ws), ws.numel() * 4, layout.edge_count, dim, _stream()),
-                       'ihg_interact_fwd')
+        h, p, w = _rows(h, 'h'), _rows(p, 'p'), _rows(w, 'w')
         ctx.save_for_backward(h, w)
         ctx.layout, ctx.order = layout, order
-        return out
+        return _interact_rows(h, p, w, layout, order)
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
-        lib = _lib.load()
         h, w = ctx.saved_tensors
-        layout, order = ctx.layout, ctx.order
-        grad_out = _rows(grad_out, 'grad_out')
-        n_edges, dim = layout.edge_count, int(h.shape[1])
-        dw = torch.zeros_like(w)
-        dh = _interact_backward(h, w, grad_out, layout, order, dw)
-        dp = node_segment_sum_raw(grad_out, layout.node_csr, role='k7.first_order_gradient')
+        grad_out, dw = _rows(grad_out, 'grad_out'), torch.zeros_like(w)
+        dh = _interact_backward(h, w, grad_out, ctx.layout, ctx.order, dw)
+        dp = node_segment_sum_raw(grad_out, ctx.layout.node_csr, role='k7.first_order_gradient')
         return dh, dp, dw, None, None
 
 
-def _gathered_backward_ok(h: Tensor, w: Tensor, dy: Tensor, layout: IncidenceLayout, order: int) -> bool:
-    lib = _lib.load()
-    n_edges, dim = layout.edge_count, int(h.shape[1])
-    # (the gathering kernel forms sum_m scale[m] dy[m] itself and has no per-hyperedge factor: a layout with multiplicities takes the K5 + member-kernel sequence)
-    return (USER_REDUCED_BACKWARD and n_edges > 0 and getattr(layout, 'user_sorted', False) and layout.edge_weight is None
-            and n_edges * 3 * dim * 4 <= MEMBER_BUFFER_LIMIT_BYTES
-            and bool(lib.ihg_interact_bwd_gathered_supported(dim, order, _ld(h), _ld(dy)))
-            and h.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0 and _ld(w) % 4 == 0)
+def interact(h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, order: int) -> Tensor:
+    """Interactive node -> hyperedge step: first-order part from ``p`` (hoisted), products contracted with ``w``."""
+    if order not in (2, 3):
+        raise ValueError('interact handles interaction orders 2 and 3; order 1 is edge_gather_sum on the hoisted features')
+    return _Interact.apply(h, p, w, layout, int(order))
 
 
 class _InteractToNodes(torch.autograd.Function):
     """Interactive node -> hyperedge step and the hyperedge -> node pass behind it (``GnnLayers.py:229-236``) as ONE autograd node:
-    ``y = out_scale * H interact(h, p, w)``.  Forward: the two kernels of the separate ops.  Backward: the hyperedge cotangent
-    ``sum_m out_scale[m] dy[m]`` is not produced by a node -> hyperedge launch (K5) - the member-gradient kernel gathers the three
-    ``dy`` rows of a hyperedge itself and leaves their sum for the weight gradients and the first-order scatter
-    (``ihg_interact_bwd_gathered``); where that kernel does not apply, the separate ops' sequence."""
+    ``y = out_scale * H interact(h, p, w)``.  Forward: the two kernels of the separate ops.  Backward: ``_interact_to_nodes_backward``, the
+    interactive layer's own (without pair sums)."""
 
     @staticmethod
     def forward(ctx, h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, order: int, out_scale: Optional[Tensor], rows: Optional[Tensor],
                 out: Optional[Tensor]) -> Tensor:
-        lib = _lib.load()
         h, p, w = _rows(h, 'h'), _rows(p, 'p'), _rows(w, 'w')
-        dim = int(h.shape[1])
         _check_out(out, h, p, w)
-        edge = torch.empty(layout.edge_count, dim, dtype=torch.float32, device=h.device)
-        ws = _workspace(int(lib.ihg_interact_fwd_workspace_bytes(layout.edge_count, dim, order)), h.device)
-        with profiler.kernel('interact_fwd', layout.edge_count, dim):
-            _lib.check(lib.ihg_interact_fwd(_ptr(h), _ld(h), _ptr(p), _ld(p), _ptr(layout.i3), _ptr(w), _ld(w), order,
-                                            _ptr(edge), _ld(edge), _ptr(ws), ws.numel() * 4, layout.edge_count, dim, _stream()),
-                       'ihg_interact_fwd')
-        mode = _lib.SCALE_NONE if out_scale is None else _lib.SCALE_MULTIPLY
-        y = node_segment_sum_raw(edge, layout.node_csr, layout.edge_weight, out_scale, mode, rows=rows, role='k7.edges_to_nodes', out=out)
         ctx.save_for_backward(h, w)
         ctx.layout, ctx.order, ctx.out_scale = layout, order, out_scale
-        return y
+        return _edges_to_nodes(_interact_rows(h, p, w, layout, order), layout, out_scale, rows, out)
 
     @staticmethod
     def backward(ctx, dy: Tensor):
-        lib = _lib.load()
         h, w = ctx.saved_tensors
-        layout, order, out_scale = ctx.layout, ctx.order, ctx.out_scale
-        dy = _rows(dy, 'dy')
-        n_edges, dim = layout.edge_count, int(h.shape[1])
-        dw = torch.zeros_like(w)
-        if _gathered_backward_ok(h, w, dy, layout, order):
-            csr_qi, qi_rows = layout.member_csr_qi()
-            dout = torch.empty(n_edges, dim, dtype=torch.float32, device=h.device)
-            g2 = torch.empty(n_edges, 2 * dim, dtype=torch.float32, device=h.device)
-            dh = torch.empty(layout.node_count, dim, dtype=torch.float32, device=h.device)
-            _zero_isolated_users(dh, layout)
-            ws = _workspace(int(lib.ihg_interact_bwd_workspace_bytes(n_edges, dim, order)), h.device)
-            with profiler.kernel('interact_bwd', n_edges, dim):
-                _lib.check(lib.ihg_interact_bwd_gathered(_ptr(h), _ld(h), _ptr(layout.i3), _ptr(w), _ld(w), order, _ptr(dy), _ld(dy), _ptr(out_scale),
-                                                         _ptr(dout), dim, _ptr(g2), _ptr(dh), dim, _ptr(dw), _ld(dw), _ptr(ws), ws.numel() * 4,
-                                                         n_edges, dim, _stream()), 'ihg_interact_bwd_gathered')
-            node_segment_sum_raw(g2.view(2 * n_edges, dim), csr_qi, out=dh, rows=qi_rows, role='k7.member_gradients', read_once=True)
-        else:
-            dout = edge_gather_sum_raw(dy, layout.i3, out_scale, None, 1.0, edge_scale=layout.edge_weight)      # (the cotangent of ALL copies of a row: x m_e)
-            dh = _interact_backward(h, w, dout, layout, order, dw)
-        dp = node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient')
+        dy, dw = _rows(dy, 'dy'), torch.zeros_like(w)
+        dh, dp = _interact_to_nodes_backward(h, w, dy, ctx.layout, ctx.order, ctx.out_scale, dw)
         return dh, dp, dw, None, None, None, None, None
 
 
@@ -993,11 +1026,9 @@ def interact_to_nodes(h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, 
 
 
 class _InteractLayer(torch.autograd.Function):
-    """The whole interactive layer behind ``feature_transform`` as ONE autograd node (``CommonLayers.py:70-85`` + ``GnnLayers.py:229-236``):
-    hoisted first-order blocks (typed row GEMM) -> product blocks (``ihg_interact_fwd``) -> hyperedge -> node pass.  Backward: the member-
-    gradient kernel forms the hyperedges' cotangents itself where it can (``ihg_interact_bwd_gathered``, else a K5 launch), the first-order
-    path's contribution to ``d h`` is ADDED by the node-level weight-gradient kernel onto the member gradients' scatter result
-    (``dx_accumulate``: no separate ``[N, d]`` add, no second ``[N, d]`` buffer), and both halves of ``d aggregation.weight`` land in one tensor."""
+    """The whole interactive layer behind ``feature_transform`` as ONE autograd node (``CommonLayers.py:70-85`` + ``GnnLayers.py:229-236``): hoisted first-order blocks
+    (typed row GEMM) -> product blocks (``ihg_interact_fwd``) -> hyperedge -> node pass, or the node-level form (pair sums + ``ihg_node_interact_fwd``).  Backward:
+    ``_interact_to_nodes_backward``, then the first-order epilogue, which ADDS its input gradient onto ``d h``; both halves of ``d aggregation.weight`` land in one tensor."""
 
     @staticmethod
     def forward(ctx, h: Tensor, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, order: int, out_scale: Optional[Tensor], rows: Optional[Tensor],
@@ -1019,99 +1050,16 @@ class _InteractLayer(torch.autograd.Function):
                            'ihg_node_interact_fwd')
             return y
         ctx.save_for_backward(h, w)
-        p = torch.empty(h.shape[0], dim, dtype=torch.float32, device=h.device)
-        ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
-        with profiler.kernel('node_linear_fwd', h.shape[0], dim):
-            _lib.check(lib.ihg_node_linear_fwd(_ptr(h), _ld(h), _ptr(w), int(w.stride(0)), dim, _ptr(bias), 0b001, 0, _type_begin(layout),
-                                               _ptr(p), _ld(p), _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd')
-        edge = torch.empty(layout.edge_count, dim, dtype=torch.float32, device=h.device)
-        ws2 = _workspace(int(lib.ihg_interact_fwd_workspace_bytes(layout.edge_count, dim, order)), h.device)
-        with profiler.kernel('interact_fwd', layout.edge_count, dim):
-            _lib.check(lib.ihg_interact_fwd(_ptr(h), _ld(h), _ptr(p), _ld(p), _ptr(layout.i3), _ptr(w), _ld(w), order,
-                                            _ptr(edge), _ld(edge), _ptr(ws2), ws2.numel() * 4, layout.edge_count, dim, _stream()),
-                       'ihg_interact_fwd')
-        mode = _lib.SCALE_NONE if out_scale is None else _lib.SCALE_MULTIPLY
-        return node_segment_sum_raw(edge, layout.node_csr, layout.edge_weight, out_scale, mode, rows=rows, role='k7.edges_to_nodes', out=out)
+        p = _first_order_rows(h, w, bias, layout)
+        return _edges_to_nodes(_interact_rows(h, p, w, layout, order), layout, out_scale, rows, out)
 
     @staticmethod
     def backward(ctx, dy: Tensor):
-        lib = _lib.load()
         h, w = ctx.saved_tensors[:2]
         sums = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
-        layout, order, out_scale = ctx.layout, ctx.order, ctx.out_scale
-        dy = _rows(dy, 'dy')
-        n_edges, dim = layout.edge_count, int(h.shape[1])
         dw = torch.empty_like(w)                               # product blocks from the interact kernels, first-order blocks from the row-GEMM pass
-        gathered = _gathered_backward_ok(h, w, dy, layout, order)
-        # the product blocks' weight gradients from node-level data (N rows, no gathers) where the forward left the pair sums
-        node_weight = (sums is not None and NODE_LEVEL_WEIGHT and dy.data_ptr() % 16 == 0 and _ld(dw) % 4 == 0 and h.data_ptr() % 16 == 0
-                       and bool(lib.ihg_node_interact_bwd_weight_supported(dim, order, _ld(h), _ld(sums), _ld(dy))))
-        if node_weight:
-            ws_w = _workspace(int(lib.ihg_node_interact_bwd_weight_workspace_bytes(dim, order)), h.device)
-            with profiler.kernel('node_interact_bwd_weight', layout.node_count, dim):
-                _lib.check(lib.ihg_node_interact_bwd_weight(_ptr(h), _ld(h), _ptr(sums), _ld(sums), _ptr(dy), _ld(dy), _ptr(out_scale), order, _type_begin(layout),
-                                                            _ptr(dw), _ld(dw), _ptr(ws_w), ws_w.numel() * 4, dim, _stream()), 'ihg_node_interact_bwd_weight')
-        del sums
-        if gathered:
-            csr_qi, qi_rows = layout.member_csr_qi()
-            # with the weight gradients taken at node level nobody but the first-order scatter would read the hyperedges' cotangents: then that gradient is
-            # the two-hop operator applied to the node-level cotangent and the [E, d] rows are not stored at all.  (Round 3 measured the opposite order - 8.81 against
-            # 8.74 ms per C3 step; since the member-gradient kernel became bound by its memory traffic the 1.1 GB it no longer writes are worth more than the two-hop
-            # launch costs over the scatter: C3 7.89 -> 7.78 ms, C2 1.92 -> 1.87, C4 10.59 -> 10.45; member kernel 1,426-1,467 -> 1,188 us, first-order gradient 672-681 -> 823-833)
-            keep_dout = not node_weight
-            dout = torch.empty(n_edges, dim, dtype=torch.float32, device=h.device) if keep_dout else None
-            g2 = torch.empty(n_edges, 2 * dim, dtype=torch.float32, device=h.device)
-            dh = torch.empty(layout.node_count, dim, dtype=torch.float32, device=h.device)
-            _zero_isolated_users(dh, layout)
-            ws = _workspace(int(lib.ihg_interact_bwd_workspace_bytes(n_edges, dim, order)), h.device)
-            with profiler.kernel('interact_bwd', n_edges, dim):
-                _lib.check(lib.ihg_interact_bwd_gathered(_ptr(h), _ld(h), _ptr(layout.i3), _ptr(w), _ld(w), order, _ptr(dy), _ld(dy), _ptr(out_scale),
-                                                         _ptr(dout) if keep_dout else None, dim, _ptr(g2), _ptr(dh), dim, None if node_weight else _ptr(dw), _ld(dw), _ptr(ws), ws.numel() * 4,
-                                                         n_edges, dim, _stream()), 'ihg_interact_bwd_gathered')
-            node_segment_sum_raw(g2.view(2 * n_edges, dim), csr_qi, out=dh, rows=qi_rows, role='k7.member_gradients', read_once=True)
-            del g2
-            if keep_dout:
-                dp = node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient')
-            else:
-                dp = _two_hop_first_order_gradient(dy, layout, out_scale)
-        else:
-            two_hop_first = n_edges * dim * 4 > FIRST_ORDER_TWO_HOP_BYTES
-            inv = None
-            if (COTANGENT_PLANES and node_weight and two_hop_first and dy.data_ptr() % 16 == 0 and bool(lib.ihg_edge_gather_sum_planes_supported(dim, _ld(dy)))
-                    and bool(lib.ihg_interact_bwd_user_reduced_planes_supported(dim, order, _ld(h)))):
-                # only the member-gradient kernel reads the hyperedges' cotangents here: K5 writes them as that kernel's operand (same bytes per row), scaled and split once
-                # instead of once per column part of the kernel
-                dout = torch.empty(n_edges, dim, dtype=torch.float32, device=h.device)
-                if _user_reduced_ok(h, w, dout, layout, order):
-                    inv = torch.empty(n_edges, dtype=torch.float32, device=h.device)
-                    with profiler.kernel('edge_gather_sum', n_edges, dim):
-                        _lib.check(lib.ihg_edge_gather_sum_planes(_ptr(dy), _ld(dy), _ptr(layout.i3), _ptr(out_scale), _ptr(layout.edge_weight), _ptr(dout), _ptr(inv), n_edges,
-                                                                  dim, _stream()), 'ihg_edge_gather_sum_planes')
-                else:
-                    del dout
-            if inv is None:
-                dout = edge_gather_sum_raw(dy, layout.i3, out_scale, None, 1.0, edge_scale=layout.edge_weight)      # (x m_e: the cotangent of all copies of the row)
-            if two_hop_first:
-                # a [E, d] table far beyond the caches (config C5: 51 GB): its scatter reads HBM at random, the two-hop operator on the node-level
-                # cotangent (10 GB) gathers twice the rows and is still the shorter launch (22 against 32 ms)
-                dp = _two_hop_first_order_gradient(dy, layout, out_scale)
-            else:
-                # the scatter of dout goes first: K5 has just written it, so most of its rows are still in the Infinity Cache for these random
-                # reads; the interact kernels read it as a stream and do not care
-                dp = node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient')
-            dh = _interact_backward(h, w, dout, layout, order, None if node_weight else dw, inv_scale=inv)
-            del inv
-        del dout
-        dbias = torch.empty(dim, dtype=torch.float32, device=h.device) if ctx.has_bias else None
-        ws2 = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
-        accumulate = bool(lib.ihg_node_linear_bwd_accumulates(dim, _ld(dp), _ld(h), _ld(dh))) and h.data_ptr() % 16 == 0 and dh.data_ptr() % 16 == 0 and dp.data_ptr() % 16 == 0
-        dx = dh if accumulate else torch.empty_like(dh)
-        with profiler.kernel('node_linear_bwd', h.shape[0], dim):
-            _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(dp), _ld(dp), _ptr(h), _ld(h), _type_begin(layout), _ptr(dw), int(dw.stride(0)), dim,
-                                                      _ptr(dbias), 0b001, 0, _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx), 1 if accumulate else 0,
-                                                      _ptr(ws2), ws2.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
-        if not accumulate:
-            dh.add_(dx)
+        dh, dp = _interact_to_nodes_backward(h, w, _rows(dy, 'dy'), ctx.layout, ctx.order, ctx.out_scale, dw, sums)
+        dbias = _first_order_backward(dp, h, w, ctx.layout, dw, dh, ctx.has_bias)
         return dh, dw, dbias, None, None, None, None, None
 
 
@@ -1124,78 +1072,10 @@ def interact_layer(h: Tensor, w: Tensor, bias: Optional[Tensor], layout: Inciden
     dim, wide = int(h.shape[1]), padded_width(int(h.shape[1]))
     if wide != dim and int(w.shape[0]) == dim and h.is_cuda:
         # a width between the tiled ones: the same layer at the next tiled width on zero-padded operands (the padding columns of the result are exactly zero and are cut off)
-        if out is not None:
-            _check_out(out, h, w, bias)
-            out.copy_(_InteractLayer.apply(pad_columns(h, wide), pad_blocks(w, wide), pad_vector(bias, wide), layout, int(order), out_scale, rows, None)[:, :dim])
-            return out
-        return _InteractLayer.apply(pad_columns(h, wide), pad_blocks(w, wide), pad_vector(bias, wide), layout, int(order), out_scale, rows, None)[:, :dim]
+        _check_out(out, h, w, bias)
+        y = _InteractLayer.apply(pad_columns(h, wide), pad_blocks(w, wide), pad_vector(bias, wide), layout, int(order), out_scale, rows, None)[:, :dim]
+        return y if out is None else out.copy_(y)
     return _InteractLayer.apply(h, w, bias, layout, int(order), out_scale, rows, out)
-
-
-class _InteractFromNodes(torch.autograd.Function):
-    """First-order blocks (typed row-GEMM) + product blocks (MFMA interact kernel) of ``FeatureInteractor`` as ONE autograd
-    node, so that in the backward the first-order path's contribution to ``d h`` is accumulated by the kernel into the member
-    gradients' scatter result (no separate ``[N, d]`` add) and both halves of ``d aggregation.weight`` land in one tensor."""
-
-    @staticmethod
-    def forward(ctx, h: Tensor, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, order: int) -> Tensor:
-        lib = _lib.load()
-        h, w = _rows(h, 'h'), _rows(w, 'w')
-        dim = int(h.shape[1])
-        p = torch.empty_like(h)
-        ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
-        with profiler.kernel('node_linear_fwd', h.shape[0], dim):
-            _lib.check(lib.ihg_node_linear_fwd(_ptr(h), _ld(h), _ptr(w), int(w.stride(0)), dim, _ptr(bias), 0b001, 0, _type_begin(layout),
-                                               _ptr(p), _ld(p), _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd')
-        out = torch.empty(layout.edge_count, dim, dtype=torch.float32, device=h.device)
-        ws2 = _workspace(int(lib.ihg_interact_fwd_workspace_bytes(layout.edge_count, dim, order)), h.device)
-        with profiler.kernel('interact_fwd', layout.edge_count, dim):
-            _lib.check(lib.ihg_interact_fwd(_ptr(h), _ld(h), _ptr(p), _ld(p), _ptr(layout.i3), _ptr(w), _ld(w), order,
-                                            _ptr(out), _ld(out), _ptr(ws2), ws2.numel() * 4, layout.edge_count, dim, _stream()),
-                       'ihg_interact_fwd')
-        ctx.save_for_backward(h, w)
-        ctx.layout, ctx.order, ctx.has_bias = layout, order, bias is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out: Tensor):
-        lib = _lib.load()
-        h, w = ctx.saved_tensors
-        layout, order = ctx.layout, ctx.order
-        grad_out = _rows(grad_out, 'grad_out')
-        n_edges, dim = layout.edge_count, int(h.shape[1])
-        dw = torch.empty_like(w)                               # product blocks from the interact kernels, first-order blocks from the row-GEMM pass
-        # the scatter of grad_out goes first: K5 has just written it, so most of its 256-byte rows are still in the Infinity Cache
-        # for these random reads; the interact kernels read it as a stream and do not care
-        dp = node_segment_sum_raw(grad_out, layout.node_csr, role='k7.first_order_gradient')
-        dh = _interact_backward(h, w, grad_out, layout, order, dw)
-        dbias = torch.empty(dim, dtype=torch.float32, device=h.device) if ctx.has_bias else None
-        ws2 = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
-        with profiler.kernel('node_linear_bwd', h.shape[0], dim):
-            _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(dp), _ld(dp), _ptr(h), _ld(h), _type_begin(layout), _ptr(dw), int(dw.stride(0)), dim,
-                                                      _ptr(dbias), 0b001, 0, _ptr(w), int(w.stride(0)), _ptr(dh), _ld(dh), 1,
-                                                      _ptr(ws2), ws2.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
-        return dh, dw, dbias, None, None
-
-
-def interact_from_nodes_supported(h: Tensor, w: Tensor) -> bool:
-    """The one-node form needs the fused row-GEMM backward (d = 64, aligned rows) and the tiled interact kernels."""
-    return node_linear_tiled(h, w) and int(h.shape[1]) == 64 and h.is_contiguous()
-
-
-def interact_from_nodes(h: Tensor, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, order: int) -> Tensor:
-    """``FeatureInteractor`` of order 2 / 3 from the node features: ``out[e] = sum_m (h[m] A_m^T) + c + sum_b W_b z_b[e]``
-    with ``w = [A_u | A_q | A_i | W_uq | W_qi | W_iu (| W_uqi)]`` (``CommonLayers.py:70-85``)."""
-    if order not in (2, 3):
-        raise ValueError('interact_from_nodes handles interaction orders 2 and 3')
-    return _InteractFromNodes.apply(h, w, bias, layout, int(order))
-
-
-def interact(h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, order: int) -> Tensor:
-    """Interactive node -> hyperedge step: first-order part from ``p`` (hoisted), products contracted with ``w``."""
-    if order not in (2, 3):
-        raise ValueError('interact handles interaction orders 2 and 3; order 1 is edge_gather_sum on the hoisted features')
-    return _Interact.apply(h, p, w, layout, int(order))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -944,6 +944,32 @@ def test_interact_to_nodes_backward_forms_the_hyperedge_cotangents_itself(order,
             assert rel(got, want) <= RTOL
 
 
+@pytest.mark.parametrize('dim', [64, 128])
+@pytest.mark.parametrize('order', [3, 2])
+def test_feature_interactor_module_call(order, dim):
+    """The module call ``FeatureInteractor(...)(h)`` - hyperedge features of orders 2 and 3 (``first_order`` + ``ops.interact``, outside the training step) - and the
+    gradients of ``h`` and of both ``aggregation`` parameters against the oracle's FeatureInteractor in float64, at d = 64 and d = 128."""
+    from types import SimpleNamespace
+    from ihgnn_amd.Models.CommonLayers import FeatureInteractor
+    from oracle import ihgnn_ref as ref
+    w_, lay = make_layout(301, 17, 211, 9000, seed=order + dim, edge_order='user')
+    torch.manual_seed(order + dim)
+    module = FeatureInteractor(SimpleNamespace(hypergraph=SimpleNamespace(layout=lay)), order, dim, dim)
+    gen = torch.Generator().manual_seed(dim)
+    h = torch.randn(lay.node_count, dim, generator=gen)
+    cot = torch.randn(lay.edge_count, dim, generator=gen)
+    h64, w64, b64 = (t.detach().double().requires_grad_(True) for t in (h, module.aggregation.weight, module.aggregation.bias))
+    want = ref.feature_interactor(h64, torch.from_numpy(lay.i3_host.astype(np.int64)), w64, b64, order)
+    want.backward(cot.double())
+    module = module.to(dev())
+    hd = h.to(dev()).requires_grad_(True)
+    got = module(hd)
+    got.backward(cot.to(dev()))
+    assert got.shape == (lay.edge_count, dim) and rel(got, want) <= RTOL
+    assert rel(hd.grad, h64.grad) <= RTOL
+    assert rel(module.aggregation.weight.grad, w64.grad) <= RTOL and rel(module.aggregation.bias.grad, b64.grad) <= RTOL
+
+
 @pytest.mark.parametrize('dim', [64, 128, 256])
 @pytest.mark.parametrize('edges', [1, 15, 33])
 def test_interact_split_kernels_on_tiny_hypergraphs(dim, edges):
