@@ -14,10 +14,10 @@ _FLAGS = (
     ('epoch_test_frequency', ('--epoch_test_frequency', '--etf'), int, 0, 'test every this many epochs'),
     ('dataset', ('--dataset', '--ds'), str, '', 'dataset sub-directory under the data root'),
     ('model', ('--model',), str, '', 'model type (RawGnn)'),
-    ('gnn', ('--gnn',), str, '', 'GNN layer type: IHGNN | HGCN (GCN / GAT are not part of this build)'),
+    ('gnn', ('--gnn',), str, '', 'GNN layer type: IHGNN | HGCN | GCN | GAT'),
     ('gnns', ('--gnns',), int, 0, 'number of GNN layers (0 = driver default 2)'),
     ('feature_order', ('--feature_order', '--fo'), int, 0, 'interaction order 1 | 2 | 3 (0 = driver default 3)'),
-    ('completeness', ('--completeness',), str, Gsv.graph_uqi, 'pairwise-graph completeness (GCN only)'),
+    ('completeness', ('--completeness',), str, Gsv.graph_uqi, 'pairwise-graph completeness (GCN / GAT)'),
     ('longtail', ('--longtail',), str, '', 'per-user long-tail statistics file name'),
     ('device', ('--device', '-d'), str, '', 'GPU ordinal ("0" = cuda:0)'),
     ('embedding_size', ('--embedding_size', '--emb'), int, 0, 'embedding width (0 = Gs.embedding_size)'),

@@ -29,6 +29,11 @@ class Gs:
     non_random_negative_sample_size = 0
     negative_sample_size = random_negative_sample_size + non_random_negative_sample_size
 
+    class Gnn:
+        # GATLayer (GnnLayers.py:65-86): the reference assigns each twice or three times and the last assignment wins (GlobalSettings.py:59-66)
+        gat_head = Gsv.concat            # or Gsv.product
+        gat_activation = (nn.LeakyReLU, 'leaky_relu')      # or (nn.ReLU, 'relu'), (nn.Tanh, 'tanh')
+
     class Query:
         transform = Gsv.mean             # the only transform on the path (EmbeddingLayers.py:37-38)
         transform_activation = nn.ReLU

@@ -22,7 +22,7 @@ from .Helpers.IOHelper import IOHelper
 from .Helpers.Metrics import Metrics, MetricsCollection
 from .Helpers.ProcessController import ProcessController
 from .Helpers.TrainTestHelper import print_network_parameters, test_and_get_avg_metrics, train_and_get_avg_loss
-from .Models import GCNLayer, HGCNLayer, HemPredictionLayer, IHGNNLayer, RawGnn, parse_gnn_layer, parse_model_type
+from .Models import GATLayer, GCNLayer, HGCNLayer, HemPredictionLayer, IHGNNLayer, RawGnn, parse_gnn_layer, parse_model_type
 
 DEFAULT_DATASET = 'AlibabaAir/Complete5Core/'
 
@@ -55,7 +55,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     if (parse_model_type[args.model] or RawGnn) is not RawGnn:
         raise NotImplementedError('only the RawGnn model is part of this build')
     layer_type = parse_gnn_layer[args.gnn] or IHGNNLayer
-    if layer_type not in (IHGNNLayer, HGCNLayer, GCNLayer):
+    if layer_type not in (IHGNNLayer, HGCNLayer, GCNLayer, GATLayer):
         raise NotImplementedError(f'{layer_type.__name__} is outside the MI355X hypergraph path')
     layer_count = args.gnns or 2
     order = args.feature_order or 3
@@ -87,7 +87,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         fn_graph_info=os.path.join(data_dir, 'graph_info.txt'),
         fn_queries_multihot=os.path.join(data_dir, 'queries_multihot.txt'),
         fn_train_data=os.path.join(data_dir, 'train_data.csv'),
-        graph_type=Pps2DGraph if layer_type is GCNLayer else PpsHyperGraph,
+        graph_type=Pps2DGraph if layer_type in (GCNLayer, GATLayer) else PpsHyperGraph,
         random_negative_sample_size=Gs.random_negative_sample_size,
         non_random_negative_sample_size=Gs.non_random_negative_sample_size,
         device=device)

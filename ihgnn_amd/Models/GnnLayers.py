@@ -3,8 +3,8 @@
 Constructor signatures, sub-module names (``feature_transform``, ``feature_interactor.aggregation``) and the
 absence of any non-linearity follow the reference; the sparse work runs in the HIP kernels of
 libihgnn_hip.so through :mod:`ihgnn_amd.ops` instead of ``torch_sparse.matmul``.
-``GCNLayer`` (pairwise-graph baseline) runs on the same segment-sum kernel over a weighted CSR; ``GATLayer`` (DGL) is
-declared for the name tables only.
+``GCNLayer`` (pairwise-graph baseline) runs on the same segment-sum kernel over a weighted CSR; ``GATLayer`` (the attention
+baseline) adds the score and softmax kernels of csrc/gat.hip in front of it.
 """
 from typing import Optional
 
@@ -13,6 +13,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import ops
+from ..Helpers.GlobalSettings import Gsv
 from .CommonLayers import FeatureInteractor
 
 
@@ -152,8 +153,49 @@ class GCNLayer(nn.Module):
         return ops.pair_spmm(_transform(self.feature_transform, input_features, self.graph), self.graph, out=out)
 
 
+_GAT_ACTIVATIONS = {'leaky_relu': nn.LeakyReLU, 'relu': nn.ReLU, 'tanh': nn.Tanh}
+
+
 class GATLayer(nn.Module):
-    def __init__(self, *args, **kwargs):
+    """Single-head attention over the pairwise graph (``GnnLayers.py:48-115``): ``h = X W^T + b``, for every edge ``u -> v`` a score
+    ``act(w . [h_u | h_v] + c)`` (head ``Gs.Gnn.gat_head`` = concatenation) or ``act(w . (h_u * h_v) + c)`` (product), a softmax over ``v``'s incoming
+    edges, ``Y[v] = sum alpha h_u``.
+
+    Construction order, initialisation and state-dict keys follow the reference (``feature_aggregate`` = Linear + activation, its weight re-drawn by
+    ``xavier_uniform_`` with the activation's gain, then ``feature_transform``), so a seeded model draws the reference's weights.  The attention runs in
+    ``ops.gat_attention`` (csrc/gat.hip + K7) over the graph's symmetric CSR; no ``[nnz, 2, d]`` rows are formed."""
+
+    def __init__(self, device: torch.device, dataset, input_dimension: int, output_dimension: int):
         super().__init__()
-        raise NotImplementedError('GATLayer (DGL edge-softmax baseline, GnnLayers.py:48-115) is outside the MI355X hypergraph '
-                                  'path (SURVEY.md §2); use IHGNNLayer, HGCNLayer or GCNLayer')
+        from ..Helpers.GlobalSettings import Gs
+        self.device = device
+        self.dataset = dataset
+        self.input_dimension = input_dimension
+        self.output_dimension = output_dimension
+        self.graph = dataset.graph2d.layout
+        head = Gs.Gnn.gat_head
+        act_type, act_name = Gs.Gnn.gat_activation
+        if head not in (Gsv.concat, Gsv.product):
+            raise ValueError(f'GATLayer: unknown head {head!r} (Gsv.concat or Gsv.product)')
+        if _GAT_ACTIVATIONS.get(act_name) is not act_type:
+            raise ValueError(f'GATLayer: activation {act_name!r} / {act_type} is not one of {sorted(_GAT_ACTIVATIONS)} with its nn class')
+        self.head, self.activation = head, act_name
+        feature_aggregate = nn.Linear(2 * output_dimension if head == Gsv.concat else output_dimension, 1)
+        nn.init.xavier_uniform_(feature_aggregate.weight, gain=nn.init.calculate_gain(act_name))
+        self.feature_aggregate = nn.Sequential(feature_aggregate, act_type())
+        self.feature_transform = nn.Linear(input_dimension, output_dimension)
+
+    def _attention_weight(self, wide: int) -> Tensor:
+        """``feature_aggregate.0.weight`` as the kernel's vector at the width the features run at: each half of a concatenation weight zero-padded on its own."""
+        w = self.feature_aggregate[0].weight
+        d = self.output_dimension
+        if wide == d:
+            return w
+        if self.head == Gsv.concat:
+            return ops.pad_columns(w.view(2, d), wide).reshape(1, 2 * wide)
+        return ops.pad_vector(w, wide)
+
+    def forward(self, input_features, out: Optional[Tensor] = None) -> Tensor:
+        """``input_features``: ``[N, d]`` (or ``ops.NodeTables``); ``out`` (inference only): the ``[N, d]`` destination, e.g. a column slice of the feature matrix."""
+        h = _transform(self.feature_transform, input_features, self.graph)
+        return ops.gat_attention(h, self.graph, self._attention_weight(_row_width(h)), self.feature_aggregate[0].bias, self.head, self.activation, out=out)

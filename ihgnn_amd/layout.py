@@ -75,7 +75,7 @@ class Csr:
         self.max_row_len = int(lens.max()) if lens.size else 0
         if self.n_heavy == 0:
             self.n_segments = 0
-            self.heavy_rows = self.heavy_segptr = self.seg_begin = self.seg_end = None
+            self.heavy_rows = self.heavy_segptr = self.seg_begin = self.seg_end = self.seg_row = None
             return
         # a row is cut into at most HEAVY_MAX_SEGMENTS pieces: the few extreme rows of a power-law graph (config C5: one query with millions of
         # hyperedges) get longer segments instead of tens of thousands of partial sums that ONE workgroup of the finish kernel adds up serially
@@ -94,6 +94,7 @@ class Csr:
         self.heavy_segptr = torch.from_numpy(segptr.astype(np.int32)).to(dev)
         self.seg_begin = torch.from_numpy(begin.astype(np.int32)).to(dev)
         self.seg_end = torch.from_numpy(end.astype(np.int32)).to(dev)
+        self.seg_row = torch.from_numpy(heavy[owner].astype(np.int32)).to(dev)      # the row each segment belongs to (the GAT softmax, csrc/gat.hip)
 
     def _plan_order(self) -> None:
         """Rows by decreasing length (stable), heavy rows last: equal-length neighbours share a wave."""
@@ -576,3 +577,37 @@ class PairLayout:
         self.degree = deg.to(device)
         isolated = deg < 0.5
         self.inv_sqrt_deg = torch.where(isolated, torch.zeros_like(deg), deg.pow(-0.5)).to(device)
+        self._mirror = None
+
+    @property
+    def mirror_host(self) -> np.ndarray:
+        """``[nnz]`` int32: for the entry ``p`` of row ``v`` with column ``u``, the position of the entry ``(u, v)`` in row ``u`` - the reverse edge, which the GAT
+        attention's backward walks (``ops.gat_attention``).  Built on first use and kept; raises if the adjacency is not symmetric or lists a pair twice."""
+        if self._mirror is None:
+            ptr = self.csr.ptr_host.astype(np.int64)
+            cols = self.csr.ids_host.astype(np.int64)
+            rows = np.repeat(np.arange(self.node_count, dtype=np.int64), np.diff(ptr))
+            n = max(self.node_count, 1)
+            key = rows * n + cols
+            order = np.argsort(key, kind='stable')             # (the builder's rows hold ascending columns: order is the identity there)
+            want = cols * n + rows
+            at = np.searchsorted(key[order], want)
+            found = at < key.shape[0]
+            found[found] = key[order][at[found]] == want[found]
+            if not found.all():
+                p = int(np.nonzero(~found)[0][0])
+                raise ValueError(f'PairLayout: the adjacency is not symmetric - entry ({int(rows[p])}, {int(cols[p])}) has no reverse entry')
+            mirror = order[at]
+            if not (mirror[mirror] == np.arange(mirror.shape[0])).all():
+                # a (row, column) pair listed twice: two entries would share one reverse position and the other would never be written
+                raise ValueError('PairLayout: the adjacency lists a (row, column) pair more than once - the reverse entries are not one-to-one')
+            self._mirror = mirror.astype(np.int32)
+        return self._mirror
+
+    @property
+    def mirror(self) -> torch.Tensor:
+        """``mirror_host`` on the device (int32)."""
+        dev = getattr(self, '_mirror_dev', None)
+        if dev is None:
+            dev = self._mirror_dev = torch.from_numpy(self.mirror_host).to(self.device)
+        return dev

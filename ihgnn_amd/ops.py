@@ -329,6 +329,96 @@ def pair_spmm(x: Tensor, graph, out: Optional[Tensor] = None) -> Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
+# GAT attention over the pairwise graph (csrc/gat.hip + K7)
+# ---------------------------------------------------------------------------------------------
+GAT_HEADS = {'concatenation': 0, 'product': 1}                  # Gsv.concat / Gsv.product -> IHG_GAT_CONCAT / IHG_GAT_PRODUCT
+GAT_ACTIVATIONS = {'leaky_relu': 0, 'relu': 1, 'tanh': 2}       # the names of Gs.Gnn.gat_activation -> IHG_GAT_*
+
+
+def _gat_plan(csr: Csr):
+    heavy = csr.n_heavy > 0
+    return (csr.heavy_threshold if heavy else 0, _ptr(csr.seg_begin) if heavy else None, _ptr(csr.seg_end) if heavy else None,
+            _ptr(csr.seg_row) if heavy else None, csr.n_segments if heavy else 0, _ptr(csr.heavy_rows) if heavy else None,
+            _ptr(csr.heavy_segptr) if heavy else None, csr.n_heavy)
+
+
+class _GatAttention(torch.autograd.Function):
+    """``out[v] = sum over v's incoming edges u -> v of softmax_v(act(score(u, v))) h[u]`` (``GnnLayers.py:98-115``): scores and softmax in
+    ``ihg_gat_attention_fwd``, the weighted sum in K7; backward: ``ihg_gat_scores_bwd``, K7 over the cotangent with the mirrored weights (and, product head,
+    over ``h`` with ``ds + ds[mirror]``), ``ihg_gat_finish_bwd``."""
+
+    @staticmethod
+    def forward(ctx, h: Tensor, weight: Tensor, bias: Tensor, graph, head: int, activation: int, out: Optional[Tensor]) -> Tensor:
+        lib = _lib.load()
+        h = _rows(h, 'h')
+        csr = graph.csr
+        n, dim = int(h.shape[0]), int(h.shape[1])
+        if n != graph.node_count:
+            raise ValueError(f'gat_attention: h has {n} rows, the graph {graph.node_count} nodes')
+        weight, bias = weight.contiguous(), bias.contiguous()
+        if int(weight.numel()) != (2 * dim if head == 0 else dim) or int(bias.numel()) != 1:
+            raise ValueError(f'gat_attention: weight of {int(weight.numel())} / bias of {int(bias.numel())} floats for width {dim}')
+        nnz = csr.nnz
+        z = torch.empty(max(nnz, 1), dtype=torch.float32, device=h.device)
+        alpha = torch.empty_like(z)
+        alpha_mirror = torch.empty_like(z)
+        ws_bytes = int(lib.ihg_gat_workspace_bytes(n, csr.n_segments, dim, head))
+        ws = _workspace(ws_bytes, h.device)
+        with profiler.kernel('gat_scores', n, dim):
+            _lib.check(lib.ihg_gat_attention_fwd(_ptr(h), _ld(h), _ptr(csr.ptr), _ptr(csr.ids), _ptr(graph.mirror), _ptr(csr.row_order), n, dim, _ptr(weight),
+                                                 _ptr(bias), head, activation, *_gat_plan(csr), _ptr(z), _ptr(alpha), _ptr(alpha_mirror), _ptr(ws), ws_bytes,
+                                                 _stream()), 'ihg_gat_attention_fwd')
+        y = node_segment_sum_raw(h, csr, None, None, _lib.SCALE_NONE, entry_scale=alpha, role='k7.gat_aggregate', out=_check_out(out, h, weight, bias))
+        ctx.graph, ctx.head, ctx.activation = graph, head, activation
+        ctx.save_for_backward(h, weight, bias, z, alpha, alpha_mirror)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor):
+        lib = _lib.load()
+        h, weight, bias, z, alpha, alpha_mirror = ctx.saved_tensors
+        graph, head = ctx.graph, ctx.head
+        csr = graph.csr
+        dy = _rows(grad_out, 'grad_out')
+        n, dim = int(h.shape[0]), int(h.shape[1])
+        ds = torch.empty_like(z)
+        node_sums = torch.empty(n, 2, dtype=torch.float32, device=h.device)
+        ws_bytes = int(lib.ihg_gat_workspace_bytes(n, csr.n_segments, dim, head))
+        ws = _workspace(ws_bytes, h.device)
+        with profiler.kernel('gat_scores_bwd', n, dim):
+            _lib.check(lib.ihg_gat_scores_bwd(_ptr(h), _ld(h), _ptr(dy), _ld(dy), _ptr(csr.ptr), _ptr(csr.ids), _ptr(graph.mirror), _ptr(csr.row_order), n, dim,
+                                              head, ctx.activation, *_gat_plan(csr), _ptr(z), _ptr(alpha), _ptr(ds), _ptr(node_sums), _ptr(ws), ws_bytes,
+                                              _stream()), 'ihg_gat_scores_bwd')
+        # the transposed aggregation: row u gathers the cotangents of the rows its edges u -> v point to, weighted by alpha of u -> v
+        dh = node_segment_sum_raw(dy, csr, None, None, _lib.SCALE_NONE, entry_scale=alpha_mirror, role='k7.gat_aggregate_bwd')
+        b = None
+        if head == GAT_HEADS['product']:
+            sym = torch.empty_like(z)
+            with profiler.kernel('gat_symmetrize', csr.nnz, 1):
+                _lib.check(lib.ihg_gat_symmetrize(_ptr(ds), _ptr(graph.mirror), csr.nnz, _ptr(sym), _stream()), 'ihg_gat_symmetrize')
+            b = node_segment_sum_raw(h, csr, None, None, _lib.SCALE_NONE, entry_scale=sym, role='k7.gat_score_bwd')
+        dweight = torch.empty_like(weight)
+        dbias = torch.empty_like(bias)
+        with profiler.kernel('gat_finish_bwd', n, dim):
+            _lib.check(lib.ihg_gat_finish_bwd(_ptr(h), _ld(h), _ptr(b), _ld(b) if b is not None else 0, _ptr(node_sums), _ptr(weight), head, n, dim, _ptr(dh),
+                                              _ld(dh), _ptr(dweight), _ptr(dbias), _ptr(ws), ws_bytes, _stream()), 'ihg_gat_finish_bwd')
+        return dh, dweight, dbias, None, None, None, None
+
+
+def gat_attention(h: Tensor, graph, weight: Tensor, bias: Tensor, head: str = 'concatenation', activation: str = 'leaky_relu',
+                  out: Optional[Tensor] = None) -> Tensor:
+    """The attention half of ``GATLayer.forward`` (``GnnLayers.py:100-115``) over a :class:`ihgnn_amd.layout.PairLayout`: for every edge ``u -> v`` (entry ``u``
+    of CSR row ``v``) ``z = act(w_src . h[u] + w_dst . h[v] + c)`` (``head`` 'concatenation', ``weight`` = ``[w_src | w_dst]``, ``2 d`` floats) or
+    ``act(w . (h[u] * h[v]) + c)`` ('product', ``d`` floats); ``alpha`` = softmax of ``z`` over ``v``'s incoming edges; ``out[v] = sum alpha h[u]`` (a node
+    without edges: a zero row).  ``activation``: 'leaky_relu' (slope 0.01), 'relu' or 'tanh'.  ``bias``: the one-float ``c`` (read on the device)."""
+    if head not in GAT_HEADS:
+        raise ValueError(f'gat_attention: unknown head {head!r} (one of {sorted(GAT_HEADS)})')
+    if activation not in GAT_ACTIVATIONS:
+        raise ValueError(f'gat_attention: unknown activation {activation!r} (one of {sorted(GAT_ACTIVATIONS)})')
+    return _GatAttention.apply(h, weight.reshape(-1), bias.reshape(-1), graph, GAT_HEADS[head], GAT_ACTIVATIONS[activation], out)
+
+
+# ---------------------------------------------------------------------------------------------
 # K2 query embedding bag (mean)
 # ---------------------------------------------------------------------------------------------
 class BagLayout:

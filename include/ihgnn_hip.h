@@ -522,6 +522,45 @@ int ihg_hem_score_bwd_typed0(const float* const* layers, int32_t n_layers, int64
 int ihg_batch_rows_put(const float* src, int64_t ld_src, int32_t width, const int64_t* rows, const int32_t* leader, int64_t n_rows,
                        float* const* dense_rows, int64_t ld_dense, const int64_t* type_begin, int32_t assign, ihg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DEVICE: the attention of the GAT baseline over the pairwise graph (csrc/gat.hip).  Replaces GATLayer.forward after its transform
+ * (Models/GnnLayers.py:98-115: the [nnz, 2, d] row gather, feature_aggregate, dgl.ops.edge_softmax and dgl.ops.u_mul_e_sum) and autograd's backward of it.
+ * Graph: the symmetric CSR of the pairwise adjacency (ihg_build_pair_csr) - entry p of row v with column u = ids[p] is the edge u -> v, so row v lists
+ * v's incoming edges; mirror[p] is the position of the reverse edge v -> u in row u.  Split-row plan as in ihg_node_segment_sum, plus seg_row[s] = the
+ * row that segment s belongs to.  h [n_rows, dim] = feature_transform(x); weight = feature_aggregate.0.weight as a DEVICE vector ([w_src | w_dst], 2 dim
+ * floats, for IHG_GAT_CONCAT; dim floats for IHG_GAT_PRODUCT), bias = feature_aggregate.0.bias (one DEVICE float); activation as Gs.Gnn.gat_activation
+ * (Helpers/GlobalSettings.py:59-66).
+ *   ihg_gat_attention_fwd  z[p] = act(w_src . h[u] + w_dst . h[v] + c)  (concat)  |  act(w . (h[u] * h[v]) + c)  (product)
+ *                          alpha[p] = softmax of z over row v (max subtracted), alpha_mirror[mirror[p]] = alpha[p]      (all [nnz], caller-owned)
+ *                          The layer output is then ihg_node_segment_sum(h, rowptr, ids, entry_scale = alpha): out[v] = sum_p alpha[p] h[u]; an empty row is zero.
+ *   ihg_gat_scores_bwd     given dout [n_rows, dim]: ds[p] = alpha (dout[v] . h[u] - sum_row alpha (dout[v] . h[u'])) act'(z[p]) - the gradient of the
+ *                          score before the activation (torch's conventions at 0) - and node_sums [n_rows, 2]: column 1 = sum of ds over row v (v as the
+ *                          destination), column 0 (concat only) = sum of ds[mirror[q]] over row v (v as the source)
+ *   ihg_gat_symmetrize     product: ds_sym[p] = ds[p] + ds[mirror[p]]
+ *   ihg_gat_finish_bwd     dh [n_rows, dim] holds ihg_node_segment_sum(dout, entry_scale = alpha_mirror) on entry (the transposed aggregation); adds the score
+ *                          terms: node_sums[v,0] w_src + node_sums[v,1] w_dst (concat) or w * b[v] with b = ihg_node_segment_sum(h, entry_scale = ds_sym)
+ *                          (product; b unused for concat), and writes dweight (2 dim or dim floats) and dbias (1 float) as fixed-order column sums.
+ * All four calls share one workspace of ihg_gat_workspace_bytes(n_rows, n_segments, dim, head) bytes.  No float atomics (bitwise reproducible), no [nnz, dim]
+ * buffer, no synchronisation.  Any dim > 0; rows with dim % 4 == 0, 16-byte aligned, take the 16-B/lane path.
+ */
+#define IHG_GAT_CONCAT        0
+#define IHG_GAT_PRODUCT       1
+#define IHG_GAT_LEAKY_RELU    0   /* nn.LeakyReLU(), slope 0.01 */
+#define IHG_GAT_RELU          1
+#define IHG_GAT_TANH          2
+int64_t ihg_gat_workspace_bytes(int64_t n_rows, int64_t n_segments, int32_t dim, int32_t head);
+int ihg_gat_attention_fwd(const float* h, int64_t ld_h, const int32_t* rowptr, const int32_t* ids, const int32_t* mirror, const int32_t* row_order, int64_t n_rows,
+                          int32_t dim, const float* weight, const float* bias, int32_t head, int32_t activation, int32_t heavy_threshold, const int32_t* seg_begin,
+                          const int32_t* seg_end, const int32_t* seg_row, int64_t n_segments, const int32_t* heavy_rows, const int32_t* heavy_segptr, int64_t n_heavy,
+                          float* z, float* alpha, float* alpha_mirror, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+int ihg_gat_scores_bwd(const float* h, int64_t ld_h, const float* dout, int64_t ld_dout, const int32_t* rowptr, const int32_t* ids, const int32_t* mirror,
+                       const int32_t* row_order, int64_t n_rows, int32_t dim, int32_t head, int32_t activation, int32_t heavy_threshold, const int32_t* seg_begin,
+                       const int32_t* seg_end, const int32_t* seg_row, int64_t n_segments, const int32_t* heavy_rows, const int32_t* heavy_segptr, int64_t n_heavy,
+                       const float* z, const float* alpha, float* ds, float* node_sums, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+int ihg_gat_symmetrize(const float* ds, const int32_t* mirror, int64_t nnz, float* ds_sym, ihg_stream_t stream);
+int ihg_gat_finish_bwd(const float* h, int64_t ld_h, const float* b, int64_t ld_b, const float* node_sums, const float* weight, int32_t head, int64_t n_rows,
+                       int32_t dim, float* dh, int64_t ld_dh, float* dweight, float* dbias, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+
 /* Small device-side helpers that keep a training step free of framework launches (torch fills / index ops of a few microseconds each):
  *   ihg_zero_floats      p[0 .. n) = 0
  *   ihg_mark_rows        mask[rows[k]] = value, k < n (rows as int64 OR int32: pass the other NULL) - the row mask of a sparse cotangent, set before
