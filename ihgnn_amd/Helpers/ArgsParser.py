@@ -23,6 +23,8 @@ _FLAGS = (
     ('embedding_size', ('--embedding_size', '--emb'), int, 0, 'embedding width (0 = Gs.embedding_size)'),
     # not in the reference: batches (positive permutation + negative sampling) produced on the GPU instead of by DataLoader + random.sample
     ('device_sampling', ('--device_sampling',), 'flag', False, 'draw training batches on the device (same distribution, different random stream)'),
+    # not in the reference's command line: its driver hard-codes phase2_attention=False (Main.py:57)
+    ('phase2', ('--phase2',), 'flag', False, 'IHGNN layers with phase-2 attention: attention weights over a node\'s hyperedges instead of their mean (Gs.Gnn.gat_head / gat_activation)'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '

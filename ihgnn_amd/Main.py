@@ -57,6 +57,11 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     layer_type = parse_gnn_layer[args.gnn] or IHGNNLayer
     if layer_type not in (IHGNNLayer, HGCNLayer, GCNLayer, GATLayer):
         raise NotImplementedError(f'{layer_type.__name__} is outside the MI355X hypergraph path')
+    phase2 = bool(getattr(args, 'phase2', False))
+    if phase2 and layer_type is not IHGNNLayer:
+        raise ValueError(f'--phase2 is the IHGNN layer\'s phase-2 attention; --gnn {args.gnn} has none')
+    if phase2 and world > 1:
+        raise NotImplementedError('--phase2 runs in a single process: the gradient exchanges of ihgnn_amd.distributed have not been run with the attention on')
     layer_count = args.gnns or 2
     order = args.feature_order or 3
     if args.device == 'cpu':
@@ -79,7 +84,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
 
     say(f'device {device} | ranks {world} | batch {Gs.batch_size} | lr {Gs.learning_rate} | emb {Gs.embedding_size} | '
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}')
-    say(f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order} | '
+    say(f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | '
         f'query transform {Gs.Query.transform} | validation {Gs.use_valid_dataset}')
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
 
@@ -108,7 +113,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
 
     model = RawGnn(device=device, dataset=dataset_train, embedding_size=Gs.embedding_size, gnn_layer_type=layer_type,
                    gnn_layer_count=layer_count, predictions=HemPredictionLayer, lambda_muq=Gs.lambda_muq_for_hem,
-                   feature_interaction_order=order, phase2_attention=False).to(device)
+                   feature_interaction_order=order, phase2_attention=phase2).to(device)
     loss_function = nn.BCEWithLogitsLoss().to(device)
     from .optim import Adam
     grad_sync = None

@@ -4,7 +4,8 @@ Constructor signatures, sub-module names (``feature_transform``, ``feature_inter
 absence of any non-linearity follow the reference; the sparse work runs in the HIP kernels of
 libihgnn_hip.so through :mod:`ihgnn_amd.ops` instead of ``torch_sparse.matmul``.
 ``GCNLayer`` (pairwise-graph baseline) runs on the same segment-sum kernel over a weighted CSR; ``GATLayer`` (the attention
-baseline) adds the score and softmax kernels of csrc/gat.hip in front of it.
+baseline) adds the score and softmax kernels of csrc/gat.hip in front of it, and ``IHGNNLayer(phase2_attention=True)`` those of csrc/phase2.hip
+(the same attention over the node <- hyperedge incidence).
 """
 from typing import Optional
 
@@ -83,34 +84,41 @@ class HGCNLayer(nn.Module):
 
 
 class IHGNNLayer(nn.Module):
-    """``Y = Dv^-1 H Interact(X W^T + b)``  (``GnnLayers.py:221-236``, phase-2 attention off)."""
+    """``Y = Dv^-1 H Interact(X W^T + b)``  (``GnnLayers.py:221-236``); with ``phase2_attention`` the mean over a node's hyperedges gives way to attention
+    weights: ``Y[v] = sum over e containing v of alpha(e, v) Ef'[e]`` (``GnnLayers.py:200-216, 227-230``, :class:`_Phase2Attention`)."""
 
     def __init__(self, device: torch.device, dataset, input_dimension: int, output_dimension: int,
                  feature_interaction_order: int, phase2_attention: bool):
         super().__init__()
         if feature_interaction_order not in (1, 2, 3):
             raise AssertionError('feature interaction order must be 1, 2 or 3')
-        if phase2_attention:
-            raise NotImplementedError('phase-2 attention (DGL edge-softmax branch, GnnLayers.py:200-216) is outside '
-                                      'the MI355X hypergraph path; the reference driver hard-codes it off (Main.py:57)')
         self.device = device
         self.dataset = dataset
         self.feature_interaction_order = feature_interaction_order
-        self.attention_phase2 = False
+        self.attention_phase2 = bool(phase2_attention)
         self.layout = dataset.hypergraph.layout
+        # construction order as in the reference (interactor, fake_gat, feature_transform): a seeded layer draws its weights
         self.feature_interactor = FeatureInteractor(dataset=dataset, max_order=feature_interaction_order,
                                                     node_feature_dimension=input_dimension,
                                                     output_dimension=input_dimension)
+        if self.attention_phase2:
+            self.fake_gat = _Phase2Attention(output_dimension)
         self.feature_transform = nn.Linear(input_dimension, output_dimension)
 
     def reads_cotangent_rows_only(self) -> bool:
-        """First-order layers run the two-hop operator, whose backward under ``output_rows`` / ``cotangent_rows`` is the masked pull."""
-        return self.feature_interaction_order == 1
+        """First-order layers run the two-hop operator, whose backward under ``output_rows`` / ``cotangent_rows`` is the masked pull; the attention's backward
+        reads every row of its cotangent."""
+        return self.feature_interaction_order == 1 and not self.attention_phase2
 
     def forward(self, input_features: Tensor, output_rows: Optional[Tensor] = None, cotangent_rows: Optional[Tensor] = None,
                 out: Optional[Tensor] = None) -> Tensor:
-        """``output_rows`` / ``cotangent_rows`` / ``out``: as in ``HGCNLayer.forward``."""
+        """``output_rows`` / ``cotangent_rows`` / ``out``: as in ``HGCNLayer.forward`` (with ``phase2_attention`` every row is computed: ``output_rows`` only
+        permits leaving the others unwritten)."""
         _check_rows(input_features, self.layout)
+        if self.attention_phase2:
+            # the hyperedge rows exist here ([E, d]): both row sets go through fake_gat's transform, then the attention - one autograd node behind the transform
+            h = _transform(self.feature_transform, input_features, self.layout)
+            return self.fake_gat(h, self.feature_interactor, self.layout, out=out)
         if self.feature_interaction_order == 1:
             # first-order layer: hoisted node-level blocks, then node -> hyperedge -> node fused into one two-hop pass
             return ops.node_two_hop(self._first_order_of_input(input_features), self.layout, out_scale=self.layout.inv_deg, rows=output_rows,
@@ -156,6 +164,56 @@ class GCNLayer(nn.Module):
 _GAT_ACTIVATIONS = {'leaky_relu': nn.LeakyReLU, 'relu': nn.ReLU, 'tanh': nn.Tanh}
 
 
+def _attention_settings(who: str):
+    """``(head, activation class, activation name)`` from ``Gs.Gnn``, refused unless the kernels have them."""
+    from ..Helpers.GlobalSettings import Gs
+    head = Gs.Gnn.gat_head
+    act_type, act_name = Gs.Gnn.gat_activation
+    if head not in (Gsv.concat, Gsv.product):
+        raise ValueError(f'{who}: unknown head {head!r} (Gsv.concat or Gsv.product)')
+    if _GAT_ACTIVATIONS.get(act_name) is not act_type:
+        raise ValueError(f'{who}: activation {act_name!r} / {act_type} is not one of {sorted(_GAT_ACTIVATIONS)} with its nn class')
+    return head, act_type, act_name
+
+
+def _feature_aggregate(dimension: int, head: str, act_type, act_name: str) -> nn.Sequential:
+    """``feature_aggregate`` of ``GATLayer.__init__`` (``GnnLayers.py:65-84``): Linear to one score, its weight re-drawn by ``xavier_uniform_`` with the activation's gain."""
+    linear = nn.Linear(2 * dimension if head == Gsv.concat else dimension, 1)
+    nn.init.xavier_uniform_(linear.weight, gain=nn.init.calculate_gain(act_name))
+    return nn.Sequential(linear, act_type())
+
+
+def _attention_weight(w: Tensor, d: int, head: str, wide: int) -> Tensor:
+    """``feature_aggregate.0.weight`` as the kernel's vector at the width the features run at: each half of a concatenation weight zero-padded on its own."""
+    if wide == d:
+        return w
+    if head == Gsv.concat:
+        return ops.pad_columns(w.view(2, d), wide).reshape(1, 2 * wide)
+    return ops.pad_vector(w, wide)
+
+
+class _Phase2Attention(nn.Module):
+    """``IHGNNLayer.fake_gat``: the reference builds a ``GATLayer`` over a "fake" graph of ``N + E`` vertices whose edges run hyperedge -> member node
+    (``GnnLayers.py:200-216``) and feeds it ``cat([h, Ef])``.  Same parameters and state-dict keys (``feature_aggregate.0.*``, ``feature_transform.*``) drawn in the same
+    order; the forward keeps the two row sets apart: ``feature_transform`` - the SAME Linear - on each, then the attention of csrc/phase2.hip + K7 over the
+    layout's node-major CSR (``ops.phase2_layer``: interactor, transform and ``ops.hyper_attention``'s kernels as one autograd node).  No ``[N + E, d]`` concatenation, no ``[3 E, 2, d]`` rows.  Kept: ``Ef`` and ``Ef'``, ``2 E d`` floats per layer."""
+
+    def __init__(self, dimension: int):
+        super().__init__()
+        self.dimension = dimension
+        self.head, act_type, self.activation = _attention_settings('IHGNNLayer(phase2_attention=True)')
+        self.feature_aggregate = _feature_aggregate(dimension, self.head, act_type, self.activation)
+        self.feature_transform = nn.Linear(dimension, dimension)
+
+    def forward(self, node_features: Tensor, interactor: FeatureInteractor, layout, out: Optional[Tensor] = None) -> Tensor:
+        """``node_features``: the layer's ``feature_transform(x)``; ``interactor``: the layer's, whose hyperedge rows are formed inside the op."""
+        wide = _row_width(node_features)
+        lin, agg = self.feature_transform, self.feature_aggregate[0]
+        agg_w, agg_b = interactor._operands(node_features)
+        return ops.phase2_layer(node_features, agg_w, agg_b, ops.pad_square(lin.weight, wide), ops.pad_vector(lin.bias, wide),
+                                _attention_weight(agg.weight, self.dimension, self.head, wide), agg.bias, layout, interactor.max_order, self.head, self.activation, out=out)
+
+
 class GATLayer(nn.Module):
     """Single-head attention over the pairwise graph (``GnnLayers.py:48-115``): ``h = X W^T + b``, for every edge ``u -> v`` a score
     ``act(w . [h_u | h_v] + c)`` (head ``Gs.Gnn.gat_head`` = concatenation) or ``act(w . (h_u * h_v) + c)`` (product), a softmax over ``v``'s incoming
@@ -167,33 +225,18 @@ class GATLayer(nn.Module):
 
     def __init__(self, device: torch.device, dataset, input_dimension: int, output_dimension: int):
         super().__init__()
-        from ..Helpers.GlobalSettings import Gs
         self.device = device
         self.dataset = dataset
         self.input_dimension = input_dimension
         self.output_dimension = output_dimension
         self.graph = dataset.graph2d.layout
-        head = Gs.Gnn.gat_head
-        act_type, act_name = Gs.Gnn.gat_activation
-        if head not in (Gsv.concat, Gsv.product):
-            raise ValueError(f'GATLayer: unknown head {head!r} (Gsv.concat or Gsv.product)')
-        if _GAT_ACTIVATIONS.get(act_name) is not act_type:
-            raise ValueError(f'GATLayer: activation {act_name!r} / {act_type} is not one of {sorted(_GAT_ACTIVATIONS)} with its nn class')
-        self.head, self.activation = head, act_name
-        feature_aggregate = nn.Linear(2 * output_dimension if head == Gsv.concat else output_dimension, 1)
-        nn.init.xavier_uniform_(feature_aggregate.weight, gain=nn.init.calculate_gain(act_name))
-        self.feature_aggregate = nn.Sequential(feature_aggregate, act_type())
+        self.head, act_type, self.activation = _attention_settings('GATLayer')
+        self.feature_aggregate = _feature_aggregate(output_dimension, self.head, act_type, self.activation)
         self.feature_transform = nn.Linear(input_dimension, output_dimension)
 
     def _attention_weight(self, wide: int) -> Tensor:
         """``feature_aggregate.0.weight`` as the kernel's vector at the width the features run at: each half of a concatenation weight zero-padded on its own."""
-        w = self.feature_aggregate[0].weight
-        d = self.output_dimension
-        if wide == d:
-            return w
-        if self.head == Gsv.concat:
-            return ops.pad_columns(w.view(2, d), wide).reshape(1, 2 * wide)
-        return ops.pad_vector(w, wide)
+        return _attention_weight(self.feature_aggregate[0].weight, self.output_dimension, self.head, wide)
 
     def forward(self, input_features, out: Optional[Tensor] = None) -> Tensor:
         """``input_features``: ``[N, d]`` (or ``ops.NodeTables``); ``out`` (inference only): the ``[N, d]`` destination, e.g. a column slice of the feature matrix."""

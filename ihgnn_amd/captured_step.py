@@ -24,6 +24,9 @@ class CapturedTrainingStep:
     def __init__(self, model, optimizer: Adam, batch_rows: int, warmup_batch=None):
         if not isinstance(optimizer, Adam):
             raise TypeError('CapturedTrainingStep records ihgnn_amd.optim.Adam')
+        if any(getattr(layer, 'attention_phase2', False) for layer in getattr(model, 'gnns', ())):
+            # (a ValueError: the training loop then goes on eagerly with one log line, TrainTestHelper.train_and_get_avg_loss)
+            raise ValueError('CapturedTrainingStep: a model with phase-2 attention is not recorded (its step has not been replayed against the eager one)')
         self.model, self.optimizer, self.batch_rows = model, optimizer, int(batch_rows)
         dev = next(model.parameters()).device
         self.users = torch.zeros(batch_rows, dtype=torch.int64, device=dev)

@@ -10,95 +10,9 @@
 // Rows longer than the split-row threshold are cut into the segments of the K7 plan: every per-row reduction (max and denominator of the softmax,
 // the sum of alpha d alpha, the row sums of ds) is formed per segment and merged per row in a fixed tree by one workgroup - no float atomics,
 // bitwise-identical results run to run.  No [nnz, d] tensor, no host synchronisation.
-#include "common.hpp"
+#include "attention.hpp"
 
 namespace {
-
-constexpr int kScalarLanes = 16;          // lanes per work unit of the scalar passes (four units per wave)
-constexpr int kParamRows = 512;           // node rows per workgroup of the parameter-gradient column sums
-
-__device__ __forceinline__ float gat_act(float x, int act) {
-    if (act == IHG_GAT_LEAKY_RELU) return x > 0.f ? x : 0.01f * x;           // nn.LeakyReLU() (slope 0.01)
-    if (act == IHG_GAT_RELU) return x > 0.f ? x : 0.f;
-    return tanhf(x);
-}
-
-// derivative from the OUTPUT, as torch takes it: leaky_relu_backward (x > 0 ? 1 : slope, so slope at 0), threshold_backward (y <= 0 -> 0), tanh_backward (1 - y^2)
-__device__ __forceinline__ float gat_act_grad(float y, int act) {
-    if (act == IHG_GAT_LEAKY_RELU) return y > 0.f ? 1.f : 0.01f;
-    if (act == IHG_GAT_RELU) return y > 0.f ? 1.f : 0.f;
-    return 1.f - y * y;
-}
-
-__device__ __forceinline__ float frag_dot(const Frag<4>& a, const Frag<4>& b) { return ((a.v.x * b.v.x + a.v.y * b.v.y) + a.v.z * b.v.z) + a.v.w * b.v.w; }
-__device__ __forceinline__ float frag_dot(const Frag<1>& a, const Frag<1>& b) { return a.v * b.v; }
-__device__ __forceinline__ Frag<4> frag_mul(const Frag<4>& a, const Frag<4>& b) { return {make_float4(a.v.x * b.v.x, a.v.y * b.v.y, a.v.z * b.v.z, a.v.w * b.v.w)}; }
-__device__ __forceinline__ Frag<1> frag_mul(const Frag<1>& a, const Frag<1>& b) { return {a.v * b.v}; }
-
-// butterfly over the G lanes of a group: every lane ends with the same bits (each step adds the same two values in either order)
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-template <int G>
-__device__ __forceinline__ int wave_max_len(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o >= G; o >>= 1) {
-        const int other = __shfl_xor(v, o);
-        v = other > v ? other : v;
-    }
-    return v;
-}
-
-// The work list of K7 (aggregate.hip): first the segments of the split rows, then the light rows in `row_order`.
-struct Plan {
-    const int32_t* rowptr;
-    const int32_t* ids;
-    const int32_t* mirror;
-    const int32_t* row_order;
-    int64_t n_rows;
-    int heavy_threshold;
-    const int32_t* seg_begin;
-    const int32_t* seg_end;
-    const int32_t* seg_row;
-    int64_t n_segments;
-    const int32_t* heavy_rows;
-    const int32_t* heavy_segptr;
-    int64_t n_heavy;
-};
-
-// seg >= 0: a segment of a split row (its partial goes to slot seg; row = the owner).  seg < 0: a whole light row; row < 0 with len 0: nothing
-// (past the end, or a split row met in the row list - its segments cover it)
-struct Unit {
-    int begin, len;
-    int64_t row, seg;
-};
-
-__device__ __forceinline__ Unit unit_at(const Plan& pl, int64_t u) {
-    Unit r{0, 0, -1, -1};
-    if (u < pl.n_segments) {
-        r.begin = pl.seg_begin[u];
-        r.len = pl.seg_end[u] - r.begin;
-        r.row = pl.seg_row[u];
-        r.seg = u;
-    } else if (u < pl.n_segments + pl.n_rows) {
-        int64_t v = u - pl.n_segments;
-        if (pl.row_order != nullptr) v = pl.row_order[v];
-        r.begin = pl.rowptr[v];
-        r.len = pl.rowptr[v + 1] - r.begin;
-        if (pl.heavy_threshold > 0 && r.len > pl.heavy_threshold) r.len = 0;
-        else r.row = v;
-    }
-    return r;
-}
 
 // ------------------------------------------------------------------------------------------------
 // concat head: s[v] = (h[v] . w_src, h[v] . w_dst) once per node (GnnLayers.py:104, 111: w . [h_u | h_v] splits into two node terms)
@@ -125,69 +39,6 @@ __global__ __launch_bounds__(kBlockThreads) void gat_project_kernel(const float*
         if (r < n_rows && lig == 0) {
             s[2 * r] = a;
             s[2 * r + 1] = b;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Row gather-dot: out[p] = act(bias + sum_k a[k] x[v][k] y[ids[p]][k]) for every entry p of row v (a NULL: ones; act < 0: neither activation nor bias).
-//   product scores (GnnLayers.py:107, 111: x = y = h, a = w) and d alpha (x = dout, y = h).  G lanes per unit hold x[v] * a in registers,
-//   eight neighbour rows in flight per lane, one butterfly per entry; lane j of the group keeps entry j of each chunk of G entries.
-// ------------------------------------------------------------------------------------------------
-template <int VEC, int G>
-__global__ __launch_bounds__(kBlockThreads) void gat_row_dot_kernel(const float* __restrict__ x, int64_t ld_x, const float* __restrict__ a,
-                                                                    const float* __restrict__ y, int64_t ld_y, const float* __restrict__ bias, int act,
-                                                                    Plan pl, int dim_vec, float* __restrict__ out) {
-    constexpr int GPW = kWave / G;
-    constexpr int UNR = G < 8 ? G : 8;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lig = lane & (G - 1);
-    const int grp = lane / G;
-    const int group_base = lane & ~(G - 1);
-    const int64_t n_units = pl.n_segments + pl.n_rows;
-    const float c0 = (act >= 0 && bias != nullptr) ? bias[0] : 0.f;
-    for (int64_t u0 = global_wave_id() * GPW; u0 < n_units; u0 += global_wave_count() * GPW) {
-        const Unit un = unit_at(pl, u0 + grp);
-        const int wave_len = wave_max_len<G>(un.len);
-        Frag<VEC> xa = Frag<VEC>::zero();
-        if (un.len > 0 && lig < dim_vec) {
-            xa = Frag<VEC>::load(x + un.row * ld_x + lig * VEC);
-            if (a != nullptr) xa = frag_mul(xa, Frag<VEC>::load(a + lig * VEC));
-        }
-        for (int base = 0; base < wave_len; base += G) {
-            const bool have = base + lig < un.len;
-            const int my_id = have ? pl.ids[un.begin + base + lig] : -1;
-            float mine = 0.f;
-#pragma unroll 1
-            for (int j = 0; j < G; j += UNR) {
-                if (base + j >= wave_len) break;                         // wave-uniform
-                int id[UNR];
-                Frag<VEC> row[UNR];
-                float d[UNR];
-#pragma unroll
-                for (int k = 0; k < UNR; ++k) id[k] = __shfl(my_id, group_base + j + k);
-#pragma unroll
-                for (int k = 0; k < UNR; ++k)
-                    row[k] = (id[k] >= 0 && lig < dim_vec) ? Frag<VEC>::load(y + static_cast<int64_t>(id[k]) * ld_y + lig * VEC) : Frag<VEC>::zero();
-#pragma unroll
-                for (int k = 0; k < UNR; ++k) d[k] = frag_dot(xa, row[k]);
-                if (un.len > 0) {
-                    // widths beyond one pass of the group (above 256, or above 64 on the 4-byte path): the further column chunks
-                    for (int c = lig + G; c < dim_vec; c += G) {
-                        Frag<VEC> xc = Frag<VEC>::load(x + un.row * ld_x + c * VEC);
-                        if (a != nullptr) xc = frag_mul(xc, Frag<VEC>::load(a + c * VEC));
-#pragma unroll
-                        for (int k = 0; k < UNR; ++k)
-                            if (id[k] >= 0) d[k] += frag_dot(xc, Frag<VEC>::load(y + static_cast<int64_t>(id[k]) * ld_y + c * VEC));
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < UNR; ++k) {
-                    const float t = group_sum<G>(d[k]);
-                    if (lig == j + k) mine = t;
-                }
-            }
-            if (have) out[un.begin + base + lig] = act >= 0 ? gat_act(mine + c0, act) : mine;
         }
     }
 }
@@ -239,26 +90,6 @@ __global__ __launch_bounds__(kBlockThreads) void gat_softmax_kernel(const float*
     }
 }
 
-__device__ __forceinline__ void merge_max_sum(float& m, float& l, float m2, float l2) {
-    if (m2 == -__builtin_huge_valf()) return;
-    const float mx = fmaxf(m, m2);
-    l = l * expf(m - mx) + l2 * expf(m2 - mx);
-    m = mx;
-}
-
-// block-wide sum in a fixed tree (thread order); every thread gets the result
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kBlockThreads / 2; o > 0; o >>= 1) {
-        if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const float total = red[0];
-    __syncthreads();
-    return total;
-}
-
 // One workgroup per split row: merge its segments' (max, sum) in a fixed tree, then write alpha over the row's entries.
 __global__ __launch_bounds__(kBlockThreads) void gat_softmax_finish_kernel(Plan pl, const float* __restrict__ z, const float* __restrict__ partials,
                                                                            float* __restrict__ alpha, float* __restrict__ alpha_mirror) {
@@ -288,80 +119,6 @@ __global__ __launch_bounds__(kBlockThreads) void gat_softmax_finish_kernel(Plan 
             alpha[p] = al;
             alpha_mirror[pl.mirror[p]] = al;
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Softmax backward: g holds d alpha on entry and ds (the gradient of the score BEFORE the activation) on return:
-//   ds[p] = alpha[p] (g[p] - c_v) act'(z[p]),  c_v = sum over row v of alpha g.   node_sums[2 v + 1] = sum over row v of ds (v as the destination).
-// Two things keep the row's cancellation out of the result:
-//   * g is taken relative to the row's first entry g0:  g - c_v = (g - g0) - sum alpha (g - g0).  Where a row's d alpha are nearly equal (smooth features),
-//     c_v formed from the raw values carries eps |c_v| of rounding, far more than the spread g - c_v that ds is made of.
-//   * with t = alpha (g - c_v), sum t = 0 (alpha sums to one), so  sum t a = - sum t (1 - a)  (a = act'): the row sum takes the form whose alpha-mass is smaller -
-//     exactly 0 for a row whose scores all have a = 1 (or all a = 0), as in exact arithmetic, instead of eps sum |t| of noise in the input gradient and d c.
-// ------------------------------------------------------------------------------------------------
-struct RowBwd {
-    float ma, mb, sa, sb;                 // sum alpha a, sum alpha (1 - a), sum t a, sum t (1 - a)
-    __device__ float row_sum() const { return mb < ma ? -sb : sa; }
-};
-
-__device__ __forceinline__ void ds_entry(const float* __restrict__ z, const float* __restrict__ alpha, float* __restrict__ g, int act, int p, float g0, float c,
-                                         RowBwd& r) {
-    const float a = gat_act_grad(z[p], act);
-    const float al = alpha[p];
-    const float t = al * ((g[p] - g0) - c);
-    g[p] = t * a;
-    r.ma += al * a;
-    r.mb += al * (1.f - a);
-    r.sa += t * a;
-    r.sb += t * (1.f - a);
-}
-
-__global__ __launch_bounds__(kBlockThreads) void gat_softmax_bwd_kernel(const float* __restrict__ z, const float* __restrict__ alpha, float* __restrict__ g, int act,
-                                                                        Plan pl, float* __restrict__ node_sums, float* __restrict__ partials) {
-    constexpr int G = kScalarLanes, GPW = kWave / G;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lig = lane & (G - 1);
-    const int grp = lane / G;
-    const int64_t n_units = pl.n_segments + pl.n_rows;
-    for (int64_t u0 = global_wave_id() * GPW; u0 < n_units; u0 += global_wave_count() * GPW) {
-        const Unit un = unit_at(pl, u0 + grp);
-        const float g0 = un.len > 0 ? g[pl.rowptr[un.row]] : 0.f;      // (read by every lane before any lane of this row writes)
-        float c = 0.f;
-        for (int i = lig; i < un.len; i += G) c += alpha[un.begin + i] * (g[un.begin + i] - g0);
-        c = group_sum<G>(c);
-        RowBwd r{0.f, 0.f, 0.f, 0.f};
-        if (un.seg < 0 && un.row >= 0)
-            for (int i = lig; i < un.len; i += G) ds_entry(z, alpha, g, act, un.begin + i, g0, c, r);
-        r.ma = group_sum<G>(r.ma);
-        r.mb = group_sum<G>(r.mb);
-        r.sa = group_sum<G>(r.sa);
-        r.sb = group_sum<G>(r.sb);
-        if (lig == 0) {
-            if (un.seg >= 0) partials[un.seg] = c;
-            else if (un.row >= 0) node_sums[2 * un.row + 1] = r.row_sum();
-        }
-    }
-}
-
-__global__ __launch_bounds__(kBlockThreads) void gat_softmax_bwd_finish_kernel(const float* __restrict__ z, const float* __restrict__ alpha, float* __restrict__ g, int act,
-                                                                               Plan pl, float* __restrict__ node_sums, const float* __restrict__ partials) {
-    __shared__ float red[kBlockThreads];
-    const int t = threadIdx.x;
-    for (int64_t hr = blockIdx.x; hr < pl.n_heavy; hr += gridDim.x) {
-        const int64_t row = pl.heavy_rows[hr];
-        const float g0 = g[pl.rowptr[row]];                                 // (block_sum's barriers order this read before the writes below)
-        const int s0 = pl.heavy_segptr[hr], s1 = pl.heavy_segptr[hr + 1];
-        float c = 0.f;
-        for (int sg = s0 + t; sg < s1; sg += kBlockThreads) c += partials[sg];
-        c = block_sum(c, red);
-        RowBwd r{0.f, 0.f, 0.f, 0.f};
-        for (int p = pl.rowptr[row] + t; p < pl.rowptr[row + 1]; p += kBlockThreads) ds_entry(z, alpha, g, act, p, g0, c, r);
-        r.ma = block_sum(r.ma, red);
-        r.mb = block_sum(r.mb, red);
-        r.sa = block_sum(r.sa, red);
-        r.sb = block_sum(r.sb, red);
-        if (t == 0) node_sums[2 * row + 1] = r.row_sum();
     }
 }
 
@@ -457,44 +214,6 @@ __global__ __launch_bounds__(kBlockThreads) void gat_param_finish_kernel(const f
     else dweight[c] = acc * weight_factor;
 }
 
-// Smallest power of two >= n, clamped to [4, 64] (K7's lane groups).
-inline int gat_group_lanes(int n) {
-    int g = 4;
-    while (g < n && g < kWave) g <<= 1;
-    return g;
-}
-
-inline int gat_grid(int64_t waves) {
-    int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks < 1) blocks = 1;
-    if (blocks > kMaxBlocks * 4) blocks = kMaxBlocks * 4;
-    return static_cast<int>(blocks);
-}
-
-inline int flat_grid(int64_t n) {
-    const int64_t blocks = (n + kBlockThreads - 1) / kBlockThreads;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(blocks, kMaxBlocks * 4)));
-}
-
-inline int heavy_grid(int64_t n_heavy) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(n_heavy, kMaxBlocks * 4))); }
-
-template <int VEC>
-void launch_row_dot(const float* x, int64_t ld_x, const float* a, const float* y, int64_t ld_y, const float* bias, int act, const Plan& pl, int dim,
-                    float* out, hipStream_t s) {
-    const int dim_vec = dim / VEC;
-#define IHG_GAT_DOT(G)                                                                                                                          \
-    hipLaunchKernelGGL((gat_row_dot_kernel<VEC, G>), dim3(gat_grid((pl.n_segments + pl.n_rows + kWave / G - 1) / (kWave / G))), dim3(kBlockThreads), 0, s, \
-                       x, ld_x, a, y, ld_y, bias, act, pl, dim_vec, out)
-    switch (gat_group_lanes(dim_vec)) {
-        case 4: IHG_GAT_DOT(4); break;
-        case 8: IHG_GAT_DOT(8); break;
-        case 16: IHG_GAT_DOT(16); break;
-        case 32: IHG_GAT_DOT(32); break;
-        default: IHG_GAT_DOT(64); break;
-    }
-#undef IHG_GAT_DOT
-}
-
 template <int VEC>
 void launch_project(const float* h, int64_t ld_h, const float* w, int dim, int64_t n_rows, float* s, hipStream_t st) {
     const int dim_vec = dim / VEC;
@@ -508,34 +227,6 @@ void launch_project(const float* h, int64_t ld_h, const float* w, int dim, int64
         default: IHG_GAT_PROJ(64); break;
     }
 #undef IHG_GAT_PROJ
-}
-
-int64_t param_blocks(int64_t n_rows) { return std::max<int64_t>(1, (n_rows + kParamRows - 1) / kParamRows); }
-
-int check_plan(const char* what, const Plan& pl, int32_t head, int32_t activation, int32_t dim) {
-    if (pl.n_rows < 0 || dim <= 0 || pl.n_segments < 0 || pl.n_heavy < 0) return fail(IHG_ERR_INVALID, "%s: bad size (rows=%lld dim=%d)", what, (long long)pl.n_rows, dim);
-    if (head != IHG_GAT_CONCAT && head != IHG_GAT_PRODUCT) return fail(IHG_ERR_INVALID, "%s: unknown head %d", what, head);
-    if (activation != IHG_GAT_LEAKY_RELU && activation != IHG_GAT_RELU && activation != IHG_GAT_TANH) return fail(IHG_ERR_INVALID, "%s: unknown activation %d", what, activation);
-    if (pl.n_rows > 0 && (pl.rowptr == nullptr || pl.ids == nullptr || pl.mirror == nullptr)) return fail(IHG_ERR_INVALID, "%s: null graph pointer", what);
-    if (pl.n_heavy > 0 && (pl.heavy_threshold <= 0 || pl.seg_begin == nullptr || pl.seg_end == nullptr || pl.seg_row == nullptr || pl.heavy_rows == nullptr ||
-                           pl.heavy_segptr == nullptr))
-        return fail(IHG_ERR_INVALID, "%s: incomplete split-row plan", what);
-    return IHG_OK;
-}
-
-Plan make_plan(const int32_t* rowptr, const int32_t* ids, const int32_t* mirror, const int32_t* row_order, int64_t n_rows, int32_t heavy_threshold,
-               const int32_t* seg_begin, const int32_t* seg_end, const int32_t* seg_row, int64_t n_segments, const int32_t* heavy_rows,
-               const int32_t* heavy_segptr, int64_t n_heavy) {
-    Plan pl{rowptr, ids, mirror, row_order, n_rows, heavy_threshold, seg_begin, seg_end, seg_row, n_segments, heavy_rows, heavy_segptr, n_heavy};
-    if (n_heavy == 0) {
-        pl.n_segments = 0;
-        pl.heavy_threshold = 0;
-    }
-    return pl;
-}
-
-bool vec4_ok(int32_t dim, int64_t ld_a, const void* a, int64_t ld_b, const void* b, const float* w) {
-    return dim % 4 == 0 && ld_a % 4 == 0 && aligned16(a) && (b == nullptr || (ld_b % 4 == 0 && aligned16(b))) && aligned16(w);
 }
 
 }  // namespace

@@ -10,6 +10,9 @@ edge_gather_sum  (K5)  ihg_edge_gather_sum         ihg_node_segment_sum   (its t
 node_segment_sum (K7)  ihg_node_segment_sum         ihg_edge_gather_sum    (its transpose)
 bag_mean         (K2)  ihg_bag_mean_fwd            ihg_bag_mean_bwd
 interact     (K5+K6)   ihg_interact_fwd            ihg_interact_bwd + 4x ihg_node_segment_sum
+gat_attention          ihg_gat_attention_fwd + K7  ihg_gat_scores_bwd, K7, ihg_gat_finish_bwd
+hyper_attention        ihg_phase2_attention_fwd    ihg_phase2_scores_bwd, ihg_phase2_edges_bwd, (K7,) ihg_phase2_finish_bwd
+                       + K7
 """
 from __future__ import annotations
 
@@ -419,6 +422,198 @@ def gat_attention(h: Tensor, graph, weight: Tensor, bias: Tensor, head: str = 'c
 
 
 # ---------------------------------------------------------------------------------------------
+# Phase-2 attention of IHGNNLayer over the node <- hyperedge incidence (csrc/phase2.hip + K7)
+# ---------------------------------------------------------------------------------------------
+def _phase2_forward_raw(h2: Tensor, ef2: Tensor, weight: Tensor, bias: Tensor, layout: IncidenceLayout, head: int, activation: int, out: Optional[Tensor]):
+    """``(y, z, alpha, alpha_edge)``: scores and softmax (``ihg_phase2_attention_fwd``), then K7 over ``ef2`` with ``entry_scale = alpha``."""
+    lib = _lib.load()
+    csr = layout.node_csr
+    n, e, dim = int(h2.shape[0]), int(ef2.shape[0]), int(h2.shape[1])
+    if n != layout.node_count or e != layout.edge_count or int(ef2.shape[1]) != dim:
+        raise ValueError(f'hyper_attention: h2 {tuple(h2.shape)} / ef2 {tuple(ef2.shape)} for a layout of {layout.node_count} nodes and {layout.edge_count} hyperedges')
+    if int(weight.numel()) != (2 * dim if head == 0 else dim) or int(bias.numel()) != 1:
+        raise ValueError(f'hyper_attention: weight of {int(weight.numel())} / bias of {int(bias.numel())} floats for width {dim}')
+    z = torch.empty(max(3 * e, 1), dtype=torch.float32, device=h2.device)
+    alpha = torch.empty_like(z)
+    alpha_edge = torch.empty_like(z)
+    ws_bytes = int(lib.ihg_phase2_workspace_bytes(n, e, csr.n_segments, dim, head))
+    ws = _workspace(ws_bytes, h2.device)
+    with profiler.kernel('phase2_scores', n, dim):
+        _lib.check(lib.ihg_phase2_attention_fwd(_ptr(h2), _ld(h2), _ptr(ef2), _ld(ef2), _ptr(csr.ptr), _ptr(csr.ids), _ptr(layout.member_csr.ids), _ptr(csr.row_order),
+                                                n, e, dim, _ptr(weight), _ptr(bias), _ptr(layout.edge_weight), head, activation, *_gat_plan(csr), _ptr(z), _ptr(alpha),
+                                                _ptr(alpha_edge), _ptr(ws), ws_bytes, _stream()), 'ihg_phase2_attention_fwd')
+    # (alpha carries the multiplicity of a hyperedge kept once: no src_scale)
+    y = node_segment_sum_raw(ef2, csr, None, None, _lib.SCALE_NONE, entry_scale=alpha, role='k7.phase2_aggregate', out=out)
+    return y, z, alpha, alpha_edge
+
+
+def _phase2_backward_raw(h2: Tensor, ef2: Tensor, weight: Tensor, z: Tensor, alpha: Tensor, alpha_edge: Tensor, dy: Tensor, layout: IncidenceLayout,
+                         head: int, activation: int):
+    """``(d h2, d ef2, d weight, d bias)`` from ``dy``: ``ihg_phase2_scores_bwd``, the edge-major ``ihg_phase2_edges_bwd`` for the hyperedge rows (product head: K7 over
+    ``ef2`` with ``ds`` for the node rows), ``ihg_phase2_finish_bwd``."""
+    lib = _lib.load()
+    csr = layout.node_csr
+    n, e, dim = int(h2.shape[0]), int(ef2.shape[0]), int(h2.shape[1])
+    ds = torch.empty_like(z)
+    ds_edge = torch.empty_like(z)
+    node_sums = torch.empty(n, 2, dtype=torch.float32, device=h2.device)
+    ws_bytes = int(lib.ihg_phase2_workspace_bytes(n, e, csr.n_segments, dim, head))
+    ws = _workspace(ws_bytes, h2.device)
+    with profiler.kernel('phase2_scores_bwd', n, dim):
+        _lib.check(lib.ihg_phase2_scores_bwd(_ptr(ef2), _ld(ef2), _ptr(dy), _ld(dy), _ptr(csr.ptr), _ptr(csr.ids), _ptr(layout.member_csr.ids), _ptr(csr.row_order),
+                                             n, e, dim, head, activation, *_gat_plan(csr), _ptr(z), _ptr(alpha), _ptr(ds), _ptr(ds_edge), _ptr(node_sums),
+                                             _ptr(ws), ws_bytes, _stream()), 'ihg_phase2_scores_bwd')
+    def2 = torch.empty(e, dim, dtype=torch.float32, device=h2.device)
+    with profiler.kernel('phase2_edges_bwd', e, dim):
+        _lib.check(lib.ihg_phase2_edges_bwd(_ptr(dy), _ld(dy), _ptr(h2), _ld(h2), _ptr(layout.i3), _ptr(alpha_edge), _ptr(ds_edge), _ptr(weight), head, e, dim,
+                                            _ptr(def2), _ld(def2), _stream()), 'ihg_phase2_edges_bwd')
+    b = None
+    if head == GAT_HEADS['product']:
+        b = node_segment_sum_raw(ef2, csr, None, None, _lib.SCALE_NONE, entry_scale=ds, role='k7.phase2_score_bwd')
+    dh2 = torch.empty(n, dim, dtype=torch.float32, device=h2.device)
+    dweight = torch.empty_like(weight)
+    dbias = torch.empty(1, dtype=torch.float32, device=h2.device)
+    with profiler.kernel('phase2_finish_bwd', n, dim):
+        _lib.check(lib.ihg_phase2_finish_bwd(_ptr(h2), _ld(h2), _ptr(ef2), _ld(ef2), _ptr(b), _ld(b) if b is not None else 0, _ptr(node_sums), _ptr(ds_edge),
+                                             _ptr(weight), head, n, e, dim, _ptr(dh2), _ld(dh2), _ptr(dweight), _ptr(dbias), _ptr(ws), ws_bytes, _stream()),
+                   'ihg_phase2_finish_bwd')
+    return dh2, def2, dweight, dbias
+
+
+class _HyperAttention(torch.autograd.Function):
+    """``out[v] = sum over v's hyperedges e of softmax_v(act(score(e, v))) ef2[e]`` (``GnnLayers.py:227-230`` through ``GATLayer.forward``); saved: ``z``, ``alpha``,
+    ``alpha_edge`` (and the operands)."""
+
+    @staticmethod
+    def forward(ctx, h2: Tensor, ef2: Tensor, weight: Tensor, bias: Tensor, layout: IncidenceLayout, head: int, activation: int, out: Optional[Tensor]) -> Tensor:
+        h2, ef2 = _rows(h2, 'h2'), _rows(ef2, 'ef2')
+        weight, bias = weight.contiguous(), bias.contiguous()
+        y, z, alpha, alpha_edge = _phase2_forward_raw(h2, ef2, weight, bias, layout, head, activation, _check_out(out, h2, ef2, weight, bias))
+        ctx.layout, ctx.head, ctx.activation = layout, head, activation
+        ctx.save_for_backward(h2, ef2, weight, z, alpha, alpha_edge)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor):
+        h2, ef2, weight, z, alpha, alpha_edge = ctx.saved_tensors
+        dh2, def2, dweight, dbias = _phase2_backward_raw(h2, ef2, weight, z, alpha, alpha_edge, _rows(grad_out, 'grad_out'), ctx.layout, ctx.head, ctx.activation)
+        return dh2, def2, dweight, dbias, None, None, None, None
+
+
+def _plain_type_begin(n_rows: int):
+    """Type boundaries of a table whose rows have no node types: every row is of the first type."""
+    return (ctypes.c_int64 * 4)(0, n_rows, n_rows, n_rows)
+
+
+def _linear_rows(x: Tensor, w: Tensor, bias: Optional[Tensor], type_begin) -> Tensor:
+    """``x @ w.T + bias`` on every row (``ihg_node_linear_fwd``, one weight for all rows)."""
+    lib = _lib.load()
+    dim = int(x.shape[1])
+    out = torch.empty(x.shape[0], dim, dtype=torch.float32, device=x.device)
+    ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), x.device)
+    with profiler.kernel('node_linear_fwd', x.shape[0], dim):
+        _lib.check(lib.ihg_node_linear_fwd(_ptr(x), _ld(x), _ptr(w), int(w.stride(0)), 0, _ptr(bias), 0b111, 0, type_begin, _ptr(out), _ld(out), _ptr(ws), ws.numel() * 4,
+                                           dim, _stream()), 'ihg_node_linear_fwd')
+    return out
+
+
+def _linear_rows_backward(g: Tensor, x: Tensor, w: Tensor, type_begin, has_bias: bool):
+    """``(d x, d w, d bias)`` of ``_linear_rows`` from ``g`` (``ihg_node_linear_bwd_weight``: weight, bias and input gradient in one call)."""
+    lib = _lib.load()
+    dim = int(x.shape[1])
+    dx, dw = torch.empty_like(x), torch.empty_like(w)
+    dbias = torch.empty(dim, dtype=torch.float32, device=x.device) if has_bias else None
+    ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), x.device)
+    with profiler.kernel('node_linear_bwd', x.shape[0], dim):
+        _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(g), _ld(g), _ptr(x), _ld(x), type_begin, _ptr(dw), int(dw.stride(0)), 0, _ptr(dbias), 0b111, 0,
+                                                  _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx), 0, _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
+    return dx, dw, dbias
+
+
+def _add_rows(dst: Tensor, src: Tensor) -> None:
+    """``dst += src`` over ``[rows, d]`` (``ihg_phase2_add_rows``)."""
+    _lib.check(_lib.load().ihg_phase2_add_rows(_ptr(dst), _ld(dst), _ptr(src), _ld(src), int(dst.shape[0]), int(dst.shape[1]), _stream()), 'ihg_phase2_add_rows')
+
+
+class _Phase2Layer(torch.autograd.Function):
+    """The whole IHGNN layer with phase-2 attention behind ``feature_transform`` as ONE autograd node (``CommonLayers.py:58-87`` + ``GnnLayers.py:227-230``): hoisted
+    first-order blocks -> hyperedge rows ``ef`` (K5 at order 1, ``ihg_interact_fwd`` above) -> ``fake_gat.feature_transform`` on the node rows and on the hyperedge
+    rows -> attention.  Backward: the attention's, the transform's on both row sets, the interactor's; the gradients that two of these passes share (the
+    transform's parameters, the node features) are added by the library (``ihg_phase2_add_rows`` / the row GEMM's accumulating epilogue), so a step launches
+    library kernels only.  Kept for the backward: ``ef`` and ``ef2`` (``2 E d`` floats), ``h2``, ``z`` / ``alpha`` / ``alpha_edge`` (``9 E`` floats)."""
+
+    @staticmethod
+    def forward(ctx, h: Tensor, agg_w: Tensor, agg_b: Optional[Tensor], wg: Tensor, bg: Tensor, weight: Tensor, bias: Tensor, layout: IncidenceLayout, order: int,
+                head: int, activation: int, out: Optional[Tensor]) -> Tensor:
+        h, agg_w, wg = _rows(h, 'h'), _rows(agg_w, 'aggregation weight'), _rows(wg, 'transform weight')
+        weight, bias, bg = weight.contiguous(), bias.contiguous(), bg.contiguous()
+        _check_out(out, h, agg_w, agg_b, wg, bg, weight, bias)
+        p = _first_order_rows(h, agg_w, agg_b, layout)
+        ef = edge_gather_sum_raw(p, layout.i3) if order == 1 else _interact_rows(h, p, agg_w, layout, order)
+        del p
+        h2 = _linear_rows(h, wg, bg, _type_begin(layout))
+        ef2 = _linear_rows(ef, wg, bg, _plain_type_begin(layout.edge_count))
+        y, z, alpha, alpha_edge = _phase2_forward_raw(h2, ef2, weight, bias, layout, head, activation, out)
+        ctx.layout, ctx.order, ctx.head, ctx.activation, ctx.has_bias = layout, order, head, activation, agg_b is not None
+        ctx.save_for_backward(h, agg_w, wg, weight, ef, h2, ef2, z, alpha, alpha_edge)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        h, agg_w, wg, weight, ef, h2, ef2, z, alpha, alpha_edge = ctx.saved_tensors
+        layout, order = ctx.layout, ctx.order
+        dh2, def2, dweight, dbias = _phase2_backward_raw(h2, ef2, weight, z, alpha, alpha_edge, _rows(dy, 'dy'), layout, ctx.head, ctx.activation)
+        # fake_gat.feature_transform, hyperedge rows: def is the cotangent of the layout's rows (a row kept once: already the sum over its copies)
+        d_ef, dwg, dbg = _linear_rows_backward(def2, ef, wg, _plain_type_begin(layout.edge_count), True)
+        del def2
+        dagg_w = torch.empty_like(agg_w)                       # product blocks from the interact kernels, first-order blocks from the row-GEMM pass
+        if order == 1:
+            dh = None
+            dp = node_segment_sum_raw(d_ef, layout.node_csr, role='k7.edges_to_nodes_bwd_of_k5')
+        else:
+            dp = node_segment_sum_raw(d_ef, layout.node_csr, role='k7.first_order_gradient')
+            dh = _interact_backward(h, agg_w, d_ef, layout, order, dagg_w)
+        del d_ef
+        # ... node rows
+        dh_nodes, dwg_nodes, dbg_nodes = _linear_rows_backward(dh2, h, wg, _type_begin(layout), True)
+        if dh is None:
+            dh = dh_nodes
+        else:
+            _add_rows(dh, dh_nodes)
+        _add_rows(dwg, dwg_nodes)
+        _add_rows(dbg.view(1, -1), dbg_nodes.view(1, -1))
+        dagg_b = _first_order_backward(dp, h, agg_w, layout, dagg_w, dh, ctx.has_bias)
+        return dh, dagg_w, dagg_b, dwg, dbg, dweight, dbias, None, None, None, None, None
+
+
+def phase2_layer(h: Tensor, agg_w: Tensor, agg_b: Optional[Tensor], wg: Tensor, bg: Tensor, weight: Tensor, bias: Tensor, layout: IncidenceLayout, order: int,
+                 head: str = 'concatenation', activation: str = 'leaky_relu', out: Optional[Tensor] = None) -> Tensor:
+    """``hyper_attention(rows_linear(h; wg, bg), rows_linear(FeatureInteractor(h; agg_w, agg_b); wg, bg), ...)`` as one differentiable op: what
+    ``IHGNNLayer(phase2_attention=True)`` runs behind its ``feature_transform``.  All operands at the width of ``h`` (``pad_blocks`` / ``pad_square`` / ...)."""
+    if head not in GAT_HEADS:
+        raise ValueError(f'phase2_layer: unknown head {head!r} (one of {sorted(GAT_HEADS)})')
+    if activation not in GAT_ACTIVATIONS:
+        raise ValueError(f'phase2_layer: unknown activation {activation!r} (one of {sorted(GAT_ACTIVATIONS)})')
+    if order not in (1, 2, 3):
+        raise ValueError('phase2_layer: interaction order 1, 2 or 3')
+    return _Phase2Layer.apply(h, agg_w, agg_b, wg, bg, weight.reshape(-1), bias.reshape(-1), layout, int(order), GAT_HEADS[head], GAT_ACTIVATIONS[activation], out)
+
+
+def hyper_attention(h2: Tensor, ef2: Tensor, layout: IncidenceLayout, weight: Tensor, bias: Tensor, head: str = 'concatenation', activation: str = 'leaky_relu',
+                    out: Optional[Tensor] = None) -> Tensor:
+    """The attention half of ``IHGNNLayer.forward`` with ``phase2_attention`` (``GnnLayers.py:227-230`` through ``GATLayer.forward``, lines 100-115) over an
+    :class:`ihgnn_amd.layout.IncidenceLayout`: ``h2 [N, d]`` and ``ef2 [E, d]`` are the node and hyperedge features after ``fake_gat.feature_transform``; for every
+    incidence (``e`` contains ``v``) ``z = act(w_src . ef2[e] + w_dst . h2[v] + c)`` (``head`` 'concatenation', ``weight`` = ``[w_src | w_dst]``: the hyperedge is the
+    edge's source) or ``act(w . (ef2[e] * h2[v]) + c)`` ('product'); ``alpha`` = softmax of ``z`` over ``v``'s hyperedges - every copy of a hyperedge that the layout
+    keeps once (``layout.edge_weight``) counted; ``out[v] = sum alpha ef2[e]`` (a node in no hyperedge: a zero row).  ``activation`` / ``bias``: as ``gat_attention``."""
+    if head not in GAT_HEADS:
+        raise ValueError(f'hyper_attention: unknown head {head!r} (one of {sorted(GAT_HEADS)})')
+    if activation not in GAT_ACTIVATIONS:
+        raise ValueError(f'hyper_attention: unknown activation {activation!r} (one of {sorted(GAT_ACTIVATIONS)})')
+    return _HyperAttention.apply(h2, ef2, weight.reshape(-1), bias.reshape(-1), layout, GAT_HEADS[head], GAT_ACTIVATIONS[activation], out)
+
+
+# ---------------------------------------------------------------------------------------------
 # K2 query embedding bag (mean)
 # ---------------------------------------------------------------------------------------------
 class BagLayout:
@@ -810,6 +1005,19 @@ def node_linear(x, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, t
         out, _token, _rows_q = _LinearFromTables.apply(x.user_table, x.item_table, x.word_table, w, bias, x, layout, bool(typed), int(bias_mask))
         return out
     return _NodeLinear.apply(x, w, bias, layout, bool(typed), int(bias_mask))
+
+
+class _PlainRows:
+    """What ``_NodeLinear`` asks of a layout, for a table whose rows have no node types (every row is of the first type)."""
+
+    def __init__(self, n_rows: int):
+        self._type_begin_c = _plain_type_begin(int(n_rows))
+
+
+def rows_linear(x: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """``out[r] = x[r] @ w.T (+ bias)`` for every row of ANY ``[rows, d]`` table (``w`` square) on the same row-GEMM kernels as ``node_linear`` - which takes its type
+    boundaries from a layout's node counts; this is for tables that are not node tables: the ``[E, d]`` hyperedge features of the phase-2 attention."""
+    return _NodeLinear.apply(x, w, bias, _PlainRows(int(x.shape[0])), False, 0b111)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -561,6 +561,44 @@ int ihg_gat_symmetrize(const float* ds, const int32_t* mirror, int64_t nnz, floa
 int ihg_gat_finish_bwd(const float* h, int64_t ld_h, const float* b, int64_t ld_b, const float* node_sums, const float* weight, int32_t head, int64_t n_rows,
                        int32_t dim, float* dh, int64_t ld_dh, float* dweight, float* dbias, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DEVICE: the phase-2 attention of IHGNNLayer (csrc/phase2.hip).  Replaces fake_gat's forward after its transform (Models/GnnLayers.py:200-216, 227-230:
+ * GATLayer.forward over the graph whose edges run hyperedge -> member node) and autograd's backward of it.
+ * Graph: the layout's node-major CSR (ihg_build_csr) - entry p of row v with e = ids[p] is the edge e -> v, so row v lists v's hyperedges; pos[p] = 3 e + type(v)
+ * is the entry's slot in an edge-major [n_edges, 3] table (a permutation of [0, 3 n_edges)); split-row plan and seg_row as in ihg_gat_attention_fwd.
+ * h [n_rows, dim] and ef [n_edges, dim]: the node and hyperedge features after fake_gat.feature_transform; weight / bias / head / activation as in
+ * ihg_gat_attention_fwd (concat: [w_src | w_dst], w_src meets ef, w_dst meets h).  edge_weight [n_edges] or NULL: the multiplicity m_e of a hyperedge kept once.
+ *   ihg_phase2_attention_fwd  z[p] = act(w_src . ef[e] + w_dst . h[v] + c)  (concat)  |  act(w . (ef[e] * h[v]) + c)  (product)
+ *                             alpha[p] = m_e exp(z[p] - max) / sum over row v of m exp(z - max),  alpha_edge[pos[p]] = alpha[p]      (all [3 n_edges], caller-owned)
+ *                             The layer output is then ihg_node_segment_sum(ef, rowptr, ids, entry_scale = alpha); an empty row is zero.
+ *   ihg_phase2_scores_bwd     given dout [n_rows, dim]: ds[p] = alpha (dout[v] . ef[e] - sum_row alpha (dout[v] . ef[e'])) act'(z[p]), ds_edge[pos[p]] = ds[p],
+ *                             node_sums [n_rows, 2]: column 1 = sum of ds over row v (column 0 is not written)
+ *   ihg_phase2_edges_bwd      edge-major, one [n_edges, dim] store: def[e] = sum_k alpha_edge[e, k] dout[i3[e, k]] + (sum_k ds_edge[e, k]) w_src  (concat)
+ *                             | + w * sum_k ds_edge[e, k] h[i3[e, k]]  (product)
+ *   ihg_phase2_finish_bwd     dh[v] = node_sums[v, 1] w_dst (concat) or w * b[v] with b = ihg_node_segment_sum(ef, entry_scale = ds) (product; b unused for
+ *                             concat, ef and ds_edge unused for product); dweight (2 dim or dim floats) and dbias (1 float) as fixed-order column sums.
+ *   ihg_phase2_add_rows       dst[r] += src[r] over [n_rows, dim] rows: the second contribution to a gradient that two passes of the layer's backward form
+ * The calls share one workspace of ihg_phase2_workspace_bytes(...) bytes.  No float atomics (bitwise reproducible), no [3 n_edges, dim] buffer, no
+ * synchronisation.  Any dim > 0; rows with dim % 4 == 0, 16-byte aligned, take the 16-B/lane path.
+ */
+int64_t ihg_phase2_workspace_bytes(int64_t n_rows, int64_t n_edges, int64_t n_segments, int32_t dim, int32_t head);
+int ihg_phase2_attention_fwd(const float* h, int64_t ld_h, const float* ef, int64_t ld_ef, const int32_t* rowptr, const int32_t* ids, const int32_t* pos,
+                             const int32_t* row_order, int64_t n_rows, int64_t n_edges, int32_t dim, const float* weight, const float* bias,
+                             const float* edge_weight, int32_t head, int32_t activation, int32_t heavy_threshold, const int32_t* seg_begin, const int32_t* seg_end,
+                             const int32_t* seg_row, int64_t n_segments, const int32_t* heavy_rows, const int32_t* heavy_segptr, int64_t n_heavy, float* z,
+                             float* alpha, float* alpha_edge, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+int ihg_phase2_scores_bwd(const float* ef, int64_t ld_ef, const float* dout, int64_t ld_dout, const int32_t* rowptr, const int32_t* ids, const int32_t* pos,
+                          const int32_t* row_order, int64_t n_rows, int64_t n_edges, int32_t dim, int32_t head, int32_t activation, int32_t heavy_threshold,
+                          const int32_t* seg_begin, const int32_t* seg_end, const int32_t* seg_row, int64_t n_segments, const int32_t* heavy_rows,
+                          const int32_t* heavy_segptr, int64_t n_heavy, const float* z, const float* alpha, float* ds, float* ds_edge, float* node_sums,
+                          void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+int ihg_phase2_edges_bwd(const float* dout, int64_t ld_dout, const float* h, int64_t ld_h, const int32_t* i3, const float* alpha_edge, const float* ds_edge,
+                         const float* weight, int32_t head, int64_t n_edges, int32_t dim, float* def, int64_t ld_def, ihg_stream_t stream);
+int ihg_phase2_finish_bwd(const float* h, int64_t ld_h, const float* ef, int64_t ld_ef, const float* b, int64_t ld_b, const float* node_sums, const float* ds_edge,
+                          const float* weight, int32_t head, int64_t n_rows, int64_t n_edges, int32_t dim, float* dh, int64_t ld_dh, float* dweight, float* dbias,
+                          void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+int ihg_phase2_add_rows(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, int64_t n_rows, int32_t dim, ihg_stream_t stream);
+
 /* Small device-side helpers that keep a training step free of framework launches (torch fills / index ops of a few microseconds each):
  *   ihg_zero_floats      p[0 .. n) = 0
  *   ihg_mark_rows        mask[rows[k]] = value, k < n (rows as int64 OR int32: pass the other NULL) - the row mask of a sparse cotangent, set before

@@ -1,0 +1,674 @@
+"""GPU: the phase-2 attention of IHGNNLayer (csrc/phase2.hip + K7, ``ops.hyper_attention``, ``IHGNNLayer(phase2_attention=True)``) against the reference
+(fixture F12, tests/golden/make_golden_phase2.py: the reference run with its ``_FakeDataset`` patched so that the branch can be constructed) and against a float64
+restatement of ``GnnLayers.py:221-230`` + ``GATLayer.forward`` kept in this file.
+
+Bars: RTOL = 1e-5 of the tensor's largest magnitude (DESIGN section 5's contract, ``tests/test_gat_layer.py``).  The cancelling sums - the score bias's gradient
+``dc = sum_p ds[p]`` and the destination half of a concatenation weight's gradient ``dw_dst = sum_p ds[p] h'[v]`` (ds sums to rounding noise inside every row
+whose scores share the activation's slope) - are held to RTOL of the sum of the magnitudes of their terms, as ``test_gat_attention_matches_float64`` holds ``dc``.
+Per-row comparisons skip rows whose reference magnitude is at most 1e-3 of the largest row's, and assert that this leaves out at most 5 % of the non-isolated rows."""
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+from conftest import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-5
+ROW_RTOL = 1e-5
+HEADS = {'concat': 'concatenation', 'product': 'product'}
+ACTIVATIONS = {'leaky_relu': (nn.LeakyReLU, 'leaky_relu'), 'relu': (nn.ReLU, 'relu'), 'tanh': (nn.Tanh, 'tanh')}
+AGG_W, AGG_B = 'fake_gat.feature_aggregate.0.weight', 'fake_gat.feature_aggregate.0.bias'
+
+
+def dev():
+    return torch.device('cuda:0')
+
+
+def as64(a):
+    return a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
+
+
+def rel(a, b):
+    a, b = as64(a), as64(b)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+def row_rel(a, b, live, floor=1e-3, name=''):
+    """Largest per-row relative error over the rows of ``b`` (the reference) above ``floor`` of its largest row; ``live``: the non-isolated rows, of which the
+    floor may leave out at most 5 %."""
+    a, b = as64(a), as64(b)
+    a, b = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
+    mag = np.abs(b).max(1)
+    keep = mag > floor * max(mag.max(), 1e-30)
+    live = np.asarray(live, bool)
+    skipped = int((live & ~keep).sum())
+    assert skipped <= 0.05 * max(int(live.sum()), 1), (name, skipped, int(live.sum()))
+    keep &= live
+    if not keep.any():
+        return 0.0
+    return float((np.abs(a - b).max(1)[keep] / mag[keep]).max())
+
+
+class settings:
+    def __init__(self, head=None, activation=None):
+        self.new = (head, activation)
+
+    def __enter__(self):
+        from ihgnn_amd.Helpers.GlobalSettings import Gs
+        self.old = (Gs.Gnn.gat_head, Gs.Gnn.gat_activation)
+        head, act = self.new
+        if head is not None:
+            Gs.Gnn.gat_head = head
+        if act is not None:
+            Gs.Gnn.gat_activation = act
+
+    def __exit__(self, *exc):
+        from ihgnn_amd.Helpers.GlobalSettings import Gs
+        Gs.Gnn.gat_head, Gs.Gnn.gat_activation = self.old
+
+
+def gs_head(head):
+    from ihgnn_amd.Helpers.GlobalSettings import Gsv
+    return {'concat': Gsv.concat, 'product': Gsv.product, 'concatenation': Gsv.concat}[head]
+
+
+# ---------------------------------------------------------------------------------------------
+# the float64 restatement
+# ---------------------------------------------------------------------------------------------
+_ACT64 = {'leaky_relu': lambda t: torch.nn.functional.leaky_relu(t, 0.01), 'relu': torch.relu, 'tanh': torch.tanh}
+
+
+def attention64(h2, ef2, w, c, lay, head, act):
+    """float64 restatement of GATLayer.forward (GnnLayers.py:100-115) after its transform, over the incidence: entry p of node row v with e = ids[p] is the edge
+    e -> v.  A hyperedge the layout keeps once stands for m_e copies with identical scores: log m_e on the logit."""
+    n, d = h2.shape
+    ptr = torch.as_tensor(lay.node_csr.ptr_host.astype(np.int64))
+    src = torch.as_tensor(lay.node_csr.ids_host.astype(np.int64))
+    dst = torch.repeat_interleave(torch.arange(n), torch.diff(ptr))
+    w = w.reshape(-1)
+    if head == 'concatenation':
+        pre = ef2[src] @ w[:d] + h2[dst] @ w[d:] + c.reshape(())
+    else:
+        pre = (ef2[src] * h2[dst]) @ w + c.reshape(())
+    if pre.requires_grad:
+        pre.retain_grad()
+    logit = _ACT64[act](pre)
+    if lay.edge_weight_host is not None:
+        logit = logit + torch.log(torch.as_tensor(lay.edge_weight_host.astype(np.float64))).to(logit.dtype)[src]
+    top = torch.full((n,), -float('inf'), dtype=logit.dtype).scatter_reduce(0, dst, logit.detach(), 'amax', include_self=True)
+    e = torch.exp(logit - top[dst])
+    den = torch.zeros(n, dtype=logit.dtype).index_add(0, dst, e)
+    alpha = e / den[dst]
+    attention64.kept = (pre, h2, dst, ef2, src)                          # (the scores before the activation: their gradient sizes the cancelling sums)
+    return torch.zeros(n, d, dtype=h2.dtype).index_add(0, dst, alpha[:, None] * ef2[src]), alpha
+
+
+class Scales:
+    """The magnitudes of the terms of the sums over the scores' gradients ds (which cancel inside every node row: sum over a row of alpha (d alpha - c) = 0, times
+    one slope): ``dc`` = sum_p |ds[p]|, ``dst[k]`` = sum_p |ds[p]| |h'[v_p, k]|, ``src[k]`` = sum_p |ds[p]| |Ef'[e_p, k]|."""
+
+    def __init__(self, kept=None):
+        if kept is None:
+            self.dc, self.dst, self.src = 0.0, None, None
+            return
+        pre, h2, dst, ef2, src = kept
+        ds = pre.grad.abs().double()
+        self.dc = float(ds.sum())
+        self.dst = (ds[:, None] * h2.detach().double()[dst].abs()).sum(0).numpy()
+        self.src = (ds[:, None] * ef2.detach().double()[src].abs()).sum(0).numpy()
+
+
+def cancelling_scales():
+    """After a backward through ``attention64``."""
+    return Scales(attention64.kept)
+
+
+def interactor64(h, A, a, i3, order):
+    """FeatureInteractor.forward (CommonLayers.py:58-87): blocks u, q, i, uq, qi, iu, uqi."""
+    i3 = torch.as_tensor(np.asarray(i3, np.int64))
+    u, q, i = h[i3[:, 0]], h[i3[:, 1]], h[i3[:, 2]]
+    blocks = [u, q, i]
+    if order >= 2:
+        blocks += [u * q, q * i, i * u]
+    if order == 3:
+        blocks += [u * q * i]
+    return torch.cat(blocks, 1) @ A.t() + a
+
+
+def layer64(x, sd, lay, order, head, act):
+    """IHGNNLayer.forward with the attention on (GnnLayers.py:221-230); ``sd``: the layer's state dict as float64 tensors."""
+    h = x @ sd['feature_transform.weight'].t() + sd['feature_transform.bias']
+    ef = interactor64(h, sd['feature_interactor.aggregation.weight'], sd['feature_interactor.aggregation.bias'], lay.i3_host, order)
+    Wg, bg = sd['fake_gat.feature_transform.weight'], sd['fake_gat.feature_transform.bias']
+    return attention64(h @ Wg.t() + bg, ef @ Wg.t() + bg, sd[AGG_W], sd[AGG_B], lay, head, act)[0]
+
+
+def check_parameter(name, got, want, head, d, scales, where='', src_bar=RTOL):
+    """A parameter gradient at RTOL of its largest magnitude; dc and the w_dst half of a concatenation weight at RTOL of the sum of their terms' magnitudes.
+    ``src_bar``: the bar of a concatenation weight's w_src half where a caller has measured that the reference's own fp32 arithmetic misses RTOL there."""
+    got, want = as64(got), as64(want)
+    if name.endswith(AGG_B):
+        assert abs(float(got.reshape(-1)[0]) - float(want.reshape(-1)[0])) <= RTOL * max(scales.dc, 1e-30), (where, name, got, want, scales.dc)
+        return
+    if name.endswith(AGG_W) and head == 'concatenation':
+        got, want = got.reshape(-1), want.reshape(-1)
+        assert rel(got[:d], want[:d]) <= src_bar, (where, name, 'w_src', rel(got[:d], want[:d]))
+        if src_bar > RTOL:
+            # ... then dw_src = sum_p ds[p] Ef'[e_p] is itself a cancelling sum (the hyperedge rows of a node's list are nearly alike and ds sums to nothing
+            # over the list): like dw_dst, RTOL of the sum of its terms' magnitudes
+            assert np.abs(got[:d] - want[:d]).max() <= RTOL * scales.src[:d].max(), (where, name, 'w_src terms', np.abs(got[:d] - want[:d]).max() / scales.src[:d].max())
+        err = np.abs(got[d:] - want[d:])
+        assert (err <= RTOL * np.maximum(scales.dst[:d], 1e-30)).all(), (where, name, 'w_dst', float((err / np.maximum(scales.dst[:d], 1e-30)).max()))
+        return
+    assert rel(got, want) <= RTOL, (where, name, rel(got, want))
+
+
+def live_rows(lay):
+    return np.diff(lay.node_csr.ptr_host.astype(np.int64)) > 0
+
+
+# ---------------------------------------------------------------------------------------------
+# F12: against the (patched) reference
+# ---------------------------------------------------------------------------------------------
+F12_CASES = [('tiny_o1_d8_concat_leaky', 'tiny', 8, 1, 'concat', 'leaky_relu'), ('tiny_o2_d8_product_tanh', 'tiny', 8, 2, 'product', 'tanh'),
+             ('tiny_o3_d32_product_leaky', 'tiny', 32, 3, 'product', 'leaky_relu'), ('tiny_o1_d64_product_leaky', 'tiny', 64, 1, 'product', 'leaky_relu'),
+             ('tiny_o1_d64_concat_tanh', 'tiny', 64, 1, 'concat', 'tanh'), ('small_o3_d32_concat_leaky', 'small', 32, 3, 'concat', 'leaky_relu'),
+             ('small_o2_d32_product_relu', 'small', 32, 2, 'product', 'relu'), ('small_o3_d8_concat_tanh', 'small', 8, 3, 'concat', 'tanh'),
+             ('small_o1_d8_product_leaky', 'small', 8, 1, 'product', 'leaky_relu'), ('small_o2_d8_concat_relu', 'small', 8, 2, 'concat', 'relu'),
+             ('small_o2_d8_concat_leaky', 'small', 8, 2, 'concat', 'leaky_relu')]
+
+
+def f12_dataset(which):
+    from ihgnn_amd.Dataset import GraphDataset
+    from ihgnn_amd.Helpers.Graph import PpsHyperGraph
+    if which == 'tiny':
+        d = os.path.join(GOLDEN, 'f1_data')
+        return GraphDataset(os.path.join(d, 'graph_info.txt'), os.path.join(d, 'queries_multihot.txt'), os.path.join(d, 'train_data.csv'), PpsHyperGraph, 10, 0, dev())
+    w = np.load(os.path.join(GOLDEN, 'f2_small_workload.npz'))
+    U, Q, I, V = (int(x) for x in w['counts'])
+    return GraphDataset.from_arrays(U, Q, I, V, w['bag_words'], w['bag_offsets'], w['triples'], graph_type=PpsHyperGraph, device=dev())
+
+
+def test_f12_covers_what_it_should():
+    z = np.load(os.path.join(GOLDEN, 'f12_phase2.npz'))
+    assert {c[0] for c in F12_CASES} == {k[:-len('.has_grad')] for k in z.files if k.endswith('.has_grad')}
+    assert {c[3] for c in F12_CASES} == {1, 2, 3} and {c[2] for c in F12_CASES} == {8, 32, 64}
+    assert {(c[4], c[5]) for c in F12_CASES} >= {(h, a) for h in ('concat', 'product') for a in ('leaky_relu', 'tanh')} | {('concat', 'relu'), ('product', 'relu')}
+    for tag, _, _, _, _, act in F12_CASES:
+        assert int(z[f'{tag}.has_grad']) == (1 if act == 'leaky_relu' else 0), tag      # the reference's in-place squeeze (GnnLayers.py:111)
+
+
+@pytest.mark.parametrize('tag,which,d,order,head,act', F12_CASES)
+def test_f12_phase2_layer_matches_reference(tag, which, d, order, head, act):
+    """y, dx and every parameter gradient of the layer against the reference's.  Under ReLU / Tanh the reference's in-place squeeze (GnnLayers.py:111) leaves it
+    without a backward: there the gradients are held against the float64 restatement, which is first held to the reference's forward at 1e-6."""
+    from ihgnn_amd.Models import IHGNNLayer
+    z = np.load(os.path.join(GOLDEN, 'f12_phase2.npz'))
+    with settings(gs_head(head), ACTIVATIONS[act]):
+        ds = f12_dataset(which)
+        layer = IHGNNLayer(dev(), ds, d, d, order, True)
+    layer.load_state_dict({k[len(tag) + 4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f'{tag}.sd.')})
+    layer.to(dev())
+    x = torch.from_numpy(z[f'{tag}.x']).to(dev()).requires_grad_(True)
+    y = layer(x)
+    cot = torch.from_numpy(z[f'{tag}.cot'])
+    y.backward(cot.to(dev()))
+    lay = layer.layout
+    live = live_rows(lay)
+    # the restatement: the reference's forward, and the sizes of the cancelling sums' terms
+    sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in layer.state_dict().items()}
+    x64 = torch.from_numpy(z[f'{tag}.x']).double().requires_grad_(True)
+    y64 = layer64(x64, sd, lay, order, HEADS[head], act)
+    assert rel(y64, z[f'{tag}.y']) <= 1e-6
+    y64.backward(cot.double())
+    scales = cancelling_scales()
+    has_grad = bool(int(z[f'{tag}.has_grad']))
+    want_dx = z[f'{tag}.dx'] if has_grad else x64.grad
+    print(f'{tag}: y {rel(y, z[f"{tag}.y"]):.2e} dx {rel(x.grad, want_dx):.2e}')
+    assert rel(y, z[f'{tag}.y']) <= RTOL
+    assert row_rel(y, z[f'{tag}.y'], live, name='y') <= ROW_RTOL
+    assert float(y.detach()[torch.from_numpy(~live).to(dev())].abs().sum()) == 0.0
+    assert rel(x.grad, want_dx) <= RTOL
+    assert row_rel(x.grad, want_dx, live, name='dx') <= ROW_RTOL
+    for name, p in layer.named_parameters():
+        want = z[f'{tag}.grad.{name}'] if has_grad else sd[name].grad
+        print(f'   {name}: {rel(p.grad, want):.2e}')
+        check_parameter(name, p.grad, want, HEADS[head], d, scales, tag)
+
+
+def test_f12_phase2_model_matches_reference():
+    """RawGnn with two IHGNN layers (order 3, then 1), attention on: scores, loss and every gradient against the reference's."""
+    from ihgnn_amd.Models import HemPredictionLayer, IHGNNLayer, RawGnn
+    z = np.load(os.path.join(GOLDEN, 'f12_phase2.npz'))
+    ds = f12_dataset('small')
+    m = RawGnn(dev(), ds, 16, IHGNNLayer, 2, 3, True, HemPredictionLayer, 0.5).to(dev())
+    sd = {k[len('model.sd.'):]: torch.from_numpy(z[k]) for k in z.files if k.startswith('model.sd.')}
+    assert set(sd) == set(m.state_dict())
+    m.load_state_dict(sd)
+    u, q, i = (torch.from_numpy(z[f'model.{k}']).to(dev()) for k in 'uqi')
+    scores = m(u, q, i)
+    loss = torch.nn.BCEWithLogitsLoss()(scores, torch.from_numpy(z['model.flags']).to(dev()))
+    loss.backward()
+    assert rel(scores, z['model.scores']) <= RTOL and abs(loss.item() - float(z['model.loss'])) <= 1e-6
+    # the terms of the cancelling sums, layer by layer, from the float64 model
+    scales = model_scales64(m, ds, u, q, i, torch.from_numpy(z['model.flags']))
+    for name, p in m.named_parameters():
+        assert p.grad is not None, name
+        want = z[f'model.grad.{name}']
+        g64 = model_scales64.grads.get(name)
+        print(f'model {name}: {rel(p.grad, want):.2e}' + ('' if g64 is None else f' | reference against float64 {rel(want, g64):.2e}, this against float64 {rel(p.grad, g64):.2e}'))
+        if name.endswith(AGG_W):
+            print(f'   w_src half: reference against float64 {rel(want.reshape(-1)[:16], g64.reshape(-1)[:16]):.2e}, this against float64 '
+                  f'{rel(p.grad.reshape(-1)[:16], g64.reshape(-1)[:16]):.2e}')
+        # gnn_1's w_src half (the last layer: a cotangent on the batch rows only, hyperedge rows nearly alike): the reference's own fp32 gradient is 1.25e-5 from
+        # float64 (measured: this path 2.6e-6), so against the reference the bar is 4 x 1.25e-5; against float64 it stays RTOL
+        layer_scales = scales.get(name.split('.')[0], Scales())
+        check_parameter(name, p.grad, want, 'concatenation', 16, layer_scales, 'model', src_bar=4 * 1.25e-5 if name.startswith('gnn_1.') else RTOL)
+        if g64 is not None:
+            check_parameter(name, p.grad, g64, 'concatenation', 16, layer_scales, 'model, float64')
+
+
+def model_scales64(m, ds, u, q, i, flags, dtype=torch.float64):
+    """{'gnn_l': Scales} of a RawGnn with attention on, from its float64 restatement (embeddings -> layers -> HEM over the batch rows); the
+    restatement's gradients are left in ``model_scales64.grads``.  ``dtype=torch.float32``: the same statements in fp32 on the CPU - the reference's arithmetic."""
+    sd = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in m.state_dict().items()}
+    x0 = m.embeddings.all_nodes().detach().cpu().to(dtype).requires_grad_(True)
+    feats, kept = [x0], []
+    for l, layer in enumerate(m.gnns):
+        p = f'gnn_{l}.'
+        feats.append(layer64(feats[-1], {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}, layer.layout, layer.feature_interaction_order,
+                             layer.fake_gat.head, layer.fake_gat.activation))
+        kept.append(attention64.kept)
+    f = torch.cat(feats, 1)
+    uu, qq, ii = u.cpu(), q.cpu() + ds.query_start_index_in_graph, i.cpu() + ds.item_start_index_in_graph
+    lam = m.prediction_layer.lambda_muq
+    s = ((lam * f[qq] + (1 - lam) * f[uu]) * f[ii]).sum(1) + sd['prediction_layer.items_bias'][i.cpu()]
+    torch.nn.BCEWithLogitsLoss()(s, flags.cpu().to(dtype)).backward()
+    out = {f'gnn_{l}': Scales(k) for l, k in enumerate(kept)}
+    model_scales64.grads = {k: v.grad for k, v in sd.items()}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# against the float64 restatement: widths, split rows, multiplicities, compact numbering, edge cases
+# ---------------------------------------------------------------------------------------------
+def hyper_layout(seed=5, U=300, Q=40, I=200, E=3000, heavy_threshold=None, isolated=0, repeat=False, **kw):
+    from ihgnn_amd import synth
+    from ihgnn_amd.layout import IncidenceLayout
+    triples = synth.draw(U, Q, I, 10, E, seed=seed, distribution='powerlaw', exponent=1.1).triples
+    if isolated:
+        # the last `isolated` users / items take part in nothing: empty rows, an exact zero output
+        triples = triples[(triples[:, 0] < U - isolated) & (triples[:, 2] < I - isolated)]
+    if repeat:
+        triples = np.concatenate([triples, triples[::3], triples[::7]])
+    kw.setdefault('edge_multiplicity', '0')
+    kw.setdefault('compact_nodes', '0')
+    return IncidenceLayout(triples, U, Q, I, dev(), heavy_threshold=heavy_threshold, **kw)
+
+
+def run_parts(lay, d, head, act, seed, wide=None, c_value=None, zero_w=False):
+    """(y, dx, def, dW, db, dw, dc) of  x, ef -> (. W^T + b) on both -> attention  from the HIP path and from float64; x [N, d] node rows, ef [E, d] hyperedge rows."""
+    from ihgnn_amd import ops
+    g = torch.Generator().manual_seed(seed)
+    n, e = lay.node_count, lay.edge_count
+    wide = wide or d
+    x = torch.randn(n, d, generator=g)
+    ef = torch.randn(e, d, generator=g)
+    W = torch.randn(d, d, generator=g) / d ** 0.5
+    b = torch.randn(d, generator=g) * 0.1
+    w = torch.randn(2 * d if head == 'concatenation' else d, generator=g) / d ** 0.5
+    if zero_w:
+        w.zero_()
+    c = torch.full((1,), float(c_value), dtype=torch.float32) if c_value is not None else torch.randn(1, generator=g)
+    cot = torch.randn(n, d, generator=g)
+    xs = [t.double().requires_grad_(True) for t in (x, ef, W, b, w, c)]
+    y64, alpha64 = attention64(xs[0] @ xs[2].t() + xs[3], xs[1] @ xs[2].t() + xs[3], xs[4], xs[5], lay, head, act)
+    y64.backward(cot.double())
+    want = [y64.detach()] + [t.grad for t in xs]
+    run_parts.scales = cancelling_scales()
+    run_parts.dc_scale = run_parts.scales.dc
+    xd = ops.pad_columns(x, wide).to(dev()).requires_grad_(True)
+    ed = ops.pad_columns(ef, wide).to(dev()).requires_grad_(True)
+    Wd = ops.pad_square(W, wide).to(dev()).requires_grad_(True)
+    bd = ops.pad_vector(b, wide).to(dev()).requires_grad_(True)
+    wv = (ops.pad_columns(w.view(2, d), wide).reshape(-1) if head == 'concatenation' else ops.pad_vector(w, wide)).to(dev()).requires_grad_(True)
+    cd = c.to(dev()).requires_grad_(True)
+    y = ops.hyper_attention(xd @ Wd.t() + bd, ed @ Wd.t() + bd, lay, wv, cd, head, act)
+    y.backward(ops.pad_columns(cot, wide).to(dev()))
+    dwv = wv.grad.cpu()
+    if wide != d:
+        dwv = dwv.view(2, wide)[:, :d].reshape(-1) if head == 'concatenation' else dwv[:d]
+        assert float(y.detach()[:, d:].abs().max()) == 0.0 and float(xd.grad[:, d:].abs().max()) == 0.0 and float(ed.grad[:, d:].abs().max()) == 0.0
+    got = [y.detach()[:, :d].cpu(), xd.grad[:, :d].cpu(), ed.grad[:, :d].cpu(), Wd.grad[:d, :d].cpu(), bd.grad[:d].cpu(), dwv, cd.grad.cpu()]
+    return got, want, alpha64.detach()
+
+
+def check_parts(got, want, head, d, where=''):
+    for name, a, b in zip(('y', 'dx', 'def', 'dW', 'db'), got, want):
+        assert rel(a, b) <= RTOL, (where, name, rel(a, b))
+    check_parameter(AGG_W, got[5], want[5], head, d, run_parts.scales, where)
+    check_parameter(AGG_B, got[6], want[6], head, d, run_parts.scales, where)
+
+
+@pytest.mark.parametrize('d,wide', [(32, 32), (64, 64), (128, 128), (256, 256), (96, 128), (30, 30)])
+@pytest.mark.parametrize('head', ['concatenation', 'product'])
+@pytest.mark.parametrize('split', [False, True])
+def test_phase2_attention_matches_float64(d, wide, head, split):
+    """Power-law hypergraph with isolated nodes, split rows forced (threshold 8) or not (threshold above every row); padded 96 -> 128 runs the attention vector
+    with each half zero-padded on its own; 30 runs the 4-byte path.  Isolated nodes: exact zero output and input gradient."""
+    lay = hyper_layout(seed=d, heavy_threshold=8 if split else 1 << 30, isolated=7)
+    assert (lay.node_csr.n_heavy > 0) == split
+    live = live_rows(lay)
+    assert (~live).sum() >= 7
+    got, want, _ = run_parts(lay, d, head, 'leaky_relu', seed=d + 3, wide=wide)
+    print(f'd {d} wide {wide} {head} split {split}: ' + ' '.join(f'{n} {rel(a, b):.2e}' for n, a, b in zip(('y', 'dx', 'def', 'dW', 'db', 'dw', 'dc'), got, want)))
+    check_parts(got, want, head, d, (d, wide, head, split))
+    # per row: the output, and the hyperedge rows' gradient (every hyperedge has three members: no empty row).  The node rows' gradient here is the score path
+    # alone (S[v] w_dst: a cancelling sum per row), held over the tensor above; per row it is held where it is the layer's dx (the F12 cases, the layer tests below)
+    assert row_rel(got[0], want[0], live, name='y') <= ROW_RTOL
+    assert row_rel(got[2], want[2], np.ones(lay.edge_count, bool), name='def') <= ROW_RTOL
+    iso = torch.from_numpy(~live)
+    assert float(got[0][iso].abs().max()) == 0.0 and float(got[1][iso].abs().max()) == 0.0
+
+
+def stub_dataset(lay):
+    return types.SimpleNamespace(hypergraph=types.SimpleNamespace(layout=lay))
+
+
+def run_layer(lay, lay64, d, order, head, act, seed, rows=None):
+    """IHGNNLayer (attention on) over ``lay`` on the device against ``layer64`` over ``lay64`` - the same graph in the reference's form (every interaction a
+    hyperedge, every node a row).  ``rows``: the public rows ``lay`` numbers (a compact layout's ``active_nodes``)."""
+    from ihgnn_amd.Models import IHGNNLayer
+    with settings(gs_head(head), ACTIVATIONS[act]):
+        torch.manual_seed(seed)
+        layer = IHGNNLayer(dev(), stub_dataset(lay), d, d, order, True).to(dev())
+    g = torch.Generator().manual_seed(seed + 1)
+    n = lay64.node_count
+    x = torch.randn(n, d, generator=g)
+    cot = torch.randn(n, d, generator=g)
+    pick = torch.arange(n) if rows is None else rows.cpu()
+    xd = x[pick].to(dev()).requires_grad_(True)
+    y = layer(xd)
+    y.backward(cot[pick].to(dev()))
+    sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in layer.state_dict().items()}
+    x64 = x.double().requires_grad_(True)
+    y64 = layer64(x64, sd, lay64, order, head, act)
+    cot64 = torch.zeros(n, d, dtype=torch.float64)
+    cot64[pick] = cot[pick].double()                                    # (rows outside the layout are isolated: zero output whatever the cotangent)
+    y64.backward(cot64)
+    scales = cancelling_scales()
+    live = live_rows(lay64)
+    y_full = torch.zeros(n, d)
+    y_full[pick] = y.detach().cpu()
+    dx_full = torch.zeros(n, d)
+    dx_full[pick] = xd.grad.cpu()
+    where = (order, head, act)
+    assert rel(y_full, y64) <= RTOL and row_rel(y_full, y64, live, name='y') <= ROW_RTOL, (where, rel(y_full, y64))
+    assert rel(dx_full, x64.grad) <= RTOL and row_rel(dx_full, x64.grad, live, name='dx') <= ROW_RTOL, (where, rel(dx_full, x64.grad))
+    assert float(y64.detach()[~torch.from_numpy(live)].abs().sum()) == 0.0
+    for name, p in layer.named_parameters():
+        check_parameter(name, p.grad, sd[name].grad, head, d, scales, where)
+    return y_full, dx_full, {k: p.grad.cpu() for k, p in layer.named_parameters()}
+
+
+@pytest.mark.parametrize('head', ['concatenation', 'product'])
+@pytest.mark.parametrize('order', [1, 3])
+def test_phase2_layer_with_multiplicities(head, order):
+    """A graph whose interactions repeat (every third triple twice, every seventh once more): the layout that keeps identical triples once (edge_weight) and the
+    one that keeps every interaction compute the same layer - each is held to the float64 restatement over the reference's form, one hyperedge per interaction."""
+    plain = hyper_layout(seed=31, heavy_threshold=16, isolated=5, repeat=True)
+    kept_once = hyper_layout(seed=31, heavy_threshold=16, isolated=5, repeat=True, edge_multiplicity='1')
+    assert kept_once.edge_weight is not None and kept_once.edge_count < plain.edge_count == plain.hyperedge_count
+    assert plain.edge_weight is None and plain.node_csr.n_heavy > 0 and kept_once.node_csr.n_heavy > 0
+    a = run_layer(plain, plain, 64, order, head, 'leaky_relu', seed=41)
+    b = run_layer(kept_once, plain, 64, order, head, 'leaky_relu', seed=41)
+    assert rel(b[0], a[0]) <= 2 * RTOL and rel(b[1], a[1]) <= 2 * RTOL               # (both within RTOL of float64)
+
+
+@pytest.mark.parametrize('head', ['concatenation', 'product'])
+def test_phase2_layer_on_a_compact_layout(head):
+    """compact_nodes=1 (isolated nodes left out of the layout's numbering) against compact_nodes=0: the same rows for the nodes that have hyperedges."""
+    full = hyper_layout(seed=32, heavy_threshold=16, isolated=9)
+    compact = hyper_layout(seed=32, heavy_threshold=16, isolated=9, compact_nodes='1')
+    assert compact.compact and compact.node_count < full.node_count == compact.public_node_count
+    a = run_layer(full, full, 32, 2, head, 'tanh', seed=43)
+    b = run_layer(compact, full, 32, 2, head, 'tanh', seed=43, rows=compact.active_nodes)
+    assert rel(b[0], a[0]) <= 2 * RTOL and rel(b[1], a[1]) <= 2 * RTOL
+
+
+def test_phase2_layer_at_a_padded_width():
+    """A 96-wide layer fed features zero-padded to 128 columns (RawGnn's compute width): the padding columns stay exactly zero, the first 96 are the 96-wide layer's."""
+    from ihgnn_amd import ops
+    from ihgnn_amd.Models import IHGNNLayer
+    lay = hyper_layout(seed=33, heavy_threshold=16, isolated=3)
+    d, wide = 96, 128
+    torch.manual_seed(3)
+    layer = IHGNNLayer(dev(), stub_dataset(lay), d, d, 3, True).to(dev())
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(lay.node_count, d, generator=g) * 0.5
+    cot = torch.randn(lay.node_count, d, generator=g)
+    xd = ops.pad_columns(x, wide).to(dev()).requires_grad_(True)
+    y = layer(xd)
+    y.backward(ops.pad_columns(cot, wide).to(dev()))
+    assert float(y.detach()[:, d:].abs().max()) == 0.0 and float(xd.grad[:, d:].abs().max()) == 0.0
+    sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in layer.state_dict().items()}
+    x64 = x.double().requires_grad_(True)
+    y64 = layer64(x64, sd, lay, 3, 'concatenation', 'leaky_relu')
+    y64.backward(cot.double())
+    scales = cancelling_scales()
+    assert rel(y.detach()[:, :d], y64) <= RTOL and rel(xd.grad[:, :d], x64.grad) <= RTOL
+    for name, p in layer.named_parameters():
+        check_parameter(name, p.grad, sd[name].grad, 'concatenation', d, scales, 'padded')
+
+
+def phase2_alpha(h2, ef2, lay, w, c, head, act):
+    """(alpha, z) of every entry from the forward launch itself (ihg_phase2_attention_fwd); the edge-major copy is checked to be the same numbers at their slots."""
+    from ihgnn_amd import _lib, ops
+    lib = _lib.load()
+    csr = lay.node_csr
+    n, d = h2.shape
+    e = lay.edge_count
+    z, alpha, ae = (torch.empty(3 * e, device=dev()) for _ in range(3))
+    wsb = int(lib.ihg_phase2_workspace_bytes(n, e, csr.n_segments, d, ops.GAT_HEADS[head]))
+    ws = torch.empty(wsb // 4 + 4, device=dev())
+    _lib.check(lib.ihg_phase2_attention_fwd(ops._ptr(h2), d, ops._ptr(ef2), d, ops._ptr(csr.ptr), ops._ptr(csr.ids), ops._ptr(lay.member_csr.ids), ops._ptr(csr.row_order),
+                                            n, e, d, ops._ptr(w), ops._ptr(c), ops._ptr(lay.edge_weight), ops.GAT_HEADS[head], ops.GAT_ACTIVATIONS[act],
+                                            *ops._gat_plan(csr), ops._ptr(z), ops._ptr(alpha), ops._ptr(ae), ops._ptr(ws), wsb, ops._stream()), 'fwd')
+    a = alpha.cpu().numpy()
+    np.testing.assert_array_equal(ae.cpu().numpy()[lay.member_csr.ids_host], a)
+    return a
+
+
+@pytest.mark.parametrize('head', ['concatenation', 'product'])
+@pytest.mark.parametrize('act', ['leaky_relu', 'relu', 'tanh'])
+def test_phase2_attention_edge_cases(head, act):
+    """Nodes with one hyperedge (alpha = 1), a zero attention vector (equal scores: alpha = 1 / degree, Y = Dv^-1 H Ef'), scores around +-80 and around 100 -
+    exp(100) overflows fp32 on its own, so every row's softmax depends on the row maximum being subtracted first."""
+    from ihgnn_amd import ops
+    lay = hyper_layout(seed=9, heavy_threshold=16)
+    deg = np.diff(lay.node_csr.ptr_host.astype(np.int64))
+    assert (deg == 1).any() and lay.node_csr.n_heavy > 0
+    for c_value, zero_w in ((None, False), (0.3, True), (80.0, False), (-80.0, False), (100.0, False)):
+        got, want, _ = run_parts(lay, 32, head, act, seed=17, c_value=c_value, zero_w=zero_w)
+        assert abs(float(got[6]) - float(want[6])) <= RTOL * max(run_parts.dc_scale, 1e-6), c_value
+        for name, a, b in zip(('y', 'dx', 'def', 'dW', 'db', 'dw'), got, want):
+            if name == 'dw' and head == 'concatenation' and float(b.abs().max()) >= 1e-12:
+                check_parameter(AGG_W, a, b, head, 32, run_parts.scales, c_value)
+                continue
+            if float(b.abs().max()) < 1e-12:
+                # a gradient that vanishes: equal scores (the softmax absorbs c) or a saturated activation (tanh at 80: 1 - z^2 is 0 in fp32, 1e-69 in fp64)
+                assert float(a.abs().max()) <= 1e-6, (c_value, name, a)
+                continue
+            assert rel(a, b) <= RTOL, (c_value, zero_w, name, rel(a, b))
+    g = torch.Generator().manual_seed(3)
+    h2 = torch.randn(lay.node_count, 32, generator=g).to(dev())
+    ef2 = torch.randn(lay.edge_count, 32, generator=g).to(dev())
+    rows = np.repeat(np.arange(lay.node_count), deg)
+    for zero_w in (False, True):
+        k = 64 if head == 'concatenation' else 32
+        w = torch.zeros(k, device=dev()) if zero_w else torch.randn(k, generator=g).to(dev())
+        c = torch.full((1,), 80.0, device=dev())
+        alpha = phase2_alpha(h2, ef2, lay, w, c, head, act)
+        sums = np.bincount(rows, weights=alpha.astype(np.float64), minlength=lay.node_count)
+        assert np.abs(sums[deg > 0] - 1).max() <= 1e-6
+        assert (alpha[np.repeat(deg == 1, deg)] == 1.0).all()
+        if zero_w:
+            np.testing.assert_allclose(alpha, 1.0 / deg[rows], rtol=2e-7)
+            # uniform alpha: the layer without attention, Y = Dv^-1 H Ef'
+            y = ops.hyper_attention(h2, ef2, lay, w, c, head, act)
+            mean = ops.node_segment_sum(ef2, lay, out_scale=lay.inv_deg)
+            assert rel(y, mean) <= 1e-6
+
+
+@pytest.mark.parametrize('head', ['concatenation', 'product'])
+def test_phase2_attention_is_bitwise_reproducible(head):
+    lay = hyper_layout(seed=4, heavy_threshold=8, repeat=True, edge_multiplicity='1')
+    outs = []
+    for _ in range(2):
+        got, _, _ = run_parts(lay, 64, head, 'leaky_relu', seed=5)
+        outs.append(got)
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------
+# training
+# ---------------------------------------------------------------------------------------------
+def phase2_dataset(seed=21):
+    from ihgnn_amd import synth
+    from ihgnn_amd.Dataset import GraphDataset
+    from ihgnn_amd.Helpers.Graph import PpsHyperGraph
+    w = synth.draw(300, 40, 200, 50, 4000, seed=seed, distribution='powerlaw')
+    return GraphDataset.from_arrays(w.user_count, w.query_count, w.item_count, w.vocab_size, w.bag_words, w.bag_offsets, w.triples, graph_type=PpsHyperGraph,
+                                    device=dev())
+
+
+def grad_close(a, b, bar=RTOL):
+    b = b.detach().cpu().double()
+    if b.numel() == 1 and float(b.abs()) < 1e-9:
+        return float(a.detach().abs().max()) < 1e-9
+    return rel(a, b) <= bar
+
+
+def test_phase2_bce_step_matches_the_plain_loss():
+    """``bce_loss`` (fused batch tail; the first layer reads the embedding tables in place, the last layer is told the batch rows) of a 2-layer model with
+    attention on equals ``BCEWithLogitsLoss(model(u, q, i))`` in loss and every gradient, and the plain path holds the float64 model."""
+    from ihgnn_amd.Models import HemPredictionLayer, IHGNNLayer, RawGnn
+    ds = phase2_dataset()
+    u, q, i, y = next(iter(ds.sample_batches(80, 1, seed=3)))
+    torch.manual_seed(5)
+    m = RawGnn(dev(), ds, 64, IHGNNLayer, 2, 3, True, HemPredictionLayer, 0.5).to(dev())
+    loss = m.bce_loss(u, q, i, y)
+    loss.backward()
+    fused = {k: p.grad.clone() for k, p in m.named_parameters()}
+    m.zero_grad(set_to_none=True)
+    plain = torch.nn.BCEWithLogitsLoss()(m(u, q, i), y.float())
+    plain.backward()
+    assert abs(loss.item() - plain.item()) <= 1e-6 * max(1.0, abs(plain.item()))
+    model_scales64(m, ds, u, q, i, y, dtype=torch.float32)
+    g32 = model_scales64.grads
+    scales = model_scales64(m, ds, u, q, i, y)
+    for k, p in m.named_parameters():
+        assert p.grad is not None and fused[k] is not None, k
+        g64 = model_scales64.grads[k]
+        if g64 is not None:
+            print(f'bce {k}: fp32 CPU against float64 {rel(g32[k], g64):.2e}, fused {rel(fused[k], g64):.2e}, plain {rel(p.grad, g64):.2e}')
+        if g64 is None:
+            # the embedding tables (the restatement starts from X0): the two paths against each other
+            assert grad_close(fused[k], p.grad), k
+            continue
+        if k.endswith(AGG_W):
+            print(f'   w_src half: fp32 CPU against float64 {rel(g32[k].reshape(-1)[:64], g64.reshape(-1)[:64]):.2e}, fused {rel(fused[k].reshape(-1)[:64], g64.reshape(-1)[:64]):.2e}')
+        # the two paths sum the same gradients in different orders: each against float64
+        # gnn_1's w_src half: the same statements in fp32 on the CPU are 2.63e-2 from float64 here (measured; the two device paths: 1.1e-5), so
+        # the bar is 4 x 2.63e-2 - and, since that says little, RTOL of the sum of the terms' magnitudes as well (check_parameter)
+        for got in (fused[k], p.grad):
+            check_parameter(k, got, g64, 'concatenation', 64, scales.get(k.split('.')[0], Scales()), 'bce', src_bar=4 * 2.63e-2 if k.startswith('gnn_1.') else RTOL)
+
+
+def test_phase2_layer_launches_only_library_kernels(tmp_path):
+    """The layer's forward + backward at d = 64 (node transform and interactor included; both heads) under a kernel trace: every kernel after the marker launch
+    is one of the library's."""
+    import csv
+    import glob
+    import shutil
+    import subprocess
+    import sys
+    profiler_exe = shutil.which('rocprofv3') or '/opt/rocm/bin/rocprofv3'
+    if not os.path.exists(profiler_exe):
+        pytest.skip('rocprofv3 not available')
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / 'phase2_trace.py'
+    script.write_text(f'''
+import sys
+sys.path.insert(0, {repo!r})
+import torch
+from ihgnn_amd import _lib, ops, synth
+from ihgnn_amd.Dataset import GraphDataset
+from ihgnn_amd.Helpers.GlobalSettings import Gs, Gsv
+from ihgnn_amd.Helpers.Graph import PpsHyperGraph
+from ihgnn_amd.Models import IHGNNLayer
+dev = torch.device('cuda:0')
+w = synth.draw(300, 40, 200, 50, 3000, seed=5, distribution='powerlaw', exponent=1.1)
+ds = GraphDataset.from_arrays(w.user_count, w.query_count, w.item_count, w.vocab_size, w.bag_words, w.bag_offsets, w.triples, graph_type=PpsHyperGraph, device=dev)
+torch.manual_seed(1)
+layers = []
+for head in (Gsv.concat, Gsv.product):
+    Gs.Gnn.gat_head = head
+    layers.append(IHGNNLayer(dev, ds, 64, 64, 3, True).to(dev))
+x = torch.randn(ds.node_count, 64, device=dev).requires_grad_(True)
+cot = torch.randn(ds.node_count, 64, device=dev)
+marker = torch.empty(8, dtype=torch.int64, device=dev)
+for rep in range(3):
+    if rep == 2:                                               # the marker: a library launch the layer never makes
+        torch.cuda.synchronize()
+        _lib.check(_lib.load().ihg_sample_negatives(1, 0, 4, 100, 2, ops._ptr(marker), ops._stream()), 'marker')
+    for layer in layers:
+        layer.zero_grad(set_to_none=True)                      # (no accumulation into earlier gradients: autograd keeps the library's tensors)
+        x.grad = None
+        layer(x).backward(cot)
+torch.cuda.synchronize()
+print('phase2 done')
+''')
+    out = str(tmp_path / 'trace')
+    r = subprocess.run([profiler_exe, '--kernel-trace', '--output-format', 'csv', '-d', out, '--', sys.executable, str(script)], cwd=str(tmp_path),
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, TMPDIR=str(tmp_path)))
+    assert r.returncode == 0 and 'phase2 done' in r.stdout, r.stderr[-2000:]
+    files = glob.glob(os.path.join(out, '**', '*kernel_trace.csv'), recursive=True)
+    assert files, 'no kernel trace written'
+    rows = sorted(csv.DictReader(open(files[0])), key=lambda x: int(x['Start_Timestamp']))
+    names = [x['Kernel_Name'] for x in rows]
+    marks = [k for k, n in enumerate(names) if 'sample_negatives_kernel' in n]
+    assert len(marks) == 1, marks
+    last = names[marks[0] + 1:]                                  # the two layers' forward + backward
+    short = sorted({n.split('(')[0] for n in last})
+    foreign = [n for n in last if 'at::native' in n or '__amd_rocclr' in n or 'elementwise_kernel' in n]
+    assert not foreign, foreign
+    for want in ('p2_project_kernel', 'p2_softmax_kernel', 'gat_row_dot_kernel', 'node_segment_sum_kernel', 'gat_softmax_bwd_kernel', 'p2_to_edge_slots_kernel',
+                 'p2_edges_bwd_kernel', 'p2_colsum_partials_kernel', 'p2_node_grad_kernel', 'p2_add_rows_kernel'):
+        assert any(want in n for n in last), (want, short)
+
+
+def test_phase2_driver_epoch(tmp_path, monkeypatch):
+    """The driver with ``--phase2`` on a small synthetic corpus: two epochs train and test with finite metrics; asked to record the step, it trains eagerly and
+    says so (CapturedTrainingStep refuses a model with attention)."""
+    import random
+    from ihgnn_amd import Main as driver, synth
+    w = synth.draw(200, 30, 150, 40, 3000, seed=8, eval_logs=40)
+    synth.write_files(w, str(tmp_path / 'Data' / 'Synth' / 'Tiny'))
+    monkeypatch.chdir(tmp_path)
+    args = ['--ds', 'Synth/Tiny/', '--phase2', '--gnns', '2', '--fo', '3', '--emb', '32', '--ec', '2', '--est', '2', '--etf', '1', '--record_step']
+    random.seed(11); torch.manual_seed(11)
+    eager = driver.main(args + ['off'])
+    random.seed(11); torch.manual_seed(11)
+    asked = driver.main(args + ['on'])
+    (_, m_e), (_, m_a) = list(eager.iter_epoch_test())[-1], list(asked.iter_epoch_test())[-1]
+    for m in (m_e, m_a):
+        assert np.isfinite([m.HitRatio_at10, m.NDCG_at10, m.MAP_at10]).all()
+    assert eager.training_step_recorded is False and asked.training_step_recorded is False
+    assert abs(m_e.NDCG_at10 - m_a.NDCG_at10) <= 2e-3                       # (both eager, same seeds)
