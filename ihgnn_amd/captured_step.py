@@ -131,11 +131,7 @@ class CapturedTrainingStep:
         group = opt.param_groups[0]
         t = opt.next_step()
         if self._table is None or self._table_lr != group['lr'] or not (self._table_first <= t < self._table_first + self.TABLE_STEPS):
-            import numpy as np
-            # exactly ihg_adam_step's arithmetic: lr and the betas arrive there as fp32, the bias corrections are formed in double
-            lr, beta1, beta2 = (float(np.float32(x)) for x in (group['lr'], group['betas'][0], group['betas'][1]))
-            steps = np.arange(t, t + self.TABLE_STEPS, dtype=np.float64)
-            table = torch.from_numpy(np.stack([lr / (1.0 - np.power(beta1, steps)), np.sqrt(1.0 - np.power(beta2, steps))], 1).astype(np.float32))
+            table = Adam.step_scalars(t, self.TABLE_STEPS, group['lr'], group['betas'])
             self._table, self._table_first, self._table_lr = table.to(self.scalars.device), t, group['lr']
         self.scalars.copy_(self._table[t - self._table_first], non_blocking=True)
 

@@ -548,14 +548,18 @@ int ihg_batch_node_rows(const int64_t* users, const int64_t* queries, const int6
 
 static int adam_launch(const char* what, const ihg_adam_tensor* tensors, int32_t n_tensors, float beta1, float beta2, float eps, float weight_decay, float step_size,
                        float bias2_sqrt, const float* scalars, ihg_stream_t stream) {
+    for (int t = 0; t < n_tensors; ++t) {                    // every tensor is checked before the first launch: a refused call has updated nothing
+        const ihg_adam_tensor& a = tensors[t];
+        if (a.count < 0 || (a.count > 0 && (a.param == nullptr || a.grad == nullptr || a.exp_avg == nullptr || a.exp_avg_sq == nullptr)))
+            return fail(IHG_ERR_INVALID, "%s: tensor %d has a null pointer or a negative count", what, t);
+    }
+    bool launched = false;
     for (int t = 0; t < n_tensors;) {                        // one launch per kAdamMaxTensors NON-EMPTY tensors; t is the only cursor
         AdamTable tab{};
         int64_t chunks = 0;
         int used = 0;
         for (; t < n_tensors && used < kAdamMaxTensors; ++t) {
             const ihg_adam_tensor& a = tensors[t];
-            if (a.count < 0 || (a.count > 0 && (a.param == nullptr || a.grad == nullptr || a.exp_avg == nullptr || a.exp_avg_sq == nullptr)))
-                return fail(IHG_ERR_INVALID, "%s: tensor %d has a null pointer or a negative count", what, t);
             if (a.count == 0) continue;
             tab.param[used] = a.param; tab.grad[used] = a.grad; tab.exp_avg[used] = a.exp_avg; tab.exp_avg_sq[used] = a.exp_avg_sq;
             tab.count[used] = a.count;
@@ -569,8 +573,9 @@ static int adam_launch(const char* what, const ihg_adam_tensor* tensors, int32_t
         const int grid = static_cast<int>(std::min<int64_t>(chunks, 256 * 16));
         hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), tab, beta1, beta2, eps, weight_decay,
                            step_size, bias2_sqrt, scalars);
+        launched = true;
     }
-    return check_launch(what);
+    return launched ? check_launch(what) : IHG_OK;           // (only empty tensors: nothing was launched, the runtime is not asked)
 }
 
 int ihg_adam_step(const ihg_adam_tensor* tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,

@@ -64,6 +64,15 @@ class Adam(Optimizer):
         return loss
 
     # ------------------------------------------------------------------ recorded steps (ihgnn_amd/captured_step.py)
+    @staticmethod
+    def step_scalars(first_step: int, count: int, lr: float, betas) -> torch.Tensor:
+        """``(lr / (1 - beta1^t), sqrt(1 - beta2^t))`` for the steps ``t = first_step .. first_step + count - 1``: float32 ``[count, 2]`` on the host, what
+        ``ihg_adam_step_device_scalars`` reads.  Exactly ``ihg_adam_step``'s arithmetic: lr and the betas arrive there as fp32, the bias corrections are formed in double."""
+        import numpy as np
+        lr, beta1, beta2 = (float(np.float32(x)) for x in (lr, betas[0], betas[1]))
+        steps = np.arange(first_step, first_step + count, dtype=np.float64)
+        return torch.from_numpy(np.stack([lr / (1.0 - np.power(beta1, steps)), np.sqrt(1.0 - np.power(beta2, steps))], 1).astype(np.float32))
+
     def next_step(self, group_index: int = 0) -> int:
         """The step number the next update of a parameter group will carry (all its parameters share one count)."""
         group = self.param_groups[group_index]

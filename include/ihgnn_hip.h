@@ -440,6 +440,8 @@ int ihg_compose_first_order_bwd(const float* a, int64_t ld_a, const float* w, in
  * stepped in TrainTestHelper.py:139-143), for all parameters in one launch per 24 tensors.  Same update as torch.optim.Adam
  * (amsgrad off, maximize off): g += wd * p; m += (g - m)(1 - b1); v = b2 v + (1 - b2) g^2;
  * p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps), t = `step` >= 1 (the caller counts).  `tensors` is a HOST array.
+ * Every entry is checked before the first launch (count >= 0; four non-null pointers where count > 0): a call that returns
+ * IHG_ERR_INVALID has updated nothing.  Empty tensors (count == 0) are skipped.
  */
 typedef struct ihg_adam_tensor {
     float* param;

@@ -62,6 +62,61 @@ def test_bad_arguments_return_codes_and_messages():
         _lib.check(_lib.ERR_INVALID, 'probe')
 
 
+def test_update_tail_bad_arguments_return_invalid_and_launch_nothing():
+    """The loss-and-update end of a step: every argument check answers IHG_ERR_INVALID before any launch (this runs where there is no GPU: a launch would answer
+    something else), also for a bad tensor BEHIND the first 24 of an Adam call - a refused call has updated nothing."""
+    from ihgnn_amd.optim import _AdamTensor
+    lib = _lib.load()
+    some = 4096                                              # a non-null address that is never dereferenced
+
+    def table(entries):
+        t = (_AdamTensor * len(entries))()
+        for slot, (p, g, m, v, count) in zip(t, entries):
+            slot.param, slot.grad, slot.exp_avg, slot.exp_avg_sq, slot.count = p, g, m, v, count
+        return ctypes.cast(t, ctypes.c_void_p), t
+
+    good = (some, some, some, some, 8)
+    one, keep = table([good])
+    hyper = (1e-3, 0.9, 0.999, 1e-8, 0.0)
+    scalars = ctypes.c_void_p(some)
+    assert lib.ihg_adam_step(one, 1, *hyper, 0, None) == _lib.ERR_INVALID                       # steps are counted from 1
+    assert lib.ihg_adam_step(one, 1, *hyper, -3, None) == _lib.ERR_INVALID
+    assert lib.ihg_adam_step(None, 1, *hyper, 1, None) == _lib.ERR_INVALID
+    assert lib.ihg_adam_step(one, -1, *hyper, 1, None) == _lib.ERR_INVALID
+    assert lib.ihg_adam_step_device_scalars(one, 1, *hyper[1:], None, None) == _lib.ERR_INVALID  # null scalars
+    assert lib.ihg_adam_step_device_scalars(None, 1, *hyper[1:], scalars, None) == _lib.ERR_INVALID
+    for bad in ((some, some, some, some, -1), (None, some, some, some, 8), (some, None, some, some, 8), (some, some, None, some, 8), (some, some, some, None, 8)):
+        for entries in ([bad], [good] * 30 + [bad], [(None, None, None, None, 0)] * 3 + [bad]):
+            ptr, keep = table(entries)
+            assert lib.ihg_adam_step(ptr, len(entries), *hyper, 1, None) == _lib.ERR_INVALID, (bad, len(entries))
+            assert f'tensor {len(entries) - 1}' in _lib.last_error()
+            assert lib.ihg_adam_step_device_scalars(ptr, len(entries), *hyper[1:], scalars, None) == _lib.ERR_INVALID, (bad, len(entries))
+    # nothing to do is fine: no tensors, or only empty ones (null pointers allowed there)
+    ptr, keep = table([(None, None, None, None, 0)] * 26)
+    assert lib.ihg_adam_step(ptr, 26, *hyper, 1, None) == _lib.OK and lib.ihg_adam_step(None, 0, *hyper, 1, None) == _lib.OK
+    assert lib.ihg_adam_step_device_scalars(ptr, 26, *hyper[1:], scalars, None) == _lib.OK
+    # BCE: 1 .. 2^24 rows
+    ws = ctypes.c_void_p(some)
+    assert lib.ihg_bce_with_logits(ws, ws, 0, ws, ws, None) == _lib.ERR_INVALID
+    assert lib.ihg_bce_with_logits(ws, ws, (1 << 24) + 1, ws, ws, None) == _lib.ERR_INVALID
+    assert lib.ihg_bce_with_logits(ws, ws, -1, ws, ws, None) == _lib.ERR_INVALID
+    for k in range(4):
+        args = [ws, ws, 10, ws, ws]
+        args[k if k < 2 else k + 1] = None
+        assert lib.ihg_bce_with_logits(*args, None) == _lib.ERR_INVALID
+    # HEM scores: 1 .. 8 layer outputs, ld >= dim > 0, row stride of the gradients >= L * dim
+    layers9 = (ctypes.c_void_p * 9)(*[some] * 9)
+    for n_layers, ld, dim in ((9, 4, 4), (0, 4, 4), (2, 3, 4), (2, 4, 0)):
+        assert lib.ihg_hem_score_fwd(layers9, n_layers, ld, dim, ws, ws, ws, 0.5, ws, 5, None) == _lib.ERR_INVALID
+        assert lib.ihg_hem_score_bwd(layers9, n_layers, ld, dim, ws, ws, 1.0, 0.5, ws, 64, 5, None) == _lib.ERR_INVALID
+        assert lib.ihg_hem_score_fwd_typed0(layers9, n_layers, ld, dim, None, 0, None, ws, None, ws, ws, 0.5, ws, 5, None) == _lib.ERR_INVALID
+        assert lib.ihg_hem_score_bwd_typed0(layers9, n_layers, ld, dim, None, 0, None, ws, None, ws, None, 1.0, 0.5, ws, 64, 5, None) == _lib.ERR_INVALID
+    assert lib.ihg_hem_score_bwd(layers9, 2, 4, 4, ws, ws, 1.0, 0.5, ws, 7, 5, None) == _lib.ERR_INVALID                   # rowgrad rows shorter than 2 x 4
+    assert lib.ihg_hem_score_bwd_typed0(layers9, 2, 4, 4, None, 0, None, ws, None, ws, None, 1.0, 0.5, ws, 7, 5, None) == _lib.ERR_INVALID
+    assert lib.ihg_hem_score_fwd_typed0(layers9, 2, 4, 4, layers9, 4, None, ws, None, ws, ws, 0.5, ws, 5, None) == _lib.ERR_INVALID   # typed layer 0 without its type ranges
+    assert lib.ihg_hem_score_fwd(layers9, 8, 4, 4, ws, ws, ws, 0.5, ws, 0, None) == _lib.OK                                 # an empty batch launches nothing
+
+
 def test_missing_library_is_a_hard_error(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libihgnn_hip.so')

@@ -2630,6 +2630,10 @@ def test_adam_matches_torch_adam():
     base = [torch.randn(*sh, generator=gen) for sh in shapes]
     ours = [torch.nn.Parameter(t.clone().to(dev())) for t in base]
     theirs = [torch.nn.Parameter(t.clone().to(dev())) for t in base]
+    flat = torch.randn(3 * 4096 + 9, generator=gen)          # the unaligned view-backed tensor: three full chunks and a tail, 4 bytes past a 16-byte boundary
+    ours.append(flat.clone().to(dev())[1:-1].requires_grad_())
+    theirs.append(flat.clone().to(dev())[1:-1].requires_grad_())
+    assert ours[-1].data_ptr() % 16 == 4 and ours[-1].is_leaf
     a = Adam(ours, lr=3e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-2)
     b = torch.optim.Adam(theirs, lr=3e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-2)
     for step in range(12):
@@ -2763,7 +2767,23 @@ def test_recorded_training_step_equals_the_eager_step_beyond_one_scatter_launch(
     _recorded_step_equals_the_eager_step(1000, True, monkeypatch)
 
 
-def _recorded_step_equals_the_eager_step(positives, collapsed, monkeypatch):
+def test_recorded_training_step_rolls_its_scalar_table_over(monkeypatch):
+    """The recorded step's device table of Adam scalars cut to 3 steps (``TABLE_STEPS``; 2,048 in production, which a small-graph run passes within an epoch): 8 replays
+    roll it over twice, the learning rate changes mid-table (before the third step) and on a table edge (before the sixth, where the driver's per-epoch decay lands
+    sooner or later) - same losses, parameters and step counts as the eager steps.  One recording."""
+    from ihgnn_amd.captured_step import CapturedTrainingStep
+    monkeypatch.setattr(CapturedTrainingStep, 'TABLE_STEPS', 3)
+    _recorded_step_equals_the_eager_step(100, False, monkeypatch, n_batches=8, lr_changes={2: 5e-4, 5: 2.5e-4})
+
+
+def test_recorded_training_step_on_an_optimizer_that_has_stepped(monkeypatch):
+    """A recording made on an optimizer that has already taken 5 eager steps (a resumed run: the table's first row is step 6, not 1), then 4 replays against the same 9
+    eager steps.  One recording."""
+    _recorded_step_equals_the_eager_step(100, False, monkeypatch, n_batches=9, eager_first=5, lr_changes={7: 5e-4})
+
+
+def _recorded_step_equals_the_eager_step(positives, collapsed, monkeypatch, n_batches=4, eager_first=0, lr_changes=None):
+    lr_changes = {2: 5e-4} if lr_changes is None else lr_changes
     from ihgnn_amd import layout as layout_mod, synth
     from ihgnn_amd.Dataset import GraphDataset
     from ihgnn_amd.captured_step import CapturedTrainingStep
@@ -2779,7 +2799,8 @@ def _recorded_step_equals_the_eager_step(positives, collapsed, monkeypatch):
         triples = np.concatenate([base, base[:1500]])
     ds = GraphDataset.from_arrays(w.user_count, w.query_count, w.item_count, w.vocab_size, w.bag_words, w.bag_offsets, triples, device=dev())
     assert ds.hypergraph.layout.compact == collapsed and (ds.hypergraph.layout.edge_weight is not None) == collapsed
-    batches = list(ds.sample_batches(positives, 4, seed=5))
+    batches = list(ds.sample_batches(positives, n_batches, seed=5))
+    assert len(batches) == n_batches
     assert (3 * batches[0][0].shape[0] > SCATTER_LIMIT) == collapsed
 
     def run(recorded):
@@ -2792,12 +2813,14 @@ def _recorded_step_equals_the_eager_step(positives, collapsed, monkeypatch):
             held = m.bce_loss(*batches[0])
             held.backward()
             opt.zero_grad(set_to_none=True)
-        step = CapturedTrainingStep(m, opt, batches[0][0].shape[0], warmup_batch=batches[0]) if recorded else None
+        step = None
         losses = []
         for k, (u, q, i, y) in enumerate(batches):
-            if k == 2:
-                opt.param_groups[0]['lr'] = 5e-4
-            if recorded:
+            if k in lr_changes:
+                opt.param_groups[0]['lr'] = lr_changes[k]
+            if recorded and k == eager_first:                # (the first eager_first steps are eager in both runs: the recording starts on an optimizer that has stepped)
+                step = CapturedTrainingStep(m, opt, batches[0][0].shape[0], warmup_batch=batches[0])
+            if step is not None:
                 losses.append(step.step(u, q, i, y).item())
             else:
                 loss = m.bce_loss(u, q, i, y)
@@ -2810,7 +2833,10 @@ def _recorded_step_equals_the_eager_step(positives, collapsed, monkeypatch):
     np.testing.assert_allclose(l1, l0, rtol=1e-6)
     for k in p0:
         assert rel(p1[k], p0[k]) <= 1e-6, k
-    assert o1.next_step() == o0.next_step() == 5
+    assert o1.next_step() == o0.next_step() == n_batches + 1
+    steps0 = [int(o0.state[p]['step']) for p in o0.param_groups[0]['params']]
+    steps1 = [int(o1.state[p]['step']) for p in o1.param_groups[0]['params']]
+    assert steps0 == steps1 == [n_batches] * len(steps0)
 
 
 @pytest.mark.parametrize('kind,layers,order,dim', [('ihgnn', 3, 3, 128), ('ihgnn', 2, 1, 128), ('hgcn', 2, 3, 128), ('ihgnn', 2, 3, 256), ('ihgnn', 1, 3, 128)])

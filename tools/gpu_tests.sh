@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=${1:?usage: tools/gpu_tests.sh OUT_DIR [K_EXPRESSION] [full]}
 mkdir -p "$O"
 if [ -n "${2:-}" ]; then
-  ( time timeout 1500 python -m pytest tests/test_gpu_parity.py -q -x -s -k "$2" ) > "$O/t_new.log" 2>&1
+  ( time timeout 1500 python -m pytest tests -m gpu -q -x -s -k "$2" ) > "$O/t_new.log" 2>&1
   grep -E "^F10|^F[0-9] |split arithmetic|passed|failed|error" "$O/t_new.log" | tail -40
 fi
 if [ "${3:-}" = "full" ]; then
