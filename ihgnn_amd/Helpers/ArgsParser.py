@@ -25,11 +25,17 @@ _FLAGS = (
     ('device_sampling', ('--device_sampling',), 'flag', False, 'draw training batches on the device (same distribution, different random stream)'),
     # not in the reference's command line: its driver hard-codes phase2_attention=False (Main.py:57)
     ('phase2', ('--phase2',), 'flag', False, 'IHGNN layers with phase-2 attention: attention weights over a node\'s hyperedges instead of their mean (Gs.Gnn.gat_head / gat_activation)'),
+    # not in the reference's command line: there one edits Gs.Query in Helpers/GlobalSettings.py:68-76
+    ('query_transform', ('--query_transform',), str, Gsv.mean, 'query transform: mean | activation (nn.Linear + --query_activation on the bag mean; Gs.Query.transform)'),
+    ('query_activation', ('--query_activation',), str, 'relu', 'activation of --query_transform activation: relu | tanh (Gs.Query.transform_activation)'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '
                                                              '< 1.5 ms) | on (also a bare --record_step) | off'),
 )
+
+
+_CHOICES = {'query_transform': (Gsv.mean, Gsv.activation), 'query_activation': ('relu', 'tanh')}
 
 
 class ConsoleArgs:
@@ -46,6 +52,8 @@ def build_parser() -> argparse.ArgumentParser:
             parser.add_argument(*flags, dest=dest, action='store_true', default=default, help=text)
         elif kind == 'optional':
             parser.add_argument(*flags, dest=dest, nargs='?', const='on', default=default, choices=('auto', 'on', 'off'), help=text)
+        elif dest in _CHOICES:
+            parser.add_argument(*flags, dest=dest, type=kind, default=default, choices=_CHOICES[dest], help=text)
         else:
             parser.add_argument(*flags, dest=dest, type=kind, default=default, help=text)
     return parser

@@ -35,8 +35,8 @@ class Gs:
         gat_activation = (nn.LeakyReLU, 'leaky_relu')      # or (nn.ReLU, 'relu'), (nn.Tanh, 'tanh')
 
     class Query:
-        transform = Gsv.mean             # the only transform on the path (EmbeddingLayers.py:37-38)
-        transform_activation = nn.ReLU
+        transform = Gsv.mean             # or Gsv.activation: nn.Linear(d, d) + transform_activation on the bag mean (EmbeddingLayers.py:37-44); Gsv.rnn raises, as in the reference
+        transform_activation = nn.ReLU   # or nn.Tanh (the reference's other assignment, GlobalSettings.py:74-76)
 
     class Prediction:
         use_cosine_similarity = False

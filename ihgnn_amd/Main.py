@@ -16,7 +16,7 @@ from torch.utils.data import DataLoader
 from . import distributed as ihg_dist
 from .Dataset import GraphDataset, TestSearchLogDataLoader
 from .Helpers.ArgsParser import parse_args
-from .Helpers.GlobalSettings import Gs
+from .Helpers.GlobalSettings import Gs, Gsv
 from .Helpers.Graph import Pps2DGraph, PpsHyperGraph
 from .Helpers.IOHelper import IOHelper
 from .Helpers.Metrics import Metrics, MetricsCollection
@@ -33,6 +33,12 @@ def result_directory(dataset_name: str, layers: int, layer_type: type, order: in
         parts.append(f'O{order}')
     parts.append(f'emb{emb}')
     return os.path.join('Results', '-'.join(parts))
+
+
+def apply_query_settings(args) -> None:
+    """``--query_transform`` / ``--query_activation`` -> ``Gs.Query`` (not in the reference's command line: one edits ``Helpers/GlobalSettings.py:68-76`` there)."""
+    Gs.Query.transform = getattr(args, 'query_transform', Gsv.mean) or Gsv.mean
+    Gs.Query.transform_activation = {'relu': nn.ReLU, 'tanh': nn.Tanh}[getattr(args, 'query_activation', 'relu') or 'relu']
 
 
 def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
@@ -64,6 +70,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         raise NotImplementedError('--phase2 runs in a single process: the gradient exchanges of ihgnn_amd.distributed have not been run with the attention on')
     layer_count = args.gnns or 2
     order = args.feature_order or 3
+    apply_query_settings(args)
     if args.device == 'cpu':
         raise RuntimeError('ihgnn_amd has no CPU path: the hypergraph kernels are HIP-only')
     device = torch.device(f'cuda:{args.device}' if args.device else f'cuda:{local_rank}')
@@ -85,7 +92,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     say(f'device {device} | ranks {world} | batch {Gs.batch_size} | lr {Gs.learning_rate} | emb {Gs.embedding_size} | '
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}')
     say(f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | '
-        f'query transform {Gs.Query.transform} | validation {Gs.use_valid_dataset}')
+        f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
+        f'validation {Gs.use_valid_dataset}')
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
 
     dataset_train = GraphDataset(

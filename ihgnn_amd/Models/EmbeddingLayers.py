@@ -7,7 +7,10 @@ padding row, xavier-uniform initialised), but the full-graph lookup that every t
 
 * users / items: ids are exactly ``1..U`` / ``1..I`` (``Dataset.py:153-154``), so the "lookup" is the view
   ``weight[1:]`` - no kernel, and its backward is a plain dense gradient;
-* queries: the HIP embedding-bag mean kernel over the CSR of query words (``ihg_bag_mean_fwd/bwd``).
+* queries: the HIP embedding-bag mean kernel over the CSR of query words (``ihg_bag_mean_fwd/bwd``); with ``Gs.Query.transform == Gsv.activation`` the
+  reference's ``query_transform = nn.Sequential(nn.Linear(d, d), Gs.Query.transform_activation())`` (``EmbeddingLayers.py:40-44``, applied at 83-84) on top of it:
+  the module is built as in the reference (state-dict keys, shapes, default init, RNG consumption), its forward is the row GEMM with the activation in its
+  epilogue (``ihg_rows_linear_act_fwd/bwd``) - ``nn.ReLU`` and ``nn.Tanh``.  ``Gsv.rnn`` raises, as in the reference.
 """
 from typing import Optional, Tuple
 
@@ -19,16 +22,33 @@ from .. import ops
 from ..Helpers.GlobalSettings import Gs, Gsv
 
 
+QUERY_ACTIVATION_NAMES = {nn.ReLU: 'relu', nn.Tanh: 'tanh'}     # Gs.Query.transform_activation -> ops.QUERY_ACTIVATIONS
+
+
 class EmbeddingLayer(nn.Module):
     def __init__(self, dataset, embedding_size: int):
         super().__init__()
-        if Gs.Query.transform != Gsv.mean:
-            raise NotImplementedError('only the mean query transform is on the MI355X path (GlobalSettings.py:71-73)')
+        if Gs.Query.transform not in (Gsv.mean, Gsv.activation):
+            raise NotImplementedError(f'query transform {Gs.Query.transform!r}: mean and activation are on the MI355X path (the reference itself raises for rnn, EmbeddingLayers.py:45-46)')
         self.dataset = dataset
         self.embedding_size = embedding_size
         self.embedding_user = EmbeddingLayer.create_embedding(dataset.user_count + 1, embedding_size, padding_idx=0)
         self.embedding_item = EmbeddingLayer.create_embedding(dataset.item_count + 1, embedding_size, padding_idx=0)
         self.embedding_bag_vocabulary = EmbeddingLayer.create_embedding_bag(dataset.vocab_size + 1, embedding_size)
+        self.query_activation: Optional[str] = None           # the activation's name for the kernels ('relu' | 'tanh'); None: the plain bag mean
+        if Gs.Query.transform == Gsv.activation:
+            act = Gs.Query.transform_activation
+            if act not in QUERY_ACTIVATION_NAMES:
+                raise NotImplementedError(f'query transform activation {act!r}: nn.ReLU and nn.Tanh are on the MI355X path')
+            self.query_activation = QUERY_ACTIVATION_NAMES[act]
+            self.query_transform = nn.Sequential(nn.Linear(embedding_size, embedding_size), act())      # (EmbeddingLayers.py:40-44: same keys, init and RNG draws)
+
+    def _transform(self):
+        """``(W_q, b_q, activation name)`` for the ops, ``(None, None, None)`` under the mean transform."""
+        if self.query_activation is None:
+            return None, None, None
+        linear = self.query_transform[0]
+        return linear.weight, linear.bias, self.query_activation
 
     def forward(self, user_indices: Optional[Tensor] = None, query_indices: Optional[Tensor] = None,
                 item_indices: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
@@ -37,7 +57,7 @@ class EmbeddingLayer(nn.Module):
     def all_nodes(self, out: Optional[Tensor] = None) -> Tensor:
         """``torch.cat(self(None, None, None))`` as one op (``RawGnn.py:112-113``): ``[U+Q+I, d]``.  ``out`` (inference only): write into
         this ``[N, d]`` destination (a column slice of the feature matrix)."""
-        return ops.embed_all_nodes(self.embedding_user.weight, self.embedding_item.weight, self.embedding_bag_vocabulary.weight, self.dataset.bag_layout, out)
+        return ops.embed_all_nodes(self.embedding_user.weight, self.embedding_item.weight, self.embedding_bag_vocabulary.weight, self.dataset.bag_layout, out, *self._transform())
 
     def node_tables(self, holder):
         """The same features WITHOUT assembling them (``ops.NodeTables``): the first layer's node-level transform reads the tables in place and its backward writes
@@ -45,7 +65,7 @@ class EmbeddingLayer(nn.Module):
         tables = (self.embedding_user.weight, self.embedding_item.weight, self.embedding_bag_vocabulary.weight)
         if not ops.NodeTables.supported(*tables):
             return None
-        return ops.NodeTables(*tables, self.dataset.bag_layout, holder)
+        return ops.NodeTables(*tables, self.dataset.bag_layout, holder, *self._transform())
 
     def embed_user(self, user_indices: Optional[Tensor] = None) -> Tensor:
         w = self.embedding_user.weight
@@ -56,7 +76,7 @@ class EmbeddingLayer(nn.Module):
         return w[1:] if item_indices is None else w[item_indices + 1]
 
     def embed_query(self, query_indices: Optional[Tensor] = None) -> Tensor:
-        queries = ops.bag_mean(self.embedding_bag_vocabulary.weight, self.dataset.bag_layout)
+        queries = ops.bag_mean(self.embedding_bag_vocabulary.weight, self.dataset.bag_layout, *self._transform())
         return queries if query_indices is None else queries[query_indices]
 
     @staticmethod

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # IHGNN_HIP_LIBRARY points at another build of the same ABI (A/B timing of kernel variants); default: the in-tree library
 LIB_PATH = os.environ.get('IHGNN_HIP_LIBRARY') or os.path.join(_HERE, 'csrc', 'libihgnn_hip.so')
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 OK, ERR_INVALID, ERR_LAUNCH, ERR_WORKSPACE = 0, -1, -2, -3
 SCALE_NONE, SCALE_MULTIPLY, SCALE_DIVIDE = 0, 1, 2
@@ -83,6 +83,9 @@ SIGNATURES = {
     'ihg_node_interact_bwd_weight': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, _i64p,
                                                     c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     'ihg_node_linear_workspace_bytes': (c_int64, [c_int32]),
+    'ihg_rows_linear_act_fwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    'ihg_rows_linear_act_bwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                               c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     'ihg_node_linear_bwd_accumulates': (c_int32, [c_int32, c_int64, c_int64, c_int64]),
     'ihg_node_linear_fwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int64, _i64p,
                                            c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),

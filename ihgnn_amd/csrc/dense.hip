@@ -14,6 +14,27 @@ namespace {
 //   row_gemm_kernel        out[v][n]   = sum_k in[v][k] * B_t[k][n] (+ bias[n])     fwd (B = W^T) and input-grad (B = W)
 //   dense_weight_grad      dW_t[c][j]  = sum_{v in t} dout[v][c] * x[v][j],  db[c] = sum_v dout[v][c]
 // ================================================================================================
+// Activations of the query transform (Models/EmbeddingLayers.py:40-44): 0 = none, IHG_ACT_RELU, IHG_ACT_TANH.  act_slope is act'(z) written in y = act(z) -
+// y > 0 / 1 - y^2 - so a backward pass needs y only: dz = dy * act_slope(y) is formed where dy is loaded and neither z nor dz is ever stored.
+template <int ACT>
+__device__ __forceinline__ float act_apply(float z) {
+    if (ACT == 1) return z > 0.f ? z : 0.f;
+    if (ACT == 2) return tanhf(z);
+    return z;
+}
+template <int ACT>
+__device__ __forceinline__ float act_dz(float dy, float y) {
+    if (ACT == 1) return y > 0.f ? dy : 0.f;
+    if (ACT == 2) return dy * (1.f - y * y);
+    return dy;
+}
+template <int ACT>
+__device__ __forceinline__ v4f act_dz4(v4f dy, const float* __restrict__ y) {
+    if (ACT == 0) return dy;
+    const v4f yv = *reinterpret_cast<const v4f*>(y);
+    return v4f{act_dz<ACT>(dy[0], yv[0]), act_dz<ACT>(dy[1], yv[1]), act_dz<ACT>(dy[2], yv[2]), act_dz<ACT>(dy[3], yv[3])};
+}
+
 struct TypePlan {
     int64_t begin[4];        // row ranges of the three node types: [begin[t], begin[t+1])
     int tile_prefix[4];      // cumulative workgroup tiles per type
@@ -46,10 +67,12 @@ __global__ __launch_bounds__(kBlockThreads) void pack_dense_kernel(const float* 
 // Register-prefetch pipeline: the rows of tile n+1 are fetched while tile n is multiplied.  vmcnt retires in issue order, so
 // the (tiny, cache-resident) weight fragments of the current tile are pulled into registers BEFORE the prefetch is issued;
 // D = 256 would need 512 registers for that and keeps the plain fetch-then-multiply order.
-template <int D>
+// ACT_OUT: out = act(in * B + bias) in the epilogue.  ACT_IN: the rows multiplied are in * act'(y) (y [rows, D], stride ld_y), formed as they are loaded.
+template <int D, int ACT_OUT = 0, int ACT_IN = 0>
 __global__ __launch_bounds__(kBlockThreads) void row_gemm_kernel(const float* __restrict__ in, int64_t ld_in, const float* __restrict__ pk,
                                                                  int64_t pk_type_stride, const float* __restrict__ bias, int bias_mask,
-                                                                 int64_t bias_type_stride, TypePlan plan, float* __restrict__ out, int64_t ld_out) {
+                                                                 int64_t bias_type_stride, TypePlan plan, float* __restrict__ out, int64_t ld_out,
+                                                                 const float* __restrict__ y, int64_t ld_y) {
     constexpr int ET = D == 32 ? 4 : 2, TE = ET * 32, STRIDE = D + kRowPad, JOBS = ET * (D / 32);
     constexpr int V4_PER_ROW = D / 4, LOADS = TE * V4_PER_ROW / kBlockThreads, T_STEPS = D / 8;
     constexpr int JOBS_PER_WAVE = JOBS / kWavesPerBlock;
@@ -90,7 +113,7 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_kernel(const float* __
             for (int k = 0; k < LOADS; ++k) {
                 const int idx = tid + kBlockThreads * k;
                 const int64_t v = r_base + idx / V4_PER_ROW;
-                xreg[k] = v < r_end ? *reinterpret_cast<const v4f*>(in + v * ld_in + (idx % V4_PER_ROW) * 4) : v4f{0.f, 0.f, 0.f, 0.f};
+                xreg[k] = v < r_end ? act_dz4<ACT_IN>(*reinterpret_cast<const v4f*>(in + v * ld_in + (idx % V4_PER_ROW) * 4), y + v * ld_y + (idx % V4_PER_ROW) * 4) : v4f{0.f, 0.f, 0.f, 0.f};
             }
         }
         if (cur >= 0) {
@@ -119,11 +142,11 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_kernel(const float* __
                 float* orow = out + (r_base + et * 32) * ld_out + c;
                 if (r_base + TE <= r_end) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) orow[static_cast<int64_t>(acc_row(r, lane)) * ld_out] = acc[r] + bv;
+                    for (int r = 0; r < 16; ++r) orow[static_cast<int64_t>(acc_row(r, lane)) * ld_out] = act_apply<ACT_OUT>(acc[r] + bv);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        if (r_base + et * 32 + acc_row(r, lane) < r_end) orow[static_cast<int64_t>(acc_row(r, lane)) * ld_out] = acc[r] + bv;
+                        if (r_base + et * 32 + acc_row(r, lane) < r_end) orow[static_cast<int64_t>(acc_row(r, lane)) * ld_out] = act_apply<ACT_OUT>(acc[r] + bv);
                 }
             }
         }
@@ -135,7 +158,7 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_kernel(const float* __
             for (int k = 0; k < LOADS; ++k) {
                 const int idx = tid + kBlockThreads * k;
                 const int64_t v = r_base + idx / V4_PER_ROW;
-                xreg[k] = v < r_end ? *reinterpret_cast<const v4f*>(in + v * ld_in + (idx % V4_PER_ROW) * 4) : v4f{0.f, 0.f, 0.f, 0.f};
+                xreg[k] = v < r_end ? act_dz4<ACT_IN>(*reinterpret_cast<const v4f*>(in + v * ld_in + (idx % V4_PER_ROW) * 4), y + v * ld_y + (idx % V4_PER_ROW) * 4) : v4f{0.f, 0.f, 0.f, 0.f};
             }
         }
         if (!have_next) break;
@@ -148,13 +171,14 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_kernel(const float* __
 // Same register-prefetch pipeline as the interactive weight-gradient kernel.
 // FUSE_DX (d == SW == 64): the dout tile is in LDS anyway, so the input gradient dx = dout * W_type of the same rows is
 // computed here too (weight fragments in registers for the whole kernel) and the separate row-GEMM launch over dout goes away.
-template <int SW, bool FUSE_DX>
-__global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_kernel(const float* __restrict__ dout, int64_t ld_dout,
-                                                                          const float* __restrict__ x, int64_t ld_x, TypePlan plan,
-                                                                          int single_weight, float* __restrict__ slabs,
-                                                                          float* __restrict__ bias_slabs, int d, const float* __restrict__ w,
-                                                                          int64_t ld_w, int64_t w_type_stride, float* __restrict__ dx, int64_t ld_dx,
-                                                                          int dx_accumulate) {
+// ACT: dout stands for dout * act'(y) (the cotangent of the pre-activation), formed as the tile is loaded: weight, bias and input gradient all see it.
+template <int SW, bool FUSE_DX, int ACT>
+__device__ __forceinline__ void dense_weight_grad_body(const float* __restrict__ dout, int64_t ld_dout,
+                                                       const float* __restrict__ x, int64_t ld_x, const TypePlan& plan,
+                                                       int single_weight, float* __restrict__ slabs,
+                                                       float* __restrict__ bias_slabs, int d, const float* __restrict__ w,
+                                                       int64_t ld_w, int64_t w_type_stride, float* __restrict__ dx, int64_t ld_dx,
+                                                       int dx_accumulate, const float* __restrict__ y, int64_t ld_y) {
     static_assert(!FUSE_DX || SW == 64, "the fused input gradient covers whole 64-wide rows");
     constexpr int TE = 64, WT = SW / 32, V4_PER_ROW = SW / 4, LOADS = TE * V4_PER_ROW / kBlockThreads;
     constexpr int DSTRIDE = FUSE_DX ? SW + kRowPad : SW;      // padded rows for the ds_read_b128 A-operand reads of the dx product
@@ -207,6 +231,10 @@ __global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_kernel(const 
                 const int64_t v = r_base + r;
                 const bool live = v < r_end;
                 dreg[k] = live ? *reinterpret_cast<const float4*>(dout + v * ld_dout + js * SW + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ACT != 0 && live) {
+                    const float4 yv = *reinterpret_cast<const float4*>(y + v * ld_y + js * SW + c4 * 4);
+                    dreg[k] = make_float4(act_dz<ACT>(dreg[k].x, yv.x), act_dz<ACT>(dreg[k].y, yv.y), act_dz<ACT>(dreg[k].z, yv.z), act_dz<ACT>(dreg[k].w, yv.w));
+                }
                 xreg[k] = live ? *reinterpret_cast<const float4*>(x + v * ld_x + cs * SW + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
@@ -266,6 +294,24 @@ __global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_kernel(const 
             slab[static_cast<int64_t>(js * SW + jt * 32 + acc_row(r, lane)) * d + cs * SW + ct * 32 + l31] = acc[r];
     }
     if (cs == 0 && tid < SW) bias_slabs[(static_cast<int64_t>(type) * n_slabs + blockIdx.x) * d + js * SW + tid] = colsum;
+}
+
+template <int SW, bool FUSE_DX>
+__global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_kernel(const float* __restrict__ dout, int64_t ld_dout,
+                                                                          const float* __restrict__ x, int64_t ld_x, TypePlan plan,
+                                                                          int single_weight, float* __restrict__ slabs,
+                                                                          float* __restrict__ bias_slabs, int d, const float* __restrict__ w,
+                                                                          int64_t ld_w, int64_t w_type_stride, float* __restrict__ dx, int64_t ld_dx,
+                                                                          int dx_accumulate) {
+    dense_weight_grad_body<SW, FUSE_DX, 0>(dout, ld_dout, x, ld_x, plan, single_weight, slabs, bias_slabs, d, w, ld_w, w_type_stride, dx, ld_dx, dx_accumulate, nullptr, 0);
+}
+
+template <int SW, bool FUSE_DX, int ACT>
+__global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_act_kernel(const float* __restrict__ dout, int64_t ld_dout, const float* __restrict__ y, int64_t ld_y,
+                                                                              const float* __restrict__ x, int64_t ld_x, TypePlan plan, float* __restrict__ slabs,
+                                                                              float* __restrict__ bias_slabs, int d, const float* __restrict__ w, int64_t ld_w,
+                                                                              float* __restrict__ dx, int64_t ld_dx) {
+    dense_weight_grad_body<SW, FUSE_DX, ACT>(dout, ld_dout, x, ld_x, plan, 1, slabs, bias_slabs, d, w, ld_w, 0, dx, ld_dx, 0, y, ld_y);
 }
 
 __global__ __launch_bounds__(kBlockThreads) void dense_slab_reduce_kernel(const float* __restrict__ slabs, const float* __restrict__ bias_slabs,
@@ -485,7 +531,7 @@ int launch_row_gemm(int dim, const float* in, int64_t ld_in, const float* w, int
     const TypePlan plan = make_plan(type_begin, dim == 32 ? 128 : 64);
     if (plan.tile_prefix[3] == 0) return IHG_OK;
     const int grid = std::min(plan.tile_prefix[3], 256 * 4);
-#define IHG_RG(D) hipLaunchKernelGGL((row_gemm_kernel<D>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, pk_type_stride, bias, bias_mask, bias_type_stride, plan, out, ld_out)
+#define IHG_RG(D) hipLaunchKernelGGL((row_gemm_kernel<D>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, pk_type_stride, bias, bias_mask, bias_type_stride, plan, out, ld_out, static_cast<const float*>(nullptr), int64_t{0})
     switch (dim) {
         case 32: IHG_RG(32); break;
         case 64: IHG_RG(64); break;
@@ -580,9 +626,11 @@ __global__ __launch_bounds__(kBlockThreads) void compose_bwd_kernel(const float*
 __device__ __forceinline__ int type_of_row(const TypePlan& plan, int64_t v) { return v >= plan.begin[2] ? 2 : (v >= plan.begin[1] ? 1 : 0); }
 
 // transpose == 0: out[v][n] = sum_k in[v][k] W_t[n][k] (+ bias);   transpose == 1: out[v][k] = sum_n in[v][n] W_t[n][k]
-__global__ __launch_bounds__(kBlockThreads) void row_gemm_generic_kernel(const float* __restrict__ in, int64_t ld_in, const float* __restrict__ w, int64_t ld_w,
-                                                                         int64_t w_type_stride, int transpose, const float* __restrict__ bias, int bias_mask,
-                                                                         int64_t bias_type_stride, TypePlan plan, float* __restrict__ out, int64_t ld_out, int d) {
+template <int ACT_OUT, int ACT_IN>
+__device__ __forceinline__ void row_gemm_generic_body(const float* __restrict__ in, int64_t ld_in, const float* __restrict__ w, int64_t ld_w,
+                                                      int64_t w_type_stride, int transpose, const float* __restrict__ bias, int bias_mask,
+                                                      int64_t bias_type_stride, const TypePlan& plan, float* __restrict__ out, int64_t ld_out, int d,
+                                                      const float* __restrict__ y, int64_t ld_y) {
     const int64_t rows = plan.begin[3] - plan.begin[0];
     const int64_t total = rows * d;
     for (int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total; idx += static_cast<int64_t>(gridDim.x) * blockDim.x) {
@@ -596,10 +644,28 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_generic_kernel(const f
             for (int k = 0; k < d; ++k) acc += row[k] * wt[static_cast<int64_t>(n) * ld_w + k];
             if (bias != nullptr && ((bias_mask >> type) & 1)) acc += bias[type * bias_type_stride + n];
         } else {
-            for (int k = 0; k < d; ++k) acc += row[k] * wt[static_cast<int64_t>(k) * ld_w + n];
+            if (ACT_IN != 0) {
+                const float* yrow = y + v * ld_y;
+                for (int k = 0; k < d; ++k) acc += act_dz<ACT_IN>(row[k], yrow[k]) * wt[static_cast<int64_t>(k) * ld_w + n];
+            } else {
+                for (int k = 0; k < d; ++k) acc += row[k] * wt[static_cast<int64_t>(k) * ld_w + n];
+            }
         }
-        out[v * ld_out + n] = acc;
+        out[v * ld_out + n] = act_apply<ACT_OUT>(acc);
     }
+}
+
+__global__ __launch_bounds__(kBlockThreads) void row_gemm_generic_kernel(const float* __restrict__ in, int64_t ld_in, const float* __restrict__ w, int64_t ld_w,
+                                                                         int64_t w_type_stride, int transpose, const float* __restrict__ bias, int bias_mask,
+                                                                         int64_t bias_type_stride, TypePlan plan, float* __restrict__ out, int64_t ld_out, int d) {
+    row_gemm_generic_body<0, 0>(in, ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, plan, out, ld_out, d, nullptr, 0);
+}
+
+template <int ACT_OUT, int ACT_IN>
+__global__ __launch_bounds__(kBlockThreads) void row_gemm_generic_act_kernel(const float* __restrict__ in, int64_t ld_in, const float* __restrict__ w, int64_t ld_w, int transpose,
+                                                                             const float* __restrict__ bias, TypePlan plan, float* __restrict__ out, int64_t ld_out, int d,
+                                                                             const float* __restrict__ y, int64_t ld_y) {
+    row_gemm_generic_body<ACT_OUT, ACT_IN>(in, ld_in, w, ld_w, 0, transpose, bias, 0b111, 0, plan, out, ld_out, d, y, ld_y);
 }
 
 // dW_t[c][j] = sum_{v in t} dout[v][c] x[v][j] and the bias gradient for ANY width: grid = (row slabs, 16 x 16 output tiles, weight
@@ -609,9 +675,10 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_generic_kernel(const f
 constexpr int kGenericSlabs = 64;
 constexpr int kGenericChunk = 32;
 
-__global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_generic_kernel(const float* __restrict__ dout, int64_t ld_dout, const float* __restrict__ x,
-                                                                                  int64_t ld_x, TypePlan plan, int single_weight, int d,
-                                                                                  float* __restrict__ slabs, float* __restrict__ bias_slabs) {
+template <int ACT>
+__device__ __forceinline__ void dense_weight_grad_generic_body(const float* __restrict__ dout, int64_t ld_dout, const float* __restrict__ x,
+                                                               int64_t ld_x, const TypePlan& plan, int single_weight, int d,
+                                                               float* __restrict__ slabs, float* __restrict__ bias_slabs, const float* __restrict__ y, int64_t ld_y) {
     __shared__ float dt[kGenericChunk][17], xt[kGenericChunk][17];
     const int tiles = (d + 15) / 16;
     const int tc = blockIdx.y / tiles, tj = blockIdx.y % tiles, type = blockIdx.z;
@@ -626,7 +693,7 @@ __global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_generic_kerne
             const int r = idx >> 4, k = idx & 15;
             const int64_t v = base + r;
             const bool live = v < v1;
-            dt[r][k] = live && 16 * tc + k < d ? dout[v * ld_dout + 16 * tc + k] : 0.f;
+            dt[r][k] = live && 16 * tc + k < d ? act_dz<ACT>(dout[v * ld_dout + 16 * tc + k], ACT != 0 ? y[v * ld_y + 16 * tc + k] : 0.f) : 0.f;
             xt[r][k] = live && 16 * tj + k < d ? x[v * ld_x + 16 * tj + k] : 0.f;
         }
         __syncthreads();
@@ -641,6 +708,19 @@ __global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_generic_kerne
     const int64_t slab = static_cast<int64_t>(type) * n_slabs + blockIdx.x;
     if (16 * tc + c < d && 16 * tj + j < d) slabs[(slab * d + 16 * tc + c) * d + 16 * tj + j] = acc;
     if (tj == 0 && j == 0 && 16 * tc + c < d) bias_slabs[slab * d + 16 * tc + c] = colsum;
+}
+
+__global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_generic_kernel(const float* __restrict__ dout, int64_t ld_dout, const float* __restrict__ x,
+                                                                                  int64_t ld_x, TypePlan plan, int single_weight, int d,
+                                                                                  float* __restrict__ slabs, float* __restrict__ bias_slabs) {
+    dense_weight_grad_generic_body<0>(dout, ld_dout, x, ld_x, plan, single_weight, d, slabs, bias_slabs, nullptr, 0);
+}
+
+template <int ACT>
+__global__ __launch_bounds__(kBlockThreads) void dense_weight_grad_generic_act_kernel(const float* __restrict__ dout, int64_t ld_dout, const float* __restrict__ y, int64_t ld_y,
+                                                                                      const float* __restrict__ x, int64_t ld_x, TypePlan plan, int d,
+                                                                                      float* __restrict__ slabs, float* __restrict__ bias_slabs) {
+    dense_weight_grad_generic_body<ACT>(dout, ld_dout, x, ld_x, plan, 1, d, slabs, bias_slabs, y, ld_y);
 }
 
 __global__ __launch_bounds__(kBlockThreads) void dense_generic_reduce_kernel(const float* __restrict__ slabs, const float* __restrict__ bias_slabs, int n_slabs,
@@ -886,6 +966,133 @@ int ihg_node_linear_bwd_weight_typed(const float* dout, int64_t ld_dout, const f
     hipLaunchKernelGGL(dense_slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, bias_slabs,
                        n_slabs, n_types, dim, dw, ld_dw, dw_type_stride, dbias, bias_type_mask, n_types == 1 ? int64_t{0} : dbias_type_stride);
     return check_launch("ihg_node_linear_bwd_weight_typed");
+}
+
+// ------------------------------------------------------------------------------------------------
+// The query transform nn.Sequential(nn.Linear(d, d), act) over the bag means (Models/EmbeddingLayers.py:40-44, 83-84): the row GEMM above with the activation in
+// its epilogue, and a backward that forms dz = dy * act'(y) where dy is loaded.  Forward at d = 128 / 256: the split-arithmetic row GEMM (split_node.hip) by default, the
+// fp32-MFMA kernel under IHG_INTERACT_ARITH=f32; d = 32 / 64 and the whole backward: fp32 MFMA (v_mfma_f32_32x32x2_f32) in either mode; any-width kernels elsewhere.
+// ------------------------------------------------------------------------------------------------
+static int rows_linear_act_check(const char* what, int32_t dim, int32_t activation, int64_t n_rows, int64_t ld_a, int64_t ld_b, int64_t ld_w, const void* workspace,
+                                 int64_t workspace_bytes) {
+    if (dim <= 0 || n_rows < 0) return fail(IHG_ERR_INVALID, "%s: dim %d, %lld rows", what, dim, static_cast<long long>(n_rows));
+    if (activation != IHG_ACT_RELU && activation != IHG_ACT_TANH) return fail(IHG_ERR_INVALID, "%s: activation %d (IHG_ACT_RELU or IHG_ACT_TANH)", what, activation);
+    if (ld_a < dim || ld_b < dim || ld_w < dim) return fail(IHG_ERR_INVALID, "%s: bad leading dimension", what);
+    if (workspace == nullptr || !aligned16(workspace)) return fail(IHG_ERR_INVALID, "%s: workspace null or not 16-byte aligned", what);
+    if (workspace_bytes < ihg_node_linear_workspace_bytes(dim)) return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", what);
+    return IHG_OK;
+}
+
+// the tiled row GEMM with an activation on either side: transpose == 0 is the forward (B = W^T, bias, ACT_OUT), transpose == 1 the input gradient (B = W, ACT_IN over y)
+static void launch_row_gemm_act(int dim, int activation, int transpose, const float* in, int64_t ld_in, const float* y, int64_t ld_y, const float* w, int64_t ld_w,
+                                const float* bias, int64_t n_rows, float* out, int64_t ld_out, float* pk, hipStream_t s) {
+    const int pack_items = (dim / 32) * (dim / 8) * kWave;
+    hipLaunchKernelGGL(pack_dense_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, int64_t{0}, 1, dim, transpose, pk);
+    const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
+    const TypePlan plan = make_plan(type_begin, dim == 32 ? 128 : 64);
+    const int grid = std::min(plan.tile_prefix[3], 256 * 4);
+#define IHG_RGA(D, AO, AI) hipLaunchKernelGGL((row_gemm_kernel<D, AO, AI>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, int64_t{0}, bias, 0b111, int64_t{0}, plan, out, ld_out, y, ld_y)
+#define IHG_RGA_D(D)                                             \
+    if (transpose == 0) {                                        \
+        if (activation == IHG_ACT_RELU) IHG_RGA(D, 1, 0);        \
+        else IHG_RGA(D, 2, 0);                                   \
+    } else {                                                     \
+        if (activation == IHG_ACT_RELU) IHG_RGA(D, 0, 1);        \
+        else IHG_RGA(D, 0, 2);                                   \
+    }
+    switch (dim) {
+        case 32: IHG_RGA_D(32); break;
+        case 64: IHG_RGA_D(64); break;
+        case 128: IHG_RGA_D(128); break;
+        default: IHG_RGA_D(256); break;
+    }
+#undef IHG_RGA_D
+#undef IHG_RGA
+}
+
+int ihg_rows_linear_act_fwd(const float* x, int64_t ld_x, const float* w, int64_t ld_w, const float* bias, int32_t activation, float* out, int64_t ld_out,
+                            int64_t n_rows, void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
+    if (int rc = rows_linear_act_check("ihg_rows_linear_act_fwd", dim, activation, n_rows, ld_x, ld_out, ld_w, workspace, workspace_bytes)) return rc;
+    if (n_rows == 0) return IHG_OK;
+    if (x == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_fwd: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ld_x % 4 == 0 && aligned16(x) && split_row_gemm_ok(dim, out, ld_out, bias, 0)) {
+        // d = 128 / 256 in the split arithmetic (the default): the node-level maps' own row GEMM - two fp16 terms per operand - with the activation in its epilogue;
+        // its planes sit behind the slabs, as in launch_row_gemm.  IHG_INTERACT_ARITH=f32, or an `out` that is not 16-byte aligned: the fp32-MFMA kernel below
+        const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
+        void* planes = static_cast<float*>(workspace) + 3LL * dim * dim + 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
+        launch_row_gemm_split(dim, typed_rows(x), ld_x, w, ld_w, 0, 0, bias, 0b111, 0, type_begin, typed_rows_out(out), ld_out, planes, s, 0, activation);
+    } else if (mfma_dim(dim) && ld_x % 4 == 0 && aligned16(x)) {   // (this kernel stores single floats: any out, any ld_out - a column slice of the feature matrix)
+        launch_row_gemm_act(dim, activation, 0, x, ld_x, nullptr, 0, w, ld_w, bias, n_rows, out, ld_out, static_cast<float*>(workspace), s);
+    } else {
+        const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
+        const TypePlan plan = make_plan(type_begin, 64);
+        const int grid = static_cast<int>(std::min<int64_t>((n_rows * dim + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
+        if (activation == IHG_ACT_RELU)
+            hipLaunchKernelGGL((row_gemm_generic_act_kernel<1, 0>), dim3(grid), dim3(kBlockThreads), 0, s, x, ld_x, w, ld_w, 0, bias, plan, out, ld_out, dim, static_cast<const float*>(nullptr), int64_t{0});
+        else
+            hipLaunchKernelGGL((row_gemm_generic_act_kernel<2, 0>), dim3(grid), dim3(kBlockThreads), 0, s, x, ld_x, w, ld_w, 0, bias, plan, out, ld_out, dim, static_cast<const float*>(nullptr), int64_t{0});
+    }
+    return check_launch("ihg_rows_linear_act_fwd");
+}
+
+int ihg_rows_linear_act_bwd(const float* dy, int64_t ld_dy, const float* y, int64_t ld_y, const float* x, int64_t ld_x, const float* w, int64_t ld_w, int32_t activation,
+                            float* dw, int64_t ld_dw, float* dbias, float* dx, int64_t ld_dx, int64_t n_rows, void* workspace, int64_t workspace_bytes, int32_t dim,
+                            ihg_stream_t stream) {
+    if (int rc = rows_linear_act_check("ihg_rows_linear_act_bwd", dim, activation, n_rows, ld_dy, ld_x, ld_w, workspace, workspace_bytes)) return rc;
+    if (ld_y < dim || ld_dw < dim || (dx != nullptr && ld_dx < dim)) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_bwd: bad leading dimension");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_rows == 0) {                                             // no rows (empty tensors come with null pointers): dW = 0, db = 0, nothing to write to dx
+        if (dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_bwd: null pointer");
+        for (int c = 0; c < dim; ++c) launch_zero_floats(dw + static_cast<int64_t>(c) * ld_dw, dim, s);
+        if (dbias != nullptr) launch_zero_floats(dbias, dim, s);
+        return check_launch("ihg_rows_linear_act_bwd");
+    }
+    if (dy == nullptr || y == nullptr || x == nullptr || w == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_bwd: null pointer");
+    const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
+    const TypePlan plan = make_plan(type_begin, 64);
+    const bool relu = activation == IHG_ACT_RELU;
+    const bool tiled = mfma_dim(dim) && ld_dy % 4 == 0 && ld_y % 4 == 0 && ld_x % 4 == 0 && aligned16(dy) && aligned16(y) && aligned16(x);
+    if (!tiled) {
+        float* gslabs = static_cast<float*>(workspace);
+        float* gbias = gslabs + 3LL * kGenericSlabs * dim * dim;
+        if (dx != nullptr && n_rows > 0) {
+            const int grid = static_cast<int>(std::min<int64_t>((n_rows * dim + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
+            if (relu) hipLaunchKernelGGL((row_gemm_generic_act_kernel<0, 1>), dim3(grid), dim3(kBlockThreads), 0, s, dy, ld_dy, w, ld_w, 1, static_cast<const float*>(nullptr), plan, dx, ld_dx, dim, y, ld_y);
+            else hipLaunchKernelGGL((row_gemm_generic_act_kernel<0, 2>), dim3(grid), dim3(kBlockThreads), 0, s, dy, ld_dy, w, ld_w, 1, static_cast<const float*>(nullptr), plan, dx, ld_dx, dim, y, ld_y);
+        }
+        const int tiles = (dim + 15) / 16;
+        if (relu) hipLaunchKernelGGL((dense_weight_grad_generic_act_kernel<1>), dim3(kGenericSlabs, tiles * tiles, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan, dim, gslabs, gbias);
+        else hipLaunchKernelGGL((dense_weight_grad_generic_act_kernel<2>), dim3(kGenericSlabs, tiles * tiles, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan, dim, gslabs, gbias);
+        const int64_t total = static_cast<int64_t>(dim) * dim + dim;
+        hipLaunchKernelGGL(dense_generic_reduce_kernel, dim3(static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks))), dim3(kBlockThreads), 0, s,
+                           gslabs, gbias, kGenericSlabs, 1, dim, dw, ld_dw, int64_t{0}, dbias, 0b111, int64_t{0});
+        return check_launch("ihg_rows_linear_act_bwd");
+    }
+    float* pk = static_cast<float*>(workspace);
+    float* slabs = pk + 3LL * dim * dim;
+    float* bias_slabs = slabs + 3LL * kDenseSlabs * dim * dim;
+    const bool fused_dx = dx != nullptr && dim == 64;                // d = 64: dm = dz * W from the dz tile that is in LDS for the weight gradient anyway
+    if (dx != nullptr && !fused_dx && n_rows > 0) launch_row_gemm_act(dim, activation, 1, dy, ld_dy, y, ld_y, w, ld_w, nullptr, n_rows, dx, ld_dx, pk, s);
+    float* const no_dx = nullptr;
+#define IHG_DWA(SW, FUSE, SUBS, DX)                                                                                                                                   \
+    if (relu) hipLaunchKernelGGL((dense_weight_grad_act_kernel<SW, FUSE, 1>), dim3(kDenseSlabs, SUBS, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan, \
+                                 slabs, bias_slabs, dim, w, ld_w, DX, ld_dx);                                                                                         \
+    else hipLaunchKernelGGL((dense_weight_grad_act_kernel<SW, FUSE, 2>), dim3(kDenseSlabs, SUBS, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan,      \
+                            slabs, bias_slabs, dim, w, ld_w, DX, ld_dx)
+    if (fused_dx) {
+        IHG_DWA(64, true, 1, dx);
+    } else if (dim == 32) {
+        IHG_DWA(32, false, 1, no_dx);
+    } else {
+        const int subs = (dim / 64) * (dim / 64);
+        IHG_DWA(64, false, subs, no_dx);
+    }
+#undef IHG_DWA
+    const int total = dim * dim + dim;
+    hipLaunchKernelGGL(dense_slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, bias_slabs, kDenseSlabs, 1, dim, dw, ld_dw, int64_t{0},
+                       dbias, 0b111, int64_t{0});
+    return check_launch("ihg_rows_linear_act_bwd");
 }
 
 int ihg_compose_first_order_fwd(const float* a, int64_t ld_a, const float* c, const float* w, int64_t ld_w, const float* b, float* w_eff,

@@ -1287,7 +1287,17 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_dense_h2_kernel(con
 // after the request (two tiles of 16 KB in flight per workgroup instead of one: the kernel is a stream whose rate is bytes in flight over the memory round trip).
 // ACC (out += ...) is a template parameter (round 5): as a run-time flag its two accumulator-shaped registers and the branch around their loads were in every instance - at
 // D = 256 the four registers the kernel spilled (256 VGPRs + 20 B of scratch per lane; now no scratch).
-template <int D, bool ACC>
+// tanh for the epilogue of a kernel that has no registers to spare (tanhf's range reduction costs the D = 256 instance 8 spilled VGPRs): the odd Taylor polynomial
+// to x^7 below |x| = 0.1 (next term 2.2e-2 x^9: < 3e-11 there), 1 - 2 / (exp(2|x|) + 1) above it (v_exp_f32 + v_rcp_f32: absolute error ~ 1.5e-7 where tanh >= 0.0997)
+__device__ __forceinline__ float tanh_lean(float x) {
+    const float a = fabsf(x), x2 = x * x;
+    const float small = x * (1.f + x2 * (-0.33333334f + x2 * (0.13333334f - 0.053968254f * x2)));
+    const float big = copysignf(1.f - 2.f * __frcp_rn(__expf(2.f * a) + 1.f), x);
+    return a < 0.1f ? small : big;
+}
+
+// ACT (the query transform, ihg_rows_linear_act_fwd): 1 = ReLU, 2 = Tanh applied to the finished rows in the epilogue (0: none - the node-level maps).
+template <int D, bool ACC, int ACT = 0>
 __global__ __launch_bounds__(512, 2) void row_gemm_split_kernel(TypedRows in, int64_t ld_in, const v4u* __restrict__ pk,
                                                                              int64_t pk_type_stride, const float* __restrict__ winv, const float* __restrict__ bias, int bias_mask,
                                                                              int64_t bias_type_stride, RowTiles plan, TypedRowsOut out, int64_t ld_out) {
@@ -1434,6 +1444,8 @@ __global__ __launch_bounds__(512, 2) void row_gemm_split_kernel(TypedRows in, in
             if (v < r_end) {
                 v4f y = acc[rt] * (wiv * (rt == 0 ? iv0 : iv1)) + bv;
                 if (ACC) y += gold[rt];
+                if (ACT == 1) y = v4f{y[0] > 0.f ? y[0] : 0.f, y[1] > 0.f ? y[1] : 0.f, y[2] > 0.f ? y[2] : 0.f, y[3] > 0.f ? y[3] : 0.f};
+                if (ACT == 2) y = v4f{tanh_lean(y[0]), tanh_lean(y[1]), tanh_lean(y[2]), tanh_lean(y[3])};
                 *reinterpret_cast<v4f*>(typed_base(out, type) + v * ld_out + c4) = y;
             }
         }
@@ -1789,7 +1801,7 @@ bool split_row_gemm_ok(int dim, const float* out, int64_t ld_out, const float* b
 }
 
 void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias,
-                           int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, TypedRowsOut out, int64_t ld_out, void* planes, hipStream_t s, int accumulate) {
+                           int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, TypedRowsOut out, int64_t ld_out, void* planes, hipStream_t s, int accumulate, int activation) {
     const int n_types = w_type_stride == 0 ? 1 : 3;
     v4u* pk = static_cast<v4u*>(planes);
     const int items = n_types * (dim / 16) * (dim / 32) * kWave;
@@ -1813,6 +1825,19 @@ void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w,
     const int n_seq = std::min((acc + 7) / 8 * 8, 256);                  // (d = 256) tile sequences: a multiple of 8, so that both halves of one land on one XCD
 #define IHG_ROW_GEMM(D, ACC, GRID) \
     hipLaunchKernelGGL((row_gemm_split_kernel<D, ACC>), dim3(GRID), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride, plan, out, ld_out)
+#define IHG_ROW_GEMM_ACT(D, ACT, GRID) \
+    hipLaunchKernelGGL((row_gemm_split_kernel<D, false, ACT>), dim3(GRID), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride, plan, out, ld_out)
+    if (activation != 0) {                                               // (out = act(...): never accumulating)
+        if (dim == 128) {
+            if (activation == 1) IHG_ROW_GEMM_ACT(128, 1, std::min(acc, 256));
+            else IHG_ROW_GEMM_ACT(128, 2, std::min(acc, 256));
+        } else {
+            if (activation == 1) IHG_ROW_GEMM_ACT(256, 1, 2 * n_seq);
+            else IHG_ROW_GEMM_ACT(256, 2, 2 * n_seq);
+        }
+        return;
+    }
+#undef IHG_ROW_GEMM_ACT
     if (dim == 128) {
         if (accumulate) IHG_ROW_GEMM(128, true, std::min(acc, 256));
         else IHG_ROW_GEMM(128, false, std::min(acc, 256));

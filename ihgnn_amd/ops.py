@@ -9,6 +9,7 @@ Operator               forward kernel              backward kernel(s)
 edge_gather_sum  (K5)  ihg_edge_gather_sum         ihg_node_segment_sum   (its transpose)
 node_segment_sum (K7)  ihg_node_segment_sum         ihg_edge_gather_sum    (its transpose)
 bag_mean         (K2)  ihg_bag_mean_fwd            ihg_bag_mean_bwd
+ + query transform     ihg_rows_linear_act_fwd     ihg_rows_linear_act_bwd  (in front of ihg_bag_mean_bwd)
 interact     (K5+K6)   ihg_interact_fwd            ihg_interact_bwd + 4x ihg_node_segment_sum
 gat_attention          ihg_gat_attention_fwd + K7  ihg_gat_scores_bwd, K7, ihg_gat_finish_bwd
 hyper_attention        ihg_phase2_attention_fwd    ihg_phase2_scores_bwd, ihg_phase2_edges_bwd, (K7,) ihg_phase2_finish_bwd
@@ -629,42 +630,101 @@ class BagLayout:
         self.n_bags, self.table_rows = int(offsets.shape[0]), int(table_rows)
         self.bags = Csr(ptr, words.astype(np.int32), device, heavy_threshold=0)
         self.words_of = self.bags.transpose(table_rows)
+        if words.size == 0:
+            # no query has a word: every row of both lists is empty and no id is ever read, but the library refuses a null id list - one id that nobody reads
+            self.bags.ids = self.words_of.ids = torch.zeros(1, dtype=torch.int32, device=device)
         lens = np.diff(ptr.astype(np.int64)).astype(np.float32)
         self.bag_len = torch.from_numpy(lens).to(device)
         inv = np.where(lens > 0, 1.0 / np.maximum(lens, 1), 0).astype(np.float32)
         self.inv_len = torch.from_numpy(inv).to(device)
 
 
+QUERY_ACTIVATIONS = {'relu': 1, 'tanh': 2}                          # the names of Gs.Query.transform_activation -> IHG_ACT_RELU / IHG_ACT_TANH
+
+
+def _query_activation(name: Optional[str]) -> int:
+    if name not in QUERY_ACTIVATIONS:
+        raise ValueError(f'query transform: unknown activation {name!r} (one of {sorted(QUERY_ACTIVATIONS)})')
+    return QUERY_ACTIVATIONS[name]
+
+
+def _query_transform_operands(wq: Optional[Tensor], bq: Optional[Tensor], dim: int):
+    """``(W_q, b_q)`` of the query transform as the library takes them (``None, None``: the plain bag mean)."""
+    if wq is None:
+        return None, None
+    if bq is None or tuple(wq.shape) != (dim, dim) or tuple(bq.shape) != (dim,):
+        raise ValueError(f'the query transform is a [{dim}, {dim}] weight with a [{dim}] bias, got {tuple(wq.shape)} and {None if bq is None else tuple(bq.shape)}')
+    return _rows(wq, 'query transform weight'), bq.contiguous()
+
+
+def _query_rows_forward(word_table: Tensor, bag: BagLayout, wq: Optional[Tensor], bq: Optional[Tensor], act: int, out: Tensor) -> Optional[Tensor]:
+    """The query rows of X0 into ``out`` (``[Q, d]``, any row stride - a row block of X0 or of a column slice of the feature matrix): the bag means ``m`` of the
+    queries' words (``ihg_bag_mean_fwd``), or - with a transform ``wq``, ``bq``, ``act`` (``Gs.Query.transform == 'activation'``) - ``act(m wq^T + bq)``
+    (``ihg_rows_linear_act_fwd``; an empty bag gives ``act(bq)``).  Returns ``m`` then (the transform's backward reads it; outside autograd the caller drops it), else ``None``."""
+    lib = _lib.load()
+    q, dim = bag.n_bags, int(word_table.shape[1])
+    means = out if wq is None else torch.empty(q, dim, dtype=torch.float32, device=word_table.device)
+    if q > 0:
+        with profiler.kernel('bag_mean_fwd', q, dim):
+            _lib.check(lib.ihg_bag_mean_fwd(_ptr(word_table), _ld(word_table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len),
+                                            _ptr(means), _ld(means), q, dim, _stream()), 'ihg_bag_mean_fwd')
+    if wq is None:
+        return None
+    if q > 0:
+        ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), word_table.device)
+        with profiler.kernel('query_transform_fwd', q, dim):
+            _lib.check(lib.ihg_rows_linear_act_fwd(_ptr(means), dim, _ptr(wq), int(wq.stride(0)), _ptr(bq), act, _ptr(out), _ld(out), q, _ptr(ws), ws.numel() * 4, dim,
+                                                   _stream()), 'ihg_rows_linear_act_fwd')
+    return means
+
+
+def _query_rows_backward(d_query: Tensor, bag: BagLayout, means: Optional[Tensor], y: Optional[Tensor], wq: Optional[Tensor], act: int):
+    """``(d word table, d wq, d bq)`` from the COMPLETE cotangent ``d_query`` of the query rows (``[Q, d]``, any row stride): the transform's backward
+    (``ihg_rows_linear_act_bwd`` on ``d_query`` and the rows ``y`` themselves: ``dz = d_query * act'(y)`` is never stored), then the bag mean's."""
+    lib = _lib.load()
+    q, dim = bag.n_bags, int(d_query.shape[1])
+    dwq = dbq = None
+    if wq is not None:
+        dm = torch.empty(q, dim, dtype=torch.float32, device=d_query.device)
+        dwq, dbq = torch.empty_like(wq), torch.empty(dim, dtype=torch.float32, device=d_query.device)
+        ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), d_query.device)
+        with profiler.kernel('query_transform_bwd', q, dim):
+            _lib.check(lib.ihg_rows_linear_act_bwd(_ptr(d_query), _ld(d_query), _ptr(y), _ld(y), _ptr(means), dim, _ptr(wq), int(wq.stride(0)), act,
+                                                   _ptr(dwq), int(dwq.stride(0)), _ptr(dbq), _ptr(dm), dim, q, _ptr(ws), ws.numel() * 4, dim, _stream()),
+                       'ihg_rows_linear_act_bwd')
+        d_query = dm
+    d_word = torch.empty(bag.table_rows, dim, dtype=torch.float32, device=d_query.device)
+    with profiler.kernel('bag_mean_bwd', bag.table_rows, dim):
+        _lib.check(lib.ihg_bag_mean_bwd(_ptr(d_query), _ld(d_query), _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids), _ptr(bag.inv_len), _ptr(d_word), dim,
+                                        bag.table_rows, dim, _stream()), 'ihg_bag_mean_bwd')
+    return d_word, dwq, dbq
+
+
 class _BagMean(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, table: Tensor, bag: BagLayout) -> Tensor:
-        lib = _lib.load()
-        ctx.bag = bag
+    def forward(ctx, table: Tensor, bag: BagLayout, wq: Optional[Tensor], bq: Optional[Tensor], act: int) -> Tensor:
         table = _rows(table, 'table')
         dim = int(table.shape[1])
+        wq, bq = _query_transform_operands(wq, bq, dim)
         out = torch.empty(bag.n_bags, dim, dtype=torch.float32, device=table.device)
-        with profiler.kernel('bag_mean_fwd', bag.n_bags, dim):
-            _lib.check(lib.ihg_bag_mean_fwd(_ptr(table), _ld(table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len),
-                                            _ptr(out), _ld(out), bag.n_bags, dim, _stream()), 'ihg_bag_mean_fwd')
+        means = _query_rows_forward(table, bag, wq, bq, act, out)
+        ctx.bag, ctx.act, ctx.transform = bag, act, wq is not None
+        if wq is not None:
+            ctx.save_for_backward(means, out, wq)
         return out
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
-        lib = _lib.load()
-        bag = ctx.bag
         grad_out = _rows(grad_out, 'grad_out')
-        dim = int(grad_out.shape[1])
-        dtable = torch.empty(bag.table_rows, dim, dtype=torch.float32, device=grad_out.device)
-        with profiler.kernel('bag_mean_bwd', bag.table_rows, dim):
-            _lib.check(lib.ihg_bag_mean_bwd(_ptr(grad_out), _ld(grad_out), _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids),
-                                            _ptr(bag.inv_len), _ptr(dtable), _ld(dtable), bag.table_rows, dim, _stream()),
-                       'ihg_bag_mean_bwd')
-        return dtable, None
+        means, y, wq = ctx.saved_tensors if ctx.transform else (None, None, None)
+        dtable, dwq, dbq = _query_rows_backward(grad_out, ctx.bag, means, y, wq, ctx.act)
+        return dtable, None, dwq, dbq, None
 
 
-def bag_mean(table: Tensor, bag: BagLayout) -> Tensor:
-    """``nn.EmbeddingBag(mode='mean')`` over every query: ``[V+1,d] -> [Q,d]``."""
-    return _BagMean.apply(table, bag)
+def bag_mean(table: Tensor, bag: BagLayout, wq: Optional[Tensor] = None, bq: Optional[Tensor] = None, activation: Optional[str] = None) -> Tensor:
+    """``nn.EmbeddingBag(mode='mean')`` over every query: ``[V+1,d] -> [Q,d]``; with ``wq [d,d]``, ``bq [d]`` and ``activation`` ('relu' | 'tanh') the reference's
+    ``query_transform`` on top (``Models/EmbeddingLayers.py:40-44, 83-84``): ``act(mean wq^T + bq)``."""
+    return _BagMean.apply(table, bag, wq, bq, _query_activation(activation) if wq is not None else 0)
 
 
 class _EmbedAllNodes(torch.autograd.Function):
@@ -672,27 +732,25 @@ class _EmbedAllNodes(torch.autograd.Function):
     kernel writes its rows in place), with a backward that hands each table its gradient without a full-size zero fill."""
 
     @staticmethod
-    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor]) -> Tensor:
-        lib = _lib.load()
+    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor], wq: Optional[Tensor], bq: Optional[Tensor],
+                act: int) -> Tensor:
         word_table = _rows(word_table, 'word table')
         u, q, i = int(user_table.shape[0]) - 1, bag.n_bags, int(item_table.shape[0]) - 1
         dim = int(word_table.shape[1])
-        x = _check_out(out, user_table, item_table, word_table)
+        wq, bq = _query_transform_operands(wq, bq, dim)
+        x = _check_out(out, user_table, item_table, word_table, wq, bq)
         if x is None:
             x = torch.empty(u + q + i, dim, dtype=torch.float32, device=word_table.device)
         x[:u].copy_(user_table[1:])
         x[u + q:].copy_(item_table[1:])
-        rows = x[u:u + q]
-        if q > 0:
-            with profiler.kernel('bag_mean_fwd', q, dim):
-                _lib.check(lib.ihg_bag_mean_fwd(_ptr(word_table), _ld(word_table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len),
-                                                _ptr(rows), _ld(x), q, dim, _stream()), 'ihg_bag_mean_fwd')
-        ctx.bag, ctx.counts = bag, (u, q, i)
+        means = _query_rows_forward(word_table, bag, wq, bq, act, x[u:u + q])
+        ctx.bag, ctx.counts, ctx.act, ctx.transform = bag, (u, q, i), act, wq is not None
+        if wq is not None and out is None:
+            ctx.save_for_backward(means, x, wq)
         return x
 
     @staticmethod
     def backward(ctx, grad: Tensor):
-        lib = _lib.load()
         bag, (u, q, i) = ctx.bag, ctx.counts
         grad = _rows(grad, 'grad')
         dim = int(grad.shape[1])
@@ -702,18 +760,16 @@ class _EmbedAllNodes(torch.autograd.Function):
         d_item = torch.empty(i + 1, dim, dtype=torch.float32, device=grad.device)
         d_item[0].zero_()
         d_item[1:].copy_(grad[u + q:])
-        d_word = torch.empty(bag.table_rows, dim, dtype=torch.float32, device=grad.device)
-        g_q = grad[u:u + q]
-        with profiler.kernel('bag_mean_bwd', bag.table_rows, dim):
-            _lib.check(lib.ihg_bag_mean_bwd(_ptr(g_q), _ld(grad), _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids),
-                                            _ptr(bag.inv_len), _ptr(d_word), dim, bag.table_rows, dim, _stream()), 'ihg_bag_mean_bwd')
-        return d_user, d_item, d_word, None, None
+        means, x, wq = ctx.saved_tensors if ctx.transform else (None, None, None)
+        d_word, dwq, dbq = _query_rows_backward(grad[u:u + q], bag, means, x[u:u + q] if x is not None else None, wq, ctx.act)
+        return d_user, d_item, d_word, None, None, dwq, dbq, None
 
 
-def embed_all_nodes(user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor] = None) -> Tensor:
+def embed_all_nodes(user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor] = None, wq: Optional[Tensor] = None,
+                    bq: Optional[Tensor] = None, activation: Optional[str] = None) -> Tensor:
     """The full-graph input features ``EmbeddingLayer(None, None, None)`` concatenated (``RawGnn.py:112-113``): ``[U+Q+I, d]``
-    from the ``[U+1, d]`` / ``[I+1, d]`` tables (row 0 = padding) and the ``[V+1, d]`` word table."""
-    return _EmbedAllNodes.apply(user_table, item_table, word_table, bag, out)
+    from the ``[U+1, d]`` / ``[I+1, d]`` tables (row 0 = padding) and the ``[V+1, d]`` word table; ``wq``, ``bq``, ``activation``: the query transform, as in ``bag_mean``."""
+    return _EmbedAllNodes.apply(user_table, item_table, word_table, bag, out, wq, bq, _query_activation(activation) if wq is not None else 0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -826,9 +882,12 @@ class NodeTables:
     gradients in place (no ``[N, d]`` gradient that autograd then cuts apart), and the batch tail reads / scatters its layer-0 rows the same way.
     Stands in for the ``[N, d]`` tensor between ``EmbeddingLayer.node_tables()`` and the first layer; ``node_linear`` resolves it (bag means, autograd token)."""
 
-    def __init__(self, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: 'BagLayout', holder: 'TailGradients'):
+    def __init__(self, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: 'BagLayout', holder: 'TailGradients', wq: Optional[Tensor] = None,
+                 bq: Optional[Tensor] = None, activation: Optional[str] = None):
         self.user_table, self.item_table, self.word_table, self.bag, self.holder = user_table, item_table, word_table, bag, holder
-        self.query_rows: Optional[Tensor] = None        # [Q, d] bag means, set by the first node_linear
+        self.wq, self.bq = _query_transform_operands(wq, bq, int(user_table.shape[1]))          # the query transform (Gs.Query.transform == 'activation'), or None
+        self.act = _query_activation(activation) if wq is not None else 0
+        self.query_rows: Optional[Tensor] = None        # [Q, d] query rows of X0 (bag means, transformed where a transform is set), set by the first node_linear
         self.token: Optional[Tensor] = None             # carries the autograd edge from the batch tail to that op
         self.dim = int(user_table.shape[1])
         self.shape = (int(user_table.shape[0]) - 1 + bag.n_bags + int(item_table.shape[0]) - 1, self.dim)
@@ -859,16 +918,13 @@ class _LinearFromTables(torch.autograd.Function):
     there (this op is also the tap of layer 0), then the bag-mean backward."""
 
     @staticmethod
-    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, w: Tensor, bias: Optional[Tensor], nodes: NodeTables, layout: IncidenceLayout,
-                typed: bool, bias_mask: int):
+    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, w: Tensor, bias: Optional[Tensor], wq: Optional[Tensor], bq: Optional[Tensor],
+                nodes: NodeTables, layout: IncidenceLayout, typed: bool, bias_mask: int):
         lib = _lib.load()
         bag, dim = nodes.bag, nodes.dim
         n = nodes.shape[0]
         query_rows = torch.empty(bag.n_bags, dim, dtype=torch.float32, device=word_table.device)
-        if bag.n_bags > 0:
-            with profiler.kernel('bag_mean_fwd', bag.n_bags, dim):
-                _lib.check(lib.ihg_bag_mean_fwd(_ptr(word_table), dim, _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len), _ptr(query_rows), dim, bag.n_bags, dim,
-                                                _stream()), 'ihg_bag_mean_fwd')
+        means = _query_rows_forward(word_table, bag, wq, bq, nodes.act, query_rows)
         nodes.query_rows, nodes.layout = query_rows, layout
         nodes.token = torch.empty(1, dtype=torch.float32, device=word_table.device)
         out = torch.empty(n, dim, dtype=torch.float32, device=word_table.device)
@@ -881,7 +937,8 @@ class _LinearFromTables(torch.autograd.Function):
         with profiler.kernel('node_linear_fwd', n, dim):
             _lib.check(lib.ihg_node_linear_fwd_typed(nodes.row_pointers(), dim, _ptr(w), int(w.stride(0)), dim if typed else 0, _ptr(bias), bias_mask, dim if per_type_bias else 0,
                                                      _type_begin(layout), _ptr(out), dim, _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd_typed')
-        ctx.save_for_backward(user_table, item_table, w, query_rows)
+        ctx.transform = wq is not None
+        ctx.save_for_backward(user_table, item_table, w, query_rows, *((means, wq) if ctx.transform else ()))
         ctx.nodes, ctx.layout, ctx.typed, ctx.bias_mask, ctx.has_bias, ctx.per_type_bias = nodes, layout, typed, bias_mask, bias is not None, per_type_bias
         ctx.mark_non_differentiable(query_rows)
         ctx.set_materialize_grads(False)                     # (the token's and the bag means' gradients are never read: no zero tensors made for them)
@@ -890,7 +947,8 @@ class _LinearFromTables(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out: Tensor, _grad_token, _grad_rows):
         lib = _lib.load()
-        user_table, item_table, w, query_rows = ctx.saved_tensors
+        user_table, item_table, w, query_rows = ctx.saved_tensors[:4]
+        means, wq = ctx.saved_tensors[4:] if ctx.transform else (None, None)
         nodes, layout = ctx.nodes, ctx.layout
         bag, dim = nodes.bag, nodes.dim
         if grad_out is None:
@@ -916,11 +974,9 @@ class _LinearFromTables(torch.autograd.Function):
         holder = nodes.holder
         if holder is not None and holder.rowgrad is not None:              # the batch tail's gradient of the layer-0 rows: this op is their tap
             holder.put_into_typed(dx_rows, dim, layout, 0, dim)
-        d_word = torch.empty(bag.table_rows, dim, dtype=torch.float32, device=dev)
-        with profiler.kernel('bag_mean_bwd', bag.table_rows, dim):
-            _lib.check(lib.ihg_bag_mean_bwd(_ptr(d_query), dim, _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids), _ptr(bag.inv_len), _ptr(d_word), dim, bag.table_rows, dim,
-                                            _stream()), 'ihg_bag_mean_bwd')
-        return d_user, d_item, d_word, dw, dbias, None, None, None, None
+        # d_query is complete now (layer 0's input gradient + the batch tail's layer-0 rows): the query transform's backward, then the bag mean's
+        d_word, dwq, dbq = _query_rows_backward(d_query, bag, means, query_rows, wq, nodes.act)
+        return d_user, d_item, d_word, dw, dbias, dwq, dbq, None, None, None, None
 
 
 class _GatherActiveNodes(torch.autograd.Function):
@@ -930,15 +986,11 @@ class _GatherActiveNodes(torch.autograd.Function):
     gradients - dense ``[U + 1, d]`` / ``[I + 1, d]`` / ``[V + 1, d]`` tensors whose rows are zero for nodes that are neither active nor in the batch."""
 
     @staticmethod
-    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, nodes: NodeTables, layout: IncidenceLayout):
-        lib = _lib.load()
+    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, wq: Optional[Tensor], bq: Optional[Tensor], nodes: NodeTables, layout: IncidenceLayout):
         bag, dim = nodes.bag, nodes.dim
         u_pub, q_pub = layout.public_user_count, layout.public_query_count
         query_rows = torch.empty(bag.n_bags, dim, dtype=torch.float32, device=word_table.device)
-        if bag.n_bags > 0:
-            with profiler.kernel('bag_mean_fwd', bag.n_bags, dim):
-                _lib.check(lib.ihg_bag_mean_fwd(_ptr(word_table), dim, _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len), _ptr(query_rows), dim, bag.n_bags, dim,
-                                                _stream()), 'ihg_bag_mean_fwd')
+        means = _query_rows_forward(word_table, bag, wq, bq, nodes.act, query_rows)
         nodes.query_rows, nodes.layout = query_rows, layout
         nodes._public_type_begin = (ctypes.c_int64 * 4)(0, u_pub, u_pub + q_pub, layout.public_node_count)
         nodes.token = torch.empty(1, dtype=torch.float32, device=word_table.device)
@@ -952,7 +1004,8 @@ class _GatherActiveNodes(torch.autograd.Function):
         torch.index_select(user_table, 0, picks[0], out=x[:ua])
         torch.index_select(query_rows, 0, picks[1], out=x[ua:ua + qa])
         torch.index_select(item_table, 0, picks[2], out=x[ua + qa:])
-        ctx.save_for_backward(user_table, item_table)
+        ctx.transform = wq is not None
+        ctx.save_for_backward(user_table, item_table, *((means, query_rows, wq) if ctx.transform else ()))
         ctx.nodes, ctx.layout, ctx.picks = nodes, layout, picks
         ctx.mark_non_differentiable(query_rows)
         ctx.set_materialize_grads(False)
@@ -960,8 +1013,8 @@ class _GatherActiveNodes(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_x: Tensor, _grad_token, _grad_rows):
-        lib = _lib.load()
-        user_table, item_table = ctx.saved_tensors
+        user_table, item_table = ctx.saved_tensors[:2]
+        means, query_rows, wq = ctx.saved_tensors[2:] if ctx.transform else (None, None, None)
         nodes, layout, picks = ctx.nodes, ctx.layout, ctx.picks
         bag, dim = nodes.bag, nodes.dim
         if grad_x is None:
@@ -978,11 +1031,8 @@ class _GatherActiveNodes(torch.autograd.Function):
             step = dim * 4
             dx_rows = (ctypes.c_void_p * 3)(d_user.data_ptr() + step, d_query.data_ptr(), d_item.data_ptr() + step)
             holder.put_into_typed(dx_rows, dim, layout, 0, dim, type_begin=nodes._public_type_begin)
-        d_word = torch.empty(bag.table_rows, dim, dtype=torch.float32, device=g.device)
-        with profiler.kernel('bag_mean_bwd', bag.table_rows, dim):
-            _lib.check(lib.ihg_bag_mean_bwd(_ptr(d_query), dim, _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids), _ptr(bag.inv_len), _ptr(d_word), dim, bag.table_rows, dim,
-                                            _stream()), 'ihg_bag_mean_bwd')
-        return d_user, d_item, d_word, None, None
+        d_word, dwq, dbq = _query_rows_backward(d_query, bag, means, query_rows, wq, nodes.act)      # (on the complete d_query, as in _LinearFromTables)
+        return d_user, d_item, d_word, dwq, dbq, None, None
 
 
 def gather_active_nodes(nodes: NodeTables, layout: IncidenceLayout) -> Tensor:
@@ -991,7 +1041,7 @@ def gather_active_nodes(nodes: NodeTables, layout: IncidenceLayout) -> Tensor:
         raise ValueError('gather_active_nodes is for a layout that leaves the isolated nodes out')
     if nodes.query_rows is not None:
         raise RuntimeError('NodeTables: the input features were already consumed (one per forward)')
-    x, _token, _rows_q = _GatherActiveNodes.apply(nodes.user_table, nodes.item_table, nodes.word_table, nodes, layout)
+    x, _token, _rows_q = _GatherActiveNodes.apply(nodes.user_table, nodes.item_table, nodes.word_table, nodes.wq, nodes.bq, nodes, layout)
     return x
 
 
@@ -1002,7 +1052,7 @@ def node_linear(x, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, t
     if isinstance(x, NodeTables):
         if x.query_rows is not None:
             raise RuntimeError('NodeTables: the input features were already consumed by a node-level transform (one per forward)')
-        out, _token, _rows_q = _LinearFromTables.apply(x.user_table, x.item_table, x.word_table, w, bias, x, layout, bool(typed), int(bias_mask))
+        out, _token, _rows_q = _LinearFromTables.apply(x.user_table, x.item_table, x.word_table, w, bias, x.wq, x.bq, x, layout, bool(typed), int(bias_mask))
         return out
     return _NodeLinear.apply(x, w, bias, layout, bool(typed), int(bias_mask))
 

@@ -420,6 +420,28 @@ int ihg_batch_rows_add(const float* src, int64_t ld_src, int32_t width, const in
                        float* dense, int64_t ld_dense, float* tail, int64_t tail_row_offset, int64_t tail_rows, ihg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE: the query transform, Gs.Query.transform == 'activation' (Helpers/GlobalSettings.py:68-76): the bag means m [n_rows, dim] of the queries go through
+ * nn.Sequential(nn.Linear(dim, dim), Gs.Query.transform_activation()) (Models/EmbeddingLayers.py:40-44, applied at 83-84), act = nn.ReLU or nn.Tanh.
+ *   ihg_rows_linear_act_fwd   out[r] = act(x[r] w^T + bias)  - the row GEMM of ihg_node_linear_fwd (one weight, no node types) with the activation in its epilogue;
+ *                             `out` may be a column slice of a wider matrix (any ld_out >= dim, no alignment asked of it).  Replaces EmbeddingLayers.py:83-84.
+ *   ihg_rows_linear_act_bwd   autograd's backward of the same two modules in one call: reads dy and y = out, forms dz = dy * act'(y) as dy is loaded
+ *                             (act'(y) = [y > 0] for ReLU, 1 - y^2 for Tanh: neither the pre-activation nor dz is ever stored), and writes
+ *                             dw[c][j] = sum_r dz[r][c] x[r][j], dbias[c] = sum_r dz[r][c] (NULL: skipped) - per-workgroup slabs added in a fixed order, no atomics,
+ *                             bitwise reproducible - and dx = dz w (NULL: skipped).
+ * dim 32 / 64 / 128 / 256 with 16-byte aligned x / dy / y rows run on the matrix cores: the forward at dim 128 / 256 in the arithmetic of ihg_node_linear_fwd (two fp16
+ * terms per operand by default - when `out` is 16-byte aligned with ld_out % 4 == 0 -, fp32 MFMA under IHG_INTERACT_ARITH=f32); dim 32 / 64 and the backward at every
+ * tiled width: fp32 MFMA (v_mfma_f32_32x32x2_f32) in either mode.  Every other shape: the any-width kernels.  n_rows == 0: the forward writes nothing, the backward
+ * zeroes dw / dbias.  `workspace`: ihg_node_linear_workspace_bytes(dim) bytes, 16-byte aligned.
+ */
+#define IHG_ACT_RELU          1   /* nn.ReLU */
+#define IHG_ACT_TANH          2   /* nn.Tanh */
+int ihg_rows_linear_act_fwd(const float* x, int64_t ld_x, const float* w, int64_t ld_w, const float* bias, int32_t activation, float* out, int64_t ld_out,
+                            int64_t n_rows, void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream);
+int ihg_rows_linear_act_bwd(const float* dy, int64_t ld_dy, const float* y, int64_t ld_y, const float* x, int64_t ld_x, const float* w, int64_t ld_w,
+                            int32_t activation, float* dw, int64_t ld_dw, float* dbias, float* dx, int64_t ld_dx, int64_t n_rows, void* workspace,
+                            int64_t workspace_bytes, int32_t dim, ihg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE: composition of the two linear maps of a first-order layer - `feature_transform` (W [d,d], b; Models/GnnLayers.py:224)
  * followed by the first-order blocks of `aggregation` (A [d,3d] = A_u | A_q | A_i, bias c; Models/CommonLayers.py:60-66) with
  * nothing non-linear between them: node type t sees x (A_t W)^T + (A_t b + [t == user] c), which is what
