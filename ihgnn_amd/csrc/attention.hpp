@@ -1,8 +1,13 @@
 // attention.hpp - what the two attention translation units share (gat.hip: the GAT baseline over the pairwise graph; phase2.hip: the IHGNN layer's
-// phase-2 attention over the node <- hyperedge incidence): activations, lane-group reductions, the K7 work list with its split rows, the row gather-dot,
-// the softmax backward and the launch helpers.  A graph is a CSR whose row v lists the SOURCES of v's incoming edges; `mirror` maps entry p to its slot in
-// the table that is walked from the other side (gat.hip: the reverse edge's position; phase2.hip: 3 e + type(v) of an edge-major [E, 3] table).
+// phase-2 attention over the node <- hyperedge incidence): activations, lane-group reductions, the K7 work list with its split rows, the row projection, the row
+// gather-dot, the softmax forward and backward, the node-row gradient, and the launch and entry-point
+// helpers.  A graph is a CSR whose row v lists the SOURCES of v's incoming edges; `mirror` maps entry p to its slot in the table that is walked from the other
+// side (gat.hip: the reverse edge's position; phase2.hip: 3 e + type(v) of an edge-major [E, 3] table).  The kernels are __global__ templates with __restrict__
+// on their own parameters (an inlined body behind a per-layer wrapper loses the qualifiers and with them the register allocation).
 #pragma once
+#include <initializer_list>
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace {
@@ -93,6 +98,36 @@ __device__ __forceinline__ Unit unit_at(const Plan& pl, int64_t u) {
     return r;
 }
 
+// out[r, k] = x[r] . w[k dim ..] for the W = 1 or 2 weight vectors of the concatenation head, out [n_rows, W] (gat.hip: W = 2, both terms of a node from one
+// load of its row; phase2.hip: W = 1 per table).  Two named sums, not an array over W: as an array the compiler packs the products another way and leaves the
+// multiply-adds of a dot unfused - the same dot, rounded differently.
+template <int VEC, int G, int W>
+__global__ __launch_bounds__(kBlockThreads) void attn_project_kernel(const float* __restrict__ x, int64_t ld_x, const float* __restrict__ w, int dim, int dim_vec,
+                                                                     int64_t n_rows, float* __restrict__ out) {
+    static_assert(W == 1 || W == 2, "one or two weight vectors");
+    constexpr int GPW = kWave / G;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int lig = lane & (G - 1);
+    const int grp = lane / G;
+    for (int64_t r0 = global_wave_id() * GPW; r0 < n_rows; r0 += global_wave_count() * GPW) {
+        const int64_t r = r0 + grp;
+        float a = 0.f, b = 0.f;
+        if (r < n_rows) {
+            for (int c = lig; c < dim_vec; c += G) {
+                const Frag<VEC> row = Frag<VEC>::load(x + r * ld_x + c * VEC);
+                a += frag_dot(row, Frag<VEC>::load(w + c * VEC));
+                if constexpr (W == 2) b += frag_dot(row, Frag<VEC>::load(w + dim + c * VEC));
+            }
+        }
+        a = group_sum<G>(a);
+        if constexpr (W == 2) b = group_sum<G>(b);
+        if (r < n_rows && lig == 0) {
+            out[W * r] = a;
+            if constexpr (W == 2) out[W * r + 1] = b;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Row gather-dot: out[p] = act(bias + sum_k a[k] x[v][k] y[ids[p]][k]) for every entry p of row v (a NULL: ones; act < 0: neither activation nor bias).
 //   product scores (GnnLayers.py:107, 111: x = y = h, a = w) and d alpha (x = dout, y = h).  G lanes per unit hold x[v] * a in registers,
@@ -161,6 +196,96 @@ __device__ __forceinline__ void merge_max_sum(float& m, float& l, float m2, floa
     const float mx = fmaxf(m, m2);
     l = l * expf(m - mx) + l2 * expf(m2 - mx);
     m = mx;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Softmax over every row (DGL edge_softmax, normalised per destination: GnnLayers.py:112).  Light rows are finished here; a segment of a split row leaves its
+// (max, sum of m exp(z - max)) in partials[2 seg ..].  CONCAT: z[p] = act(src_term[STRIDE ids[p]] + dst_term[STRIDE v] + c) is formed (and stored) here (STRIDE 1: a
+// plane per term, phase2.hip; 2: the two terms of a node side by side, gat.hip).  MULT: entry p
+// stands for mult[ids[p]] copies with identical scores (phase2.hip's hyperedges kept once); without it no multiplicity is read.
+// ------------------------------------------------------------------------------------------------
+template <bool MULT>
+__device__ __forceinline__ float softmax_weight(const float* __restrict__ mult, int id, float e) {
+    if constexpr (MULT) return mult[id] * e;
+    else return e;
+}
+
+template <bool CONCAT, bool MULT, int STRIDE>
+__global__ __launch_bounds__(kBlockThreads) void attn_softmax_kernel(const float* __restrict__ src_term, const float* __restrict__ dst_term,
+                                                                     const float* __restrict__ bias, const float* __restrict__ mult, int act, Plan pl,
+                                                                     float* __restrict__ z, float* __restrict__ alpha, float* __restrict__ alpha_mirror,
+                                                                     float* __restrict__ partials) {
+    constexpr int G = kScalarLanes, GPW = kWave / G;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int lig = lane & (G - 1);
+    const int grp = lane / G;
+    const int64_t n_units = pl.n_segments + pl.n_rows;
+    for (int64_t u0 = global_wave_id() * GPW; u0 < n_units; u0 += global_wave_count() * GPW) {
+        const Unit un = unit_at(pl, u0 + grp);
+        float m = -__builtin_huge_valf();
+        if (CONCAT) {
+            const float dst = un.len > 0 ? dst_term[STRIDE * un.row] + bias[0] : 0.f;
+            for (int i = lig; i < un.len; i += G) {
+                const int p = un.begin + i;
+                const float v = gat_act(src_term[STRIDE * static_cast<int64_t>(pl.ids[p])] + dst, act);
+                z[p] = v;
+                m = fmaxf(m, v);
+            }
+        } else {
+            for (int i = lig; i < un.len; i += G) m = fmaxf(m, z[un.begin + i]);
+        }
+        m = group_max<G>(m);
+        float l = 0.f;
+        for (int i = lig; i < un.len; i += G) l += softmax_weight<MULT>(mult, pl.ids[un.begin + i], expf(z[un.begin + i] - m));
+        l = group_sum<G>(l);
+        if (un.seg >= 0) {
+            if (lig == 0) {
+                partials[2 * un.seg] = m;
+                partials[2 * un.seg + 1] = l;
+            }
+        } else if (un.row >= 0) {
+            for (int i = lig; i < un.len; i += G) {
+                const int p = un.begin + i;
+                const float al = softmax_weight<MULT>(mult, pl.ids[p], expf(z[p] - m)) / l;
+                alpha[p] = al;
+                alpha_mirror[pl.mirror[p]] = al;
+            }
+        }
+    }
+}
+
+// One workgroup per split row: merge its segments' (max, sum) in a fixed tree, then write alpha over the row's entries.
+template <bool MULT>
+__global__ __launch_bounds__(kBlockThreads) void attn_softmax_finish_kernel(Plan pl, const float* __restrict__ z, const float* __restrict__ mult,
+                                                                            const float* __restrict__ partials, float* __restrict__ alpha,
+                                                                            float* __restrict__ alpha_mirror) {
+    __shared__ float rm[kBlockThreads], rl[kBlockThreads];
+    const int t = threadIdx.x;
+    for (int64_t hr = blockIdx.x; hr < pl.n_heavy; hr += gridDim.x) {
+        const int s0 = pl.heavy_segptr[hr], s1 = pl.heavy_segptr[hr + 1];
+        float m = -__builtin_huge_valf(), l = 0.f;
+        for (int sg = s0 + t; sg < s1; sg += kBlockThreads) merge_max_sum(m, l, partials[2 * static_cast<int64_t>(sg)], partials[2 * static_cast<int64_t>(sg) + 1]);
+        rm[t] = m;
+        rl[t] = l;
+        __syncthreads();
+        for (int o = kBlockThreads / 2; o > 0; o >>= 1) {
+            if (t < o) {
+                float mm = rm[t], ll = rl[t];
+                merge_max_sum(mm, ll, rm[t + o], rl[t + o]);
+                rm[t] = mm;
+                rl[t] = ll;
+            }
+            __syncthreads();
+        }
+        const float mx = rm[0], den = rl[0];
+        __syncthreads();
+        const int64_t row = pl.heavy_rows[hr];
+        for (int p = pl.rowptr[row] + t; p < pl.rowptr[row + 1]; p += kBlockThreads) {
+            const float al = softmax_weight<MULT>(mult, pl.ids[p], expf(z[p] - mx)) / den;
+            alpha[p] = al;
+            alpha_mirror[pl.mirror[p]] = al;
+        }
+    }
 }
 
 // block-wide sum in a fixed tree (thread order); every thread gets the result
@@ -250,19 +375,47 @@ __global__ __launch_bounds__(kBlockThreads) void gat_softmax_bwd_finish_kernel(c
     }
 }
 
-// Smallest power of two >= n, clamped to [4, 64] (K7's lane groups).
-inline int gat_group_lanes(int n) {
-    int g = 4;
-    while (g < n && g < kWave) g <<= 1;
-    return g;
+// dh[v] (+)= [node_sums[2 v] w_src +] node_sums[2 v + 1] w_dst (concat)   |   dh[v] (+)= w * b[v] (product).  ACCUM: dh holds the transposed aggregation on entry
+// (gat.hip); SRC: v is also the source of edges (gat.hip; in phase2.hip the sources are the hyperedge rows)
+template <int VEC, bool ACCUM, bool SRC>
+__global__ __launch_bounds__(kBlockThreads) void attn_node_grad_kernel(float* __restrict__ dh, int64_t ld_dh, const float* __restrict__ b, int64_t ld_b,
+                                                                       const float* __restrict__ node_sums, const float* __restrict__ w, int head, int64_t n_rows,
+                                                                       int dim, int dim_vec) {
+    const int64_t total = n_rows * dim_vec;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlockThreads + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * kBlockThreads) {
+        const int64_t r = i / dim_vec;
+        const int c = static_cast<int>(i - r * dim_vec);
+        Frag<VEC> acc = Frag<VEC>::zero();
+        if constexpr (ACCUM) acc = Frag<VEC>::load(dh + r * ld_dh + c * VEC);
+        if (head == IHG_GAT_CONCAT) {
+            Frag<VEC> t = Frag<VEC>::zero();
+            if constexpr (SRC) t.add_scaled(Frag<VEC>::load(w + c * VEC), node_sums[2 * r]);
+            t.add_scaled(Frag<VEC>::load(w + dim + c * VEC), node_sums[2 * r + 1]);
+            if constexpr (ACCUM) acc.add(t);
+            else acc = t;
+        } else {
+            const Frag<VEC> t = frag_mul(Frag<VEC>::load(w + c * VEC), Frag<VEC>::load(b + r * ld_b + c * VEC));
+            if constexpr (ACCUM) acc.add(t);
+            else acc = t;
+        }
+        acc.store(dh + r * ld_dh + c * VEC);
+    }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Launch helpers
+// ------------------------------------------------------------------------------------------------
 inline int gat_grid(int64_t waves) {
     int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks < 1) blocks = 1;
     if (blocks > kMaxBlocks * 4) blocks = kMaxBlocks * 4;
     return static_cast<int>(blocks);
 }
+
+// n units, one per group of G lanes
+inline int group_grid(int64_t n, int G) { return gat_grid((n + kWave / G - 1) / (kWave / G)); }
+
+inline int scalar_grid(const Plan& pl) { return group_grid(pl.n_segments + pl.n_rows, kScalarLanes); }
 
 inline int flat_grid(int64_t n) {
     const int64_t blocks = (n + kBlockThreads - 1) / kBlockThreads;
@@ -271,33 +424,101 @@ inline int flat_grid(int64_t n) {
 
 inline int heavy_grid(int64_t n_heavy) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(n_heavy, kMaxBlocks * 4))); }
 
-template <int VEC>
-void launch_row_dot(const float* x, int64_t ld_x, const float* a, const float* y, int64_t ld_y, const float* bias, int act, const Plan& pl, int dim,
+// rows of `dim` floats at stride ld from p can be read 16 bytes at a time
+inline bool rows16(int32_t dim, int64_t ld, const void* p) { return dim % 4 == 0 && ld % 4 == 0 && aligned16(p); }
+
+// f(VEC, G) with both as compile-time values (std::integral_constant): VEC = 4 floats per lane where the caller found the rows 16-byte addressable, else 1;
+// G = the lanes that own a row, the smallest power of two >= dim / VEC clamped to [4, 64] (K7's lane groups)
+template <class F>
+void with_row_lanes(bool vec4, int dim, F f) {
+    const auto lanes = [&](auto vec) {
+        int g = 4;
+        while (g < dim / vec() && g < kWave) g <<= 1;
+        switch (g) {
+            case 4: f(vec, std::integral_constant<int, 4>{}); break;
+            case 8: f(vec, std::integral_constant<int, 8>{}); break;
+            case 16: f(vec, std::integral_constant<int, 16>{}); break;
+            case 32: f(vec, std::integral_constant<int, 32>{}); break;
+            default: f(vec, std::integral_constant<int, 64>{}); break;
+        }
+    };
+    if (vec4) lanes(std::integral_constant<int, 4>{});
+    else lanes(std::integral_constant<int, 1>{});
+}
+
+template <int W>
+void launch_project(bool vec4, const float* x, int64_t ld_x, const float* w, int dim, int64_t n_rows, float* out, hipStream_t s) {
+    with_row_lanes(vec4, dim, [&](auto vec, auto g) {
+        constexpr int VEC = decltype(vec)::value, G = decltype(g)::value;
+        hipLaunchKernelGGL((attn_project_kernel<VEC, G, W>), dim3(group_grid(n_rows, G)), dim3(kBlockThreads), 0, s, x, ld_x, w, dim, dim / VEC, n_rows, out);
+    });
+}
+
+void launch_row_dot(bool vec4, const float* x, int64_t ld_x, const float* a, const float* y, int64_t ld_y, const float* bias, int act, const Plan& pl, int dim,
                     float* out, hipStream_t s) {
-    const int dim_vec = dim / VEC;
-#define IHG_GAT_DOT(G)                                                                                                                          \
-    hipLaunchKernelGGL((gat_row_dot_kernel<VEC, G>), dim3(gat_grid((pl.n_segments + pl.n_rows + kWave / G - 1) / (kWave / G))), dim3(kBlockThreads), 0, s, \
-                       x, ld_x, a, y, ld_y, bias, act, pl, dim_vec, out)
-    switch (gat_group_lanes(dim_vec)) {
-        case 4: IHG_GAT_DOT(4); break;
-        case 8: IHG_GAT_DOT(8); break;
-        case 16: IHG_GAT_DOT(16); break;
-        case 32: IHG_GAT_DOT(32); break;
-        default: IHG_GAT_DOT(64); break;
-    }
-#undef IHG_GAT_DOT
+    with_row_lanes(vec4, dim, [&](auto vec, auto g) {
+        constexpr int VEC = decltype(vec)::value, G = decltype(g)::value;
+        hipLaunchKernelGGL((gat_row_dot_kernel<VEC, G>), dim3(group_grid(pl.n_segments + pl.n_rows, G)), dim3(kBlockThreads), 0, s, x, ld_x, a, y, ld_y, bias, act, pl,
+                           dim / VEC, out);
+    });
+}
+
+// the softmax over every row and, where the plan has split rows, their finish
+template <bool CONCAT, bool MULT, int STRIDE = 1>
+void launch_softmax(const float* src_term, const float* dst_term, const float* bias, const float* mult, int act, const Plan& pl, float* z, float* alpha,
+                    float* alpha_mirror, float* partials, hipStream_t s) {
+    hipLaunchKernelGGL((attn_softmax_kernel<CONCAT, MULT, STRIDE>), dim3(scalar_grid(pl)), dim3(kBlockThreads), 0, s, src_term, dst_term, bias, mult, act, pl, z, alpha,
+                       alpha_mirror, partials);
+    if (pl.n_heavy > 0)
+        hipLaunchKernelGGL(attn_softmax_finish_kernel<MULT>, dim3(heavy_grid(pl.n_heavy)), dim3(kBlockThreads), 0, s, pl, z, mult, partials, alpha, alpha_mirror);
+}
+
+void launch_softmax_bwd(const float* z, const float* alpha, float* g, int act, const Plan& pl, float* node_sums, float* partials, hipStream_t s) {
+    hipLaunchKernelGGL(gat_softmax_bwd_kernel, dim3(scalar_grid(pl)), dim3(kBlockThreads), 0, s, z, alpha, g, act, pl, node_sums, partials);
+    if (pl.n_heavy > 0)
+        hipLaunchKernelGGL(gat_softmax_bwd_finish_kernel, dim3(heavy_grid(pl.n_heavy)), dim3(kBlockThreads), 0, s, z, alpha, g, act, pl, node_sums, partials);
+}
+
+template <bool ACCUM, bool SRC>
+void launch_node_grad(bool vec4, float* dh, int64_t ld_dh, const float* b, int64_t ld_b, const float* node_sums, const float* w, int head, int64_t n_rows, int dim,
+                      hipStream_t s) {
+    if (vec4)
+        hipLaunchKernelGGL((attn_node_grad_kernel<4, ACCUM, SRC>), dim3(flat_grid(n_rows * (dim / 4))), dim3(kBlockThreads), 0, s, dh, ld_dh, b, ld_b, node_sums, w, head,
+                           n_rows, dim, dim / 4);
+    else
+        hipLaunchKernelGGL((attn_node_grad_kernel<1, ACCUM, SRC>), dim3(flat_grid(n_rows * dim)), dim3(kBlockThreads), 0, s, dh, ld_dh, b, ld_b, node_sums, w, head, n_rows,
+                           dim, dim);
 }
 
 int64_t param_blocks(int64_t n_rows) { return std::max<int64_t>(1, (n_rows + kParamRows - 1) / kParamRows); }
 
+// ------------------------------------------------------------------------------------------------
+// Entry-point checks (`what`: the entry point's name, as its messages carry it)
+// ------------------------------------------------------------------------------------------------
+int check_head(const char* what, int32_t head) {
+    if (head != IHG_GAT_CONCAT && head != IHG_GAT_PRODUCT) return fail(IHG_ERR_INVALID, "%s: unknown head %d", what, head);
+    return IHG_OK;
+}
+
 int check_plan(const char* what, const Plan& pl, int32_t head, int32_t activation, int32_t dim) {
     if (pl.n_rows < 0 || dim <= 0 || pl.n_segments < 0 || pl.n_heavy < 0) return fail(IHG_ERR_INVALID, "%s: bad size (rows=%lld dim=%d)", what, (long long)pl.n_rows, dim);
-    if (head != IHG_GAT_CONCAT && head != IHG_GAT_PRODUCT) return fail(IHG_ERR_INVALID, "%s: unknown head %d", what, head);
+    if (const int rc = check_head(what, head); rc != IHG_OK) return rc;
     if (activation != IHG_GAT_LEAKY_RELU && activation != IHG_GAT_RELU && activation != IHG_GAT_TANH) return fail(IHG_ERR_INVALID, "%s: unknown activation %d", what, activation);
     if (pl.n_rows > 0 && (pl.rowptr == nullptr || pl.ids == nullptr || pl.mirror == nullptr)) return fail(IHG_ERR_INVALID, "%s: null graph pointer", what);
     if (pl.n_heavy > 0 && (pl.heavy_threshold <= 0 || pl.seg_begin == nullptr || pl.seg_end == nullptr || pl.seg_row == nullptr || pl.heavy_rows == nullptr ||
                            pl.heavy_segptr == nullptr))
         return fail(IHG_ERR_INVALID, "%s: incomplete split-row plan", what);
+    return IHG_OK;
+}
+
+int check_pointers(const char* what, std::initializer_list<const void*> pointers) {
+    for (const void* p : pointers)
+        if (p == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    return IHG_OK;
+}
+
+int check_workspace(const char* what, int64_t have, int64_t need) {
+    if (have < need) return fail(IHG_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes", what, (long long)have, (long long)need);
     return IHG_OK;
 }
 
@@ -310,10 +531,6 @@ Plan make_plan(const int32_t* rowptr, const int32_t* ids, const int32_t* mirror,
         pl.heavy_threshold = 0;
     }
     return pl;
-}
-
-bool vec4_ok(int32_t dim, int64_t ld_a, const void* a, int64_t ld_b, const void* b, const float* w) {
-    return dim % 4 == 0 && ld_a % 4 == 0 && aligned16(a) && (b == nullptr || (ld_b % 4 == 0 && aligned16(b))) && aligned16(w);
 }
 
 }  // namespace

@@ -339,11 +339,24 @@ GAT_HEADS = {'concatenation': 0, 'product': 1}                  # Gsv.concat / G
 GAT_ACTIVATIONS = {'leaky_relu': 0, 'relu': 1, 'tanh': 2}       # the names of Gs.Gnn.gat_activation -> IHG_GAT_*
 
 
-def _gat_plan(csr: Csr):
+def _split_row_args(csr: Csr):
     heavy = csr.n_heavy > 0
     return (csr.heavy_threshold if heavy else 0, _ptr(csr.seg_begin) if heavy else None, _ptr(csr.seg_end) if heavy else None,
             _ptr(csr.seg_row) if heavy else None, csr.n_segments if heavy else 0, _ptr(csr.heavy_rows) if heavy else None,
             _ptr(csr.heavy_segptr) if heavy else None, csr.n_heavy)
+_gat_plan = _split_row_args                                     # (its earlier name: the attention tests of earlier revisions call it, and run on this build)
+
+
+def _attention_codes(caller: str, head: str, activation: str):
+    for kind, name, codes in (('head', head, GAT_HEADS), ('activation', activation, GAT_ACTIVATIONS)):
+        if name not in codes:
+            raise ValueError(f'{caller}: unknown {kind} {name!r} (one of {sorted(codes)})')
+    return GAT_HEADS[head], GAT_ACTIVATIONS[activation]
+
+
+def _check_attention_operands(caller: str, weight: Tensor, bias: Tensor, head: int, dim: int) -> None:
+    if int(weight.numel()) != (2 * dim if head == 0 else dim) or int(bias.numel()) != 1:
+        raise ValueError(f'{caller}: weight of {int(weight.numel())} / bias of {int(bias.numel())} floats for width {dim}')
 
 
 class _GatAttention(torch.autograd.Function):
@@ -360,8 +373,7 @@ class _GatAttention(torch.autograd.Function):
         if n != graph.node_count:
             raise ValueError(f'gat_attention: h has {n} rows, the graph {graph.node_count} nodes')
         weight, bias = weight.contiguous(), bias.contiguous()
-        if int(weight.numel()) != (2 * dim if head == 0 else dim) or int(bias.numel()) != 1:
-            raise ValueError(f'gat_attention: weight of {int(weight.numel())} / bias of {int(bias.numel())} floats for width {dim}')
+        _check_attention_operands('gat_attention', weight, bias, head, dim)
         nnz = csr.nnz
         z = torch.empty(max(nnz, 1), dtype=torch.float32, device=h.device)
         alpha = torch.empty_like(z)
@@ -370,7 +382,7 @@ class _GatAttention(torch.autograd.Function):
         ws = _workspace(ws_bytes, h.device)
         with profiler.kernel('gat_scores', n, dim):
             _lib.check(lib.ihg_gat_attention_fwd(_ptr(h), _ld(h), _ptr(csr.ptr), _ptr(csr.ids), _ptr(graph.mirror), _ptr(csr.row_order), n, dim, _ptr(weight),
-                                                 _ptr(bias), head, activation, *_gat_plan(csr), _ptr(z), _ptr(alpha), _ptr(alpha_mirror), _ptr(ws), ws_bytes,
+                                                 _ptr(bias), head, activation, *_split_row_args(csr), _ptr(z), _ptr(alpha), _ptr(alpha_mirror), _ptr(ws), ws_bytes,
                                                  _stream()), 'ihg_gat_attention_fwd')
         y = node_segment_sum_raw(h, csr, None, None, _lib.SCALE_NONE, entry_scale=alpha, role='k7.gat_aggregate', out=_check_out(out, h, weight, bias))
         ctx.graph, ctx.head, ctx.activation = graph, head, activation
@@ -391,7 +403,7 @@ class _GatAttention(torch.autograd.Function):
         ws = _workspace(ws_bytes, h.device)
         with profiler.kernel('gat_scores_bwd', n, dim):
             _lib.check(lib.ihg_gat_scores_bwd(_ptr(h), _ld(h), _ptr(dy), _ld(dy), _ptr(csr.ptr), _ptr(csr.ids), _ptr(graph.mirror), _ptr(csr.row_order), n, dim,
-                                              head, ctx.activation, *_gat_plan(csr), _ptr(z), _ptr(alpha), _ptr(ds), _ptr(node_sums), _ptr(ws), ws_bytes,
+                                              head, ctx.activation, *_split_row_args(csr), _ptr(z), _ptr(alpha), _ptr(ds), _ptr(node_sums), _ptr(ws), ws_bytes,
                                               _stream()), 'ihg_gat_scores_bwd')
         # the transposed aggregation: row u gathers the cotangents of the rows its edges u -> v point to, weighted by alpha of u -> v
         dh = node_segment_sum_raw(dy, csr, None, None, _lib.SCALE_NONE, entry_scale=alpha_mirror, role='k7.gat_aggregate_bwd')
@@ -415,11 +427,7 @@ def gat_attention(h: Tensor, graph, weight: Tensor, bias: Tensor, head: str = 'c
     of CSR row ``v``) ``z = act(w_src . h[u] + w_dst . h[v] + c)`` (``head`` 'concatenation', ``weight`` = ``[w_src | w_dst]``, ``2 d`` floats) or
     ``act(w . (h[u] * h[v]) + c)`` ('product', ``d`` floats); ``alpha`` = softmax of ``z`` over ``v``'s incoming edges; ``out[v] = sum alpha h[u]`` (a node
     without edges: a zero row).  ``activation``: 'leaky_relu' (slope 0.01), 'relu' or 'tanh'.  ``bias``: the one-float ``c`` (read on the device)."""
-    if head not in GAT_HEADS:
-        raise ValueError(f'gat_attention: unknown head {head!r} (one of {sorted(GAT_HEADS)})')
-    if activation not in GAT_ACTIVATIONS:
-        raise ValueError(f'gat_attention: unknown activation {activation!r} (one of {sorted(GAT_ACTIVATIONS)})')
-    return _GatAttention.apply(h, weight.reshape(-1), bias.reshape(-1), graph, GAT_HEADS[head], GAT_ACTIVATIONS[activation], out)
+    return _GatAttention.apply(h, weight.reshape(-1), bias.reshape(-1), graph, *_attention_codes('gat_attention', head, activation), out)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -432,8 +440,7 @@ def _phase2_forward_raw(h2: Tensor, ef2: Tensor, weight: Tensor, bias: Tensor, l
     n, e, dim = int(h2.shape[0]), int(ef2.shape[0]), int(h2.shape[1])
     if n != layout.node_count or e != layout.edge_count or int(ef2.shape[1]) != dim:
         raise ValueError(f'hyper_attention: h2 {tuple(h2.shape)} / ef2 {tuple(ef2.shape)} for a layout of {layout.node_count} nodes and {layout.edge_count} hyperedges')
-    if int(weight.numel()) != (2 * dim if head == 0 else dim) or int(bias.numel()) != 1:
-        raise ValueError(f'hyper_attention: weight of {int(weight.numel())} / bias of {int(bias.numel())} floats for width {dim}')
+    _check_attention_operands('hyper_attention', weight, bias, head, dim)
     z = torch.empty(max(3 * e, 1), dtype=torch.float32, device=h2.device)
     alpha = torch.empty_like(z)
     alpha_edge = torch.empty_like(z)
@@ -441,7 +448,7 @@ def _phase2_forward_raw(h2: Tensor, ef2: Tensor, weight: Tensor, bias: Tensor, l
     ws = _workspace(ws_bytes, h2.device)
     with profiler.kernel('phase2_scores', n, dim):
         _lib.check(lib.ihg_phase2_attention_fwd(_ptr(h2), _ld(h2), _ptr(ef2), _ld(ef2), _ptr(csr.ptr), _ptr(csr.ids), _ptr(layout.member_csr.ids), _ptr(csr.row_order),
-                                                n, e, dim, _ptr(weight), _ptr(bias), _ptr(layout.edge_weight), head, activation, *_gat_plan(csr), _ptr(z), _ptr(alpha),
+                                                n, e, dim, _ptr(weight), _ptr(bias), _ptr(layout.edge_weight), head, activation, *_split_row_args(csr), _ptr(z), _ptr(alpha),
                                                 _ptr(alpha_edge), _ptr(ws), ws_bytes, _stream()), 'ihg_phase2_attention_fwd')
     # (alpha carries the multiplicity of a hyperedge kept once: no src_scale)
     y = node_segment_sum_raw(ef2, csr, None, None, _lib.SCALE_NONE, entry_scale=alpha, role='k7.phase2_aggregate', out=out)
@@ -462,7 +469,7 @@ def _phase2_backward_raw(h2: Tensor, ef2: Tensor, weight: Tensor, z: Tensor, alp
     ws = _workspace(ws_bytes, h2.device)
     with profiler.kernel('phase2_scores_bwd', n, dim):
         _lib.check(lib.ihg_phase2_scores_bwd(_ptr(ef2), _ld(ef2), _ptr(dy), _ld(dy), _ptr(csr.ptr), _ptr(csr.ids), _ptr(layout.member_csr.ids), _ptr(csr.row_order),
-                                             n, e, dim, head, activation, *_gat_plan(csr), _ptr(z), _ptr(alpha), _ptr(ds), _ptr(ds_edge), _ptr(node_sums),
+                                             n, e, dim, head, activation, *_split_row_args(csr), _ptr(z), _ptr(alpha), _ptr(ds), _ptr(ds_edge), _ptr(node_sums),
                                              _ptr(ws), ws_bytes, _stream()), 'ihg_phase2_scores_bwd')
     def2 = torch.empty(e, dim, dtype=torch.float32, device=h2.device)
     with profiler.kernel('phase2_edges_bwd', e, dim):
@@ -591,13 +598,10 @@ def phase2_layer(h: Tensor, agg_w: Tensor, agg_b: Optional[Tensor], wg: Tensor, 
                  head: str = 'concatenation', activation: str = 'leaky_relu', out: Optional[Tensor] = None) -> Tensor:
     """``hyper_attention(rows_linear(h; wg, bg), rows_linear(FeatureInteractor(h; agg_w, agg_b); wg, bg), ...)`` as one differentiable op: what
     ``IHGNNLayer(phase2_attention=True)`` runs behind its ``feature_transform``.  All operands at the width of ``h`` (``pad_blocks`` / ``pad_square`` / ...)."""
-    if head not in GAT_HEADS:
-        raise ValueError(f'phase2_layer: unknown head {head!r} (one of {sorted(GAT_HEADS)})')
-    if activation not in GAT_ACTIVATIONS:
-        raise ValueError(f'phase2_layer: unknown activation {activation!r} (one of {sorted(GAT_ACTIVATIONS)})')
+    codes = _attention_codes('phase2_layer', head, activation)
     if order not in (1, 2, 3):
         raise ValueError('phase2_layer: interaction order 1, 2 or 3')
-    return _Phase2Layer.apply(h, agg_w, agg_b, wg, bg, weight.reshape(-1), bias.reshape(-1), layout, int(order), GAT_HEADS[head], GAT_ACTIVATIONS[activation], out)
+    return _Phase2Layer.apply(h, agg_w, agg_b, wg, bg, weight.reshape(-1), bias.reshape(-1), layout, int(order), *codes, out)
 
 
 def hyper_attention(h2: Tensor, ef2: Tensor, layout: IncidenceLayout, weight: Tensor, bias: Tensor, head: str = 'concatenation', activation: str = 'leaky_relu',
@@ -607,11 +611,7 @@ def hyper_attention(h2: Tensor, ef2: Tensor, layout: IncidenceLayout, weight: Te
     incidence (``e`` contains ``v``) ``z = act(w_src . ef2[e] + w_dst . h2[v] + c)`` (``head`` 'concatenation', ``weight`` = ``[w_src | w_dst]``: the hyperedge is the
     edge's source) or ``act(w . (ef2[e] * h2[v]) + c)`` ('product'); ``alpha`` = softmax of ``z`` over ``v``'s hyperedges - every copy of a hyperedge that the layout
     keeps once (``layout.edge_weight``) counted; ``out[v] = sum alpha ef2[e]`` (a node in no hyperedge: a zero row).  ``activation`` / ``bias``: as ``gat_attention``."""
-    if head not in GAT_HEADS:
-        raise ValueError(f'hyper_attention: unknown head {head!r} (one of {sorted(GAT_HEADS)})')
-    if activation not in GAT_ACTIVATIONS:
-        raise ValueError(f'hyper_attention: unknown activation {activation!r} (one of {sorted(GAT_ACTIVATIONS)})')
-    return _HyperAttention.apply(h2, ef2, weight.reshape(-1), bias.reshape(-1), layout, GAT_HEADS[head], GAT_ACTIVATIONS[activation], out)
+    return _HyperAttention.apply(h2, ef2, weight.reshape(-1), bias.reshape(-1), layout, *_attention_codes('hyper_attention', head, activation), out)
 
 
 # ---------------------------------------------------------------------------------------------

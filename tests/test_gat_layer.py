@@ -292,7 +292,7 @@ def gat_alpha(h, lay, w, c, head, act):
     wsb = int(lib.ihg_gat_workspace_bytes(n, csr.n_segments, d, ops.GAT_HEADS[head]))
     ws = torch.empty(wsb // 4 + 4, device=dev())
     _lib.check(lib.ihg_gat_attention_fwd(ops._ptr(h), d, ops._ptr(csr.ptr), ops._ptr(csr.ids), ops._ptr(lay.mirror), ops._ptr(csr.row_order), n, d, ops._ptr(w),
-                                         ops._ptr(c), ops.GAT_HEADS[head], ops.GAT_ACTIVATIONS[act], *ops._gat_plan(csr), ops._ptr(z), ops._ptr(alpha), ops._ptr(am),
+                                         ops._ptr(c), ops.GAT_HEADS[head], ops.GAT_ACTIVATIONS[act], *ops._split_row_args(csr), ops._ptr(z), ops._ptr(alpha), ops._ptr(am),
                                          ops._ptr(ws), wsb, ops._stream()), 'fwd')
     a = alpha.cpu().numpy()[:csr.nnz]
     np.testing.assert_array_equal(am.cpu().numpy()[:csr.nnz][lay.mirror_host], a)       # the mirrored copy is the same numbers at the reverse positions
@@ -538,8 +538,8 @@ print('gat done')
     foreign = [n for n in last if 'at::native' in n or '__amd_rocclr' in n or 'elementwise_kernel' in n]
     assert not foreign, foreign
     short = sorted({n.split('(')[0] for n in last})
-    for want in ('gat_project_kernel', 'gat_row_dot_kernel', 'node_segment_sum_kernel', 'gat_softmax_bwd_kernel', 'gat_source_sums_kernel', 'gat_symmetrize_kernel',
-                 'gat_param_partials_kernel', 'gat_combine_kernel'):
+    for want in ('attn_project_kernel', 'attn_softmax_kernel', 'gat_row_dot_kernel', 'node_segment_sum_kernel', 'gat_softmax_bwd_kernel', 'gat_source_sums_kernel',
+                 'gat_symmetrize_kernel', 'gat_param_partials_kernel', 'gat_param_finish_kernel', 'attn_node_grad_kernel'):
         assert any(want in n for n in last), (want, short)
-    gat = {n for n in short if 'gat_' in n or 'node_segment_sum' in n or 'heavy_finish' in n}
+    gat = {n for n in short if 'gat_' in n or 'attn_' in n or 'node_segment_sum' in n or 'heavy_finish' in n}
     assert len(short) > len(gat), short                          # the node transform's kernels (forward, input and weight gradients) are in the window too

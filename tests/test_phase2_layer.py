@@ -478,7 +478,7 @@ def phase2_alpha(h2, ef2, lay, w, c, head, act):
     ws = torch.empty(wsb // 4 + 4, device=dev())
     _lib.check(lib.ihg_phase2_attention_fwd(ops._ptr(h2), d, ops._ptr(ef2), d, ops._ptr(csr.ptr), ops._ptr(csr.ids), ops._ptr(lay.member_csr.ids), ops._ptr(csr.row_order),
                                             n, e, d, ops._ptr(w), ops._ptr(c), ops._ptr(lay.edge_weight), ops.GAT_HEADS[head], ops.GAT_ACTIVATIONS[act],
-                                            *ops._gat_plan(csr), ops._ptr(z), ops._ptr(alpha), ops._ptr(ae), ops._ptr(ws), wsb, ops._stream()), 'fwd')
+                                            *ops._split_row_args(csr), ops._ptr(z), ops._ptr(alpha), ops._ptr(ae), ops._ptr(ws), wsb, ops._stream()), 'fwd')
     a = alpha.cpu().numpy()
     np.testing.assert_array_equal(ae.cpu().numpy()[lay.member_csr.ids_host], a)
     return a
@@ -649,8 +649,8 @@ print('phase2 done')
     short = sorted({n.split('(')[0] for n in last})
     foreign = [n for n in last if 'at::native' in n or '__amd_rocclr' in n or 'elementwise_kernel' in n]
     assert not foreign, foreign
-    for want in ('p2_project_kernel', 'p2_softmax_kernel', 'gat_row_dot_kernel', 'node_segment_sum_kernel', 'gat_softmax_bwd_kernel', 'p2_to_edge_slots_kernel',
-                 'p2_edges_bwd_kernel', 'p2_colsum_partials_kernel', 'p2_node_grad_kernel', 'p2_add_rows_kernel'):
+    for want in ('attn_project_kernel', 'attn_softmax_kernel', 'gat_row_dot_kernel', 'node_segment_sum_kernel', 'gat_softmax_bwd_kernel', 'p2_to_edge_slots_kernel',
+                 'p2_edges_bwd_kernel', 'p2_colsum_partials_kernel', 'p2_colsum_finish_kernel', 'attn_node_grad_kernel', 'p2_add_rows_kernel'):
         assert any(want in n for n in last), (want, short)
 
 
