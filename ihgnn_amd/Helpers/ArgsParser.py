@@ -28,6 +28,8 @@ _FLAGS = (
     # not in the reference's command line: there one edits Gs.Query in Helpers/GlobalSettings.py:68-76
     ('query_transform', ('--query_transform',), str, Gsv.mean, 'query transform: mean | activation (nn.Linear + --query_activation on the bag mean; Gs.Query.transform)'),
     ('query_activation', ('--query_activation',), str, 'relu', 'activation of --query_transform activation: relu | tanh (Gs.Query.transform_activation)'),
+    # not in the reference's command line: there one edits Gs.Prediction in Helpers/GlobalSettings.py
+    ('cosine', ('--cosine',), 'flag', False, 'score with the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity) instead of the dot product'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '

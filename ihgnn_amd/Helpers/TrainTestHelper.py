@@ -32,8 +32,8 @@ def print_network_parameters(module: nn.Module, name_filter: Optional[str] = Non
 
 
 def _evaluate_batched(model, logs, item_count: int, device: torch.device, indices) -> List[Tuple[int, Metrics]]:
-    """Top-10 of many searches per launch (``ihg_score_topk``: scores on the matrix cores, running top-10 in registers, no
-    ``[C, I]`` matrix), one D2H copy per chunk (the reference scores one log at a time and syncs on every one,
+    """Top-10 of many searches per launch (``ihg_score_topk`` / ``ihg_score_topk_cosine``, whichever head ``Gs.Prediction.use_cosine_similarity`` names: scores on
+    the matrix cores, running top-10 in registers, no ``[C, I]`` matrix), one D2H copy per chunk (the reference scores one log at a time and syncs on every one,
     ``TrainTestHelper.py:58-67``, ``Metrics.py:60-61``)."""
     out: List[Tuple[int, Metrics]] = []
     chunk = 8192
@@ -67,7 +67,7 @@ def test_and_get_avg_metrics(model, dataset_train: GraphDataset, dataloader: Tes
     with torch.no_grad():
         model.save_features_for_test()
         try:
-            if hasattr(model, 'top_items') and not Gs.Prediction.use_cosine_similarity:
+            if hasattr(model, 'top_items'):
                 scored = _evaluate_batched(model, logs, dataset_train.item_count, device, mine)
             else:
                 scored = []

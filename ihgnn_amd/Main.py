@@ -41,6 +41,12 @@ def apply_query_settings(args) -> None:
     Gs.Query.transform_activation = {'relu': nn.ReLU, 'tanh': nn.Tanh}[getattr(args, 'query_activation', 'relu') or 'relu']
 
 
+def apply_prediction_settings(args) -> None:
+    """``--cosine`` -> ``Gs.Prediction.use_cosine_similarity``, assigned both ways: a run without the flag scores with the dot product whatever an earlier ``main()`` of
+    this process set (not in the reference's command line: one edits ``Helpers/GlobalSettings.py`` there)."""
+    Gs.Prediction.use_cosine_similarity = bool(getattr(args, 'cosine', False))
+
+
 def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     args = parse_args(argv)
     rank, local_rank, world = ihg_dist.init_from_env()
@@ -71,6 +77,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     layer_count = args.gnns or 2
     order = args.feature_order or 3
     apply_query_settings(args)
+    apply_prediction_settings(args)
     if args.device == 'cpu':
         raise RuntimeError('ihgnn_amd has no CPU path: the hypergraph kernels are HIP-only')
     device = torch.device(f'cuda:{args.device}' if args.device else f'cuda:{local_rank}')
@@ -93,7 +100,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}')
     say(f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | '
         f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
-        f'validation {Gs.use_valid_dataset}')
+        f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | validation {Gs.use_valid_dataset}')
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
 
     dataset_train = GraphDataset(

@@ -200,9 +200,10 @@ class RawGnn(nn.Module):
                               item_indices + ds.item_start_index_in_graph])
             layers = self.propagate_layers()
             head = self.prediction_layer
-            if layers[0].is_cuda and not Gs.Prediction.use_cosine_similarity and len(layers) <= 8:
+            if layers[0].is_cuda and len(layers) <= 8:
                 from .. import ops
-                return ops.hem_score(layers, rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph)      # fused batch tail
+                return ops.hem_score(layers, rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph,
+                                     cosine=Gs.Prediction.use_cosine_similarity)      # fused batch tail (either head: the setting is read at every call, PredictionLayers.py:38)
             picked = torch.cat([x[rows] for x in layers], 1)
             b = user_indices.shape[0]
             return head(picked[:b], picked[b:2 * b], picked[2 * b:], item_indices)
@@ -227,6 +228,7 @@ class RawGnn(nn.Module):
         rank calls it, with batches of the same size."""
         from .. import ops
         ds, head = self.dataset, self.prediction_layer
+        cosine = bool(Gs.Prediction.use_cosine_similarity)       # read at every call, as the reference's head does (PredictionLayers.py:38)
         rows = ops.batch_node_rows(user_indices, query_indices, item_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph)
         if cotangent_sync is not None and torch.is_grad_enabled():
             holder = ops.TailGradients(exchange=cotangent_sync.exchange, grad_scale=1.0 / cotangent_sync.world_size)
@@ -237,18 +239,18 @@ class RawGnn(nn.Module):
         compact = self._compact_layout()
         if compact is None:
             return ops.hem_bce_loss(self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer), rows, item_indices, labels,
-                                    head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder)
+                                    head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder, cosine=cosine)
         if holder is None:
             # (no gradient wanted: the public matrices, the plain tail)
             return nn.functional.binary_cross_entropy_with_logits(
-                ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph), labels.float())
+                ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, cosine=cosine), labels.float())
         holder.row_map = compact.node_map
         return ops.hem_bce_loss(self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer), rows, item_indices, labels,
-                                head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder, rows_upper=compact.compact_rows(rows))
+                                head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder, rows_upper=compact.compact_rows(rows), cosine=cosine)
 
     def supports_fused_loss(self, loss_function) -> bool:
         return (isinstance(loss_function, nn.BCEWithLogitsLoss) and loss_function.reduction == 'mean' and loss_function.weight is None
-                and loss_function.pos_weight is None and self._saved_output_feature is None and not Gs.Prediction.use_cosine_similarity
+                and loss_function.pos_weight is None and self._saved_output_feature is None
                 and len(self.gnns) + 1 <= 8 and next(self.parameters()).is_cuda)
 
     def score_all_items(self, user_indices: Tensor, query_indices: Tensor) -> Tensor:
@@ -256,19 +258,23 @@ class RawGnn(nn.Module):
         notebooks - the evaluation loop uses ``top_items``, which never builds that matrix).
 
         Same arithmetic as ``forward(u * ones(I), q * ones(I), None)`` per pair (``RawGnn.py:124-137`` +
-        ``PredictionLayers.py:35-43``), batched: ``(lam*F[q] + (1-lam)*F[u]) @ F_items^T + bias``."""
+        ``PredictionLayers.py:35-43``), batched: ``(lam*F[q] + (1-lam)*F[u]) @ F_items^T + bias``; under ``Gs.Prediction.use_cosine_similarity`` both sides'
+        rows are divided by ``max(norm, 1e-8)`` first (``torch.cosine_similarity``)."""
         features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
         ds, head = self.dataset, self.prediction_layer
         item_feature = features[ds.item_start_index_in_graph:]
         lam = head.lambda_muq
         mixed = lam * features[query_indices + ds.query_start_index_in_graph] + (1 - lam) * features[user_indices]
+        if Gs.Prediction.use_cosine_similarity:
+            mixed = mixed / mixed.norm(dim=1, keepdim=True).clamp_min(1e-8)
+            item_feature = item_feature / item_feature.norm(dim=1, keepdim=True).clamp_min(1e-8)
         return torch.addmm(head.items_bias.unsqueeze(0), mixed, item_feature.t())
 
     def top_items(self, user_indices: Tensor, query_indices: Tensor, k: int = 10):
         """``(items [C, k] int32, scores [C, k])``: the ``k`` best items of each (user, query) pair over the whole catalogue, best
         first - what ``Metrics.calculate_on_all_items`` keeps of ``forward(u, q, None)`` (``Metrics.py:60-61``) - from the fused
         HIP scoring + running top-k kernel; the ``[C, I]`` scores are never stored.  Ties: ascending item id.  No torch path: any feature width
-        ``d (L + 1)`` up to ``MAX_SCORED_WIDTH`` (checked at construction)."""
+        ``d (L + 1)`` up to ``MAX_SCORED_WIDTH`` (checked at construction).  Scores with the head that ``Gs.Prediction.use_cosine_similarity`` names."""
         from .. import ops
         features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
         ds, head = self.dataset, self.prediction_layer
@@ -276,7 +282,7 @@ class RawGnn(nn.Module):
         if k > 10:
             raise NotImplementedError('RawGnn.top_items keeps at most ten items per pair (the reference reports HR / NDCG / MAP @10, Metrics.py:60-88)')
         return ops.score_topk(features, user_indices, query_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph,
-                              head.items_bias, head.lambda_muq, k)
+                              head.items_bias, head.lambda_muq, k, cosine=Gs.Prediction.use_cosine_similarity)
 
     def save_features_for_test(self) -> None:
         """Cache one propagation for the evaluation loop (call under ``torch.no_grad()``)."""

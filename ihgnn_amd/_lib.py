@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # IHGNN_HIP_LIBRARY points at another build of the same ABI (A/B timing of kernel variants); default: the in-tree library
 LIB_PATH = os.environ.get('IHGNN_HIP_LIBRARY') or os.path.join(_HERE, 'csrc', 'libihgnn_hip.so')
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 OK, ERR_INVALID, ERR_LAUNCH, ERR_WORKSPACE = 0, -1, -2, -3
 SCALE_NONE, SCALE_MULTIPLY, SCALE_DIVIDE = 0, 1, 2
@@ -127,6 +127,13 @@ SIGNATURES = {
     'ihg_hem_score_bwd_typed0': (ctypes.c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64, _i64p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                                 c_void_p, c_int64, c_int64, c_void_p]),
     'ihg_batch_rows_put': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, _i64p, c_int32, c_void_p]),
+    # the cosine head (Gs.Prediction.use_cosine_similarity): the _typed0 shape plus the per-row stats, and ihg_score_topk's signature
+    'ihg_hem_cosine_fwd': (ctypes.c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64, _i64p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                          c_void_p, c_void_p, c_int64, c_void_p]),
+    'ihg_hem_cosine_bwd': (ctypes.c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64, _i64p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                          c_void_p, c_int64, c_int64, c_void_p]),
+    'ihg_score_topk_cosine': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
+                                             c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'ihg_zero_floats': (ctypes.c_int, [c_void_p, c_int64, c_void_p]),
     'ihg_mark_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_batch_node_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

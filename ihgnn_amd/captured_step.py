@@ -98,9 +98,12 @@ class CapturedTrainingStep:
         self._baked = self._baked_settings()
 
     def _baked_hyperparameters(self):
-        """The optimizer's hyper-parameters and the model attribute a replay cannot change any more (cheap: compared at every ``step()``)."""
+        """The optimizer's hyper-parameters, the model attribute and the scoring head (``Gs.Prediction.use_cosine_similarity``: the model reads it at every call, the
+        recording holds the kernels of the head that was set) a replay cannot change any more (cheap: compared at every ``step()``)."""
+        from .Helpers.GlobalSettings import Gs
         group = self.optimizer.param_groups[0]
-        return (tuple(group['betas']), float(group['eps']), float(group['weight_decay']), bool(self.model.batch_rows_only_last_layer))
+        return (tuple(group['betas']), float(group['eps']), float(group['weight_decay']), bool(self.model.batch_rows_only_last_layer),
+                bool(Gs.Prediction.use_cosine_similarity))
 
     def _baked_settings(self):
         """Everything a replay cannot change any more: the recording holds the kernels these settings selected.  Only the learning rate is
@@ -115,12 +118,12 @@ class CapturedTrainingStep:
 
     def stale(self, full: bool = False) -> bool:
         """True when a setting that is baked into the recording has changed since: the caller must record a new step (``TrainTestHelper`` does) - replaying would
-        silently ignore the change.  The default compares Adam's betas / eps / weight decay and ``batch_rows_only_last_layer`` - four values, what every ``step()``
-        checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
+        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer`` and the scoring head - five values, what
+        every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
         epoch, not per replay on the launch-bound path the recording exists for)."""
         if full:
             return self._baked != self._baked_settings()
-        return self._baked[:4] != self._baked_hyperparameters()
+        return self._baked[:5] != self._baked_hyperparameters()
 
     TABLE_STEPS = 2048
 
@@ -139,7 +142,7 @@ class CapturedTrainingStep:
         if users.shape[0] != self.batch_rows:
             raise ValueError(f'this step was recorded for batches of {self.batch_rows} rows, got {users.shape[0]}')
         if self.stale():
-            raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay or batch_rows_only_last_layer - the values '
+            raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay, batch_rows_only_last_layer or the scoring head - the values '
                                'every step() compares; the IHG_* environment and the switches of ihgnn_amd.ops are compared by stale(full=True), which the training loop '
                                'asks once per epoch); record a new step')
         self.users.copy_(users, non_blocking=True)

@@ -80,17 +80,32 @@ __device__ __forceinline__ void eval_split8(const float (&x)[8], v4u& hi, v4u& l
 
 // Item rows -> frag[tile][ks][plane][lane][8 x fp16] (tile = 32 items, ks = 16 columns; lane = 32 (column half of the k-step) + item % 32: the A fragment of
 // v_mfma_f32_32x32x16_f16), aux[item] = {inverse scale, bias}.  One wave per item row; columns past `dim` are zero.
+// COSINE (Gs.Prediction.use_cosine_similarity, PredictionLayers.py:38-40): the row's sum of squares is reduced beside its largest magnitude and
+// aux[item].x = inverse scale / max(||a||, 1e-8) - the hot loop of score_topk_kernel multiplies by it as it does by the plain inverse scale.
+constexpr float kEvalCosineEps = 1e-8f;
+
+template <bool COSINE = false>
 __global__ __launch_bounds__(kBlockThreads) void score_prepare_kernel(const float* __restrict__ feat, int64_t ld, int dim, int ksteps, int64_t item_row0, int64_t n_items,
                                                                       const float* __restrict__ bias, v4u* __restrict__ frag, float2* __restrict__ aux) {
     const int lane = threadIdx.x & 63;
     for (int64_t item = global_wave_id(); item < n_items; item += global_wave_count()) {
         const float* row = feat + (item_row0 + item) * ld;
         float m = 0.f;
-        for (int c = lane; c < dim; c += kWave) m = fmaxf(m, fabsf(row[c]));
+        [[maybe_unused]] float ss = 0.f;
+        for (int c = lane; c < dim; c += kWave) {
+            const float v = row[c];
+            m = fmaxf(m, fabsf(v));
+            if constexpr (COSINE) ss += v * v;
+        }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
         float inv;
         const float sc = eval_scale_up_for(m, inv);
+        if constexpr (COSINE) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
+            inv /= fmaxf(sqrtf(ss), kEvalCosineEps);
+        }
         if (lane == 0) aux[item] = make_float2(inv, bias[item]);
         const int64_t tile = item >> 5;
         for (int chunk = lane; chunk < 2 * ksteps; chunk += kWave) {      // eight consecutive columns
@@ -107,7 +122,7 @@ __global__ __launch_bounds__(kBlockThreads) void score_prepare_kernel(const floa
 }
 
 // grid (pair blocks of 32 PB pairs, item slices); 512 threads.  partial[(pair * n_lists + list) * kTopMax + p]
-template <int PB>
+template <int PB, bool COSINE = false>
 __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
     const float* __restrict__ feat, int64_t ld, int dim, int ksteps, const v4u* __restrict__ frag, const float2* __restrict__ aux, int64_t n_items,
     const int64_t* __restrict__ users, const int64_t* __restrict__ queries, int64_t query_row0, float lam, int64_t n_pairs,
@@ -126,11 +141,21 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
         const float* qrow = feat + (queries[pr] + query_row0) * ld;
         const float* urow = feat + users[pr] * ld;
         float m = 0.f;
-        for (int c = lane; c < dim; c += kWave) m = fmaxf(m, fabsf(lam * qrow[c] + (1.f - lam) * urow[c]));
+        [[maybe_unused]] float ss = 0.f;
+        for (int c = lane; c < dim; c += kWave) {
+            const float v = lam * qrow[c] + (1.f - lam) * urow[c];
+            m = fmaxf(m, fabsf(v));
+            if constexpr (COSINE) ss += v * v;
+        }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
         float inv;
         const float sc = eval_scale_up_for(m, inv);
+        if constexpr (COSINE) {                                             // pinv = inverse scale / max(||m||, eps): the cosine's other factor
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
+            inv /= fmaxf(sqrtf(ss), kEvalCosineEps);
+        }
         if (lane == 0) pinv[r] = inv;
         for (int chunk = lane; chunk < 2 * ksteps; chunk += kWave) {
             float x[8];
@@ -291,6 +316,48 @@ inline int eval_slices(int64_t n_pairs, int64_t n_items, int dim) {
 inline int64_t eval_frag_bytes(int64_t n_items, int dim) { return ((n_items + 31) / 32) * eval_ksteps(dim) * 2 * kWave * 16; }
 inline int64_t eval_aux_bytes(int64_t n_items) { return ((n_items + 31) / 32) * 32 * 8; }
 
+template <bool COSINE>
+int score_topk_launch(const char* what, const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
+                   const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
+                   int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
+    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kTopMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (k <= %d)", what, kTopMax);
+    if (n_pairs == 0) return IHG_OK;
+    if (features == nullptr || item_bias == nullptr || users == nullptr || queries == nullptr || top_scores == nullptr || top_items == nullptr)
+        return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
+    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
+    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_score_topk_workspace_bytes(n_pairs, n_items, dim))
+        return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
+    const int slices = eval_slices(n_pairs, n_items, dim);
+    const int64_t n_lists = static_cast<int64_t>(slices) * kEvalWavesPerBlock * 2;
+    v4u* frag = static_cast<v4u*>(workspace);
+    float2* aux = reinterpret_cast<float2*>(static_cast<unsigned char*>(workspace) + eval_frag_bytes(n_items, dim));
+    float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
+    int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
+    hipLaunchKernelGGL(score_prepare_kernel<COSINE>, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux);
+    static bool attr_set[64] = {};                           // per device ordinal: the opt-in to > 64 KB of LDS belongs to the device's code object
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
+    if (device < 0 || device >= 64 || !attr_set[device]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (device >= 0 && device < 64) attr_set[device] = true;
+    }
+    const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
+    const size_t lds = eval_lds_bytes(dim, pb);
+    if (pb == 2)
+        hipLaunchKernelGGL((score_topk_kernel<2, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx);
+    else
+        hipLaunchKernelGGL((score_topk_kernel<1, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx);
+    hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs,
+                       static_cast<int>(n_lists * kTopMax), k, top_scores, top_items);
+    return check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -311,42 +378,14 @@ int64_t ihg_score_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t
 int ihg_score_topk(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                    const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
                    int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
-    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kTopMax || ld < dim) return fail(IHG_ERR_INVALID, "ihg_score_topk: bad size (k <= %d)", kTopMax);
-    if (n_pairs == 0) return IHG_OK;
-    if (features == nullptr || item_bias == nullptr || users == nullptr || queries == nullptr || top_scores == nullptr || top_items == nullptr)
-        return fail(IHG_ERR_INVALID, "ihg_score_topk: null pointer");
-    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "ihg_score_topk: item ids are int32");
-    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "ihg_score_topk: feature width %d does not fit the LDS pair block (widest: %d)", dim, ihg_score_topk_max_dim());
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_score_topk_workspace_bytes(n_pairs, n_items, dim))
-        return fail(IHG_ERR_WORKSPACE, "ihg_score_topk: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
-    const int slices = eval_slices(n_pairs, n_items, dim);
-    const int64_t n_lists = static_cast<int64_t>(slices) * kEvalWavesPerBlock * 2;
-    v4u* frag = static_cast<v4u*>(workspace);
-    float2* aux = reinterpret_cast<float2*>(static_cast<unsigned char*>(workspace) + eval_frag_bytes(n_items, dim));
-    float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
-    int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
-    hipLaunchKernelGGL(score_prepare_kernel, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux);
-    static bool attr_set[64] = {};                           // per device ordinal: the opt-in to > 64 KB of LDS belongs to the device's code object
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
-    if (device < 0 || device >= 64 || !attr_set[device]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (device >= 0 && device < 64) attr_set[device] = true;
-    }
-    const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
-    const size_t lds = eval_lds_bytes(dim, pb);
-    if (pb == 2)
-        hipLaunchKernelGGL(score_topk_kernel<2>, dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx);
-    else
-        hipLaunchKernelGGL(score_topk_kernel<1>, dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx);
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs,
-                       static_cast<int>(n_lists * kTopMax), k, top_scores, top_items);
-    return check_launch("ihg_score_topk");
+    return score_topk_launch<false>("ihg_score_topk", features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace, workspace_bytes, stream);
+}
+
+// the cosine head: the same kernels with the rows' inverse norms folded into the two scale factors (score_prepare_kernel<true>, score_topk_kernel<PB, true>)
+int ihg_score_topk_cosine(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
+                   const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
+                   int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
+    return score_topk_launch<true>("ihg_score_topk_cosine", features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -81,7 +81,91 @@ __global__ __launch_bounds__(kBlockThreads) void hem_score_bwd_kernel(LayerPtrs 
     }
 }
 
+// ================================================================================================
+// The cosine head (Gs.Prediction.use_cosine_similarity, Models/PredictionLayers.py:38-40): the same rows, the same addressing, but the score is
+//   c = (a . m) / (max(||a||, eps) max(||m||, eps)) + bias[item],   a = [X_0 | .. | X_L][item],  m = lam a[query] + (1 - lam) a[user],  eps = 1e-8
+// (torch.cosine_similarity).  The norms run over the WHOLE concatenated row: an isolated node's zero rows above layer 0 add nothing to the sums but the other
+// rows' squares still count, so no layer is skipped.  fwd leaves the three sums of a row in stats[r] = {a.m, ||a||^2, ||m||^2, 0} (16 B per row); bwd reads them
+// and every column's three outputs follow from a[c] and m[c] alone.  torch clamps the norm's VALUE and differentiates the unclamped norm (d||a||/da = a / ||a||, 0 at a = 0):
+//   dc/da = m / (na nm) - c a / (na ||a||),   dc/dm = a / (na nm) - c m / (nm ||m||)      (second terms 0 for a zero row; = c a / na^2 wherever ||a|| >= eps)
+//   rowgrad[0B + r] = ds (1 - lam) dc/dm,  rowgrad[1B + r] = ds lam dc/dm,  rowgrad[2B + r] = ds dc/da  - the layout of hem_score_bwd_kernel, bias column included.
+// ================================================================================================
+constexpr float kCosineEps = 1e-8f;
 
+__global__ __launch_bounds__(kBlockThreads) void hem_cosine_fwd_kernel(LayerPtrs layers, int n_layers, int dim,
+                                                                       const int64_t* __restrict__ rows, const int64_t* __restrict__ items,
+                                                                       const float* __restrict__ bias, float lam, float* __restrict__ scores,
+                                                                       float4* __restrict__ stats, int64_t batch, const int64_t* __restrict__ rows_upper) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t r = global_wave_id(); r < batch; r += global_wave_count()) {
+        float dot = 0.f, aa = 0.f, mm = 0.f;
+        for (int l = 0; l < n_layers; ++l) {
+            const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
+            const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
+            const float* pu = layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l];
+            const float* pq = layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l];
+            const float* pi = layers.x[l][2] + (it < 0 ? 0 : it) * layers.ld[l];
+            for (int c = lane; c < dim; c += kWave) {
+                const float xu = u < 0 ? 0.f : pu[c], xq = q < 0 ? 0.f : pq[c], a = it < 0 ? 0.f : pi[c];
+                const float m = lam * xq + (1.f - lam) * xu;
+                dot += a * m;
+                aa += a * a;
+                mm += m * m;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) dot += __shfl_xor(dot, o);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) aa += __shfl_xor(aa, o);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mm += __shfl_xor(mm, o);
+        if (lane == 0) {
+            const float na = fmaxf(sqrtf(aa), kCosineEps), nm = fmaxf(sqrtf(mm), kCosineEps);
+            scores[r] = dot / (na * nm) + bias[items[r]];
+            stats[r] = make_float4(dot, aa, mm, 0.f);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlockThreads) void hem_cosine_bwd_kernel(LayerPtrs layers, int n_layers, int dim,
+                                                                       const int64_t* __restrict__ rows, const float* __restrict__ dscores,
+                                                                       const float4* __restrict__ stats, float grad_scale, float lam,
+                                                                       float* __restrict__ rowgrad, int64_t width, int64_t batch,
+                                                                       const float* __restrict__ grad_scale_device, const int64_t* __restrict__ rows_upper) {
+    const int lane = threadIdx.x & 63;
+    if (grad_scale_device != nullptr) grad_scale *= *grad_scale_device;      // (as in hem_score_bwd_kernel)
+    for (int64_t r = global_wave_id(); r < batch; r += global_wave_count()) {
+        const float ds = dscores[r] * grad_scale;
+        if (lane == 0 && width > static_cast<int64_t>(n_layers) * dim) {
+            const int64_t col = static_cast<int64_t>(n_layers) * dim;
+            rowgrad[r * width + col] = 0.f;
+            rowgrad[(batch + r) * width + col] = 0.f;
+            rowgrad[(2 * batch + r) * width + col] = ds;
+        }
+        const float4 st = stats[r];
+        const float ra = sqrtf(st.y), rm = sqrtf(st.z);
+        const float na = fmaxf(ra, kCosineEps), nm = fmaxf(rm, kCosineEps);
+        const float cross = 1.f / (na * nm);
+        const float cosv = st.x * cross;
+        const float ka = ra > 0.f ? cosv / na / ra : 0.f, km = rm > 0.f ? cosv / nm / rm : 0.f;      // (ra >= sqrt(smallest denormal) = 3.7e-23 where it is not 0: no overflow)
+        for (int l = 0; l < n_layers; ++l) {
+            const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
+            const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
+            const float* pu = layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l];
+            const float* pq = layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l];
+            const float* pi = layers.x[l][2] + (it < 0 ? 0 : it) * layers.ld[l];
+            for (int c = lane; c < dim; c += kWave) {
+                const float xu = u < 0 ? 0.f : pu[c], xq = q < 0 ? 0.f : pq[c], a = it < 0 ? 0.f : pi[c];
+                const float m = lam * xq + (1.f - lam) * xu;
+                const float dm = ds * (a * cross - km * m);
+                const int64_t col = static_cast<int64_t>(l) * dim + c;
+                rowgrad[r * width + col] = (1.f - lam) * dm;
+                rowgrad[(batch + r) * width + col] = lam * dm;
+                rowgrad[(2 * batch + r) * width + col] = ds * (m * cross - ka * a);
+            }
+        }
+    }
+}
 
 constexpr int kScatterThreads = 1024;
 
@@ -435,6 +519,41 @@ int ihg_hem_score_bwd_typed0(const float* const* layers, int32_t n_layers, int64
     hipLaunchKernelGGL(hem_score_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
                        dim, rows, dscores, grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch, grad_scale_device, rows_upper);
     return check_launch("ihg_hem_score_bwd_typed0");
+}
+
+static int hem_cosine_check(const char* what, const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                            const int64_t* type_begin, int64_t batch) {
+    if (layer0_rows != nullptr && (type_begin == nullptr || ld0 < dim)) return fail(IHG_ERR_INVALID, "%s: type ranges / row stride of layer 0 missing", what);
+    if (n_layers < 1 || n_layers > 8 || ld < dim || dim <= 0 || batch < 0 || layers == nullptr) return fail(IHG_ERR_INVALID, "%s: bad size", what);
+    for (int l = layer0_rows != nullptr ? 1 : 0; l < n_layers; ++l)
+        if (layers[l] == nullptr) return fail(IHG_ERR_INVALID, "%s: null layer pointer", what);
+    return IHG_OK;
+}
+
+int ihg_hem_cosine_fwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                       const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const int64_t* items, const float* bias, float lambda_muq,
+                       float* scores, float* stats, int64_t batch, ihg_stream_t stream) {
+    if (int rc = hem_cosine_check("ihg_hem_cosine_fwd", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
+    if (batch == 0) return IHG_OK;
+    if (rows == nullptr || items == nullptr || bias == nullptr || scores == nullptr || stats == nullptr || !aligned16(stats))
+        return fail(IHG_ERR_INVALID, "ihg_hem_cosine_fwd: null pointer or stats not 16-byte aligned");
+    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
+    hipLaunchKernelGGL(hem_cosine_fwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
+                       dim, rows, items, bias, lambda_muq, scores, reinterpret_cast<float4*>(stats), batch, rows_upper);
+    return check_launch("ihg_hem_cosine_fwd");
+}
+
+int ihg_hem_cosine_bwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                       const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const float* dscores, const float* stats,
+                       const float* grad_scale_device, float grad_scale, float lambda_muq, float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream) {
+    if (int rc = hem_cosine_check("ihg_hem_cosine_bwd", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
+    if (batch == 0) return IHG_OK;
+    if (rows == nullptr || dscores == nullptr || stats == nullptr || !aligned16(stats) || rowgrad == nullptr || ld_rowgrad < static_cast<int64_t>(n_layers) * dim)
+        return fail(IHG_ERR_INVALID, "ihg_hem_cosine_bwd: null pointer, stats not 16-byte aligned or short row stride");
+    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
+    hipLaunchKernelGGL(hem_cosine_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
+                       dim, rows, dscores, reinterpret_cast<const float4*>(stats), grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch, grad_scale_device, rows_upper);
+    return check_launch("ihg_hem_cosine_bwd");
 }
 
 int ihg_bce_with_logits(const float* scores, const float* labels, int64_t n, float* loss, float* dscores, ihg_stream_t stream) {

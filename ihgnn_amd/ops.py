@@ -1429,9 +1429,32 @@ def interact_layer(h: Tensor, w: Tensor, bias: Optional[Tensor], layout: Inciden
 # ---------------------------------------------------------------------------------------------
 # Batch tail: HEM scores of a training batch straight from the layer outputs
 # ---------------------------------------------------------------------------------------------
-def _hem_row_gradients(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, dscores: Tensor, grad_scale: float, tables=None, grad_scale_device=None, rows_upper=None):
+def _hem_cosine_operands(layers, tables, dim: int):
+    """``(layers, (layer0_rows, ld0, type_begin))`` of the cosine entry points: plain matrices, or layer 0 as the embedding tables in place."""
+    if tables is None:
+        return (ctypes.c_void_p * len(layers))(*[x.data_ptr() for x in layers]), (None, 0, None)
+    ptrs = (ctypes.c_void_p * (len(layers) + 1))(tables.query_rows.data_ptr(), *[x.data_ptr() for x in layers])     # (slot 0 is replaced by the typed rows)
+    return ptrs, (tables.row_pointers(), dim, tables.type_begin())
+
+
+def _hem_cosine_forward(layers, tables, rows: Tensor, rows_upper: Optional[Tensor], items: Tensor, bias: Tensor, lam: float, scores: Tensor) -> Tensor:
+    """The cosine head's scores of a batch into ``scores`` (the caller names the launch to the profiler); returns the rows' ``[B, 4]`` stats (``a . m``, ``||a||^2``, ``||m||^2``, 0: include/ihgnn_hip.h) for the backward.
+    One entry point for plain matrices, the embedding tables in place (``tables``) and a layout's own numbering above layer 0 (``rows_upper``)."""
+    lib = _lib.load()
+    batch = int(items.shape[0])
+    dim = int(layers[0].shape[1]) if layers else tables.dim
+    stats = torch.empty(batch, 4, dtype=torch.float32, device=bias.device)
+    ptrs, typed0 = _hem_cosine_operands(layers, tables, dim)
+    _lib.check(lib.ihg_hem_cosine_fwd(ptrs, len(ptrs), _ld(layers[0]) if layers else dim, dim, *typed0, _ptr(rows), _ptr(rows_upper), _ptr(items), _ptr(bias), float(lam),
+                                      _ptr(scores), _ptr(stats), batch, _stream()), 'ihg_hem_cosine_fwd')
+    return stats
+
+
+def _hem_row_gradients(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, dscores: Tensor, grad_scale: float, tables=None, grad_scale_device=None, rows_upper=None,
+                       stats: Optional[Tensor] = None):
     """Per-batch-row gradients of the tail: ``[3B, (L+1) d + 4]``, layer l in columns ``l d .. (l+1) d``, d bias in column ``(L+1) d``.  ``tables`` (a resolved
-    ``NodeTables``): layer 0 is read from the embedding tables in place and ``layers`` are the outputs of the layers above it."""
+    ``NodeTables``): layer 0 is read from the embedding tables in place and ``layers`` are the outputs of the layers above it.  ``stats`` (``[B, 4]``, left by the
+    cosine head's forward): the cosine head's row gradients, same layout."""
     lib = _lib.load()
     batch = int(items.shape[0])
     dim = int(layers[0].shape[1]) if layers else tables.dim
@@ -1440,6 +1463,12 @@ def _hem_row_gradients(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: f
     rowgrad = torch.empty(3 * batch, width + 4, dtype=torch.float32, device=bias.device)
     if grad_scale_device is not None and (grad_scale_device.dtype != torch.float32 or grad_scale_device.numel() != 1):
         raise TypeError('grad_scale_device is a float32 device scalar')
+    if stats is not None:
+        ptrs, typed0 = _hem_cosine_operands(layers, tables, dim)
+        with profiler.kernel('hem_cosine_bwd', batch, dim):
+            _lib.check(lib.ihg_hem_cosine_bwd(ptrs, n_layers, _ld(layers[0]) if layers else dim, dim, *typed0, _ptr(rows), _ptr(rows_upper), _ptr(dscores), _ptr(stats),
+                                              _ptr(grad_scale_device), float(grad_scale), float(lam), _ptr(rowgrad), width + 4, batch, _stream()), 'ihg_hem_cosine_bwd')
+        return rowgrad
     with profiler.kernel('hem_score_bwd', batch, dim):
         if tables is None:
             ptrs = (ctypes.c_void_p * n_layers)(*[x.data_ptr() for x in layers])
@@ -1473,14 +1502,14 @@ def _scatter_rows(rowgrad: Tensor, col0: int, width: int, rows: Tensor, dense: O
                                                  int(tail.shape[0]) if tail is not None else 0, _stream()), 'ihg_batch_scatter_add')
 
 
-def _hem_backward(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, dscores: Tensor, grad_scale: float, item_row_offset: int):
+def _hem_backward(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, dscores: Tensor, grad_scale: float, item_row_offset: int, stats: Optional[Tensor] = None):
     """Backward of the batch tail without taps: per-row gradients (one kernel), then ONE deterministic scatter that lands every
     layer's gradient in its own contiguous ``[N, d]`` matrix and d bias beside them.  -> (d bias, layer gradients)."""
     lib = _lib.load()
     batch, dim, n_layers = int(items.shape[0]), int(layers[0].shape[1]), len(layers)
     width = n_layers * dim
     n_nodes = int(layers[0].shape[0])
-    rowgrad = _hem_row_gradients(layers, rows, items, bias, lam, dscores, grad_scale)
+    rowgrad = _hem_row_gradients(layers, rows, items, bias, lam, dscores, grad_scale, stats=stats)
     n_bias = int(bias.shape[0])
     flat = torch.zeros(n_layers * n_nodes * dim + n_bias, dtype=torch.float32, device=bias.device)
     dense = flat[:n_layers * n_nodes * dim].view(n_layers, n_nodes, dim)
@@ -1622,24 +1651,29 @@ def _same_layout(layers):
 
 class _HemScore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rows: Tensor, items: Tensor, bias: Tensor, lam: float, item_row_offset: int, *layers: Tensor) -> Tensor:
+    def forward(ctx, rows: Tensor, items: Tensor, bias: Tensor, lam: float, item_row_offset: int, cosine: bool, *layers: Tensor) -> Tensor:
         lib = _lib.load()
         layers = _same_layout(layers)
         batch, dim = int(items.shape[0]), int(layers[0].shape[1])
-        ptrs = (ctypes.c_void_p * len(layers))(*[x.data_ptr() for x in layers])
         scores = torch.empty(batch, dtype=torch.float32, device=bias.device)
-        with profiler.kernel('hem_score_fwd', batch, dim):
-            _lib.check(lib.ihg_hem_score_fwd(ptrs, len(layers), _ld(layers[0]), dim, _ptr(rows), _ptr(items), _ptr(bias), float(lam), _ptr(scores),
-                                             batch, _stream()), 'ihg_hem_score_fwd')
+        stats = None
+        if cosine:
+            with profiler.kernel('hem_cosine_fwd', batch, dim):
+                stats = _hem_cosine_forward(layers, None, rows, None, items, bias, lam, scores)
+        else:
+            ptrs = (ctypes.c_void_p * len(layers))(*[x.data_ptr() for x in layers])
+            with profiler.kernel('hem_score_fwd', batch, dim):
+                _lib.check(lib.ihg_hem_score_fwd(ptrs, len(layers), _ld(layers[0]), dim, _ptr(rows), _ptr(items), _ptr(bias), float(lam), _ptr(scores),
+                                                 batch, _stream()), 'ihg_hem_score_fwd')
         ctx.save_for_backward(rows, items, bias, *layers)
-        ctx.lam, ctx.offset = float(lam), int(item_row_offset)
+        ctx.lam, ctx.offset, ctx.stats = float(lam), int(item_row_offset), stats
         return scores
 
     @staticmethod
     def backward(ctx, dscores: Tensor):
         rows, items, bias, *layers = ctx.saved_tensors
-        dbias, grads = _hem_backward(layers, rows, items, bias, ctx.lam, dscores.contiguous(), 1.0, ctx.offset)
-        return (None, None, dbias, None, None) + grads
+        dbias, grads = _hem_backward(layers, rows, items, bias, ctx.lam, dscores.contiguous(), 1.0, ctx.offset, ctx.stats)
+        return (None, None, dbias, None, None, None) + grads
 
 
 class _HemBceLoss(torch.autograd.Function):
@@ -1648,7 +1682,8 @@ class _HemBceLoss(torch.autograd.Function):
     returned here); without one they are returned dense."""
 
     @staticmethod
-    def forward(ctx, rows: Tensor, items: Tensor, labels: Tensor, bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, *layers: Tensor) -> Tensor:
+    def forward(ctx, rows: Tensor, items: Tensor, labels: Tensor, bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, cosine: bool,
+                *layers: Tensor) -> Tensor:
         # tables (a resolved NodeTables): layer 0 is the embedding tables in place; layers[0] is then its token (the autograd edge), not a matrix
         lib = _lib.load()
         real = _same_layout(layers[1:] if tables is not None else layers)
@@ -1657,8 +1692,11 @@ class _HemBceLoss(torch.autograd.Function):
         dscores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         loss = torch.empty((), dtype=torch.float32, device=bias.device)
         labels = labels.to(torch.float32).contiguous()
-        with profiler.kernel('hem_score_fwd', batch, dim):
-            if tables is None and rows_upper is None:
+        stats = None
+        with profiler.kernel('hem_cosine_fwd' if cosine else 'hem_score_fwd', batch, dim):
+            if cosine:
+                stats = _hem_cosine_forward(real, tables, rows, rows_upper, items, bias, lam, scores)     # (one entry point for the three forms of the layers below)
+            elif tables is None and rows_upper is None:
                 ptrs = (ctypes.c_void_p * len(real))(*[x.data_ptr() for x in real])
                 _lib.check(lib.ihg_hem_score_fwd(ptrs, len(real), _ld(real[0]), dim, _ptr(rows), _ptr(items), _ptr(bias), float(lam), _ptr(scores),
                                                  batch, _stream()), 'ihg_hem_score_fwd')
@@ -1673,7 +1711,7 @@ class _HemBceLoss(torch.autograd.Function):
                                                         _ptr(rows), _ptr(rows_upper), _ptr(items), _ptr(bias), float(lam), _ptr(scores), batch, _stream()), 'ihg_hem_score_fwd_typed0')
             _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), batch, _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
         ctx.save_for_backward(rows, items, bias, dscores, *real)
-        ctx.rows_upper = rows_upper
+        ctx.rows_upper, ctx.stats = rows_upper, stats
         ctx.lam, ctx.offset, ctx.holder, ctx.tables = float(lam), int(item_row_offset), holder, tables
         ctx.token_shape = tuple(layers[0].shape) if tables is not None else None
         return loss
@@ -1685,10 +1723,10 @@ class _HemBceLoss(torch.autograd.Function):
         if ctx.holder is None:
             if tables is not None or ctx.rows_upper is not None:
                 raise _lib.IhgnnHipError('hem_bce_loss over NodeTables / a compact layout needs a TailGradients holder')
-            dbias, grads = _hem_backward(layers, rows, items, bias, ctx.lam, dscores * grad_loss, 1.0, ctx.offset)
-            return (None, None, None, dbias, None, None, None, None, None) + grads
+            dbias, grads = _hem_backward(layers, rows, items, bias, ctx.lam, dscores * grad_loss, 1.0, ctx.offset, ctx.stats)
+            return (None, None, None, dbias, None, None, None, None, None, None) + grads
         holder = ctx.holder
-        rowgrad = _hem_row_gradients(layers, rows, items, bias, ctx.lam, dscores, holder.grad_scale, tables, grad_loss.contiguous(), ctx.rows_upper)     # d loss stays on the device: no host read, no multiply launch
+        rowgrad = _hem_row_gradients(layers, rows, items, bias, ctx.lam, dscores, holder.grad_scale, tables, grad_loss.contiguous(), ctx.rows_upper, ctx.stats)     # d loss stays on the device: no host read, no multiply launch
         lib = _lib.load()
         if holder.exchange is not None:
             # every rank's propagation is the same function of the same parameters and its backward is linear in the cotangent of the layer outputs, which is non-zero on
@@ -1731,7 +1769,7 @@ class _HemBceLoss(torch.autograd.Function):
         placeholders = tuple(_zero_like_expanded(x.shape, x.device) for x in layers)
         if tables is not None:
             placeholders = (_zero_like_expanded(ctx.token_shape, bias.device),) + placeholders
-        return (None, None, None, dbias, None, None, None, None, None) + placeholders
+        return (None, None, None, dbias, None, None, None, None, None, None) + placeholders
 
 
 def score_topk_max_width() -> int:
@@ -1745,10 +1783,11 @@ def score_topk_supported(features: Tensor) -> bool:
             and (features.shape[0] <= 1 or features.stride(0) >= features.shape[1]))
 
 
-def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int = 10):
+def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int = 10, cosine: bool = False):
     """Evaluation scoring: for every (user, query) pair the ``k`` best items over ALL items and their HEM scores,
     ``(top_items [C, k] int32, top_scores [C, k])``, best first, ties in ascending item order; the ``[C, I]`` score matrix is
-    never materialised.  ``features`` = the cached ``[N, D]`` propagation output (any width up to ``score_topk_max_width()``); items are its rows from ``item_row0`` on."""
+    never materialised.  ``features`` = the cached ``[N, D]`` propagation output (any width up to ``score_topk_max_width()``); items are its rows from ``item_row0`` on.
+    ``cosine``: the cosine-similarity head (``Gs.Prediction.use_cosine_similarity``) - same kernels, the rows' inverse norms folded into their scale factors."""
     lib = _lib.load()
     if not score_topk_supported(features):
         raise _lib.IhgnnHipError(f'ihg_score_topk needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
@@ -1761,10 +1800,11 @@ def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int
     top_scores = torch.empty(n_pairs, k, dtype=torch.float32, device=features.device)
     top_items = torch.empty(n_pairs, k, dtype=torch.int32, device=features.device)
     ws = _workspace(int(lib.ihg_score_topk_workspace_bytes(n_pairs, n_items, dim)), features.device)
-    with profiler.kernel('score_topk', n_pairs, dim):
-        _lib.check(lib.ihg_score_topk(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias),
-                                      _ptr(users), _ptr(queries), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws),
-                                      ws.numel() * 4, _stream()), 'ihg_score_topk')
+    name = 'score_topk_cosine' if cosine else 'score_topk'
+    with profiler.kernel(name, n_pairs, dim):
+        _lib.check(getattr(lib, 'ihg_' + name)(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias),
+                                               _ptr(users), _ptr(queries), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws),
+                                               ws.numel() * 4, _stream()), 'ihg_' + name)
     return top_items, top_scores
 
 
@@ -1793,18 +1833,19 @@ def backward(loss: Tensor) -> None:
     loss.backward(one)
 
 
-def hem_score(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, item_row_offset: int) -> Tensor:
+def hem_score(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, item_row_offset: int, cosine: bool = False) -> Tensor:
     """HEM scores of a batch: ``rows`` = global node rows of users, queries, items (``[3B]`` int64), ``items`` = 0-based item
-    ids (``[B]``), ``layers`` = the ``[N,d]`` outputs ``X_0..X_L`` whose concatenation the reference scores on."""
-    return _HemScore.apply(rows, items, bias, float(lam), int(item_row_offset), *layers)
+    ids (``[B]``), ``layers`` = the ``[N,d]`` outputs ``X_0..X_L`` whose concatenation the reference scores on.  ``cosine``: the cosine-similarity head
+    (``Gs.Prediction.use_cosine_similarity``, ``PredictionLayers.py:38-40``) instead of the dot product."""
+    return _HemScore.apply(rows, items, bias, float(lam), int(item_row_offset), bool(cosine), *layers)
 
 
 def hem_bce_loss(layers, rows: Tensor, items: Tensor, labels: Tensor, bias: Tensor, lam: float, item_row_offset: int,
-                 holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None) -> Tensor:
+                 holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
     """``nn.BCEWithLogitsLoss()(hem_score(...), labels)`` as one differentiable op (scalar).  ``holder``: the layers are the
     tail halves of ``tap`` outputs made with this holder, and their gradients travel through it (see ``TailGradients``).  ``rows_upper`` (with ``holder.row_map``): the
     layers above layer 0 are numbered by the layout's own node ids (a layout without the isolated nodes): their rows of the batch, -1 = isolated = zero.  ``layers[0]`` may be a
-    ``NodeTables`` (resolved by the first layer's transform): the head reads its layer-0 rows from the embedding tables in place."""
+    ``NodeTables`` (resolved by the first layer's transform): the head reads its layer-0 rows from the embedding tables in place.  ``cosine``: as in ``hem_score``."""
     tables = None
     layers = list(layers)
     if layers and isinstance(layers[0], NodeTables):
@@ -1814,4 +1855,4 @@ def hem_bce_loss(layers, rows: Tensor, items: Tensor, labels: Tensor, bias: Tens
         layers[0] = tables.token
     if rows_upper is not None and holder is not None and holder.row_map is None:
         raise ValueError('rows_upper comes with holder.row_map (the layout\'s public -> own node map)')
-    return _HemBceLoss.apply(rows, items, labels, bias, float(lam), int(item_row_offset), holder, tables, rows_upper, *layers)
+    return _HemBceLoss.apply(rows, items, labels, bias, float(lam), int(item_row_offset), holder, tables, rows_upper, bool(cosine), *layers)

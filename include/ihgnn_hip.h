@@ -547,6 +547,30 @@ int ihg_batch_rows_put(const float* src, int64_t ld_src, int32_t width, const in
                        float* const* dense_rows, int64_t ld_dense, const int64_t* type_begin, int32_t assign, ihg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE: the cosine-similarity head (Gs.Prediction.use_cosine_similarity, Models/PredictionLayers.py:38-40).  With a the item's concatenated row
+ * [X_0 | .. | X_L][item] and m = lambda a[query] + (1 - lambda) a[user]:
+ *   score = (a . m) / (max(||a||, 1e-8) max(||m||, 1e-8)) + bias[item]        (torch.cosine_similarity and its autograd: the norm's value is clamped, its derivative a / ||a|| is not)
+ * The norms run over the whole concatenated row; an isolated node's zero rows above layer 0 (negative rows_upper) add zeros to the sums.
+ *   ihg_hem_cosine_fwd   arguments of ihg_hem_score_fwd_typed0 (layer0_rows / ld0 / type_begin and rows_upper may be NULL) plus
+ *                        stats [batch][4] floats, 16-byte aligned, caller-owned: stats[r] = {a . m, ||a||^2, ||m||^2, 0} of batch row r, kept for the backward
+ *   ihg_hem_cosine_bwd   arguments of ihg_hem_score_bwd_typed0 plus the stats of the forward; writes the same [3 batch, ld_rowgrad] row gradients
+ *                        (user rows | query rows | item rows, layer l in columns l dim .., d bias in column n_layers dim of the item rows where ld_rowgrad leaves room),
+ *                        so everything downstream of them (ihg_batch_combine, ihg_batch_rows_add / _put, the cotangent exchange) is shared with the dot-product head
+ *   ihg_score_topk_cosine  ihg_score_topk (same arguments, workspace and width limit) for this head: the item rows' and the mixed rows' inverse norms are folded into
+ *                        the two scale factors the kernel multiplies its accumulators by; the loop over the items is the same code
+ * No host reads, no allocations: a stream capture holds all three.
+ */
+int ihg_hem_cosine_fwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                       const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const int64_t* items, const float* bias, float lambda_muq,
+                       float* scores, float* stats, int64_t batch, ihg_stream_t stream);
+int ihg_hem_cosine_bwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                       const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const float* dscores, const float* stats,
+                       const float* grad_scale_device, float grad_scale, float lambda_muq, float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream);
+int ihg_score_topk_cosine(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
+                          const float* item_bias, const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs,
+                          int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE: the attention of the GAT baseline over the pairwise graph (csrc/gat.hip).  Replaces GATLayer.forward after its transform
  * (Models/GnnLayers.py:98-115: the [nnz, 2, d] row gather, feature_aggregate, dgl.ops.edge_softmax and dgl.ops.u_mul_e_sum) and autograd's backward of it.
  * Graph: the symmetric CSR of the pairwise adjacency (ihg_build_pair_csr) - entry p of row v with column u = ids[p] is the edge u -> v, so row v lists

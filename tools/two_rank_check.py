@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """N ranks of the HIP model == 1 rank on the union batch, runnable on ONE GPU.
 
-    python tools/two_rank_check.py [--ranks 2] [--sync flat|bucketed|sharded|cotangent] [--device 0] [--backend gloo]
+    python tools/two_rank_check.py [--ranks 2] [--sync flat|bucketed|sharded|cotangent] [--device 0] [--backend gloo] [--cosine]
 
 The parent starts the rank processes before touching the GPU (as bench.py does).  Every rank builds the same RawGnn replica on
 GPU `--device` (RCCL refuses two ranks on one GPU, so the single-GPU form uses gloo; on a multi-GPU node pass `--backend nccl
@@ -33,6 +33,7 @@ def main():
     ap.add_argument('--steps', type=int, default=2, help='training steps; beyond a handful the comparison with the one-rank run is dropped (Adam amplifies rounding noise entry by entry) and only the '
                     'replicas are compared with each other: bitwise, under the cotangent exchange')
     ap.add_argument('--batch', type=int, default=64, help='batch rows per rank (8 ranks x 700: the union of the ranks\' 3 B batch rows exceeds 16,384 - the wide instance of the combine kernel)')
+    ap.add_argument('--cosine', action='store_true', help='the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity): its row gradients travel in the same layout')
     args = ap.parse_args()
     if 'WORLD_SIZE' not in os.environ:
         import socket
@@ -53,7 +54,9 @@ def main():
     from ihgnn_amd.Dataset import GraphDataset
     from ihgnn_amd.Models import HemPredictionLayer, IHGNNLayer, RawGnn
     from ihgnn_amd.optim import Adam
+    from ihgnn_amd.Helpers.GlobalSettings import Gs
 
+    Gs.Prediction.use_cosine_similarity = bool(args.cosine)
     rank, local, world = ihg_dist.init_from_env(args.backend)
     dev = torch.device(f'cuda:{args.device if args.device >= 0 else local}')
     torch.cuda.set_device(dev)
