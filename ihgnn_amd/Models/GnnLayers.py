@@ -58,7 +58,7 @@ class HGCNLayer(nn.Module):
         self.general = isinstance(self.layout, LogHyperLayout)  # per-search-log hyperedges of variable arity (PpsLogHyperGraph)
         if not self.general:
             self.edge_scale = float(torch.tensor(3.0).pow(-1))      # De^-1 of a 3-uniform hypergraph, as fp32
-            self.out_scale = self.layout.inv_sqrt_deg * self.edge_scale
+            self.out_scale = self.layout.inv_sqrt_deg_times(self.edge_scale)      # (one vector per layout, shared by its layers)
         self.feature_transform = nn.Linear(input_dimension, output_dimension)
 
     def reads_cotangent_rows_only(self) -> bool:

@@ -26,6 +26,7 @@ OK, ERR_INVALID, ERR_LAUNCH, ERR_WORKSPACE = 0, -1, -2, -3
 SCALE_NONE, SCALE_MULTIPLY, SCALE_DIVIDE = 0, 1, 2
 SCALE_ACCUMULATE = 0x100      # OR-ed into the mode of ihg_node_segment_sum: out += instead of out =
 SRC_READ_ONCE = 0x400         # OR-ed into the mode of ihg_node_segment_sum: every source row of this launch is read exactly once (non-temporal loads)
+SRC_SCALE_IN_ENTRIES = 0x800  # OR-ed into the mode of ihg_node_segment_sum: entry_scale already holds src_scale[ids] (x the entry weights); src_scale serves the row's own term only
 
 _i64p, _i32p, _f32p = POINTER(c_int64), POINTER(c_int32), POINTER(c_float)
 

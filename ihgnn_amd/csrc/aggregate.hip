@@ -143,10 +143,12 @@ __device__ __forceinline__ Frag<VEC> accumulate_list(const float* __restrict__ s
     for (int base = 0; base < wave_max_len; base += G) {
         const bool have = base + lig < len;
         int my_id = have ? ids[begin + base + lig] : -1;
+        // the entry's weight sits beside its id: asked for in the same batch as the id (its address does not need the id), selected away below where the id is not live
+        const float my_entry = (entry_scale != nullptr && have) ? entry_scale[begin + base + lig] : 1.f;
         if (src_mask != nullptr && have && src_mask[my_id] == 0) my_id = -1;      // a source row known to be zero: not fetched
         const bool live = my_id >= 0;
         float my_w = (src_scale != nullptr && live) ? src_scale[my_id] : 1.f;
-        if (entry_scale != nullptr && live) my_w *= entry_scale[begin + base + lig];
+        if (entry_scale != nullptr && live) my_w *= my_entry;
 #pragma unroll 1
         for (int j = 0; j < G; j += UNR) {
             if (base + j >= wave_max_len) break;      // wave-uniform: nothing left in any group
@@ -188,7 +190,7 @@ __device__ __forceinline__ Frag<VEC> accumulate_list_masked(const float* __restr
         if (have && src_mask[my_id] == 0) my_id = -1;
         const bool live = my_id >= 0;
         float my_w = (src_scale != nullptr && live) ? src_scale[my_id] : 1.f;
-        if (entry_scale != nullptr && live) my_w *= entry_scale[begin + base + lig];
+        if (entry_scale != nullptr && live) my_w *= entry_scale[begin + base + lig];      // (only the listed ids, a per cent or two: not hoisted to the id load as in accumulate_list - that would stream every entry's weight)
         uint64_t gm = __ballot(live) >> group_base;
         if (G < 64) gm &= (uint64_t{1} << G) - 1;
         while (__ballot(gm != 0) != 0) {                                     // wave-uniform: until every group has walked its listed ids
@@ -240,7 +242,8 @@ __global__ __launch_bounds__(kBlockThreads, IHG_K7_WAVES) void node_segment_sum_
     const float* __restrict__ out_scale, int mode,
     float* __restrict__ out, int64_t ld_out, int64_t n_rows, int dim, int dim_vec, int heavy_threshold,
     const int32_t* __restrict__ seg_begin, const int32_t* __restrict__ seg_end, int64_t n_segments, float* __restrict__ partials,
-    const float* __restrict__ self_weight, const uint8_t* __restrict__ src_mask) {
+    const float* __restrict__ self_weight, const uint8_t* __restrict__ src_mask, const float* __restrict__ self_scale) {
+    // src_scale: the per-source factor the GATHER applies (null under IHG_SRC_SCALE_IN_ENTRIES: the entries carry it); self_scale: the same vector for the row's own term
     constexpr int GPW = kWave / G;
     const int lane = threadIdx.x & (kWave - 1);
     const int lig = lane & (G - 1);
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(kBlockThreads, IHG_K7_WAVES) void node_segment_sum_
                 if (scale_row >= 0) {
                     if (self_weight != nullptr && (src_mask == nullptr || src_mask[scale_row] != 0))   // square operators: the row's own source row, weighted (a masked row is zero: not fetched)
                         acc.add_scaled(Frag<VEC>::load(src + scale_row * ld_src + col * VEC),
-                                       self_weight[scale_row] * (src_scale != nullptr ? src_scale[scale_row] : 1.f));
+                                       self_weight[scale_row] * (self_scale != nullptr ? self_scale[scale_row] : 1.f));
                     apply_out_scale<VEC>(acc, out_scale, mode, scale_row);
                     if (mode & IHG_SCALE_ACCUMULATE) acc.add(Frag<VEC>::load(dst + col * VEC));     // out += (hyperedge chunks of one scatter)
                 }
@@ -602,22 +605,26 @@ void launch_segment_sum_g(const float* src, int64_t ld_src, const int32_t* rowpt
     constexpr int GPW = kWave / G;
     const int dim_vec = dim / VEC;
     const int grid = agg_grid((n_rows + hp.n_segments + GPW - 1) / GPW);
+    // IHG_SRC_SCALE_IN_ENTRIES: entry_scale[p] already holds src_scale[ids[p]] (times the entry's weight) - the gather does not fetch the scale per id, the
+    // row's own term (here and in the split-row finish) still takes it
+    const float* self_scale = src_scale;
+    if (mode & IHG_SRC_SCALE_IN_ENTRIES) src_scale = nullptr;
     if (hp.src_mask != nullptr)                               // the masked pull: its own instance (see accumulate_list)
         hipLaunchKernelGGL((node_segment_sum_kernel<VEC, G, true>), dim3(grid), dim3(kBlockThreads), 0, stream, src, ld_src, rowptr, ids, row_order,
                            src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, dim_vec, heavy_threshold, hp.seg_begin, hp.seg_end,
-                           hp.n_segments, hp.partials, self_weight, hp.src_mask);
+                           hp.n_segments, hp.partials, self_weight, hp.src_mask, self_scale);
     else if (mode & IHG_SRC_READ_ONCE)
         hipLaunchKernelGGL((node_segment_sum_kernel<VEC, G, false, true>), dim3(grid), dim3(kBlockThreads), 0, stream, src, ld_src, rowptr, ids, row_order,
                            src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, dim_vec, heavy_threshold, hp.seg_begin, hp.seg_end,
-                           hp.n_segments, hp.partials, self_weight, hp.src_mask);
+                           hp.n_segments, hp.partials, self_weight, hp.src_mask, self_scale);
     else
         hipLaunchKernelGGL((node_segment_sum_kernel<VEC, G>), dim3(grid), dim3(kBlockThreads), 0, stream, src, ld_src, rowptr, ids, row_order,
                            src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, dim_vec, heavy_threshold, hp.seg_begin, hp.seg_end,
-                           hp.n_segments, hp.partials, self_weight, hp.src_mask);
+                           hp.n_segments, hp.partials, self_weight, hp.src_mask, self_scale);
     if (hp.n_heavy > 0)
         hipLaunchKernelGGL((heavy_finish_kernel<VEC, G>), dim3(static_cast<int>(std::min<int64_t>(hp.n_heavy, kMaxBlocks * 4))),
                            dim3(kBlockThreads), 0, stream, hp.partials, hp.heavy_rows, hp.heavy_segptr, hp.n_heavy, out_scale, mode, out,
-                           ld_out, dim, dim_vec, src, ld_src, src_scale, self_weight, hp.src_mask);
+                           ld_out, dim, dim_vec, src, ld_src, self_scale, self_weight, hp.src_mask);
 }
 
 template <int VEC>
@@ -637,7 +644,7 @@ int launch_segment_sum(const float* src, int64_t ld_src, const int32_t* rowptr, 
 }
 
 inline bool scale_mode_ok(int mode, const float* scale) {
-    if (mode & ~(0xff | IHG_SCALE_ACCUMULATE | IHG_SRC_READ_ONCE)) return false;
+    if (mode & ~(0xff | IHG_SCALE_ACCUMULATE | IHG_SRC_READ_ONCE | IHG_SRC_SCALE_IN_ENTRIES)) return false;
     mode &= 0xff;
     if (mode == IHG_SCALE_NONE) return true;
     return (mode == IHG_SCALE_MULTIPLY || mode == IHG_SCALE_DIVIDE) && scale != nullptr;
@@ -685,6 +692,8 @@ int ihg_node_segment_sum(const float* src, int64_t ld_src, const int32_t* rowptr
     if (src == nullptr || rowptr == nullptr || ids == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: null pointer");
     if (n_heavy > 0 && (heavy_threshold <= 0 || seg_begin == nullptr || seg_end == nullptr || heavy_rows == nullptr || heavy_segptr == nullptr || partials == nullptr))
         return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: incomplete split-row plan");
+    if ((out_scale_mode & IHG_SRC_SCALE_IN_ENTRIES) && (src_scale == nullptr || entry_scale == nullptr))
+        return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: IHG_SRC_SCALE_IN_ENTRIES needs src_scale and entry_scale");
     if (n_heavy == 0) {
         n_segments = 0;
         heavy_threshold = 0;

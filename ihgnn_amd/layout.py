@@ -168,6 +168,9 @@ MULTIPLICITY_MIN_EDGES = int(os.environ.get('IHG_MULTIPLICITY_MIN_EDGES', 1 << 1
 # the first-order launches walk the two-hop list with a row's repeated (destination, source) entries merged into one weighted entry when at least this share of
 # the 6 E entries are repeats (C5: 79 %; C3 / C4 / C2: 8.6 / 13.6 / 17.9 %, where round 5 measured no gain - the repeats were cache hits); ops.TWO_HOP_MERGED overrides
 TWO_HOP_MERGED_MIN_SHARE = float(os.environ.get('IHG_TWO_HOP_MERGED_MIN_SHARE', 0.25))
+# per-entry source weights of the two-hop lists (IncidenceLayout.two_hop_source_weights): how many (list, scale vector) pairs a layout keeps - inv_deg and inv_sqrt_deg
+# (x De^-1 for HGCN's output side) over one of the two lists is all the layers ask for
+SOURCE_WEIGHT_SLOTS = 4
 # IHG_COMPACT_NODES = auto | 0 | 1: number the nodes INSIDE the layout without the isolated ones (nodes that are in no hyperedge).  Every layer output of such a node is exactly
 # zero (an empty sum times Dv^-1, App. B 2) and nobody gathers its rows, so the propagation - pair sums, node-level contractions, linear maps and their backward - runs on
 # the N' nodes that have hyperedges; the public numbering (embedding tables, batch indices, evaluation, PpsHyperGraph's tensors) stays the reference's (Graph.py:110-111) and the
@@ -406,6 +409,48 @@ class IncidenceLayout:
             weights = torch.from_numpy(counts[:n].copy()).to(self.device)
             cached = self.__dict__['_two_hop_merged'] = (csr, weights, 1.0 - n / max(6 * self.hyperedge_count, 1))
         return cached
+
+    def two_hop_source_weights(self, scale: torch.Tensor, merged: bool, max_bytes: Optional[int] = None) -> Optional[torch.Tensor]:
+        """``w[p] = scale[ids[p]]`` over the two-hop list (``merged``: ``scale[ids[p]] * weights[p]`` over the merged one, the product formed in float32 in that
+        order - what the K7 kernel forms per entry from ``src_scale`` and ``entry_scale``, bit for bit).  A launch that takes a per-source scale (the backward of a
+        first-order layer, HGCN's forward) then reads its factor beside the id, one coalesced load, instead of gathering ``scale`` by id in front of the row loads
+        (``IHG_SRC_SCALE_IN_ENTRIES``).  ``scale`` is graph data (``inv_deg``, ``inv_sqrt_deg``): built on first use per (list, vector) and kept, each entry
+        holding its vector, so an address is never mistaken for another tensor's; a vector changed in place is rebuilt.
+        ``None`` - the caller keeps the per-id gather - when the weights of the list would exceed ``max_bytes`` (4 bytes per entry), or when the layout already
+        keeps ``SOURCE_WEIGHT_SLOTS`` other vectors (a caller that makes a new scale vector every step gets no rebuild per step and no growing cache)."""
+        if merged:
+            csr, entry_weights, _ = self.two_hop_merged()
+        else:
+            csr, entry_weights = self.hop2_csr, None
+        if max_bytes is not None and 4 * csr.nnz > max_bytes:
+            return None
+        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != self.node_count or scale.device != csr.ids.device:
+            raise ValueError(f'two_hop_source_weights: scale must be a float32 [{self.node_count}] tensor on {csr.ids.device}')
+        cache = self.__dict__.setdefault('_two_hop_source_weights', {})
+        key = (bool(merged), scale.data_ptr())
+        hit = cache.get(key)
+        if hit is None or hit[1] != scale._version:
+            if hit is None and len(cache) >= SOURCE_WEIGHT_SLOTS:
+                return None
+            w = torch.index_select(scale.detach(), 0, csr.ids)
+            if entry_weights is not None:
+                w = w * entry_weights
+            hit = cache[key] = (scale, scale._version, w)
+        return hit[2]
+
+    def inv_sqrt_deg_times(self, factor: float) -> torch.Tensor:
+        """``inv_sqrt_deg * factor`` (``HGCNLayer``'s output scale ``Dv^-1/2 De^-1``): one vector per factor, owned by the layout and shared by every layer over it,
+        so the per-entry source weights are built once for all of them."""
+        cache = self.__dict__.setdefault('_inv_sqrt_deg_times', {})
+        key = float(factor)
+        if key not in cache:
+            cache[key] = self.inv_sqrt_deg * key
+        return cache[key]
+
+    def has_two_hop_source_weights(self, scale: torch.Tensor, merged: bool) -> bool:
+        """Whether ``two_hop_source_weights(scale, merged)`` is already built (a stream capture must not build it: the build is not part of the step)."""
+        hit = self.__dict__.get('_two_hop_source_weights', {}).get((bool(merged), scale.data_ptr()))
+        return hit is not None and hit[1] == scale._version
 
     def drop_row_mask(self) -> None:
         """Forget the mask (the next ``row_mask()`` makes a fresh all-zero one): what a user that raised between its set and its clear calls."""

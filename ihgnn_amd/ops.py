@@ -82,12 +82,14 @@ def node_segment_sum_raw(src: Tensor, csr: Union[Csr, CsrRows], src_scale: Optio
                          out_scale: Optional[Tensor] = None, mode: int = _lib.SCALE_NONE,
                          out: Optional[Tensor] = None, entry_scale: Optional[Tensor] = None,
                          self_weight: Optional[Tensor] = None, rows: Optional[Tensor] = None, src_mask: Optional[Tensor] = None,
-                         role: Optional[str] = None, accumulate: bool = False, read_once: bool = False) -> Tensor:
+                         role: Optional[str] = None, accumulate: bool = False, read_once: bool = False, src_scale_in_entries: bool = False) -> Tensor:
     """``role`` names the launch for the profiler (one kernel, several jobs with different byte counts: ``bench.py`` reports each).
     ``rows`` (int32, device): only these output rows are needed.  The split rows of the plan are always computed; of the
     others only the listed ones are, and the rest of ``out`` is left unwritten.  ``src_mask`` (uint8 per source row): rows with a 0
     are all-zero and are not fetched.  ``accumulate``: ``out +=`` instead of ``out =`` (``out`` required; the hyperedge chunks of one scatter; with ``rows``: the listed rows and the plan's split rows).
-    ``read_once``: every source row is read exactly once by this launch (non-temporal loads)."""
+    ``read_once``: every source row is read exactly once by this launch (non-temporal loads).  ``src_scale_in_entries``: ``entry_scale[p]`` already holds
+    ``src_scale[ids[p]]`` (times the entry's weight; ``IncidenceLayout.two_hop_source_weights``) - the gather does not fetch ``src_scale`` per id, the row's own
+    term still takes it."""
     lib = _lib.load()
     src = _rows(src, 'src')
     dim = int(src.shape[1])
@@ -97,6 +99,8 @@ def node_segment_sum_raw(src: Tensor, csr: Union[Csr, CsrRows], src_scale: Optio
         mode = mode | _lib.SCALE_ACCUMULATE
     if read_once:
         mode = mode | _lib.SRC_READ_ONCE
+    if src_scale_in_entries:
+        mode = mode | _lib.SRC_SCALE_IN_ENTRIES
     if out is None:
         out = torch.empty(csr.n_rows, dim, dtype=torch.float32, device=src.device)
     heavy = csr.n_heavy > 0
@@ -218,10 +222,34 @@ def _two_hop_list(layout: IncidenceLayout):
     return layout.hop2_csr, None
 
 
+# A two-hop launch with a per-source scale (the backward of a first-order layer: the two diagonal scalings swapped; HGCN's forward) gathered src_scale[id] for every
+# id of the list - a divergent 4-byte load per entry, and one more dependent round trip in front of the row loads (ids -> scale -> rows): 772 / 767 us against the
+# unscaled forward's 700 at C3.  The scale vectors are graph data, so the layout keeps scale[ids[p]] (x the merged list's weight) per ENTRY and the launch reads it beside
+# the id.  Lists whose weights would take more than SOURCE_WEIGHTS_MAX_BYTES keep the per-id gather: 128 MiB covers C3 (13.2 M entries, 53 MB) and C4 (19.8 M, 79 MB);
+# C5's merged list is past it and stays as it was.  IHG_K7_SOURCE_WEIGHTS=0 (or this attribute) turns it off: same bits either way.
+SOURCE_WEIGHTS_MAX_BYTES = 128 << 20
+SOURCE_WEIGHTS = _os.environ.get('IHG_K7_SOURCE_WEIGHTS', '1') != '0'
+
+
+def two_hop_scaled_list(layout: IncidenceLayout, src_scale: Optional[Tensor]):
+    """``(csr, entry weights or None, src_scale_in_entries)`` for a two-hop launch that scales its source rows by ``src_scale``."""
+    csr, weights = _two_hop_list(layout)
+    if src_scale is None or not SOURCE_WEIGHTS:
+        return csr, weights, False
+    merged = weights is not None
+    if src_scale.is_cuda and torch.cuda.is_current_stream_capturing() and not layout.has_two_hop_source_weights(src_scale, merged):
+        return csr, weights, False                            # (a capture without its warm-up steps: the build is no part of the recorded step)
+    folded = layout.two_hop_source_weights(src_scale, merged, SOURCE_WEIGHTS_MAX_BYTES)
+    if folded is None:
+        return csr, weights, False
+    return csr, folded, True
+
+
 def _two_hop_first_order_gradient(dy: Tensor, layout: IncidenceLayout, out_scale: Optional[Tensor]) -> Tensor:
     """``d P = H H^T (out_scale * dy)``: the first-order blocks' gradient of the interactive layer by the two-hop operator on the node-level cotangent."""
-    csr, weights = _two_hop_list(layout)
-    return node_segment_sum_raw(dy, csr, out_scale, None, _lib.SCALE_NONE, entry_scale=weights, self_weight=layout.self_weight, role='k7.two_hop_first_order_gradient')
+    csr, weights, folded = two_hop_scaled_list(layout, out_scale)
+    return node_segment_sum_raw(dy, csr, out_scale, None, _lib.SCALE_NONE, entry_scale=weights, self_weight=layout.self_weight, role='k7.two_hop_first_order_gradient',
+                                src_scale_in_entries=folded)
 
 
 class _TwoHop(torch.autograd.Function):
@@ -236,9 +264,9 @@ class _TwoHop(torch.autograd.Function):
         # rows outside which the cotangent is zero: the rows that were computed at all, or the caller's explicit promise
         ctx.cot_rows = rows if rows is not None else (cotangent_rows if SPARSE_LAST_COTANGENT else None)
         mode = _lib.SCALE_NONE if out_scale is None else _lib.SCALE_MULTIPLY
-        csr, weights = _two_hop_list(layout)
+        csr, weights, folded = two_hop_scaled_list(layout, in_scale)
         return node_segment_sum_raw(x, csr, in_scale, out_scale, mode, entry_scale=weights, self_weight=layout.self_weight, rows=rows, role='k7.two_hop',
-                                    out=_check_out(out, x))
+                                    out=_check_out(out, x), src_scale_in_entries=folded)
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
@@ -258,9 +286,11 @@ class _TwoHop(torch.autograd.Function):
                 _lib.check(lib.ihg_mark_rows(r64, r32, int(rows.shape[0]), _ptr(mask), 0, _stream()), 'ihg_mark_rows')
                 raise RuntimeError('node_two_hop: the cotangent is not zero outside cotangent_rows / rows - the output has a consumer the caller did not declare')
         try:
-            csr, weights = _two_hop_list(lay)
+            # (the masked pull keeps the per-id gather: it fetches the scale of the LISTED ids only, a per cent or two of the list, while the per-entry weights
+            # are a stream over every entry - measured at C3: 149 us by id, 169 with the weights)
+            csr, weights, folded = two_hop_scaled_list(lay, ctx.out_scale if mask is None else None)
             out = node_segment_sum_raw(grad_out, csr, ctx.out_scale, ctx.in_scale, mode, entry_scale=weights, self_weight=lay.self_weight, src_mask=mask,
-                                       role='k7.two_hop_bwd' if mask is None else 'k7.two_hop_bwd_masked')
+                                       role='k7.two_hop_bwd' if mask is None else 'k7.two_hop_bwd_masked', src_scale_in_entries=folded)
             if mask is not None:
                 _lib.check(lib.ihg_mark_rows(r64, r32, int(rows.shape[0]), _ptr(mask), 0, _stream()), 'ihg_mark_rows')
         except BaseException:

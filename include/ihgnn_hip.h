@@ -35,6 +35,7 @@ extern "C" {
 #define IHG_SCALE_DIVIDE      2   /* out[r] = sum / scale[r]   (EmbeddingBag 'mean': scale = bag length) */
 #define IHG_SRC_READ_ONCE     0x400 /* OR-ed into out_scale_mode of ihg_node_segment_sum: every source row is read exactly once by this launch (a scatter of per-member rows) - non-temporal loads */
 #define IHG_SCALE_ACCUMULATE  0x100 /* OR-ed into out_scale_mode of ihg_node_segment_sum: out[r] += (scaled) sum - the hyperedge chunks of one scatter add up in `out` */
+#define IHG_SRC_SCALE_IN_ENTRIES 0x800 /* OR-ed into out_scale_mode of ihg_node_segment_sum: entry_scale[k] already holds src_scale[ids[k]] (times the entry's own weight), so the gather does not fetch src_scale per id; src_scale is still read for the row's own term (self_weight).  Needs both pointers. */
 
 typedef void* ihg_stream_t;       /* hipStream_t */
 
@@ -176,6 +177,8 @@ int ihg_edge_gather_sum_planes(const float* src, int64_t ld_src, const int32_t* 
  * decreasing row length keeps the groups of one wave equally busy; NULL = natural order.  Results do not depend on it.
  * It may also be a SUBSET of the rows (n_rows = its length; rowptr is still indexed by row id): only those rows, and the
  * rows of the split-row plan, are written - the last layer of a training step, whose output is read at the batch rows only.
+ * With IHG_SRC_SCALE_IN_ENTRIES in the mode word w(ids[k]) = entry_scale[k] alone: the caller has folded src_scale[ids[k]] into the entries (a list and a scale
+ * vector that stay the same from launch to launch: one coalesced 4-byte load beside the id instead of a divergent gather per id); w(r) of the row's own term stays src_scale[r].
  * `src_mask` (optional, one byte per source row): rows with a 0 are known to be all-zero and are not fetched (the gradient
  * of that last layer's output is zero outside the batch rows).
  * Replaces: thsp.matmul(self.incidence, edge_features) and Dv^-1 * / Dv^-1/2 * (Models/GnnLayers.py:151-152,

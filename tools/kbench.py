@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the individual HIP ops at a bench.py workload shape (interleaved rounds, HIP-event timing).
 
-    python tools/kbench.py [--config C2] [--rounds 10] [--ops k5,k7,pairs,twohop,interact,layer0,layer,ifwd,linear]
+    python tools/kbench.py [--config C2] [--rounds 10] [--ops k5,k7,pairs,masked,twohop,twohop_bwd,twohop_hgcn,interact,layer0,layer,ifwd,linear]
 """
 import argparse
 import os
@@ -56,6 +56,13 @@ def main():
             ops.node_segment_sum_raw(xm, lay.hop2_csr, lay.inv_deg, None, 0, self_weight=lay.self_weight, src_mask=mask, role='k7.two_hop_bwd_masked')
         if 'twohop' in want:                                              # a first-order layer's two-hop launch
             ops.node_segment_sum_raw(x, lay.hop2_csr, None, lay.inv_deg, 1, self_weight=lay.self_weight, role='k7.two_hop')
+        if 'twohop_bwd' in want:                                          # the same launch with a per-source scale: a first-order layer's backward (the scale beside
+            csr, weights, folded = ops.two_hop_scaled_list(lay, lay.inv_deg)     # the ids unless IHG_K7_SOURCE_WEIGHTS=0)
+            ops.node_segment_sum_raw(dy_layer, csr, lay.inv_deg, None, 0, entry_scale=weights, self_weight=lay.self_weight, role='k7.two_hop_bwd', src_scale_in_entries=folded)
+        if 'twohop_hgcn' in want:                                         # HGCNLayer's forward: Dv^-1/2 on the way in, Dv^-1/2 De^-1 on the way out
+            csr, weights, folded = ops.two_hop_scaled_list(lay, lay.inv_sqrt_deg)
+            ops.node_segment_sum_raw(x, csr, lay.inv_sqrt_deg, lay.inv_sqrt_deg_times(1 / 3), 1, entry_scale=weights, self_weight=lay.self_weight, role='k7.two_hop_hgcn',
+                                     src_scale_in_entries=folded)
         if 'linear' in want:
             xr = x.detach().requires_grad_(True)
             y = ops.node_linear(xr, wt, b, lay)
