@@ -95,18 +95,15 @@ class RawGnn(nn.Module):
         x = None
         padded = self.compute_width != self.embedding_size
         compact = self._compact_layout()
-        if (tail_gradients is not None and last >= 1 and ops.NODE_TABLES and not padded and compact is None
+        tables = None
+        if (tail_gradients is not None and last >= 1 and ops.NODE_TABLES and not padded
                 and (batch_rows is None or int(batch_rows.shape[0]) <= ops.SCATTER_CHUNK_ROWS)):
             # a training step through the fused batch tail: X0 is not assembled - the first layer's transform and the tail read the embedding tables in place
-            x = self.embeddings.node_tables(tail_gradients)
-        tables = None
-        if (tail_gradients is not None and last >= 1 and ops.NODE_TABLES and not padded and compact is not None
-                and (batch_rows is None or int(batch_rows.shape[0]) <= ops.SCATTER_CHUNK_ROWS)):
-            # ... over a layout without the isolated nodes: the active nodes' rows are gathered straight from the tables ([N', d]; the public [N, d] is never assembled), the
-            # tail reads its layer-0 rows from the tables in place and the gather's backward adds their gradients to the tables' gradients
             tables = self.embeddings.node_tables(tail_gradients)
-            if tables is not None:
-                x = ops.gather_active_nodes(tables, compact)
+        if tables is not None:
+            # ... over a layout without the isolated nodes the active nodes' rows are gathered straight from the tables ([N', d]; the public [N, d] is never assembled), the
+            # tail reads its layer-0 rows from the tables in place and the gather's backward adds their gradients to the tables' gradients
+            x = tables if compact is None else ops.gather_active_nodes(tables, compact)
         if x is None:
             x = self.embeddings.all_nodes()
             if padded:
@@ -132,11 +129,8 @@ class RawGnn(nn.Module):
                 else:
                     x = layer(x)
             if tail_gradients is not None:
-                if isinstance(x, ops.NodeTables):
-                    outputs.append(x)                        # (no tap: the first layer's transform adds the tail's layer-0 gradients itself)
-                    continue
                 if depth == 0 and tables is not None:
-                    outputs.append(tables)                   # (no tap either: the gather's backward adds them; x is already the layout's [N', d])
+                    outputs.append(tables)                   # (no tap: the first layer's transform - over a compact layout the gather's backward - adds the tail's layer-0 gradients itself)
                     continue
                 x, for_tail = ops.tap(x, tail_gradients, depth, sparse_top)
                 outputs.append(for_tail)
@@ -237,16 +231,15 @@ class RawGnn(nn.Module):
             holder = ops.TailGradients() if torch.is_grad_enabled() else None
             read_rows = rows
         compact = self._compact_layout()
-        if compact is None:
-            return ops.hem_bce_loss(self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer), rows, item_indices, labels,
-                                    head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder, cosine=cosine)
-        if holder is None:
+        if compact is not None and holder is None:
             # (no gradient wanted: the public matrices, the plain tail)
             return nn.functional.binary_cross_entropy_with_logits(
                 ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, cosine=cosine), labels.float())
-        holder.row_map = compact.node_map
-        return ops.hem_bce_loss(self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer), rows, item_indices, labels,
-                                head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder, rows_upper=compact.compact_rows(rows), cosine=cosine)
+        if compact is not None:
+            holder.row_map = compact.node_map
+        layers = self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer)
+        return ops.hem_bce_loss(layers, rows, item_indices, labels, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
+                                rows_upper=compact.compact_rows(rows) if compact is not None else None, cosine=cosine)
 
     def supports_fused_loss(self, loss_function) -> bool:
         return (isinstance(loss_function, nn.BCEWithLogitsLoss) and loss_function.reduction == 'mean' and loss_function.weight is None

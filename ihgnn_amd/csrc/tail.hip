@@ -22,20 +22,38 @@ struct LayerPtrs {
 
 // rows_upper (optional): the rows of the layers ABOVE layer 0 where they are numbered differently from layer 0's - a layout that leaves the isolated nodes out of its own
 // numbering (IncidenceLayout.node_map) while layer 0 is read from the embedding tables by public id; a negative entry is an isolated node: its rows above layer 0 are zero
+// (constants: the row gradients written for them are never added anywhere - ihg_batch_rows_add / _put skip negative rows)
+struct BatchRow {
+    const float *pu, *pq, *pi;                              // the user / query / item row of batch row r in layer l (the layer's first row where the id is negative: not read)
+    int64_t u, q, it;                                       // their ids; negative = a zero row
+};
+
+__device__ __forceinline__ BatchRow batch_row(const LayerPtrs& layers, int l, const int64_t* __restrict__ rows, const int64_t* __restrict__ rows_upper, int64_t batch, int64_t r) {
+    const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
+    const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
+    return {layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l], layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l], layers.x[l][2] + (it < 0 ? 0 : it) * layers.ld[l], u, q, it};
+}
+
+// optional extra column of the row gradients (width > L1 * d): d bias, carried by the item row
+__device__ __forceinline__ void bias_column(float* __restrict__ rowgrad, int64_t width, int n_layers, int dim, int64_t batch, int64_t r, float ds) {
+    if ((threadIdx.x & 63) == 0 && width > static_cast<int64_t>(n_layers) * dim) {
+        const int64_t col = static_cast<int64_t>(n_layers) * dim;
+        rowgrad[r * width + col] = 0.f;
+        rowgrad[(batch + r) * width + col] = 0.f;
+        rowgrad[(2 * batch + r) * width + col] = ds;
+    }
+}
+
 __global__ __launch_bounds__(kBlockThreads) void hem_score_fwd_kernel(LayerPtrs layers, int n_layers, int dim,
                                                                       const int64_t* __restrict__ rows, const int64_t* __restrict__ items,
                                                                       const float* __restrict__ bias, float lam, float* __restrict__ scores,
-                                                                      int64_t batch, const int64_t* __restrict__ rows_upper = nullptr) {
+                                                                      int64_t batch, const int64_t* __restrict__ rows_upper) {
     const int lane = threadIdx.x & 63;
     for (int64_t r = global_wave_id(); r < batch; r += global_wave_count()) {
         float acc = 0.f;
         for (int l = 0; l < n_layers; ++l) {
-            const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
-            const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
+            const auto [xu, xq, xi, u, q, it] = batch_row(layers, l, rows, rows_upper, batch, r);
             if (it < 0 || (u < 0 && q < 0)) continue;       // an isolated item (or both other rows zero): the layer adds nothing
-            const float* xu = layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l];
-            const float* xq = layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l];
-            const float* xi = layers.x[l][2] + it * layers.ld[l];
             const float wu = u < 0 ? 0.f : 1.f - lam, wq = q < 0 ? 0.f : lam;
             for (int c = lane; c < dim; c += kWave) {
                 const float m = wq * xq[c] + wu * xu[c];
@@ -51,25 +69,15 @@ __global__ __launch_bounds__(kBlockThreads) void hem_score_fwd_kernel(LayerPtrs 
 __global__ __launch_bounds__(kBlockThreads) void hem_score_bwd_kernel(LayerPtrs layers, int n_layers, int dim,
                                                                       const int64_t* __restrict__ rows, const float* __restrict__ dscores,
                                                                       float grad_scale, float lam, float* __restrict__ rowgrad, int64_t width,
-                                                                      int64_t batch, const float* __restrict__ grad_scale_device = nullptr,
-                                                                      const int64_t* __restrict__ rows_upper = nullptr) {
+                                                                      int64_t batch, const float* __restrict__ grad_scale_device,
+                                                                      const int64_t* __restrict__ rows_upper) {
     const int lane = threadIdx.x & 63;
     if (grad_scale_device != nullptr) grad_scale *= *grad_scale_device;      // the upstream gradient of the loss, still on the device (no host read, no extra launch)
     for (int64_t r = global_wave_id(); r < batch; r += global_wave_count()) {
         const float ds = dscores[r] * grad_scale;
-        if (lane == 0 && width > static_cast<int64_t>(n_layers) * dim) {       // optional extra column: d bias, carried by the item row
-            const int64_t col = static_cast<int64_t>(n_layers) * dim;
-            rowgrad[r * width + col] = 0.f;
-            rowgrad[(batch + r) * width + col] = 0.f;
-            rowgrad[(2 * batch + r) * width + col] = ds;
-        }
+        bias_column(rowgrad, width, n_layers, dim, batch, r, ds);
         for (int l = 0; l < n_layers; ++l) {
-            const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
-            const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
-            // (an isolated node's rows above layer 0 are zero constants: the row gradients written for them are never added anywhere - ihg_batch_rows_add / _put skip negative rows)
-            const float* pu = layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l];
-            const float* pq = layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l];
-            const float* pi = layers.x[l][2] + (it < 0 ? 0 : it) * layers.ld[l];
+            const auto [pu, pq, pi, u, q, it] = batch_row(layers, l, rows, rows_upper, batch, r);
             for (int c = lane; c < dim; c += kWave) {
                 const float xu = u < 0 ? 0.f : pu[c], xq = q < 0 ? 0.f : pq[c], xi = it < 0 ? 0.f : pi[c];
                 const int64_t col = static_cast<int64_t>(l) * dim + c;
@@ -100,11 +108,7 @@ __global__ __launch_bounds__(kBlockThreads) void hem_cosine_fwd_kernel(LayerPtrs
     for (int64_t r = global_wave_id(); r < batch; r += global_wave_count()) {
         float dot = 0.f, aa = 0.f, mm = 0.f;
         for (int l = 0; l < n_layers; ++l) {
-            const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
-            const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
-            const float* pu = layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l];
-            const float* pq = layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l];
-            const float* pi = layers.x[l][2] + (it < 0 ? 0 : it) * layers.ld[l];
+            const auto [pu, pq, pi, u, q, it] = batch_row(layers, l, rows, rows_upper, batch, r);
             for (int c = lane; c < dim; c += kWave) {
                 const float xu = u < 0 ? 0.f : pu[c], xq = q < 0 ? 0.f : pq[c], a = it < 0 ? 0.f : pi[c];
                 const float m = lam * xq + (1.f - lam) * xu;
@@ -133,15 +137,10 @@ __global__ __launch_bounds__(kBlockThreads) void hem_cosine_bwd_kernel(LayerPtrs
                                                                        float* __restrict__ rowgrad, int64_t width, int64_t batch,
                                                                        const float* __restrict__ grad_scale_device, const int64_t* __restrict__ rows_upper) {
     const int lane = threadIdx.x & 63;
-    if (grad_scale_device != nullptr) grad_scale *= *grad_scale_device;      // (as in hem_score_bwd_kernel)
+    if (grad_scale_device != nullptr) grad_scale *= *grad_scale_device;
     for (int64_t r = global_wave_id(); r < batch; r += global_wave_count()) {
         const float ds = dscores[r] * grad_scale;
-        if (lane == 0 && width > static_cast<int64_t>(n_layers) * dim) {
-            const int64_t col = static_cast<int64_t>(n_layers) * dim;
-            rowgrad[r * width + col] = 0.f;
-            rowgrad[(batch + r) * width + col] = 0.f;
-            rowgrad[(2 * batch + r) * width + col] = ds;
-        }
+        bias_column(rowgrad, width, n_layers, dim, batch, r, ds);
         const float4 st = stats[r];
         const float ra = sqrtf(st.y), rm = sqrtf(st.z);
         const float na = fmaxf(ra, kCosineEps), nm = fmaxf(rm, kCosineEps);
@@ -149,11 +148,7 @@ __global__ __launch_bounds__(kBlockThreads) void hem_cosine_bwd_kernel(LayerPtrs
         const float cosv = st.x * cross;
         const float ka = ra > 0.f ? cosv / na / ra : 0.f, km = rm > 0.f ? cosv / nm / rm : 0.f;      // (ra >= sqrt(smallest denormal) = 3.7e-23 where it is not 0: no overflow)
         for (int l = 0; l < n_layers; ++l) {
-            const int64_t* rr = (l > 0 && rows_upper != nullptr) ? rows_upper : rows;
-            const int64_t u = rr[r], q = rr[batch + r], it = rr[2 * batch + r];
-            const float* pu = layers.x[l][0] + (u < 0 ? 0 : u) * layers.ld[l];
-            const float* pq = layers.x[l][1] + (q < 0 ? 0 : q) * layers.ld[l];
-            const float* pi = layers.x[l][2] + (it < 0 ? 0 : it) * layers.ld[l];
+            const auto [pu, pq, pi, u, q, it] = batch_row(layers, l, rows, rows_upper, batch, r);
             for (int c = lane; c < dim; c += kWave) {
                 const float xu = u < 0 ? 0.f : pu[c], xq = q < 0 ? 0.f : pq[c], a = it < 0 ? 0.f : pi[c];
                 const float m = lam * xq + (1.f - lam) * xu;
@@ -464,95 +459,89 @@ static LayerPtrs layer_ptrs(const float* const* layers, int32_t n_layers, int64_
     return lp;
 }
 
-static int hem_common_check(const char* what, const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const int64_t* rows, int64_t batch) {
+// The one argument check of the six HEM entry points, in the name (`what`) of the one that was called.  IHG_OK = go on: an empty batch returns after it, the buffers are looked at last.
+static int hem_check(const char* what, const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                     const int64_t* type_begin, int64_t batch) {
     if (n_layers < 1 || n_layers > 8) return fail(IHG_ERR_INVALID, "%s: 1..8 layer outputs supported, got %d", what, n_layers);
-    if (layers == nullptr || rows == nullptr || dim <= 0 || ld < dim || batch < 0) return fail(IHG_ERR_INVALID, "%s: bad argument", what);
-    for (int l = 0; l < n_layers; ++l)
+    if (ld < dim || dim <= 0 || batch < 0 || layers == nullptr) return fail(IHG_ERR_INVALID, "%s: bad size", what);
+    if (layer0_rows != nullptr && (type_begin == nullptr || ld0 < dim)) return fail(IHG_ERR_INVALID, "%s: type ranges / row stride of layer 0 missing", what);
+    for (int l = layer0_rows != nullptr ? 1 : 0; l < n_layers; ++l)      // (slot 0 is not read when layer 0 is typed)
         if (layers[l] == nullptr) return fail(IHG_ERR_INVALID, "%s: null layer pointer", what);
     return IHG_OK;
 }
 
+static int hem_score_fwd(const char* what, const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                         const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const int64_t* items, const float* bias, float lambda_muq,
+                         float* scores, int64_t batch, ihg_stream_t stream) {
+    if (int rc = hem_check(what, layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
+    if (batch == 0) return IHG_OK;
+    if (rows == nullptr || items == nullptr || bias == nullptr || scores == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
+    hipLaunchKernelGGL(hem_score_fwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers, dim,
+                       rows, items, bias, lambda_muq, scores, batch, rows_upper);
+    return check_launch(what);
+}
+
+static int hem_score_bwd(const char* what, const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
+                         const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const float* dscores, const float* grad_scale_device,
+                         float grad_scale, float lambda_muq, float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream) {
+    if (int rc = hem_check(what, layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
+    if (batch == 0) return IHG_OK;
+    if (rows == nullptr || dscores == nullptr || rowgrad == nullptr || ld_rowgrad < static_cast<int64_t>(n_layers) * dim)
+        return fail(IHG_ERR_INVALID, "%s: null pointer or short row stride", what);
+    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
+    hipLaunchKernelGGL(hem_score_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers, dim,
+                       rows, dscores, grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch, grad_scale_device, rows_upper);
+    return check_launch(what);
+}
+
 int ihg_hem_score_fwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const int64_t* rows, const int64_t* items,
                       const float* bias, float lambda_muq, float* scores, int64_t batch, ihg_stream_t stream) {
-    if (int rc = hem_common_check("ihg_hem_score_fwd", layers, n_layers, ld, dim, rows, batch)) return rc;
-    if (batch == 0) return IHG_OK;
-    if (items == nullptr || bias == nullptr || scores == nullptr) return fail(IHG_ERR_INVALID, "ihg_hem_score_fwd: null pointer");
-    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, nullptr, 0, nullptr);
-    hipLaunchKernelGGL(hem_score_fwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
-                       dim, rows, items, bias, lambda_muq, scores, batch);
-    return check_launch("ihg_hem_score_fwd");
+    return hem_score_fwd("ihg_hem_score_fwd", layers, n_layers, ld, dim, nullptr, 0, nullptr, rows, nullptr, items, bias, lambda_muq, scores, batch, stream);
 }
 
 int ihg_hem_score_bwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const int64_t* rows, const float* dscores,
                       float grad_scale, float lambda_muq, float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream) {
-    if (int rc = hem_common_check("ihg_hem_score_bwd", layers, n_layers, ld, dim, rows, batch)) return rc;
-    if (batch == 0) return IHG_OK;
-    if (dscores == nullptr || rowgrad == nullptr || ld_rowgrad < static_cast<int64_t>(n_layers) * dim) return fail(IHG_ERR_INVALID, "ihg_hem_score_bwd: null pointer or short row stride");
-    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, nullptr, 0, nullptr);
-    hipLaunchKernelGGL(hem_score_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
-                       dim, rows, dscores, grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch);
-    return check_launch("ihg_hem_score_bwd");
+    return hem_score_bwd("ihg_hem_score_bwd", layers, n_layers, ld, dim, nullptr, 0, nullptr, rows, nullptr, dscores, nullptr, grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch,
+                         stream);
 }
 
 int ihg_hem_score_fwd_typed0(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
                              const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const int64_t* items, const float* bias, float lambda_muq,
                              float* scores, int64_t batch, ihg_stream_t stream) {
-    if (layer0_rows != nullptr && (type_begin == nullptr || ld0 < dim)) return fail(IHG_ERR_INVALID, "ihg_hem_score_fwd_typed0: type ranges / row stride of layer 0 missing");
-    if (n_layers < 1 || n_layers > 8 || ld < dim || dim <= 0 || batch < 0 || layers == nullptr) return fail(IHG_ERR_INVALID, "ihg_hem_score_fwd_typed0: bad size");
-    if (batch == 0) return IHG_OK;
-    if (rows == nullptr || items == nullptr || bias == nullptr || scores == nullptr) return fail(IHG_ERR_INVALID, "ihg_hem_score_fwd_typed0: null pointer");
-    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
-    hipLaunchKernelGGL(hem_score_fwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
-                       dim, rows, items, bias, lambda_muq, scores, batch, rows_upper);
-    return check_launch("ihg_hem_score_fwd_typed0");
+    return hem_score_fwd("ihg_hem_score_fwd_typed0", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, rows, rows_upper, items, bias, lambda_muq, scores, batch, stream);
 }
 
 int ihg_hem_score_bwd_typed0(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
                              const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const float* dscores, const float* grad_scale_device,
                              float grad_scale, float lambda_muq, float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream) {
-    if (layer0_rows != nullptr && (type_begin == nullptr || ld0 < dim)) return fail(IHG_ERR_INVALID, "ihg_hem_score_bwd_typed0: type ranges / row stride of layer 0 missing");
-    if (n_layers < 1 || n_layers > 8 || ld < dim || dim <= 0 || batch < 0 || layers == nullptr) return fail(IHG_ERR_INVALID, "ihg_hem_score_bwd_typed0: bad size");
-    if (batch == 0) return IHG_OK;
-    if (rows == nullptr || dscores == nullptr || rowgrad == nullptr || ld_rowgrad < static_cast<int64_t>(n_layers) * dim)
-        return fail(IHG_ERR_INVALID, "ihg_hem_score_bwd_typed0: null pointer or short row stride");
-    const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
-    hipLaunchKernelGGL(hem_score_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
-                       dim, rows, dscores, grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch, grad_scale_device, rows_upper);
-    return check_launch("ihg_hem_score_bwd_typed0");
-}
-
-static int hem_cosine_check(const char* what, const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
-                            const int64_t* type_begin, int64_t batch) {
-    if (layer0_rows != nullptr && (type_begin == nullptr || ld0 < dim)) return fail(IHG_ERR_INVALID, "%s: type ranges / row stride of layer 0 missing", what);
-    if (n_layers < 1 || n_layers > 8 || ld < dim || dim <= 0 || batch < 0 || layers == nullptr) return fail(IHG_ERR_INVALID, "%s: bad size", what);
-    for (int l = layer0_rows != nullptr ? 1 : 0; l < n_layers; ++l)
-        if (layers[l] == nullptr) return fail(IHG_ERR_INVALID, "%s: null layer pointer", what);
-    return IHG_OK;
+    return hem_score_bwd("ihg_hem_score_bwd_typed0", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, rows, rows_upper, dscores, grad_scale_device, grad_scale, lambda_muq,
+                         rowgrad, ld_rowgrad, batch, stream);
 }
 
 int ihg_hem_cosine_fwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
                        const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const int64_t* items, const float* bias, float lambda_muq,
                        float* scores, float* stats, int64_t batch, ihg_stream_t stream) {
-    if (int rc = hem_cosine_check("ihg_hem_cosine_fwd", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
+    if (int rc = hem_check("ihg_hem_cosine_fwd", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
     if (batch == 0) return IHG_OK;
     if (rows == nullptr || items == nullptr || bias == nullptr || scores == nullptr || stats == nullptr || !aligned16(stats))
         return fail(IHG_ERR_INVALID, "ihg_hem_cosine_fwd: null pointer or stats not 16-byte aligned");
     const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
-    hipLaunchKernelGGL(hem_cosine_fwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
-                       dim, rows, items, bias, lambda_muq, scores, reinterpret_cast<float4*>(stats), batch, rows_upper);
+    hipLaunchKernelGGL(hem_cosine_fwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers, dim,
+                       rows, items, bias, lambda_muq, scores, reinterpret_cast<float4*>(stats), batch, rows_upper);
     return check_launch("ihg_hem_cosine_fwd");
 }
 
 int ihg_hem_cosine_bwd(const float* const* layers, int32_t n_layers, int64_t ld, int32_t dim, const float* const* layer0_rows, int64_t ld0,
                        const int64_t* type_begin, const int64_t* rows, const int64_t* rows_upper, const float* dscores, const float* stats,
                        const float* grad_scale_device, float grad_scale, float lambda_muq, float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream) {
-    if (int rc = hem_cosine_check("ihg_hem_cosine_bwd", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
+    if (int rc = hem_check("ihg_hem_cosine_bwd", layers, n_layers, ld, dim, layer0_rows, ld0, type_begin, batch)) return rc;
     if (batch == 0) return IHG_OK;
     if (rows == nullptr || dscores == nullptr || stats == nullptr || !aligned16(stats) || rowgrad == nullptr || ld_rowgrad < static_cast<int64_t>(n_layers) * dim)
         return fail(IHG_ERR_INVALID, "ihg_hem_cosine_bwd: null pointer, stats not 16-byte aligned or short row stride");
     const LayerPtrs lp = layer_ptrs(layers, n_layers, ld, layer0_rows, ld0, type_begin);
-    hipLaunchKernelGGL(hem_cosine_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers,
-                       dim, rows, dscores, reinterpret_cast<const float4*>(stats), grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch, grad_scale_device, rows_upper);
+    hipLaunchKernelGGL(hem_cosine_bwd_kernel, dim3(grid_for_waves(batch)), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), lp, n_layers, dim,
+                       rows, dscores, reinterpret_cast<const float4*>(stats), grad_scale, lambda_muq, rowgrad, ld_rowgrad, batch, grad_scale_device, rows_upper);
     return check_launch("ihg_hem_cosine_bwd");
 }
 

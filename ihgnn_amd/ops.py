@@ -1459,24 +1459,35 @@ def interact_layer(h: Tensor, w: Tensor, bias: Optional[Tensor], layout: Inciden
 # ---------------------------------------------------------------------------------------------
 # Batch tail: HEM scores of a training batch straight from the layer outputs
 # ---------------------------------------------------------------------------------------------
-def _hem_cosine_operands(layers, tables, dim: int):
-    """``(layers, (layer0_rows, ld0, type_begin))`` of the cosine entry points: plain matrices, or layer 0 as the embedding tables in place."""
+def _tail_shape(layers, tables):
+    """``(n_layers, dim, width)`` of a batch tail over the matrices ``layers``, below them layer 0 in the embedding tables (``tables``, optional); ``width = n_layers * dim``."""
+    n_layers = len(layers) + (1 if tables is not None else 0)
+    dim = int(layers[0].shape[1]) if layers else tables.dim
+    return n_layers, dim, n_layers * dim
+
+
+def _hem_operands(layers, tables, dim: int):
+    """``(layers, (layer0_rows, ld0, type_begin))`` of the HEM entry points: plain matrices, or layer 0 as the embedding tables in place."""
     if tables is None:
         return (ctypes.c_void_p * len(layers))(*[x.data_ptr() for x in layers]), (None, 0, None)
     ptrs = (ctypes.c_void_p * (len(layers) + 1))(tables.query_rows.data_ptr(), *[x.data_ptr() for x in layers])     # (slot 0 is replaced by the typed rows)
     return ptrs, (tables.row_pointers(), dim, tables.type_begin())
 
 
-def _hem_cosine_forward(layers, tables, rows: Tensor, rows_upper: Optional[Tensor], items: Tensor, bias: Tensor, lam: float, scores: Tensor) -> Tensor:
-    """The cosine head's scores of a batch into ``scores`` (the caller names the launch to the profiler); returns the rows' ``[B, 4]`` stats (``a . m``, ``||a||^2``, ``||m||^2``, 0: include/ihgnn_hip.h) for the backward.
-    One entry point for plain matrices, the embedding tables in place (``tables``) and a layout's own numbering above layer 0 (``rows_upper``)."""
+def _hem_forward(layers, tables, rows: Tensor, rows_upper: Optional[Tensor], items: Tensor, bias: Tensor, lam: float, cosine: bool, scores: Tensor) -> Optional[Tensor]:
+    """The scores of a batch into ``scores`` (the caller names the launch to the profiler).  The cosine head returns the rows' ``[B, 4]`` stats (``a . m``, ``||a||^2``, ``||m||^2``, 0:
+    include/ihgnn_hip.h) for the backward, the dot product ``None``.  One entry point per head for plain matrices, the embedding tables in place (``tables``) and a layout's own
+    numbering above layer 0 (``rows_upper``)."""
     lib = _lib.load()
     batch = int(items.shape[0])
-    dim = int(layers[0].shape[1]) if layers else tables.dim
+    n_layers, dim, _ = _tail_shape(layers, tables)
+    ptrs, typed0 = _hem_operands(layers, tables, dim)
+    args = (ptrs, n_layers, _ld(layers[0]) if layers else dim, dim, *typed0, _ptr(rows), _ptr(rows_upper), _ptr(items), _ptr(bias), float(lam), _ptr(scores))
+    if not cosine:
+        _lib.check(lib.ihg_hem_score_fwd_typed0(*args, batch, _stream()), 'ihg_hem_score_fwd_typed0')
+        return None
     stats = torch.empty(batch, 4, dtype=torch.float32, device=bias.device)
-    ptrs, typed0 = _hem_cosine_operands(layers, tables, dim)
-    _lib.check(lib.ihg_hem_cosine_fwd(ptrs, len(ptrs), _ld(layers[0]) if layers else dim, dim, *typed0, _ptr(rows), _ptr(rows_upper), _ptr(items), _ptr(bias), float(lam),
-                                      _ptr(scores), _ptr(stats), batch, _stream()), 'ihg_hem_cosine_fwd')
+    _lib.check(lib.ihg_hem_cosine_fwd(*args, _ptr(stats), batch, _stream()), 'ihg_hem_cosine_fwd')
     return stats
 
 
@@ -1487,37 +1498,28 @@ def _hem_row_gradients(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: f
     cosine head's forward): the cosine head's row gradients, same layout."""
     lib = _lib.load()
     batch = int(items.shape[0])
-    dim = int(layers[0].shape[1]) if layers else tables.dim
-    n_layers = len(layers) + (1 if tables is not None else 0)
-    width = n_layers * dim
+    n_layers, dim, width = _tail_shape(layers, tables)
     rowgrad = torch.empty(3 * batch, width + 4, dtype=torch.float32, device=bias.device)
     if grad_scale_device is not None and (grad_scale_device.dtype != torch.float32 or grad_scale_device.numel() != 1):
         raise TypeError('grad_scale_device is a float32 device scalar')
-    if stats is not None:
-        ptrs, typed0 = _hem_cosine_operands(layers, tables, dim)
-        with profiler.kernel('hem_cosine_bwd', batch, dim):
-            _lib.check(lib.ihg_hem_cosine_bwd(ptrs, n_layers, _ld(layers[0]) if layers else dim, dim, *typed0, _ptr(rows), _ptr(rows_upper), _ptr(dscores), _ptr(stats),
-                                              _ptr(grad_scale_device), float(grad_scale), float(lam), _ptr(rowgrad), width + 4, batch, _stream()), 'ihg_hem_cosine_bwd')
-        return rowgrad
-    with profiler.kernel('hem_score_bwd', batch, dim):
-        if tables is None:
-            ptrs = (ctypes.c_void_p * n_layers)(*[x.data_ptr() for x in layers])
-            _lib.check(lib.ihg_hem_score_bwd_typed0(ptrs, n_layers, _ld(layers[0]), dim, None, 0, None, _ptr(rows), _ptr(rows_upper), _ptr(dscores), _ptr(grad_scale_device),
-                                                    float(grad_scale), float(lam), _ptr(rowgrad), width + 4, batch, _stream()), 'ihg_hem_score_bwd_typed0')
+    ptrs, typed0 = _hem_operands(layers, tables, dim)
+    args = (ptrs, n_layers, _ld(layers[0]) if layers else dim, dim, *typed0, _ptr(rows), _ptr(rows_upper), _ptr(dscores))
+    out = (_ptr(grad_scale_device), float(grad_scale), float(lam), _ptr(rowgrad), width + 4, batch, _stream())
+    with profiler.kernel('hem_score_bwd' if stats is None else 'hem_cosine_bwd', batch, dim):
+        if stats is None:
+            _lib.check(lib.ihg_hem_score_bwd_typed0(*args, *out), 'ihg_hem_score_bwd_typed0')
         else:
-            ptrs = (ctypes.c_void_p * n_layers)(tables.query_rows.data_ptr(), *[x.data_ptr() for x in layers])
-            _lib.check(lib.ihg_hem_score_bwd_typed0(ptrs, n_layers, _ld(layers[0]) if layers else dim, dim, tables.row_pointers(), dim, tables.type_begin(), _ptr(rows),
-                                                    _ptr(rows_upper), _ptr(dscores), _ptr(grad_scale_device), float(grad_scale), float(lam), _ptr(rowgrad), width + 4, batch, _stream()),
-                       'ihg_hem_score_bwd_typed0')
+            _lib.check(lib.ihg_hem_cosine_bwd(*args, _ptr(stats), *out), 'ihg_hem_cosine_bwd')
     return rowgrad
 
 
 SCATTER_CHUNK_ROWS = 32768          # rows one ihg_batch_scatter_add / ihg_batch_combine launch takes (= ihg_batch_scatter_max_rows(): its id list lives in LDS; tests/test_abi.py)
 
 
-def _scatter_rows(rowgrad: Tensor, col0: int, width: int, rows: Tensor, dense: Optional[Tensor], tail: Optional[Tensor] = None, tail_offset: int = 0):
+def _scatter_rows(rowgrad: Tensor, col0: int, width: int, rows: Tensor, dense: Optional[Tensor], tail: Optional[Tensor] = None, tail_offset: int = 0, block_stride: int = 0):
     """``dense[rows[k]] += rowgrad[k, col0 : col0 + width]`` (duplicates combined in a fixed order; deterministic).  With
-    ``tail``: the LAST of the ``width`` columns goes to ``tail[rows[k] - tail_offset]`` instead.  Batches beyond one launch's
+    ``tail``: the LAST of the ``width`` columns goes to ``tail[rows[k] - tail_offset]`` instead.  With ``block_stride``: ``dense`` is the first of several
+    matrices, ``block_stride`` floats apart, and every further ``dense.shape[1]`` columns land in the next of them.  Batches beyond one launch's
     capacity go through in row chunks, in order (same sums, associated chunk by chunk)."""
     lib = _lib.load()
     n = int(rows.shape[0])
@@ -1528,28 +1530,34 @@ def _scatter_rows(rowgrad: Tensor, col0: int, width: int, rows: Tensor, dense: O
         src = rowgrad[lo:hi, col0:]
         with profiler.kernel('batch_scatter_add', hi - lo, width):
             _lib.check(lib.ihg_batch_scatter_add(_ptr(src), int(rowgrad.stride(0)), width, _ptr(rows[lo:hi]), hi - lo, _ptr(target),
-                                                 _ld(target) if dense is not None else 1, block, 0, _ptr(tail), int(tail_offset),
+                                                 _ld(target) if dense is not None else 1, block, int(block_stride), _ptr(tail), int(tail_offset),
                                                  int(tail.shape[0]) if tail is not None else 0, _stream()), 'ihg_batch_scatter_add')
+
+
+def _combine_rows(rowgrad: Tensor, rows: Tensor, width: int) -> Optional[Tensor]:
+    """Sums the rows of ``rowgrad[:, 0 : width + 1]`` (the layers' columns and d bias) that share a destination into the first of them, in place; -> ``leader`` (int32, 1 on those
+    first occurrences), or ``None`` (nothing done) beyond one launch's capacity.  ``rows`` = users | queries | items: its thirds share no destination."""
+    lib = _lib.load()
+    n = int(rows.shape[0])
+    if lib.ihg_batch_scatter_workspace_bytes(n) < 0:
+        return None
+    leader = torch.empty(n, dtype=torch.int32, device=rows.device)
+    with profiler.kernel('batch_combine', n, width + 1):
+        _lib.check(lib.ihg_batch_combine(_ptr(rowgrad), int(rowgrad.stride(0)), width + 1, _ptr(rows), n, n // 3, _ptr(leader), _stream()), 'ihg_batch_combine')
+    return leader
 
 
 def _hem_backward(layers, rows: Tensor, items: Tensor, bias: Tensor, lam: float, dscores: Tensor, grad_scale: float, item_row_offset: int, stats: Optional[Tensor] = None):
     """Backward of the batch tail without taps: per-row gradients (one kernel), then ONE deterministic scatter that lands every
     layer's gradient in its own contiguous ``[N, d]`` matrix and d bias beside them.  -> (d bias, layer gradients)."""
-    lib = _lib.load()
-    batch, dim, n_layers = int(items.shape[0]), int(layers[0].shape[1]), len(layers)
-    width = n_layers * dim
+    n_layers, dim, width = _tail_shape(layers, None)
     n_nodes = int(layers[0].shape[0])
     rowgrad = _hem_row_gradients(layers, rows, items, bias, lam, dscores, grad_scale, stats=stats)
-    n_bias = int(bias.shape[0])
-    flat = torch.zeros(n_layers * n_nodes * dim + n_bias, dtype=torch.float32, device=bias.device)
-    dense = flat[:n_layers * n_nodes * dim].view(n_layers, n_nodes, dim)
+    flat = torch.zeros(n_layers * n_nodes * dim + int(bias.shape[0]), dtype=torch.float32, device=bias.device)
+    dense = flat[:n_layers * n_nodes * dim].view(n_layers * n_nodes, dim)
     dbias = flat[n_layers * n_nodes * dim:]
-    for lo in range(0, 3 * batch, SCATTER_CHUNK_ROWS):        # one launch lands every layer's block and the bias column; big batches in row chunks
-        hi = min(lo + SCATTER_CHUNK_ROWS, 3 * batch)
-        with profiler.kernel('batch_scatter_add', hi - lo, width + 1):
-            _lib.check(lib.ihg_batch_scatter_add(_ptr(rowgrad[lo:hi]), width + 4, width + 1, _ptr(rows[lo:hi]), hi - lo, _ptr(dense), dim, dim, n_nodes * dim,
-                                                 _ptr(dbias), int(item_row_offset), n_bias, _stream()), 'ihg_batch_scatter_add')
-    return dbias, tuple(dense[l] for l in range(n_layers))
+    _scatter_rows(rowgrad, 0, width + 1, rows, dense, dbias, item_row_offset, block_stride=n_nodes * dim)      # one launch lands every layer's block and the bias column
+    return dbias, tuple(dense[l * n_nodes:(l + 1) * n_nodes] for l in range(n_layers))
 
 
 class TailGradients:
@@ -1682,19 +1690,11 @@ def _same_layout(layers):
 class _HemScore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rows: Tensor, items: Tensor, bias: Tensor, lam: float, item_row_offset: int, cosine: bool, *layers: Tensor) -> Tensor:
-        lib = _lib.load()
         layers = _same_layout(layers)
         batch, dim = int(items.shape[0]), int(layers[0].shape[1])
         scores = torch.empty(batch, dtype=torch.float32, device=bias.device)
-        stats = None
-        if cosine:
-            with profiler.kernel('hem_cosine_fwd', batch, dim):
-                stats = _hem_cosine_forward(layers, None, rows, None, items, bias, lam, scores)
-        else:
-            ptrs = (ctypes.c_void_p * len(layers))(*[x.data_ptr() for x in layers])
-            with profiler.kernel('hem_score_fwd', batch, dim):
-                _lib.check(lib.ihg_hem_score_fwd(ptrs, len(layers), _ld(layers[0]), dim, _ptr(rows), _ptr(items), _ptr(bias), float(lam), _ptr(scores),
-                                                 batch, _stream()), 'ihg_hem_score_fwd')
+        with profiler.kernel('hem_cosine_fwd' if cosine else 'hem_score_fwd', batch, dim):
+            stats = _hem_forward(layers, None, rows, None, items, bias, lam, cosine, scores)
         ctx.save_for_backward(rows, items, bias, *layers)
         ctx.lam, ctx.offset, ctx.stats = float(lam), int(item_row_offset), stats
         return scores
@@ -1715,30 +1715,16 @@ class _HemBceLoss(torch.autograd.Function):
     def forward(ctx, rows: Tensor, items: Tensor, labels: Tensor, bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, cosine: bool,
                 *layers: Tensor) -> Tensor:
         # tables (a resolved NodeTables): layer 0 is the embedding tables in place; layers[0] is then its token (the autograd edge), not a matrix
+        # rows_upper (a layout without the isolated nodes): layer 0 is in the public numbering (rows), the layers above are in the layout's (rows_upper; -1: zero row)
         lib = _lib.load()
         real = _same_layout(layers[1:] if tables is not None else layers)
-        batch, dim = int(items.shape[0]), int(real[0].shape[1]) if real else tables.dim
+        batch, dim = int(items.shape[0]), _tail_shape(real, tables)[1]
         scores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         dscores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         loss = torch.empty((), dtype=torch.float32, device=bias.device)
         labels = labels.to(torch.float32).contiguous()
-        stats = None
         with profiler.kernel('hem_cosine_fwd' if cosine else 'hem_score_fwd', batch, dim):
-            if cosine:
-                stats = _hem_cosine_forward(real, tables, rows, rows_upper, items, bias, lam, scores)     # (one entry point for the three forms of the layers below)
-            elif tables is None and rows_upper is None:
-                ptrs = (ctypes.c_void_p * len(real))(*[x.data_ptr() for x in real])
-                _lib.check(lib.ihg_hem_score_fwd(ptrs, len(real), _ld(real[0]), dim, _ptr(rows), _ptr(items), _ptr(bias), float(lam), _ptr(scores),
-                                                 batch, _stream()), 'ihg_hem_score_fwd')
-            elif tables is None:
-                # a layout without the isolated nodes: layer 0 is a matrix in the public numbering (rows), the layers above are in the layout's (rows_upper; -1: zero row)
-                ptrs = (ctypes.c_void_p * len(real))(*[x.data_ptr() for x in real])
-                _lib.check(lib.ihg_hem_score_fwd_typed0(ptrs, len(real), _ld(real[0]), dim, None, 0, None, _ptr(rows), _ptr(rows_upper), _ptr(items), _ptr(bias), float(lam),
-                                                        _ptr(scores), batch, _stream()), 'ihg_hem_score_fwd_typed0')
-            else:
-                ptrs = (ctypes.c_void_p * (len(real) + 1))(tables.query_rows.data_ptr(), *[x.data_ptr() for x in real])     # (slot 0 is replaced by the typed rows)
-                _lib.check(lib.ihg_hem_score_fwd_typed0(ptrs, len(real) + 1, _ld(real[0]) if real else dim, dim, tables.row_pointers(), dim, tables.type_begin(),
-                                                        _ptr(rows), _ptr(rows_upper), _ptr(items), _ptr(bias), float(lam), _ptr(scores), batch, _stream()), 'ihg_hem_score_fwd_typed0')
+            stats = _hem_forward(real, tables, rows, rows_upper, items, bias, lam, cosine, scores)
             _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), batch, _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
         ctx.save_for_backward(rows, items, bias, dscores, *real)
         ctx.rows_upper, ctx.stats = rows_upper, stats
@@ -1757,7 +1743,7 @@ class _HemBceLoss(torch.autograd.Function):
             return (None, None, None, dbias, None, None, None, None, None, None) + grads
         holder = ctx.holder
         rowgrad = _hem_row_gradients(layers, rows, items, bias, ctx.lam, dscores, holder.grad_scale, tables, grad_loss.contiguous(), ctx.rows_upper, ctx.stats)     # d loss stays on the device: no host read, no multiply launch
-        lib = _lib.load()
+        width = _tail_shape(layers, tables)[2]
         if holder.exchange is not None:
             # every rank's propagation is the same function of the same parameters and its backward is linear in the cotangent of the layer outputs, which is non-zero on
             # the batch rows only: the ranks exchange THOSE rows (3B x (D + 1) floats each) and every rank runs the one propagation backward on the union - the averaged
@@ -1765,18 +1751,11 @@ class _HemBceLoss(torch.autograd.Function):
             # A rank's own duplicates are summed BEFORE the exchange (a batch repeats every positive's user and query with its ten negatives: ~ 1,300 of 3,300 rows are
             # first occurrences) and marked in a spare column of the row gradients, which travels with them: the union's combine then skips the other rows (and the
             # zero rows that pad a shorter batch) - its duplicate search is quadratic in the rows that take part
-            n_own = int(rows.shape[0])
-            width_own = (len(layers) + (1 if tables is not None else 0)) * (int(layers[0].shape[1]) if layers else tables.dim)
-            if lib.ihg_batch_scatter_workspace_bytes(n_own) >= 0:
-                own = torch.empty(n_own, dtype=torch.int32, device=rows.device)
-                with profiler.kernel('batch_combine', n_own, width_own + 1):
-                    _lib.check(lib.ihg_batch_combine(_ptr(rowgrad), int(rowgrad.stride(0)), width_own + 1, _ptr(rows), n_own, n_own // 3, _ptr(own), _stream()), 'ihg_batch_combine')
-                rowgrad[:, width_own + 1] = own.to(torch.float32)
-            else:
-                rowgrad[:, width_own + 1] = 1.0
+            own = _combine_rows(rowgrad, rows, width)
+            rowgrad[:, width + 1] = own.to(torch.float32) if own is not None else 1.0
             rows, rowgrad = holder.exchange(rows, rowgrad)
-            rows = torch.where(rowgrad[:, width_own + 1] > 0, rows, torch.full_like(rows, -1))
-        holder.rows, holder.rowgrad, holder.leader = rows, rowgrad, None
+            rows = torch.where(rowgrad[:, width + 1] > 0, rows, torch.full_like(rows, -1))
+        holder.rows, holder.rowgrad = rows, rowgrad
         # (the union's rows after an exchange; this batch's otherwise - through the layout's map where it numbers its nodes without the isolated ones)
         if holder.row_map is None:
             holder.rows_upper = None
@@ -1785,16 +1764,9 @@ class _HemBceLoss(torch.autograd.Function):
         else:
             mapped = holder.row_map[rows.clamp_min(0)]
             holder.rows_upper = torch.where(rows < 0, torch.full_like(mapped, -1), mapped)
-        lib = _lib.load()
-        n_layers = len(layers) + (1 if tables is not None else 0)
-        n, width = int(rows.shape[0]), n_layers * (int(layers[0].shape[1]) if layers else tables.dim)
-        if lib.ihg_batch_scatter_workspace_bytes(n) >= 0:    # one pass sums duplicate destinations; the taps then add plain rows
-            holder.leader = torch.empty(n, dtype=torch.int32, device=rows.device)
-            with profiler.kernel('batch_combine', n, width + 1):
-                _lib.check(lib.ihg_batch_combine(_ptr(rowgrad), int(rowgrad.stride(0)), width + 1, _ptr(rows), n, n // 3, _ptr(holder.leader), _stream()),
-                           'ihg_batch_combine')
+        holder.leader = _combine_rows(rowgrad, rows, width)      # one pass sums duplicate destinations; the taps then add plain rows (None: beyond one launch - they scatter)
         dbias = torch.empty_like(bias)
-        _lib.check(lib.ihg_zero_floats(_ptr(dbias), dbias.numel(), _stream()), 'ihg_zero_floats')
+        _lib.check(_lib.load().ihg_zero_floats(_ptr(dbias), dbias.numel(), _stream()), 'ihg_zero_floats')
         holder.add_into(None, width, 1, dbias, ctx.offset)
         placeholders = tuple(_zero_like_expanded(x.shape, x.device) for x in layers)
         if tables is not None:

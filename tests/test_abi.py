@@ -115,6 +115,20 @@ def test_update_tail_bad_arguments_return_invalid_and_launch_nothing():
     assert lib.ihg_hem_score_bwd_typed0(layers9, 2, 4, 4, None, 0, None, ws, None, ws, None, 1.0, 0.5, ws, 7, 5, None) == _lib.ERR_INVALID
     assert lib.ihg_hem_score_fwd_typed0(layers9, 2, 4, 4, layers9, 4, None, ws, None, ws, ws, 0.5, ws, 5, None) == _lib.ERR_INVALID   # typed layer 0 without its type ranges
     assert lib.ihg_hem_score_fwd(layers9, 8, 4, 4, ws, ws, ws, 0.5, ws, 0, None) == _lib.OK                                 # an empty batch launches nothing
+    # every layer pointer that is read must be there: all of them, or all but slot 0 when layer 0 is typed (its three tables stand in for it)
+    dot_fwd = lambda layers, l0, ld0, tb, batch: lib.ihg_hem_score_fwd_typed0(layers, 2, 4, 4, l0, ld0, tb, ws, None, ws, ws, 0.5, ws, batch, None)
+    dot_bwd = lambda layers, l0, ld0, tb, batch: lib.ihg_hem_score_bwd_typed0(layers, 2, 4, 4, l0, ld0, tb, ws, None, ws, None, 1.0, 0.5, ws, 12, batch, None)
+    cos_fwd = lambda layers, l0, ld0, tb, batch: lib.ihg_hem_cosine_fwd(layers, 2, 4, 4, l0, ld0, tb, ws, None, ws, ws, 0.5, ws, ws, batch, None)
+    cos_bwd = lambda layers, l0, ld0, tb, batch: lib.ihg_hem_cosine_bwd(layers, 2, 4, 4, l0, ld0, tb, ws, None, ws, ws, None, 1.0, 0.5, ws, 12, batch, None)
+    holes = (ctypes.c_void_p * 2)(some, None)
+    first_null = (ctypes.c_void_p * 2)(None, some)
+    type_begin = (ctypes.c_int64 * 4)(0, 1, 2, 3)
+    for call in (lambda: lib.ihg_hem_score_fwd(holes, 2, 4, 4, ws, ws, ws, 0.5, ws, 5, None), lambda: lib.ihg_hem_score_bwd(holes, 2, 4, 4, ws, ws, 1.0, 0.5, ws, 12, 5, None),
+                 lambda: dot_fwd(holes, None, 0, None, 5), lambda: dot_bwd(holes, None, 0, None, 5)):
+        assert call() == _lib.ERR_INVALID and 'null layer' in _lib.last_error()
+    for entry in (dot_fwd, dot_bwd, cos_fwd, cos_bwd):
+        assert entry(first_null, layers9, 4, type_begin, 0) == _lib.OK
+        assert entry(first_null, None, 0, None, 0) == _lib.ERR_INVALID and 'null layer' in _lib.last_error()
 
 
 def test_missing_library_is_a_hard_error(monkeypatch):

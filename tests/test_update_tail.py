@@ -473,6 +473,34 @@ def test_hem_score_kernels_match_float64(n_layers, dim):
     torch.cuda.synchronize()
 
 
+def test_hem_score_plain_entry_points_are_the_typed0_ones_bitwise():
+    """``ihg_hem_score_fwd / _bwd`` forward into the body of the ``_typed0`` pair with no typed layer 0, no ``rows_upper`` and no device scalar: the same kernel with the
+    same arguments, so scores and row gradients are ``torch.equal`` - 2 layers of 100 columns (two passes over the lanes, the second partial), 5 rows (a partly filled
+    second workgroup), 12 nodes; the row gradients in sentinel-filled buffers of width 2 x 100 + 4, where a write behind the bias column shows."""
+    from ihgnn_amd import _lib, ops
+    lib = _lib.load()
+    n_layers, dim, batch, n_nodes = 2, 100, 5, 12
+    width = n_layers * dim
+    gen = torch.Generator().manual_seed(577)
+    layers = [torch.randn(n_nodes, dim, generator=gen).to(dev()) for _ in range(n_layers)]
+    bias = torch.randn(4, generator=gen).to(dev())
+    items = torch.randint(0, 4, (batch,), generator=gen)
+    rows = torch.cat([torch.randint(0, 4, (batch,), generator=gen), 4 + torch.randint(0, 4, (batch,), generator=gen), 8 + items]).to(dev())
+    items, dscores = items.to(dev()), torch.randn(batch, generator=gen).to(dev())
+    ptrs = (ctypes.c_void_p * n_layers)(*[x.data_ptr() for x in layers])
+    scores = [torch.full((batch,), SENTINEL, dtype=torch.float32, device=dev()) for _ in range(2)]
+    rowgrad = [torch.full((3 * batch, width + 4), SENTINEL, dtype=torch.float32, device=dev()) for _ in range(2)]
+    _lib.check(lib.ihg_hem_score_fwd(ptrs, n_layers, dim, dim, ops._ptr(rows), ops._ptr(items), ops._ptr(bias), 0.3, ops._ptr(scores[0]), batch, ops._stream()), 'ihg_hem_score_fwd')
+    _lib.check(lib.ihg_hem_score_fwd_typed0(ptrs, n_layers, dim, dim, None, 0, None, ops._ptr(rows), None, ops._ptr(items), ops._ptr(bias), 0.3, ops._ptr(scores[1]), batch,
+                                            ops._stream()), 'ihg_hem_score_fwd_typed0')
+    _lib.check(lib.ihg_hem_score_bwd(ptrs, n_layers, dim, dim, ops._ptr(rows), ops._ptr(dscores), 0.75, 0.3, ops._ptr(rowgrad[0]), width + 4, batch, ops._stream()),
+               'ihg_hem_score_bwd')
+    _lib.check(lib.ihg_hem_score_bwd_typed0(ptrs, n_layers, dim, dim, None, 0, None, ops._ptr(rows), None, ops._ptr(dscores), None, 0.75, 0.3, ops._ptr(rowgrad[1]), width + 4,
+                                            batch, ops._stream()), 'ihg_hem_score_bwd_typed0')
+    assert bool((scores[0] != SENTINEL).all()) and torch.equal(scores[0], scores[1])
+    assert bool((rowgrad[0][:, :width + 1] != SENTINEL).all()) and bool((rowgrad[0][:, width + 1:] == SENTINEL).all()) and torch.equal(rowgrad[0], rowgrad[1])
+
+
 def test_hem_score_refuses_nine_layers():
     from ihgnn_amd import _lib, ops
     lib = _lib.load()
