@@ -508,7 +508,7 @@ int launch_row_gemm(int dim, const float* in, int64_t ld_in, const float* w, int
     if (out_ok && split_row_gemm_ok(dim, nullptr, ld_out, bias, bias_type_stride)) {   // the bf16 planes sit behind the slabs (see ihg_node_linear_workspace_bytes)
         void* planes = pk + 3LL * dim * dim + 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
         launch_row_gemm_split(dim, in_typed != nullptr ? *in_typed : typed_rows(in), ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin,
-                              out_typed != nullptr ? *out_typed : typed_rows_out(out), ld_out, planes, s, accumulate);
+                              out_typed != nullptr ? *out_typed : typed_rows_out(out), ld_out, planes, s, accumulate, 0);
         return IHG_OK;
     }
     if (accumulate) return fail(IHG_ERR_INVALID, "node-level linear map accumulating into its output: needs the bf16-split kernels (dim 128 / 256, aligned rows)");

@@ -1,6 +1,9 @@
 // interact.hip - the interactive (order 2 / 3) node -> hyperedge step and its backward on the matrix cores (exact fp32 MFMA),
 // plus the one-thread-per-output kernels that take every other shape.
+#include <initializer_list>
+
 #include "common.hpp"
+#include "interact_args.hpp"
 #include "narrow.hpp"
 #include "split.hpp"
 
@@ -1879,8 +1882,16 @@ __global__ __launch_bounds__(kBlockThreads) void slab_reduce_kernel(const float*
     }
 }
 
+// ================================================================================================
+// Host side.  An entry point checks its arguments (edge_form_check / node_form_check: one order of tests and one set of messages per family), carves the
+// workspace and fills ONE record - FwdCall, or BwdCall: the operands, where the hyperedges' cotangents come from (EdgeCotangent: fp32 rows, fp16 planes, or a
+// node-level cotangent the kernel gathers, with the place to leave the rows it forms), the user-reduced outputs where that form is asked for (UserReduced), dw
+// where the weight gradients are wanted.  The backward is two steps: member_gradients picks one kernel family by shape and returns the [E, d] rows that exist
+// in memory afterwards; weight_gradients reads those.  dispatch_nblk (interact_args.hpp) turns the record's order into the kernels' NBLK.
+// ================================================================================================
 constexpr int kPipeGridSlabs = 256;
-inline int64_t packed_weight_floats(int dim, int order) { return static_cast<int64_t>(order == 3 ? 4 : 3) * dim * dim; }
+inline int product_blocks(int order) { return order == 3 ? 4 : 3; }
+inline int64_t packed_weight_floats(int dim, int order) { return static_cast<int64_t>(product_blocks(order)) * dim * dim; }
 inline int weight_slabs(int dim) {
     if (dim == 128) return kPipeGridSlabs;                  // interact_bwd_weight_strip_kernel: one full slab per workgroup
     const int subs = dim >= 64 ? (dim / 64) * (dim / 64) : 1;
@@ -1923,6 +1934,7 @@ int resident_grid(Kernel kernel) {
     return per_cu * cus;
 }
 
+inline int grid_for_tiles(int64_t n_edges, int tile, int limit) { return static_cast<int>(std::min<int64_t>((n_edges + tile - 1) / tile, limit)); }
 
 // the strip kernels (D = 128) move rows as 16-byte vectors and form addresses as 32 x 32-bit products
 inline bool strip_fwd_ok(int dim, const float* p, int64_t ld_p, const float* out, int64_t ld_out, int64_t ld_h) {
@@ -1930,134 +1942,208 @@ inline bool strip_fwd_ok(int dim, const float* p, int64_t ld_p, const float* out
 }
 inline bool strip_bwd_ok(int dim, const float* g, int64_t ld_h) { return (dim == 128 || dim == 256) && aligned16(g) && ld_h < (int64_t{1} << 30); }
 
-template <int NBLK>
-void launch_interact_fwd_mfma(int dim, const float* h, int64_t ld_h, const float* p, int64_t ld_p, const int32_t* i3, const float* wp,
-                              float* out, int64_t ld_out, int64_t n_edges, hipStream_t s) {
-    if (strip_fwd_ok(dim, p, ld_p, out, ld_out, ld_h)) {                    // wp is strip-packed (the caller asked strip_fwd_ok too)
-        if (dim == 256) {
-            const int grid = static_cast<int>(std::min<int64_t>((n_edges + kStrip256TE - 1) / kStrip256TE, kStrip256Grid));
-            hipLaunchKernelGGL((interact_fwd_strip256_kernel<NBLK>), dim3(grid, 4), dim3(kWsThreads), 0, s, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges);
-            return;
-        }
-        const int grid = static_cast<int>(std::min<int64_t>((n_edges + kStripTE - 1) / kStripTE, kPipeGrid));
-        hipLaunchKernelGGL((interact_fwd_strip_kernel<128, NBLK>), dim3(grid), dim3(kWsThreads), 0, s, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges);
-        return;
-    }
-#define IHG_FWD(D)                                                                                                          \
-    {                                                                                                                       \
-        const int64_t tiles = (n_edges + TileShape<D>::TE - 1) / TileShape<D>::TE;                                          \
-        static const int resident = resident_grid(interact_fwd_mfma_kernel<D, NBLK>);                                       \
-        const int grid = static_cast<int>(std::min<int64_t>(tiles, resident));                                              \
-        hipLaunchKernelGGL((interact_fwd_mfma_kernel<D, NBLK>), dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges); \
-    }
-#define IHG_FWD_PIPE(D)                                                                                                     \
-    {                                                                                                                       \
-        const int64_t tiles = (n_edges + TileShape<D>::TE - 1) / TileShape<D>::TE;                                          \
-        const int grid = static_cast<int>(std::min<int64_t>(tiles, kPipeGrid));                                             \
-        hipLaunchKernelGGL((interact_fwd_ws_kernel<D, NBLK>), dim3(grid), dim3(kWsThreads), 0, s, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges); \
-    }
-    // the wave-specialised form moves first-order rows and results as 16-byte vectors and forms addresses as 32x32-bit products
-    const bool vector_io = aligned16(p) && aligned16(out) && ld_p % 4 == 0 && ld_out % 4 == 0 && ld_h < (int64_t{1} << 30) && ld_p < (int64_t{1} << 30);
-    switch (dim) {
-        case 32:
-            if (vector_io) IHG_FWD_PIPE(32) else IHG_FWD(32)
-            break;
-        case 64:
-            if (vector_io) IHG_FWD_PIPE(64) else IHG_FWD(64)
-            break;
-        case 128: IHG_FWD(128) break;
-        default: IHG_FWD(256) break;
-    }
-#undef IHG_FWD
-#undef IHG_FWD_PIPE
+// the fp32 fragment image of w's product blocks, in the strip kernels' order or the other tiled kernels'; one image per direction (the other pointer is nullptr)
+void launch_pack_weights(bool strip, const float* w, int64_t ld_w, int dim, int order, float* wp_fwd, float* wq_bwd, hipStream_t s) {
+    const int nblk = product_blocks(order);
+    const int pack_items = (dim / 32) * nblk * (dim / 8) * kWave;
+    const auto kernel = strip ? pack_weights_strip_kernel : pack_weights_kernel;
+    hipLaunchKernelGGL(kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
+                       wp_fwd, wq_bwd);
 }
 
+// ---- forward ----
+struct FwdCall {
+    int dim, order;
+    const float* h; int64_t ld_h; const float* p; int64_t ld_p; const int32_t* i3;
+    const float* wp;                 // packed by launch_pack_weights: strip order where strip_fwd_ok
+    float* out; int64_t ld_out; int64_t n_edges; hipStream_t s;
+};
+
+template <typename Kernel>           // every tiled forward kernel takes the same arguments
+void launch_fwd(Kernel kernel, dim3 grid, int threads, const FwdCall& c) {
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, c.s, c.h, c.ld_h, c.p, c.ld_p, c.i3, c.wp, c.out, c.ld_out, c.n_edges);
+}
+template <int D, int NBLK>
+void launch_fwd_mfma(const FwdCall& c) {
+    static const int resident = resident_grid(interact_fwd_mfma_kernel<D, NBLK>);
+    launch_fwd(interact_fwd_mfma_kernel<D, NBLK>, grid_for_tiles(c.n_edges, TileShape<D>::TE, resident), kBlockThreads, c);
+}
+template <int D, int NBLK>
+void launch_fwd_ws(const FwdCall& c) { launch_fwd(interact_fwd_ws_kernel<D, NBLK>, grid_for_tiles(c.n_edges, TileShape<D>::TE, kPipeGrid), kWsThreads, c); }
+
+struct ForwardTiled {
+    template <int NBLK>
+    static void run(const FwdCall& c) {
+        if (strip_fwd_ok(c.dim, c.p, c.ld_p, c.out, c.ld_out, c.ld_h)) {
+            if (c.dim == 256) return launch_fwd(interact_fwd_strip256_kernel<NBLK>, dim3(grid_for_tiles(c.n_edges, kStrip256TE, kStrip256Grid), 4), kWsThreads, c);
+            return launch_fwd(interact_fwd_strip_kernel<128, NBLK>, grid_for_tiles(c.n_edges, kStripTE, kPipeGrid), kWsThreads, c);
+        }
+        // the wave-specialised form moves first-order rows and results as 16-byte vectors and forms addresses as 32x32-bit products
+        const bool vector_io = aligned16(c.p) && aligned16(c.out) && c.ld_p % 4 == 0 && c.ld_out % 4 == 0 && c.ld_h < (int64_t{1} << 30) && c.ld_p < (int64_t{1} << 30);
+        switch (c.dim) {
+            case 32: vector_io ? launch_fwd_ws<32, NBLK>(c) : launch_fwd_mfma<32, NBLK>(c); break;
+            case 64: vector_io ? launch_fwd_ws<64, NBLK>(c) : launch_fwd_mfma<64, NBLK>(c); break;
+            case 128: launch_fwd_mfma<128, NBLK>(c); break;
+            default: launch_fwd_mfma<256, NBLK>(c); break;
+        }
+    }
+};
+
+// ---- backward ----
+struct BwdCall {
+    int dim, order;
+    const float* h; int64_t ld_h; const int32_t* i3; const float* w; int64_t ld_w;
+    EdgeCotangent cot;
+    float* g;                        // member buffer: [E, 3, d], or [E, 2, d] with ur
+    const UserReduced* ur;           // nullptr: the [E, 3, d] form
+    float* dw; int64_t ld_dw;        // nullptr: member gradients only (the caller takes d w from the node-level kernel)
+    BwdWorkspace ws;                 // ws.wq packed by launch_pack_weights where an fp32 kernel may run; ws.planes == nullptr: no split / narrow kernel at this width
+    int64_t n_edges; hipStream_t s;
+};
+
+template <typename Kernel>           // the fp32 member-gradient kernels of the [E, 3, d] form take the same arguments (the cotangents are fp32 rows)
+void launch_members(Kernel kernel, dim3 grid, int threads, const BwdCall& c) {
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, c.s, c.h, c.ld_h, c.i3, c.ws.wq, c.cot.src, c.cot.ld, c.g, c.n_edges);
+}
+template <int D, int NBLK>
+void launch_members_mfma(const BwdCall& c) {
+    static const int resident = resident_grid(interact_bwd_members_mfma_kernel<D, NBLK>);
+    launch_members(interact_bwd_members_mfma_kernel<D, NBLK>, grid_for_tiles(c.n_edges, D == 32 ? 128 : 64, resident), kBlockThreads, c);
+}
+template <int D, int NBLK>
+void launch_members_ws(const BwdCall& c) { launch_members(interact_bwd_members_ws_kernel<D, NBLK>, grid_for_tiles(c.n_edges, D == 32 ? 128 : 64, kPipeGrid), kWsThreads, c); }
+
+// The member gradients into c.g (and c.ur->dh): one kernel family by shape - narrow, split, strip256, strip user-reduced, strip, ws, mfma, wsbig.  Only the narrow and
+// split kernels read anything but fp32 rows (the entry points that pass planes or a node-level cotangent have checked that one of them takes the call).  Returns the
+// [E, d] rows the weight step reads.
 template <int NBLK>
-void launch_interact_bwd_mfma(int dim, const float* h, int64_t ld_h, const int32_t* i3, const float* wq, const float* dout, int64_t ld_dout,
-                              float* g, float* slabs, float* dw, int64_t ld_dw, int64_t n_edges, hipStream_t s,
-                              float* dh_user = nullptr, int64_t ld_dh = 0, float* bnd_val = nullptr, int32_t* bnd_user = nullptr,
-                              const float* w_raw = nullptr, int64_t ld_w = 0, void* planes = nullptr,
-                              const float* dy_scale = nullptr, float* dout_store = nullptr, int64_t ld_store = 0) {
-    // dout_store != nullptr (the caller has checked the split kernels take the shape): `dout` is the node-level cotangent, the member-gradient
-    // kernel forms the hyperedges' cotangents from it and leaves them in dout_store for everything after it
-#define IHG_MEM(D)                                                                                                          \
-    {                                                                                                                       \
-        constexpr int TE = D == 32 ? 128 : 64;                                                                              \
-        static const int resident = resident_grid(interact_bwd_members_mfma_kernel<D, NBLK>);                               \
-        const int grid = static_cast<int>(std::min<int64_t>((n_edges + TE - 1) / TE, resident));                            \
-        hipLaunchKernelGGL((interact_bwd_members_mfma_kernel<D, NBLK>), dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, i3, wq, dout, ld_dout, g, n_edges); \
-    }
-#define IHG_MEM_PIPE(D)                                                                                                     \
-    {                                                                                                                       \
-        constexpr int TE = D == 32 ? 128 : 64;                                                                              \
-        const int grid = static_cast<int>(std::min<int64_t>((n_edges + TE - 1) / TE, kPipeGrid));                           \
-        hipLaunchKernelGGL((interact_bwd_members_ws_kernel<D, NBLK>), dim3(grid), dim3(kWsThreads), 0, s, h, ld_h, i3, wq, dout, ld_dout, g, n_edges); \
-    }
-    const bool vector_io = aligned16(g) && ld_h < (int64_t{1} << 30);     // the pipelined form stores g as 16-byte vectors
-    if (dim == kNarrowDim && dh_user != nullptr && planes != nullptr && narrow_members_ok(dim, NBLK == 4 ? 3 : 2, g, ld_h, ld_dout, dout)) {
-        // d = 32, user-reduced (g is [E, 2, d]): one wave per 16-hyperedge tile on fp32 MFMA, gathering the node-level cotangent when dy_scale / dout_store say so
-        const bool gather = dout_store != nullptr || ld_store < 0;
+EdgeRows member_gradients(const BwdCall& c) {
+    const int dim = c.dim;
+    const int64_t n_edges = c.n_edges;
+    const float* wq = c.ws.wq;
+    const float* dout = c.cot.src;
+    const int64_t ld_dout = c.cot.ld;
+    const bool vector_io = aligned16(c.g) && c.ld_h < (int64_t{1} << 30);     // the pipelined form stores g as 16-byte vectors
+    if (dim == kNarrowDim && c.ur != nullptr && c.ws.planes != nullptr && narrow_members_ok(dim, c.order, c.g, c.ld_h, ld_dout, dout)) {
+        // d = 32, user-reduced (g is [E, 2, d]): one wave per 16-hyperedge tile on fp32 MFMA
+        launch_members_narrow(c.order, c.h, c.ld_h, c.i3, c.w, c.ld_w, static_cast<float*>(c.ws.planes), c.cot, c.g, n_edges, *c.ur, c.s);
+    } else if (c.ws.planes != nullptr && split_members_ok(dim, c.order, c.g, c.ld_h, ld_dout, dout)) {   // bf16-split contraction
         int entries = 0;
-        launch_members_narrow(NBLK == 4 ? 3 : 2, gather ? 1 : 0, h, ld_h, i3, w_raw, ld_w, static_cast<float*>(planes), dout, ld_dout, dy_scale, ld_store > 0 ? dout_store : nullptr,
-                              ld_store, g, n_edges, dh_user, ld_dh, bnd_val, bnd_user, &entries, s);
-        if (gather && ld_store > 0) {
-            dout = dout_store;
-            ld_dout = ld_store;
+        launch_members_split(dim, c.order, c.h, c.ld_h, c.i3, c.w, c.ld_w, c.ws.planes, c.cot, c.g, n_edges, c.ur, &entries, c.s);
+        if (c.ur != nullptr)
+            hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, c.s, c.ur->bnd_val, c.ur->bnd_user, entries, dim, c.ur->dh, c.ur->ld_dh);
+    } else if (strip_bwd_ok(dim, c.g, c.ld_h) && dim == 256) {             // wq is strip-packed
+        launch_members(interact_bwd_members_strip256_kernel<NBLK>, dim3(grid_for_tiles(n_edges, kStrip256TE, kStrip256Grid), 4), kWsThreads, c);
+    } else if (strip_bwd_ok(dim, c.g, c.ld_h) && c.ur != nullptr) {        // user-reduced form: g is [E, 2, d]
+        const int grid = grid_for_tiles(n_edges, kStripTE, kPipeGrid);
+        hipLaunchKernelGGL((interact_bwd_members_strip_kernel<128, NBLK, true>), dim3(grid), dim3(kWsThreads), 0, c.s, c.h, c.ld_h, c.i3, wq, dout, ld_dout, c.g, n_edges, c.ur->dh,
+                           c.ur->ld_dh, c.ur->bnd_val, c.ur->bnd_user);
+        hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(2 * grid), dim3(128), 0, c.s, c.ur->bnd_val, c.ur->bnd_user, 2 * grid, dim, c.ur->dh, c.ur->ld_dh);
+    } else if (strip_bwd_ok(dim, c.g, c.ld_h)) {
+        hipLaunchKernelGGL((interact_bwd_members_strip_kernel<128, NBLK, false>), dim3(grid_for_tiles(n_edges, kStripTE, kPipeGrid)), dim3(kWsThreads), 0, c.s, c.h, c.ld_h, c.i3, wq,
+                           dout, ld_dout, c.g, n_edges, static_cast<float*>(nullptr), int64_t{0}, static_cast<float*>(nullptr), static_cast<int32_t*>(nullptr));
+    } else {
+        switch (dim) {
+            case 32: vector_io ? launch_members_ws<32, NBLK>(c) : launch_members_mfma<32, NBLK>(c); break;
+            case 64: vector_io ? launch_members_ws<64, NBLK>(c) : launch_members_mfma<64, NBLK>(c); break;
+            case 128: launch_members(interact_bwd_members_wsbig_kernel<128, NBLK>, grid_for_tiles(n_edges, 64, kPipeGrid), kWsThreads, c); break;
+            default: launch_members_mfma<256, NBLK>(c); break;
         }
-    } else if (planes != nullptr && split_members_ok(dim, NBLK == 4 ? 3 : 2, g, ld_h, ld_dout, dout, dh_user != nullptr)) {   // bf16-split contraction
-        int entries = 0;
-        launch_members_split(dim, NBLK == 4 ? 3 : 2, h, ld_h, i3, w_raw, ld_w, planes, dout, ld_dout, g, n_edges, dh_user, ld_dh, bnd_val, bnd_user, &entries, s,
-                             dy_scale, dout_store, ld_store);
-        if (dh_user != nullptr) hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, s, bnd_val, bnd_user, entries, dim, dh_user, ld_dh);
-        if (dout_store != nullptr) {
-            dout = dout_store;
-            ld_dout = ld_store;
-        }
-    } else if (strip_bwd_ok(dim, g, ld_h) && dim == 256) {               // wq is strip-packed
-        const int grid = static_cast<int>(std::min<int64_t>((n_edges + kStrip256TE - 1) / kStrip256TE, kStrip256Grid));
-        hipLaunchKernelGGL((interact_bwd_members_strip256_kernel<NBLK>), dim3(grid, 4), dim3(kWsThreads), 0, s, h, ld_h, i3, wq, dout, ld_dout, g, n_edges);
-    } else if (strip_bwd_ok(dim, g, ld_h) && dh_user != nullptr) {       // user-reduced form: g is [E, 2, d]
-        const int grid = static_cast<int>(std::min<int64_t>((n_edges + kStripTE - 1) / kStripTE, kPipeGrid));
-        hipLaunchKernelGGL((interact_bwd_members_strip_kernel<128, NBLK, true>), dim3(grid), dim3(kWsThreads), 0, s, h, ld_h, i3, wq, dout, ld_dout, g, n_edges,
-                           dh_user, ld_dh, bnd_val, bnd_user);
-        hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(2 * grid), dim3(128), 0, s, bnd_val, bnd_user, 2 * grid, dim, dh_user, ld_dh);
-    } else if (strip_bwd_ok(dim, g, ld_h)) {
-        const int grid = static_cast<int>(std::min<int64_t>((n_edges + kStripTE - 1) / kStripTE, kPipeGrid));
-        hipLaunchKernelGGL((interact_bwd_members_strip_kernel<128, NBLK, false>), dim3(grid), dim3(kWsThreads), 0, s, h, ld_h, i3, wq, dout, ld_dout, g, n_edges,
-                           static_cast<float*>(nullptr), int64_t{0}, static_cast<float*>(nullptr), static_cast<int32_t*>(nullptr));
-    } else
-    switch (dim) {
-        case 32:
-            if (vector_io) IHG_MEM_PIPE(32) else IHG_MEM(32)
-            break;
-        case 64:
-            if (vector_io) IHG_MEM_PIPE(64) else IHG_MEM(64)
-            break;
-        case 128: {
-            const int grid = static_cast<int>(std::min<int64_t>((n_edges + 63) / 64, kPipeGrid));
-            hipLaunchKernelGGL((interact_bwd_members_wsbig_kernel<128, NBLK>), dim3(grid), dim3(kWsThreads), 0, s, h, ld_h, i3, wq, dout, ld_dout, g, n_edges);
-        } break;
-        default: IHG_MEM(256) break;
     }
-#undef IHG_MEM
-#undef IHG_MEM_PIPE
-    if (dw == nullptr) return;                               // member gradients only (the caller takes d w from the node-level kernel)
+    return c.cot.rows_in_memory();
+}
+
+// The product blocks' weight gradients into c.dw from the hyperedges' cotangents `rows`: split, strip, ws, mfma<64>, mfma<32> into slabs, then their sum.
+template <int NBLK>
+void weight_gradients(const BwdCall& c, EdgeRows rows) {
+    const int dim = c.dim;
+    const int64_t n_edges = c.n_edges;
+    float* slabs = c.ws.slabs;
     const int subs_ws = (dim / 64) * (dim / 64);
     int n_slabs = static_cast<int>(std::min<int64_t>(dim >= 64 ? std::max(kPipeGrid / subs_ws, 8) : weight_slabs(dim), (n_edges + 63) / 64));
-    if (split_weight_ok(dim, NBLK == 4 ? 3 : 2, ld_h, ld_dout, dout)) {      // bf16-split contraction
-        n_slabs = launch_weight_split(dim, NBLK == 4 ? 3 : 2, h, ld_h, i3, dout, ld_dout, slabs, n_edges, s);
-    } else if (dim == 128 && ld_h < (int64_t{1} << 30)) {
-        n_slabs = static_cast<int>(std::min<int64_t>((n_edges + kStripTE - 1) / kStripTE, kPipeGridSlabs));
-        hipLaunchKernelGGL((interact_bwd_weight_strip_kernel<128, NBLK>), dim3(n_slabs), dim3(kWsThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges);
-    } else if (dim >= 64 && ld_h < (int64_t{1} << 30)) {
-        hipLaunchKernelGGL((interact_bwd_weight_ws_kernel<NBLK>), dim3(n_slabs, subs_ws), dim3(kWsThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges, dim);
+    if (split_weight_ok(dim, c.order, c.ld_h, rows.ld, rows.p)) {           // bf16-split contraction
+        n_slabs = launch_weight_split(dim, c.order, c.h, c.ld_h, c.i3, rows.p, rows.ld, slabs, n_edges, c.s);
+    } else if (dim == 128 && c.ld_h < (int64_t{1} << 30)) {
+        n_slabs = grid_for_tiles(n_edges, kStripTE, kPipeGridSlabs);
+        hipLaunchKernelGGL((interact_bwd_weight_strip_kernel<128, NBLK>), dim3(n_slabs), dim3(kWsThreads), 0, c.s, c.h, c.ld_h, c.i3, rows.p, rows.ld, slabs, n_edges);
+    } else if (dim >= 64 && c.ld_h < (int64_t{1} << 30)) {
+        hipLaunchKernelGGL((interact_bwd_weight_ws_kernel<NBLK>), dim3(n_slabs, subs_ws), dim3(kWsThreads), 0, c.s, c.h, c.ld_h, c.i3, rows.p, rows.ld, slabs, n_edges, dim);
     } else if (dim >= 64) {                                  // row strides beyond 32-bit byte offsets: the plain tiling
-        hipLaunchKernelGGL((interact_bwd_weight_mfma_kernel<64, NBLK>), dim3(n_slabs, subs_ws), dim3(kBlockThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges, dim);
+        hipLaunchKernelGGL((interact_bwd_weight_mfma_kernel<64, NBLK>), dim3(n_slabs, subs_ws), dim3(kBlockThreads), 0, c.s, c.h, c.ld_h, c.i3, rows.p, rows.ld, slabs, n_edges, dim);
     } else {
-        hipLaunchKernelGGL((interact_bwd_weight_mfma_kernel<32, NBLK>), dim3(n_slabs, 1), dim3(kBlockThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges, dim);
+        hipLaunchKernelGGL((interact_bwd_weight_mfma_kernel<32, NBLK>), dim3(n_slabs, 1), dim3(kBlockThreads), 0, c.s, c.h, c.ld_h, c.i3, rows.p, rows.ld, slabs, n_edges, dim);
     }
     const int total = dim * NBLK * dim;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, n_slabs, dim, NBLK, dw, ld_dw);
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, c.s, slabs, n_slabs, dim, NBLK, c.dw, c.ld_dw);
+}
+
+struct BackwardTiled {
+    template <int NBLK>
+    static void run(const BwdCall& c) {
+        const EdgeRows rows = member_gradients<NBLK>(c);
+        if (c.dw != nullptr) weight_gradients<NBLK>(c, rows);
+    }
+};
+
+// ---- argument checks ----
+// One pointer argument of an entry point and the row stride that goes with it.
+enum class Rows { kNone, kDim, kWeights };     // no row stride to check / rows of dim floats (ld >= dim) / rows of the weight matrix (ld >= 6 or 7 dim, by order)
+struct Operand { const void* p; int64_t ld; Rows rows; unsigned flags; };
+constexpr unsigned kOptional = 1;    // may be null
+constexpr unsigned kLdIfThere = 2;   // its row stride counts only when it is there (every optional operand; ihg_interact_bwd_gathered's dout also where it is required)
+constexpr unsigned kVector = 4;      // the tiled kernels move it as 16-byte vectors: 16-byte aligned, row stride a multiple of 4
+
+enum class Empty { kRefused, kReturnsAtOnce, kTaken };     // n_edges == 0: bad size / nothing to do, said before the pointers are looked at / an ordinary call
+
+// What differs between the entry points of the hyperedge form.
+struct EdgeFormEntry {
+    const char* name;
+    const char* covers;          // nullptr: a plain entry - every width, orders 2 and 3, and whatever the tiled kernels do not take goes to the scalar kernels;
+                                 // otherwise what <name>_supported() covers (for its message), and operands the kernels do not take are refused
+    bool supported;              // <name>_supported()'s answer
+    Empty empty;
+    bool tiled_form;             // plain entries: the tiled kernels have a form for this call
+    int64_t workspace_needed;
+};
+
+// The tests in the order every entry point makes them: order / shape support, sizes, null pointers, alignment, workspace.  *tiled: a tiled kernel takes the call
+// (always, for an entry that is not plain).
+int edge_form_check(const EdgeFormEntry& e, int dim, int order, int64_t n_edges, std::initializer_list<Operand> operands, int64_t workspace_bytes, bool* tiled) {
+    const bool plain = e.covers == nullptr;
+    *tiled = false;
+    if (plain && order != 2 && order != 3) return fail(IHG_ERR_INVALID, "%s: order must be 2 or 3, got %d", e.name, order);
+    if (!plain && !e.supported) return fail(IHG_ERR_INVALID, "%s: %s not supported (ask %s_supported)", e.name, e.covers, e.name);
+    const int64_t k = order == 3 ? 7 : 6;
+    bool bad_size = n_edges < (e.empty == Empty::kRefused ? 1 : 0) || dim <= 0, null = false, vector = true;
+    for (const Operand& o : operands) {
+        const bool there = o.p != nullptr;
+        if ((there || !(o.flags & (kOptional | kLdIfThere))) && o.rows != Rows::kNone && o.ld < (o.rows == Rows::kWeights ? k : 1) * dim) bad_size = true;
+        if (!there && !(o.flags & kOptional)) null = true;
+        if ((o.flags & kVector) && (!aligned16(o.p) || (there && o.rows != Rows::kNone && o.ld % 4 != 0) || (plain && !there))) vector = false;
+    }
+    if (bad_size) return fail(IHG_ERR_INVALID, "%s: bad size", e.name);
+    if (n_edges == 0 && e.empty == Empty::kReturnsAtOnce) return IHG_OK;
+    if (null) return fail(IHG_ERR_INVALID, "%s: null pointer", e.name);
+    if (!plain && !vector) return fail(IHG_ERR_INVALID, "%s: rows must be 16-byte aligned", e.name);
+    *tiled = !plain || (vector && mfma_dim(dim) && n_edges > 0 && e.tiled_form);
+    if (*tiled && workspace_bytes < e.workspace_needed) return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", e.name);
+    return IHG_OK;
+}
+
+// The node-level entry points: order, type ranges, sizes (rows of h and of the result / cotangent, pair sums, weights), then - unless there are no nodes and the
+// entry returns at once for that - null pointers, whether a kernel takes the shape (`shape_ok`, the entry's own *_ok predicates), workspace.
+int node_form_check(const char* name, int dim, int order, const int64_t* type_begin, int64_t ld_h, int64_t ld_rows, int64_t ld_sums, int64_t ld_weights, bool empty_returns,
+                    std::initializer_list<const void*> required, bool shape_ok, const void* workspace, int64_t workspace_bytes, int64_t workspace_needed) {
+    if (order != 2 && order != 3) return fail(IHG_ERR_INVALID, "%s: order must be 2 or 3, got %d", name, order);
+    if (type_begin == nullptr || type_begin[0] != 0 || type_begin[1] < type_begin[0] || type_begin[2] < type_begin[1] || type_begin[3] < type_begin[2])
+        return fail(IHG_ERR_INVALID, "%s: bad type_begin", name);
+    if (dim <= 0 || ld_h < dim || ld_rows < dim || ld_sums < 3LL * dim || ld_weights < static_cast<int64_t>(order == 3 ? 7 : 6) * dim) return fail(IHG_ERR_INVALID, "%s: bad size", name);
+    if (empty_returns && type_begin[3] == 0) return IHG_OK;
+    for (const void* p : required)
+        if (p == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", name);
+    if (!shape_ok) return fail(IHG_ERR_INVALID, "%s: dim %d / order %d / alignment not supported (%s_supported)", name, dim, order, name);
+    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < workspace_needed) return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", name);
+    return IHG_OK;
 }
 
 }  // namespace
@@ -2073,38 +2159,28 @@ int64_t ihg_interact_fwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t o
 int ihg_interact_fwd(const float* h, int64_t ld_h, const float* p, int64_t ld_p, const int32_t* i3, const float* w, int64_t ld_w,
                      int32_t order, float* out, int64_t ld_out, void* workspace, int64_t workspace_bytes, int64_t n_edges,
                      int32_t dim, ihg_stream_t stream) {
-    if (order != 2 && order != 3) return fail(IHG_ERR_INVALID, "ihg_interact_fwd: order must be 2 or 3, got %d", order);
-    const int k = order == 3 ? 7 : 6;
-    if (n_edges < 0 || dim <= 0 || ld_h < dim || ld_out < dim || ld_w < static_cast<int64_t>(k) * dim || (p != nullptr && ld_p < dim))
-        return fail(IHG_ERR_INVALID, "ihg_interact_fwd: bad size");
+    const char* name = "ihg_interact_fwd";
+    bool tiled;
+    if (int rc = edge_form_check({name, nullptr, true, Empty::kReturnsAtOnce, p != nullptr, ihg_interact_fwd_workspace_bytes(n_edges, dim, order)}, dim, order, n_edges,
+                                 {{h, ld_h, Rows::kDim, kVector}, {p, ld_p, Rows::kDim, kOptional}, {i3, 0, Rows::kNone, 0}, {w, ld_w, Rows::kWeights, kVector}, {out, ld_out, Rows::kDim, 0}, {workspace, 0, Rows::kNone, kOptional | kVector}},
+                                 workspace_bytes, &tiled))
+        return rc;
     if (n_edges == 0) return IHG_OK;
-    if (h == nullptr || i3 == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_interact_fwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool tiled = mfma_dim(dim) && p != nullptr && ld_h % 4 == 0 && ld_w % 4 == 0 && aligned16(h) && aligned16(w) && workspace != nullptr &&
-                       aligned16(workspace);
     if (tiled) {
-        if (workspace_bytes < ihg_interact_fwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_fwd: workspace too small");
         float* wp = static_cast<float*>(workspace);
-        const int nblk = order == 3 ? 4 : 3;
         if (split_fwd_ok(dim, order, p, ld_p, out, ld_out, ld_h)) {       // bf16-split contraction; its planes sit behind the fp32-packed weights
             launch_fwd_split(dim, order, h, ld_h, p, ld_p, i3, w, ld_w, wp + packed_weight_floats(dim, order), out, ld_out, n_edges, s);
-            return check_launch("ihg_interact_fwd");
+            return check_launch(name);
         }
-        const int pack_items = (dim / 32) * nblk * (dim / 8) * kWave;
-        if (strip_fwd_ok(dim, p, ld_p, out, ld_out, ld_h))
-            hipLaunchKernelGGL(pack_weights_strip_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, wp,
-                               static_cast<float*>(nullptr));
-        else
-            hipLaunchKernelGGL(pack_weights_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, wp,
-                               static_cast<float*>(nullptr));
-        if (nblk == 4) launch_interact_fwd_mfma<4>(dim, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges, s);
-        else launch_interact_fwd_mfma<3>(dim, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges, s);
-        return check_launch("ihg_interact_fwd");
+        launch_pack_weights(strip_fwd_ok(dim, p, ld_p, out, ld_out, ld_h), w, ld_w, dim, order, wp, nullptr, s);
+        dispatch_nblk<ForwardTiled>(FwdCall{dim, order, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges, s});
+        return check_launch(name);
     }
     const int64_t total = n_edges * dim;
     const int grid = static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
     hipLaunchKernelGGL(interact_fwd_generic_kernel, dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, p, ld_p, i3, w, ld_w, order, out, ld_out, n_edges, dim);
-    return check_launch("ihg_interact_fwd");
+    return check_launch(name);
 }
 
 int32_t ihg_node_interact_fwd_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_sums, int64_t ld_out) {
@@ -2120,24 +2196,18 @@ int64_t ihg_node_interact_fwd_workspace_bytes(int32_t dim) {
 int ihg_node_interact_fwd(const float* h, int64_t ld_h, const float* sums, int64_t ld_sums, const float* degree, const float* out_scale, const float* bias,
                           const float* w, int64_t ld_w, int32_t order, const int64_t* type_begin, float* out, int64_t ld_out, void* workspace,
                           int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (order != 2 && order != 3) return fail(IHG_ERR_INVALID, "ihg_node_interact_fwd: order must be 2 or 3, got %d", order);
-    if (type_begin == nullptr || type_begin[0] != 0 || type_begin[1] < type_begin[0] || type_begin[2] < type_begin[1] || type_begin[3] < type_begin[2])
-        return fail(IHG_ERR_INVALID, "ihg_node_interact_fwd: bad type_begin");
-    if (dim <= 0 || ld_h < dim || ld_out < dim || ld_sums < 3LL * dim || ld_w < static_cast<int64_t>(order == 3 ? 7 : 6) * dim)
-        return fail(IHG_ERR_INVALID, "ihg_node_interact_fwd: bad size");
-    if (type_begin[3] == 0) return IHG_OK;
-    if (h == nullptr || sums == nullptr || degree == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_interact_fwd: null pointer");
+    const char* name = "ihg_node_interact_fwd";
     const bool narrow = narrow_node_fwd_ok(dim, order, ld_h, ld_sums, out, ld_out, bias);
-    if ((!narrow && !split_node_fwd_ok(dim, order, ld_h, ld_sums, out, ld_out, bias)) || !aligned16(h) || !aligned16(sums))
-        return fail(IHG_ERR_INVALID, "ihg_node_interact_fwd: dim %d / order %d / alignment not supported (ihg_node_interact_fwd_supported)", dim, order);
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_node_interact_fwd_workspace_bytes(dim))
-        return fail(IHG_ERR_WORKSPACE, "ihg_node_interact_fwd: workspace too small");
-    if (narrow) {                                                        // d = 32: plain fp32 MFMA, one wave per 16-row tile (narrow.hip)
+    const bool shape_ok = (narrow || split_node_fwd_ok(dim, order, ld_h, ld_sums, out, ld_out, bias)) && aligned16(h) && aligned16(sums);
+    if (int rc = node_form_check(name, dim, order, type_begin, ld_h, ld_out, ld_sums, ld_w, true, {h, sums, degree, w, out}, shape_ok, workspace, workspace_bytes,
+                                 ihg_node_interact_fwd_workspace_bytes(dim)))
+        return rc;
+    if (type_begin[3] == 0) return IHG_OK;
+    if (narrow)                                                          // d = 32: plain fp32 MFMA, one wave per 16-row tile (narrow.hip)
         launch_node_fwd_narrow(order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-        return check_launch("ihg_node_interact_fwd");
-    }
-    launch_node_fwd_split(dim, order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, workspace, static_cast<hipStream_t>(stream));
-    return check_launch("ihg_node_interact_fwd");
+    else
+        launch_node_fwd_split(dim, order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, workspace, static_cast<hipStream_t>(stream));
+    return check_launch(name);
 }
 
 int32_t ihg_node_interact_bwd_weight_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_sums, int64_t ld_dy) {
@@ -2152,23 +2222,17 @@ int64_t ihg_node_interact_bwd_weight_workspace_bytes(int32_t dim, int32_t order)
 
 int ihg_node_interact_bwd_weight(const float* h, int64_t ld_h, const float* sums, int64_t ld_sums, const float* dy, int64_t ld_dy, const float* dy_scale, int32_t order,
                                  const int64_t* type_begin, float* dw, int64_t ld_dw, void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (order != 2 && order != 3) return fail(IHG_ERR_INVALID, "ihg_node_interact_bwd_weight: order must be 2 or 3, got %d", order);
-    if (type_begin == nullptr || type_begin[0] != 0 || type_begin[1] < type_begin[0] || type_begin[2] < type_begin[1] || type_begin[3] < type_begin[2])
-        return fail(IHG_ERR_INVALID, "ihg_node_interact_bwd_weight: bad type_begin");
-    if (dim <= 0 || ld_h < dim || ld_dy < dim || ld_sums < 3LL * dim || ld_dw < static_cast<int64_t>(order == 3 ? 7 : 6) * dim)
-        return fail(IHG_ERR_INVALID, "ihg_node_interact_bwd_weight: bad size");
-    if (h == nullptr || sums == nullptr || dy == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_interact_bwd_weight: null pointer");
+    const char* name = "ihg_node_interact_bwd_weight";
     const bool narrow = narrow_node_weight_ok(dim, order, ld_h, ld_sums, ld_dy, dy);
-    if ((!narrow && !split_node_weight_ok(dim, order, ld_h, ld_sums, ld_dy, dy)) || !aligned16(h) || !aligned16(sums))
-        return fail(IHG_ERR_INVALID, "ihg_node_interact_bwd_weight: dim %d / order %d / alignment not supported (ihg_node_interact_bwd_weight_supported)", dim, order);
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_node_interact_bwd_weight_workspace_bytes(dim, order))
-        return fail(IHG_ERR_WORKSPACE, "ihg_node_interact_bwd_weight: workspace too small");
-    if (narrow) {
+    const bool shape_ok = (narrow || split_node_weight_ok(dim, order, ld_h, ld_sums, ld_dy, dy)) && aligned16(h) && aligned16(sums);
+    if (int rc = node_form_check(name, dim, order, type_begin, ld_h, ld_dy, ld_sums, ld_dw, false, {h, sums, dy, dw}, shape_ok, workspace, workspace_bytes,
+                                 ihg_node_interact_bwd_weight_workspace_bytes(dim, order)))
+        return rc;
+    if (narrow)
         launch_node_weight_narrow(order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, static_cast<float*>(workspace), dw, ld_dw, static_cast<hipStream_t>(stream));
-        return check_launch("ihg_node_interact_bwd_weight");
-    }
-    launch_node_weight_split(dim, order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, static_cast<float*>(workspace), dw, ld_dw, static_cast<hipStream_t>(stream));
-    return check_launch("ihg_node_interact_bwd_weight");
+    else
+        launch_node_weight_split(dim, order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, static_cast<float*>(workspace), dw, ld_dw, static_cast<hipStream_t>(stream));
+    return check_launch(name);
 }
 
 int64_t ihg_interact_bwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t order) {
@@ -2188,24 +2252,20 @@ int32_t ihg_interact_bwd_user_reduced_supported(int32_t dim, int32_t order, int6
 int ihg_interact_bwd_user_reduced(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
                                   const float* dout, int64_t ld_dout, float* g2, float* dh, int64_t ld_dh, float* dw, int64_t ld_dw,
                                   void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream) {
-    if (!ihg_interact_bwd_user_reduced_supported(dim, order, ld_h)) return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced: shape not supported (ask ihg_interact_bwd_user_reduced_supported)");
-    const int k = order == 3 ? 7 : 6;
-    if (n_edges <= 0 || ld_h < dim || ld_dout < dim || ld_dh < dim || ld_w < static_cast<int64_t>(k) * dim || (dw != nullptr && ld_dw < static_cast<int64_t>(k) * dim))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced: bad size");
-    if (h == nullptr || i3 == nullptr || w == nullptr || dout == nullptr || g2 == nullptr || dh == nullptr || workspace == nullptr)
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced: null pointer");
-    if (ld_w % 4 || ld_dout % 4 || !aligned16(h) || !aligned16(w) || !aligned16(dout) || !aligned16(g2) || !aligned16(workspace))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced: rows must be 16-byte aligned");
-    if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd_user_reduced: workspace too small");
+    const char* name = "ihg_interact_bwd_user_reduced";
+    bool tiled;
+    if (int rc = edge_form_check({name, "shape", ihg_interact_bwd_user_reduced_supported(dim, order, ld_h) != 0, Empty::kRefused, true, ihg_interact_bwd_workspace_bytes(n_edges, dim, order)},
+                                 dim, order, n_edges,
+                                 {{h, ld_h, Rows::kDim, kVector}, {i3, 0, Rows::kNone, 0}, {w, ld_w, Rows::kWeights, kVector}, {dout, ld_dout, Rows::kDim, kVector}, {g2, 0, Rows::kNone, kVector}, {dh, ld_dh, Rows::kDim, 0}, {dw, ld_dw, Rows::kWeights, kOptional},
+                                  {workspace, 0, Rows::kNone, kVector}},
+                                 workspace_bytes, &tiled))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nblk = order == 3 ? 4 : 3;
     const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
-    const int pack_items = (dim / 16) * nblk * (dim / 16) * kWave;
-    hipLaunchKernelGGL(pack_weights_strip_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
-                       static_cast<float*>(nullptr), ws.wq);
-    if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes);
-    else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes);
-    return check_launch("ihg_interact_bwd_user_reduced");
+    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user};
+    launch_pack_weights(true, w, ld_w, dim, order, nullptr, ws.wq, s);
+    dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::rows(dout, ld_dout), g2, &ur, dw, ld_dw, ws, n_edges, s});
+    return check_launch(name);
 }
 
 int32_t ihg_interact_bwd_user_reduced_planes_supported(int32_t dim, int32_t order, int64_t ld_h) {
@@ -2215,22 +2275,21 @@ int32_t ihg_interact_bwd_user_reduced_planes_supported(int32_t dim, int32_t orde
 int ihg_interact_bwd_user_reduced_planes(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order, const void* planes_rows,
                                          const float* inv_scale, float* g2, float* dh, int64_t ld_dh, void* workspace, int64_t workspace_bytes, int64_t n_edges,
                                          int32_t dim, ihg_stream_t stream) {
-    if (!ihg_interact_bwd_user_reduced_planes_supported(dim, order, ld_h))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced_planes: shape or arithmetic mode not supported (ask ihg_interact_bwd_user_reduced_planes_supported)");
-    const int k = order == 3 ? 7 : 6;
-    if (n_edges <= 0 || ld_h < dim || ld_dh < dim || ld_w < static_cast<int64_t>(k) * dim) return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced_planes: bad size");
-    if (h == nullptr || i3 == nullptr || w == nullptr || planes_rows == nullptr || inv_scale == nullptr || g2 == nullptr || dh == nullptr || workspace == nullptr)
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced_planes: null pointer");
-    if (ld_w % 4 || !aligned16(h) || !aligned16(w) || !aligned16(planes_rows) || !aligned16(g2) || !aligned16(workspace))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_user_reduced_planes: rows must be 16-byte aligned");
-    if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd_user_reduced_planes: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const char* name = "ihg_interact_bwd_user_reduced_planes";
+    bool tiled;
+    if (int rc = edge_form_check({name, "shape or arithmetic mode", ihg_interact_bwd_user_reduced_planes_supported(dim, order, ld_h) != 0, Empty::kRefused, true,
+                                  ihg_interact_bwd_workspace_bytes(n_edges, dim, order)},
+                                 dim, order, n_edges,
+                                 {{h, ld_h, Rows::kDim, kVector}, {i3, 0, Rows::kNone, 0}, {w, ld_w, Rows::kWeights, kVector}, {planes_rows, 0, Rows::kNone, kVector}, {inv_scale, 0, Rows::kNone, 0}, {g2, 0, Rows::kNone, kVector}, {dh, ld_dh, Rows::kDim, 0},
+                                  {workspace, 0, Rows::kNone, kVector}},
+                                 workspace_bytes, &tiled))
+        return rc;
+    // (the shape is one the split kernel takes: member_gradients launches it and the boundary runs' sum, nothing else)
     const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
-    int entries = 0;
-    launch_members_split(dim, order, h, ld_h, i3, w, ld_w, ws.planes, static_cast<const float*>(planes_rows), dim, g2, n_edges, dh, ld_dh, ws.bnd_val, ws.bnd_user, &entries, s,
-                         nullptr, nullptr, 0, inv_scale);
-    hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, s, ws.bnd_val, ws.bnd_user, entries, dim, dh, ld_dh);
-    return check_launch("ihg_interact_bwd_user_reduced_planes");
+    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user};
+    dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::planes(planes_rows, dim, inv_scale), g2, &ur, nullptr, 0, ws, n_edges,
+                                         static_cast<hipStream_t>(stream)});
+    return check_launch(name);
 }
 
 int32_t ihg_interact_bwd_gathered_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_dy) {
@@ -2240,72 +2299,54 @@ int32_t ihg_interact_bwd_gathered_supported(int32_t dim, int32_t order, int64_t 
 int ihg_interact_bwd_gathered(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
                               const float* dy, int64_t ld_dy, const float* dy_scale, float* dout, int64_t ld_dout, float* g2, float* dh, int64_t ld_dh,
                               float* dw, int64_t ld_dw, void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream) {
-    if (!ihg_interact_bwd_gathered_supported(dim, order, ld_h, ld_dy))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_gathered: shape or arithmetic mode not supported (ask ihg_interact_bwd_gathered_supported)");
-    const int k = order == 3 ? 7 : 6;
-    if (n_edges <= 0 || ld_h < dim || (dout != nullptr && ld_dout < dim) || ld_dh < dim || ld_w < static_cast<int64_t>(k) * dim || (dw != nullptr && ld_dw < static_cast<int64_t>(k) * dim))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_gathered: bad size");
-    if (h == nullptr || i3 == nullptr || w == nullptr || dy == nullptr || (dout == nullptr && dw != nullptr) || g2 == nullptr || dh == nullptr || workspace == nullptr)
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_gathered: null pointer");
-    if (dout == nullptr) {                                               // the hyperedges' cotangents are formed and used on chip only
-        dout = g2;
-        ld_dout = -1;
-    }
-    if (ld_w % 4 || (ld_dout > 0 && ld_dout % 4) || !aligned16(h) || !aligned16(w) || !aligned16(dy) || !aligned16(dout) || !aligned16(g2) || !aligned16(workspace))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_gathered: rows must be 16-byte aligned");
-    if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd_gathered: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nblk = order == 3 ? 4 : 3;
+    const char* name = "ihg_interact_bwd_gathered";
+    bool tiled;
+    // dout == NULL: the hyperedges' cotangents are formed and used on chip only - allowed where no weight step reads them
+    if (int rc = edge_form_check({name, "shape or arithmetic mode", ihg_interact_bwd_gathered_supported(dim, order, ld_h, ld_dy) != 0, Empty::kRefused, true,
+                                  ihg_interact_bwd_workspace_bytes(n_edges, dim, order)},
+                                 dim, order, n_edges,
+                                 {{h, ld_h, Rows::kDim, kVector}, {i3, 0, Rows::kNone, 0}, {w, ld_w, Rows::kWeights, kVector}, {dy, ld_dy, Rows::kDim, kVector}, {dout, ld_dout, Rows::kDim, kVector | kLdIfThere | (dw != nullptr ? 0u : kOptional)},
+                                  {g2, 0, Rows::kNone, kVector}, {dh, ld_dh, Rows::kDim, 0}, {dw, ld_dw, Rows::kWeights, kOptional}, {workspace, 0, Rows::kNone, kVector}},
+                                 workspace_bytes, &tiled))
+        return rc;
     const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);  // (the fp32 fragment image of w, ws.wq, is not needed by the split kernels)
-    if (dim == kNarrowDim ? (!narrow_members_ok(dim, order, g2, ld_h, ld_dy, dy) || (dw != nullptr && ld_dout <= 0))
-                          : (!split_members_ok(dim, order, g2, ld_h, ld_dy, dy, true) || (dw != nullptr && !split_weight_ok(dim, order, ld_h, ld_dout, dout))))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd_gathered: the kernels do not take these strides / alignments");
-    if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, ws.wq, dy, ld_dy, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes, dy_scale,
-                                               dout, ld_dout);
-    else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, ws.wq, dy, ld_dy, g2, ws.slabs, dw, ld_dw, n_edges, s, dh, ld_dh, ws.bnd_val, ws.bnd_user, w, ld_w, ws.planes, dy_scale,
-                                     dout, ld_dout);
-    return check_launch("ihg_interact_bwd_gathered");
+    if (dim == kNarrowDim ? !narrow_members_ok(dim, order, g2, ld_h, ld_dy, dy)
+                          : (!split_members_ok(dim, order, g2, ld_h, ld_dy, dy) || (dw != nullptr && !split_weight_ok(dim, order, ld_h, ld_dout, dout))))
+        return fail(IHG_ERR_INVALID, "%s: the kernels do not take these strides / alignments", name);
+    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user};
+    dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::node_level(dy, ld_dy, dy_scale, dout, ld_dout), g2, &ur, dw, ld_dw, ws, n_edges,
+                                         static_cast<hipStream_t>(stream)});
+    return check_launch(name);
 }
 
 int ihg_interact_bwd(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
                      const float* dout, int64_t ld_dout, float* g, float* dw, int64_t ld_dw, void* workspace,
                      int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream) {
-    if (order != 2 && order != 3) return fail(IHG_ERR_INVALID, "ihg_interact_bwd: order must be 2 or 3, got %d", order);
-    const int k = order == 3 ? 7 : 6;
-    if (n_edges < 0 || dim <= 0 || ld_h < dim || ld_dout < dim || ld_w < static_cast<int64_t>(k) * dim || (dw != nullptr && ld_dw < static_cast<int64_t>(k) * dim))
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd: bad size");
-    if (h == nullptr || i3 == nullptr || w == nullptr || dout == nullptr || g == nullptr)
-        return fail(IHG_ERR_INVALID, "ihg_interact_bwd: null pointer");
+    const char* name = "ihg_interact_bwd";
+    bool tiled;
+    if (int rc = edge_form_check({name, nullptr, true, Empty::kTaken, true, ihg_interact_bwd_workspace_bytes(n_edges, dim, order)}, dim, order, n_edges,
+                                 {{h, ld_h, Rows::kDim, kVector}, {i3, 0, Rows::kNone, 0}, {w, ld_w, Rows::kWeights, kVector}, {dout, ld_dout, Rows::kDim, kVector}, {g, 0, Rows::kNone, 0}, {dw, ld_dw, Rows::kWeights, kOptional},
+                                  {workspace, 0, Rows::kNone, kOptional | kVector}},
+                                 workspace_bytes, &tiled))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool tiled = mfma_dim(dim) && n_edges > 0 && ld_h % 4 == 0 && ld_w % 4 == 0 && ld_dout % 4 == 0 && aligned16(h) && aligned16(w) &&
-                       aligned16(dout) && workspace != nullptr && aligned16(workspace);
     if (tiled) {
-        if (workspace_bytes < ihg_interact_bwd_workspace_bytes(n_edges, dim, order)) return fail(IHG_ERR_WORKSPACE, "ihg_interact_bwd: workspace too small");
-        const int nblk = order == 3 ? 4 : 3;
-        const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
-        const int pack_items = (dim / 32) * nblk * (dim / 8) * kWave;
-        if (strip_bwd_ok(dim, g, ld_h))
-            hipLaunchKernelGGL(pack_weights_strip_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
-                               static_cast<float*>(nullptr), ws.wq);
-        else
-            hipLaunchKernelGGL(pack_weights_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk,
-                               static_cast<float*>(nullptr), ws.wq);
-        // the bf16 planes of the split contraction sit behind the boundary table (only d = 128 has either)
-        void* planes = split_plane_floats(dim, order) == 0 ? nullptr : ws.planes;
-        if (nblk == 4) launch_interact_bwd_mfma<4>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g, ws.slabs, dw, ld_dw, n_edges, s, nullptr, 0, nullptr, nullptr, w, ld_w, planes);
-        else launch_interact_bwd_mfma<3>(dim, h, ld_h, i3, ws.wq, dout, ld_dout, g, ws.slabs, dw, ld_dw, n_edges, s, nullptr, 0, nullptr, nullptr, w, ld_w, planes);
-        return check_launch("ihg_interact_bwd");
+        BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
+        launch_pack_weights(strip_bwd_ok(dim, g, ld_h), w, ld_w, dim, order, nullptr, ws.wq, s);
+        if (split_plane_floats(dim, order) == 0) ws.planes = nullptr;     // d = 32: no split kernel, and the narrow one has the user-reduced form only
+        dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::rows(dout, ld_dout), g, nullptr, dw, ld_dw, ws, n_edges, s});
+        return check_launch(name);
     }
     if (n_edges > 0) {
         const int64_t total = n_edges * dim;
         const int grid = static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
         hipLaunchKernelGGL(interact_bwd_members_generic_kernel, dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, i3, w, ld_w, order, dout, ld_dout, g, n_edges, dim);
     }
-    if (dw == nullptr) return check_launch("ihg_interact_bwd");
-    const int64_t wtotal = static_cast<int64_t>(dim) * (order == 3 ? 4 : 3) * dim;
+    if (dw == nullptr) return check_launch(name);
+    const int64_t wtotal = static_cast<int64_t>(dim) * product_blocks(order) * dim;
     const int wgrid = static_cast<int>(std::min<int64_t>((wtotal + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
     hipLaunchKernelGGL(interact_bwd_weight_generic_kernel, dim3(wgrid), dim3(kBlockThreads), 0, s, h, ld_h, i3, order, dout, ld_dout, dw, ld_dw, n_edges, dim);
-    return check_launch("ihg_interact_bwd");
+    return check_launch(name);
 }
 
 }  // extern "C"

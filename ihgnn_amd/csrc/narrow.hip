@@ -799,33 +799,42 @@ bool narrow_members_ok(int dim, int order, const float* g2, int64_t ld_h, int64_
     return dim == ND && (order == 2 || order == 3) && ld_h % 4 == 0 && ld_d % 4 == 0 && ld_h < (int64_t{1} << 31) && ld_d < (int64_t{1} << 31) && aligned16(g2) && aligned16(dsrc);
 }
 
-void launch_members_narrow(int order, int gather, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, float* packed, const float* dsrc, int64_t ld_d,
-                           const float* dy_scale, float* dout_store, int64_t ld_store, float* g2, int64_t n_edges, float* dh_user, int64_t ld_dh, float* bnd_val,
-                           int32_t* bnd_user, int* n_boundary_entries, hipStream_t s) {
+namespace {
+struct MembersNarrowCall {
+    int order;
+    const float* h; int64_t ld_h; const int32_t* i3; float* packed;
+    const EdgeCotangent& cot; float* g2; int64_t n_edges; const UserReduced& ur; int n_ranges; hipStream_t s;
+};
+
+template <int NBLK, bool GATHER, bool STORE>
+void launch_members_narrow_kernel(const MembersNarrowCall& c) {
+    float* dump = c.packed + narrow_members_packed(c.order) + 16;
+    hipLaunchKernelGGL((members_narrow_kernel<NBLK, GATHER, STORE>), dim3(grid_for_waves(c.n_ranges)), dim3(kBlockThreads), 0, c.s, c.h, c.ld_h, c.i3, c.packed, c.cot.src, c.cot.ld,
+                       GATHER ? c.cot.scale : nullptr, STORE ? c.cot.store : nullptr, STORE ? c.cot.ld_store : int64_t{0}, c.g2, c.n_edges, c.ur.dh, c.ur.ld_dh, c.ur.bnd_val,
+                       c.ur.bnd_user, c.n_ranges, dump);
+}
+
+struct MembersNarrow {
+    template <int NBLK>
+    static void run(const MembersNarrowCall& c) {
+        if (c.cot.kind != EdgeCotangent::Kind::kNodeLevel) launch_members_narrow_kernel<NBLK, false, false>(c);
+        else if (c.cot.store != nullptr) launch_members_narrow_kernel<NBLK, true, true>(c);
+        else launch_members_narrow_kernel<NBLK, true, false>(c);
+    }
+};
+}  // namespace
+
+void launch_members_narrow(int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, float* packed, const EdgeCotangent& cot, float* g2,
+                           int64_t n_edges, const UserReduced& ur, hipStream_t s) {
     const int nblk = order == 3 ? 4 : 3;
     const int items = nblk * 2 * 8 * kWave;
     hipLaunchKernelGGL(pack_members_narrow_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, nblk, packed);
     const int64_t n_tiles = (n_edges + NT - 1) / NT;
     const int n_ranges = static_cast<int>(std::min<int64_t>(n_tiles, kNarrowMemberRanges));
-    *n_boundary_entries = 2 * n_ranges;
-    const int grid = grid_for_waves(n_ranges);
-    float* dump = packed + narrow_members_packed(order) + 16;
-#define IHG_NARROW_MEMBERS(NBLK, GATHER, STORE)                                                                                                                            \
-    hipLaunchKernelGGL((members_narrow_kernel<NBLK, GATHER, STORE>), dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, i3, packed, dsrc, ld_d, dy_scale, dout_store, ld_store, g2, \
-                       n_edges, dh_user, ld_dh, bnd_val, bnd_user, n_ranges, dump)
-    const bool store = gather && dout_store != nullptr;
-    if (nblk == 4) {
-        if (!gather) IHG_NARROW_MEMBERS(4, false, false);
-        else if (store) IHG_NARROW_MEMBERS(4, true, true);
-        else IHG_NARROW_MEMBERS(4, true, false);
-    } else {
-        if (!gather) IHG_NARROW_MEMBERS(3, false, false);
-        else if (store) IHG_NARROW_MEMBERS(3, true, true);
-        else IHG_NARROW_MEMBERS(3, true, false);
-    }
-#undef IHG_NARROW_MEMBERS
+    dispatch_nblk<MembersNarrow>(MembersNarrowCall{order, h, ld_h, i3, packed, cot, g2, n_edges, ur, n_ranges, s});
     const int per_block = kBlockThreads / ND;
-    hipLaunchKernelGGL(narrow_boundary_fixup_kernel, dim3((2 * n_ranges + per_block - 1) / per_block), dim3(kBlockThreads), 0, s, bnd_val, bnd_user, 2 * n_ranges, dh_user, ld_dh);
+    hipLaunchKernelGGL(narrow_boundary_fixup_kernel, dim3((2 * n_ranges + per_block - 1) / per_block), dim3(kBlockThreads), 0, s, ur.bnd_val, ur.bnd_user, 2 * n_ranges, ur.dh,
+                       ur.ld_dh);
 }
 
 bool narrow_linear_ok(int dim, int64_t ld_a, int64_t ld_b) { return (dim == 32 || dim == 64) && ld_a % 4 == 0 && ld_b % 4 == 0; }

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "interact_args.hpp"
 
 #ifndef IHG_INTERNAL
 #define IHG_INTERNAL __attribute__((visibility("hidden")))
@@ -31,14 +32,13 @@ IHG_INTERNAL bool narrow_node_weight_ok(int dim, int order, int64_t ld_h, int64_
 IHG_INTERNAL void launch_node_weight_narrow(int order, const float* h, int64_t ld_h, const float* sums, int64_t ld_s, const float* dy, int64_t ld_dy, const float* dy_scale,
                                             const int64_t* type_begin, float* slabs, float* dw, int64_t ld_dw, hipStream_t s);
 
-// member gradients, user slot reduced on chip (g2 is [E, 2, d]; hyperedges numbered by user).  dy_scale / dout_store as in launch_members_split: with gather != 0 `dsrc` is
-// the node-level cotangent [N, d] and the kernel forms the hyperedges' cotangents itself (dout_store != nullptr: and leaves them there).  packed: narrow_members_floats(order)
-// floats of workspace; the boundary table holds 2 * kNarrowMemberRanges entries; *n_boundary_entries = entries written.  The boundary runs are added up by the launch itself.
+// member gradients, user slot reduced on chip (g2 is [E, 2, d]; hyperedges numbered by user; `ur` and `cot`: interact_args.hpp).  The cotangents are fp32 rows or a
+// node-level cotangent [N, d] that the kernel gathers and sums itself, leaving the rows in cot.store where there is one (no planes at this width).  packed:
+// narrow_members_floats(order) floats of workspace; the boundary table holds 2 * kNarrowMemberRanges entries.  The boundary runs are added up by the launch itself.
 IHG_INTERNAL int64_t narrow_members_floats(int order);
 IHG_INTERNAL bool narrow_members_ok(int dim, int order, const float* g2, int64_t ld_h, int64_t ld_d, const float* dsrc);
-IHG_INTERNAL void launch_members_narrow(int order, int gather, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, float* packed, const float* dsrc,
-                                        int64_t ld_d, const float* dy_scale, float* dout_store, int64_t ld_store, float* g2, int64_t n_edges, float* dh_user, int64_t ld_dh,
-                                        float* bnd_val, int32_t* bnd_user, int* n_boundary_entries, hipStream_t s);
+IHG_INTERNAL void launch_members_narrow(int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, float* packed, const EdgeCotangent& cot, float* g2,
+                                        int64_t n_edges, const UserReduced& ur, hipStream_t s);
 
 // node-level linear maps (ihg_node_linear_*) at dim 32 and 64: forward / input gradient as one stream over the rows; weight + bias gradient (and, dx != nullptr, the input gradient
 // of the same rows) in one pass, slabs in dense.hip's layout (returns the slabs per type); pk: 3 dim^2 floats of workspace for the packed weights

@@ -11,21 +11,20 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "interact_args.hpp"
 
 #define IHG_INTERNAL __attribute__((visibility("hidden")))
 
 // floats of workspace the weight planes of one direction take (sized for three bf16 per weight; the two-fp16 kernels use two thirds of it)
 IHG_INTERNAL int64_t split_plane_floats(int dim, int order);
 IHG_INTERNAL bool split_arith_enabled();                       // IHG_INTERACT_ARITH != "f32"
-IHG_INTERNAL bool split_members_ok(int dim, int order, const float* g, int64_t ld_h, int64_t ld_dout, const float* dout, bool user_reduced);
+IHG_INTERNAL bool split_members_ok(int dim, int order, const float* g, int64_t ld_h, int64_t ld_dout, const float* dout);
 
-// member gradients; dh_user == nullptr: g is [E, 3, d], else the user-reduced form (g is [E, 2, d], boundary table as in interact.hip).
-// dout_store != nullptr (dim 128, user-reduced form): `dout` is a node-level cotangent [N, d]; the kernel forms dout[e] = sum over the members
-// of dy_scale[m] dout[m] (dy_scale == nullptr: 1) itself and leaves it in dout_store [E, ld_store]
-IHG_INTERNAL void launch_members_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, void* planes, const float* dout,
-                                       int64_t ld_dout, float* g, int64_t n_edges, float* dh_user, int64_t ld_dh, float* bnd_val, int32_t* bnd_user,
-                                       int* n_boundary_entries, hipStream_t s, const float* dy_scale = nullptr, float* dout_store = nullptr, int64_t ld_store = 0,
-                                       const float* inv_src = nullptr);     // inv_src != nullptr (dim 256): `dout` rows are fp16 planes with these inverse scales (ihg_edge_gather_sum_planes)
+// member gradients; ur == nullptr: g is [E, 3, d], else the user-reduced form (g is [E, 2, d]; interact_args.hpp).  `cot` says where the hyperedges' cotangents come
+// from: fp32 rows; fp16 planes with their inverse scales (dim 256); or a node-level cotangent [N, d] (dim 64 / 128, user-reduced form) that the kernel gathers and
+// sums itself, leaving the rows in cot.store where there is one
+IHG_INTERNAL void launch_members_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, void* planes, const EdgeCotangent& cot,
+                                       float* g, int64_t n_edges, const UserReduced* ur, int* n_boundary_entries, hipStream_t s);
 
 // forward (first-order rows p required); planes: split_plane_floats(dim, order) floats of workspace
 IHG_INTERNAL bool split_fwd_ok(int dim, int order, const float* p, int64_t ld_p, const float* out, int64_t ld_out, int64_t ld_h);
@@ -41,13 +40,13 @@ IHG_INTERNAL int64_t split_dense_plane_floats(int dim);
 IHG_INTERNAL bool split_row_gemm_ok(int dim, const float* out, int64_t ld_out, const float* bias, int64_t bias_type_stride);
 IHG_INTERNAL void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias,
                                         int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, TypedRowsOut out, int64_t ld_out, void* planes, hipStream_t s,
-                                        int accumulate = 0, int activation = 0);      // accumulate: out += (out holds another contribution to the same rows)
+                                        int accumulate, int activation);      // accumulate: out += (out holds another contribution to the same rows)
 
 // weight / bias gradient of the node-level linear maps into dense.hip's slabs ([type][slab][d][d], [type][slab][d]); returns the slabs per type
 IHG_INTERNAL bool split_dense_weight_ok(int dim, const float* dout, int64_t ld_dout, const float* x, int64_t ld_x);
 IHG_INTERNAL int launch_dense_weight_split(int dim, const float* dout, int64_t ld_dout, TypedRows x, int64_t ld_x, const int64_t* type_begin, int n_types,
                                            float* slabs, float* bias_slabs, const float* w, int64_t ld_w, int64_t w_type_stride, const TypedRowsOut* dx, int64_t ld_dx,
-                                           void* planes, hipStream_t s, int dx_accumulate = 0);   // dx != nullptr (dim 128, 16-byte aligned rows): dx (+)= dout W_t of the same rows, fused
+                                           void* planes, hipStream_t s, int dx_accumulate);   // dx != nullptr (dim 128, 16-byte aligned rows): dx (+)= dout W_t of the same rows, fused
 
 // node-level form of the interactive layer's forward (d = 64 / 128 / 256): out = scale * (sum over the node's hyperedges of their features) from h and the
 // pair sums of ihg_node_pair_sums; planes: split_node_fwd_plane_floats(dim) floats of workspace

@@ -109,9 +109,8 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
                                                                                       const float* __restrict__ dout, int64_t ld_dout,
                                                                                       float* __restrict__ g_out, int64_t n_edges, float* __restrict__ dh_user,
                                                                                       int64_t ld_dh, float* __restrict__ bnd_val, int32_t* __restrict__ bnd_user,
-                                                                                      const float* __restrict__ dy_scale = nullptr,
-                                                                                      float* __restrict__ dout_store = nullptr, int64_t ld_store = 0,
-                                                                                      const float* __restrict__ inv_src = nullptr) {
+                                                                                      const float* __restrict__ dy_scale, float* __restrict__ dout_store,
+                                                                                      int64_t ld_store, const float* __restrict__ inv_src) {
     static_assert(D == 128 || D == 64 || D == 256, "shapes");
     static_assert(!PLANES || !GATHER, "the gathering form makes its cotangents itself");
     static_assert(!GATHER || ((D == 128 || D == 64) && UR), "the gathering form exists where the layer's backward uses it");
@@ -1204,49 +1203,44 @@ bool split_arith_enabled() {                                             // read
 }
 
 // either form of g at every width (the gathering form: dim 64 and 128, the caller asks ihg_interact_bwd_gathered_supported)
-bool split_members_ok(int dim, int order, const float* g, int64_t ld_h, int64_t ld_dout, const float* dout, bool user_reduced) {
-    (void)user_reduced;
+bool split_members_ok(int dim, int order, const float* g, int64_t ld_h, int64_t ld_dout, const float* dout) {
     return split_arith_enabled() && (dim == 128 || dim == 64 || dim == 256) && (order == 2 || order == 3) && aligned16(g) && aligned16(dout) &&
            ld_ok(ld_h) && ld_ok(ld_dout);
 }
 
 namespace {
-template <int D, int NBLK>
-void launch_members_split_t(const float* h, int64_t ld_h, const int32_t* i3, const v4u* wsp, const float* winv, const float* dout, int64_t ld_dout, float* g, int64_t n_edges,
-                            float* dh_user, int64_t ld_dh, float* bnd_val, int32_t* bnd_user, const float* dy_scale, float* dout_store, int64_t ld_store,
-                            const float* inv_src, hipStream_t s) {
-    if constexpr (D == 256) {
-        if (inv_src != nullptr) {                                        // `dout` holds fp16 planes (ihg_edge_gather_sum_planes)
-            if (dh_user != nullptr)
-                hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, true, NBLK, false, true>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, wsp, winv, dout, ld_dout,
-                                   g, n_edges, dh_user, ld_dh, bnd_val, bnd_user, static_cast<const float*>(nullptr), static_cast<float*>(nullptr), int64_t{0}, inv_src);
-            else
-                hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, false, NBLK, false, true>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, wsp, winv, dout, ld_dout,
-                                   g, n_edges, static_cast<float*>(nullptr), int64_t{0}, static_cast<float*>(nullptr), static_cast<int32_t*>(nullptr),
-                                   static_cast<const float*>(nullptr), static_cast<float*>(nullptr), int64_t{0}, inv_src);
-            return;
-        }
-    }
-    if constexpr (D == 128 || D == 64) {
-        if (dh_user != nullptr && dout_store != nullptr) {              // `dout` is the node-level cotangent: gathered, summed, stored
-            hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, true, NBLK, true>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, wsp, winv, dout, ld_dout, g,
-                               n_edges, dh_user, ld_dh, bnd_val, bnd_user, dy_scale, dout_store, ld_store);
-            return;
-        }
-    }
-    if (dh_user != nullptr) {
-        hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, true, NBLK>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, wsp, winv, dout, ld_dout, g, n_edges,
-                           dh_user, ld_dh, bnd_val, bnd_user);
-        return;
-    }
-    hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, false, NBLK>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, wsp, winv, dout, ld_dout, g, n_edges,
-                       static_cast<float*>(nullptr), int64_t{0}, static_cast<float*>(nullptr), static_cast<int32_t*>(nullptr));
+// one launch of the member-gradient kernel: the call's operands and where launch_members_split left the weight planes and the inverse column scales
+struct MembersSplitCall {
+    int order;
+    const float* h; int64_t ld_h; const int32_t* i3; const v4u* wsp; const float* winv;
+    const EdgeCotangent& cot; float* g; int64_t n_edges; const UserReduced* ur; hipStream_t s;
+};
+
+template <int D, int NBLK, bool UR, bool GATHER, bool PLANES>
+void launch_members_split_kernel(const MembersSplitCall& c) {
+    const UserReduced ur = UR ? *c.ur : UserReduced{nullptr, 0, nullptr, nullptr};
+    hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, UR, NBLK, GATHER, PLANES>), dim3(256), dim3(kSplitThreads), 0, c.s, c.h, c.ld_h, c.i3, c.wsp, c.winv, c.cot.src,
+                       c.cot.ld, c.g, c.n_edges, ur.dh, ur.ld_dh, ur.bnd_val, ur.bnd_user, GATHER ? c.cot.scale : nullptr, GATHER ? c.cot.store : nullptr,
+                       GATHER ? c.cot.ld_store : int64_t{0}, PLANES ? c.cot.scale : nullptr);
 }
+
+template <int D>
+struct MembersSplit {
+    template <int NBLK>
+    static void run(const MembersSplitCall& c) {
+        const bool ur = c.ur != nullptr;
+        if constexpr (D == 256) {                                        // the cotangents are fp16 planes (ihg_edge_gather_sum_planes)
+            if (c.cot.kind == EdgeCotangent::Kind::kPlanes) return ur ? launch_members_split_kernel<D, NBLK, true, false, true>(c) : launch_members_split_kernel<D, NBLK, false, false, true>(c);
+        } else {                                                         // the node-level cotangent: gathered, summed, stored where there is a place
+            if (ur && c.cot.kind == EdgeCotangent::Kind::kNodeLevel) return launch_members_split_kernel<D, NBLK, true, true, false>(c);
+        }
+        ur ? launch_members_split_kernel<D, NBLK, true, false, false>(c) : launch_members_split_kernel<D, NBLK, false, false, false>(c);
+    }
+};
 }  // namespace
 
-void launch_members_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, void* planes, const float* dout,
-                          int64_t ld_dout, float* g, int64_t n_edges, float* dh_user, int64_t ld_dh, float* bnd_val, int32_t* bnd_user,
-                          int* n_boundary_entries, hipStream_t s, const float* dy_scale, float* dout_store, int64_t ld_store, const float* inv_src) {
+void launch_members_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, void* planes, const EdgeCotangent& cot, float* g,
+                          int64_t n_edges, const UserReduced* ur, int* n_boundary_entries, hipStream_t s) {
     v4u* wsp = static_cast<v4u*>(planes);
     const int nblk = order == 3 ? 4 : 3;
     const int items = (dim / 32) * 4 * (dim / 32) * 2 * kWave;
@@ -1256,13 +1250,10 @@ void launch_members_split(int dim, int order, const float* h, int64_t ld_h, cons
     hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(nblk) * dim)), dim3(kBlockThreads), 0, s, w + 3 * dim, ld_w, int64_t{dim}, nblk, dim, 1,
                        wsc, winv);
     hipLaunchKernelGGL(pack_planes_members_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, wsc, wsp);
-#define IHG_MEMBERS(D)                                                                                                                       \
-    {                                                                                                                                        \
-        if (nblk == 4) launch_members_split_t<D, 4>(h, ld_h, i3, wsp, winv, dout, ld_dout, g, n_edges, dh_user, ld_dh, bnd_val, bnd_user, dy_scale, dout_store, ld_store, inv_src, s); \
-        else launch_members_split_t<D, 3>(h, ld_h, i3, wsp, winv, dout, ld_dout, g, n_edges, dh_user, ld_dh, bnd_val, bnd_user, dy_scale, dout_store, ld_store, inv_src, s);           \
-    }
-    if (dim == 256) IHG_MEMBERS(256) else if (dim == 64) IHG_MEMBERS(64) else IHG_MEMBERS(128)
-#undef IHG_MEMBERS
+    const MembersSplitCall call{order, h, ld_h, i3, wsp, winv, cot, g, n_edges, ur, s};
+    if (dim == 256) dispatch_nblk<MembersSplit<256>>(call);
+    else if (dim == 64) dispatch_nblk<MembersSplit<64>>(call);
+    else dispatch_nblk<MembersSplit<128>>(call);
     if (n_boundary_entries != nullptr) *n_boundary_entries = 2 * (dim == 64 ? 256 : (dim == 128 ? kSplitRanges : 32));     // two per tile range (256 workgroups / column parts: 256, 128, 32 ranges)
 }
 
@@ -1327,13 +1318,8 @@ void launch_fwd_split(int dim, int order, const float* h, int64_t ld_h, const fl
     {
         const int items = (dim / 64) * 4 * 4 * (dim / 32) * kWave;
         hipLaunchKernelGGL(pack_planes_fwd_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, order == 3 ? 4 : 3, wsp);
-#define IHG_FWD(D)                                                                                                                                              \
-    {                                                                                                                                                           \
-        if (order == 3) hipLaunchKernelGGL((interact_fwd_split_ws_kernel<D, 4>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges); \
-        else hipLaunchKernelGGL((interact_fwd_split_ws_kernel<D, 3>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges);           \
-    }
-        IHG_FWD(64)
-#undef IHG_FWD
+        if (order == 3) hipLaunchKernelGGL((interact_fwd_split_ws_kernel<64, 4>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges);
+        else hipLaunchKernelGGL((interact_fwd_split_ws_kernel<64, 3>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges);
     }
 }
 

@@ -131,6 +131,120 @@ def test_update_tail_bad_arguments_return_invalid_and_launch_nothing():
         assert entry(first_null, None, 0, None, 0) == _lib.ERR_INVALID and 'null layer' in _lib.last_error()
 
 
+def _refused(rc, code, word):
+    assert rc == code and word in _lib.last_error(), (rc, _lib.last_error())
+
+
+def test_interact_hyperedge_entries_check_arguments_in_one_order(monkeypatch):
+    """The five hyperedge-form entry points of the interactive layer: what each refuses, with which word, and which of two faults present at once is reported
+    (shape support, sizes, null pointers, alignment, workspace - in that order).  ``ok`` is an aligned address that is never dereferenced, ``odd`` a misaligned one."""
+    monkeypatch.delenv('IHG_INTERACT_ARITH', raising=False)
+    lib = _lib.load()
+    ok, odd, INV, WS = ctypes.c_void_p(16), ctypes.c_void_p(8), _lib.ERR_INVALID, _lib.ERR_WORKSPACE
+
+    def bwd(order=3, ld_w=28, n=3, dim=4, p=ok):               # (h, ld_h, i3, w, ld_w, order, dout, ld_dout, g, dw, ld_dw, ws, bytes, n, dim, stream)
+        return lib.ihg_interact_bwd(p, 4, p, p, ld_w, order, p, 4, p, None, 0, None, 0, n, dim, None)
+    _refused(bwd(order=1), INV, 'order')
+    _refused(bwd(ld_w=27), INV, 'bad size')
+    _refused(bwd(p=None), INV, 'null pointer')
+    _refused(bwd(order=1, ld_w=8, p=None), INV, 'order')      # the order is looked at first,
+    _refused(bwd(ld_w=8, p=None), INV, 'bad size')             # then the sizes
+    _refused(bwd(n=0, p=None), INV, 'null pointer')            # (no early return for an empty problem in the backward)
+    _refused(lib.ihg_interact_bwd(ok, 4, ok, ok, 28, 3, ok, 4, ok, ok, 27, None, 0, 3, 4, None), INV, 'bad size')    # ld_dw counts only with a dw
+
+    def fwd(order=3, ld_w=28, n=0, p=None):                    # (h, ld_h, p, ld_p, i3, w, ld_w, order, out, ld_out, ws, bytes, n, dim, stream)
+        return lib.ihg_interact_fwd(p, 4, p, 4, p, p, ld_w, order, p, 4, None, 0, n, 4, None)
+    assert fwd() == _lib.OK and fwd(order=2, ld_w=24) == _lib.OK       # an empty problem with valid sizes: nothing to do, before the pointers are looked at
+    _refused(fwd(ld_w=27), INV, 'bad size')                    # sizes before the empty-problem return
+    _refused(fwd(order=0, ld_w=8), INV, 'order')
+    _refused(fwd(n=-1), INV, 'bad size')
+    _refused(fwd(n=3), INV, 'null pointer')
+
+    def reduced(dim=128, ld=128, n=5, h=ok, dh=ok, ws=ok, ws_bytes=1 << 40, dw=None, ld_dw=0):
+        # (h, ld_h, i3, w, ld_w, order, dout, ld_dout, g2, dh, ld_dh, dw, ld_dw, ws, bytes, n, dim, stream)
+        return lib.ihg_interact_bwd_user_reduced(h, ld, ok, ok, 7 * dim, 3, ok, ld, ok, dh, ld, dw, ld_dw, ws, ws_bytes, n, dim, None)
+    _refused(reduced(dim=12, ld=12), INV, 'not supported')
+    _refused(reduced(n=0), INV, 'bad size')
+    _refused(reduced(dh=None), INV, 'null pointer')
+    _refused(reduced(h=odd), INV, '16-byte aligned')
+    _refused(reduced(ws_bytes=0), WS, 'workspace too small')
+    _refused(reduced(dim=12, ld=12, n=0, dh=None), INV, 'not supported')
+    _refused(reduced(n=0, dh=None, h=odd), INV, 'bad size')
+    _refused(reduced(dh=None, h=odd, ws_bytes=0), INV, 'null pointer')
+    _refused(reduced(ws=None, ws_bytes=0), INV, 'null pointer')        # a missing workspace is a null pointer here, not a small workspace
+    _refused(reduced(h=odd, ws_bytes=0), INV, '16-byte aligned')
+    _refused(reduced(dw=ok, ld_dw=7 * 128 - 1), INV, 'bad size')
+    _refused(lib.ihg_interact_bwd_user_reduced(ok, 128, ok, ok, 896, 1, ok, 128, ok, ok, 128, None, 0, ok, 1 << 40, 5, 128, None), INV, 'not supported')   # a bad order too
+
+    def planes(dim=256, n=5, rows=ok, g2=ok, ws_bytes=1 << 40):
+        # (h, ld_h, i3, w, ld_w, order, planes_rows, inv_scale, g2, dh, ld_dh, ws, bytes, n, dim, stream)
+        return lib.ihg_interact_bwd_user_reduced_planes(ok, dim, ok, ok, 7 * dim, 3, rows, ok, g2, ok, dim, ok, ws_bytes, n, dim, None)
+    _refused(planes(dim=128), INV, 'not supported')
+    _refused(planes(dim=128, n=0, rows=None), INV, 'not supported')
+    _refused(planes(n=0, rows=None), INV, 'bad size')
+    _refused(planes(rows=None, g2=odd), INV, 'null pointer')
+    _refused(planes(g2=odd, ws_bytes=0), INV, '16-byte aligned')
+    _refused(planes(rows=odd), INV, '16-byte aligned')
+    _refused(planes(ws_bytes=0), WS, 'workspace too small')
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32')            # the planes are an operand of the split kernels only
+    _refused(planes(), INV, 'not supported')
+    monkeypatch.delenv('IHG_INTERACT_ARITH')
+
+    def gathered(dim=32, n=5, h=ok, dout=ok, ld_dout=None, dw=None, ws_bytes=0):
+        # (h, ld_h, i3, w, ld_w, order, dy, ld_dy, dy_scale, dout, ld_dout, g2, dh, ld_dh, dw, ld_dw, ws, bytes, n, dim, stream)
+        return lib.ihg_interact_bwd_gathered(h, dim, ok, ok, 7 * dim, 3, ok, dim, None, dout, dim if ld_dout is None else ld_dout, ok, ok, dim, dw, 7 * dim, ok, ws_bytes, n,
+                                             dim, None)
+    _refused(gathered(dim=256), INV, 'not supported')
+    _refused(gathered(dim=256, n=0, h=None), INV, 'not supported')
+    _refused(gathered(dout=None, dw=ok), INV, 'null pointer')            # the weight step reads the stored rows
+    _refused(gathered(dout=None, dw=None), WS, 'workspace too small')    # without it they need not be stored: past the null test, refused for the workspace
+    _refused(gathered(dout=None, ld_dout=0), WS, 'workspace too small')  # ... and their row stride is not looked at, neither for size
+    _refused(gathered(dout=None, ld_dout=34), WS, 'workspace too small')  # nor for alignment
+    _refused(gathered(ld_dout=0), INV, 'bad size')
+    _refused(gathered(ld_dout=34), INV, '16-byte aligned')
+    _refused(gathered(dout=odd), INV, '16-byte aligned')
+    _refused(gathered(n=0, h=None), INV, 'bad size')
+    _refused(gathered(h=None, dout=odd), INV, 'null pointer')
+    _refused(gathered(dim=128, dout=ok, dw=ok), WS, 'workspace too small')
+    _refused(gathered(dim=128, ld_dout=1 << 31, dw=ok, ws_bytes=1 << 40), INV, 'strides')    # rows the weight kernel cannot address: the last check before the launch
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32')            # d = 64 / 128 gather on the split kernels only, d = 32 in fp32 either way
+    _refused(gathered(dim=128), INV, 'not supported')
+    _refused(gathered(dim=32), WS, 'workspace too small')
+
+
+def test_interact_node_entries_check_arguments_in_one_order():
+    """``ihg_node_interact_fwd`` / ``ihg_node_interact_bwd_weight``: order, type ranges, sizes, (forward: no nodes = nothing to do,) null pointers, shape support,
+    workspace - in that order."""
+    lib = _lib.load()
+    ok, odd, INV, WS = ctypes.c_void_p(16), ctypes.c_void_p(8), _lib.ERR_INVALID, _lib.ERR_WORKSPACE
+    rising, falling, empty = (ctypes.c_int64 * 4)(0, 3, 5, 9), (ctypes.c_int64 * 4)(0, 5, 3, 9), (ctypes.c_int64 * 4)(0, 0, 0, 0)
+
+    def fwd(order=3, tb=rising, ld_w=7 * 32, dim=32, p=ok, h=None, ws_bytes=1 << 40):
+        # (h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, order, type_begin, out, ld_out, ws, bytes, dim, stream)
+        return lib.ihg_node_interact_fwd(p if h is None else h, dim, p, 3 * dim, p, None, None, p, ld_w, order, tb, p, dim, p, ws_bytes, dim, None)
+
+    def weight(order=3, tb=rising, ld_w=7 * 32, dim=32, p=ok, h=None, ws_bytes=1 << 40):
+        # (h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, order, type_begin, dw, ld_dw, ws, bytes, dim, stream)
+        return lib.ihg_node_interact_bwd_weight(p if h is None else h, dim, p, 3 * dim, p, dim, None, order, tb, p, ld_w, p, ws_bytes, dim, None)
+
+    for entry in (fwd, weight):
+        _refused(entry(order=4), INV, 'order')
+        _refused(entry(tb=falling), INV, 'type_begin')
+        _refused(entry(tb=None), INV, 'type_begin')
+        _refused(entry(tb=(ctypes.c_int64 * 4)(1, 3, 5, 9)), INV, 'type_begin')
+        _refused(entry(order=4, tb=falling, ld_w=8), INV, 'order')
+        _refused(entry(tb=falling, ld_w=8, p=None), INV, 'type_begin')
+        _refused(entry(ld_w=7 * 32 - 1, p=None), INV, 'bad size')
+        _refused(entry(p=None), INV, 'null pointer')
+        _refused(entry(p=None, dim=12, ld_w=7 * 12), INV, 'null pointer')
+        _refused(entry(dim=12, ld_w=7 * 12, ws_bytes=0), INV, 'not supported')
+        _refused(entry(h=odd, ws_bytes=0), INV, 'not supported')
+        _refused(entry(ws_bytes=0), WS, 'workspace too small')
+    assert fwd(tb=empty, p=None) == _lib.OK                     # no nodes: nothing to do, before the pointers are looked at
+    _refused(fwd(tb=empty, ld_w=8, p=None), INV, 'bad size')
+    _refused(weight(tb=empty, p=None), INV, 'null pointer')     # (the weight gradient has no such return)
+
+
 def test_missing_library_is_a_hard_error(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libihgnn_hip.so')

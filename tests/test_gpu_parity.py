@@ -944,6 +944,44 @@ def test_interact_to_nodes_backward_forms_the_hyperedge_cotangents_itself(order,
             assert rel(got, want) <= RTOL
 
 
+@pytest.mark.parametrize('dim', [32, 64, 128])
+@pytest.mark.parametrize('order', [2, 3])
+@pytest.mark.parametrize('edges', [33, 300 * 32 + 9])
+def test_interact_bwd_gathered_with_and_without_stored_cotangents(edges, order, dim):
+    """``ihg_interact_bwd_gathered`` called directly, twice on the same operands: with a ``dout`` buffer and ``dw`` (the kernel stores the hyperedges' cotangents it forms,
+    the weight step reads them) and with ``dout = NULL, dw = NULL`` (they stay on chip).  The member gradients ``g2`` / ``dh`` do not depend on which, bit for bit, and
+    the stored rows are K5's (``ihg_edge_gather_sum``: the sum formed in the same order).  7 users over 33 hyperedges (one tile and a row) and over 9,609 (a user's run
+    across workgroups, a partial last tile)."""
+    from ihgnn_amd import _lib, ops
+    lib = _lib.load()
+    w_, lay = make_layout(7, 17, 211, edges, seed=order + edges + dim, edge_order='user')
+    gen = torch.Generator().manual_seed(edges + dim)
+    k = 6 if order == 2 else 7
+    h = torch.randn(lay.node_count, dim, generator=gen).to(dev())
+    w = (torch.randn(dim, k * dim, generator=gen) / np.sqrt(k * dim)).to(dev())
+    dy = (torch.randn(lay.node_count, dim, generator=gen) / 8).to(dev())
+    scale = lay.inv_deg
+    n = lay.edge_count
+    assert lib.ihg_interact_bwd_gathered_supported(dim, order, dim, dim)
+    ws = ops._workspace(int(lib.ihg_interact_bwd_workspace_bytes(n, dim, order)), dev())
+
+    def run(store):
+        dout = torch.zeros(n, dim, device=dev()) if store else None
+        dw = torch.zeros(dim, k * dim, device=dev()) if store else None
+        g2, dh = torch.zeros(n, 2 * dim, device=dev()), torch.zeros(lay.node_count, dim, device=dev())
+        _lib.check(lib.ihg_interact_bwd_gathered(ops._ptr(h), dim, ops._ptr(lay.i3), ops._ptr(w), k * dim, order, ops._ptr(dy), dim, ops._ptr(scale), ops._ptr(dout), dim,
+                                                 ops._ptr(g2), ops._ptr(dh), dim, ops._ptr(dw), k * dim, ops._ptr(ws), ws.numel() * 4, n, dim, ops._stream()),
+                   'ihg_interact_bwd_gathered')
+        torch.cuda.synchronize()
+        return g2, dh, dout
+
+    g2_s, dh_s, dout = run(True)
+    g2_n, dh_n, _ = run(False)
+    assert torch.equal(g2_s, g2_n) and torch.equal(dh_s, dh_n)
+    assert torch.equal(dout, ops.edge_gather_sum_raw(dy, lay.i3, scale))
+    assert float(g2_s.abs().max()) > 0 and float(dh_s[:7].abs().max()) > 0
+
+
 @pytest.mark.parametrize('dim', [64, 128])
 @pytest.mark.parametrize('order', [3, 2])
 def test_feature_interactor_module_call(order, dim):
