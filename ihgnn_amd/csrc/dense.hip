@@ -492,53 +492,72 @@ __global__ __launch_bounds__(512, 4) void row_gemm_strip_kernel(const float* __r
 }
 
 constexpr int kDenseSlabs = 256;
+constexpr int kGenericSlabs = 64;        // row slabs of the any-width weight gradient (dense_weight_grad_generic_kernel)
 
-// in_typed / out_typed: the rows of every node type start at an address of their own (TypedRows; `in` / `out` are then ignored) - on the bf16-split kernels only
-int launch_row_gemm(int dim, const float* in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose,
-                    const float* bias, int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, float* out, int64_t ld_out, float* pk,
-                    hipStream_t s, const TypedRows* in_typed = nullptr, const TypedRowsOut* out_typed = nullptr, int accumulate = 0) {
+// The workspace of the node-level linear maps, in floats: packed weights [3][d][d] | kDenseSlabs weight slabs per type | their bias parts | the 16-bit weight planes of
+// the split kernels.  The any-width weight gradient keeps kGenericSlabs partials per type at the front instead (every width's workspace holds at least those).
+struct DenseWorkspace {
+    float *pk, *slabs, *bias_slabs, *planes;
+    float *gslabs, *gbias;               // any-width partials: weight part, bias part
+    int64_t floats, generic_floats;      // what a call needs / what its any-width branch needs
+};
+inline DenseWorkspace dense_workspace(void* workspace, int dim) {
+    const int64_t dd = static_cast<int64_t>(dim) * dim;
+    const int64_t o_slabs = 3 * dd, o_bias = o_slabs + 3LL * kDenseSlabs * dd, o_planes = o_bias + 3LL * kDenseSlabs * dim, o_gbias = 3LL * kGenericSlabs * dd;
+    const int64_t generic_floats = o_gbias + 3LL * kGenericSlabs * dim;
+    auto at = [&](int64_t offset) { return workspace != nullptr ? static_cast<float*>(workspace) + offset : nullptr; };       // (nullptr: the size query)
+    return {at(0), at(o_slabs), at(o_bias), at(o_planes), at(0), at(o_gbias), mfma_dim(dim) ? o_planes + split_dense_plane_floats(dim) : generic_floats, generic_floats};
+}
+
+// Rows of a row GEMM: typed rows (common.hpp) and, where they are ONE contiguous matrix, its base; base == nullptr: the rows of every node type start at an address of their own
+struct RowsIn { TypedRows rows; const float* base; };
+struct RowsOut { TypedRowsOut rows; float* base; };
+inline RowsIn rows_in(const float* base) { return {typed_rows(base), base}; }
+inline RowsOut rows_out(float* base) { return {typed_rows_out(base), base}; }
+template <typename Rows> inline bool rows_aligned16(const Rows& r) { return aligned16(r.p[0]) && aligned16(r.p[1]) && aligned16(r.p[2]); }
+
+template <int D, int ACT_OUT, int ACT_IN>
+void launch_row_gemm_tiled(const float* in, int64_t ld_in, const float* pk, int64_t pk_type_stride, const float* bias, int bias_mask, int64_t bias_type_stride,
+                           const TypePlan& plan, float* out, int64_t ld_out, const float* y, int64_t ld_y, hipStream_t s) {
+    hipLaunchKernelGGL((row_gemm_kernel<D, ACT_OUT, ACT_IN>), dim3(std::min(plan.tile_prefix[3], 256 * 4)), dim3(kBlockThreads), 0, s, in, ld_in, pk, pk_type_stride, bias, bias_mask,
+                       bias_type_stride, plan, out, ld_out, y, ld_y);
+}
+
+// pk, planes: the packed-weight and plane parts of the workspace (DenseWorkspace).  accumulate (out += ) and typed rows: on the narrow and the bf16-split kernels only
+int launch_row_gemm(int dim, const RowsIn& in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias, int bias_mask,
+                    int64_t bias_type_stride, const int64_t* type_begin, const RowsOut& out, int64_t ld_out, int accumulate, float* pk, void* planes, hipStream_t s) {
     const int n_types = w_type_stride == 0 ? 1 : 3;
-    const bool out_ok = out_typed != nullptr ? (aligned16(out_typed->p[0]) && aligned16(out_typed->p[1]) && aligned16(out_typed->p[2])) : aligned16(out);
-    const bool in_ok = in_typed != nullptr ? (aligned16(in_typed->p[0]) && aligned16(in_typed->p[1]) && aligned16(in_typed->p[2])) : aligned16(in);
-    if (narrow_linear_ok(dim, ld_in, ld_out) && in_ok && out_ok && (bias == nullptr || (aligned16(bias) && bias_type_stride % 4 == 0))) {      // d = 32 / 64: narrow.hip (fp32 MFMA, any arithmetic mode)
-        launch_row_gemm_narrow(dim, in_typed != nullptr ? *in_typed : typed_rows(in), ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin,
-                               out_typed != nullptr ? *out_typed : typed_rows_out(out), ld_out, accumulate, pk, s);
+    const bool in_ok = rows_aligned16(in.rows), out_ok = rows_aligned16(out.rows), bias_ok = bias == nullptr || (aligned16(bias) && bias_type_stride % 4 == 0);
+    if (narrow_linear_ok(dim, ld_in, ld_out) && in_ok && out_ok && bias_ok) {      // d = 32 / 64: narrow.hip (fp32 MFMA, any arithmetic mode)
+        launch_row_gemm_narrow(dim, in.rows, ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin, out.rows, ld_out, accumulate, pk, s);
         return IHG_OK;
     }
-    if (out_ok && split_row_gemm_ok(dim, nullptr, ld_out, bias, bias_type_stride)) {   // the bf16 planes sit behind the slabs (see ihg_node_linear_workspace_bytes)
-        void* planes = pk + 3LL * dim * dim + 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
-        launch_row_gemm_split(dim, in_typed != nullptr ? *in_typed : typed_rows(in), ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin,
-                              out_typed != nullptr ? *out_typed : typed_rows_out(out), ld_out, planes, s, accumulate, 0);
+    if (out_ok && split_row_gemm_ok(dim, nullptr, ld_out, bias, bias_type_stride)) {
+        launch_row_gemm_split(dim, in.rows, ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin, out.rows, ld_out, planes, s, accumulate, 0);
         return IHG_OK;
     }
     if (accumulate) return fail(IHG_ERR_INVALID, "node-level linear map accumulating into its output: needs the bf16-split kernels (dim 128 / 256, aligned rows)");
-    if (in_typed != nullptr || out_typed != nullptr) return fail(IHG_ERR_INVALID, "node-level linear map over typed rows: needs the bf16-split kernels (dim 128 / 256, aligned rows)");
-    if (dim == 128 && aligned16(out) && ld_out % 4 == 0 && (bias == nullptr || (aligned16(bias) && bias_type_stride % 4 == 0))) {
+    if (in.base == nullptr || out.base == nullptr) return fail(IHG_ERR_INVALID, "node-level linear map over typed rows: needs the bf16-split kernels (dim 128 / 256, aligned rows)");
+    const int64_t pk_type_stride = n_types == 1 ? int64_t{0} : static_cast<int64_t>(dim) * dim;
+    if (dim == 128 && out_ok && ld_out % 4 == 0 && bias_ok) {
         const int items = n_types * (dim / 16) * (dim / 16) * kWave;
         hipLaunchKernelGGL(pack_dense_strip_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride,
                            n_types, dim, transpose, pk);
         // tiles of 32 rows, two workgroups per CU (66 KB of LDS each): a pure stream over [N, d] wants bytes in flight more than big tiles
         const TypePlan plan = make_plan(type_begin, 32);
         if (plan.tile_prefix[3] == 0) return IHG_OK;
-        hipLaunchKernelGGL((row_gemm_strip_kernel<128, 32>), dim3(std::min(plan.tile_prefix[3], 512)), dim3(512), 0, s, in, ld_in, pk,
-                           n_types == 1 ? int64_t{0} : static_cast<int64_t>(dim) * dim, bias, bias_mask, bias_type_stride, plan, out, ld_out);
+        hipLaunchKernelGGL((row_gemm_strip_kernel<128, 32>), dim3(std::min(plan.tile_prefix[3], 512)), dim3(512), 0, s, in.base, ld_in, pk, pk_type_stride, bias, bias_mask,
+                           bias_type_stride, plan, out.base, ld_out);
         return IHG_OK;
     }
     const int pack_items = n_types * (dim / 32) * (dim / 8) * kWave;
     hipLaunchKernelGGL(pack_dense_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride,
                        n_types, dim, transpose, pk);
-    const int64_t pk_type_stride = n_types == 1 ? 0 : static_cast<int64_t>(dim) * dim;
     const TypePlan plan = make_plan(type_begin, dim == 32 ? 128 : 64);
     if (plan.tile_prefix[3] == 0) return IHG_OK;
-    const int grid = std::min(plan.tile_prefix[3], 256 * 4);
-#define IHG_RG(D) hipLaunchKernelGGL((row_gemm_kernel<D>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, pk_type_stride, bias, bias_mask, bias_type_stride, plan, out, ld_out, static_cast<const float*>(nullptr), int64_t{0})
-    switch (dim) {
-        case 32: IHG_RG(32); break;
-        case 64: IHG_RG(64); break;
-        case 128: IHG_RG(128); break;
-        default: IHG_RG(256); break;
-    }
-#undef IHG_RG
+    dispatch_width(dim, [&](auto width) {
+        launch_row_gemm_tiled<decltype(width)::value, 0, 0>(in.base, ld_in, pk, pk_type_stride, bias, bias_mask, bias_type_stride, plan, out.base, ld_out, nullptr, 0, s);
+    });
     return IHG_OK;
 }
 
@@ -672,7 +691,6 @@ __global__ __launch_bounds__(kBlockThreads) void row_gemm_generic_act_kernel(con
 // types); a workgroup walks its slab of the type's rows in chunks of 32 staged in LDS, thread (c, j) of the tile keeps one sum (rows in
 // index order); per-slab partials in dense_weight_grad_kernel's slab layout ([type][slab][d][d], bias part [type][slab][d]), added up in
 // slab order by dense_generic_reduce_kernel - deterministic, and N / slabs serial steps per thread instead of N.
-constexpr int kGenericSlabs = 64;
 constexpr int kGenericChunk = 32;
 
 template <int ACT>
@@ -756,14 +774,88 @@ inline bool tiled_node_linear(int dim, int64_t ld_a, int64_t ld_b, const void* a
     return mfma_dim(dim) && ld_a % 4 == 0 && ld_b % 4 == 0 && aligned16(a) && workspace != nullptr && aligned16(workspace);
 }
 
+inline int generic_row_grid(int64_t n_rows, int dim) { return static_cast<int>(std::min<int64_t>((n_rows * dim + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4)); }
+
 inline void launch_row_gemm_generic(int dim, const float* in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose,
                                     const float* bias, int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, float* out, int64_t ld_out,
                                     hipStream_t s) {
-    const TypePlan plan = make_plan(type_begin, 64);
-    const int64_t total = (type_begin[3] - type_begin[0]) * dim;
-    const int grid = static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
-    hipLaunchKernelGGL(row_gemm_generic_kernel, dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask,
-                       bias_type_stride, plan, out, ld_out, dim);
+    hipLaunchKernelGGL(row_gemm_generic_kernel, dim3(generic_row_grid(type_begin[3] - type_begin[0], dim)), dim3(kBlockThreads), 0, s, in, ld_in, w, ld_w, w_type_stride, transpose, bias,
+                       bias_mask, bias_type_stride, make_plan(type_begin, 64), out, ld_out, dim);
+}
+
+// the any-width row GEMM with an activation on either side (one weight, a table of n_rows rows): ACT_OUT on the way out of the forward, ACT_IN over y on the way into the input gradient
+template <int ACT_OUT, int ACT_IN>
+void launch_row_gemm_generic_act(int dim, int transpose, const float* in, int64_t ld_in, const float* y, int64_t ld_y, const float* w, int64_t ld_w, const float* bias,
+                                 const TypePlan& plan, float* out, int64_t ld_out, hipStream_t s) {
+    hipLaunchKernelGGL((row_gemm_generic_act_kernel<ACT_OUT, ACT_IN>), dim3(generic_row_grid(plan.begin[3], dim)), dim3(kBlockThreads), 0, s, in, ld_in, w, ld_w, transpose, bias, plan, out,
+                       ld_out, dim, y, ld_y);
+}
+
+// where a weight gradient goes: dw / dbias of n_types weight blocks (dw_type_stride == 0: one weight for every row)
+struct WeightGrad { int n_types; float* dw; int64_t ld_dw, dw_type_stride; float* dbias; int bias_mask; int64_t dbias_type_stride; };
+inline WeightGrad weight_grad(float* dw, int64_t ld_dw, int64_t dw_type_stride, float* dbias, int bias_mask, int64_t dbias_type_stride) {
+    return {dw_type_stride == 0 ? 1 : 3, dw, ld_dw, dw_type_stride, dbias, bias_mask, dw_type_stride == 0 ? int64_t{0} : dbias_type_stride};
+}
+
+inline void launch_slab_reduce(int dim, const float* slabs, const float* bias_slabs, int n_slabs, const WeightGrad& g, hipStream_t s) {
+    const int total = dim * dim * g.n_types + dim;
+    hipLaunchKernelGGL(dense_slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, bias_slabs, n_slabs, g.n_types, dim, g.dw, g.ld_dw, g.dw_type_stride,
+                       g.dbias, g.bias_mask, g.dbias_type_stride);
+}
+
+// The two fp32 weight-gradient sequences, once for the plain maps (ACT == 0: y unused) and the activation maps (ACT: dout stands for dout * act'(y), one weight).
+// Any width: row-slab partials at the front of the workspace, then a sum in slab order.
+template <int ACT>
+void launch_weight_grad_generic(int dim, const float* dout, int64_t ld_dout, const float* y, int64_t ld_y, const float* x, int64_t ld_x, const TypePlan& plan, const DenseWorkspace& ws,
+                                const WeightGrad& g, hipStream_t s) {
+    const int tiles = (dim + 15) / 16;
+    const dim3 grid(kGenericSlabs, tiles * tiles, g.n_types);
+    if constexpr (ACT == 0)
+        hipLaunchKernelGGL(dense_weight_grad_generic_kernel, grid, dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan, g.n_types == 1 ? 1 : 0, dim, ws.gslabs, ws.gbias);
+    else
+        hipLaunchKernelGGL((dense_weight_grad_generic_act_kernel<ACT>), grid, dim3(kBlockThreads), 0, s, dout, ld_dout, y, ld_y, x, ld_x, plan, dim, ws.gslabs, ws.gbias);
+    const int64_t total = static_cast<int64_t>(dim) * dim * g.n_types + dim;
+    hipLaunchKernelGGL(dense_generic_reduce_kernel, dim3(static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks))), dim3(kBlockThreads), 0, s, ws.gslabs,
+                       ws.gbias, kGenericSlabs, g.n_types, dim, g.dw, g.ld_dw, g.dw_type_stride, g.dbias, g.bias_mask, g.dbias_type_stride);
+}
+
+// Tiled widths: slabs of kDenseSlabs row ranges, (d / SW)^2 sub-blocks each; d = 64 with a dx forms the input gradient dx (+)= dout W_t from the dout tile that is in LDS
+// anyway, at every other width dx is the caller's to form
+template <int ACT>
+void launch_weight_grad_tiled(int dim, const float* dout, int64_t ld_dout, const float* y, int64_t ld_y, const float* x, int64_t ld_x, const TypePlan& plan, const DenseWorkspace& ws,
+                              int n_types, const float* w, int64_t ld_w, int64_t w_type_stride, float* dx, int64_t ld_dx, int dx_accumulate, hipStream_t s) {
+    auto launch = [&](auto sub_width, auto fuse_dx) {
+        constexpr int SW = decltype(sub_width)::value; constexpr bool FUSE_DX = decltype(fuse_dx)::value;
+        const dim3 grid(kDenseSlabs, (dim / SW) * (dim / SW), n_types);
+        if constexpr (ACT != 0)
+            hipLaunchKernelGGL((dense_weight_grad_act_kernel<SW, FUSE_DX, ACT>), grid, dim3(kBlockThreads), 0, s, dout, ld_dout, y, ld_y, x, ld_x, plan, ws.slabs, ws.bias_slabs, dim, w, ld_w,
+                               FUSE_DX ? dx : nullptr, ld_dx);
+        else if constexpr (FUSE_DX)
+            hipLaunchKernelGGL((dense_weight_grad_kernel<SW, true>), grid, dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan, n_types == 1 ? 1 : 0, ws.slabs, ws.bias_slabs, dim, w, ld_w,
+                               w_type_stride, dx, ld_dx, dx_accumulate);
+        else                                                 // (the plain kernel without the fused input gradient is told nothing about w and dx)
+            hipLaunchKernelGGL((dense_weight_grad_kernel<SW, false>), grid, dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan, n_types == 1 ? 1 : 0, ws.slabs, ws.bias_slabs, dim,
+                               static_cast<const float*>(nullptr), int64_t{0}, int64_t{0}, static_cast<float*>(nullptr), int64_t{0}, 0);
+    };
+    if (dim == 64 && dx != nullptr) launch(std::integral_constant<int, 64>{}, std::true_type{});
+    else if (dim == 32) launch(std::integral_constant<int, 32>{}, std::false_type{});
+    else launch(std::integral_constant<int, 64>{}, std::false_type{});
+}
+
+// the tiled row GEMM with an activation on either side: transpose == 0 is the forward (B = W^T, bias, ACT_OUT), transpose == 1 the input gradient (B = W, ACT_IN over y)
+void launch_row_gemm_act(int dim, int activation, int transpose, const float* in, int64_t ld_in, const float* y, int64_t ld_y, const float* w, int64_t ld_w,
+                         const float* bias, int64_t n_rows, float* out, int64_t ld_out, float* pk, hipStream_t s) {
+    const int pack_items = (dim / 32) * (dim / 8) * kWave;
+    hipLaunchKernelGGL(pack_dense_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, int64_t{0}, 1, dim, transpose, pk);
+    const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
+    const TypePlan plan = make_plan(type_begin, dim == 32 ? 128 : 64);
+    dispatch_width(dim, [&](auto width) {
+        dispatch_act(activation, [&](auto act) {
+            constexpr int D = decltype(width)::value, ACT = decltype(act)::value;
+            if (transpose == 0) launch_row_gemm_tiled<D, ACT, 0>(in, ld_in, pk, 0, bias, 0b111, 0, plan, out, ld_out, y, ld_y, s);
+            else launch_row_gemm_tiled<D, 0, ACT>(in, ld_in, pk, 0, bias, 0b111, 0, plan, out, ld_out, y, ld_y, s);
+        });
+    });
 }
 
 }  // namespace
@@ -771,11 +863,7 @@ inline void launch_row_gemm_generic(int dim, const float* in, int64_t ld_in, con
 extern "C" {
 
 int64_t ihg_node_linear_workspace_bytes(int32_t dim) {
-    if (dim <= 0) return -1;
-    if (!mfma_dim(dim)) return 3LL * kGenericSlabs * (static_cast<int64_t>(dim) * dim + dim) * static_cast<int64_t>(sizeof(float));      // any-width kernels: row-slab partials only
-    const int64_t packed = 3LL * dim * dim;
-    const int64_t slabs = 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
-    return (packed + slabs + split_dense_plane_floats(dim)) * static_cast<int64_t>(sizeof(float));
+    return dim <= 0 ? -1 : dense_workspace(nullptr, dim).floats * static_cast<int64_t>(sizeof(float));
 }
 
 static int node_linear_common_check(const char* what, int32_t dim, int64_t ld_a, int64_t ld_b, int64_t ld_w, const int64_t* type_begin,
@@ -790,33 +878,39 @@ static int node_linear_common_check(const char* what, int32_t dim, int64_t ld_a,
     return IHG_OK;
 }
 
+// out = in W_t^T + bias (transpose == 0) or in W_t (transpose == 1) behind the three row-GEMM entry points, which have done their checks: the tiled kernels or the any-width one
+static int node_linear_rows(const char* what, bool tiled, int dim, const RowsIn& in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias,
+                            int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, const RowsOut& out, int64_t ld_out, void* workspace, ihg_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (tiled) {
+        const DenseWorkspace ws = dense_workspace(workspace, dim);
+        if (int rc = launch_row_gemm(dim, in, ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin, out, ld_out, 0, ws.pk, ws.planes, s)) return rc;
+    } else {
+        launch_row_gemm_generic(dim, in.base, ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin, out.base, ld_out, s);
+    }
+    return check_launch(what);
+}
+
+// the two entry points over ONE contiguous matrix: the forward (transpose == 0) and the input gradient (transpose == 1, no bias)
+static int node_linear_matrix(const char* what, const float* in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias, int bias_mask,
+                              int64_t bias_type_stride, const int64_t* type_begin, float* out, int64_t ld_out, void* workspace, int64_t workspace_bytes, int dim, ihg_stream_t stream) {
+    if (int rc = node_linear_common_check(what, dim, ld_in, ld_out, ld_w, type_begin, workspace, workspace_bytes)) return rc;
+    if (type_begin[3] == type_begin[0]) return IHG_OK;
+    if (in == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    return node_linear_rows(what, tiled_node_linear(dim, ld_in, ld_out, in, workspace), dim, rows_in(in), ld_in, w, ld_w, w_type_stride, transpose, bias, bias_mask, bias_type_stride, type_begin,
+                            rows_out(out), ld_out, workspace, stream);
+}
+
 int ihg_node_linear_fwd(const float* x, int64_t ld_x, const float* w, int64_t ld_w, int64_t w_type_stride, const float* bias,
                         int32_t bias_type_mask, int64_t bias_type_stride, const int64_t* type_begin, float* out, int64_t ld_out, void* workspace,
                         int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (int rc = node_linear_common_check("ihg_node_linear_fwd", dim, ld_x, ld_out, ld_w, type_begin, workspace, workspace_bytes)) return rc;
-    if (type_begin[3] == type_begin[0]) return IHG_OK;
-    if (x == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_linear_fwd: null pointer");
-    if (tiled_node_linear(dim, ld_x, ld_out, x, workspace))
-        launch_row_gemm(dim, x, ld_x, w, ld_w, w_type_stride, 0, bias, bias_type_mask, bias_type_stride, type_begin, out, ld_out,
-                        static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    else
-        launch_row_gemm_generic(dim, x, ld_x, w, ld_w, w_type_stride, 0, bias, bias_type_mask, bias_type_stride, type_begin, out, ld_out,
-                                static_cast<hipStream_t>(stream));
-    return check_launch("ihg_node_linear_fwd");
+    return node_linear_matrix("ihg_node_linear_fwd", x, ld_x, w, ld_w, w_type_stride, 0, bias, bias_type_mask, bias_type_stride, type_begin, out, ld_out, workspace, workspace_bytes, dim, stream);
 }
 
 int ihg_node_linear_bwd_input(const float* dout, int64_t ld_dout, const float* w, int64_t ld_w, int64_t w_type_stride,
                               const int64_t* type_begin, float* dx, int64_t ld_dx, void* workspace, int64_t workspace_bytes,
                               int32_t dim, ihg_stream_t stream) {
-    if (int rc = node_linear_common_check("ihg_node_linear_bwd_input", dim, ld_dout, ld_dx, ld_w, type_begin, workspace, workspace_bytes)) return rc;
-    if (type_begin[3] == type_begin[0]) return IHG_OK;
-    if (dout == nullptr || w == nullptr || dx == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_input: null pointer");
-    if (tiled_node_linear(dim, ld_dout, ld_dx, dout, workspace))
-        launch_row_gemm(dim, dout, ld_dout, w, ld_w, w_type_stride, 1, nullptr, 0, 0, type_begin, dx, ld_dx, static_cast<float*>(workspace),
-                        static_cast<hipStream_t>(stream));
-    else
-        launch_row_gemm_generic(dim, dout, ld_dout, w, ld_w, w_type_stride, 1, nullptr, 0, 0, type_begin, dx, ld_dx, static_cast<hipStream_t>(stream));
-    return check_launch("ihg_node_linear_bwd_input");
+    return node_linear_matrix("ihg_node_linear_bwd_input", dout, ld_dout, w, ld_w, w_type_stride, 1, nullptr, 0, 0, type_begin, dx, ld_dx, workspace, workspace_bytes, dim, stream);
 }
 
 int32_t ihg_node_linear_bwd_accumulates(int32_t dim, int64_t ld_dout, int64_t ld_x, int64_t ld_dx) {
@@ -825,81 +919,65 @@ int32_t ihg_node_linear_bwd_accumulates(int32_t dim, int64_t ld_dout, int64_t ld
     return dim == 64 || dim == kNarrowDim || ((dim == 128 || dim == 256) && split_arith_enabled()) ? 1 : 0;       // (d = 256: the input gradient is a row-GEMM launch of its own, which adds onto dx)
 }
 
+// The weight / bias gradient on the narrow (d = 32 / 64) or the bf16-split (d = 128 / 256) kernels behind the two weight-gradient entry points, which have done their checks.
+// dx (nullptr: none): the input gradient of the same rows - from the same pass over dout on the narrow kernels and, fused_dx, at d = 128; a row-GEMM launch of its own otherwise.
+static int node_linear_weight(const char* what, bool narrow, bool fused_dx, int dim, const float* dout, int64_t ld_dout, const TypedRows& x, int64_t ld_x, const int64_t* type_begin,
+                              const WeightGrad& g, const float* w, int64_t ld_w, const RowsOut* dx, int64_t ld_dx, int dx_accumulate, void* workspace, hipStream_t s) {
+    const DenseWorkspace ws = dense_workspace(workspace, dim);
+    int n_slabs;
+    // weights of type t are the column block t of w exactly as for dw: w_type_stride == dw_type_stride
+    if (narrow) {
+        n_slabs = launch_dense_weight_narrow(dim, dout, ld_dout, x, ld_x, type_begin, g.n_types, ws.slabs, ws.bias_slabs, w, ld_w, g.dw_type_stride, dx != nullptr ? &dx->rows : nullptr, ld_dx,
+                                             dx_accumulate, ws.pk, s);
+    } else {
+        if (dx != nullptr && !fused_dx) {
+            if (int rc = launch_row_gemm(dim, rows_in(dout), ld_dout, w, ld_w, g.dw_type_stride, 1, nullptr, 0, 0, type_begin, *dx, ld_dx, dx_accumulate, ws.pk, ws.planes, s)) return rc;
+        }
+        n_slabs = launch_dense_weight_split(dim, dout, ld_dout, x, ld_x, type_begin, g.n_types, ws.slabs, ws.bias_slabs, w, ld_w, g.dw_type_stride, fused_dx ? &dx->rows : nullptr, ld_dx,
+                                            ws.planes, s, fused_dx ? dx_accumulate : 0);
+    }
+    launch_slab_reduce(dim, ws.slabs, ws.bias_slabs, n_slabs, g, s);
+    return check_launch(what);
+}
+
 int ihg_node_linear_bwd_weight(const float* dout, int64_t ld_dout, const float* x, int64_t ld_x, const int64_t* type_begin,
                                float* dw, int64_t ld_dw, int64_t dw_type_stride, float* dbias, int32_t bias_type_mask, int64_t dbias_type_stride,
                                const float* w, int64_t ld_w, float* dx, int64_t ld_dx, int32_t dx_accumulate,
                                void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (int rc = node_linear_common_check("ihg_node_linear_bwd_weight", dim, ld_dout, ld_x, ld_dw, type_begin, workspace, workspace_bytes)) return rc;
-    if (dout == nullptr || x == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight: null pointer");
-    if (dx != nullptr && (w == nullptr || ld_w < dim || ld_dx < dim)) return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight: dx needs w and row strides >= dim");
+    const char* what = "ihg_node_linear_bwd_weight";
+    if (int rc = node_linear_common_check(what, dim, ld_dout, ld_x, ld_dw, type_begin, workspace, workspace_bytes)) return rc;
+    if (dout == nullptr || x == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    if (dx != nullptr && (w == nullptr || ld_w < dim || ld_dx < dim)) return fail(IHG_ERR_INVALID, "%s: dx needs w and row strides >= dim", what);
     if (dx_accumulate && (dx == nullptr || !ihg_node_linear_bwd_accumulates(dim, ld_dout, ld_x, ld_dx)))
-        return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight: dx_accumulate needs dx and a fused input-gradient kernel (ihg_node_linear_bwd_accumulates)");
+        return fail(IHG_ERR_INVALID, "%s: dx_accumulate needs dx and a fused input-gradient kernel (ihg_node_linear_bwd_accumulates)", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n_types = dw_type_stride == 0 ? 1 : 3;
+    const WeightGrad g = weight_grad(dw, ld_dw, dw_type_stride, dbias, bias_type_mask, dbias_type_stride);
+    const DenseWorkspace ws = dense_workspace(workspace, dim);
+    const TypePlan plan = make_plan(type_begin, 64);
     if (!tiled_node_linear(dim, ld_dout, ld_x, dout, workspace) || !aligned16(x) || (dx != nullptr && ld_dx % 4)) {
         // the any-width kernels OVERWRITE dx: a caller that asked for dx += (the member gradients are already in it) on rows this branch takes - unaligned dout / x
         // at a width ihg_node_linear_bwd_accumulates said yes to - is refused, not silently given a dx without its first addend
-        if (dx_accumulate) return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight: dx_accumulate needs 16-byte aligned dout and x rows (the any-width kernels overwrite dx)");
+        if (dx_accumulate) return fail(IHG_ERR_INVALID, "%s: dx_accumulate needs 16-byte aligned dout and x rows (the any-width kernels overwrite dx)", what);
+        if (workspace == nullptr || workspace_bytes < ws.generic_floats * static_cast<int64_t>(sizeof(float))) return fail(IHG_ERR_WORKSPACE, "%s: workspace too small (any-width path)", what);
         if (dx != nullptr) launch_row_gemm_generic(dim, dout, ld_dout, w, ld_w, dw_type_stride, 1, nullptr, 0, 0, type_begin, dx, ld_dx, s);
-        // row-slab partials at the front of the workspace (every width's workspace holds at least kGenericSlabs of them), then a fixed-order sum
-        const int64_t need = 3LL * kGenericSlabs * (static_cast<int64_t>(dim) * dim + dim) * static_cast<int64_t>(sizeof(float));
-        if (workspace == nullptr || workspace_bytes < need) return fail(IHG_ERR_WORKSPACE, "ihg_node_linear_bwd_weight: workspace too small (any-width path)");
-        float* gslabs = static_cast<float*>(workspace);
-        float* gbias = gslabs + 3LL * kGenericSlabs * dim * dim;
-        const int tiles = (dim + 15) / 16;
-        hipLaunchKernelGGL(dense_weight_grad_generic_kernel, dim3(kGenericSlabs, tiles * tiles, n_types), dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x,
-                           make_plan(type_begin, 64), n_types == 1 ? 1 : 0, dim, gslabs, gbias);
-        const int64_t total = static_cast<int64_t>(dim) * dim * n_types + dim;
-        hipLaunchKernelGGL(dense_generic_reduce_kernel, dim3(static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks))),
-                           dim3(kBlockThreads), 0, s, gslabs, gbias, kGenericSlabs, n_types, dim, dw, ld_dw, dw_type_stride, dbias, bias_type_mask,
-                           n_types == 1 ? int64_t{0} : dbias_type_stride);
-        return check_launch("ihg_node_linear_bwd_weight");
+        launch_weight_grad_generic<0>(dim, dout, ld_dout, nullptr, 0, x, ld_x, plan, ws, g, s);
+        return check_launch(what);
     }
-    float* slabs = static_cast<float*>(workspace) + 3LL * dim * dim;
-    float* bias_slabs = slabs + 3LL * kDenseSlabs * dim * dim;
-    const TypePlan plan = make_plan(type_begin, 64);
-    // weights of type t are the column block t of w exactly as for dw: w_type_stride == dw_type_stride
-    int n_slabs = kDenseSlabs;
-    if (narrow_linear_ok(dim, ld_dout, ld_x) && aligned16(dout) && (dx == nullptr || (aligned16(dx) && aligned16(w) && ld_w % 4 == 0))) {
+    const RowsOut dx_rows = rows_out(dx);
+    if (narrow_linear_ok(dim, ld_dout, ld_x) && aligned16(dout) && (dx == nullptr || (aligned16(dx) && aligned16(w) && ld_w % 4 == 0)))
         // d = 32 / 64: weight, bias and input gradient in one pass over (dout, x) (narrow.hip)
-        const TypedRowsOut dx_rows = typed_rows_out(dx);
-        n_slabs = launch_dense_weight_narrow(dim, dout, ld_dout, typed_rows(x), ld_x, type_begin, n_types, slabs, bias_slabs, w, ld_w, dw_type_stride, dx != nullptr ? &dx_rows : nullptr, ld_dx,
-                                             dx_accumulate, static_cast<float*>(workspace), s);
-    } else if (dx_accumulate && dim == kNarrowDim) {
-        return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight: dx_accumulate at dim 32 needs 16-byte aligned rows");
-    } else if (split_dense_weight_ok(dim, dout, ld_dout, x, ld_x)) {             // bf16-split contraction (d = 128, 256); the input gradient stays a row-GEMM launch
+        return node_linear_weight(what, true, false, dim, dout, ld_dout, typed_rows(x), ld_x, type_begin, g, w, ld_w, dx != nullptr ? &dx_rows : nullptr, ld_dx, dx_accumulate, workspace, s);
+    if (dx_accumulate && dim == kNarrowDim) return fail(IHG_ERR_INVALID, "%s: dx_accumulate at dim 32 needs 16-byte aligned rows", what);
+    if (split_dense_weight_ok(dim, dout, ld_dout, x, ld_x)) {                     // bf16-split contraction (d = 128, 256)
         const bool fused_dx = dx != nullptr && dim == 128 && aligned16(dx) && ld_dx % 4 == 0;
-        if (dx_accumulate && !fused_dx && !(dim == 256 && aligned16(dx) && ld_dx % 4 == 0))
-            return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight: dx_accumulate needs 16-byte aligned dx rows");
-        if (dx != nullptr && !fused_dx) {
-            if (int rc = launch_row_gemm(dim, dout, ld_dout, w, ld_w, dw_type_stride, 1, nullptr, 0, 0, type_begin, dx, ld_dx, static_cast<float*>(workspace), s, nullptr, nullptr, dx_accumulate)) return rc;
-        }
-        void* planes = static_cast<float*>(workspace) + 3LL * dim * dim + 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
-        const TypedRowsOut dx_rows = typed_rows_out(dx);
-        n_slabs = launch_dense_weight_split(dim, dout, ld_dout, typed_rows(x), ld_x, type_begin, n_types, slabs, bias_slabs, w, ld_w, dw_type_stride, fused_dx ? &dx_rows : nullptr, ld_dx,
-                                            planes, s, fused_dx ? dx_accumulate : 0);
-    } else if (dim == 64 && dx != nullptr) {
-        hipLaunchKernelGGL((dense_weight_grad_kernel<64, true>), dim3(kDenseSlabs, 1, n_types), dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                           n_types == 1 ? 1 : 0, slabs, bias_slabs, dim, w, ld_w, dw_type_stride, dx, ld_dx, dx_accumulate);
-    } else {
-        if (dx != nullptr) {                               // other widths: the row-GEMM pass over dout stays a launch of its own
-            launch_row_gemm(dim, dout, ld_dout, w, ld_w, dw_type_stride, 1, nullptr, 0, 0, type_begin, dx, ld_dx, static_cast<float*>(workspace), s);
-        }
-        if (dim == 32) {
-            hipLaunchKernelGGL((dense_weight_grad_kernel<32, false>), dim3(kDenseSlabs, 1, n_types), dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                               n_types == 1 ? 1 : 0, slabs, bias_slabs, dim, static_cast<const float*>(nullptr), int64_t{0}, int64_t{0},
-                               static_cast<float*>(nullptr), int64_t{0}, 0);
-        } else {
-            const int subs = (dim / 64) * (dim / 64);
-            hipLaunchKernelGGL((dense_weight_grad_kernel<64, false>), dim3(kDenseSlabs, subs, n_types), dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                               n_types == 1 ? 1 : 0, slabs, bias_slabs, dim, static_cast<const float*>(nullptr), int64_t{0}, int64_t{0},
-                               static_cast<float*>(nullptr), int64_t{0}, 0);
-        }
+        if (dx_accumulate && !fused_dx && !(dim == 256 && aligned16(dx) && ld_dx % 4 == 0)) return fail(IHG_ERR_INVALID, "%s: dx_accumulate needs 16-byte aligned dx rows", what);
+        return node_linear_weight(what, false, fused_dx, dim, dout, ld_dout, typed_rows(x), ld_x, type_begin, g, w, ld_w, dx != nullptr ? &dx_rows : nullptr, ld_dx, dx_accumulate, workspace, s);
     }
-    const int total = dim * dim * n_types + dim;
-    hipLaunchKernelGGL(dense_slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, bias_slabs,
-                       n_slabs, n_types, dim, dw, ld_dw, dw_type_stride, dbias, bias_type_mask, n_types == 1 ? int64_t{0} : dbias_type_stride);
-    return check_launch("ihg_node_linear_bwd_weight");
+    // fp32 MFMA (IHG_INTERACT_ARITH=f32, or d = 32 / 64 rows the narrow kernels do not take): d = 64 forms dx in the weight-gradient kernel, elsewhere it is a row-GEMM launch of its own
+    if (dx != nullptr && dim != 64) launch_row_gemm(dim, rows_in(dout), ld_dout, w, ld_w, dw_type_stride, 1, nullptr, 0, 0, type_begin, dx_rows, ld_dx, 0, ws.pk, ws.planes, s);
+    launch_weight_grad_tiled<0>(dim, dout, ld_dout, nullptr, 0, x, ld_x, plan, ws, g.n_types, w, ld_w, dw_type_stride, dx, ld_dx, dx_accumulate, s);
+    launch_slab_reduce(dim, ws.slabs, ws.bias_slabs, kDenseSlabs, g, s);
+    return check_launch(what);
 }
 
 int32_t ihg_node_linear_typed_supported(int32_t dim, int64_t ld_x, int64_t ld_out) {
@@ -909,63 +987,45 @@ int32_t ihg_node_linear_typed_supported(int32_t dim, int64_t ld_x, int64_t ld_ou
 int ihg_node_linear_fwd_typed(const float* const* x_rows, int64_t ld_x, const float* w, int64_t ld_w, int64_t w_type_stride, const float* bias,
                               int32_t bias_type_mask, int64_t bias_type_stride, const int64_t* type_begin, float* out, int64_t ld_out, void* workspace,
                               int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (int rc = node_linear_common_check("ihg_node_linear_fwd_typed", dim, ld_x, ld_out, ld_w, type_begin, workspace, workspace_bytes)) return rc;
+    const char* what = "ihg_node_linear_fwd_typed";
+    if (int rc = node_linear_common_check(what, dim, ld_x, ld_out, ld_w, type_begin, workspace, workspace_bytes)) return rc;
     if (type_begin[3] == type_begin[0]) return IHG_OK;
-    if (x_rows == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_linear_fwd_typed: null pointer");
+    if (x_rows == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
     for (int t = 0; t < 3; ++t)
-        if (type_begin[t + 1] > type_begin[t] && (x_rows[t] == nullptr || !aligned16(x_rows[t]))) return fail(IHG_ERR_INVALID, "ihg_node_linear_fwd_typed: rows of type %d null or not 16-byte aligned", t);
+        if (type_begin[t + 1] > type_begin[t] && (x_rows[t] == nullptr || !aligned16(x_rows[t]))) return fail(IHG_ERR_INVALID, "%s: rows of type %d null or not 16-byte aligned", what, t);
     if (!ihg_node_linear_typed_supported(dim, ld_x, ld_out) || workspace == nullptr || !aligned16(workspace))
-        return fail(IHG_ERR_INVALID, "ihg_node_linear_fwd_typed: not available for this shape (ihg_node_linear_typed_supported)");
-    const TypedRows in = typed_rows(x_rows, type_begin, ld_x);
-    if (int rc = launch_row_gemm(dim, nullptr, ld_x, w, ld_w, w_type_stride, 0, bias, bias_type_mask, bias_type_stride, type_begin, out, ld_out, static_cast<float*>(workspace),
-                                 static_cast<hipStream_t>(stream), &in, nullptr))
-        return rc;
-    return check_launch("ihg_node_linear_fwd_typed");
+        return fail(IHG_ERR_INVALID, "%s: not available for this shape (ihg_node_linear_typed_supported)", what);
+    return node_linear_rows(what, true, dim, RowsIn{typed_rows(x_rows, type_begin, ld_x), nullptr}, ld_x, w, ld_w, w_type_stride, 0, bias, bias_type_mask, bias_type_stride, type_begin,
+                            rows_out(out), ld_out, workspace, stream);
 }
 
 int ihg_node_linear_bwd_weight_typed(const float* dout, int64_t ld_dout, const float* const* x_rows, int64_t ld_x, const int64_t* type_begin,
                                      float* dw, int64_t ld_dw, int64_t dw_type_stride, float* dbias, int32_t bias_type_mask, int64_t dbias_type_stride,
                                      const float* w, int64_t ld_w, float* const* dx_rows, int64_t ld_dx, int32_t zero_row_before_mask,
                                      void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (int rc = node_linear_common_check("ihg_node_linear_bwd_weight_typed", dim, ld_dout, ld_x, ld_dw, type_begin, workspace, workspace_bytes)) return rc;
-    if (dout == nullptr || x_rows == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight_typed: null pointer");
-    if (dx_rows != nullptr && (w == nullptr || ld_w < dim || ld_dx < dim)) return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight_typed: dx needs w and row strides >= dim");
+    const char* what = "ihg_node_linear_bwd_weight_typed";
+    if (int rc = node_linear_common_check(what, dim, ld_dout, ld_x, ld_dw, type_begin, workspace, workspace_bytes)) return rc;
+    if (dout == nullptr || x_rows == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    if (dx_rows != nullptr && (w == nullptr || ld_w < dim || ld_dx < dim)) return fail(IHG_ERR_INVALID, "%s: dx needs w and row strides >= dim", what);
     for (int t = 0; t < 3; ++t) {
         if (type_begin[t + 1] == type_begin[t]) continue;
         if (x_rows[t] == nullptr || !aligned16(x_rows[t]) || (dx_rows != nullptr && (dx_rows[t] == nullptr || !aligned16(dx_rows[t]))))
-            return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight_typed: rows of type %d null or not 16-byte aligned", t);
+            return fail(IHG_ERR_INVALID, "%s: rows of type %d null or not 16-byte aligned", what, t);
     }
     const bool narrow = narrow_linear_ok(dim, ld_dout, ld_x) && aligned16(dout) && (dx_rows == nullptr || (aligned16(w) && ld_w % 4 == 0 && ld_dx % 4 == 0));
     if (!ihg_node_linear_typed_supported(dim, ld_x, dx_rows != nullptr ? ld_dx : ld_x) || (!narrow && !split_dense_weight_ok(dim, dout, ld_dout, x_rows[0], ld_x)) || workspace == nullptr ||
         !aligned16(workspace))
-        return fail(IHG_ERR_INVALID, "ihg_node_linear_bwd_weight_typed: not available for this shape (ihg_node_linear_typed_supported)");
+        return fail(IHG_ERR_INVALID, "%s: not available for this shape (ihg_node_linear_typed_supported)", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n_types = dw_type_stride == 0 ? 1 : 3;
-    float* slabs = static_cast<float*>(workspace) + 3LL * dim * dim;
-    float* bias_slabs = slabs + 3LL * kDenseSlabs * dim * dim;
-    void* planes = static_cast<float*>(workspace) + 3LL * dim * dim + 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
-    const TypedRows xin = typed_rows(x_rows, type_begin, ld_x);
-    TypedRowsOut dxo = typed_rows_out(nullptr);
+    RowsOut dx{};
     if (dx_rows != nullptr) {
-        dxo = typed_rows_out(dx_rows, type_begin, ld_dx);
+        dx.rows = typed_rows_out(dx_rows, type_begin, ld_dx);
         // gradient tables with a padding row in front of a type's rows (row 0 of the [U + 1, d] / [I + 1, d] embedding tables, Models/EmbeddingLayers.py:33-35): zeroed here
         for (int t = 0; t < 3; ++t)
             if ((zero_row_before_mask >> t) & 1) launch_zero_floats(dx_rows[t] - ld_dx, dim, s);
     }
-    const bool fused_dx = dx_rows != nullptr && dim == 128;
-    int n_slabs = 0;
-    if (narrow) {
-        n_slabs = launch_dense_weight_narrow(dim, dout, ld_dout, xin, ld_x, type_begin, n_types, slabs, bias_slabs, w, ld_w, dw_type_stride, dx_rows != nullptr ? &dxo : nullptr, ld_dx, 0, static_cast<float*>(workspace), s);
-    } else {
-        if (dx_rows != nullptr && !fused_dx) {
-            if (int rc = launch_row_gemm(dim, dout, ld_dout, w, ld_w, dw_type_stride, 1, nullptr, 0, 0, type_begin, nullptr, ld_dx, static_cast<float*>(workspace), s, nullptr, &dxo)) return rc;
-        }
-        n_slabs = launch_dense_weight_split(dim, dout, ld_dout, xin, ld_x, type_begin, n_types, slabs, bias_slabs, w, ld_w, dw_type_stride, fused_dx ? &dxo : nullptr, ld_dx, planes, s, 0);
-    }
-    const int total = dim * dim * n_types + dim;
-    hipLaunchKernelGGL(dense_slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, bias_slabs,
-                       n_slabs, n_types, dim, dw, ld_dw, dw_type_stride, dbias, bias_type_mask, n_types == 1 ? int64_t{0} : dbias_type_stride);
-    return check_launch("ihg_node_linear_bwd_weight_typed");
+    return node_linear_weight(what, narrow, dx_rows != nullptr && dim == 128, dim, dout, ld_dout, typed_rows(x_rows, type_begin, ld_x), ld_x, type_begin,
+                              weight_grad(dw, ld_dw, dw_type_stride, dbias, bias_type_mask, dbias_type_stride), w, ld_w, dx_rows != nullptr ? &dx : nullptr, ld_dx, 0, workspace, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -983,116 +1043,60 @@ static int rows_linear_act_check(const char* what, int32_t dim, int32_t activati
     return IHG_OK;
 }
 
-// the tiled row GEMM with an activation on either side: transpose == 0 is the forward (B = W^T, bias, ACT_OUT), transpose == 1 the input gradient (B = W, ACT_IN over y)
-static void launch_row_gemm_act(int dim, int activation, int transpose, const float* in, int64_t ld_in, const float* y, int64_t ld_y, const float* w, int64_t ld_w,
-                                const float* bias, int64_t n_rows, float* out, int64_t ld_out, float* pk, hipStream_t s) {
-    const int pack_items = (dim / 32) * (dim / 8) * kWave;
-    hipLaunchKernelGGL(pack_dense_kernel, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, int64_t{0}, 1, dim, transpose, pk);
-    const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
-    const TypePlan plan = make_plan(type_begin, dim == 32 ? 128 : 64);
-    const int grid = std::min(plan.tile_prefix[3], 256 * 4);
-#define IHG_RGA(D, AO, AI) hipLaunchKernelGGL((row_gemm_kernel<D, AO, AI>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, int64_t{0}, bias, 0b111, int64_t{0}, plan, out, ld_out, y, ld_y)
-#define IHG_RGA_D(D)                                             \
-    if (transpose == 0) {                                        \
-        if (activation == IHG_ACT_RELU) IHG_RGA(D, 1, 0);        \
-        else IHG_RGA(D, 2, 0);                                   \
-    } else {                                                     \
-        if (activation == IHG_ACT_RELU) IHG_RGA(D, 0, 1);        \
-        else IHG_RGA(D, 0, 2);                                   \
-    }
-    switch (dim) {
-        case 32: IHG_RGA_D(32); break;
-        case 64: IHG_RGA_D(64); break;
-        case 128: IHG_RGA_D(128); break;
-        default: IHG_RGA_D(256); break;
-    }
-#undef IHG_RGA_D
-#undef IHG_RGA
-}
-
 int ihg_rows_linear_act_fwd(const float* x, int64_t ld_x, const float* w, int64_t ld_w, const float* bias, int32_t activation, float* out, int64_t ld_out,
                             int64_t n_rows, void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream) {
-    if (int rc = rows_linear_act_check("ihg_rows_linear_act_fwd", dim, activation, n_rows, ld_x, ld_out, ld_w, workspace, workspace_bytes)) return rc;
+    const char* what = "ihg_rows_linear_act_fwd";
+    if (int rc = rows_linear_act_check(what, dim, activation, n_rows, ld_x, ld_out, ld_w, workspace, workspace_bytes)) return rc;
     if (n_rows == 0) return IHG_OK;
-    if (x == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_fwd: null pointer");
+    if (x == nullptr || w == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const DenseWorkspace ws = dense_workspace(workspace, dim);
+    const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
     if (ld_x % 4 == 0 && aligned16(x) && split_row_gemm_ok(dim, out, ld_out, bias, 0)) {
-        // d = 128 / 256 in the split arithmetic (the default): the node-level maps' own row GEMM - two fp16 terms per operand - with the activation in its epilogue;
-        // its planes sit behind the slabs, as in launch_row_gemm.  IHG_INTERACT_ARITH=f32, or an `out` that is not 16-byte aligned: the fp32-MFMA kernel below
-        const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
-        void* planes = static_cast<float*>(workspace) + 3LL * dim * dim + 3LL * kDenseSlabs * (static_cast<int64_t>(dim) * dim + dim);
-        launch_row_gemm_split(dim, typed_rows(x), ld_x, w, ld_w, 0, 0, bias, 0b111, 0, type_begin, typed_rows_out(out), ld_out, planes, s, 0, activation);
+        // d = 128 / 256 in the split arithmetic (the default): the node-level maps' own row GEMM - two fp16 terms per operand - with the activation in its epilogue.
+        // IHG_INTERACT_ARITH=f32, or an `out` that is not 16-byte aligned: the fp32-MFMA kernel below
+        launch_row_gemm_split(dim, typed_rows(x), ld_x, w, ld_w, 0, 0, bias, 0b111, 0, type_begin, typed_rows_out(out), ld_out, ws.planes, s, 0, activation);
     } else if (mfma_dim(dim) && ld_x % 4 == 0 && aligned16(x)) {   // (this kernel stores single floats: any out, any ld_out - a column slice of the feature matrix)
-        launch_row_gemm_act(dim, activation, 0, x, ld_x, nullptr, 0, w, ld_w, bias, n_rows, out, ld_out, static_cast<float*>(workspace), s);
+        launch_row_gemm_act(dim, activation, 0, x, ld_x, nullptr, 0, w, ld_w, bias, n_rows, out, ld_out, ws.pk, s);
     } else {
-        const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
         const TypePlan plan = make_plan(type_begin, 64);
-        const int grid = static_cast<int>(std::min<int64_t>((n_rows * dim + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
-        if (activation == IHG_ACT_RELU)
-            hipLaunchKernelGGL((row_gemm_generic_act_kernel<1, 0>), dim3(grid), dim3(kBlockThreads), 0, s, x, ld_x, w, ld_w, 0, bias, plan, out, ld_out, dim, static_cast<const float*>(nullptr), int64_t{0});
-        else
-            hipLaunchKernelGGL((row_gemm_generic_act_kernel<2, 0>), dim3(grid), dim3(kBlockThreads), 0, s, x, ld_x, w, ld_w, 0, bias, plan, out, ld_out, dim, static_cast<const float*>(nullptr), int64_t{0});
+        dispatch_act(activation, [&](auto act) { launch_row_gemm_generic_act<decltype(act)::value, 0>(dim, 0, x, ld_x, nullptr, 0, w, ld_w, bias, plan, out, ld_out, s); });
     }
-    return check_launch("ihg_rows_linear_act_fwd");
+    return check_launch(what);
 }
 
 int ihg_rows_linear_act_bwd(const float* dy, int64_t ld_dy, const float* y, int64_t ld_y, const float* x, int64_t ld_x, const float* w, int64_t ld_w, int32_t activation,
                             float* dw, int64_t ld_dw, float* dbias, float* dx, int64_t ld_dx, int64_t n_rows, void* workspace, int64_t workspace_bytes, int32_t dim,
                             ihg_stream_t stream) {
-    if (int rc = rows_linear_act_check("ihg_rows_linear_act_bwd", dim, activation, n_rows, ld_dy, ld_x, ld_w, workspace, workspace_bytes)) return rc;
-    if (ld_y < dim || ld_dw < dim || (dx != nullptr && ld_dx < dim)) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_bwd: bad leading dimension");
+    const char* what = "ihg_rows_linear_act_bwd";
+    if (int rc = rows_linear_act_check(what, dim, activation, n_rows, ld_dy, ld_x, ld_w, workspace, workspace_bytes)) return rc;
+    if (ld_y < dim || ld_dw < dim || (dx != nullptr && ld_dx < dim)) return fail(IHG_ERR_INVALID, "%s: bad leading dimension", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n_rows == 0) {                                             // no rows (empty tensors come with null pointers): dW = 0, db = 0, nothing to write to dx
-        if (dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_bwd: null pointer");
+        if (dw == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
         for (int c = 0; c < dim; ++c) launch_zero_floats(dw + static_cast<int64_t>(c) * ld_dw, dim, s);
         if (dbias != nullptr) launch_zero_floats(dbias, dim, s);
-        return check_launch("ihg_rows_linear_act_bwd");
+        return check_launch(what);
     }
-    if (dy == nullptr || y == nullptr || x == nullptr || w == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "ihg_rows_linear_act_bwd: null pointer");
+    if (dy == nullptr || y == nullptr || x == nullptr || w == nullptr || dw == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
     const int64_t type_begin[4] = {0, n_rows, n_rows, n_rows};
     const TypePlan plan = make_plan(type_begin, 64);
-    const bool relu = activation == IHG_ACT_RELU;
+    const DenseWorkspace ws = dense_workspace(workspace, dim);
+    const WeightGrad g = weight_grad(dw, ld_dw, 0, dbias, 0b111, 0);
     const bool tiled = mfma_dim(dim) && ld_dy % 4 == 0 && ld_y % 4 == 0 && ld_x % 4 == 0 && aligned16(dy) && aligned16(y) && aligned16(x);
-    if (!tiled) {
-        float* gslabs = static_cast<float*>(workspace);
-        float* gbias = gslabs + 3LL * kGenericSlabs * dim * dim;
-        if (dx != nullptr && n_rows > 0) {
-            const int grid = static_cast<int>(std::min<int64_t>((n_rows * dim + kBlockThreads - 1) / kBlockThreads, kMaxBlocks * 4));
-            if (relu) hipLaunchKernelGGL((row_gemm_generic_act_kernel<0, 1>), dim3(grid), dim3(kBlockThreads), 0, s, dy, ld_dy, w, ld_w, 1, static_cast<const float*>(nullptr), plan, dx, ld_dx, dim, y, ld_y);
-            else hipLaunchKernelGGL((row_gemm_generic_act_kernel<0, 2>), dim3(grid), dim3(kBlockThreads), 0, s, dy, ld_dy, w, ld_w, 1, static_cast<const float*>(nullptr), plan, dx, ld_dx, dim, y, ld_y);
+    dispatch_act(activation, [&](auto act) {
+        constexpr int ACT = decltype(act)::value;
+        if (!tiled) {
+            if (dx != nullptr) launch_row_gemm_generic_act<0, ACT>(dim, 1, dy, ld_dy, y, ld_y, w, ld_w, nullptr, plan, dx, ld_dx, s);
+            launch_weight_grad_generic<ACT>(dim, dy, ld_dy, y, ld_y, x, ld_x, plan, ws, g, s);
+            return;
         }
-        const int tiles = (dim + 15) / 16;
-        if (relu) hipLaunchKernelGGL((dense_weight_grad_generic_act_kernel<1>), dim3(kGenericSlabs, tiles * tiles, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan, dim, gslabs, gbias);
-        else hipLaunchKernelGGL((dense_weight_grad_generic_act_kernel<2>), dim3(kGenericSlabs, tiles * tiles, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan, dim, gslabs, gbias);
-        const int64_t total = static_cast<int64_t>(dim) * dim + dim;
-        hipLaunchKernelGGL(dense_generic_reduce_kernel, dim3(static_cast<int>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks))), dim3(kBlockThreads), 0, s,
-                           gslabs, gbias, kGenericSlabs, 1, dim, dw, ld_dw, int64_t{0}, dbias, 0b111, int64_t{0});
-        return check_launch("ihg_rows_linear_act_bwd");
-    }
-    float* pk = static_cast<float*>(workspace);
-    float* slabs = pk + 3LL * dim * dim;
-    float* bias_slabs = slabs + 3LL * kDenseSlabs * dim * dim;
-    const bool fused_dx = dx != nullptr && dim == 64;                // d = 64: dm = dz * W from the dz tile that is in LDS for the weight gradient anyway
-    if (dx != nullptr && !fused_dx && n_rows > 0) launch_row_gemm_act(dim, activation, 1, dy, ld_dy, y, ld_y, w, ld_w, nullptr, n_rows, dx, ld_dx, pk, s);
-    float* const no_dx = nullptr;
-#define IHG_DWA(SW, FUSE, SUBS, DX)                                                                                                                                   \
-    if (relu) hipLaunchKernelGGL((dense_weight_grad_act_kernel<SW, FUSE, 1>), dim3(kDenseSlabs, SUBS, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan, \
-                                 slabs, bias_slabs, dim, w, ld_w, DX, ld_dx);                                                                                         \
-    else hipLaunchKernelGGL((dense_weight_grad_act_kernel<SW, FUSE, 2>), dim3(kDenseSlabs, SUBS, 1), dim3(kBlockThreads), 0, s, dy, ld_dy, y, ld_y, x, ld_x, plan,      \
-                            slabs, bias_slabs, dim, w, ld_w, DX, ld_dx)
-    if (fused_dx) {
-        IHG_DWA(64, true, 1, dx);
-    } else if (dim == 32) {
-        IHG_DWA(32, false, 1, no_dx);
-    } else {
-        const int subs = (dim / 64) * (dim / 64);
-        IHG_DWA(64, false, subs, no_dx);
-    }
-#undef IHG_DWA
-    const int total = dim * dim + dim;
-    hipLaunchKernelGGL(dense_slab_reduce_kernel, dim3((total + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, bias_slabs, kDenseSlabs, 1, dim, dw, ld_dw, int64_t{0},
-                       dbias, 0b111, int64_t{0});
-    return check_launch("ihg_rows_linear_act_bwd");
+        // d = 64: dm = dz * W from the dz tile that is in LDS for the weight gradient anyway; other widths: a row-GEMM launch of its own
+        if (dx != nullptr && dim != 64) launch_row_gemm_act(dim, activation, 1, dy, ld_dy, y, ld_y, w, ld_w, nullptr, n_rows, dx, ld_dx, ws.pk, s);
+        launch_weight_grad_tiled<ACT>(dim, dy, ld_dy, y, ld_y, x, ld_x, plan, ws, 1, w, ld_w, 0, dx, ld_dx, 0, s);
+        launch_slab_reduce(dim, ws.slabs, ws.bias_slabs, kDenseSlabs, g, s);
+    });
+    return check_launch(what);
 }
 
 int ihg_compose_first_order_fwd(const float* a, int64_t ld_a, const float* c, const float* w, int64_t ld_w, const float* b, float* w_eff,

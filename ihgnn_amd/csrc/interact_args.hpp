@@ -2,6 +2,7 @@
 // kernels (interact.hip, split_arith.hip, narrow.hip): where the hyperedges' cotangents come from and whether the user slot is reduced on chip.  Host side only.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 // [E, ld] fp32 rows of hyperedge cotangents that exist in memory (what the weight-gradient kernels read); p == nullptr: there are none
 struct EdgeRows { const float* p; int64_t ld; };
@@ -38,4 +39,19 @@ struct UserReduced { float* dh; int64_t ld_dh; float* bnd_val; int32_t* bnd_user
 template <typename Step, typename Call>
 auto dispatch_nblk(const Call& call) {
     return call.order == 3 ? Step::template run<4>(call) : Step::template run<3>(call);
+}
+
+// The same for the node-level linear maps' launchers, which are lambdas: f(std::integral_constant<int, V>{}) with V the tiled width (32 / 64 / 128, else 256) or the
+// activation of the query transform (IHG_ACT_RELU = 1, else IHG_ACT_TANH = 2); the lambda reads it back as decltype(arg)::value
+template <typename F>
+void dispatch_width(int dim, F&& f) {
+    if (dim == 32) f(std::integral_constant<int, 32>{});
+    else if (dim == 64) f(std::integral_constant<int, 64>{});
+    else if (dim == 128) f(std::integral_constant<int, 128>{});
+    else f(std::integral_constant<int, 256>{});
+}
+template <typename F>
+void dispatch_act(int activation, F&& f) {
+    if (activation == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
 }

@@ -1800,6 +1800,18 @@ bool split_row_gemm_ok(int dim, const float* out, int64_t ld_out, const float* b
     return split_arith_enabled() && (dim == 128 || dim == 256) && aligned16(out) && ld_out % 4 == 0 && (bias == nullptr || (aligned16(bias) && bias_type_stride % 4 == 0));
 }
 
+static RowTiles row_tiles(const int64_t* type_begin, int rows_per_tile) {
+    RowTiles plan;
+    int acc = 0;
+    for (int t = 0; t < 4; ++t) plan.begin[t] = type_begin[t];
+    for (int t = 0; t < 3; ++t) {
+        plan.tile_prefix[t] = acc;
+        acc += static_cast<int>((type_begin[t + 1] - type_begin[t] + rows_per_tile - 1) / rows_per_tile);
+    }
+    plan.tile_prefix[3] = acc;
+    return plan;
+}
+
 void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias,
                            int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, TypedRowsOut out, int64_t ld_out, void* planes, hipStream_t s, int accumulate, int activation) {
     const int n_types = w_type_stride == 0 ? 1 : 3;
@@ -1812,40 +1824,23 @@ void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w,
                        wsc, winv);
     hipLaunchKernelGGL(pack_planes_dense_h2_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim,
                        transpose, wsc, pk);
-    RowTiles plan;
-    int acc = 0;
-    for (int t = 0; t < 4; ++t) plan.begin[t] = type_begin[t];
-    for (int t = 0; t < 3; ++t) {
-        plan.tile_prefix[t] = acc;
-        acc += static_cast<int>((type_begin[t + 1] - type_begin[t] + 31) / 32);
-    }
-    plan.tile_prefix[3] = acc;
-    if (acc == 0) return;
+    const RowTiles plan = row_tiles(type_begin, 32);
+    if (plan.tile_prefix[3] == 0) return;
     const int64_t pk_type_stride = n_types == 1 ? int64_t{0} : static_cast<int64_t>(dim / 16) * (dim / 32) * 2 * kWave;
-    const int n_seq = std::min((acc + 7) / 8 * 8, 256);                  // (d = 256) tile sequences: a multiple of 8, so that both halves of one land on one XCD
-#define IHG_ROW_GEMM(D, ACC, GRID) \
-    hipLaunchKernelGGL((row_gemm_split_kernel<D, ACC>), dim3(GRID), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride, plan, out, ld_out)
-#define IHG_ROW_GEMM_ACT(D, ACT, GRID) \
-    hipLaunchKernelGGL((row_gemm_split_kernel<D, false, ACT>), dim3(GRID), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride, plan, out, ld_out)
-    if (activation != 0) {                                               // (out = act(...): never accumulating)
-        if (dim == 128) {
-            if (activation == 1) IHG_ROW_GEMM_ACT(128, 1, std::min(acc, 256));
-            else IHG_ROW_GEMM_ACT(128, 2, std::min(acc, 256));
-        } else {
-            if (activation == 1) IHG_ROW_GEMM_ACT(256, 1, 2 * n_seq);
-            else IHG_ROW_GEMM_ACT(256, 2, 2 * n_seq);
-        }
-        return;
-    }
-#undef IHG_ROW_GEMM_ACT
-    if (dim == 128) {
-        if (accumulate) IHG_ROW_GEMM(128, true, std::min(acc, 256));
-        else IHG_ROW_GEMM(128, false, std::min(acc, 256));
-    } else {
-        if (accumulate) IHG_ROW_GEMM(256, true, 2 * n_seq);
-        else IHG_ROW_GEMM(256, false, 2 * n_seq);
-    }
-#undef IHG_ROW_GEMM
+    // ACC: out += ; ACT: out = act(...) (never accumulating).  d = 128: a workgroup per tile up to 256; d = 256: tile sequences, a multiple of 8, so that both halves of one land on one XCD
+    auto launch = [&](auto acc, auto act) {
+        constexpr bool ACC = decltype(acc)::value;
+        constexpr int ACT = decltype(act)::value;
+        const int tiles = plan.tile_prefix[3];
+        if (dim == 128)
+            hipLaunchKernelGGL((row_gemm_split_kernel<128, ACC, ACT>), dim3(std::min(tiles, 256)), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride, plan, out, ld_out);
+        else
+            hipLaunchKernelGGL((row_gemm_split_kernel<256, ACC, ACT>), dim3(2 * std::min((tiles + 7) / 8 * 8, 256)), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride,
+                               plan, out, ld_out);
+    };
+    if (activation != 0) dispatch_act(activation, [&](auto act) { launch(std::false_type{}, act); });
+    else if (accumulate) launch(std::true_type{}, std::integral_constant<int, 0>{});
+    else launch(std::false_type{}, std::integral_constant<int, 0>{});
 }
 
 // node-level forward of the interactive layer: node_interact_fwd_grouped_kernel (d = 128), node_interact_fwd_grouped256_kernel (d = 256), node_interact_fwd_q_kernel (d = 64)
@@ -1862,18 +1857,6 @@ int64_t split_node_fwd_plane_floats(int dim) {
 bool split_node_fwd_ok(int dim, int order, int64_t ld_h, int64_t ld_s, const float* out, int64_t ld_out, const float* bias) {
     return split_arith_enabled() && (dim == 64 || dim == 128 || dim == 256) && (order == 2 || order == 3) && ld_ok(ld_h) && ld_ok(ld_s) && ld_ok(ld_out) && aligned16(out) &&
            (bias == nullptr || aligned16(bias));
-}
-
-static RowTiles row_tiles(const int64_t* type_begin, int rows_per_tile) {
-    RowTiles plan;
-    int acc = 0;
-    for (int t = 0; t < 4; ++t) plan.begin[t] = type_begin[t];
-    for (int t = 0; t < 3; ++t) {
-        plan.tile_prefix[t] = acc;
-        acc += static_cast<int>((type_begin[t + 1] - type_begin[t] + rows_per_tile - 1) / rows_per_tile);
-    }
-    plan.tile_prefix[3] = acc;
-    return plan;
 }
 
 void launch_node_fwd_split(int dim, int order, const float* h, int64_t ld_h, const float* sums, int64_t ld_s, const float* deg, const float* scale, const float* bias,
@@ -1985,40 +1968,43 @@ bool split_dense_weight_ok(int dim, const float* dout, int64_t ld_dout, const fl
 int launch_dense_weight_split(int dim, const float* dout, int64_t ld_dout, TypedRows x, int64_t ld_x, const int64_t* type_begin, int n_types, float* slabs,
                               float* bias_slabs, const float* w, int64_t ld_w, int64_t w_type_stride, const TypedRowsOut* dx_rows, int64_t ld_dx, void* planes, hipStream_t s,
                               int dx_accumulate) {
-    const bool has_dx = dx_rows != nullptr;
-    const TypedRowsOut dx = has_dx ? *dx_rows : typed_rows_out(nullptr);
     RowTiles plan;
     for (int t = 0; t < 4; ++t) plan.begin[t] = type_begin[t];
     for (int t = 0; t < 4; ++t) plan.tile_prefix[t] = 0;                 // (the kernel takes its tiles from the row ranges)
-    if (dim == 128) {
-        const int n_seq = 256;
-        if (has_dx) {                                                    // fused input gradient: planes of W for out = in W
-            // two fp16 planes per weight, then the output columns' scales and their inverses ([types][128] floats each)
-            v4u* pk = static_cast<v4u*>(planes);
-            float* wsc = reinterpret_cast<float*>(pk + static_cast<int64_t>(n_types) * 8 * 4 * 2 * kWave);
-            float* winv = wsc + n_types * dim;
-            const int items = n_types * 8 * 4 * kWave;
-            hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(n_types) * dim)), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim, 1,
-                               wsc, winv);
-            hipLaunchKernelGGL(pack_planes_dense_h2_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types,
-                               dim, 1, wsc, pk);
-            if (dx_accumulate)
-                hipLaunchKernelGGL((dense_weight_grad_split_kernel<128, true, true>), dim3(n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                                   n_types == 1 ? 1 : 0, slabs, bias_slabs, pk, n_types == 1 ? int64_t{0} : int64_t{8 * 4 * 2 * kWave}, winv, dx, ld_dx);
-            else
-                hipLaunchKernelGGL((dense_weight_grad_split_kernel<128, true, false>), dim3(n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                                   n_types == 1 ? 1 : 0, slabs, bias_slabs, pk, n_types == 1 ? int64_t{0} : int64_t{8 * 4 * 2 * kWave}, winv, dx, ld_dx);
-        } else {
-            hipLaunchKernelGGL((dense_weight_grad_split_kernel<128, false, false>), dim3(n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                               n_types == 1 ? 1 : 0, slabs, bias_slabs, static_cast<const v4u*>(nullptr), int64_t{0}, static_cast<const float*>(nullptr),
-                               typed_rows_out(nullptr), int64_t{0});
-        }
+    const int single_weight = n_types == 1 ? 1 : 0;
+    if (dim == 256) {
+        const int n_seq = 128;
+        hipLaunchKernelGGL((dense_weight_grad_split_kernel<256, false, false>), dim3(2 * n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan, single_weight, slabs,
+                           bias_slabs, static_cast<const v4u*>(nullptr), int64_t{0}, static_cast<const float*>(nullptr), typed_rows_out(nullptr), int64_t{0});
         return n_seq;
     }
-    const int n_seq = 128;
-    hipLaunchKernelGGL((dense_weight_grad_split_kernel<256, false, false>), dim3(2 * n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                       n_types == 1 ? 1 : 0, slabs, bias_slabs, static_cast<const v4u*>(nullptr), int64_t{0}, static_cast<const float*>(nullptr), typed_rows_out(nullptr),
-                       int64_t{0});
+    // the fused input gradient's operands (dx_rows != nullptr), told to the kernel only then: planes of W for out = in W - two fp16 planes per weight, then the output
+    // columns' scales and their inverses ([types][128] floats each)
+    const int n_seq = 256;
+    const v4u* pk = nullptr;
+    const float* winv = nullptr;
+    int64_t pk_type_stride = 0;
+    TypedRowsOut dx = typed_rows_out(nullptr);
+    if (dx_rows != nullptr) {
+        v4u* pkw = static_cast<v4u*>(planes);
+        float* wsc = reinterpret_cast<float*>(pkw + static_cast<int64_t>(n_types) * 8 * 4 * 2 * kWave);
+        const int items = n_types * 8 * 4 * kWave;
+        hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(n_types) * dim)), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim, 1,
+                           wsc, wsc + n_types * dim);
+        hipLaunchKernelGGL(pack_planes_dense_h2_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types,
+                           dim, 1, wsc, pkw);
+        pk = pkw, winv = wsc + n_types * dim, dx = *dx_rows;
+        pk_type_stride = single_weight ? int64_t{0} : int64_t{8 * 4 * 2 * kWave};
+    } else {
+        ld_dx = 0;
+    }
+    auto launch = [&](auto with_dx, auto acc) {
+        hipLaunchKernelGGL((dense_weight_grad_split_kernel<128, decltype(with_dx)::value, decltype(acc)::value>), dim3(n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan,
+                           single_weight, slabs, bias_slabs, pk, pk_type_stride, winv, dx, ld_dx);
+    };
+    if (dx_rows == nullptr) launch(std::false_type{}, std::false_type{});
+    else if (dx_accumulate) launch(std::true_type{}, std::true_type{});
+    else launch(std::true_type{}, std::false_type{});
     return n_seq;
 }
 

@@ -543,29 +543,48 @@ def _plain_type_begin(n_rows: int):
     return (ctypes.c_int64 * 4)(0, n_rows, n_rows, n_rows)
 
 
-def _linear_rows(x: Tensor, w: Tensor, bias: Optional[Tensor], type_begin) -> Tensor:
-    """``x @ w.T + bias`` on every row (``ihg_node_linear_fwd``, one weight for all rows)."""
+def _node_linear_fwd(x: Tensor, w: Tensor, w_type_stride: int, bias: Optional[Tensor], bias_mask: int, type_begin, out: Optional[Tensor] = None) -> Tensor:
+    """``out[v] = x[v] @ W_type(v).T (+ bias)`` (``ihg_node_linear_fwd``).  ``w_type_stride``: ``d`` - node type t uses the column block t of ``w`` -, or 0: one weight for
+    every row.  ``bias`` is ``[d]`` or one vector per type, ``[3, d]``, added to the types in ``bias_mask``."""
     lib = _lib.load()
     dim = int(x.shape[1])
-    out = torch.empty(x.shape[0], dim, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(x.shape[0], dim, dtype=torch.float32, device=x.device)
     ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), x.device)
     with profiler.kernel('node_linear_fwd', x.shape[0], dim):
-        _lib.check(lib.ihg_node_linear_fwd(_ptr(x), _ld(x), _ptr(w), int(w.stride(0)), 0, _ptr(bias), 0b111, 0, type_begin, _ptr(out), _ld(out), _ptr(ws), ws.numel() * 4,
-                                           dim, _stream()), 'ihg_node_linear_fwd')
+        _lib.check(lib.ihg_node_linear_fwd(_ptr(x), _ld(x), _ptr(w), int(w.stride(0)), w_type_stride, _ptr(bias), bias_mask, dim if bias is not None and bias.dim() == 2 else 0,
+                                           type_begin, _ptr(out), _ld(out), _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd')
     return out
 
 
-def _linear_rows_backward(g: Tensor, x: Tensor, w: Tensor, type_begin, has_bias: bool):
-    """``(d x, d w, d bias)`` of ``_linear_rows`` from ``g`` (``ihg_node_linear_bwd_weight``: weight, bias and input gradient in one call)."""
+def _bias_gradient(has_bias: bool, per_type_bias: bool, dim: int, device: torch.device) -> Optional[Tensor]:
+    return torch.empty((3, dim) if per_type_bias else (dim,), dtype=torch.float32, device=device) if has_bias else None
+
+
+def _node_linear_bwd(g: Tensor, x: Tensor, w: Tensor, w_type_stride: int, type_begin, dw: Tensor, dx: Optional[Tensor], dx_accumulate: bool, has_bias: bool,
+                     per_type_bias: bool, bias_mask: int) -> Optional[Tensor]:
+    """The gradients of ``_node_linear_fwd`` from ``g`` in one call (``ihg_node_linear_bwd_weight``): the weight gradient into ``dw``, the input gradient into ``dx`` (``None``:
+    not wanted; ``dx_accumulate``: added onto what ``dx`` holds) from the same pass over ``g`` where the width allows.  Returns the bias gradient (``None`` without a bias)."""
     lib = _lib.load()
     dim = int(x.shape[1])
-    dx, dw = torch.empty_like(x), torch.empty_like(w)
-    dbias = torch.empty(dim, dtype=torch.float32, device=x.device) if has_bias else None
+    dbias = _bias_gradient(has_bias, per_type_bias, dim, x.device)
     ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), x.device)
     with profiler.kernel('node_linear_bwd', x.shape[0], dim):
-        _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(g), _ld(g), _ptr(x), _ld(x), type_begin, _ptr(dw), int(dw.stride(0)), 0, _ptr(dbias), 0b111, 0,
-                                                  _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx), 0, _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
-    return dx, dw, dbias
+        _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(g), _ld(g), _ptr(x), _ld(x), type_begin, _ptr(dw), int(dw.stride(0)), w_type_stride, _ptr(dbias), bias_mask,
+                                                  dim if per_type_bias else 0, _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx) if dx is not None else 0, 1 if dx_accumulate else 0,
+                                                  _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
+    return dbias
+
+
+def _linear_rows(x: Tensor, w: Tensor, bias: Optional[Tensor], type_begin) -> Tensor:
+    """``x @ w.T + bias`` on every row (one weight for all rows)."""
+    return _node_linear_fwd(x, w, 0, bias, 0b111, type_begin)
+
+
+def _linear_rows_backward(g: Tensor, x: Tensor, w: Tensor, type_begin, has_bias: bool):
+    """``(d x, d w, d bias)`` of ``_linear_rows`` from ``g``."""
+    dx, dw = torch.empty_like(x), torch.empty_like(w)
+    return dx, dw, _node_linear_bwd(g, x, w, 0, type_begin, dw, dx, False, has_bias, False, 0b111)
 
 
 def _add_rows(dst: Tensor, src: Tensor) -> None:
@@ -822,50 +841,44 @@ def _type_begin(layout: IncidenceLayout):
     return tb
 
 
+def _per_type_bias(bias: Optional[Tensor], typed: bool, dim: int):
+    """``(bias, per_type_bias)``: a 2-D bias is ``[3, d]``, one vector per node type, and goes with typed weights."""
+    if bias is None or bias.dim() != 2:
+        return bias, False
+    if not typed or tuple(bias.shape) != (3, dim):
+        raise ValueError(f'a per-type bias is [3, {dim}] and needs typed weights, got {tuple(bias.shape)}')
+    return bias.contiguous(), True
+
+
+def _cotangent_rows(grad_out: Tensor) -> Tensor:
+    """``grad_out`` as the weight-gradient kernels take it: rows 16-byte aligned."""
+    g = _rows(grad_out, 'grad_out')
+    return g.contiguous() if g.stride(0) % 4 or g.data_ptr() % 16 else g
+
+
+def _weight_gradient(w: Tensor, typed: bool, dim: int) -> Tensor:
+    """Where ``dw`` goes: the product-block columns of a ``[d, k*d]`` weight, which a node-level map does not touch, stay 0."""
+    return torch.zeros_like(w) if w.shape[1] != dim * (3 if typed else 1) else torch.empty_like(w)
+
+
 class _NodeLinear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x: Tensor, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, typed: bool, bias_mask: int) -> Tensor:
-        lib = _lib.load()
+    def forward(ctx, x: Tensor, w: Tensor, bias: Optional[Tensor], type_begin, typed: bool, bias_mask: int) -> Tensor:
         x = _rows(x, 'x')
         dim = int(x.shape[1])
-        out = torch.empty(x.shape[0], dim, dtype=torch.float32, device=x.device)
-        ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), x.device)
-        stride = dim if typed else 0
-        per_type_bias = bias is not None and bias.dim() == 2                       # [3, d]: one bias vector per node type
-        if per_type_bias:
-            if not typed or tuple(bias.shape) != (3, dim):
-                raise ValueError(f'a per-type bias is [3, {dim}] and needs typed weights, got {tuple(bias.shape)}')
-            bias = bias.contiguous()
-        with profiler.kernel('node_linear_fwd', x.shape[0], dim):
-            _lib.check(lib.ihg_node_linear_fwd(_ptr(x), _ld(x), _ptr(w), int(w.stride(0)), stride, _ptr(bias), bias_mask, dim if per_type_bias else 0,
-                                               _type_begin(layout), _ptr(out), _ld(out), _ptr(ws), ws.numel() * 4, dim, _stream()),
-                       'ihg_node_linear_fwd')
+        bias, per_type_bias = _per_type_bias(bias, typed, dim)
+        out = _node_linear_fwd(x, w, dim if typed else 0, bias, bias_mask, type_begin)
         ctx.save_for_backward(x, w)
-        ctx.layout, ctx.typed, ctx.bias_mask, ctx.has_bias, ctx.per_type_bias = layout, typed, bias_mask, bias is not None, per_type_bias
+        ctx.type_begin, ctx.typed, ctx.bias_mask, ctx.has_bias, ctx.per_type_bias = type_begin, typed, bias_mask, bias is not None, per_type_bias
         return out
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
-        lib = _lib.load()
         x, w = ctx.saved_tensors
-        g = _rows(grad_out, 'grad_out')
-        if g.stride(0) % 4 or g.data_ptr() % 16:
-            g = g.contiguous()
         dim = int(x.shape[1])
-        stride = dim if ctx.typed else 0
-        tb = _type_begin(ctx.layout)
-        ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dw = torch.zeros_like(w) if w.shape[1] != dim * (3 if ctx.typed else 1) else torch.empty_like(w)   # product-block columns of a [d, k*d] weight stay 0
-        dbias = None
-        if ctx.has_bias:
-            dbias = torch.empty((3, dim) if ctx.per_type_bias else (dim,), dtype=torch.float32, device=x.device)
-        # one call: the weight / bias gradient, and the input gradient from the same pass over grad_out where the width allows
-        with profiler.kernel('node_linear_bwd', x.shape[0], dim):
-            _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(g), _ld(g), _ptr(x), _ld(x), tb, _ptr(dw), int(dw.stride(0)), stride,
-                                                      _ptr(dbias), ctx.bias_mask, dim if ctx.per_type_bias else 0,
-                                                      _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx) if dx is not None else 0, 0,
-                                                      _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
+        dw = _weight_gradient(w, ctx.typed, dim)
+        dbias = _node_linear_bwd(_cotangent_rows(grad_out), x, w, dim if ctx.typed else 0, ctx.type_begin, dw, dx, False, ctx.has_bias, ctx.per_type_bias, ctx.bias_mask)
         return dx, dw, dbias, None, None, None
 
 
@@ -959,11 +972,7 @@ class _LinearFromTables(torch.autograd.Function):
         nodes.token = torch.empty(1, dtype=torch.float32, device=word_table.device)
         out = torch.empty(n, dim, dtype=torch.float32, device=word_table.device)
         ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), word_table.device)
-        per_type_bias = bias is not None and bias.dim() == 2
-        if per_type_bias:
-            if not typed or tuple(bias.shape) != (3, dim):
-                raise ValueError(f'a per-type bias is [3, {dim}] and needs typed weights, got {tuple(bias.shape)}')
-            bias = bias.contiguous()
+        bias, per_type_bias = _per_type_bias(bias, typed, dim)
         with profiler.kernel('node_linear_fwd', n, dim):
             _lib.check(lib.ihg_node_linear_fwd_typed(nodes.row_pointers(), dim, _ptr(w), int(w.stride(0)), dim if typed else 0, _ptr(bias), bias_mask, dim if per_type_bias else 0,
                                                      _type_begin(layout), _ptr(out), dim, _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd_typed')
@@ -983,16 +992,12 @@ class _LinearFromTables(torch.autograd.Function):
         bag, dim = nodes.bag, nodes.dim
         if grad_out is None:
             raise RuntimeError('the output of the first node-level transform received no gradient')
-        g = _rows(grad_out, 'grad_out')
-        if g.stride(0) % 4 or g.data_ptr() % 16:
-            g = g.contiguous()
+        g = _cotangent_rows(grad_out)
         dev = g.device
         d_user, d_item = torch.empty_like(user_table), torch.empty_like(item_table)
         d_query = torch.empty_like(query_rows)
-        dw = torch.zeros_like(w) if w.shape[1] != dim * (3 if ctx.typed else 1) else torch.empty_like(w)
-        dbias = None
-        if ctx.has_bias:
-            dbias = torch.empty((3, dim) if ctx.per_type_bias else (dim,), dtype=torch.float32, device=dev)
+        dw = _weight_gradient(w, ctx.typed, dim)
+        dbias = _bias_gradient(ctx.has_bias, ctx.per_type_bias, dim, dev)
         step = dim * 4
         x_rows = (ctypes.c_void_p * 3)(user_table.data_ptr() + step, query_rows.data_ptr(), item_table.data_ptr() + step)
         dx_rows = (ctypes.c_void_p * 3)(d_user.data_ptr() + step, d_query.data_ptr(), d_item.data_ptr() + step)
@@ -1084,20 +1089,13 @@ def node_linear(x, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, t
             raise RuntimeError('NodeTables: the input features were already consumed by a node-level transform (one per forward)')
         out, _token, _rows_q = _LinearFromTables.apply(x.user_table, x.item_table, x.word_table, w, bias, x.wq, x.bq, x, layout, bool(typed), int(bias_mask))
         return out
-    return _NodeLinear.apply(x, w, bias, layout, bool(typed), int(bias_mask))
-
-
-class _PlainRows:
-    """What ``_NodeLinear`` asks of a layout, for a table whose rows have no node types (every row is of the first type)."""
-
-    def __init__(self, n_rows: int):
-        self._type_begin_c = _plain_type_begin(int(n_rows))
+    return _NodeLinear.apply(x, w, bias, _type_begin(layout), bool(typed), int(bias_mask))
 
 
 def rows_linear(x: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tensor:
     """``out[r] = x[r] @ w.T (+ bias)`` for every row of ANY ``[rows, d]`` table (``w`` square) on the same row-GEMM kernels as ``node_linear`` - which takes its type
     boundaries from a layout's node counts; this is for tables that are not node tables: the ``[E, d]`` hyperedge features of the phase-2 attention."""
-    return _NodeLinear.apply(x, w, bias, _PlainRows(int(x.shape[0])), False, 0b111)
+    return _NodeLinear.apply(x, w, bias, _plain_type_begin(int(x.shape[0])), False, 0b111)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1190,15 +1188,8 @@ def _user_reduced_ok(h: Tensor, w: Tensor, grad_out: Tensor, layout: IncidenceLa
 
 
 def _first_order_rows(h: Tensor, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout) -> Tensor:
-    """``[N, d]`` first-order blocks per node: the typed row GEMM with ``w``'s blocks u / q / i, the bias on the users (``ihg_node_linear_fwd``, bias mask ``0b001``)."""
-    lib = _lib.load()
-    dim = int(h.shape[1])
-    p = torch.empty(h.shape[0], dim, dtype=torch.float32, device=h.device)
-    ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
-    with profiler.kernel('node_linear_fwd', h.shape[0], dim):
-        _lib.check(lib.ihg_node_linear_fwd(_ptr(h), _ld(h), _ptr(w), int(w.stride(0)), dim, _ptr(bias), 0b001, 0, _type_begin(layout),
-                                           _ptr(p), _ld(p), _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd')
-    return p
+    """``[N, d]`` first-order blocks per node: the typed row GEMM with ``w``'s blocks u / q / i, the bias on the users (bias mask ``0b001``)."""
+    return _node_linear_fwd(h, w, int(h.shape[1]), bias, 0b001, _type_begin(layout))
 
 
 def _interact_rows(h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, order: int) -> Tensor:
@@ -1214,18 +1205,13 @@ def _interact_rows(h: Tensor, p: Tensor, w: Tensor, layout: IncidenceLayout, ord
 
 
 def _first_order_backward(dp: Tensor, h: Tensor, w: Tensor, layout: IncidenceLayout, dw: Tensor, dh: Tensor, has_bias: bool) -> Optional[Tensor]:
-    """The first-order blocks' gradients from ``dp`` (``ihg_node_linear_bwd_weight``): weights into ``dw``'s blocks u / q / i, the input gradient ADDED onto ``dh`` - by
-    the kernel (``dx_accumulate``: no separate ``[N, d]`` add) where it can.  Returns the bias gradient (``None`` without a bias)."""
-    lib = _lib.load()
+    """The first-order blocks' gradients from ``dp``: weights into ``dw``'s blocks u / q / i, the input gradient ADDED onto ``dh`` - by the kernel (``dx_accumulate``: no
+    separate ``[N, d]`` add) where it can.  Returns the bias gradient (``None`` without a bias)."""
     dim = int(h.shape[1])
-    dbias = torch.empty(dim, dtype=torch.float32, device=h.device) if has_bias else None
-    ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), h.device)
-    accumulate = bool(lib.ihg_node_linear_bwd_accumulates(dim, _ld(dp), _ld(h), _ld(dh))) and h.data_ptr() % 16 == 0 and dh.data_ptr() % 16 == 0 and dp.data_ptr() % 16 == 0
+    accumulate = (bool(_lib.load().ihg_node_linear_bwd_accumulates(dim, _ld(dp), _ld(h), _ld(dh))) and h.data_ptr() % 16 == 0 and dh.data_ptr() % 16 == 0
+                  and dp.data_ptr() % 16 == 0)
     dx = dh if accumulate else torch.empty_like(dh)
-    with profiler.kernel('node_linear_bwd', h.shape[0], dim):
-        _lib.check(lib.ihg_node_linear_bwd_weight(_ptr(dp), _ld(dp), _ptr(h), _ld(h), _type_begin(layout), _ptr(dw), int(dw.stride(0)), dim,
-                                                  _ptr(dbias), 0b001, 0, _ptr(w), int(w.stride(0)), _ptr(dx), _ld(dx), 1 if accumulate else 0,
-                                                  _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_bwd_weight')
+    dbias = _node_linear_bwd(dp, h, w, dim, _type_begin(layout), dw, dx, accumulate, has_bias, False, 0b001)
     if not accumulate:
         dh.add_(dx)
     return dbias

@@ -245,6 +245,185 @@ def test_interact_node_entries_check_arguments_in_one_order():
     _refused(weight(tb=empty, p=None), INV, 'null pointer')     # (the weight gradient has no such return)
 
 
+def test_node_linear_entries_check_arguments_in_one_order(monkeypatch):
+    """The seven entry points of the node-level linear maps: what each refuses, with which code and word (its own name in front), which of two faults present at once is
+    reported, and where the empty-problem returns come.  Shared front of the five ``ihg_node_linear_*``: dim, ``type_begin``, leading dimensions - and at a tiled width
+    with rows of whole float4s and a workspace: type ranges, workspace size, workspace alignment; everything else is the any-width kernels', which ask for none of the
+    three.  Every call here is refused or has nothing to do: ``ok`` is an aligned address that is never dereferenced, ``odd`` a misaligned one."""
+    monkeypatch.delenv('IHG_INTERACT_ARITH', raising=False)
+    lib = _lib.load()
+    ok, odd, INV, WS, BIG = ctypes.c_void_p(16), ctypes.c_void_p(8), _lib.ERR_INVALID, _lib.ERR_WORKSPACE, 1 << 40
+    rising, falling, empty = (ctypes.c_int64 * 4)(0, 3, 5, 9), (ctypes.c_int64 * 4)(0, 5, 3, 9), (ctypes.c_int64 * 4)(4, 4, 4, 4)
+    hollow = (ctypes.c_int64 * 4)(0, 3, 3, 9)                  # no rows of the middle type
+    rows = lambda a=16, b=16, c=16: (ctypes.c_void_p * 3)(a, b, c)
+
+    def fwd(dim=32, x=ok, ld_x=None, w=ok, ld_w=None, tb=rising, out=ok, ld_out=None, ws=ok, ws_bytes=BIG):
+        # (x, ld_x, w, ld_w, w_type_stride, bias, bias_mask, bias_type_stride, type_begin, out, ld_out, ws, bytes, dim, stream)
+        return lib.ihg_node_linear_fwd(x, dim if ld_x is None else ld_x, w, dim if ld_w is None else ld_w, 0, None, 0b111, 0, tb, out, dim if ld_out is None else ld_out,
+                                       ws, ws_bytes, dim, None)
+
+    def bwd_input(dim=32, x=ok, ld_x=None, w=ok, ld_w=None, tb=rising, out=ok, ld_out=None, ws=ok, ws_bytes=BIG):
+        # (dout, ld_dout, w, ld_w, w_type_stride, type_begin, dx, ld_dx, ws, bytes, dim, stream)
+        return lib.ihg_node_linear_bwd_input(x, dim if ld_x is None else ld_x, w, dim if ld_w is None else ld_w, 0, tb, out, dim if ld_out is None else ld_out, ws, ws_bytes, dim, None)
+
+    def fwd_typed(dim=32, x=rows(), ld_x=None, w=ok, ld_w=None, tb=rising, out=ok, ld_out=None, ws=ok, ws_bytes=BIG):
+        return lib.ihg_node_linear_fwd_typed(x, dim if ld_x is None else ld_x, w, dim if ld_w is None else ld_w, 0, None, 0b111, 0, tb, out, dim if ld_out is None else ld_out,
+                                             ws, ws_bytes, dim, None)
+
+    for name, entry in (('ihg_node_linear_fwd', fwd), ('ihg_node_linear_bwd_input', bwd_input), ('ihg_node_linear_fwd_typed', fwd_typed)):
+        _refused(entry(dim=0, tb=None), INV, name + ': dim 0')
+        _refused(entry(dim=-4, ld_x=-8), INV, name + ': dim -4')
+        _refused(entry(tb=None, ld_x=31), INV, name + ': null pointer')
+        for ld in ('ld_x', 'ld_w', 'ld_out'):
+            _refused(entry(tb=falling, **{ld: 31}), INV, name + ': bad leading dimension')
+        _refused(entry(tb=falling, ws_bytes=0), INV, name + ': type ranges not ascending')
+        _refused(entry(ws=odd, ws_bytes=0), WS, name + ': workspace too small')
+        _refused(entry(ws_bytes=int(lib.ihg_node_linear_workspace_bytes(32)) - 1), WS, name + ': workspace too small')
+        _refused(entry(ws=odd, x=None), INV, name + ': workspace not 16-byte aligned')
+        for operand in ('x', 'w', 'out'):
+            _refused(entry(**{operand: None}), INV, name + ': null pointer')
+        # the empty problem: nothing to do once the front has passed, before the operands are looked at
+        assert entry(tb=empty, x=None, w=None, out=None) == _lib.OK
+        assert entry(tb=empty, dim=12, x=None, ws=None, ws_bytes=0) == _lib.OK
+        _refused(entry(tb=empty, ld_out=31), INV, name + ': bad leading dimension')
+        _refused(entry(tb=empty, ws_bytes=0), WS, name + ': workspace too small')
+        # rows for the any-width kernels (a width that is not tiled, rows that are not whole float4s, no workspace): ranges and workspace are not looked at
+        _refused(entry(dim=12, tb=falling, ws=odd, ws_bytes=0, x=None), INV, name + ': null pointer')
+        _refused(entry(ld_x=33, tb=falling, ws=odd, ws_bytes=0, out=None), INV, name + ': null pointer')
+        _refused(entry(ws=None, ws_bytes=0, tb=falling, w=None), INV, name + ': null pointer')
+
+    name = 'ihg_node_linear_fwd_typed'
+    _refused(fwd_typed(x=rows(b=8)), INV, name + ': rows of type 1')
+    _refused(fwd_typed(x=rows(a=None, b=8)), INV, name + ': rows of type 0')
+    _refused(fwd_typed(x=rows(c=None), dim=12), INV, name + ': rows of type 2')          # the rows before the shape
+    _refused(fwd_typed(x=rows(b=8), out=None), INV, name + ': null pointer')             # the operands before the rows
+    _refused(fwd_typed(x=rows(b=8), tb=hollow, dim=12), INV, name + ': not available for this shape')     # (the rows of a type that has none are not looked at)
+    _refused(fwd_typed(dim=12), INV, name + ': not available for this shape')
+    _refused(fwd_typed(ld_x=33), INV, name + ': not available for this shape')
+    _refused(fwd_typed(ld_out=34), INV, name + ': not available for this shape')
+    _refused(fwd_typed(ws=None), INV, name + ': not available for this shape')
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32')            # typed rows at d = 128 / 256 are the split kernels'
+    _refused(fwd_typed(dim=128), INV, name + ': not available for this shape')
+    _refused(fwd_typed(dim=256), INV, name + ': not available for this shape')
+    monkeypatch.delenv('IHG_INTERACT_ARITH')
+
+    def weight(dim=32, dout=ok, ld_dout=None, x=ok, ld_x=None, tb=rising, dw=ok, ld_dw=None, w=ok, ld_w=None, dx=None, ld_dx=None, acc=0, ws=ok, ws_bytes=BIG):
+        # (dout, ld_dout, x, ld_x, type_begin, dw, ld_dw, dw_type_stride, dbias, bias_mask, dbias_type_stride, w, ld_w, dx, ld_dx, dx_accumulate, ws, bytes, dim, stream)
+        return lib.ihg_node_linear_bwd_weight(dout, dim if ld_dout is None else ld_dout, x, dim if ld_x is None else ld_x, tb, dw, dim if ld_dw is None else ld_dw, 0, None, 0b111, 0,
+                                              w, dim if ld_w is None else ld_w, dx, dim if ld_dx is None else ld_dx, acc, ws, ws_bytes, dim, None)
+
+    def weight_typed(dim=32, dout=ok, ld_dout=None, x=rows(), ld_x=None, tb=rising, dw=ok, ld_dw=None, w=ok, ld_w=None, dx=None, ld_dx=None, acc=0, ws=ok, ws_bytes=BIG):
+        # (..., w, ld_w, dx_rows, ld_dx, zero_row_before_mask, ws, bytes, dim, stream): `acc` is not an argument of this one
+        return lib.ihg_node_linear_bwd_weight_typed(dout, dim if ld_dout is None else ld_dout, x, dim if ld_x is None else ld_x, tb, dw, dim if ld_dw is None else ld_dw, 0, None, 0b111,
+                                                    0, w, dim if ld_w is None else ld_w, dx, dim if ld_dx is None else ld_dx, 0, ws, ws_bytes, dim, None)
+
+    for name, entry, some_dx in (('ihg_node_linear_bwd_weight', weight, ok), ('ihg_node_linear_bwd_weight_typed', weight_typed, rows())):
+        _refused(entry(dim=0, tb=None), INV, name + ': dim 0')
+        _refused(entry(tb=None, ld_x=31), INV, name + ': null pointer')
+        for ld in ('ld_dout', 'ld_x', 'ld_dw'):
+            _refused(entry(tb=falling, **{ld: 31}), INV, name + ': bad leading dimension')
+        _refused(entry(tb=falling, ws_bytes=0), INV, name + ': type ranges not ascending')
+        _refused(entry(ws=odd, ws_bytes=0), WS, name + ': workspace too small')
+        _refused(entry(ws=odd, dout=None), INV, name + ': workspace not 16-byte aligned')
+        for operand in ('dout', 'x', 'dw'):
+            _refused(entry(**{operand: None}), INV, name + ': null pointer')
+        _refused(entry(tb=empty, dout=None), INV, name + ': null pointer')       # (no early return for an empty problem in the weight gradient)
+        _refused(entry(tb=empty, ws_bytes=0, dout=None), WS, name + ': workspace too small')
+        _refused(entry(dim=12, tb=falling, ws=odd, ws_bytes=0, x=None), INV, name + ': null pointer')
+        _refused(entry(dx=some_dx, w=None), INV, name + ': dx needs w')
+        _refused(entry(dx=some_dx, ld_w=31), INV, name + ': dx needs w')
+        _refused(entry(dx=some_dx, ld_dx=31), INV, name + ': dx needs w')
+        _refused(entry(dx=some_dx, w=None, dw=None), INV, name + ': null pointer')     # the operands before the dx rule
+        assert _lib.last_error().startswith(name + ':')
+
+    name = 'ihg_node_linear_bwd_weight'
+    _refused(weight(dim=64, acc=1), INV, name + ': dx_accumulate needs dx and a fused')                     # no dx
+    _refused(weight(dim=12, dx=ok, acc=1), INV, name + ': dx_accumulate needs dx and a fused')              # no such kernel at this width
+    _refused(weight(dim=64, dx=ok, ld_x=65, acc=1, ws_bytes=0), INV, name + ': dx_accumulate needs dx and a fused')   # ... nor for these rows; before the any-width workspace
+    _refused(weight(dim=64, dx=ok, w=None, acc=1), INV, name + ': dx needs w')                              # the dx rule before the accumulate rules
+    _refused(weight(dim=64, dx=ok, acc=1, dout=odd), INV, name + ': dx_accumulate needs 16-byte aligned dout and x rows')     # rows for the any-width kernels, which overwrite
+    _refused(weight(dim=64, dx=ok, acc=1, x=odd), INV, name + ': dx_accumulate needs 16-byte aligned dout and x rows')
+    _refused(weight(dim=32, dx=ok, acc=1, w=odd), INV, name + ': dx_accumulate at dim 32')
+    _refused(weight(dim=32, dx=odd, acc=1), INV, name + ': dx_accumulate at dim 32')
+    _refused(weight(dim=128, dx=odd, acc=1), INV, name + ': dx_accumulate needs 16-byte aligned dx rows')
+    _refused(weight(dim=256, dx=odd, acc=1), INV, name + ': dx_accumulate needs 16-byte aligned dx rows')
+    # the any-width branch asks for its own, smaller workspace - when there is no dx, before anything is launched (with a dx: tests/test_gpu_parity.py)
+    _refused(weight(dim=12, ws_bytes=64), WS, name + ': workspace too small (any-width path)')
+    _refused(weight(dim=12, ws_bytes=3 * 64 * (12 * 12 + 12) * 4 - 1), WS, name + ': workspace too small (any-width path)')
+    _refused(weight(dim=32, ws=None, ws_bytes=BIG), WS, name + ': workspace too small (any-width path)')
+    _refused(weight(dim=32, ld_x=33, ws_bytes=64), WS, name + ': workspace too small (any-width path)')
+    _refused(weight(dim=32, dout=odd, ws_bytes=64), WS, name + ': workspace too small')                      # (16-byte rows of whole float4s: the front has asked for the tiled size)
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32')            # d = 128 / 256 form dx in the weight-gradient pass on the split kernels only
+    _refused(weight(dim=128, dx=ok, acc=1), INV, name + ': dx_accumulate needs dx and a fused')
+    _refused(weight(dim=256, dx=ok, acc=1), INV, name + ': dx_accumulate needs dx and a fused')
+    monkeypatch.delenv('IHG_INTERACT_ARITH')
+
+    name = 'ihg_node_linear_bwd_weight_typed'
+    _refused(weight_typed(x=rows(b=8)), INV, name + ': rows of type 1')
+    _refused(weight_typed(dx=rows(c=8)), INV, name + ': rows of type 2')
+    _refused(weight_typed(dx=rows(a=None), dim=12), INV, name + ': rows of type 0')      # the rows before the shape
+    _refused(weight_typed(dx=rows(a=None), w=None), INV, name + ': dx needs w')          # the dx rule before the rows
+    _refused(weight_typed(x=rows(b=8), dx=rows(b=None), tb=hollow, dim=12), INV, name + ': not available for this shape')
+    _refused(weight_typed(dim=12), INV, name + ': not available for this shape')
+    _refused(weight_typed(ld_x=33), INV, name + ': not available for this shape')
+    _refused(weight_typed(dx=rows(), ld_dx=34), INV, name + ': not available for this shape')
+    _refused(weight_typed(dx=rows(), w=odd), INV, name + ': not available for this shape')         # d = 32: the one-pass kernel reads w in float4s
+    _refused(weight_typed(dout=odd), INV, name + ': not available for this shape')
+    _refused(weight_typed(dim=128, dout=odd), INV, name + ': not available for this shape')
+    _refused(weight_typed(dim=128, x=rows(a=8), tb=(ctypes.c_int64 * 4)(0, 0, 5, 9)), INV, name + ': not available for this shape')
+    _refused(weight_typed(ws=None), INV, name + ': not available for this shape')
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32')
+    _refused(weight_typed(dim=128), INV, name + ': not available for this shape')
+    monkeypatch.delenv('IHG_INTERACT_ARITH')
+
+    def act_fwd(dim=32, act=1, n=5, x=ok, ld_x=None, w=ok, ld_w=None, out=ok, ld_out=None, ws=ok, ws_bytes=BIG):
+        # (x, ld_x, w, ld_w, bias, activation, out, ld_out, n_rows, ws, bytes, dim, stream)
+        return lib.ihg_rows_linear_act_fwd(x, dim if ld_x is None else ld_x, w, dim if ld_w is None else ld_w, None, act, out, dim if ld_out is None else ld_out, n, ws, ws_bytes, dim, None)
+
+    def act_bwd(dim=32, act=1, n=5, x=ok, ld_x=None, w=ok, ld_w=None, out=ok, ld_out=None, ws=ok, ws_bytes=BIG, ld_y=None, dw=ok, ld_dw=None, dx=None, ld_dx=0):
+        # (dy, ld_dy, y, ld_y, x, ld_x, w, ld_w, activation, dw, ld_dw, dbias, dx, ld_dx, n_rows, ws, bytes, dim, stream): `x` stands for dy here, `out` for x
+        return lib.ihg_rows_linear_act_bwd(x, dim if ld_x is None else ld_x, ok, dim if ld_y is None else ld_y, out, dim if ld_out is None else ld_out, w, dim if ld_w is None else ld_w,
+                                           act, dw, dim if ld_dw is None else ld_dw, None, dx, ld_dx, n, ws, ws_bytes, dim, None)
+
+    for name, entry in (('ihg_rows_linear_act_fwd', act_fwd), ('ihg_rows_linear_act_bwd', act_bwd)):
+        _refused(entry(dim=0, act=0), INV, name + ': dim 0')
+        _refused(entry(n=-1, act=0), INV, name + ': dim 32, -1 rows')
+        _refused(entry(act=0, ld_x=31), INV, name + ': activation 0')
+        _refused(entry(act=3), INV, name + ': activation 3')
+        for ld in ('ld_x', 'ld_w', 'ld_out'):
+            _refused(entry(ws=None, **{ld: 31}), INV, name + ': bad leading dimension')
+        _refused(entry(ws=None, ws_bytes=0), INV, name + ': workspace null or not 16-byte aligned')
+        _refused(entry(ws=odd, ws_bytes=0), INV, name + ': workspace null or not 16-byte aligned')
+        _refused(entry(ws_bytes=0, x=None), WS, name + ': workspace too small')
+        _refused(entry(dim=12, ws_bytes=3 * 64 * (12 * 12 + 12) * 4 - 1, x=None), WS, name + ': workspace too small')
+        for operand in ('x', 'w', 'out'):
+            _refused(entry(**{operand: None}), INV, name + ': null pointer')
+    assert act_fwd(n=0, x=None, w=None, out=None) == _lib.OK   # no rows: nothing to do, after the front, before the operands
+    _refused(act_fwd(n=0, ws_bytes=0), WS, 'ihg_rows_linear_act_fwd: workspace too small')
+    name = 'ihg_rows_linear_act_bwd'
+    for ld in ({'ld_y': 31}, {'ld_dw': 31}, {'dx': ok, 'ld_dx': 31}):
+        _refused(act_bwd(x=None, **ld), INV, name + ': bad leading dimension')
+    _refused(act_bwd(ld_y=31, ws_bytes=0), WS, name + ': workspace too small')          # its own three strides come after the shared front
+    _refused(act_bwd(n=0, dw=None), INV, name + ': null pointer')                       # no rows: dw and dbias are zeroed, so dw is still asked for
+    _refused(act_bwd(dw=None), INV, name + ': null pointer')
+
+
+def test_node_linear_workspace_bytes_arithmetic():
+    """``ihg_node_linear_workspace_bytes``: packed weights ``[3, d, d]``, 256 weight slabs ``[3, d, d]`` with their bias parts ``[3, d]``, and at d = 128 / 256 the two-byte
+    weight planes (three per weight) - at a tiled width; elsewhere the 64 row-slab partials of the any-width weight gradient."""
+    lib = _lib.load()
+    for d in (12, 32, 128, 256):
+        if d in (32, 64, 128, 256):
+            floats = 3 * d * d + 3 * 256 * (d * d + d) + ((3 * 3 * d * d) // 2 if d >= 128 else 0)
+        else:
+            floats = 3 * 64 * (d * d + d)
+        assert int(lib.ihg_node_linear_workspace_bytes(d)) == 4 * floats
+    assert int(lib.ihg_node_linear_workspace_bytes(0)) == -1 and int(lib.ihg_node_linear_workspace_bytes(-32)) == -1
+    # every width's workspace holds the any-width partials too (unaligned rows at a tiled width take that branch)
+    for d in (32, 64, 128, 256):
+        assert int(lib.ihg_node_linear_workspace_bytes(d)) >= 4 * 3 * 64 * (d * d + d)
+
+
 def test_missing_library_is_a_hard_error(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libihgnn_hip.so')

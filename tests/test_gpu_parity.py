@@ -703,6 +703,170 @@ def test_node_linear_forward_backward(dim, typed):
         assert (wg.grad[:, 3 * dim:] == 0).all()
 
 
+# ---------------------------------------------------------------------------------------------
+# The node-level linear maps through the C ABI: every route of the row GEMM and of the weight gradient, with operands ops.py never produces
+# ---------------------------------------------------------------------------------------------
+NL_ROWS = ((0, 70, 79, 210), (0, 70, 70, 210))       # ranges that are no multiple of the 16- / 32- / 64- / 128-row tiles; the second without rows of the middle type
+NL_WIDTHS = (32, 64, 128, 256, 12)
+
+
+def _nl_operands(dim, typed, tb, seed=0):
+    """float64 operands on the CPU: rows x and a cotangent g ``[N, d]``, weights ``[d, 3 d]`` (typed) or ``[d, d]``, a bias ``[d]`` - for the users where the weights are
+    typed - and the float64 results: out = x W_t^T + b, dx = g W_t, dw_t = g_t^T x_t, db = column sums of g over the rows that have the bias."""
+    import ctypes
+    gen = torch.Generator().manual_seed(1000 * dim + 10 * seed + typed)
+    n = tb[3]
+    x, g = torch.randn(n, dim, generator=gen).double(), torch.randn(n, dim, generator=gen).double()
+    w = (torch.randn(dim, 3 * dim if typed else dim, generator=gen) / np.sqrt(dim)).double()
+    b = torch.randn(dim, generator=gen).double()
+    out, dx, dw = torch.empty(n, dim).double(), torch.empty(n, dim).double(), torch.zeros_like(w)
+    for t in range(3):
+        lo, hi = tb[t], tb[t + 1]
+        wt = w[:, t * dim:(t + 1) * dim] if typed else w
+        out[lo:hi] = x[lo:hi] @ wt.T + (b if t == 0 or not typed else 0)
+        dx[lo:hi] = g[lo:hi] @ wt
+        if typed:
+            dw[:, t * dim:(t + 1) * dim] = g[lo:hi].T @ x[lo:hi]
+    if not typed:
+        dw = g.T @ x
+    db = g[:tb[1]].sum(0) if typed else g.sum(0)
+    return dict(x=x, g=g, w=w, b=b, out=out, dx=dx, dw=dw, db=db, tb=(ctypes.c_int64 * 4)(*tb), stride=dim if typed else 0, mask=0b001 if typed else 0b111)
+
+
+def _nl_rows(t, how):
+    """``t`` ``[N, d]`` on the GPU as a view of a wider buffer: ``'aligned'`` - rows of d floats at a 16-byte aligned address; ``'offset'`` - one float into rows of d + 4
+    (whole float4s, misaligned address); ``'odd_ld'`` - rows of d + 1 floats."""
+    n, dim = t.shape
+    width = {'aligned': dim, 'offset': dim + 4, 'odd_ld': dim + 1}[how]
+    buf = torch.full((n * width + 4,), float('nan'), dtype=torch.float32, device=dev())
+    view = buf[1 if how == 'offset' else 0:][:n * width].view(n, width)[:, :dim]
+    view.copy_(t)
+    return view
+
+
+def _nl_call(name, *args):
+    from ihgnn_amd import _lib
+    rc = getattr(_lib.load(), name)(*args)
+    torch.cuda.synchronize()
+    return rc
+
+
+@pytest.mark.parametrize('arith', ['split', 'f32'])
+@pytest.mark.parametrize('typed', [False, True])
+@pytest.mark.parametrize('dim', NL_WIDTHS)
+def test_node_linear_row_gemm_routes(dim, typed, arith, monkeypatch):
+    """``ihg_node_linear_fwd`` and ``ihg_node_linear_bwd_input`` against float64 on every route of the row GEMM: aligned operands (d = 32 / 64: the one-stream kernels, d = 128 /
+    256: the split kernels, or under ``IHG_INTERACT_ARITH=f32`` the fp32 strip kernel / ``row_gemm_kernel``), a misaligned output (``row_gemm_kernel<D>``), input rows of
+    d + 1 floats (the any-width kernel at a tiled width), d = 12 (the any-width kernel).  Tolerance: ``test_node_linear_forward_backward``'s for rows."""
+    from ihgnn_amd import _lib, ops
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32') if arith == 'f32' else monkeypatch.delenv('IHG_INTERACT_ARITH', raising=False)
+    lib = _lib.load()
+    ws = ops._workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), dev())
+    for tb in NL_ROWS:
+        c = _nl_operands(dim, typed, tb)
+        w, b = c['w'].float().to(dev()), c['b'].float().to(dev())
+        for in_how, out_how in (('aligned', 'aligned'), ('aligned', 'offset'), ('odd_ld', 'aligned')):
+            x, g = _nl_rows(c['x'].float(), in_how), _nl_rows(c['g'].float(), in_how)
+            out, dx = _nl_rows(torch.zeros(tb[3], dim), out_how), _nl_rows(torch.zeros(tb[3], dim), out_how)
+            assert _nl_call('ihg_node_linear_fwd', ops._ptr(x), x.stride(0), ops._ptr(w), w.stride(0), c['stride'], ops._ptr(b), c['mask'], 0, c['tb'], ops._ptr(out),
+                            out.stride(0), ops._ptr(ws), ws.numel() * 4, dim, ops._stream()) == _lib.OK, _lib.last_error()
+            assert _nl_call('ihg_node_linear_bwd_input', ops._ptr(g), g.stride(0), ops._ptr(w), w.stride(0), c['stride'], c['tb'], ops._ptr(dx), dx.stride(0), ops._ptr(ws),
+                            ws.numel() * 4, dim, ops._stream()) == _lib.OK, _lib.last_error()
+            assert rel(out, c['out']) <= RTOL_SUM * 2, (tb, in_how, out_how, rel(out, c['out']))
+            assert rel(dx, c['dx']) <= RTOL_SUM * 2, (tb, in_how, out_how, rel(dx, c['dx']))
+
+
+@pytest.mark.parametrize('arith', ['split', 'f32'])
+@pytest.mark.parametrize('typed', [False, True])
+@pytest.mark.parametrize('dim', NL_WIDTHS)
+def test_node_linear_weight_gradient_routes(dim, typed, arith, monkeypatch):
+    """``ihg_node_linear_bwd_weight`` against float64 on every route: without a ``dx``, with one, and adding onto one (``dx_accumulate``, where
+    ``ihg_node_linear_bwd_accumulates`` says it can: ``dx`` is prefilled and must come back as prefill + product); aligned rows, ``x`` rows of d + 1 floats (the any-width
+    kernels) and a misaligned ``dx`` (the fp32 kernels at d = 32 / 64, a row-GEMM launch of its own at d = 128).  Tolerances: ``test_node_linear_forward_backward``'s - ``RTOL`` for ``dw`` / ``dbias``, ``RTOL_SUM * 2`` for ``dx``."""
+    from ihgnn_amd import _lib, ops
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32') if arith == 'f32' else monkeypatch.delenv('IHG_INTERACT_ARITH', raising=False)
+    lib = _lib.load()
+    ws = ops._workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), dev())
+    for tb in NL_ROWS:
+        c = _nl_operands(dim, typed, tb, seed=1)
+        w = c['w'].float().to(dev())
+        prefill = torch.randn(tb[3], dim, generator=torch.Generator().manual_seed(dim))
+        for x_how, dx_how in (('aligned', 'aligned'), ('odd_ld', 'aligned'), ('aligned', 'offset')):
+            x, g = _nl_rows(c['x'].float(), x_how), _nl_rows(c['g'].float(), 'aligned')
+            can_add = dx_how == 'aligned' and bool(lib.ihg_node_linear_bwd_accumulates(dim, g.stride(0), x.stride(0), dim))
+            assert can_add == (x_how == dx_how == 'aligned' and (dim in (32, 64) or (dim in (128, 256) and arith == 'split')))
+            for with_dx, add in (((False, 0),) if dx_how == 'aligned' else ()) + ((True, 0),) + (((True, 1),) if can_add else ()):
+                dw, dbias = torch.full_like(w, float('nan')), torch.full((dim,), float('nan'), device=dev())
+                dx = _nl_rows(prefill, dx_how) if with_dx else None
+                assert _nl_call('ihg_node_linear_bwd_weight', ops._ptr(g), g.stride(0), ops._ptr(x), x.stride(0), c['tb'], ops._ptr(dw), dw.stride(0), c['stride'], ops._ptr(dbias),
+                                c['mask'], 0, ops._ptr(w), w.stride(0), ops._ptr(dx), dx.stride(0) if with_dx else 0, add, ops._ptr(ws), ws.numel() * 4, dim,
+                                ops._stream()) == _lib.OK, _lib.last_error()
+                where = (tb, x_how, dx_how, with_dx, add)
+                assert rel(dw, c['dw']) <= RTOL, (where, rel(dw, c['dw']))
+                assert rel(dbias, c['db']) <= RTOL, (where, rel(dbias, c['db']))
+                if with_dx:
+                    want = c['dx'] + prefill.double() if add else c['dx']
+                    assert rel(dx, want) <= RTOL_SUM * 2, (where, rel(dx, want))
+
+
+@pytest.mark.parametrize('arith', ['split', 'f32'])
+def test_node_linear_plain_and_typed_entries_agree_bitwise(arith, monkeypatch):
+    """``ihg_node_linear_fwd_typed`` / ``ihg_node_linear_bwd_weight_typed`` over three separately allocated row blocks - the first and the third with a padding row in
+    front, as the embedding tables have - give bit for bit what the plain entries give over the same rows concatenated: at these shapes both reach the same kernels with
+    the same tiles.  The padding rows of ``dx`` are zeroed.  (Typed rows at d = 128 / 256 exist in the split arithmetic only.)"""
+    import ctypes
+    from ihgnn_amd import _lib, ops
+    monkeypatch.setenv('IHG_INTERACT_ARITH', 'f32') if arith == 'f32' else monkeypatch.delenv('IHG_INTERACT_ARITH', raising=False)
+    lib = _lib.load()
+    tb = NL_ROWS[0]
+    for dim in (32, 64, 128, 256) if arith == 'split' else (32, 64):
+        ws = ops._workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), dev())
+        for typed in (False, True):
+            c = _nl_operands(dim, typed, tb, seed=2)
+            w, b, g, x = (c[k].float().to(dev()) for k in ('w', 'b', 'g', 'x'))
+            pad = (1, 0, 1)
+            blocks = [torch.cat([torch.full((pad[t], dim), 7.0, device=dev()), x[tb[t]:tb[t + 1]]]).contiguous() for t in range(3)]
+            x_rows = (ctypes.c_void_p * 3)(*(blk.data_ptr() + pad[t] * dim * 4 for t, blk in enumerate(blocks)))
+            outs, grads = [], []
+            for entry in ('plain', 'typed'):
+                out, dw, dbias = torch.full((tb[3], dim), float('nan'), device=dev()), torch.full_like(w, float('nan')), torch.full((dim,), float('nan'), device=dev())
+                if entry == 'plain':
+                    dx = torch.full((tb[3], dim), float('nan'), device=dev())
+                    rc = _nl_call('ihg_node_linear_fwd', ops._ptr(x), dim, ops._ptr(w), w.stride(0), c['stride'], ops._ptr(b), c['mask'], 0, c['tb'], ops._ptr(out), dim, ops._ptr(ws),
+                                  ws.numel() * 4, dim, ops._stream())
+                    rc = rc or _nl_call('ihg_node_linear_bwd_weight', ops._ptr(g), dim, ops._ptr(x), dim, c['tb'], ops._ptr(dw), dw.stride(0), c['stride'], ops._ptr(dbias), c['mask'], 0,
+                                        ops._ptr(w), w.stride(0), ops._ptr(dx), dim, 0, ops._ptr(ws), ws.numel() * 4, dim, ops._stream())
+                    dx_blocks = [dx[tb[t]:tb[t + 1]] for t in range(3)]
+                else:
+                    dxs = [torch.full_like(blk, float('nan')) for blk in blocks]
+                    dx_rows = (ctypes.c_void_p * 3)(*(blk.data_ptr() + pad[t] * dim * 4 for t, blk in enumerate(dxs)))
+                    rc = _nl_call('ihg_node_linear_fwd_typed', x_rows, dim, ops._ptr(w), w.stride(0), c['stride'], ops._ptr(b), c['mask'], 0, c['tb'], ops._ptr(out), dim, ops._ptr(ws),
+                                  ws.numel() * 4, dim, ops._stream())
+                    rc = rc or _nl_call('ihg_node_linear_bwd_weight_typed', ops._ptr(g), dim, x_rows, dim, c['tb'], ops._ptr(dw), dw.stride(0), c['stride'], ops._ptr(dbias), c['mask'],
+                                        0, ops._ptr(w), w.stride(0), dx_rows, dim, 0b101, ops._ptr(ws), ws.numel() * 4, dim, ops._stream())
+                    dx_blocks = [blk[pad[t]:] for t, blk in enumerate(dxs)]
+                    assert all(bool((blk[:pad[t]] == 0).all()) for t, blk in enumerate(dxs)), (dim, typed)
+                assert rc == _lib.OK, (entry, dim, typed, _lib.last_error())
+                outs.append(out)
+                grads.append([dw[:, :3 * dim if typed else dim], dbias] + dx_blocks)
+            assert rel(outs[0], c['out']) <= RTOL_SUM * 2 and rel(torch.cat(grads[0][2:]), c['dx']) <= RTOL_SUM * 2      # (and they are the right bits)
+            assert torch.equal(outs[0], outs[1]), (dim, typed)
+            for name, plain, from_rows in zip(('dw', 'dbias', 'dx users', 'dx queries', 'dx items'), *grads):
+                assert torch.equal(plain, from_rows), (dim, typed, name)
+
+
+def test_node_linear_weight_gradient_refused_for_its_workspace_launches_nothing():
+    """A call refused with ``IHG_ERR_WORKSPACE`` has launched nothing: on the any-width branch (d = 12) the workspace is looked at before the input gradient is formed."""
+    from ihgnn_amd import _lib, ops
+    c = _nl_operands(12, False, (0, 8, 8, 8))
+    x, g, w = (c[k].float().to(dev()) for k in ('x', 'g', 'w'))
+    dx, dw, ws = torch.full((8, 12), 123.0, device=dev()), torch.zeros(12, 12, device=dev()), torch.zeros(16, device=dev())
+    rc = _nl_call('ihg_node_linear_bwd_weight', ops._ptr(g), 12, ops._ptr(x), 12, c['tb'], ops._ptr(dw), 12, 0, None, 0b111, 0, ops._ptr(w), 12, ops._ptr(dx), 12, 0, ops._ptr(ws),
+                  64, 12, ops._stream())
+    assert rc == _lib.ERR_WORKSPACE, _lib.last_error()
+    assert bool((dx == 123.0).all())
+
+
 def test_any_width_node_linear_is_not_serial_over_the_rows():
     """Widths outside {32, 64, 128, 256} run on the any-width kernels.  Their weight gradient used to walk ALL rows in one thread per
     matrix element (N serial steps); it is row-slab partials + a fixed-order sum now.  At a realistic N (300 k rows, d = 100) the whole
