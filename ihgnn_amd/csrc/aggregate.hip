@@ -8,6 +8,7 @@
 // dependent row gathers of several hyperedges are in flight together.
 #include "common.hpp"
 #include "split_common.hpp"
+#include "worklist.hpp"
 
 namespace {
 
@@ -128,11 +129,11 @@ __global__ __launch_bounds__(kBlockThreads) void edge_gather_sum_kernel(
 #ifndef IHG_PAIR_UNR_W
 #define IHG_PAIR_UNR_W 8      // the weighted pair sums (a multiplicity per pair: config C5) carry a weight per pair in flight as well: 8 ids, seven resident waves (13.06 -> 12.72 ms)
 #endif
-template <int VEC, int G, bool STREAM = false>
+template <int VEC, int G, bool STREAM>
 __device__ __forceinline__ Frag<VEC> accumulate_list(const float* __restrict__ src, int64_t ld_src,
                                                      const int32_t* __restrict__ ids, const float* __restrict__ src_scale,
                                                      const float* __restrict__ entry_scale, const uint8_t* __restrict__ src_mask,
-                                                     int begin, int len, int wave_max_len, int lane, int col) {
+                                                     int begin, int len, int wave_len, int lane, int col) {
     // row gathers in flight per lane: 16 at G = 32 (d = 128: 2-3 % on C3's launches over 8), 8 otherwise - at G = 64 (d = 256) eight leave the registers for six resident
     // waves instead of four and C5's two-hop launches go 9.19 / 9.43 -> 8.71 / 8.96 ms (round 6: profiles/r6/09_ab_gather_occupancy.txt; asking the compiler for more
     // waves than the loop's registers allow - launch bounds - spills and doubles the launch)
@@ -140,7 +141,7 @@ __device__ __forceinline__ Frag<VEC> accumulate_list(const float* __restrict__ s
     const int lig = lane & (G - 1);
     const int group_base = lane & ~(G - 1);
     Frag<VEC> acc = Frag<VEC>::zero();
-    for (int base = 0; base < wave_max_len; base += G) {
+    for (int base = 0; base < wave_len; base += G) {
         const bool have = base + lig < len;
         int my_id = have ? ids[begin + base + lig] : -1;
         // the entry's weight sits beside its id: asked for in the same batch as the id (its address does not need the id), selected away below where the id is not live
@@ -151,7 +152,7 @@ __device__ __forceinline__ Frag<VEC> accumulate_list(const float* __restrict__ s
         if (entry_scale != nullptr && live) my_w *= my_entry;
 #pragma unroll 1
         for (int j = 0; j < G; j += UNR) {
-            if (base + j >= wave_max_len) break;      // wave-uniform: nothing left in any group
+            if (base + j >= wave_len) break;      // wave-uniform: nothing left in any group
             int id[UNR];
             float w[UNR];
             Frag<VEC> row[UNR];
@@ -179,12 +180,12 @@ __device__ __forceinline__ Frag<VEC> accumulate_list(const float* __restrict__ s
 template <int VEC, int G>
 __device__ __forceinline__ Frag<VEC> accumulate_list_masked(const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ ids,
                                                             const float* __restrict__ src_scale, const float* __restrict__ entry_scale,
-                                                            const uint8_t* __restrict__ src_mask, int begin, int len, int wave_max_len, int lane, int col) {
+                                                            const uint8_t* __restrict__ src_mask, int begin, int len, int wave_len, int lane, int col) {
     constexpr int FLY = 8;
     const int lig = lane & (G - 1);
     const int group_base = lane & ~(G - 1);
     Frag<VEC> acc = Frag<VEC>::zero();
-    for (int base = 0; base < wave_max_len; base += G) {
+    for (int base = 0; base < wave_len; base += G) {
         const bool have = base + lig < len;
         int my_id = have ? ids[begin + base + lig] : -1;
         if (have && src_mask[my_id] == 0) my_id = -1;
@@ -212,16 +213,6 @@ __device__ __forceinline__ Frag<VEC> accumulate_list_masked(const float* __restr
     return acc;
 }
 
-template <int G>
-__device__ __forceinline__ int wave_max_over_groups(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o >= G; o >>= 1) {
-        const int other = __shfl_xor(v, o);
-        v = other > v ? other : v;
-    }
-    return v;
-}
-
 template <int VEC>
 __device__ __forceinline__ void apply_out_scale(Frag<VEC>& acc, const float* out_scale, int mode, int64_t row) {
     mode &= 0xff;                                           // (IHG_SCALE_ACCUMULATE rides in the mode word)
@@ -235,7 +226,7 @@ __device__ __forceinline__ void apply_out_scale(Frag<VEC>& acc, const float* out
 
 // Work list of one launch: first the fixed-length segments of the split (heavy) rows, then the light rows in `row_order`
 // (decreasing length).  Unit u < n_segments writes partials[u]; unit u >= n_segments writes its output row.
-template <int VEC, int G, bool MASKED = false, bool STREAM = false>
+template <int VEC, int G, bool MASKED, bool STREAM>
 __global__ __launch_bounds__(kBlockThreads, IHG_K7_WAVES) void node_segment_sum_kernel(
     const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ ids,
     const int32_t* __restrict__ row_order, const float* __restrict__ src_scale, const float* __restrict__ entry_scale,
@@ -270,7 +261,7 @@ __global__ __launch_bounds__(kBlockThreads, IHG_K7_WAVES) void node_segment_sum_
                 scale_row = r;
             }
         }
-        const int wave_len = wave_max_over_groups<G>(len);
+        const int wave_len = wave_max_len<G>(len);
         const int col_iters = (dim_vec + G - 1) / G;
         for (int ci = 0; ci < col_iters; ++ci) {
             const int c = ci * G + lig;
@@ -303,7 +294,7 @@ __global__ __launch_bounds__(kBlockThreads, IHG_K7_WAVES) void node_segment_sum_
 #ifndef IHG_PAIR_UNR
 #define IHG_PAIR_UNR 16
 #endif
-template <int G, bool WEIGHTED = false>
+template <int G, bool WEIGHTED>
 __global__ __launch_bounds__(kBlockThreads, IHG_PAIR_WAVES) void node_pair_sums_kernel(
     const float* __restrict__ h, int64_t ld_h, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ ids,
     const int32_t* __restrict__ row_order, float* __restrict__ out, int64_t ld_out, int64_t n_rows, int dim, int dim_vec,
@@ -332,34 +323,37 @@ __global__ __launch_bounds__(kBlockThreads, IHG_PAIR_WAVES) void node_pair_sums_
             if (heavy_threshold > 0 && len > heavy_threshold) len = 0;      // finished from the partials
             else dst = out + r * ld_out;
         }
-        const int wave_len = wave_max_over_groups<G>(len);
+        const int wave_len = wave_max_len<G>(len);
         const int col_iters = (dim_vec + G - 1) / G;
         for (int ci = 0; ci < col_iters; ++ci) {
             const int c = ci * G + lig;
             const bool col_ok = c < dim_vec;
             Frag<4> sa = Frag<4>::zero(), sb = Frag<4>::zero(), sab = Frag<4>::zero();
-            if (WEIGHTED) {
-                // a layout with duplicate (user, query, item) triples collapsed: pair p of the list (ids 2 p, 2 p + 1; the lists start at even offsets) stands for
-                // pair_weight[p] hyperedges - every sum takes the pair that many times
-                for (int base = 0; base < wave_len; base += G) {
-                    const bool have = base + lig < len;
-                    const int my_id = have ? ids[begin + base + lig] : -1;
-                    const float my_w = have ? pair_weight[(begin + base + lig) >> 1] : 0.f;
+            // WEIGHTED - a layout with duplicate (user, query, item) triples collapsed: pair p of the list (ids 2 p, 2 p + 1; the lists start at even offsets) stands for
+            // pair_weight[p] hyperedges - every sum takes the pair that many times
+            for (int base = 0; base < wave_len; base += G) {
+                const bool have = base + lig < len;
+                const int my_id = have ? ids[begin + base + lig] : -1;
+                [[maybe_unused]] float my_w = 0.f;
+                if constexpr (WEIGHTED) my_w = have ? pair_weight[(begin + base + lig) >> 1] : 0.f;
 #pragma unroll 1
-                    for (int j = 0; j < G; j += UNR) {
-                        if (base + j >= wave_len) break;          // wave-uniform
-                        int id[UNR];
-                        float w[UNR / 2];
-                        Frag<4> row[UNR];
+                for (int j = 0; j < G; j += UNR) {
+                    if (base + j >= wave_len) break;          // wave-uniform
+                    int id[UNR];
+                    [[maybe_unused]] float w[UNR / 2];
+                    Frag<4> row[UNR];
 #pragma unroll
-                        for (int k = 0; k < UNR; ++k) id[k] = __shfl(my_id, group_base + j + k);
+                    for (int k = 0; k < UNR; ++k) id[k] = __shfl(my_id, group_base + j + k);
+                    if constexpr (WEIGHTED) {
 #pragma unroll
                         for (int k = 0; k < UNR; k += 2) w[k / 2] = __shfl(my_w, group_base + j + k);
+                    }
 #pragma unroll
-                        for (int k = 0; k < UNR; ++k)
-                            row[k] = (id[k] >= 0 && col_ok) ? Frag<4>::load(h + static_cast<int64_t>(id[k]) * ld_h + c * 4) : Frag<4>::zero();
+                    for (int k = 0; k < UNR; ++k)
+                        row[k] = (id[k] >= 0 && col_ok) ? Frag<4>::load(h + static_cast<int64_t>(id[k]) * ld_h + c * 4) : Frag<4>::zero();
 #pragma unroll
-                        for (int k = 0; k < UNR; k += 2) {
+                    for (int k = 0; k < UNR; k += 2) {
+                        if constexpr (WEIGHTED) {
                             const float m = w[k / 2];
                             sa.add_scaled(row[k], m);
                             sb.add_scaled(row[k + 1], m);
@@ -367,30 +361,14 @@ __global__ __launch_bounds__(kBlockThreads, IHG_PAIR_WAVES) void node_pair_sums_
                             sab.v.y += m * (row[k].v.y * row[k + 1].v.y);
                             sab.v.z += m * (row[k].v.z * row[k + 1].v.z);
                             sab.v.w += m * (row[k].v.w * row[k + 1].v.w);
+                        } else {
+                            sa.add(row[k]);
+                            sb.add(row[k + 1]);
+                            sab.v.x += row[k].v.x * row[k + 1].v.x;
+                            sab.v.y += row[k].v.y * row[k + 1].v.y;
+                            sab.v.z += row[k].v.z * row[k + 1].v.z;
+                            sab.v.w += row[k].v.w * row[k + 1].v.w;
                         }
-                    }
-                }
-            } else
-            for (int base = 0; base < wave_len; base += G) {
-                const int my_id = base + lig < len ? ids[begin + base + lig] : -1;
-#pragma unroll 1
-                for (int j = 0; j < G; j += UNR) {
-                    if (base + j >= wave_len) break;          // wave-uniform
-                    int id[UNR];
-                    Frag<4> row[UNR];
-#pragma unroll
-                    for (int k = 0; k < UNR; ++k) id[k] = __shfl(my_id, group_base + j + k);
-#pragma unroll
-                    for (int k = 0; k < UNR; ++k)
-                        row[k] = (id[k] >= 0 && col_ok) ? Frag<4>::load(h + static_cast<int64_t>(id[k]) * ld_h + c * 4) : Frag<4>::zero();
-#pragma unroll
-                    for (int k = 0; k < UNR; k += 2) {
-                        sa.add(row[k]);
-                        sb.add(row[k + 1]);
-                        sab.v.x += row[k].v.x * row[k + 1].v.x;
-                        sab.v.y += row[k].v.y * row[k + 1].v.y;
-                        sab.v.z += row[k].v.z * row[k + 1].v.z;
-                        sab.v.w += row[k].v.w * row[k + 1].v.w;
                     }
                 }
             }
@@ -410,7 +388,7 @@ __global__ __launch_bounds__(kBlockThreads) void heavy_finish_kernel(
     const float* __restrict__ partials, const int32_t* __restrict__ heavy_rows, const int32_t* __restrict__ heavy_segptr,
     int64_t n_heavy, const float* __restrict__ out_scale, int mode, float* __restrict__ out, int64_t ld_out, int dim, int dim_vec,
     const float* __restrict__ src, int64_t ld_src, const float* __restrict__ src_scale, const float* __restrict__ self_weight,
-    const uint8_t* __restrict__ src_mask = nullptr) {
+    const uint8_t* __restrict__ src_mask) {
     constexpr int GROUPS = kBlockThreads / G;
     __shared__ __attribute__((aligned(16))) float red[GROUPS][G * VEC];
     const int lig = threadIdx.x & (G - 1);
@@ -557,90 +535,48 @@ inline int agg_grid(int64_t waves) {
     return static_cast<int>(blocks);
 }
 
-// Smallest power of two >= n, clamped to [4, 64].
-inline int group_lanes(int n) {
-    int g = 4;
-    while (g < n && g < kWave) g <<= 1;
-    return g;
+// K5: consecutive hyperedges per lane group of G lanes
+template <int G>
+constexpr int k5_edges_per_group() {
+    return G == 4 ? 1 : G == 8 ? 2 : G == 16 ? IHG_K5_U16 : G == 32 ? IHG_K5_U32 : IHG_K5_U64;
 }
 
-template <int VEC>
-int launch_edge_gather_sum(const float* src, int64_t ld_src, const int32_t* i3, const float* node_scale, const float* bias,
-                           float alpha, const float* edge_scale, float* out, int64_t ld_out, int64_t n_edges, int dim, hipStream_t stream) {
-    const int dim_vec = dim / VEC;
-    const int g = group_lanes(dim_vec);
-#define IHG_LAUNCH_K5(G, U)                                                                                         \
-    {                                                                                                               \
-        constexpr int EPW = (kWave / G) * U;                                                                        \
-        const int grid = agg_grid((n_edges + EPW - 1) / EPW);                                                 \
-        hipLaunchKernelGGL((edge_gather_sum_kernel<VEC, G, U>), dim3(grid), dim3(kBlockThreads), 0, stream, src,    \
-                           ld_src, i3, node_scale, bias, alpha, edge_scale, out, ld_out, n_edges, dim_vec);         \
-    }
-    switch (g) {
-        case 4: IHG_LAUNCH_K5(4, 1) break;
-        case 8: IHG_LAUNCH_K5(8, 2) break;
-        case 16: IHG_LAUNCH_K5(16, IHG_K5_U16) break;
-        case 32: IHG_LAUNCH_K5(32, IHG_K5_U32) break;
-        default: IHG_LAUNCH_K5(64, IHG_K5_U64) break;
-    }
-#undef IHG_LAUNCH_K5
-    return check_launch("ihg_edge_gather_sum");
+// a gather launch over the plan's work list: one lane group of G lanes per unit
+inline int plan_grid(const Plan& pl, int G) {
+    const int gpw = kWave / G;
+    return agg_grid((pl.n_rows + pl.n_segments + gpw - 1) / gpw);
 }
 
-struct HeavyPlan {
-    const int32_t* seg_begin;
-    const int32_t* seg_end;
-    int64_t n_segments;
-    const int32_t* heavy_rows;
-    const int32_t* heavy_segptr;
-    int64_t n_heavy;
-    float* partials;
-    const uint8_t* src_mask;      // optional: source rows with a 0 here are known to be zero and are not fetched
+// rows [0, n_rows) of a CSR, every one of them summed where it stands: a work list without split rows and without an order
+inline Plan whole_rows(const int32_t* rowptr, const int32_t* ids, int64_t n_rows) {
+    Plan pl{};
+    pl.rowptr = rowptr;
+    pl.ids = ids;
+    pl.n_rows = n_rows;
+    return pl;
+}
+
+// the split rows of a gather launch are all there, and so are the partials their segments leave (pair sums: read 16 bytes at a time by the finish)
+int check_gather_plan(const char* what, const Plan& pl, const float* partials, bool partials16) {
+    if (const int rc = check_split_rows(what, pl, false); rc != IHG_OK) return rc;
+    if (pl.n_heavy > 0 && (partials == nullptr || (partials16 && !aligned16(partials)))) return fail(IHG_ERR_INVALID, "%s: incomplete split-row plan", what);
+    return IHG_OK;
+}
+
+// What the finish of a split row does to the sum of its partials before it stores the row: K7's scale and accumulate bit, the row's own term, the mask.  RowFinish{}:
+// nothing of it, a plain sum (the pair sums)
+struct RowFinish {
+    const float* out_scale; int mode;
+    const float* src; int64_t ld_src; const float* self_scale; const float* self_weight; const uint8_t* src_mask;
 };
+static_assert(IHG_SCALE_NONE == 0, "RowFinish{} is a plain sum");
 
+// the finish of a launch whose plan has split rows: a workgroup per split row, col_blocks of them where a row is wider than one pass of the G lanes
 template <int VEC, int G>
-void launch_segment_sum_g(const float* src, int64_t ld_src, const int32_t* rowptr, const int32_t* ids, const int32_t* row_order,
-                          const float* src_scale, const float* entry_scale, const float* out_scale, int mode, float* out, int64_t ld_out, int64_t n_rows, int dim,
-                          int heavy_threshold, const HeavyPlan& hp, const float* self_weight, hipStream_t stream) {
-    constexpr int GPW = kWave / G;
-    const int dim_vec = dim / VEC;
-    const int grid = agg_grid((n_rows + hp.n_segments + GPW - 1) / GPW);
-    // IHG_SRC_SCALE_IN_ENTRIES: entry_scale[p] already holds src_scale[ids[p]] (times the entry's weight) - the gather does not fetch the scale per id, the
-    // row's own term (here and in the split-row finish) still takes it
-    const float* self_scale = src_scale;
-    if (mode & IHG_SRC_SCALE_IN_ENTRIES) src_scale = nullptr;
-    if (hp.src_mask != nullptr)                               // the masked pull: its own instance (see accumulate_list)
-        hipLaunchKernelGGL((node_segment_sum_kernel<VEC, G, true>), dim3(grid), dim3(kBlockThreads), 0, stream, src, ld_src, rowptr, ids, row_order,
-                           src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, dim_vec, heavy_threshold, hp.seg_begin, hp.seg_end,
-                           hp.n_segments, hp.partials, self_weight, hp.src_mask, self_scale);
-    else if (mode & IHG_SRC_READ_ONCE)
-        hipLaunchKernelGGL((node_segment_sum_kernel<VEC, G, false, true>), dim3(grid), dim3(kBlockThreads), 0, stream, src, ld_src, rowptr, ids, row_order,
-                           src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, dim_vec, heavy_threshold, hp.seg_begin, hp.seg_end,
-                           hp.n_segments, hp.partials, self_weight, hp.src_mask, self_scale);
-    else
-        hipLaunchKernelGGL((node_segment_sum_kernel<VEC, G>), dim3(grid), dim3(kBlockThreads), 0, stream, src, ld_src, rowptr, ids, row_order,
-                           src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, dim_vec, heavy_threshold, hp.seg_begin, hp.seg_end,
-                           hp.n_segments, hp.partials, self_weight, hp.src_mask, self_scale);
-    if (hp.n_heavy > 0)
-        hipLaunchKernelGGL((heavy_finish_kernel<VEC, G>), dim3(static_cast<int>(std::min<int64_t>(hp.n_heavy, kMaxBlocks * 4))),
-                           dim3(kBlockThreads), 0, stream, hp.partials, hp.heavy_rows, hp.heavy_segptr, hp.n_heavy, out_scale, mode, out,
-                           ld_out, dim, dim_vec, src, ld_src, self_scale, self_weight, hp.src_mask);
-}
-
-template <int VEC>
-int launch_segment_sum(const float* src, int64_t ld_src, const int32_t* rowptr, const int32_t* ids, const int32_t* row_order,
-                       const float* src_scale, const float* entry_scale, const float* out_scale, int mode, float* out, int64_t ld_out, int64_t n_rows, int dim,
-                       int heavy_threshold, const HeavyPlan& hp, const float* self_weight, hipStream_t stream) {
-#define IHG_K7(G) launch_segment_sum_g<VEC, G>(src, ld_src, rowptr, ids, row_order, src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, heavy_threshold, hp, self_weight, stream)
-    switch (group_lanes(dim / VEC)) {
-        case 4: IHG_K7(4); break;
-        case 8: IHG_K7(8); break;
-        case 16: IHG_K7(16); break;
-        case 32: IHG_K7(32); break;
-        default: IHG_K7(64); break;
-    }
-#undef IHG_K7
-    return check_launch("ihg_node_segment_sum");
+void launch_heavy_finish(const Plan& pl, const float* partials, float* out, int64_t ld_out, int dim, int col_blocks, const RowFinish& f, hipStream_t s) {
+    if (pl.n_heavy == 0) return;
+    hipLaunchKernelGGL((heavy_finish_kernel<VEC, G>), dim3(heavy_grid(pl.n_heavy), col_blocks), dim3(kBlockThreads), 0, s, partials, pl.heavy_rows, pl.heavy_segptr, pl.n_heavy,
+                       f.out_scale, f.mode, out, ld_out, dim, dim / VEC, f.src, f.ld_src, f.self_scale, f.self_weight, f.src_mask);
 }
 
 inline bool scale_mode_ok(int mode, const float* scale) {
@@ -648,6 +584,67 @@ inline bool scale_mode_ok(int mode, const float* scale) {
     mode &= 0xff;
     if (mode == IHG_SCALE_NONE) return true;
     return (mode == IHG_SCALE_MULTIPLY || mode == IHG_SCALE_DIVIDE) && scale != nullptr;
+}
+
+// One K7 call as its entry point states it (ihg_node_segment_sum and the bag-mean pair); segment_sum() checks it and launches from it.
+struct SegmentSum {
+    const float* src; int64_t ld_src;           // source rows
+    Plan pl;                                    // (mirror and seg_row stay null: K7 reads neither)
+    const float* src_scale; const float* entry_scale; const float* out_scale; int mode;
+    float* out; int64_t ld_out; int dim;
+    float* partials;                            // [n_segments, dim]: what the segments of the split rows leave for the finish
+    const float* self_weight;
+    const uint8_t* src_mask;                    // optional: source rows with a 0 here are known to be zero and are not fetched
+};
+
+int segment_sum(const SegmentSum& a, ihg_stream_t stream) {
+    const Plan& pl = a.pl;
+    if (pl.n_rows < 0 || a.dim <= 0 || a.ld_src < a.dim || a.ld_out < a.dim || pl.n_segments < 0 || pl.n_heavy < 0) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: bad size");
+    if (!scale_mode_ok(a.mode, a.out_scale)) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: bad out_scale_mode %d", a.mode);
+    if (pl.n_rows == 0) return IHG_OK;
+    if (a.src == nullptr || pl.rowptr == nullptr || pl.ids == nullptr || a.out == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: null pointer");
+    if (const int rc = check_gather_plan("ihg_node_segment_sum", pl, a.partials, false); rc != IHG_OK) return rc;
+    if ((a.mode & IHG_SRC_SCALE_IN_ENTRIES) && (a.src_scale == nullptr || a.entry_scale == nullptr))
+        return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: IHG_SRC_SCALE_IN_ENTRIES needs src_scale and entry_scale");
+    // IHG_SRC_SCALE_IN_ENTRIES: entry_scale[p] already holds src_scale[ids[p]] (times the entry's weight) - the gather does not fetch the scale per id, the
+    // row's own term (here and in the split-row finish) still takes it
+    const float* self_scale = a.src_scale;
+    const float* gather_scale = (a.mode & IHG_SRC_SCALE_IN_ENTRIES) ? nullptr : a.src_scale;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool vec4 = rows16(a.dim, a.ld_src, a.src) && rows16(a.dim, a.ld_out, a.out) && (pl.n_heavy == 0 || aligned16(a.partials));
+    with_row_lanes(vec4, a.dim, [&](auto vec, auto g) {
+        constexpr int VEC = decltype(vec)::value, G = decltype(g)::value;
+        const int dim_vec = a.dim / VEC;
+        auto kernel = node_segment_sum_kernel<VEC, G, false, false>;
+        if (a.src_mask != nullptr) kernel = node_segment_sum_kernel<VEC, G, true, false>;                      // the masked pull: its own instance (see accumulate_list_masked)
+        else if (a.mode & IHG_SRC_READ_ONCE) kernel = node_segment_sum_kernel<VEC, G, false, true>;
+        hipLaunchKernelGGL(kernel, dim3(plan_grid(pl, G)), dim3(kBlockThreads), 0, s, a.src, a.ld_src, pl.rowptr, pl.ids, pl.row_order, gather_scale, a.entry_scale,
+                           a.out_scale, a.mode, a.out, a.ld_out, pl.n_rows, a.dim, dim_vec, pl.heavy_threshold, pl.seg_begin, pl.seg_end, pl.n_segments, a.partials,
+                           a.self_weight, a.src_mask, self_scale);
+        launch_heavy_finish<VEC, G>(pl, a.partials, a.out, a.ld_out, a.dim, 1, {a.out_scale, a.mode, a.src, a.ld_src, self_scale, a.self_weight, a.src_mask}, s);
+    });
+    return check_launch("ihg_node_segment_sum");
+}
+
+// One pair-sum call, checked by its entry point.
+struct PairSums {
+    const float* h; int64_t ld_h;
+    Plan pl;                                    // the two-hop list: ids in pairs (mirror and seg_row stay null)
+    float* out; int64_t ld_out; int dim;        // [n_rows, 3 dim]
+    float* partials;                            // [n_segments, 3 dim]
+    const float* pair_weight;                   // optional: a multiplicity per pair
+};
+
+void launch_pair_sums(const PairSums& a, hipStream_t s) {
+    const Plan& pl = a.pl;
+    with_row_lanes(true, a.dim, [&](auto, auto g) {
+        constexpr int G = decltype(g)::value;
+        const int dim_vec = a.dim / 4;
+        const auto kernel = a.pair_weight != nullptr ? node_pair_sums_kernel<G, true> : node_pair_sums_kernel<G, false>;
+        hipLaunchKernelGGL(kernel, dim3(plan_grid(pl, G)), dim3(kBlockThreads), 0, s, a.h, a.ld_h, pl.rowptr, pl.ids, pl.row_order, a.out, a.ld_out, pl.n_rows, a.dim, dim_vec,
+                           pl.heavy_threshold, pl.seg_begin, pl.seg_end, pl.n_segments, a.partials, a.pair_weight);
+        launch_heavy_finish<4, G>(pl, a.partials, a.out, a.ld_out, 3 * a.dim, (3 * dim_vec + G - 1) / G, RowFinish{}, s);      // rows of 3 dim floats, plain sums
+    });
 }
 
 }  // namespace
@@ -660,9 +657,12 @@ int ihg_edge_gather_sum(const float* src, int64_t ld_src, const int32_t* i3, con
     if (n_edges == 0) return IHG_OK;
     if (src == nullptr || i3 == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_edge_gather_sum: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool wide = dim % 4 == 0 && ld_src % 4 == 0 && ld_out % 4 == 0 && aligned16(src) && aligned16(out) && (bias == nullptr || aligned16(bias));
-    return wide ? launch_edge_gather_sum<4>(src, ld_src, i3, node_scale, bias, alpha, edge_scale, out, ld_out, n_edges, dim, s)
-                : launch_edge_gather_sum<1>(src, ld_src, i3, node_scale, bias, alpha, edge_scale, out, ld_out, n_edges, dim, s);
+    with_row_lanes(rows16(dim, ld_src, src) && rows16(dim, ld_out, out) && (bias == nullptr || aligned16(bias)), dim, [&](auto vec, auto g) {
+        constexpr int VEC = decltype(vec)::value, G = decltype(g)::value, U = k5_edges_per_group<G>(), EPW = (kWave / G) * U;
+        hipLaunchKernelGGL((edge_gather_sum_kernel<VEC, G, U>), dim3(agg_grid((n_edges + EPW - 1) / EPW)), dim3(kBlockThreads), 0, s, src, ld_src, i3, node_scale, bias, alpha,
+                           edge_scale, out, ld_out, n_edges, dim / VEC);
+    });
+    return check_launch("ihg_edge_gather_sum");
 }
 
 int32_t ihg_edge_gather_sum_planes_supported(int32_t dim, int64_t ld_src) { return dim == 256 && ld_src >= dim && ld_src % 4 == 0 ? 1 : 0; }
@@ -686,23 +686,9 @@ int ihg_node_segment_sum(const float* src, int64_t ld_src, const int32_t* rowptr
                          int64_t n_rows, int32_t dim, int32_t heavy_threshold, const int32_t* seg_begin, const int32_t* seg_end,
                          int64_t n_segments, const int32_t* heavy_rows, const int32_t* heavy_segptr, int64_t n_heavy, float* partials,
                          const float* self_weight, const uint8_t* src_mask, ihg_stream_t stream) {
-    if (n_rows < 0 || dim <= 0 || ld_src < dim || ld_out < dim || n_segments < 0 || n_heavy < 0) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: bad size");
-    if (!scale_mode_ok(out_scale_mode, out_scale)) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: bad out_scale_mode %d", out_scale_mode);
-    if (n_rows == 0) return IHG_OK;
-    if (src == nullptr || rowptr == nullptr || ids == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: null pointer");
-    if (n_heavy > 0 && (heavy_threshold <= 0 || seg_begin == nullptr || seg_end == nullptr || heavy_rows == nullptr || heavy_segptr == nullptr || partials == nullptr))
-        return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: incomplete split-row plan");
-    if ((out_scale_mode & IHG_SRC_SCALE_IN_ENTRIES) && (src_scale == nullptr || entry_scale == nullptr))
-        return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: IHG_SRC_SCALE_IN_ENTRIES needs src_scale and entry_scale");
-    if (n_heavy == 0) {
-        n_segments = 0;
-        heavy_threshold = 0;
-    }
-    const HeavyPlan hp{seg_begin, seg_end, n_segments, heavy_rows, heavy_segptr, n_heavy, partials, src_mask};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool wide = dim % 4 == 0 && ld_src % 4 == 0 && ld_out % 4 == 0 && aligned16(src) && aligned16(out) && (n_heavy == 0 || aligned16(partials));
-    return wide ? launch_segment_sum<4>(src, ld_src, rowptr, ids, row_order, src_scale, entry_scale, out_scale, out_scale_mode, out, ld_out, n_rows, dim, heavy_threshold, hp, self_weight, s)
-                : launch_segment_sum<1>(src, ld_src, rowptr, ids, row_order, src_scale, entry_scale, out_scale, out_scale_mode, out, ld_out, n_rows, dim, heavy_threshold, hp, self_weight, s);
+    if (n_segments < 0) return fail(IHG_ERR_INVALID, "ihg_node_segment_sum: bad size");      // (here: a plan without split rows forgets its segment count)
+    const Plan pl = make_plan(rowptr, ids, nullptr, row_order, n_rows, heavy_threshold, seg_begin, seg_end, nullptr, n_segments, heavy_rows, heavy_segptr, n_heavy);
+    return segment_sum({src, ld_src, pl, src_scale, entry_scale, out_scale, out_scale_mode, out, ld_out, dim, partials, self_weight, src_mask}, stream);
 }
 
 int ihg_node_pair_sums(const float* h, int64_t ld_h, const int32_t* pair_ptr, const int32_t* pair_ids, const int32_t* row_order, float* out,
@@ -714,49 +700,33 @@ int ihg_node_pair_sums(const float* h, int64_t ld_h, const int32_t* pair_ptr, co
     if (n_rows == 0) return IHG_OK;
     if (h == nullptr || pair_ptr == nullptr || pair_ids == nullptr || out == nullptr || !aligned16(h) || !aligned16(out))
         return fail(IHG_ERR_INVALID, "ihg_node_pair_sums: null or unaligned pointer");
-    if (n_heavy > 0 && (heavy_threshold <= 0 || seg_begin == nullptr || seg_end == nullptr || heavy_rows == nullptr || heavy_segptr == nullptr || partials == nullptr || !aligned16(partials)))
-        return fail(IHG_ERR_INVALID, "ihg_node_pair_sums: incomplete split-row plan");
-    if (n_heavy == 0) {
-        n_segments = 0;
-        heavy_threshold = 0;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int dim_vec = dim / 4;
-#define IHG_PAIRS(G)                                                                                                                        \
-    {                                                                                                                                       \
-        constexpr int GPW = kWave / G;                                                                                                      \
-        const int grid = agg_grid((n_rows + n_segments + GPW - 1) / GPW);                                                             \
-        if (pair_weight != nullptr)                                                                                                         \
-            hipLaunchKernelGGL((node_pair_sums_kernel<G, true>), dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, pair_ptr, pair_ids, row_order, out, \
-                               ld_out, n_rows, dim, dim_vec, heavy_threshold, seg_begin, seg_end, n_segments, partials, pair_weight);       \
-        else                                                                                                                                \
-            hipLaunchKernelGGL((node_pair_sums_kernel<G>), dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, pair_ptr, pair_ids, row_order, out, \
-                               ld_out, n_rows, dim, dim_vec, heavy_threshold, seg_begin, seg_end, n_segments, partials, pair_weight);       \
-        if (n_heavy > 0)                                                                                                                    \
-            hipLaunchKernelGGL((heavy_finish_kernel<4, G>), dim3(static_cast<int>(std::min<int64_t>(n_heavy, kMaxBlocks * 4)), (3 * dim_vec + G - 1) / G), \
-                               dim3(kBlockThreads), 0, s, partials, heavy_rows, heavy_segptr, n_heavy, nullptr, IHG_SCALE_NONE, out, ld_out, \
-                               3 * dim, 3 * dim_vec, nullptr, 0, nullptr, nullptr);                                                         \
-    }
-    switch (group_lanes(dim_vec)) {
-        case 4: IHG_PAIRS(4) break;
-        case 8: IHG_PAIRS(8) break;
-        case 16: IHG_PAIRS(16) break;
-        case 32: IHG_PAIRS(32) break;
-        default: IHG_PAIRS(64) break;
-    }
-#undef IHG_PAIRS
+    const Plan pl = make_plan(pair_ptr, pair_ids, nullptr, row_order, n_rows, heavy_threshold, seg_begin, seg_end, nullptr, n_segments, heavy_rows, heavy_segptr, n_heavy);
+    if (const int rc = check_gather_plan("ihg_node_pair_sums", pl, partials, true); rc != IHG_OK) return rc;
+    launch_pair_sums({h, ld_h, pl, out, ld_out, dim, partials, pair_weight}, static_cast<hipStream_t>(stream));
     return check_launch("ihg_node_pair_sums");
 }
 
+// the mean of every bag's rows: K7 over the bags, divided by their lengths
 int ihg_bag_mean_fwd(const float* table, int64_t ld_table, const int32_t* bag_ptr, const int32_t* words, const float* bag_len,
                      float* out, int64_t ld_out, int64_t n_bags, int32_t dim, ihg_stream_t stream) {
     if (bag_len == nullptr && n_bags > 0) return fail(IHG_ERR_INVALID, "ihg_bag_mean_fwd: null bag_len");
-    return ihg_node_segment_sum(table, ld_table, bag_ptr, words, nullptr, nullptr, nullptr, bag_len, IHG_SCALE_DIVIDE, out, ld_out, n_bags, dim, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, stream);
+    SegmentSum a{};
+    a.src = table, a.ld_src = ld_table;
+    a.pl = whole_rows(bag_ptr, words, n_bags);
+    a.out_scale = bag_len, a.mode = IHG_SCALE_DIVIDE;
+    a.out = out, a.ld_out = ld_out, a.dim = dim;
+    return segment_sum(a, stream);
 }
 
+// its transpose: K7 over the bags of every word, each bag's cotangent times 1 / its length
 int ihg_bag_mean_bwd(const float* dout, int64_t ld_dout, const int32_t* word_ptr, const int32_t* word_bags, const float* inv_len,
                      float* dtable, int64_t ld_dtable, int64_t n_table_rows, int32_t dim, ihg_stream_t stream) {
     if (inv_len == nullptr && n_table_rows > 0) return fail(IHG_ERR_INVALID, "ihg_bag_mean_bwd: null inv_len");
-    return ihg_node_segment_sum(dout, ld_dout, word_ptr, word_bags, nullptr, inv_len, nullptr, nullptr, IHG_SCALE_NONE, dtable, ld_dtable, n_table_rows, dim, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, stream);
+    SegmentSum a{};
+    a.src = dout, a.ld_src = ld_dout;
+    a.pl = whole_rows(word_ptr, word_bags, n_table_rows);
+    a.src_scale = inv_len, a.mode = IHG_SCALE_NONE;
+    a.out = dtable, a.ld_out = ld_dtable, a.dim = dim;
+    return segment_sum(a, stream);
 }
 }  // extern "C"

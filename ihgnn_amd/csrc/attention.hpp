@@ -1,14 +1,14 @@
 // attention.hpp - what the two attention translation units share (gat.hip: the GAT baseline over the pairwise graph; phase2.hip: the IHGNN layer's
-// phase-2 attention over the node <- hyperedge incidence): activations, lane-group reductions, the K7 work list with its split rows, the row projection, the row
-// gather-dot, the softmax forward and backward, the node-row gradient, and the launch and entry-point
-// helpers.  A graph is a CSR whose row v lists the SOURCES of v's incoming edges; `mirror` maps entry p to its slot in the table that is walked from the other
+// phase-2 attention over the node <- hyperedge incidence): activations, lane-group reductions, the row projection, the row gather-dot, the softmax forward and
+// backward, the node-row gradient, and the launch and entry-point helpers.  The kernels walk K7's work list with its split rows (worklist.hpp).  A graph is a CSR
+// whose row v lists the SOURCES of v's incoming edges; `mirror` maps entry p to its slot in the table that is walked from the other
 // side (gat.hip: the reverse edge's position; phase2.hip: 3 e + type(v) of an edge-major [E, 3] table).  The kernels are __global__ templates with __restrict__
 // on their own parameters (an inlined body behind a per-layer wrapper loses the qualifiers and with them the register allocation).
 #pragma once
 #include <initializer_list>
-#include <type_traits>
 
 #include "common.hpp"
+#include "worklist.hpp"
 
 namespace {
 
@@ -46,58 +46,6 @@ __device__ __forceinline__ float group_max(float v) {
     for (int o = G / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-template <int G>
-__device__ __forceinline__ int wave_max_len(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o >= G; o >>= 1) {
-        const int other = __shfl_xor(v, o);
-        v = other > v ? other : v;
-    }
-    return v;
-}
-
-// The work list of K7 (aggregate.hip): first the segments of the split rows, then the light rows in `row_order`.
-struct Plan {
-    const int32_t* rowptr;
-    const int32_t* ids;
-    const int32_t* mirror;
-    const int32_t* row_order;
-    int64_t n_rows;
-    int heavy_threshold;
-    const int32_t* seg_begin;
-    const int32_t* seg_end;
-    const int32_t* seg_row;
-    int64_t n_segments;
-    const int32_t* heavy_rows;
-    const int32_t* heavy_segptr;
-    int64_t n_heavy;
-};
-
-// seg >= 0: a segment of a split row (its partial goes to slot seg; row = the owner).  seg < 0: a whole light row; row < 0 with len 0: nothing
-// (past the end, or a split row met in the row list - its segments cover it)
-struct Unit {
-    int begin, len;
-    int64_t row, seg;
-};
-
-__device__ __forceinline__ Unit unit_at(const Plan& pl, int64_t u) {
-    Unit r{0, 0, -1, -1};
-    if (u < pl.n_segments) {
-        r.begin = pl.seg_begin[u];
-        r.len = pl.seg_end[u] - r.begin;
-        r.row = pl.seg_row[u];
-        r.seg = u;
-    } else if (u < pl.n_segments + pl.n_rows) {
-        int64_t v = u - pl.n_segments;
-        if (pl.row_order != nullptr) v = pl.row_order[v];
-        r.begin = pl.rowptr[v];
-        r.len = pl.rowptr[v + 1] - r.begin;
-        if (pl.heavy_threshold > 0 && r.len > pl.heavy_threshold) r.len = 0;
-        else r.row = v;
-    }
-    return r;
-}
-
 // out[r, k] = x[r] . w[k dim ..] for the W = 1 or 2 weight vectors of the concatenation head, out [n_rows, W] (gat.hip: W = 2, both terms of a node from one
 // load of its row; phase2.hip: W = 1 per table).  Two named sums, not an array over W: as an array the compiler packs the products another way and leaves the
 // multiply-adds of a dot unfused - the same dot, rounded differently.
@@ -422,30 +370,6 @@ inline int flat_grid(int64_t n) {
     return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(blocks, kMaxBlocks * 4)));
 }
 
-inline int heavy_grid(int64_t n_heavy) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(n_heavy, kMaxBlocks * 4))); }
-
-// rows of `dim` floats at stride ld from p can be read 16 bytes at a time
-inline bool rows16(int32_t dim, int64_t ld, const void* p) { return dim % 4 == 0 && ld % 4 == 0 && aligned16(p); }
-
-// f(VEC, G) with both as compile-time values (std::integral_constant): VEC = 4 floats per lane where the caller found the rows 16-byte addressable, else 1;
-// G = the lanes that own a row, the smallest power of two >= dim / VEC clamped to [4, 64] (K7's lane groups)
-template <class F>
-void with_row_lanes(bool vec4, int dim, F f) {
-    const auto lanes = [&](auto vec) {
-        int g = 4;
-        while (g < dim / vec() && g < kWave) g <<= 1;
-        switch (g) {
-            case 4: f(vec, std::integral_constant<int, 4>{}); break;
-            case 8: f(vec, std::integral_constant<int, 8>{}); break;
-            case 16: f(vec, std::integral_constant<int, 16>{}); break;
-            case 32: f(vec, std::integral_constant<int, 32>{}); break;
-            default: f(vec, std::integral_constant<int, 64>{}); break;
-        }
-    };
-    if (vec4) lanes(std::integral_constant<int, 4>{});
-    else lanes(std::integral_constant<int, 1>{});
-}
-
 template <int W>
 void launch_project(bool vec4, const float* x, int64_t ld_x, const float* w, int dim, int64_t n_rows, float* out, hipStream_t s) {
     with_row_lanes(vec4, dim, [&](auto vec, auto g) {
@@ -505,10 +429,7 @@ int check_plan(const char* what, const Plan& pl, int32_t head, int32_t activatio
     if (const int rc = check_head(what, head); rc != IHG_OK) return rc;
     if (activation != IHG_GAT_LEAKY_RELU && activation != IHG_GAT_RELU && activation != IHG_GAT_TANH) return fail(IHG_ERR_INVALID, "%s: unknown activation %d", what, activation);
     if (pl.n_rows > 0 && (pl.rowptr == nullptr || pl.ids == nullptr || pl.mirror == nullptr)) return fail(IHG_ERR_INVALID, "%s: null graph pointer", what);
-    if (pl.n_heavy > 0 && (pl.heavy_threshold <= 0 || pl.seg_begin == nullptr || pl.seg_end == nullptr || pl.seg_row == nullptr || pl.heavy_rows == nullptr ||
-                           pl.heavy_segptr == nullptr))
-        return fail(IHG_ERR_INVALID, "%s: incomplete split-row plan", what);
-    return IHG_OK;
+    return check_split_rows(what, pl, true);
 }
 
 int check_pointers(const char* what, std::initializer_list<const void*> pointers) {
@@ -520,17 +441,6 @@ int check_pointers(const char* what, std::initializer_list<const void*> pointers
 int check_workspace(const char* what, int64_t have, int64_t need) {
     if (have < need) return fail(IHG_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes", what, (long long)have, (long long)need);
     return IHG_OK;
-}
-
-Plan make_plan(const int32_t* rowptr, const int32_t* ids, const int32_t* mirror, const int32_t* row_order, int64_t n_rows, int32_t heavy_threshold,
-               const int32_t* seg_begin, const int32_t* seg_end, const int32_t* seg_row, int64_t n_segments, const int32_t* heavy_rows,
-               const int32_t* heavy_segptr, int64_t n_heavy) {
-    Plan pl{rowptr, ids, mirror, row_order, n_rows, heavy_threshold, seg_begin, seg_end, seg_row, n_segments, heavy_rows, heavy_segptr, n_heavy};
-    if (n_heavy == 0) {
-        pl.n_segments = 0;
-        pl.heavy_threshold = 0;
-    }
-    return pl;
 }
 
 }  // namespace

@@ -61,6 +61,15 @@ def _workspace(n_bytes: int, device: torch.device) -> Tensor:
     return torch.empty(max(n_bytes, 16) // 4, dtype=torch.float32, device=device)
 
 
+def _plan_args(csr: Union[Csr, CsrRows], seg_row: bool = False):
+    """The split-row plan of ``csr`` in the order every entry point takes it - threshold, ``seg_begin``, ``seg_end``, (``seg_row``: the attention calls only,) segment
+    count, ``heavy_rows``, ``heavy_segptr``, row count; without split rows: zeros and nulls."""
+    if csr.n_heavy == 0:
+        return (0, None, None) + ((None,) if seg_row else ()) + (0, None, None, 0)
+    return ((csr.heavy_threshold, _ptr(csr.seg_begin), _ptr(csr.seg_end)) + ((_ptr(csr.seg_row),) if seg_row else ())
+            + (csr.n_segments, _ptr(csr.heavy_rows), _ptr(csr.heavy_segptr), csr.n_heavy))
+
+
 # ---------------------------------------------------------------------------------------------
 # raw launches (no autograd)
 # ---------------------------------------------------------------------------------------------
@@ -103,17 +112,14 @@ def node_segment_sum_raw(src: Tensor, csr: Union[Csr, CsrRows], src_scale: Optio
         mode = mode | _lib.SRC_SCALE_IN_ENTRIES
     if out is None:
         out = torch.empty(csr.n_rows, dim, dtype=torch.float32, device=src.device)
-    heavy = csr.n_heavy > 0
     if rows is not None and rows.dtype != torch.int32:
         raise TypeError('rows must be an int32 tensor')
     order, n_light = (rows, int(rows.shape[0])) if rows is not None else (csr.row_order, csr.n_rows)
     with profiler.kernel((role or 'node_segment_sum') + ('' if rows is None else '_rows'), n_light, dim):
         _lib.check(lib.ihg_node_segment_sum(
             _ptr(src), _ld(src), _ptr(csr.ptr), _ptr(csr.ids), _ptr(order), _ptr(src_scale), _ptr(entry_scale), _ptr(out_scale), mode,
-            _ptr(out), _ld(out), n_light, dim, csr.heavy_threshold if heavy else 0,
-            _ptr(csr.seg_begin) if heavy else None, _ptr(csr.seg_end) if heavy else None, csr.n_segments if heavy else 0,
-            _ptr(csr.heavy_rows) if heavy else None, _ptr(csr.heavy_segptr) if heavy else None, csr.n_heavy,
-            _ptr(csr.partials(dim)) if heavy else None, _ptr(self_weight), _ptr(src_mask), _stream()), 'ihg_node_segment_sum')
+            _ptr(out), _ld(out), n_light, dim, *_plan_args(csr), _ptr(csr.partials(dim)) if csr.n_heavy > 0 else None,
+            _ptr(self_weight), _ptr(src_mask), _stream()), 'ihg_node_segment_sum')
     return out
 
 
@@ -126,13 +132,10 @@ def node_pair_sums_raw(h: Tensor, layout: IncidenceLayout, out: Optional[Tensor]
     csr = layout.hop2_csr
     if out is None:
         out = torch.empty(layout.node_count, 3 * dim, dtype=torch.float32, device=h.device)
-    heavy = csr.n_heavy > 0
     with profiler.kernel('node_pair_sums', layout.node_count, dim):
         _lib.check(lib.ihg_node_pair_sums(
             _ptr(h), _ld(h), _ptr(csr.ptr), _ptr(csr.ids), _ptr(csr.row_order), _ptr(out), _ld(out), csr.n_rows, dim,
-            csr.heavy_threshold if heavy else 0, _ptr(csr.seg_begin) if heavy else None, _ptr(csr.seg_end) if heavy else None,
-            csr.n_segments if heavy else 0, _ptr(csr.heavy_rows) if heavy else None, _ptr(csr.heavy_segptr) if heavy else None, csr.n_heavy,
-            _ptr(csr.partials(3 * dim)) if heavy else None, _ptr(layout.pair_weight), _stream()), 'ihg_node_pair_sums')
+            *_plan_args(csr), _ptr(csr.partials(3 * dim)) if csr.n_heavy > 0 else None, _ptr(layout.pair_weight), _stream()), 'ihg_node_pair_sums')
     return out
 
 
@@ -370,10 +373,8 @@ GAT_ACTIVATIONS = {'leaky_relu': 0, 'relu': 1, 'tanh': 2}       # the names of G
 
 
 def _split_row_args(csr: Csr):
-    heavy = csr.n_heavy > 0
-    return (csr.heavy_threshold if heavy else 0, _ptr(csr.seg_begin) if heavy else None, _ptr(csr.seg_end) if heavy else None,
-            _ptr(csr.seg_row) if heavy else None, csr.n_segments if heavy else 0, _ptr(csr.heavy_rows) if heavy else None,
-            _ptr(csr.heavy_segptr) if heavy else None, csr.n_heavy)
+    """The plan arguments of the attention entry points: their kernels read ``seg_row`` too."""
+    return _plan_args(csr, seg_row=True)
 _gat_plan = _split_row_args                                     # (its earlier name: the attention tests of earlier revisions call it, and run on this build)
 
 

@@ -408,6 +408,133 @@ def test_node_linear_entries_check_arguments_in_one_order(monkeypatch):
     _refused(act_bwd(dw=None), INV, name + ': null pointer')
 
 
+def test_gather_entries_check_arguments_in_one_order():
+    """``ihg_edge_gather_sum``, ``ihg_edge_gather_sum_planes``, ``ihg_node_segment_sum``, ``ihg_node_pair_sums`` and the bag-mean pair: every refusal with its code
+    and its words, the empty problem (answered before the pointers are looked at, after the sizes and the mode), and which of two faults present at once is reported.
+    Every call here is refused or has nothing to do: ``ok`` is an aligned address that is never dereferenced, ``odd`` a misaligned one."""
+    lib = _lib.load()
+    ok, odd, INV = ctypes.c_void_p(16), ctypes.c_void_p(8), _lib.ERR_INVALID
+
+    def k5(src=ok, ld_src=8, i3=ok, out=ok, ld_out=8, n=5, dim=8):
+        # (src, ld_src, i3, node_scale, bias, alpha, edge_scale, out, ld_out, n_edges, dim, stream)
+        return lib.ihg_edge_gather_sum(src, ld_src, i3, None, None, 1.0, None, out, ld_out, n, dim, None)
+    for bad in (dict(n=-1), dict(dim=0), dict(dim=-8), dict(ld_src=7), dict(ld_out=7)):
+        _refused(k5(**bad), INV, 'ihg_edge_gather_sum: bad size (E=')
+    _refused(k5(n=0, ld_out=7, src=None), INV, 'ihg_edge_gather_sum: bad size')           # the sizes before the empty problem
+    assert k5(n=0, src=None, i3=None, out=None) == _lib.OK
+    for operand in ('src', 'i3', 'out'):
+        _refused(k5(**{operand: None}), INV, 'ihg_edge_gather_sum: null pointer')
+
+    def planes(src=ok, ld_src=256, i3=ok, rows=ok, inv=ok, n=5, dim=256):
+        # (src, ld_src, i3, node_scale, edge_scale, planes, inv_scale, n_edges, dim, stream)
+        return lib.ihg_edge_gather_sum_planes(src, ld_src, i3, None, None, rows, inv, n, dim, None)
+    for bad in (dict(dim=128, ld_src=128), dict(ld_src=252), dict(ld_src=258), dict(dim=128, ld_src=128, n=-1, src=None)):
+        _refused(planes(**bad), INV, 'ihg_edge_gather_sum_planes: shape not supported')
+    _refused(planes(n=-1, src=None), INV, 'ihg_edge_gather_sum_planes: bad size')
+    assert planes(n=0, src=None, i3=None, rows=None, inv=None) == _lib.OK
+    for bad in (dict(src=None), dict(i3=None), dict(rows=None), dict(inv=None), dict(src=odd), dict(rows=odd)):
+        _refused(planes(**bad), INV, 'ihg_edge_gather_sum_planes: null or unaligned pointer')
+
+    NONE, MUL, DIV, ACC, ONCE, IN_ENTRIES = _lib.SCALE_NONE, _lib.SCALE_MULTIPLY, _lib.SCALE_DIVIDE, _lib.SCALE_ACCUMULATE, _lib.SRC_READ_ONCE, _lib.SRC_SCALE_IN_ENTRIES
+    plan_pointers = ('seg_begin', 'seg_end', 'heavy_rows', 'heavy_segptr', 'partials')
+
+    def k7(src=ok, ld_src=8, rowptr=ok, ids=ok, src_scale=None, entry_scale=None, out_scale=None, mode=NONE, out=ok, ld_out=8, n=5, dim=8, threshold=0, seg_begin=None,
+           seg_end=None, n_segments=0, heavy_rows=None, heavy_segptr=None, n_heavy=0, partials=None):
+        # (src, ld_src, rowptr, ids, row_order, src_scale, entry_scale, out_scale, mode, out, ld_out, n_rows, dim, heavy_threshold, seg_begin, seg_end, n_segments,
+        #  heavy_rows, heavy_segptr, n_heavy, partials, self_weight, src_mask, stream)
+        return lib.ihg_node_segment_sum(src, ld_src, rowptr, ids, None, src_scale, entry_scale, out_scale, mode, out, ld_out, n, dim, threshold, seg_begin, seg_end, n_segments,
+                                        heavy_rows, heavy_segptr, n_heavy, partials, None, None, None)
+    split = dict(threshold=2, seg_begin=ok, seg_end=ok, n_segments=3, heavy_rows=ok, heavy_segptr=ok, n_heavy=1, partials=ok)
+    name = 'ihg_node_segment_sum'
+    for bad in (dict(n=-1), dict(dim=0), dict(ld_src=7), dict(ld_out=7), dict(n_segments=-1), dict(n_heavy=-1), dict(split, n_segments=-1)):
+        _refused(k7(**bad), INV, name + ': bad size')
+    _refused(k7(ld_src=7, mode=7, n=0), INV, name + ': bad size')                          # the sizes first,
+    for mode in (3, 7, 0x1000, 0x200 | MUL, MUL, DIV, MUL | ACC, DIV | ONCE | IN_ENTRIES):
+        _refused(k7(mode=mode), INV, name + f': bad out_scale_mode {mode}')               # (MULTIPLY / DIVIDE: without an out_scale)
+        _refused(k7(mode=mode, n=0, src=None), INV, name + ': bad out_scale_mode')        # then the mode, also where there are no rows,
+    for mode, scale in ((NONE, None), (MUL, ok), (DIV | ACC | ONCE | IN_ENTRIES, ok), (NONE | ACC, None)):
+        assert k7(mode=mode, out_scale=scale, n=0, src=None, rowptr=None, ids=None, out=None) == _lib.OK      # then the empty problem, before the pointers
+    for operand in ('src', 'rowptr', 'ids', 'out'):
+        _refused(k7(**{operand: None}), INV, name + ': null pointer')
+        _refused(k7(**dict(split, seg_end=None, mode=IN_ENTRIES, **{operand: None})), INV, name + ': null pointer')     # the operands before the plan
+    for pointer in plan_pointers:
+        _refused(k7(**dict(split, **{pointer: None})), INV, name + ': incomplete split-row plan')
+    _refused(k7(**dict(split, threshold=0)), INV, name + ': incomplete split-row plan')
+    _refused(k7(**dict(split, threshold=-2)), INV, name + ': incomplete split-row plan')
+    _refused(k7(**dict(split, partials=None, mode=IN_ENTRIES)), INV, name + ': incomplete split-row plan')         # the plan before the entry scales
+    for scales in (dict(), dict(src_scale=ok), dict(entry_scale=ok)):
+        _refused(k7(mode=IN_ENTRIES, **scales), INV, name + ': IHG_SRC_SCALE_IN_ENTRIES needs src_scale and entry_scale')
+        _refused(k7(**dict(split, mode=IN_ENTRIES | MUL | ACC, out_scale=ok, **scales)), INV, name + ': IHG_SRC_SCALE_IN_ENTRIES needs')
+
+    def pairs(h=ok, ld_h=8, ptr=ok, ids=ok, out=ok, ld_out=24, n=5, dim=8, threshold=0, seg_begin=None, seg_end=None, n_segments=0, heavy_rows=None, heavy_segptr=None,
+              n_heavy=0, partials=None):
+        # (h, ld_h, pair_ptr, pair_ids, row_order, out, ld_out, n_rows, dim, heavy_threshold, seg_begin, seg_end, n_segments, heavy_rows, heavy_segptr, n_heavy, partials,
+        #  pair_weight, stream)
+        return lib.ihg_node_pair_sums(h, ld_h, ptr, ids, None, out, ld_out, n, dim, threshold, seg_begin, seg_end, n_segments, heavy_rows, heavy_segptr, n_heavy, partials,
+                                      None, None)
+    name = 'ihg_node_pair_sums'
+    for bad in (dict(n=-1), dict(dim=0), dict(dim=6, ld_h=8, ld_out=24), dict(ld_h=4), dict(ld_h=10), dict(ld_out=23), dict(ld_out=26), dict(n_segments=-1), dict(n_heavy=-1),
+                dict(n=0, ld_out=23, h=None)):
+        _refused(pairs(**bad), INV, name + ': bad size (rows=')
+    assert pairs(n=0, h=None, ptr=None, ids=None, out=None) == _lib.OK
+    for bad in (dict(h=None), dict(ptr=None), dict(ids=None), dict(out=None), dict(h=odd), dict(out=odd), dict(split, out=odd, seg_end=None)):
+        _refused(pairs(**bad), INV, name + ': null or unaligned pointer')
+    for pointer in plan_pointers:
+        _refused(pairs(**dict(split, **{pointer: None})), INV, name + ': incomplete split-row plan')
+    _refused(pairs(**dict(split, threshold=0)), INV, name + ': incomplete split-row plan')
+    _refused(pairs(**dict(split, partials=odd)), INV, name + ': incomplete split-row plan')        # unaligned partials
+
+    def bag_fwd(table=ok, ld_table=8, ptr=ok, words=ok, bag_len=ok, out=ok, ld_out=8, n=5, dim=8):
+        return lib.ihg_bag_mean_fwd(table, ld_table, ptr, words, bag_len, out, ld_out, n, dim, None)
+
+    def bag_bwd(table=ok, ld_table=8, ptr=ok, words=ok, bag_len=ok, out=ok, ld_out=8, n=5, dim=8):      # (dout, ld_dout, word_ptr, word_bags, inv_len, dtable, ld_dtable, rows, dim)
+        return lib.ihg_bag_mean_bwd(table, ld_table, ptr, words, bag_len, out, ld_out, n, dim, None)
+    _refused(bag_fwd(bag_len=None), INV, 'ihg_bag_mean_fwd: null bag_len')
+    _refused(bag_bwd(bag_len=None), INV, 'ihg_bag_mean_bwd: null inv_len')
+    _refused(bag_fwd(bag_len=None, dim=0), INV, 'ihg_bag_mean_fwd: null bag_len')         # its own vector first
+    _refused(bag_bwd(bag_len=None, dim=0), INV, 'ihg_bag_mean_bwd: null inv_len')
+    for entry in (bag_fwd, bag_bwd):                                                      # the rest are K7's answers, under K7's name
+        for bad in (dict(n=-1), dict(dim=0), dict(ld_table=7), dict(ld_out=7), dict(n=0, ld_out=7)):
+            _refused(entry(**bad), INV, 'ihg_node_segment_sum: bad size')
+        assert entry(n=0, table=None, ptr=None, words=None, out=None) == _lib.OK
+        for operand in ('table', 'ptr', 'words', 'out'):
+            _refused(entry(**{operand: None}), INV, 'ihg_node_segment_sum: null pointer')
+    _refused(bag_fwd(n=0, bag_len=None), INV, 'ihg_node_segment_sum: bad out_scale_mode 2')        # no bags and no lengths: the divide mode without its vector
+    assert bag_bwd(n=0, bag_len=None) == _lib.OK                                          # (the backward's vector scales the sources: no mode to refuse)
+
+
+def test_plan_arguments_of_the_gather_and_attention_calls():
+    """``ops._plan_args``: for a ``Csr`` with split rows and for one without, the arguments ``node_segment_sum_raw``, ``node_pair_sums_raw`` and (with ``seg_row``) the
+    attention calls pass for the plan - written out here as those calls listed them one by one."""
+    import numpy as np
+    from ihgnn_amd import ops
+    from ihgnn_amd.layout import Csr, CsrRows
+    lengths = [1, 5, 0, 2, 4, 3]
+    ptr = np.zeros(len(lengths) + 1, np.int64)
+    np.cumsum(lengths, out=ptr[1:])
+    ids = np.arange(int(ptr[-1])) % 7
+    split = Csr(ptr, ids, torch.device('cpu'), heavy_threshold=2, heavy_chunk=2)
+    plain = Csr(ptr, ids, torch.device('cpu'), heavy_threshold=0)
+    assert split.n_heavy == 3 and split.n_segments == 3 + 2 + 2 and plain.n_heavy == 0
+
+    def values(args):
+        return tuple(a.value if isinstance(a, ctypes.c_void_p) else a for a in args)
+
+    def listed(csr, seg_row):
+        heavy = csr.n_heavy > 0
+        address = lambda t: t.data_ptr() if heavy else None
+        front = (csr.heavy_threshold if heavy else 0, address(csr.seg_begin), address(csr.seg_end))
+        back = (csr.n_segments if heavy else 0, address(csr.heavy_rows), address(csr.heavy_segptr), csr.n_heavy)
+        return front + ((address(csr.seg_row),) if seg_row else ()) + back
+
+    for csr in (split, plain):
+        assert values(ops._plan_args(csr)) == listed(csr, False) and len(ops._plan_args(csr)) == 7
+        assert values(ops._split_row_args(csr)) == values(ops._gat_plan(csr)) == values(ops._plan_args(csr, seg_row=True)) == listed(csr, True)
+    assert values(ops._plan_args(split)) == (2, split.seg_begin.data_ptr(), split.seg_end.data_ptr(), 7, split.heavy_rows.data_ptr(), split.heavy_segptr.data_ptr(), 3)
+    assert values(ops._split_row_args(plain)) == (0, None, None, None, 0, None, None, 0) and values(ops._plan_args(plain)) == (0, None, None, 0, None, None, 0)
+    assert values(ops._plan_args(CsrRows(split, 1, 3))) == (0, None, None, 0, None, None, 0)      # a slice of rows: summed in place, no plan
+
+
 def test_node_linear_workspace_bytes_arithmetic():
     """``ihg_node_linear_workspace_bytes``: packed weights ``[3, d, d]``, 256 weight slabs ``[3, d, d]`` with their bias parts ``[3, d]``, and at d = 128 / 256 the two-byte
     weight planes (three per weight) - at a tiled width; elsewhere the 64 row-slab partials of the any-width weight gradient."""

@@ -651,3 +651,32 @@ def test_bag_mean_of_exact_inputs_with_odd_lengths():
     total = R.segment_sum_reference(table, torch.from_numpy(ptr), torch.from_numpy(words))
     R.assert_exact_condition(total, 'bag mean, odd lengths', bits=0)
     R.assert_mean_of_exact_sum(got, total.want, torch.from_numpy(np.diff(ptr)), 'bag mean, odd lengths')
+
+
+@pytest.mark.parametrize('dim', [8, 100])
+def test_bag_mean_entries_are_k7_launches(dim):
+    """``ihg_bag_mean_fwd`` / ``ihg_bag_mean_bwd`` through the binding, bags of 0, 1, 2, 3, 64, 4, 0 words: bit for bit what ``node_segment_sum_raw`` gives for the same
+    operands - the bags divided by ``bag_len`` forward, the transposed lists with ``src_scale = inv_len`` backward (dim 100: 25 float4 columns on 32 lanes)."""
+    from ihgnn_amd import _lib, ops
+    from ihgnn_amd.ops import _ld, _ptr, _stream
+    rng = _rng(26, dim)
+    lens = np.array([0, 1, 2, 3, 64, 4, 0])
+    ptr = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    words = rng.integers(1, BAG_WORDS + 1, int(ptr[-1]))
+    bag = ops.BagLayout(words, ptr[:-1], BAG_WORDS + 1, dev())
+    lib = _lib.load()
+    table, dout = _to(R.features(rng, BAG_WORDS + 1, dim, False)), _to(R.features(rng, len(lens), dim, False))
+    means = torch.full((len(lens), dim), float('nan'), device=dev())
+    _lib.check(lib.ihg_bag_mean_fwd(_ptr(table), _ld(table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len), _ptr(means), _ld(means), len(lens), dim, _stream()),
+               'ihg_bag_mean_fwd')
+    grad = torch.full((BAG_WORDS + 1, dim), float('nan'), device=dev())
+    _lib.check(lib.ihg_bag_mean_bwd(_ptr(dout), _ld(dout), _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids), _ptr(bag.inv_len), _ptr(grad), _ld(grad), BAG_WORDS + 1, dim,
+                                    _stream()), 'ihg_bag_mean_bwd')
+    assert bag.bags.n_heavy == 0 and bag.words_of.n_heavy == 0
+    want_means = ops.node_segment_sum_raw(table, bag.bags, None, bag.bag_len, _lib.SCALE_DIVIDE)
+    want_grad = ops.node_segment_sum_raw(dout, bag.words_of, bag.inv_len, None, _lib.SCALE_NONE)
+    torch.cuda.synchronize()
+    empty = torch.from_numpy(lens == 0)
+    assert bool(torch.isfinite(means).all()) and bool((means.cpu()[empty] == 0).all()) and bool((means.cpu()[~empty] != 0).any()) and bool(torch.isfinite(grad).all())
+    assert torch.equal(means, want_means) and torch.equal(grad, want_grad)
