@@ -4,6 +4,25 @@ from typing import Optional, Sequence
 
 from .GlobalSettings import Gsv
 
+MIN_EXTRA_CUTOFF, MAX_EXTRA_CUTOFF = 11, 128               # above the reference's ten, up to the deepest ranking the scoring kernel returns
+
+
+def cutoff_list(text: str):
+    """``'20,50,100'`` -> ``(20, 50, 100)`` (sorted, duplicates dropped; ``''`` -> ``()``); every value an integer in 11..128."""
+    out = set()
+    for part in (text or '').split(','):
+        if not part.strip():
+            continue
+        try:
+            value = int(part)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f'--cutoffs takes integers separated by commas, got {part.strip()!r}')
+        if not MIN_EXTRA_CUTOFF <= value <= MAX_EXTRA_CUTOFF:
+            raise argparse.ArgumentTypeError(f'--cutoffs: every cutoff must be in {MIN_EXTRA_CUTOFF}..{MAX_EXTRA_CUTOFF} (@10 is always reported), got {value}')
+        out.add(value)
+    return tuple(sorted(out))
+
+
 # (dest, flags, kind, default, help); kind is a type or 'flag'
 _FLAGS = (
     ('checkpoint', ('--checkpoint', '--cp'), str, '', 'checkpoint file inside the result dir, or "latest"; empty = fresh start'),
@@ -30,6 +49,8 @@ _FLAGS = (
     ('query_activation', ('--query_activation',), str, 'relu', 'activation of --query_transform activation: relu | tanh (Gs.Query.transform_activation)'),
     # not in the reference's command line: there one edits Gs.Prediction in Helpers/GlobalSettings.py
     ('cosine', ('--cosine',), 'flag', False, 'score with the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity) instead of the dot product'),
+    # not in the reference, which reports @10 only (Metrics.py:60-63)
+    ('cutoffs', ('--cutoffs',), cutoff_list, '', 'further metric cutoffs, e.g. 20,50,100 (each in 11..128): HR / NDCG / MAP @K beside the @10 triple, from one ranking at the largest (Gs.Evaluation.extra_cutoffs)'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '

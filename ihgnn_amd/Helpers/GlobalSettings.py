@@ -41,6 +41,9 @@ class Gs:
     class Prediction:
         use_cosine_similarity = False
 
+    class Evaluation:
+        extra_cutoffs = ()               # not in the reference (which reports @10 only): further cutoffs K in 11..128 (--cutoffs), HR / NDCG / MAP @K beside the @10 triple
+
     class Dataset:
         user_history_limit = 500
 

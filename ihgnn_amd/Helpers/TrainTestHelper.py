@@ -34,17 +34,19 @@ def print_network_parameters(module: nn.Module, name_filter: Optional[str] = Non
 def _evaluate_batched(model, logs, item_count: int, device: torch.device, indices) -> List[Tuple[int, Metrics]]:
     """Top-10 of many searches per launch (``ihg_score_topk`` / ``ihg_score_topk_cosine``, whichever head ``Gs.Prediction.use_cosine_similarity`` names: scores on
     the matrix cores, running top-10 in registers, no ``[C, I]`` matrix), one D2H copy per chunk (the reference scores one log at a time and syncs on every one,
-    ``TrainTestHelper.py:58-67``, ``Metrics.py:60-61``)."""
+    ``TrainTestHelper.py:58-67``, ``Metrics.py:60-61``).  With ``Gs.Evaluation.extra_cutoffs`` the ONE ranking per chunk is as deep as the largest cutoff
+    (``ihg_score_topk_deep``) and every cutoff's metrics are read from a prefix of it."""
     out: List[Tuple[int, Metrics]] = []
     chunk = 8192
-    k = min(10, item_count)
+    extras = tuple(Gs.Evaluation.extra_cutoffs)
+    k = min(max((10,) + extras), item_count)
     for lo in range(0, len(indices), chunk):
         part = indices[lo:lo + chunk]
         uq = torch.tensor([(logs[i][0], logs[i][1]) for i in part], dtype=torch.long, device=device)
         top = model.top_items(uq[:, 0], uq[:, 1], k)[0].tolist()          # HIP kernel: fp32-MFMA scores reduced to a running top-10 on chip
         for i, row in zip(part, top):
             _, _, items, flags, all_1 = logs[i]
-            out.append((i, Metrics.from_top_indices(row, items, flags, all_1)))
+            out.append((i, Metrics.at_cutoffs(row, items, flags, all_1, extras)))
     return out
 
 
@@ -82,9 +84,11 @@ def test_and_get_avg_metrics(model, dataset_train: GraphDataset, dataloader: Tes
         total.add_to_self(m)
         if get_long_tail_stat:
             per_user[logs[i][0]].append(m)
-    sums = ihg_dist.all_reduce_sums([total.HitRatio_at10, total.NDCG_at10, total.MAP_at10, float(len(scored))], device)
+    extras = tuple(Gs.Evaluation.extra_cutoffs) if hasattr(model, 'top_items') else ()
+    sums = ihg_dist.all_reduce_sums([total.HitRatio_at10, total.NDCG_at10, total.MAP_at10, float(len(scored))]
+                                    + [v for cutoff in extras for v in total.extra.get(cutoff, (0.0, 0.0, 0.0))], device)
     counted = int(round(sums[3]))
-    average = Metrics(sums[0], sums[1], sums[2]).divide_and_get_new(max(counted, 1))
+    average = Metrics(sums[0], sums[1], sums[2], {cutoff: tuple(sums[4 + 3 * n:7 + 3 * n]) for n, cutoff in enumerate(extras)}).divide_and_get_new(max(counted, 1))
     user_avgs = None
     if get_long_tail_stat:                                  # per-user sums and counts, added up over the ranks' shares of the logs
         table = torch.zeros(dataset_train.user_count, 4, dtype=torch.float64)

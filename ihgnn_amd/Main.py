@@ -47,6 +47,11 @@ def apply_prediction_settings(args) -> None:
     Gs.Prediction.use_cosine_similarity = bool(getattr(args, 'cosine', False))
 
 
+def apply_evaluation_settings(args) -> None:
+    """``--cutoffs`` -> ``Gs.Evaluation.extra_cutoffs``, assigned both ways like the head above (not in the reference, which reports @10 only)."""
+    Gs.Evaluation.extra_cutoffs = tuple(getattr(args, 'cutoffs', ()) or ())
+
+
 def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     args = parse_args(argv)
     rank, local_rank, world = ihg_dist.init_from_env()
@@ -78,6 +83,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     order = args.feature_order or 3
     apply_query_settings(args)
     apply_prediction_settings(args)
+    apply_evaluation_settings(args)
     if args.device == 'cpu':
         raise RuntimeError('ihgnn_amd has no CPU path: the hypergraph kernels are HIP-only')
     device = torch.device(f'cuda:{args.device}' if args.device else f'cuda:{local_rank}')

@@ -266,14 +266,15 @@ class RawGnn(nn.Module):
     def top_items(self, user_indices: Tensor, query_indices: Tensor, k: int = 10):
         """``(items [C, k] int32, scores [C, k])``: the ``k`` best items of each (user, query) pair over the whole catalogue, best
         first - what ``Metrics.calculate_on_all_items`` keeps of ``forward(u, q, None)`` (``Metrics.py:60-61``) - from the fused
-        HIP scoring + running top-k kernel; the ``[C, I]`` scores are never stored.  Ties: ascending item id.  No torch path: any feature width
+        HIP scoring + running top-k kernel; the ``[C, I]`` scores are never stored.  Ties: ascending item id.  ``k`` up to ``ops.score_topk_max_k()`` = 128
+        (beyond ten the kernel runs in passes, ``ops.score_topk_deep``; the reference itself stops at ten).  No torch path: any feature width
         ``d (L + 1)`` up to ``MAX_SCORED_WIDTH`` (checked at construction).  Scores with the head that ``Gs.Prediction.use_cosine_similarity`` names."""
         from .. import ops
         features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
         ds, head = self.dataset, self.prediction_layer
+        if k > ops.score_topk_max_k():
+            raise ValueError(f'RawGnn.top_items ranks at most {ops.score_topk_max_k()} items per pair, got k = {k}')
         k = min(k, ds.item_count)
-        if k > 10:
-            raise NotImplementedError('RawGnn.top_items keeps at most ten items per pair (the reference reports HR / NDCG / MAP @10, Metrics.py:60-88)')
         return ops.score_topk(features, user_indices, query_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph,
                               head.items_bias, head.lambda_muq, k, cosine=Gs.Prediction.use_cosine_similarity)
 

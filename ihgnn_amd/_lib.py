@@ -135,6 +135,11 @@ SIGNATURES = {
                                           c_void_p, c_int64, c_int64, c_void_p]),
     'ihg_score_topk_cosine': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
                                              c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    # ranking deeper than ten (csrc/eval.hip): ihg_score_topk's arguments, then the head, then the optional per-pair pass counts
+    'ihg_score_topk_max_k': (c_int32, []),
+    'ihg_score_topk_deep_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    'ihg_score_topk_deep': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
+                                           c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     'ihg_zero_floats': (ctypes.c_int, [c_void_p, c_int64, c_void_p]),
     'ihg_mark_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_batch_node_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

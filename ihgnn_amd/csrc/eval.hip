@@ -121,13 +121,37 @@ __global__ __launch_bounds__(kBlockThreads) void score_prepare_kernel(const floa
     }
 }
 
+// What a pair carries from one pass of the deep top-k (k > kTopMax, ihg_score_topk_deep) to the next: `count` ranks are in the output, the last of them is the
+// boundary (b_val, b_idx); `passes` counts the passes that found the pair incomplete.
+struct DeepState {
+    float b_val;
+    int32_t b_idx;
+    int32_t count;
+    int32_t passes;
+};
+
 // grid (pair blocks of 32 PB pairs, item slices); 512 threads.  partial[(pair * n_lists + list) * kTopMax + p]
-template <int PB, bool COSINE = false>
+// DEEP (ihg_score_topk_deep): a candidate enters a lane's list only if it ranks strictly after its pair's boundary, and a workgroup whose pairs all have
+// `target` ranks returns before it touches LDS or the item fragments.  The scores are those of the plain kernel, bit for bit: one expression, one item order.
+template <bool DEEP>
+struct DeepArgs {};
+template <>
+struct DeepArgs<true> {
+    const DeepState* state;
+    int target;                                                             // min(k, n_items): the ranks a complete pair has
+};
+
+template <int PB, bool COSINE = false, bool DEEP = false>
 __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
     const float* __restrict__ feat, int64_t ld, int dim, int ksteps, const v4u* __restrict__ frag, const float2* __restrict__ aux, int64_t n_items,
     const int64_t* __restrict__ users, const int64_t* __restrict__ queries, int64_t query_row0, float lam, int64_t n_pairs,
-    float* __restrict__ part_val, int32_t* __restrict__ part_idx) {
+    float* __restrict__ part_val, int32_t* __restrict__ part_idx, [[maybe_unused]] const DeepArgs<DEEP> deep) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];    // mixed planes: [32 PB][hi: 2 dp bytes | lo: 2 dp bytes | 16 bytes of padding], then pinv[32 PB]
+    if constexpr (DEEP) {                                                   // every wave asks the same question of the same (read-only) state: no barrier
+        const int64_t pr = static_cast<int64_t>(blockIdx.x) * (32 * PB) + (threadIdx.x & 63);
+        const bool open = (threadIdx.x & 63) < 32 * PB && pr < n_pairs && deep.state[pr].count < deep.target;
+        if (__ballot(open) == 0) return;
+    }
     const int dp = 16 * ksteps;
     const int row_bytes = 4 * dp + 16;                                      // (the padding spreads the pairs' equal chunks over the banks)
     float* pinv = reinterpret_cast<float*>(smem + static_cast<size_t>(32 * PB) * row_bytes);
@@ -189,6 +213,17 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
     TopList top[PB];
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) top[pb].init();
+    [[maybe_unused]] float b_val[PB];
+    [[maybe_unused]] int b_idx[PB];
+    if constexpr (DEEP) {
+#pragma unroll
+        for (int pb = 0; pb < PB; ++pb) {
+            int64_t pr = pair0 + 32 * pb + n31;
+            pr = pr < n_pairs ? pr : n_pairs - 1;
+            b_val[pb] = deep.state[pr].b_val;
+            b_idx[pb] = deep.state[pr].b_idx;
+        }
+    }
 
     constexpr int PF = 4;                                                   // k-steps of item fragments in flight
     for (int64_t tile = tile_begin; tile < tile_end; ++tile) {
@@ -237,7 +272,11 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
 #pragma unroll
                 for (int pb = 0; pb < PB; ++pb) {
                     const float s = acc[pb][4 * r4 + x] * (ax[x].x * my_pinv[pb]) + ax[x].y;
-                    if (i0 + x < n_items && ranks_before(s, i, top[pb].val[kTopMax - 1], top[pb].idx[kTopMax - 1])) top[pb].insert(s, i);
+                    if constexpr (DEEP) {
+                        if (i0 + x < n_items && ranks_before(b_val[pb], b_idx[pb], s, i) && ranks_before(s, i, top[pb].val[kTopMax - 1], top[pb].idx[kTopMax - 1])) top[pb].insert(s, i);
+                    } else {
+                        if (i0 + x < n_items && ranks_before(s, i, top[pb].val[kTopMax - 1], top[pb].idx[kTopMax - 1])) top[pb].insert(s, i);
+                    }
                 }
             }
         }
@@ -298,6 +337,128 @@ __global__ __launch_bounds__(kBlockThreads) void merge_topk_kernel(const float* 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Deep top-k (kTopMax < k <= kDeepMax) in passes; the lanes keep their lists of ten.  A pass = score_topk_kernel<PB, COSINE, true> (the candidates that rank after the
+// pair's boundary) + merge_deep_kernel: the pair's n_lists lists are sorted best first over disjoint items, so with t = the best-ranking LAST entry over the full lists
+// (a list with an empty slot hides nothing) every item that ranks at or before t is in some list, and the union of the lists is exact down to t.  The merge appends
+// those candidates in order, stops at k, and moves the boundary to the last one appended.  A full list alone brings ten, so an incomplete pair gains at least ten ranks
+// per pass: ceil(min(k, n_items) / 10) passes always suffice, and the host launches exactly that many - no read-back, no atomics, no spinning.
+// ------------------------------------------------------------------------------------------------
+constexpr int kDeepMax = 128;
+constexpr int kDeepListsPerLane = 16;       // 64 slices x 8 waves x 2 lane halves = 1,024 lists at most (eval_slices)
+
+// once per call: no rank emitted, every item after the boundary; the output holds the fill of merge_topk_kernel (-FLT_MAX, -1) wherever no rank will be written
+__global__ __launch_bounds__(kBlockThreads) void deep_init_kernel(DeepState* __restrict__ state, int64_t n_pairs, int k, float* __restrict__ out_val, int32_t* __restrict__ out_idx) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < n_pairs * k; t += stride) {
+        out_val[t] = -FLT_MAX;
+        out_idx[t] = -1;
+        if (t < n_pairs) state[t] = DeepState{__builtin_inff(), -1, 0, 0};
+    }
+}
+
+// one wave per incomplete pair.  Lane l owns lists l, l + 64, ...: the head of each in registers (statically indexed: no scratch), the best head of the wave by
+// shuffles, and the one lane that owned it loads its list's next entry - one load per emitted rank, where k full scans of the candidates would be k x n_lists x 10.
+__global__ __launch_bounds__(kBlockThreads) void merge_deep_kernel(const float* __restrict__ part_val, const int32_t* __restrict__ part_idx, int64_t n_pairs, int n_lists, int k,
+                                                                    int target, DeepState* __restrict__ state, float* __restrict__ out_val, int32_t* __restrict__ out_idx,
+                                                                    int32_t* __restrict__ passes) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t pair = global_wave_id(); pair < n_pairs; pair += global_wave_count()) {
+        const DeepState st = state[pair];
+        if (st.count >= target) continue;                                   // complete (wave-uniform): its lists are stale and its output is final
+        const float* pv = part_val + pair * n_lists * kTopMax;
+        const int32_t* pi = part_idx + pair * n_lists * kTopMax;
+        float hv[kDeepListsPerLane];
+        int hi[kDeepListsPerLane], pos[kDeepListsPerLane];
+        float tv = -FLT_MAX;                                                // t: nothing ranks after (-FLT_MAX, INT_MAX), so with no full list every candidate is taken
+        int ti = INT_MAX;
+#pragma unroll
+        for (int j = 0; j < kDeepListsPerLane; ++j) {
+            const int list = lane + kWave * j;
+            hv[j] = -FLT_MAX;
+            hi[j] = INT_MAX;
+            pos[j] = 0;
+            if (list < n_lists) {
+                hv[j] = pv[list * kTopMax];
+                hi[j] = pi[list * kTopMax];
+                const float lv = pv[list * kTopMax + kTopMax - 1];
+                const int li = pi[list * kTopMax + kTopMax - 1];
+                if (li != INT_MAX && ranks_before(lv, li, tv, ti)) {
+                    tv = lv;
+                    ti = li;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(tv, off);
+            const int oi = __shfl_xor(ti, off);
+            if (ranks_before(ov, oi, tv, ti)) {
+                tv = ov;
+                ti = oi;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kDeepListsPerLane; ++j)
+            if (ranks_before(tv, ti, hv[j], hi[j])) hi[j] = INT_MAX;        // a head after t: the list has nothing more to give (an empty head has INT_MAX already)
+        int count = st.count;
+        float last_v = st.b_val;
+        int last_i = st.b_idx;
+        while (count < k) {
+            float bv = -FLT_MAX;
+            int bi = INT_MAX, bj = 0;
+#pragma unroll
+            for (int j = 0; j < kDeepListsPerLane; ++j)
+                if (hi[j] != INT_MAX && (bi == INT_MAX || ranks_before(hv[j], hi[j], bv, bi))) {
+                    bv = hv[j];
+                    bi = hi[j];
+                    bj = j;
+                }
+            float wv = bv;
+            int wi = bi;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ov = __shfl_xor(wv, off);
+                const int oi = __shfl_xor(wi, off);
+                if (oi != INT_MAX && (wi == INT_MAX || ranks_before(ov, oi, wv, wi))) {
+                    wv = ov;
+                    wi = oi;
+                }
+            }
+            if (wi == INT_MAX) break;                                       // every list is spent down to t
+            if (lane == 0) {
+                out_val[pair * k + count] = wv;
+                out_idx[pair * k + count] = wi;
+            }
+            ++count;
+            last_v = wv;
+            last_i = wi;
+            if (bi == wi) {                                                 // the one lane that held the winner (items are distinct across lists): its list's next entry
+#pragma unroll
+                for (int j = 0; j < kDeepListsPerLane; ++j)
+                    if (j == bj) {
+                        const int np = pos[j] + 1;
+                        float nv = -FLT_MAX;
+                        int ni = INT_MAX;
+                        if (np < kTopMax) {
+                            const int at = (lane + kWave * j) * kTopMax + np;
+                            nv = pv[at];
+                            ni = pi[at];
+                            if (ranks_before(tv, ti, nv, ni)) ni = INT_MAX;
+                        }
+                        pos[j] = np;
+                        hv[j] = nv;
+                        hi[j] = ni;
+                    }
+            }
+        }
+        if (lane == 0) {
+            state[pair] = DeepState{last_v, last_i, count, st.passes + 1};
+            if (passes != nullptr) passes[pair] = st.passes + 1;                // (every pair is incomplete in the first pass: each passes[c] is written)
+        }
+    }
+}
+
 constexpr int kEvalWavesPerBlock = kEvalThreads / kWave;
 
 inline int eval_ksteps(int dim) { return (dim + 15) / 16; }
@@ -349,12 +510,56 @@ int score_topk_launch(const char* what, const float* features, int64_t ld, int32
     const size_t lds = eval_lds_bytes(dim, pb);
     if (pb == 2)
         hipLaunchKernelGGL((score_topk_kernel<2, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx);
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{});
     else
         hipLaunchKernelGGL((score_topk_kernel<1, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx);
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{});
     hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs,
                        static_cast<int>(n_lists * kTopMax), k, top_scores, top_items);
+    return check_launch(what);
+}
+
+inline int64_t eval_lists(int64_t n_pairs, int64_t n_items, int dim) { return static_cast<int64_t>(eval_slices(n_pairs, n_items, dim)) * kEvalWavesPerBlock * 2; }
+
+template <bool COSINE>
+int score_topk_deep_launch(const char* what, const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
+                           const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
+                           int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t* passes, ihg_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
+    const int slices = eval_slices(n_pairs, n_items, dim);
+    const int64_t n_lists = eval_lists(n_pairs, n_items, dim);
+    v4u* frag = static_cast<v4u*>(workspace);
+    float2* aux = reinterpret_cast<float2*>(static_cast<unsigned char*>(workspace) + eval_frag_bytes(n_items, dim));
+    float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
+    int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
+    DeepState* state = reinterpret_cast<DeepState*>(part_idx + n_pairs * n_lists * kTopMax);
+    const int target = static_cast<int>(std::min<int64_t>(k, n_items));
+    hipLaunchKernelGGL(score_prepare_kernel<COSINE>, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux);
+    hipLaunchKernelGGL(deep_init_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n_pairs * k + kBlockThreads - 1) / kBlockThreads, 4096))), dim3(kBlockThreads), 0, s, state, n_pairs,
+                       k, top_scores, top_items);
+    static bool attr_set[64] = {};                           // per device ordinal, as in score_topk_launch
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
+    if (device < 0 || device >= 64 || !attr_set[device]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (device >= 0 && device < 64) attr_set[device] = true;
+    }
+    const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
+    const size_t lds = eval_lds_bytes(dim, pb);
+    const DeepArgs<true> deep{state, target};
+    const int n_passes = (target + kTopMax - 1) / kTopMax;
+    for (int pass = 0; pass < n_passes; ++pass) {
+        if (pb == 2)
+            hipLaunchKernelGGL((score_topk_kernel<2, COSINE, true>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
+                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep);
+        else
+            hipLaunchKernelGGL((score_topk_kernel<1, COSINE, true>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
+                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep);
+        hipLaunchKernelGGL(merge_deep_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs, static_cast<int>(n_lists), k, target, state, top_scores,
+                           top_items, passes);
+    }
     return check_launch(what);
 }
 
@@ -386,6 +591,32 @@ int ihg_score_topk_cosine(const float* features, int64_t ld, int32_t dim, int64_
                    const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
                    int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
     return score_topk_launch<true>("ihg_score_topk_cosine", features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace, workspace_bytes, stream);
+}
+
+int32_t ihg_score_topk_max_k(void) { return kDeepMax; }
+
+int64_t ihg_score_topk_deep_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) {
+    if (n_pairs <= 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax) return 0;
+    return ihg_score_topk_workspace_bytes(n_pairs, n_items, dim) + n_pairs * static_cast<int64_t>(sizeof(DeepState));
+}
+
+int ihg_score_topk_deep(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
+                        const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
+                        int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes, ihg_stream_t stream) {
+    const char* what = "ihg_score_topk_deep";
+    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kDeepMax);
+    if (n_pairs == 0) return IHG_OK;
+    if (features == nullptr || item_bias == nullptr || users == nullptr || queries == nullptr || top_scores == nullptr || top_items == nullptr)
+        return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
+    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
+    if (eval_lists(n_pairs, n_items, dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", what);
+    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k))
+        return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", what);
+    return cosine != 0 ? score_topk_deep_launch<true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace,
+                                                      workspace_bytes, passes, stream)
+                       : score_topk_deep_launch<false>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace,
+                                                       workspace_bytes, passes, stream);
 }
 
 }  // extern "C"

@@ -1776,7 +1776,10 @@ def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int
     """Evaluation scoring: for every (user, query) pair the ``k`` best items over ALL items and their HEM scores,
     ``(top_items [C, k] int32, top_scores [C, k])``, best first, ties in ascending item order; the ``[C, I]`` score matrix is
     never materialised.  ``features`` = the cached ``[N, D]`` propagation output (any width up to ``score_topk_max_width()``); items are its rows from ``item_row0`` on.
-    ``cosine``: the cosine-similarity head (``Gs.Prediction.use_cosine_similarity``) - same kernels, the rows' inverse norms folded into their scale factors."""
+    ``cosine``: the cosine-similarity head (``Gs.Prediction.use_cosine_similarity``) - same kernels, the rows' inverse norms folded into their scale factors.
+    ``k`` > 10 goes to ``score_topk_deep`` (up to ``score_topk_max_k()``)."""
+    if k > 10:
+        return score_topk_deep(features, users, queries, query_row0, item_row0, item_bias, lam, k, cosine=cosine)[:2]
     lib = _lib.load()
     if not score_topk_supported(features):
         raise _lib.IhgnnHipError(f'ihg_score_topk needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
@@ -1795,6 +1798,36 @@ def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int
                                                _ptr(users), _ptr(queries), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws),
                                                ws.numel() * 4, _stream()), 'ihg_' + name)
     return top_items, top_scores
+
+
+def score_topk_max_k() -> int:
+    """The deepest ranking ``ihg_score_topk_deep`` returns (128)."""
+    return int(_lib.load().ihg_score_topk_max_k())
+
+
+def score_topk_deep(features: Tensor, users: Tensor, queries: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int, cosine: bool = False):
+    """``score_topk`` for any ``1 <= k <= score_topk_max_k()``: ``(top_items [C, k] int32, top_scores [C, k], passes [C] int32)``.  The kernels keep their lists of ten
+    and the call runs in passes that each rank at least ten more items of every pair that is not complete yet (``include/ihgnn_hip.h`` has the scheme);
+    ``passes[c]`` = the passes that found pair ``c`` incomplete, at most ``ceil(min(k, I) / 10)``.  Exact, with the tie order and the ``-1`` tail of ``score_topk``."""
+    lib = _lib.load()
+    if not score_topk_supported(features):
+        raise _lib.IhgnnHipError(f'ihg_score_topk_deep needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
+    n_pairs = int(users.shape[0])
+    n_items = int(features.shape[0]) - int(item_row0)
+    dim = int(features.shape[1])
+    users = users.to(device=features.device, dtype=torch.int64).contiguous()
+    queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
+    bias = item_bias.detach().to(torch.float32).contiguous()
+    width = max(int(k), 0)
+    top_scores = torch.empty(n_pairs, width, dtype=torch.float32, device=features.device)
+    top_items = torch.empty(n_pairs, width, dtype=torch.int32, device=features.device)
+    passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
+    ws = _workspace(int(lib.ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
+    with profiler.kernel('score_topk_deep_cosine' if cosine else 'score_topk_deep', n_pairs, dim):
+        _lib.check(lib.ihg_score_topk_deep(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), float(lam),
+                                           n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)), _ptr(passes), _stream()),
+                   'ihg_score_topk_deep')
+    return top_items, top_scores, passes
 
 
 def batch_node_rows(users: Tensor, queries: Tensor, items: Tensor, query_row0: int, item_row0: int) -> Tensor:

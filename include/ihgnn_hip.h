@@ -574,6 +574,28 @@ int ihg_score_topk_cosine(const float* features, int64_t ld, int32_t dim, int64_
                           int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE: ranking deeper than ten.  ihg_score_topk_deep is ihg_score_topk (its arguments, outputs, tie order, width limit and -1 tail; `cosine` != 0: the scores of
+ * ihg_score_topk_cosine) for 1 <= k <= ihg_score_topk_max_k() = 128; any other k answers IHG_ERR_INVALID before anything is launched.
+ * Scheme: the kernels keep their lists of ten per lane and the call runs in passes.  Per pair the workspace carries `count`, the ranks already in the output, and the
+ * boundary, the last of them.  A pass scores every item again (the split item rows are prepared once per call) and lets a candidate into a lane's list only if it
+ * ranks strictly after its pair's boundary; a workgroup whose pairs are all complete (count == min(k, n_items)) returns at once.  The pair's lists are sorted and
+ * cover disjoint items, so with t = the best-ranking tenth entry over the FULL lists every item that ranks at or before t is in some list: a merge kernel (one wave per
+ * pair, one head per list in registers) appends exactly those to the output, in order, stops at k and moves the boundary.  Every pass adds at least ten ranks to an
+ * incomplete pair, so ceil(min(k, n_items) / 10) passes always suffice - 13 at k = 128 - and the call launches that fixed number of (score, merge) pairs: no
+ * device-to-host read, no allocation, no atomics, no spinning; a stream capture holds it.  Random scores need one scoring pass at a catalogue's size; scores sorted by
+ * item id, or all equal, need 8 at k = 128.  Every pass computes bit-identical scores (one kernel, one item order), so the boundary comparison is exact under ties and
+ * two calls return the same bits; k <= 10 returns the bits of ihg_score_topk / ihg_score_topk_cosine.
+ *   passes (optional, [n_pairs] int32): passes[c] = the number of passes that found pair c incomplete.
+ * Workspace: ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k) bytes (that of ihg_score_topk + 16 bytes per pair).
+ */
+int32_t ihg_score_topk_max_k(void);
+int64_t ihg_score_topk_deep_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k);
+int ihg_score_topk_deep(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
+                        const float* item_bias, const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs,
+                        int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes,
+                        ihg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE: the attention of the GAT baseline over the pairwise graph (csrc/gat.hip).  Replaces GATLayer.forward after its transform
  * (Models/GnnLayers.py:98-115: the [nnz, 2, d] row gather, feature_aggregate, dgl.ops.edge_softmax and dgl.ops.u_mul_e_sum) and autograd's backward of it.
  * Graph: the symmetric CSR of the pairwise adjacency (ihg_build_pair_csr) - entry p of row v with column u = ids[p] is the edge u -> v, so row v lists
