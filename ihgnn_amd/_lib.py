@@ -73,6 +73,10 @@ SIGNATURES = {
     'ihg_interact_bwd_gathered_supported': (c_int32, [c_int32, c_int32, c_int64, c_int64]),
     'ihg_interact_bwd_gathered': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                                  c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
+    'ihg_interact_bwd_gathered_first_order_supported': (c_int32, [c_int32, c_int32, c_int64, c_int64]),
+    'ihg_interact_bwd_gathered_first_order': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                                             c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32,
+                                                             c_void_p]),
     'ihg_node_pair_sums': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
                                           c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'ihg_node_interact_fwd_supported': (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64]),

@@ -1233,9 +1233,11 @@ __global__ __launch_bounds__(kWsThreads) void interact_bwd_members_strip_kernel(
 // Adds up the boundary runs of the user-reduced member-gradient kernels in workgroup order.  One workgroup per table entry: the entry
 // that opens a user's run (the valid entry before it belongs to another user) walks on while the following entries carry the same
 // user - nearly always one or two - and writes dh[user]; every other workgroup leaves at once.  Same order of additions as a single
-// walk over the table.
+// walk over the table.  bnd_dp != nullptr: a second value table under the same users (the first-order run sums of the gathering split kernel), added in the
+// same order into dp_user.
 __global__ __launch_bounds__(256) void user_boundary_fixup_kernel(const float* __restrict__ bnd_val, const int32_t* __restrict__ bnd_user, int n_entries, int d,
-                                                                  float* __restrict__ dh_user, int64_t ld_dh) {
+                                                                  float* __restrict__ dh_user, int64_t ld_dh, const float* __restrict__ bnd_dp,
+                                                                  float* __restrict__ dp_user, int64_t ld_dp) {
     const int k0 = blockIdx.x, c = threadIdx.x;
     const int user = bnd_user[k0];
     if (user < 0 || c >= d) return;
@@ -1244,14 +1246,18 @@ __global__ __launch_bounds__(256) void user_boundary_fixup_kernel(const float* _
         if (u == user) return;                    // an earlier entry opens this run
         if (u >= 0) break;
     }
+    const bool second = bnd_dp != nullptr;
     float acc = bnd_val[static_cast<int64_t>(k0) * d + c];
+    float acc_dp = second ? bnd_dp[static_cast<int64_t>(k0) * d + c] : 0.f;
     for (int k = k0 + 1; k < n_entries; ++k) {
         const int u = bnd_user[k];
         if (u < 0) continue;
         if (u != user) break;
         acc += bnd_val[static_cast<int64_t>(k) * d + c];
+        if (second) acc_dp += bnd_dp[static_cast<int64_t>(k) * d + c];
     }
     dh_user[static_cast<int64_t>(user) * ld_dh + c] = acc;
+    if (second) dp_user[static_cast<int64_t>(user) * ld_dp + c] = acc_dp;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1904,11 +1910,12 @@ constexpr int kPipeGrid = 256;          // wave-specialised and strip kernels: o
 inline int64_t boundary_ranges(int dim) { return dim == 128 || dim == 64 || dim == 256 ? kPipeGrid : (dim == kNarrowDim ? kNarrowMemberRanges : 0); }
 
 // The backward's workspace in the order ihg_interact_bwd_workspace_bytes sizes it: packed weights, weight slabs, the boundary runs of the user-reduced form
-// (values, then their users), the planes of the split / narrow member kernels.
+// (values, the first-order values beside them, then their users), the planes of the split / narrow member kernels.
 struct BwdWorkspace {
     float* wq;
     float* slabs;
     float* bnd_val;
+    float* bnd_dp;
     int32_t* bnd_user;
     void* planes;
 };
@@ -1917,7 +1924,8 @@ inline BwdWorkspace carve_bwd_workspace(void* workspace, int dim, int order) {
     ws.wq = static_cast<float*>(workspace);
     ws.slabs = ws.wq + packed_weight_floats(dim, order);
     ws.bnd_val = ws.slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order);
-    ws.bnd_user = reinterpret_cast<int32_t*>(ws.bnd_val + 2LL * boundary_ranges(dim) * dim);
+    ws.bnd_dp = ws.bnd_val + 2LL * boundary_ranges(dim) * dim;
+    ws.bnd_user = reinterpret_cast<int32_t*>(ws.bnd_dp + 2LL * boundary_ranges(dim) * dim);
     ws.planes = ws.bnd_user + 2LL * boundary_ranges(dim);
     return ws;
 }
@@ -2031,14 +2039,16 @@ EdgeRows member_gradients(const BwdCall& c) {
         int entries = 0;
         launch_members_split(dim, c.order, c.h, c.ld_h, c.i3, c.w, c.ld_w, c.ws.planes, c.cot, c.g, n_edges, c.ur, &entries, c.s);
         if (c.ur != nullptr)
-            hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, c.s, c.ur->bnd_val, c.ur->bnd_user, entries, dim, c.ur->dh, c.ur->ld_dh);
+            hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(entries), dim3(std::max(128, dim)), 0, c.s, c.ur->bnd_val, c.ur->bnd_user, entries, dim, c.ur->dh, c.ur->ld_dh,
+                               c.ur->dp != nullptr ? c.ur->bnd_dp : nullptr, c.ur->dp, c.ur->ld_dp);
     } else if (strip_bwd_ok(dim, c.g, c.ld_h) && dim == 256) {             // wq is strip-packed
         launch_members(interact_bwd_members_strip256_kernel<NBLK>, dim3(grid_for_tiles(n_edges, kStrip256TE, kStrip256Grid), 4), kWsThreads, c);
     } else if (strip_bwd_ok(dim, c.g, c.ld_h) && c.ur != nullptr) {        // user-reduced form: g is [E, 2, d]
         const int grid = grid_for_tiles(n_edges, kStripTE, kPipeGrid);
         hipLaunchKernelGGL((interact_bwd_members_strip_kernel<128, NBLK, true>), dim3(grid), dim3(kWsThreads), 0, c.s, c.h, c.ld_h, c.i3, wq, dout, ld_dout, c.g, n_edges, c.ur->dh,
                            c.ur->ld_dh, c.ur->bnd_val, c.ur->bnd_user);
-        hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(2 * grid), dim3(128), 0, c.s, c.ur->bnd_val, c.ur->bnd_user, 2 * grid, dim, c.ur->dh, c.ur->ld_dh);
+        hipLaunchKernelGGL(user_boundary_fixup_kernel, dim3(2 * grid), dim3(128), 0, c.s, c.ur->bnd_val, c.ur->bnd_user, 2 * grid, dim, c.ur->dh, c.ur->ld_dh,
+                           static_cast<const float*>(nullptr), static_cast<float*>(nullptr), int64_t{0});
     } else if (strip_bwd_ok(dim, c.g, c.ld_h)) {
         hipLaunchKernelGGL((interact_bwd_members_strip_kernel<128, NBLK, false>), dim3(grid_for_tiles(n_edges, kStripTE, kPipeGrid)), dim3(kWsThreads), 0, c.s, c.h, c.ld_h, c.i3, wq,
                            dout, ld_dout, c.g, n_edges, static_cast<float*>(nullptr), int64_t{0}, static_cast<float*>(nullptr), static_cast<int32_t*>(nullptr));
@@ -2239,7 +2249,7 @@ int64_t ihg_interact_bwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t o
     (void)n_edges;
     if (!mfma_dim(dim) || (order != 2 && order != 3)) return 0;
     const int64_t w_floats = packed_weight_floats(dim, order);
-    const int64_t boundary = 2LL * boundary_ranges(dim) * dim + 2LL * boundary_ranges(dim);               // user-reduced form: boundary runs + their users
+    const int64_t boundary = 2 * 2LL * boundary_ranges(dim) * dim + 2LL * boundary_ranges(dim);           // user-reduced form: boundary runs (two value tables) + their users
     const int64_t planes = dim == kNarrowDim ? narrow_members_floats(order) : split_plane_floats(dim, order);
     return (w_floats + static_cast<int64_t>(weight_slabs(dim)) * w_floats + boundary + planes) * static_cast<int64_t>(sizeof(float));
 }
@@ -2262,7 +2272,7 @@ int ihg_interact_bwd_user_reduced(const float* h, int64_t ld_h, const int32_t* i
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
-    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user};
+    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user, nullptr, 0, nullptr};
     launch_pack_weights(true, w, ld_w, dim, order, nullptr, ws.wq, s);
     dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::rows(dout, ld_dout), g2, &ur, dw, ld_dw, ws, n_edges, s});
     return check_launch(name);
@@ -2286,7 +2296,7 @@ int ihg_interact_bwd_user_reduced_planes(const float* h, int64_t ld_h, const int
         return rc;
     // (the shape is one the split kernel takes: member_gradients launches it and the boundary runs' sum, nothing else)
     const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
-    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user};
+    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user, nullptr, 0, nullptr};
     dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::planes(planes_rows, dim, inv_scale), g2, &ur, nullptr, 0, ws, n_edges,
                                          static_cast<hipStream_t>(stream)});
     return check_launch(name);
@@ -2296,27 +2306,55 @@ int32_t ihg_interact_bwd_gathered_supported(int32_t dim, int32_t order, int64_t 
     return dim != 256 && ihg_interact_bwd_user_reduced_supported(dim, order, ld_h) && (split_arith_enabled() || dim == kNarrowDim) && ld_dy >= dim && ld_dy % 4 == 0 && ld_dy < (int64_t{1} << 30) ? 1 : 0;
 }
 
-int ihg_interact_bwd_gathered(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
-                              const float* dy, int64_t ld_dy, const float* dy_scale, float* dout, int64_t ld_dout, float* g2, float* dh, int64_t ld_dh,
-                              float* dw, int64_t ld_dw, void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream) {
-    const char* name = "ihg_interact_bwd_gathered";
+// The users' first-order gradient from the member kernel: the widths the gathering split kernel has that form for
+int32_t ihg_interact_bwd_gathered_first_order_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_dy) {
+    return dim == 128 && split_arith_enabled() && ihg_interact_bwd_gathered_supported(dim, order, ld_h, ld_dy) ? 1 : 0;
+}
+
+}  // extern "C"
+
+namespace {
+// ihg_interact_bwd_gathered, and with dp != nullptr ihg_interact_bwd_gathered_first_order
+int interact_bwd_gathered(const char* name, bool supported, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order, const float* dy,
+                          int64_t ld_dy, const float* dy_scale, float* dout, int64_t ld_dout, float* g2, float* dh, int64_t ld_dh, float* dp, int64_t ld_dp, float* dw,
+                          int64_t ld_dw, void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream) {
     bool tiled;
     // dout == NULL: the hyperedges' cotangents are formed and used on chip only - allowed where no weight step reads them
-    if (int rc = edge_form_check({name, "shape or arithmetic mode", ihg_interact_bwd_gathered_supported(dim, order, ld_h, ld_dy) != 0, Empty::kRefused, true,
-                                  ihg_interact_bwd_workspace_bytes(n_edges, dim, order)},
+    if (int rc = edge_form_check({name, "shape or arithmetic mode", supported, Empty::kRefused, true, ihg_interact_bwd_workspace_bytes(n_edges, dim, order)},
                                  dim, order, n_edges,
                                  {{h, ld_h, Rows::kDim, kVector}, {i3, 0, Rows::kNone, 0}, {w, ld_w, Rows::kWeights, kVector}, {dy, ld_dy, Rows::kDim, kVector}, {dout, ld_dout, Rows::kDim, kVector | kLdIfThere | (dw != nullptr ? 0u : kOptional)},
-                                  {g2, 0, Rows::kNone, kVector}, {dh, ld_dh, Rows::kDim, 0}, {dw, ld_dw, Rows::kWeights, kOptional}, {workspace, 0, Rows::kNone, kVector}},
+                                  {g2, 0, Rows::kNone, kVector}, {dh, ld_dh, Rows::kDim, 0}, {dp, ld_dp, Rows::kDim, kOptional}, {dw, ld_dw, Rows::kWeights, kOptional},
+                                  {workspace, 0, Rows::kNone, kVector}},
                                  workspace_bytes, &tiled))
         return rc;
     const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);  // (the fp32 fragment image of w, ws.wq, is not needed by the split kernels)
     if (dim == kNarrowDim ? !narrow_members_ok(dim, order, g2, ld_h, ld_dy, dy)
                           : (!split_members_ok(dim, order, g2, ld_h, ld_dy, dy) || (dw != nullptr && !split_weight_ok(dim, order, ld_h, ld_dout, dout))))
         return fail(IHG_ERR_INVALID, "%s: the kernels do not take these strides / alignments", name);
-    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user};
+    const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user, dp, dp != nullptr ? ld_dp : 0, ws.bnd_dp};
     dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::node_level(dy, ld_dy, dy_scale, dout, ld_dout), g2, &ur, dw, ld_dw, ws, n_edges,
                                          static_cast<hipStream_t>(stream)});
     return check_launch(name);
+}
+}  // namespace
+
+extern "C" {
+
+int ihg_interact_bwd_gathered(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
+                              const float* dy, int64_t ld_dy, const float* dy_scale, float* dout, int64_t ld_dout, float* g2, float* dh, int64_t ld_dh,
+                              float* dw, int64_t ld_dw, void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream) {
+    return interact_bwd_gathered("ihg_interact_bwd_gathered", ihg_interact_bwd_gathered_supported(dim, order, ld_h, ld_dy) != 0, h, ld_h, i3, w, ld_w, order, dy, ld_dy,
+                                 dy_scale, dout, ld_dout, g2, dh, ld_dh, nullptr, 0, dw, ld_dw, workspace, workspace_bytes, n_edges, dim, stream);
+}
+
+int ihg_interact_bwd_gathered_first_order(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
+                                          const float* dy, int64_t ld_dy, const float* dy_scale, float* dout, int64_t ld_dout, float* g2, float* dh, int64_t ld_dh,
+                                          float* dp, int64_t ld_dp, float* dw, int64_t ld_dw, void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim,
+                                          ihg_stream_t stream) {
+    const char* name = "ihg_interact_bwd_gathered_first_order";
+    if (dp == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", name);
+    return interact_bwd_gathered(name, ihg_interact_bwd_gathered_first_order_supported(dim, order, ld_h, ld_dy) != 0, h, ld_h, i3, w, ld_w, order, dy, ld_dy, dy_scale, dout,
+                                 ld_dout, g2, dh, ld_dh, dp, ld_dp, dw, ld_dw, workspace, workspace_bytes, n_edges, dim, stream);
 }
 
 int ihg_interact_bwd(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,

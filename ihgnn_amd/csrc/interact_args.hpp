@@ -33,7 +33,9 @@ struct EdgeCotangent {
 // The outputs of the user-reduced form (hyperedges numbered by user): the kernel sums the user slot on chip and writes dh[users] itself, the member buffer g is
 // [E, 2, d]; runs that cross a tile range go through the boundary table (values, then their users).  A launcher that takes a pointer to this takes nullptr for
 // the [E, 3, d] form.
-struct UserReduced { float* dh; int64_t ld_dh; float* bnd_val; int32_t* bnd_user; };
+// dp != nullptr (the gathering split kernel, where first_order_users_ok says so): the kernel also sums the cotangents it forms over each user's run - the users' rows of
+// the first-order gradient, [N, ld_dp] - with the boundary runs in bnd_dp, a second value table indexed like bnd_val under the same bnd_user.
+struct UserReduced { float* dh; int64_t ld_dh; float* bnd_val; int32_t* bnd_user; float* dp; int64_t ld_dp; float* bnd_dp; };
 
 // order -> NBLK, the number of product blocks a kernel template is instantiated for (order 2: uq ui qi, order 3: and uqi): Step::run<NBLK>(call)
 template <typename Step, typename Call>

@@ -100,30 +100,42 @@ __device__ unsigned long long g_phase_trace[2][1024][4];
 // the node -> hyperedge kernel (K5) and store it to dout_store (each column half its 64 columns) for the weight-gradient kernel and the
 // first-order scatter: K5's launch - memory-bound, on a chip whose issue slots it leaves idle - disappears into a kernel that is
 // issue-bound and leaves the memory pipes idle.
+// FO (GATHER, D = 128): the users' rows of the layer's FIRST-ORDER gradient, dp[u] = sum over u's hyperedges of dout[e] - the two-hop operator's row of a user
+// (deg(u) D[u] + the D rows of its hyperedges' queries and items, D = dy_scale o dy) - is a run sum of the cotangents this kernel has on chip.  A service thread keeps
+// its column half's eight fp32 values of a tile (K5's sum, before the row scaling and the split) from the phase that splits the tile to the phase of the tile's
+// product rule - two register sets, by tile parity - and lays them into image 1 (utile[1], shaped and double-buffered like the user-slot gradients' image 0) there; a
+// phase later the matrix waves run the SAME window / chain steps over both images in their innermost loops: one ballot, one set of run starts and scalar
+// conditions, one user id per run, two sums.  Runs inside a range go to dp_user[user], the range's first and last run to bnd_dp - a second value table under the
+// same bnd_user - and user_boundary_fixup_kernel adds both tables in the same order.  Costs 17 registers (233), 21.5 KB of LDS (146 KB) and ~ 90 us at C3 (1,337 ->
+// 1,426 us: ~ 350 cycles per phase, the added instructions of both roles on the shared issue port); the two-hop launch behind the kernel then leaves the users' rows
+// out (724 -> 505 us).  Rows of users without hyperedges are not written (the caller zeroes them, as for dh).
 // PLANES (round 5; D = 256): `dout` holds the hyperedges' cotangents already scaled and taken apart - rows of [plane][D] fp16, 4 D bytes like the fp32 row, written by
 // edge_gather_sum_planes256_kernel (aggregate.hip) with the inverse scales in inv_src - so the service waves copy 16-byte pieces into the images instead of finding each
 // row's maximum, scaling and splitting it in every one of the eight column parts (15 % of the kernel at config C5).
-template <int D, bool UR, int NBLK, bool GATHER = false, bool PLANES = false>
+template <int D, bool UR, int NBLK, bool GATHER = false, bool PLANES = false, bool FO = false>
 __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_kernel(const float* __restrict__ h, int64_t ld_h, const int32_t* __restrict__ i3,
                                                                                       const v4u* __restrict__ wsp, const float* __restrict__ winv,
                                                                                       const float* __restrict__ dout, int64_t ld_dout,
                                                                                       float* __restrict__ g_out, int64_t n_edges, float* __restrict__ dh_user,
                                                                                       int64_t ld_dh, float* __restrict__ bnd_val, int32_t* __restrict__ bnd_user,
                                                                                       const float* __restrict__ dy_scale, float* __restrict__ dout_store,
-                                                                                      int64_t ld_store, const float* __restrict__ inv_src) {
+                                                                                      int64_t ld_store, const float* __restrict__ inv_src,
+                                                                                      float* __restrict__ dp_user, int64_t ld_dp, float* __restrict__ bnd_dp) {
     static_assert(D == 128 || D == 64 || D == 256, "shapes");
+    static_assert(!FO || (UR && GATHER), "the users' first-order gradient is a run sum of the cotangents the gathering form makes");
     static_assert(!PLANES || !GATHER, "the gathering form makes its cotangents itself");
     static_assert(!GATHER || ((D == 128 || D == 64) && UR), "the gathering form exists where the layer's backward uses it");
     constexpr int TE = kSplitTE, PARTS = D == 64 ? 1 : (D == 128 ? 2 : 8), RANGES = 256 / PARTS, HC = D / PARTS, CT = HC / 16, KB = D / 32, RB = 2 * D;
     constexpr int SWZ = RB / 16 - 1 < 15 ? RB / 16 - 1 : 15;            // the row swizzle stays inside a row (D = 64: rows of 8 chunks)
     constexpr int DOCT = D / 64, EX = HC / 32;                          // per service thread: dout octets, 4-column groups of the product rule
     constexpr int DZ = HC + 4, UTS = HC + 4, GS = UR ? 2 : 3;
+    constexpr int NS = FO ? 2 : 1;                                      // images the run sums go over: 0 the user-slot gradients, 1 (FO) the cotangents themselves
     __shared__ __attribute__((aligned(16))) unsigned char planes[2][2][TE][RB];
     __shared__ float sinv[2][TE];                                        // inverse scales of the rows whose images are in planes[.]
     __shared__ __attribute__((aligned(16))) float dzimg[2][4][TE][DZ];
-    __shared__ __attribute__((aligned(16))) float utile[UR ? 2 : 1][UR ? TE : 1][UTS];    // user-slot gradients of a tile, [row][column of the half]
-    __shared__ float ucarry[2][UR ? HC : 1];                              // sum so far of the run that is open when tile t begins: [t & 1]
-    __shared__ float uhead[2][4][UR ? HC : 1], utail[2][4][UR ? HC : 1];  // per 8-row window of a tile: sum before its first run start / after its last
+    __shared__ __attribute__((aligned(16))) float utile[NS][UR ? 2 : 1][UR ? TE : 1][UTS];    // per image: a tile's rows, [row][column of the half]
+    __shared__ float ucarry[NS][2][UR ? HC : 1];                              // sum so far of the run that is open when tile t begins: [t & 1]
+    __shared__ float uhead[NS][2][4][UR ? HC : 1], utail[NS][2][4][UR ? HC : 1];  // per 8-row window of a tile: sum before its first run start / after its last
     __shared__ int ids[8][3 * TE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -151,7 +163,10 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
     // Every wave keeps the open run's user and whether it still is the range's first run.
     int cur_user = -1, first_user = -1;
     bool first_run_open = true;                                      // no run has ended yet in this range
-    float* const first_slot = UR ? bnd_val + static_cast<int64_t>(2 * range) * D : nullptr;
+    // per image: the rows its runs go to (image 1: dp_user), their stride, and the range's two slots of its boundary table (image 1: bnd_dp, beside bnd_val)
+    float* const run_rows[2] = {dh_user, dp_user};
+    const int64_t run_ld[2] = {ld_dh, ld_dp};
+    float* const first_slot[2] = {UR ? bnd_val + static_cast<int64_t>(2 * range) * D : nullptr, FO ? bnd_dp + static_cast<int64_t>(2 * range) * D : nullptr};
     // (D = 256: parts of 32 columns - the upper half of a wave mirrors the lower one's column (ul) through the sums and leaves the stores to it (uw))
     const int ul = lane & (HC - 1);
     const bool uw = lane < HC;
@@ -171,14 +186,17 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
         const int prev_uid = r == 0 ? last_user : idk[(r - 1) * 3];
         return __ballot(lane < rows && uid != prev_uid);
     };
-    auto run_target = [&](int t, int r, int uid) {                   // destination of the run that starts at row r of tile t
-        return (t == 0 && r == 0) ? first_slot : dh_user + static_cast<int64_t>(__builtin_amdgcn_readlane(uid, r)) * ld_dh;
+    // (every step below goes over the NS images in its innermost loop: one ballot, one set of run starts and scalar conditions, one user id per run for all of them)
+    auto run_target = [&](int s, bool first, int user) {             // destination of image s's sum of a run of `user` (`first`: the range's first run)
+        return first ? first_slot[s] : run_rows[s] + static_cast<int64_t>(user) * run_ld[s];
     };
-    auto load_window = [&](int t, float (&v)[8]) {
+    auto load_window = [&](int t, float (&v)[NS][8]) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = utile[t & 1][8 * win + i][ul];
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[s][i] = utile[s][t & 1][8 * win + i][ul];
     };
-    auto sum_window = [&](int t, const float (&v)[8]) {              // tile t, 0 <= t < n_my
+    auto sum_window = [&](int t, const float (&v)[NS][8]) {          // tile t, 0 <= t < n_my
         int uid, rows;
         // (CHAIN_SVC: this role does not carry the open run's user - the last row of the tile before, full by construction, is still in the id ring)
         const uint64_t m = tile_heads(t, CHAIN_SVC ? (t == 0 ? -1 : ids[(t - 1) & 7][(TE - 1) * 3]) : cur_user, uid, rows);
@@ -186,29 +204,39 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
         uid_prev = uid;
         rows_prev = rows;
         const unsigned mw = static_cast<unsigned>(m >> (8 * win)) & 0xffu;
-        float pre[8], sum = 0.f;                                     // (rows past the end hold zeros and start no run)
+        float pre[NS][8], sum[NS];                                   // (rows past the end hold zeros and start no run)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            sum = sum * ((mw >> i) & 1 ? 0.f : 1.f) + v[i];
-            pre[i] = sum;
+        for (int s = 0; s < NS; ++s) {
+            sum[s] = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                sum[s] = sum[s] * ((mw >> i) & 1 ? 0.f : 1.f) + v[s][i];
+                pre[s][i] = sum[s];
+            }
+            utail[s][t & 1][win][ul] = sum[s];
         }
-        utail[t & 1][win][ul] = sum;
-        if (mw != 0) {                                               // (0.85 run starts per window on C3)
+        if (mw != 0) {                                             // (0.85 run starts per window on C3)
             // Row i + 1 starts a run: the run row i belongs to ends at row i.  Begun inside the window (a start at or before i): its sum is pre[i] and goes to its user's
             // row; begun earlier: pre[i] is the window's piece in front of its first start (uhead; a start at the window's row 0: nothing in front).  Unrolled over i with
             // wave-uniform conditions - compile-time register indices, no selection chains.  (Round 4's form looped over the set bits and picked pre[next - 1] through seven
             // selects per run: 310 instructions and 34 branches in a matrix wave's phase beside its 96 MFMAs.)
-            if (mw & 1u) uhead[t & 1][win][ul] = 0.f;
+            if (mw & 1u) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) uhead[s][t & 1][win][ul] = 0.f;
+            }
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
                 const unsigned upto = mw & ((2u << i) - 1u);         // starts at window rows 0 .. i
                 if ((mw >> (i + 1)) & 1u) {
                     if (upto != 0) {
-                        float* dst = (t == 0 && win == 0 && upto == 1u) ? first_slot
-                                                                         : dh_user + static_cast<int64_t>(__builtin_amdgcn_readlane(uid, 8 * win + i)) * ld_dh;
-                        if (uw) dst[colg] = pre[i];
+                        const bool first = t == 0 && win == 0 && upto == 1u;
+                        const int user = first ? 0 : __builtin_amdgcn_readlane(uid, 8 * win + i);
+#pragma unroll
+                        for (int s = 0; s < NS; ++s)
+                            if (uw) run_target(s, first, user)[colg] = pre[s][i];
                     } else {
-                        uhead[t & 1][win][ul] = pre[i];
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) uhead[s][t & 1][win][ul] = pre[s][i];
                     }
                 }
             }
@@ -223,30 +251,45 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
     struct Chain {
         float tail[4], head, carry;
     };
-    auto load_chain = [&](int t, Chain& c) {
+    auto load_chain = [&](int t, Chain (&c)[NS]) {
 #pragma unroll
-        for (int w = 0; w < 4; ++w) c.tail[w] = utail[t & 1][w][ul];
-        c.head = uhead[t & 1][win][ul];
-        c.carry = ucarry[t & 1][ul];
+        for (int s = 0; s < NS; ++s) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) c[s].tail[w] = utail[s][t & 1][w][ul];
+            c[s].head = uhead[s][t & 1][win][ul];
+            c[s].carry = ucarry[s][t & 1][ul];
+        }
     };
-    auto chain_windows = [&](int t, const Chain& c) {                // tile t, a phase after sum_window(t)
+    auto chain_windows = [&](int t, const Chain (&c)[NS]) {          // tile t, a phase after sum_window(t)
         if (CHAIN_SVC) heads_prev = tile_heads(t, cur_user, uid_prev, rows_prev);
         const unsigned m = static_cast<unsigned>(heads_prev);
         const unsigned before_me = m & ((1u << (8 * win)) - 1u);     // run starts in earlier windows of the tile
         const int p = before_me != 0 ? (31 - __builtin_clz(before_me)) >> 3 : -1;            // the last earlier window that has one
         if (((m >> (8 * win)) & 0xffu) != 0 || win == 3) {
-            float sum = p < 0 ? c.carry : 0.f;
+            float sum[NS];
 #pragma unroll
-            for (int w = 0; w < 3; ++w)
-                if (w < win && w >= p) sum += c.tail[w];
-            if (((m >> (8 * win)) & 0xffu) != 0) {                   // the open run ends at this window's first run start
-                float* dst = nullptr;
-                if (p >= 0) dst = run_target(t, 31 - __builtin_clz(before_me), uid_prev);
-                else if (cur_user >= 0) dst = first_run_open ? first_slot : dh_user + static_cast<int64_t>(cur_user) * ld_dh;
-                if (dst != nullptr && uw) dst[colg] = sum + c.head;
-                sum = 0.f;
+            for (int s = 0; s < NS; ++s) {
+                sum[s] = p < 0 ? c[s].carry : 0.f;
+#pragma unroll
+                for (int w = 0; w < 3; ++w)
+                    if (w < win && w >= p) sum[s] += c[s].tail[w];
             }
-            if (win == 3) ucarry[(t + 1) & 1][ul] = sum + c.tail[3];
+            if (((m >> (8 * win)) & 0xffu) != 0) {                   // the open run ends at this window's first run start
+                // its user and whether it is the range's first run: begun in this tile at row r (first: r == 0 of tile 0), or open since an earlier tile
+                const int r = 31 - __builtin_clz(before_me | 1u);
+                const bool known = p >= 0 || cur_user >= 0;
+                const bool first = p >= 0 ? (t == 0 && r == 0) : first_run_open;
+                const int user = p >= 0 ? __builtin_amdgcn_readlane(uid_prev, r) : cur_user;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    if (known && uw) run_target(s, first, user)[colg] = sum[s] + c[s].head;
+                    sum[s] = 0.f;
+                }
+            }
+            if (win == 3) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) ucarry[s][(t + 1) & 1][ul] = sum[s] + c[s].tail[3];
+            }
         }
         if (t == 0) first_user = __builtin_amdgcn_readlane(uid_prev, 0);
         if (m != 0) first_run_open = t == 0 && m == 1u;
@@ -256,9 +299,11 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
         // the last run of the range may continue in the next one: second boundary slot - unless it IS the first run
         const bool one_run = first_run_open;
         if (cur_user >= 0 && win == 0 && uw) {
-            const float run_sum = ucarry[n_my & 1][ul];              // (written before the last barrier)
-            if (one_run) first_slot[colg] = run_sum;
-            else bnd_val[static_cast<int64_t>(2 * range + 1) * D + colg] = run_sum;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const float run_sum = ucarry[s][n_my & 1][ul];       // (written before the last barrier)
+                (one_run ? first_slot[s] : first_slot[s] + D)[colg] = run_sum;
+            }
         }
         if (half == 0 && win == 0 && lane == 0) {
             bnd_user[2 * range] = first_user;
@@ -417,7 +462,7 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
                     g_i = z_qi;
                 }
                 const bool live = e < n_edges;
-                if (UR) *reinterpret_cast<v4f*>(&utile[(k - 1) & 1][row][c]) = live ? g_u : v4f{0.f, 0.f, 0.f, 0.f};     // (rows past the end: zeros for the sums)
+                if (UR) *reinterpret_cast<v4f*>(&utile[0][(k - 1) & 1][row][c]) = live ? g_u : v4f{0.f, 0.f, 0.f, 0.f};     // (rows past the end: zeros for the sums)
                 if ((live || abl::m_uncond) && !abl::m_no_g_stores) {
                     // (where the stores land does not matter: into a 48 MB window, as one contiguous stream per column part or as plain stores the kernel takes the same
                     // time - ablate.hpp, profiles/r5/22_abl_member_stores_d256.txt: removing them "saves" 10 of 18 ms only because the product rule goes with them)
@@ -437,7 +482,21 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
                 }
             }
         };
-        if (UR && st < HC) ucarry[0][st] = 0.f;
+        // FO: this half's cotangent values of a tile (K5's sum, before the row scaling and the split) wait in registers from the phase that splits the tile until the
+        // phase of its product rule, and go into image 1 there - beside the user-slot gradients of the same tile, for the same run sums (a phase later, matrix waves)
+        auto keep_cotangent = [&](const v4f (&dr)[2 * DOCT], v4f (&fo)[2]) {
+            fo[0] = dr[DOCT == 1 ? 0 : 2 * half];
+            fo[1] = dr[DOCT == 1 ? 1 : 2 * half + 1];
+        };
+        auto store_cotangent = [&](int k, const v4f (&fo)[2]) {          // tile k - 1
+            const bool live = (t0 + k - 1) * TE + row < n_edges;           // (rows past the end: zeros for the sums)
+            *reinterpret_cast<v4f*>(&utile[NS - 1][(k - 1) & 1][row][8 * o]) = live ? fo[0] : v4f{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<v4f*>(&utile[NS - 1][(k - 1) & 1][row][8 * o + 4]) = live ? fo[1] : v4f{0.f, 0.f, 0.f, 0.f};
+        };
+        if (UR && st < HC) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) ucarry[s][0][st] = 0.f;
+        }
         if (st < 3 * TE) {
             ids[0][st] = fetch_id(0);
 #pragma unroll
@@ -448,11 +507,13 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
         // (GATHER) the rows behind the dout values: TWO sets - the rows of tile k + 3 are requested in phase k and summed at the end of phase k + 1 (one set, requested and
         // summed inside one phase, made every phase wait out a loaded memory round trip)
         Raw raw0, raw1;
+        v4f fo0[2], fo1[2];                                              // (FO) cotangent values of tile m for image 1 in fo<m & 1>
         float iv0 = 1.f, iv1 = 1.f;                                      // (PLANES) inverse row scales beside dr0 / dr1
         if (GATHER) {                                                    // one set of dout values: a tile's sum is formed after the previous one was split
             load_gather(0, raw0);
             combine(0, raw0, dr0);
             split_tile(dr0, 0, 1.f);
+            if (FO) keep_cotangent(dr0, fo0);
             load_gather(1, raw0);
             load_gather(2, raw1);
             combine(1, raw0, dr0);
@@ -464,7 +525,7 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
         __syncthreads();
         int id_carry = 0;
         auto phase = [&](int k, v4f (&use)[2 * DOCT], v4f (&fill)[2 * DOCT], v4f (&hm_cur)[EX][3], v4f (&hm_prev)[EX][3], Raw& raw_use, Raw& raw_req, float& iv_use,
-                         float& iv_fill) {
+                         float& iv_fill, v4f (&fo)[2]) {
             // (Round 5 tried the streaming form - config C5's kernel - with this phase's requests first and then the work on what was requested a PHASE AGO behind one exact
             // wait, every request unconditional: the loop's waits became vmcnt(11 .. 22) instead of two vmcnt(0) per trip, and the kernel went 29.7 -> 31.1 ms at C5: it does not
             // wait for latency - 78 GB of L2-miss traffic and a matrix pipe half busy share its 30 ms.  Reverted.)
@@ -474,7 +535,7 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
             // count that leaves them (and the stores) in flight.
             if (wave == 4) { IHG_TRACE(1, k, 0) }
             const int id_new = fetch_id(std::min(k + 4 + AHEAD, n_my - 1));
-            Chain chain;
+            Chain chain[NS];
             if (CHAIN_SVC && !abl::m_no_user_sums && k >= 3) load_chain(k - 3, chain);      // LDS reads of the run sums this phase closes, used at its end
             // ids of tile k + 3 + AHEAD (requested in the previous phase) into the ring: a phase ahead of their first readers (the gathered rows of
             // that tile in the next phase)
@@ -485,6 +546,10 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
             id_carry = id_new;
             if (wave == 4) { IHG_TRACE(1, k, 1) }
             if (k + 1 < n_my) split_tile(use, (k + 1) & 1, iv_use);
+            if (FO) {                                                    // `fo` holds tile k - 1 (kept two phases ago) and takes tile k + 1 before its sum is overwritten
+                if (k >= 1 && k - 1 < n_my) store_cotangent(k, fo);
+                keep_cotangent(use, fo);
+            }
             if (wave == 4) { IHG_TRACE(1, k, 2) }
             // delivery of this phase's requests, THEN everything that stores: the memory counter is in order, a wait behind a store sits out
             // the store's round trip to memory
@@ -504,10 +569,10 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
         int k = 0;
 #pragma clang loop unroll(disable)
         for (; k + 1 < n_phases; k += 2) {                                // exactly two phases per trip: the register sets come back in place
-            phase(k, GATHER ? dr0 : dr1, dr0, hm0, hm1, raw1, raw0, iv1, iv0);
-            phase(k + 1, dr0, GATHER ? dr0 : dr1, hm1, hm0, raw0, raw1, iv0, iv1);
+            phase(k, GATHER ? dr0 : dr1, dr0, hm0, hm1, raw1, raw0, iv1, iv0, fo1);
+            phase(k + 1, dr0, GATHER ? dr0 : dr1, hm1, hm0, raw0, raw1, iv0, iv1, fo0);
         }
-        if (k < n_phases) phase(k, GATHER ? dr0 : dr1, dr0, hm0, hm1, raw1, raw0, iv1, iv0);
+        if (k < n_phases) phase(k, GATHER ? dr0 : dr1, dr0, hm0, hm1, raw1, raw0, iv1, iv0, fo1);
         if (CHAIN_SVC) close_range();
         return;
     }
@@ -529,8 +594,8 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_members_split_ws_k
     __syncthreads();
     __syncthreads();
     for (int k = 0; k < n_phases; ++k) {
-        float wrows[8];
-        Chain chain;
+        float wrows[NS][8];
+        Chain chain[NS];
         if (wave == 0) { IHG_TRACE(0, k, 0) }
         const bool sums_now = UR && !abl::m_no_user_sums && k >= 2 && k - 2 < n_my;
         if (UR && !abl::m_no_user_sums) {                                // LDS reads of this phase's run sums, used at its end
@@ -1216,12 +1281,12 @@ struct MembersSplitCall {
     const EdgeCotangent& cot; float* g; int64_t n_edges; const UserReduced* ur; hipStream_t s;
 };
 
-template <int D, int NBLK, bool UR, bool GATHER, bool PLANES>
+template <int D, int NBLK, bool UR, bool GATHER, bool PLANES, bool FO = false>
 void launch_members_split_kernel(const MembersSplitCall& c) {
-    const UserReduced ur = UR ? *c.ur : UserReduced{nullptr, 0, nullptr, nullptr};
-    hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, UR, NBLK, GATHER, PLANES>), dim3(256), dim3(kSplitThreads), 0, c.s, c.h, c.ld_h, c.i3, c.wsp, c.winv, c.cot.src,
+    const UserReduced ur = UR ? *c.ur : UserReduced{nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr};
+    hipLaunchKernelGGL((interact_bwd_members_split_ws_kernel<D, UR, NBLK, GATHER, PLANES, FO>), dim3(256), dim3(kSplitThreads), 0, c.s, c.h, c.ld_h, c.i3, c.wsp, c.winv, c.cot.src,
                        c.cot.ld, c.g, c.n_edges, ur.dh, ur.ld_dh, ur.bnd_val, ur.bnd_user, GATHER ? c.cot.scale : nullptr, GATHER ? c.cot.store : nullptr,
-                       GATHER ? c.cot.ld_store : int64_t{0}, PLANES ? c.cot.scale : nullptr);
+                       GATHER ? c.cot.ld_store : int64_t{0}, PLANES ? c.cot.scale : nullptr, FO ? ur.dp : nullptr, FO ? ur.ld_dp : int64_t{0}, FO ? ur.bnd_dp : nullptr);
 }
 
 template <int D>
@@ -1232,7 +1297,12 @@ struct MembersSplit {
         if constexpr (D == 256) {                                        // the cotangents are fp16 planes (ihg_edge_gather_sum_planes)
             if (c.cot.kind == EdgeCotangent::Kind::kPlanes) return ur ? launch_members_split_kernel<D, NBLK, true, false, true>(c) : launch_members_split_kernel<D, NBLK, false, false, true>(c);
         } else {                                                         // the node-level cotangent: gathered, summed, stored where there is a place
-            if (ur && c.cot.kind == EdgeCotangent::Kind::kNodeLevel) return launch_members_split_kernel<D, NBLK, true, true, false>(c);
+            if (ur && c.cot.kind == EdgeCotangent::Kind::kNodeLevel) {
+                if constexpr (D == 128) {                                // (first_order_users_ok: the widths this form is instantiated for)
+                    if (c.ur->dp != nullptr) return launch_members_split_kernel<D, NBLK, true, true, false, true>(c);
+                }
+                return launch_members_split_kernel<D, NBLK, true, true, false>(c);
+            }
         }
         ur ? launch_members_split_kernel<D, NBLK, true, false, false>(c) : launch_members_split_kernel<D, NBLK, false, false, false>(c);
     }

@@ -91,14 +91,15 @@ def node_segment_sum_raw(src: Tensor, csr: Union[Csr, CsrRows], src_scale: Optio
                          out_scale: Optional[Tensor] = None, mode: int = _lib.SCALE_NONE,
                          out: Optional[Tensor] = None, entry_scale: Optional[Tensor] = None,
                          self_weight: Optional[Tensor] = None, rows: Optional[Tensor] = None, src_mask: Optional[Tensor] = None,
-                         role: Optional[str] = None, accumulate: bool = False, read_once: bool = False, src_scale_in_entries: bool = False) -> Tensor:
+                         role: Optional[str] = None, accumulate: bool = False, read_once: bool = False, src_scale_in_entries: bool = False,
+                         role_names_rows: bool = True) -> Tensor:
     """``role`` names the launch for the profiler (one kernel, several jobs with different byte counts: ``bench.py`` reports each).
     ``rows`` (int32, device): only these output rows are needed.  The split rows of the plan are always computed; of the
     others only the listed ones are, and the rest of ``out`` is left unwritten.  ``src_mask`` (uint8 per source row): rows with a 0
     are all-zero and are not fetched.  ``accumulate``: ``out +=`` instead of ``out =`` (``out`` required; the hyperedge chunks of one scatter; with ``rows``: the listed rows and the plan's split rows).
     ``read_once``: every source row is read exactly once by this launch (non-temporal loads).  ``src_scale_in_entries``: ``entry_scale[p]`` already holds
     ``src_scale[ids[p]]`` (times the entry's weight; ``IncidenceLayout.two_hop_source_weights``) - the gather does not fetch ``src_scale`` per id, the row's own
-    term still takes it."""
+    term still takes it.  ``role_names_rows=False``: the launch keeps its role's name with a row list (otherwise ``<role>_rows``)."""
     lib = _lib.load()
     src = _rows(src, 'src')
     dim = int(src.shape[1])
@@ -115,7 +116,7 @@ def node_segment_sum_raw(src: Tensor, csr: Union[Csr, CsrRows], src_scale: Optio
     if rows is not None and rows.dtype != torch.int32:
         raise TypeError('rows must be an int32 tensor')
     order, n_light = (rows, int(rows.shape[0])) if rows is not None else (csr.row_order, csr.n_rows)
-    with profiler.kernel((role or 'node_segment_sum') + ('' if rows is None else '_rows'), n_light, dim):
+    with profiler.kernel((role or 'node_segment_sum') + ('' if rows is None or not role_names_rows else '_rows'), n_light, dim):
         _lib.check(lib.ihg_node_segment_sum(
             _ptr(src), _ld(src), _ptr(csr.ptr), _ptr(csr.ids), _ptr(order), _ptr(src_scale), _ptr(entry_scale), _ptr(out_scale), mode,
             _ptr(out), _ld(out), n_light, dim, *_plan_args(csr), _ptr(csr.partials(dim)) if csr.n_heavy > 0 else None,
@@ -248,11 +249,13 @@ def two_hop_scaled_list(layout: IncidenceLayout, src_scale: Optional[Tensor]):
     return csr, folded, True
 
 
-def _two_hop_first_order_gradient(dy: Tensor, layout: IncidenceLayout, out_scale: Optional[Tensor]) -> Tensor:
-    """``d P = H H^T (out_scale * dy)``: the first-order blocks' gradient of the interactive layer by the two-hop operator on the node-level cotangent."""
+def _two_hop_first_order_gradient(dy: Tensor, layout: IncidenceLayout, out_scale: Optional[Tensor], rows: Optional[Tensor] = None,
+                                  out: Optional[Tensor] = None) -> Tensor:
+    """``d P = H H^T (out_scale * dy)``: the first-order blocks' gradient of the interactive layer by the two-hop operator on the node-level cotangent
+    (``rows`` / ``out``: only these rows, and the plan's split rows, into an existing ``[N, d]``)."""
     csr, weights, folded = two_hop_scaled_list(layout, out_scale)
     return node_segment_sum_raw(dy, csr, out_scale, None, _lib.SCALE_NONE, entry_scale=weights, self_weight=layout.self_weight, role='k7.two_hop_first_order_gradient',
-                                src_scale_in_entries=folded)
+                                src_scale_in_entries=folded, rows=rows, out=out, role_names_rows=False)
 
 
 class _TwoHop(torch.autograd.Function):
@@ -1178,6 +1181,11 @@ def _node_level_forward_ok(h: Tensor, w: Tensor, bias: Optional[Tensor], out: Op
 
 # the input features read from the embedding tables in place (NodeTables) in a training step through the fused batch tail; IHG_NODE_TABLES=0: X0 assembled by copies (A/B, tests)
 NODE_TABLES = _os.environ.get('IHG_NODE_TABLES', '1') != '0'
+# Layer-0 backward where the member-gradient kernel gathers the node-level cotangent (d = 128): hyperedges are numbered by user, so a user's row of the first-order
+# gradient, sum over its hyperedges of dout[e], is a run sum of the cotangents that kernel forms anyway - it writes those rows (ihg_interact_bwd_gathered_first_order)
+# and the two-hop launch behind it computes the query and item rows only (2 E of its 6 E entries and N_u of its N self terms fewer).  The users' rows are then summed in
+# hyperedge order instead of two-hop list order; every other output keeps its bits.  IHG_FIRST_ORDER_USER_SUMS=0 (or this attribute) turns it off: the full two-hop launch.
+FIRST_ORDER_USER_SUMS = _os.environ.get('IHG_FIRST_ORDER_USER_SUMS', '1') != '0'
 
 
 def _user_reduced_ok(h: Tensor, w: Tensor, grad_out: Tensor, layout: IncidenceLayout, order: int) -> bool:
@@ -1302,12 +1310,29 @@ def _interact_to_nodes_backward(h: Tensor, w: Tensor, dy: Tensor, layout: Incide
         # launch costs over the scatter: C3 7.89 -> 7.78 ms, C2 1.92 -> 1.87, C4 10.59 -> 10.45; member kernel 1,426-1,467 -> 1,188 us, first-order gradient 672-681 -> 823-833)
         keep_dout = not node_weight
         dout = torch.empty(n_edges, dim, dtype=torch.float32, device=h.device) if keep_dout else None
+        # the users' rows of the first-order gradient from the member kernel's run sums (a user's degree is its run's length: layout.self_weight without multiplicities)
+        user_sums = (FIRST_ORDER_USER_SUMS and not keep_dout and bool(lib.ihg_interact_bwd_gathered_first_order_supported(dim, order, _ld(h), _ld(dy))))
+        dp = None
+        if user_sums:
+            dp = torch.empty(layout.node_count, dim, dtype=torch.float32, device=h.device)
+            idx = layout.users_without_hyperedges()
+            if idx.numel():
+                _lib.check(lib.ihg_zero_rows(_ptr(dp), _ld(dp), dim, _ptr(idx), int(idx.numel()), _stream()), 'ihg_zero_rows')
         def launch(e0, e1, g2, dh, dw_part, ws):             # (one launch: _gathered_backward_ok keeps even the [E, 3, d] buffer within MEMBER_BUFFER_LIMIT_BYTES)
+            if user_sums:
+                _lib.check(lib.ihg_interact_bwd_gathered_first_order(_ptr(h), _ld(h), _ptr(layout.i3), _ptr(w), _ld(w), order, _ptr(dy), _ld(dy), _ptr(out_scale),
+                                                                     _ptr(dout), dim, _ptr(g2), _ptr(dh), dim, _ptr(dp), _ld(dp), _ptr(dw_part), _ld(dw), _ptr(ws),
+                                                                     ws.numel() * 4, n_edges, dim, _stream()), 'ihg_interact_bwd_gathered_first_order')
+                return
             _lib.check(lib.ihg_interact_bwd_gathered(_ptr(h), _ld(h), _ptr(layout.i3), _ptr(w), _ld(w), order, _ptr(dy), _ld(dy), _ptr(out_scale),
                                                      _ptr(dout), dim, _ptr(g2), _ptr(dh), dim, _ptr(dw_part), _ld(dw), _ptr(ws), ws.numel() * 4,
                                                      n_edges, dim, _stream()), 'ihg_interact_bwd_gathered')
         dh = _member_gradients(h, layout, order, None if node_weight else dw, True, launch)
-        return dh, (node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient') if keep_dout else _two_hop_first_order_gradient(dy, layout, out_scale))
+        if keep_dout:
+            return dh, node_segment_sum_raw(dout, layout.node_csr, role='k7.first_order_gradient')
+        if user_sums:                                        # the query and item rows (member_csr_qi keeps their list on the layout) into the same [N, d]
+            return dh, _two_hop_first_order_gradient(dy, layout, out_scale, rows=layout.member_csr_qi()[1], out=dp)
+        return dh, _two_hop_first_order_gradient(dy, layout, out_scale)
     two_hop_first = n_edges * dim * 4 > FIRST_ORDER_TWO_HOP_BYTES
     inv = None
     if (COTANGENT_PLANES and node_weight and two_hop_first and dy.data_ptr() % 16 == 0 and bool(lib.ihg_edge_gather_sum_planes_supported(dim, _ld(dy)))

@@ -298,6 +298,20 @@ int ihg_interact_bwd_gathered(const float* h, int64_t ld_h, const int32_t* i3, c
                               float* g2, float* dh, int64_t ld_dh, float* dw, int64_t ld_dw,
                               void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream);
 
+/* ihg_interact_bwd_gathered that also leaves the USERS' rows of the first-order gradient: hyperedges are numbered by user, so
+ *   dp[u] = sum over the hyperedges e of user u of dout[e]
+ * is a sum over u's contiguous run of the cotangents the kernel forms anyway; it is added up on chip in hyperedge order (runs that cross the kernel's tile
+ * ranges: in range order) and written to dp [n_nodes, ld_dp] (ld_dp >= dim) for every user that has a hyperedge.  Rows of users without hyperedges and of
+ * query / item nodes are NOT written: the caller zeroes the former (ihg_zero_rows) and takes the latter from ihg_node_segment_sum over the two-hop list
+ * with `rows`.  Needs hyperedge lists without multiplicities (sum_run dout = deg(u) D[u] + the two-hop sum only then).  Everything else, bit for bit, as
+ * ihg_interact_bwd_gathered.  Available where ihg_interact_bwd_gathered_first_order_supported says so (dim 128 with the split arithmetic on).
+ */
+int32_t ihg_interact_bwd_gathered_first_order_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_dy);
+int ihg_interact_bwd_gathered_first_order(const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, int32_t order,
+                                          const float* dy, int64_t ld_dy, const float* dy_scale, float* dout, int64_t ld_dout,
+                                          float* g2, float* dh, int64_t ld_dh, float* dp, int64_t ld_dp, float* dw, int64_t ld_dw,
+                                          void* workspace, int64_t workspace_bytes, int64_t n_edges, int32_t dim, ihg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * The interactive layer in its NODE-LEVEL form: out = out_scale * H FeatureInteractor(h) without any [n_edges, dim] tensor.
  * Replaces, for the layer as a whole, the reference's FeatureInteractor.forward + torch.sparse.mm(norm_factor * H, .)
