@@ -404,8 +404,10 @@ int ihg_node_linear_bwd_weight(const float* dout, int64_t ld_dout, const float* 
  *            row (blocks 0 / 1 / 2) for the upstream gradient grad_scale * dscores[batch].  If ld_rowgrad > n_layers*dim,
  *            column n_layers*dim carries d bias: dscores[r] on the item row, 0 on the other two.
  * ihg_bce_with_logits: nn.BCEWithLogitsLoss() (mean) and d loss / d scores in one launch (Main.py:191, TrainTestHelper.py:132).
- * ihg_batch_scatter_add: dense[rows[k], c] += rowgrad[k, c] for k < n_rows <= 16384, duplicates summed in batch order
+ * ihg_batch_scatter_add: dense[rows[k], c] += rowgrad[k, c] for k < n_rows <= 32768 (ihg_batch_scatter_max_rows()), duplicates summed in batch order
  *            without atomics or a sort (one wave per batch row; the first occurrence of a destination adds all later ones).
+ *            A NEGATIVE rows[k] takes no part: its row is neither added anywhere nor matched with another row (the same holds in
+ *            ihg_batch_combine, where leader[k] = 0 and rowgrad[k] stays as it is, and in ihg_batch_rows_add / _put, which skip it).
  *            Column c lands at dense[(c / block_width) * block_stride + row * ld_dense + c % block_width] - with
  *            block_width = dim, block_stride = N * dim every layer's gradient is its own contiguous [N, dim] matrix; if `tail`
  *            is given, the last column goes to tail[row - tail_row_offset] instead (d bias).  Replaces the

@@ -913,6 +913,7 @@ def test_row_subset_outputs_equal_full_outputs():
         assert torch.equal(full[rows], part[rows])
 
 
+# (both launches on their own, per element at d = 1 ... 256 with strided operands and c / dc NULL: tests/test_batch_rows_kernels.py)
 @pytest.mark.parametrize('dim', [8, 64, 96])
 def test_compose_first_order_matches_torch(dim):
     """W_eff = [A_u W | A_q W | A_i W], b_eff = A_t b (+ c on users) and their gradients to A, c, W, b against torch matmul."""
@@ -2761,6 +2762,7 @@ def test_scatter_rows_beyond_one_launch_goes_in_row_chunks():
     assert rel(got[0], want) <= RTOL_SUM * 2 and torch.equal(got[0], got[1])
 
 
+# (the batch-row launches on their own - per element, exact, behind guards, over ladders from the kernels' loop bounds: tests/test_batch_rows_kernels.py)
 @pytest.mark.parametrize('n,width', [(1, 5), (77, 33), (3300, 193), (8192, 64), (16384, 300), (26400, 129), (32768, 9)])
 def test_batch_scatter_add_matches_index_put(n, width):
     """Deterministic sort-free scatter: equals index_put_(accumulate=True), bitwise repeatable with duplicates; plain-matrix
