@@ -72,6 +72,7 @@ def read_query_bags(filename: str) -> Tuple[np.ndarray, np.ndarray]:
 
 class GraphDataset(Dataset):
     device: torch.device = None        # class attribute, as in the reference (Dataset.py:135): collate_fn is static
+    SAMPLE_MAX = 16                    # negatives per positive the device sampler draws at most (kSampleMax of csrc/tail.hip)
 
     def __init__(self, fn_graph_info: str, fn_queries_multihot: str, fn_train_data: str, graph_type: type,
                  random_negative_sample_size: int, non_random_negative_sample_size: int, device: torch.device):
@@ -99,9 +100,10 @@ class GraphDataset(Dataset):
                     bag_words: np.ndarray, bag_offsets: np.ndarray, triples: np.ndarray,
                     graph_type: type = PpsHyperGraph, random_negative_sample_size: int = 10,
                     non_random_negative_sample_size: int = 0, device: torch.device = torch.device('cuda:0'),
-                    pos_log: Optional[np.ndarray] = None) -> 'GraphDataset':
+                    pos_log: Optional[np.ndarray] = None, neg_triples: Optional[np.ndarray] = None) -> 'GraphDataset':
         """In-memory construction (synthetic corpora): ``bag_words`` are 0-based word ids, ``triples`` 0-based per type;
-        ``pos_log[e]`` = the search log hyperedge ``e`` came from (default: one log per positive)."""
+        ``pos_log[e]`` = the search log hyperedge ``e`` came from (default: one log per positive); ``neg_triples`` ``[M, 3]`` = the logged
+        negatives (user, query, item), array order standing for file order (default: none)."""
         self = cls.__new__(cls)
         Dataset.__init__(self)
         self._setup([user_count, query_count, item_count, vocab_size], np.asarray(bag_words, np.int64),
@@ -111,7 +113,7 @@ class GraphDataset(Dataset):
             self.pos_log = np.ascontiguousarray(pos_log, dtype=np.int64)
         self._fn_train_data = None
         self._search_logs = None
-        self._neg_triples = np.zeros((0, 3), np.int64)
+        self._neg_triples = np.zeros((0, 3), np.int64) if neg_triples is None else np.ascontiguousarray(neg_triples, dtype=np.int64).reshape(-1, 3)
         self._neg_interactions = None
         self._neg_of = None
         return self
@@ -167,15 +169,38 @@ class GraphDataset(Dataset):
 
     @property
     def neg_items_for_user_query_pair(self) -> Dict[Tuple[int, int], List[int]]:
-        """(user, query) -> logged negative items in file order; every logged pair has an entry (``Dataset.py:201-210``)."""
+        """(user, query) -> logged negative items in file order; every logged pair has an entry (``Dataset.py:201-210``).  Without a
+        file (``from_arrays``) the table is built from the ``neg_triples`` given there."""
         if self._neg_of is None:
             table: Dict[Tuple[int, int], List[int]] = {}
             if self.search_logs is not None:
                 for log in self.search_logs:
                     bucket = table.setdefault((log.user, log.query), [])
                     bucket.extend(item for item, flag in zip(log.items, log.interactions) if flag <= 0)
+            else:
+                for u, q, item in self._neg_triples.tolist():
+                    table.setdefault((u, q), []).append(item)
             self._neg_of = table
         return self._neg_of
+
+    @property
+    def logged_negative_lists(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The logged negatives as the device sampler reads them: ``(pair_of_edge [E] int32, neg_ptr [P + 1] int64, neg_items [M'] int32)``.
+        ``pair_of_edge[e]`` is the (user, query) pair of positive ``e`` among the ``P`` pairs that have a positive, and
+        ``neg_items[neg_ptr[p]:neg_ptr[p + 1]]`` is the list ``neg_items_for_user_query_pair`` holds for pair ``p``: file order, repeats
+        kept, empty for a pair without logged negatives.  Logged negatives of a pair without a positive are dropped (nothing looks them up)."""
+        if getattr(self, '_neg_lists', None) is None:
+            pos, neg = self.pos_triples, self._neg_triples
+            span = int(max(self.query_count, pos[:, 1].max(initial=-1) + 1, neg[:, 1].max(initial=-1) + 1))
+            pairs, pair_of_edge = np.unique(pos[:, 0] * span + pos[:, 1], return_inverse=True)
+            neg_key = neg[:, 0] * span + neg[:, 1]
+            slot = np.minimum(np.searchsorted(pairs, neg_key), max(len(pairs) - 1, 0))
+            kept = np.flatnonzero(pairs[slot] == neg_key) if len(pairs) else np.zeros(0, np.int64)
+            by_pair = kept[np.argsort(slot[kept], kind='stable')]                    # stable: a pair's items stay in file order
+            neg_ptr = np.zeros(len(pairs) + 1, np.int64)
+            np.cumsum(np.bincount(slot[kept], minlength=len(pairs)), out=neg_ptr[1:])
+            self._neg_lists = (np.ascontiguousarray(pair_of_edge.reshape(-1), np.int32), neg_ptr, np.ascontiguousarray(neg[by_pair, 2], np.int32))
+        return self._neg_lists
 
     @property
     def pos_interactions(self) -> List[PosInteraction]:
@@ -277,20 +302,35 @@ class GraphDataset(Dataset):
         (this rank's share of it when ``world_size`` > 1), the ``rand_neg_sample_size`` negatives of every positive come from
         ``ihg_sample_negatives`` (distinct within a sample, uniform over the catalogue, may hit the positive - the semantics of
         ``random.sample(range(I), k)``, ``Dataset.py:107-109``).  Yields the 8-tuple of ``collate_fn`` (positives then negatives;
-        users, queries, items, flags) with no host -> device copy and no host-side sampling per step.  Logged (non-random)
-        negatives are a host-side table and are not drawn here."""
+        users, queries, items, flags) with no host -> device copy and no host-side sampling per step.
+
+        With ``nonrand_neg_sample_size`` > 0 a batch is ONE launch, ``ihg_device_batch``: it gathers the positives, draws every
+        positive's logged negatives from ``logged_negative_lists`` by the rule of ``__getitem__`` (``Dataset.py:110-119``) and its
+        random ones from the stream of ``ihg_sample_negatives``, and writes the ``[4, n (1 + k)]`` array of ``collate_fn``, of which
+        the 8-tuple is views."""
         import ctypes
         from . import _lib
-        if self.nonrand_neg_sample_size:
-            raise ValueError('device_batches draws random negatives only (non_random_negative_sample_size must be 0)')
         lib = _lib.load()
         dev = GraphDataset.device
         if getattr(self, '_pos_device', None) is None:
             self._pos_device = torch.from_numpy(self.pos_triples).to(dev)
         k = self.rand_neg_sample_size
+        k_logged = self.nonrand_neg_sample_size
+        if k_logged:
+            if k + k_logged > self.SAMPLE_MAX:
+                raise ValueError(f'device_batches draws at most {self.SAMPLE_MAX} negatives per positive, got {k} random + {k_logged} logged')
+            if k + k_logged > self.item_count:
+                raise ValueError(f'device_batches draws distinct items: at most item_count = {self.item_count} negatives per positive, '
+                                 f'got {k} random + {k_logged} logged')
+            if getattr(self, '_neg_device', None) is None:
+                # (a corpus without logged negatives: one unread int32, since an empty tensor has no address to pass)
+                self._neg_device = tuple(torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(dev) for a in self.logged_negative_lists)
+            pair_of_edge, neg_ptr, neg_items = (ctypes.c_void_p(t.data_ptr()) for t in self._neg_device)
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed * 1_000_003 + epoch)
         order = torch.randperm(len(self), device=dev, generator=gen)[rank::world_size]
+        if k_logged:
+            order = order.contiguous()                                           # the launch reads a batch's edge ids where they lie
         n_batches = -(-(-(-len(self) // world_size)) // batch_size)
         mine = int(order.shape[0])
         if mine < n_batches:
@@ -304,6 +344,16 @@ class GraphDataset(Dataset):
                 hi = min(lo + batch_size, mine)
             else:                                                        # equal batch counts on every rank, sizes within one row of each other
                 hi = lo + base + (1 if b < extra else 0)
+            if k_logged:
+                n = hi - lo
+                pack = torch.empty(4, n * (1 + k + k_logged), dtype=torch.int64, device=dev)
+                _lib.check(lib.ihg_device_batch(seed * 7919 + rank, (epoch << 32) + b, ctypes.c_void_p(self._pos_device.data_ptr()),
+                                                ctypes.c_void_p(order.data_ptr() + 8 * lo), n, pair_of_edge, neg_ptr, neg_items, self.item_count, k, k_logged,
+                                                ctypes.c_void_p(pack.data_ptr()), stream), 'ihg_device_batch')
+                lo = hi
+                pos, neg = pack[:, :n], pack[:, n:]
+                yield pos[0], pos[1], pos[2], pos[3], neg[0], neg[1], neg[2], neg[3]
+                continue
             pos = self._pos_device[order[lo:hi]]
             lo = hi
             n = int(pos.shape[0])

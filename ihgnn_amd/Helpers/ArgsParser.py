@@ -42,6 +42,9 @@ _FLAGS = (
     ('embedding_size', ('--embedding_size', '--emb'), int, 0, 'embedding width (0 = Gs.embedding_size)'),
     # not in the reference: batches (positive permutation + negative sampling) produced on the GPU instead of by DataLoader + random.sample
     ('device_sampling', ('--device_sampling',), 'flag', False, 'draw training batches on the device (same distribution, different random stream)'),
+    # not in the reference's command line: there one edits non_random_negative_sample_size in Helpers/GlobalSettings.py
+    ('logged_negatives', ('--logged_negatives',), int, 0, 'logged negatives per positive: items the same (user, query) pair was shown and did not click, beside the random ones '
+                                                          '(Gs.non_random_negative_sample_size; 0 = leave the setting alone); with or without --device_sampling'),
     # not in the reference's command line: its driver hard-codes phase2_attention=False (Main.py:57)
     ('phase2', ('--phase2',), 'flag', False, 'IHGNN layers with phase-2 attention: attention weights over a node\'s hyperedges instead of their mean (Gs.Gnn.gat_head / gat_activation)'),
     # not in the reference's command line: there one edits Gs.Query in Helpers/GlobalSettings.py:68-76

@@ -52,6 +52,17 @@ def apply_evaluation_settings(args) -> None:
     Gs.Evaluation.extra_cutoffs = tuple(getattr(args, 'cutoffs', ()) or ())
 
 
+def apply_sampling_settings(args) -> None:
+    """``--logged_negatives N`` -> ``Gs.non_random_negative_sample_size`` (0: the setting stays as it is) and the sum ``Gs.negative_sample_size``, which the class
+    body evaluates once and which would go stale (not in the reference's command line: one edits ``Helpers/GlobalSettings.py`` there)."""
+    wanted = int(getattr(args, 'logged_negatives', 0) or 0)
+    if wanted < 0:
+        raise ValueError(f'--logged_negatives takes a count >= 0, got {wanted}')
+    if wanted:
+        Gs.non_random_negative_sample_size = wanted
+    Gs.negative_sample_size = Gs.random_negative_sample_size + Gs.non_random_negative_sample_size
+
+
 def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     args = parse_args(argv)
     rank, local_rank, world = ihg_dist.init_from_env()
@@ -84,6 +95,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     apply_query_settings(args)
     apply_prediction_settings(args)
     apply_evaluation_settings(args)
+    apply_sampling_settings(args)
     if args.device == 'cpu':
         raise RuntimeError('ihgnn_amd has no CPU path: the hypergraph kernels are HIP-only')
     device = torch.device(f'cuda:{args.device}' if args.device else f'cuda:{local_rank}')

@@ -408,25 +408,80 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {                  // spli
 }
 
 constexpr int kSampleMax = 16;
+constexpr uint64_t kPositionStream = 0xA0761D6478BD642Full;             // the stream of list positions: a row's key xor this (ihg_device_batch)
+
+__device__ __forceinline__ uint64_t sample_row_key(uint64_t seed, uint64_t counter, int64_t row) {
+    return mix64(seed ^ mix64(counter)) ^ mix64(static_cast<uint64_t>(row) * 0xD1B54A32D192ED03ull);
+}
+
+// picked[0..c) = c DISTINCT values below m (c <= min(kSampleMax, m)), the draws of the stream `key` with its attempts counted from 0: the first c' <= c of
+// them are what a call with c' gives.  Both streams of both kernels below come from here.
+__device__ __forceinline__ void draw_distinct(uint64_t key, uint64_t m, int c, int64_t (&picked)[kSampleMax]) {
+    uint64_t attempt = 0;
+#pragma unroll 1
+    for (int slot = 0; slot < c; ++slot) {
+        int64_t value;
+        bool fresh;
+        do {
+            const uint64_t r = mix64(key + (attempt++) * 0x2545F4914F6CDD1Dull);
+            value = static_cast<int64_t>(__umul64hi(r, m));                                      // uniform on [0, m) up to 2^-64 m
+            fresh = true;
+            for (int j = 0; j < slot; ++j) fresh = fresh && picked[j] != value;
+        } while (!fresh);
+        picked[slot] = value;
+    }
+}
 
 __global__ __launch_bounds__(kBlockThreads) void sample_negatives_kernel(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int k,
                                                                          int64_t* __restrict__ out) {
     for (int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; row < n_rows; row += static_cast<int64_t>(gridDim.x) * blockDim.x) {
         int64_t picked[kSampleMax];
-        const uint64_t key = mix64(seed ^ mix64(counter)) ^ mix64(static_cast<uint64_t>(row) * 0xD1B54A32D192ED03ull);
-        uint64_t attempt = 0;
-#pragma unroll 1
-        for (int slot = 0; slot < k; ++slot) {
-            int64_t item;
-            bool fresh;
-            do {
-                const uint64_t r = mix64(key + (attempt++) * 0x2545F4914F6CDD1Dull);
-                item = static_cast<int64_t>(__umul64hi(r, static_cast<uint64_t>(n_items)));      // uniform on [0, n_items) up to 2^-64 n_items
-                fresh = true;
-                for (int j = 0; j < slot; ++j) fresh = fresh && picked[j] != item;
-            } while (!fresh);
-            picked[slot] = item;
-            out[row * k + slot] = item;
+        draw_distinct(sample_row_key(seed, counter, row), static_cast<uint64_t>(n_items), k, picked);
+        for (int slot = 0; slot < k; ++slot) out[row * k + slot] = picked[slot];
+    }
+}
+
+// One thread per positive writes its column of the pack and the k = k_rand + k_logged columns of its negatives (header: ihg_device_batch).
+__global__ __launch_bounds__(kBlockThreads) void device_batch_kernel(uint64_t seed, uint64_t counter, const int64_t* __restrict__ pos_triples,
+                                                                     const int64_t* __restrict__ edge_ids, int64_t n, const int32_t* __restrict__ pair_of_edge,
+                                                                     const int64_t* __restrict__ neg_ptr, const int32_t* __restrict__ neg_items, int64_t n_items,
+                                                                     int k_rand, int k_logged, int64_t* __restrict__ pack) {
+    const int k = k_rand + k_logged;
+    const int64_t width = n * (1 + k);
+    int64_t* const users = pack;
+    int64_t* const queries = pack + width;
+    int64_t* const items = pack + 2 * width;
+    int64_t* const flags = pack + 3 * width;
+    for (int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; row < n; row += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t edge = edge_ids[row];
+        const int64_t user = pos_triples[3 * edge], query = pos_triples[3 * edge + 1];
+        users[row] = user;
+        queries[row] = query;
+        items[row] = pos_triples[3 * edge + 2];
+        flags[row] = 1;
+
+        int64_t list = 0, len = 0;                                       // the pair's logged negatives: neg_items[list .. list + len)
+        if (k_logged > 0) {
+            const int32_t pair = pair_of_edge[edge];
+            list = neg_ptr[pair];
+            len = neg_ptr[pair + 1] - list;
+        }
+        const bool enough = len >= k_logged;
+        const int n_random = enough ? k_rand : k - static_cast<int>(len);
+        const int n_listed = k - n_random;                               // k_logged drawn positions, or the whole (shorter) list
+        const int first_random = enough ? n_listed : 0;                  // drawn logged items come first; a short list comes last, in file order
+        const int first_listed = enough ? 0 : n_random;
+        const int64_t col0 = n + row * k;
+        const uint64_t key = sample_row_key(seed, counter, row);
+        int64_t picked[kSampleMax];
+        if (enough && n_listed > 0) draw_distinct(key ^ kPositionStream, static_cast<uint64_t>(len), n_listed, picked);
+        for (int j = 0; j < n_listed; ++j) items[col0 + first_listed + j] = neg_items[list + (enough ? picked[j] : j)];
+        draw_distinct(key, static_cast<uint64_t>(n_items), n_random, picked);
+        for (int j = 0; j < n_random; ++j) items[col0 + first_random + j] = picked[j];
+        for (int j = 0; j < k; ++j) {
+            users[col0 + j] = user;
+            queries[col0 + j] = query;
+            flags[col0 + j] = 0;
         }
     }
 }
@@ -441,6 +496,21 @@ int ihg_sample_negatives(uint64_t seed, uint64_t counter, int64_t n_rows, int64_
     const int grid = static_cast<int>(std::min<int64_t>((n_rows + kBlockThreads - 1) / kBlockThreads, kMaxBlocks));
     hipLaunchKernelGGL(sample_negatives_kernel, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, k, out);
     return check_launch("ihg_sample_negatives");
+}
+
+int ihg_device_batch(uint64_t seed, uint64_t counter, const int64_t* pos_triples, const int64_t* edge_ids, int64_t n, const int32_t* pair_of_edge,
+                     const int64_t* neg_ptr, const int32_t* neg_items, int64_t n_items, int32_t k_rand, int32_t k_logged, int64_t* pack, ihg_stream_t stream) {
+    if (n < 0 || n_items <= 0 || k_rand < 0 || k_logged < 0 || k_rand > kSampleMax || k_logged > kSampleMax || k_rand + k_logged < 1 || k_rand + k_logged > kSampleMax ||
+        k_rand + k_logged > n_items)
+        return fail(IHG_ERR_INVALID, "ihg_device_batch: need k_rand >= 0, k_logged >= 0 and 1 <= k_rand + k_logged <= min(%d, n_items)", kSampleMax);
+    if (n == 0) return IHG_OK;                                           // (an empty batch has nothing to point at)
+    if (pos_triples == nullptr || edge_ids == nullptr || pack == nullptr) return fail(IHG_ERR_INVALID, "ihg_device_batch: null pointer");
+    if (k_logged > 0 && (pair_of_edge == nullptr || neg_ptr == nullptr || neg_items == nullptr))
+        return fail(IHG_ERR_INVALID, "ihg_device_batch: k_logged > 0 needs the lists of logged negatives (pair_of_edge, neg_ptr, neg_items)");
+    const int grid = static_cast<int>(std::min<int64_t>((n + kBlockThreads - 1) / kBlockThreads, kMaxBlocks));
+    hipLaunchKernelGGL(device_batch_kernel, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), seed, counter, pos_triples, edge_ids, n, pair_of_edge,
+                       neg_ptr, neg_items, n_items, k_rand, k_logged, pack);
+    return check_launch("ihg_device_batch");
 }
 
 

@@ -507,6 +507,25 @@ int ihg_adam_step_device_scalars(const ihg_adam_tensor* tensors, int32_t n_tenso
  */
 int ihg_sample_negatives(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t k, int64_t* out, ihg_stream_t stream);
 
+/* DEVICE: one whole training batch in one launch, logged negatives included.  Replaces, for the n positives `edge_ids` of pos_triples [E, 3]
+ * (user, query, item), GraphDataset.__getitem__ + collate_fn (Dataset.py:107-119, 282-291).  pack is the [4, n (1 + k)] array collate_fn builds, k = k_rand + k_logged,
+ * rows users / queries / items / flags: columns [0, n) are the positives in edge_ids order with flag 1; column n + row k + slot is negative `slot` of positive `row`,
+ * with the positive's user and query and flag 0.
+ * The logged negatives (items the same (user, query) pair was shown and did not click) are lists in file order with repeats kept: pair_of_edge [E] = the pair of
+ * every positive, list of pair p = neg_items[neg_ptr[p] .. neg_ptr[p + 1]).  With L the row's list and len its length, the reference's rule:
+ *   len >= k_logged: k_logged entries of L at DISTINCT positions drawn uniformly (an item repeats where L repeats it), then k_rand random items;
+ *   len <  k_logged: k - len random items, then all of L in file order.
+ * Random items are distinct within the row, uniform over [0, n_items), the positive not excluded: ihg_sample_negatives' contract.
+ * Two counter-based streams per row, both "c distinct values below m" by the same multiply-high draw with reject-and-redraw, attempts counted from 0:
+ *   items:     key(seed, counter, row) of ihg_sample_negatives, m = n_items: the c random items of row r are bit for bit the first c entries of row r of
+ *              ihg_sample_negatives(seed, counter, n, n_items, k), so k_logged = 0 reproduces that launch;
+ *   positions: key(seed, counter, row) ^ 0xA0761D6478BD642F, m = len.
+ * A pure function of (seed, counter, row).  k_rand >= 0, k_logged >= 0, 1 <= k <= min(16, n_items); the three list pointers may be null only when k_logged == 0;
+ * ids in edge_ids must be in [0, E).  IHG_ERR_INVALID has launched nothing; n == 0 returns IHG_OK.
+ */
+int ihg_device_batch(uint64_t seed, uint64_t counter, const int64_t* pos_triples, const int64_t* edge_ids, int64_t n, const int32_t* pair_of_edge,
+                     const int64_t* neg_ptr, const int32_t* neg_items, int64_t n_items, int32_t k_rand, int32_t k_logged, int64_t* pack, ihg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DEVICE: evaluation scoring with a running top-k.  Replaces, for `n_pairs` search logs at once, the per-log
  * sequence RawGnn.forward(u * ones(I), q * ones(I), None) (Models/RawGnn.py:124-137) -> HemPredictionLayer.forward
