@@ -491,10 +491,9 @@ __global__ __launch_bounds__(512, 4) void row_gemm_strip_kernel(const float* __r
     store_out(n_my - 1);
 }
 
-constexpr int kDenseSlabs = 256;
 constexpr int kGenericSlabs = 64;        // row slabs of the any-width weight gradient (dense_weight_grad_generic_kernel)
 
-// The workspace of the node-level linear maps, in floats: packed weights [3][d][d] | kDenseSlabs weight slabs per type | their bias parts | the 16-bit weight planes of
+// The workspace of the node-level linear maps, in floats: packed weights [3][d][d] | kDenseSlabs (narrow.hpp) weight slabs per type | their bias parts | the 16-bit weight planes of
 // the split kernels.  The any-width weight gradient keeps kGenericSlabs partials per type at the front instead (every width's workspace holds at least those).
 struct DenseWorkspace {
     float *pk, *slabs, *bias_slabs, *planes;

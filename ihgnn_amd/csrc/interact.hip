@@ -1906,28 +1906,41 @@ inline int weight_slabs(int dim) {
 }
 constexpr int kFwdGrid = 256 * 3;
 constexpr int kPipeGrid = 256;          // wave-specialised and strip kernels: one 512-thread workgroup per CU
-// tile ranges of the user-reduced member-gradient kernels (two boundary-table entries each): one per workgroup at d = 64 / 128, one per wave at d = 32 (narrow.hip)
+// tile ranges the boundary tables of the user-reduced form are sized for (two entries each): kPipeGrid, the fp32 strip kernel's count at d = 128 (the split kernels have
+// split_ranges(dim) <= that: split_common.hpp); one per wave at d = 32 (narrow.hip)
 inline int64_t boundary_ranges(int dim) { return dim == 128 || dim == 64 || dim == 256 ? kPipeGrid : (dim == kNarrowDim ? kNarrowMemberRanges : 0); }
 
-// The backward's workspace in the order ihg_interact_bwd_workspace_bytes sizes it: packed weights, weight slabs, the boundary runs of the user-reduced form
-// (values, the first-order values beside them, then their users), the planes of the split / narrow member kernels.
-struct BwdWorkspace {
-    float* wq;
-    float* slabs;
-    float* bnd_val;
-    float* bnd_dp;
-    int32_t* bnd_user;
-    void* planes;
-};
-inline BwdWorkspace carve_bwd_workspace(void* workspace, int dim, int order) {
-    BwdWorkspace ws;
-    ws.wq = static_cast<float*>(workspace);
-    ws.slabs = ws.wq + packed_weight_floats(dim, order);
-    ws.bnd_val = ws.slabs + static_cast<int64_t>(weight_slabs(dim)) * packed_weight_floats(dim, order);
-    ws.bnd_dp = ws.bnd_val + 2LL * boundary_ranges(dim) * dim;
-    ws.bnd_user = reinterpret_cast<int32_t*>(ws.bnd_dp + 2LL * boundary_ranges(dim) * dim);
-    ws.planes = ws.bnd_user + 2LL * boundary_ranges(dim);
-    return ws;
+// The four workspaces.  Each layout function serves the size query (base == nullptr: ihg_*_workspace_bytes is its `floats`) and the carving, region after region in the
+// order of the record; a width / order without tiled kernels takes none.  A plane region holds the image of whichever kernel runs, laid out by the sub-layout beside
+// that kernel's pack kernel (split.hpp).
+// Forward: the fp32 fragment image of the product blocks (launch_pack_weights) | the split kernel's planes.
+struct FwdWorkspace { float* wp; Region planes; int64_t floats; };
+inline FwdWorkspace fwd_workspace(void* base, int dim, int order) {
+    if (!mfma_dim(dim) || (order != 2 && order != 3)) return {nullptr, {nullptr, 0}, 0};
+    const int64_t o_planes = packed_weight_floats(dim, order), n_planes = split_plane_floats(dim, order);
+    return {carve(base, 0), {carve(base, o_planes), n_planes}, o_planes + n_planes};
+}
+// Backward: the fp32 fragment image | weight-gradient slabs | the boundary runs of the user-reduced form: values, the first-order values beside them, their users |
+// the planes of the split member kernel, at d = 32 the narrow one's image.
+struct BwdWorkspace { float *wq, *slabs, *bnd_val, *bnd_dp; int32_t* bnd_user; Region planes; int64_t floats; };
+inline BwdWorkspace bwd_workspace(void* base, int dim, int order) {
+    if (!mfma_dim(dim) || (order != 2 && order != 3)) return {nullptr, nullptr, nullptr, nullptr, nullptr, {nullptr, 0}, 0};
+    const int64_t w_floats = packed_weight_floats(dim, order), table = 2 * boundary_ranges(dim) * dim;
+    const int64_t o_val = w_floats + weight_slabs(dim) * w_floats, o_dp = o_val + table, o_user = o_dp + table, o_planes = o_user + 2 * boundary_ranges(dim);
+    const int64_t n_planes = dim == kNarrowDim ? narrow_members_floats(order) : split_plane_floats(dim, order);
+    return {carve(base, 0), carve(base, w_floats), carve(base, o_val), carve(base, o_dp), carve<int32_t>(base, o_user), {carve(base, o_planes), n_planes}, o_planes + n_planes};
+}
+// Node-level forward: one weight image, all seven blocks at either order - d = 32: fp32 fragments (narrow.hip); else two-fp16 planes | weight-row scales | inverses (split.hpp).
+struct NodeFwdWorkspace { float* packed; NodeFwdPlanes planes; int64_t floats; };
+inline NodeFwdWorkspace node_fwd_workspace(void* base, int dim, int /*order*/) {
+    if (dim == kNarrowDim) return {carve(base, 0), {nullptr, nullptr, nullptr, 0}, narrow_node_fwd_floats()};
+    const NodeFwdPlanes planes = split_node_fwd_planes(base, dim);
+    return {nullptr, planes, planes.floats};
+}
+// Node-level weight gradients: one [d][blocks d] slab per row range of the width's kernel.
+struct NodeWeightWorkspace { float* slabs; int64_t floats; };
+inline NodeWeightWorkspace node_weight_workspace(void* base, int dim, int order) {
+    return {carve(base, 0), dim == kNarrowDim ? narrow_node_weight_floats(order) : split_node_weight_slab_floats(dim, order)};
 }
 
 // Persistent grid of a plain (one role) tiling: as many workgroups as are resident at once - a larger grid runs in rounds, and
@@ -2005,7 +2018,7 @@ struct BwdCall {
     float* g;                        // member buffer: [E, 3, d], or [E, 2, d] with ur
     const UserReduced* ur;           // nullptr: the [E, 3, d] form
     float* dw; int64_t ld_dw;        // nullptr: member gradients only (the caller takes d w from the node-level kernel)
-    BwdWorkspace ws;                 // ws.wq packed by launch_pack_weights where an fp32 kernel may run; ws.planes == nullptr: no split / narrow kernel at this width
+    BwdWorkspace ws;                 // ws.wq packed by launch_pack_weights where an fp32 kernel may run; ws.planes.p == nullptr: no split / narrow kernel at this width
     int64_t n_edges; hipStream_t s;
 };
 
@@ -2032,10 +2045,10 @@ EdgeRows member_gradients(const BwdCall& c) {
     const float* dout = c.cot.src;
     const int64_t ld_dout = c.cot.ld;
     const bool vector_io = aligned16(c.g) && c.ld_h < (int64_t{1} << 30);     // the pipelined form stores g as 16-byte vectors
-    if (dim == kNarrowDim && c.ur != nullptr && c.ws.planes != nullptr && narrow_members_ok(dim, c.order, c.g, c.ld_h, ld_dout, dout)) {
+    if (dim == kNarrowDim && c.ur != nullptr && c.ws.planes.p != nullptr && narrow_members_ok(dim, c.order, c.g, c.ld_h, ld_dout, dout)) {
         // d = 32, user-reduced (g is [E, 2, d]): one wave per 16-hyperedge tile on fp32 MFMA
-        launch_members_narrow(c.order, c.h, c.ld_h, c.i3, c.w, c.ld_w, static_cast<float*>(c.ws.planes), c.cot, c.g, n_edges, *c.ur, c.s);
-    } else if (c.ws.planes != nullptr && split_members_ok(dim, c.order, c.g, c.ld_h, ld_dout, dout)) {   // bf16-split contraction
+        launch_members_narrow(c.order, c.h, c.ld_h, c.i3, c.w, c.ld_w, c.ws.planes, c.cot, c.g, n_edges, *c.ur, c.s);
+    } else if (c.ws.planes.p != nullptr && split_members_ok(dim, c.order, c.g, c.ld_h, ld_dout, dout)) {   // bf16-split contraction
         int entries = 0;
         launch_members_split(dim, c.order, c.h, c.ld_h, c.i3, c.w, c.ld_w, c.ws.planes, c.cot, c.g, n_edges, c.ur, &entries, c.s);
         if (c.ur != nullptr)
@@ -2162,8 +2175,7 @@ extern "C" {
 
 int64_t ihg_interact_fwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t order) {
     (void)n_edges;
-    if (!mfma_dim(dim) || (order != 2 && order != 3)) return 0;
-    return (packed_weight_floats(dim, order) + split_plane_floats(dim, order)) * static_cast<int64_t>(sizeof(float));
+    return fwd_workspace(nullptr, dim, order).floats * static_cast<int64_t>(sizeof(float));
 }
 
 int ihg_interact_fwd(const float* h, int64_t ld_h, const float* p, int64_t ld_p, const int32_t* i3, const float* w, int64_t ld_w,
@@ -2178,13 +2190,13 @@ int ihg_interact_fwd(const float* h, int64_t ld_h, const float* p, int64_t ld_p,
     if (n_edges == 0) return IHG_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (tiled) {
-        float* wp = static_cast<float*>(workspace);
-        if (split_fwd_ok(dim, order, p, ld_p, out, ld_out, ld_h)) {       // bf16-split contraction; its planes sit behind the fp32-packed weights
-            launch_fwd_split(dim, order, h, ld_h, p, ld_p, i3, w, ld_w, wp + packed_weight_floats(dim, order), out, ld_out, n_edges, s);
+        const FwdWorkspace ws = fwd_workspace(workspace, dim, order);
+        if (split_fwd_ok(dim, order, p, ld_p, out, ld_out, ld_h)) {       // bf16-split contraction
+            launch_fwd_split(dim, order, h, ld_h, p, ld_p, i3, w, ld_w, ws.planes, out, ld_out, n_edges, s);
             return check_launch(name);
         }
-        launch_pack_weights(strip_fwd_ok(dim, p, ld_p, out, ld_out, ld_h), w, ld_w, dim, order, wp, nullptr, s);
-        dispatch_nblk<ForwardTiled>(FwdCall{dim, order, h, ld_h, p, ld_p, i3, wp, out, ld_out, n_edges, s});
+        launch_pack_weights(strip_fwd_ok(dim, p, ld_p, out, ld_out, ld_h), w, ld_w, dim, order, ws.wp, nullptr, s);
+        dispatch_nblk<ForwardTiled>(FwdCall{dim, order, h, ld_h, p, ld_p, i3, ws.wp, out, ld_out, n_edges, s});
         return check_launch(name);
     }
     const int64_t total = n_edges * dim;
@@ -2200,7 +2212,7 @@ int32_t ihg_node_interact_fwd_supported(int32_t dim, int32_t order, int64_t ld_h
 }
 
 int64_t ihg_node_interact_fwd_workspace_bytes(int32_t dim) {
-    return (dim == kNarrowDim ? narrow_node_fwd_floats() : split_node_fwd_plane_floats(dim)) * static_cast<int64_t>(sizeof(float));
+    return node_fwd_workspace(nullptr, dim, 3).floats * static_cast<int64_t>(sizeof(float));
 }
 
 int ihg_node_interact_fwd(const float* h, int64_t ld_h, const float* sums, int64_t ld_sums, const float* degree, const float* out_scale, const float* bias,
@@ -2213,10 +2225,11 @@ int ihg_node_interact_fwd(const float* h, int64_t ld_h, const float* sums, int64
                                  ihg_node_interact_fwd_workspace_bytes(dim)))
         return rc;
     if (type_begin[3] == 0) return IHG_OK;
+    const NodeFwdWorkspace ws = node_fwd_workspace(workspace, dim, order);
     if (narrow)                                                          // d = 32: plain fp32 MFMA, one wave per 16-row tile (narrow.hip)
-        launch_node_fwd_narrow(order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+        launch_node_fwd_narrow(order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, ws.packed, static_cast<hipStream_t>(stream));
     else
-        launch_node_fwd_split(dim, order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, workspace, static_cast<hipStream_t>(stream));
+        launch_node_fwd_split(dim, order, h, ld_h, sums, ld_sums, degree, out_scale, bias, w, ld_w, type_begin, out, ld_out, ws.planes, static_cast<hipStream_t>(stream));
     return check_launch(name);
 }
 
@@ -2227,7 +2240,7 @@ int32_t ihg_node_interact_bwd_weight_supported(int32_t dim, int32_t order, int64
 }
 
 int64_t ihg_node_interact_bwd_weight_workspace_bytes(int32_t dim, int32_t order) {
-    return (dim == kNarrowDim ? narrow_node_weight_floats(order) : split_node_weight_slab_floats(dim, order)) * static_cast<int64_t>(sizeof(float));
+    return node_weight_workspace(nullptr, dim, order).floats * static_cast<int64_t>(sizeof(float));
 }
 
 int ihg_node_interact_bwd_weight(const float* h, int64_t ld_h, const float* sums, int64_t ld_sums, const float* dy, int64_t ld_dy, const float* dy_scale, int32_t order,
@@ -2238,20 +2251,17 @@ int ihg_node_interact_bwd_weight(const float* h, int64_t ld_h, const float* sums
     if (int rc = node_form_check(name, dim, order, type_begin, ld_h, ld_dy, ld_sums, ld_dw, false, {h, sums, dy, dw}, shape_ok, workspace, workspace_bytes,
                                  ihg_node_interact_bwd_weight_workspace_bytes(dim, order)))
         return rc;
+    const NodeWeightWorkspace ws = node_weight_workspace(workspace, dim, order);
     if (narrow)
-        launch_node_weight_narrow(order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, static_cast<float*>(workspace), dw, ld_dw, static_cast<hipStream_t>(stream));
+        launch_node_weight_narrow(order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, ws.slabs, dw, ld_dw, static_cast<hipStream_t>(stream));
     else
-        launch_node_weight_split(dim, order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, static_cast<float*>(workspace), dw, ld_dw, static_cast<hipStream_t>(stream));
+        launch_node_weight_split(dim, order, h, ld_h, sums, ld_sums, dy, ld_dy, dy_scale, type_begin, ws.slabs, dw, ld_dw, static_cast<hipStream_t>(stream));
     return check_launch(name);
 }
 
 int64_t ihg_interact_bwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t order) {
     (void)n_edges;
-    if (!mfma_dim(dim) || (order != 2 && order != 3)) return 0;
-    const int64_t w_floats = packed_weight_floats(dim, order);
-    const int64_t boundary = 2 * 2LL * boundary_ranges(dim) * dim + 2LL * boundary_ranges(dim);           // user-reduced form: boundary runs (two value tables) + their users
-    const int64_t planes = dim == kNarrowDim ? narrow_members_floats(order) : split_plane_floats(dim, order);
-    return (w_floats + static_cast<int64_t>(weight_slabs(dim)) * w_floats + boundary + planes) * static_cast<int64_t>(sizeof(float));
+    return bwd_workspace(nullptr, dim, order).floats * static_cast<int64_t>(sizeof(float));
 }
 
 int32_t ihg_interact_bwd_user_reduced_supported(int32_t dim, int32_t order, int64_t ld_h) {
@@ -2271,7 +2281,7 @@ int ihg_interact_bwd_user_reduced(const float* h, int64_t ld_h, const int32_t* i
                                  workspace_bytes, &tiled))
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
+    const BwdWorkspace ws = bwd_workspace(workspace, dim, order);
     const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user, nullptr, 0, nullptr};
     launch_pack_weights(true, w, ld_w, dim, order, nullptr, ws.wq, s);
     dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::rows(dout, ld_dout), g2, &ur, dw, ld_dw, ws, n_edges, s});
@@ -2295,7 +2305,7 @@ int ihg_interact_bwd_user_reduced_planes(const float* h, int64_t ld_h, const int
                                  workspace_bytes, &tiled))
         return rc;
     // (the shape is one the split kernel takes: member_gradients launches it and the boundary runs' sum, nothing else)
-    const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
+    const BwdWorkspace ws = bwd_workspace(workspace, dim, order);
     const UserReduced ur{dh, ld_dh, ws.bnd_val, ws.bnd_user, nullptr, 0, nullptr};
     dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::planes(planes_rows, dim, inv_scale), g2, &ur, nullptr, 0, ws, n_edges,
                                          static_cast<hipStream_t>(stream)});
@@ -2327,7 +2337,7 @@ int interact_bwd_gathered(const char* name, bool supported, const float* h, int6
                                   {workspace, 0, Rows::kNone, kVector}},
                                  workspace_bytes, &tiled))
         return rc;
-    const BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);  // (the fp32 fragment image of w, ws.wq, is not needed by the split kernels)
+    const BwdWorkspace ws = bwd_workspace(workspace, dim, order);  // (the fp32 fragment image of w, ws.wq, is not needed by the split kernels)
     if (dim == kNarrowDim ? !narrow_members_ok(dim, order, g2, ld_h, ld_dy, dy)
                           : (!split_members_ok(dim, order, g2, ld_h, ld_dy, dy) || (dw != nullptr && !split_weight_ok(dim, order, ld_h, ld_dout, dout))))
         return fail(IHG_ERR_INVALID, "%s: the kernels do not take these strides / alignments", name);
@@ -2369,9 +2379,9 @@ int ihg_interact_bwd(const float* h, int64_t ld_h, const int32_t* i3, const floa
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (tiled) {
-        BwdWorkspace ws = carve_bwd_workspace(workspace, dim, order);
+        BwdWorkspace ws = bwd_workspace(workspace, dim, order);
         launch_pack_weights(strip_bwd_ok(dim, g, ld_h), w, ld_w, dim, order, nullptr, ws.wq, s);
-        if (split_plane_floats(dim, order) == 0) ws.planes = nullptr;     // d = 32: no split kernel, and the narrow one has the user-reduced form only
+        if (split_plane_floats(dim, order) == 0) ws.planes.p = nullptr;    // d = 32: no split kernel, and the narrow one has the user-reduced form only
         dispatch_nblk<BackwardTiled>(BwdCall{dim, order, h, ld_h, i3, w, ld_w, EdgeCotangent::rows(dout, ld_dout), g, nullptr, dw, ld_dw, ws, n_edges, s});
         return check_launch(name);
     }

@@ -1,8 +1,16 @@
 // interact_args.hpp - what a backward call of the interactive layer wants, said once by the entry point (interact.hip) and read by every launcher of member-gradient
-// kernels (interact.hip, split_arith.hip, narrow.hip): where the hyperedges' cotangents come from and whether the user slot is reduced on chip.  Host side only.
+// kernels (interact.hip, split_arith.hip, narrow.hip): where the hyperedges' cotangents come from and whether the user slot is reduced on chip; and the two pieces every
+// workspace layout is written with (Region, carve).  Host side only.
 #pragma once
 #include <cstdint>
 #include <type_traits>
+
+// A region of a caller's workspace as the launcher of one of its tenants gets it: where it starts (nullptr: no such region at this width) and how many floats it
+// holds.  The launcher lays its image out from p with the sub-layout that stands beside its pack kernel and checks the image's end against `floats`.
+struct Region { float* p; int64_t floats; };
+// Float `offset` of a workspace that starts at `base`, as a T*.  base == nullptr stays nullptr: a layout function called so answers the size query.
+template <typename T = float>
+inline T* carve(void* base, int64_t offset) { return base != nullptr ? reinterpret_cast<T*>(static_cast<float*>(base) + offset) : nullptr; }
 
 // [E, ld] fp32 rows of hyperedge cotangents that exist in memory (what the weight-gradient kernels read); p == nullptr: there are none
 struct EdgeRows { const float* p; int64_t ld; };
@@ -41,6 +49,17 @@ struct UserReduced { float* dh; int64_t ld_dh; float* bnd_val; int32_t* bnd_user
 template <typename Step, typename Call>
 auto dispatch_nblk(const Call& call) {
     return call.order == 3 ? Step::template run<4>(call) : Step::template run<3>(call);
+}
+// The same for a launch that is one lambda, f(std::integral_constant<int, NBLK>{}), and its sibling for the kernels templated on the order itself (2 / 3)
+template <typename F>
+void dispatch_nblk(int order, F&& f) {
+    if (order == 3) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 3>{});
+}
+template <typename F>
+void dispatch_order(int order, F&& f) {
+    if (order == 3) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 2>{});
 }
 
 // The same for the node-level linear maps' launchers, which are lambdas: f(std::integral_constant<int, V>{}) with V the tiled width (32 / 64 / 128, else 256) or the

@@ -10,6 +10,8 @@
 // halves of 16 rows, and what a lane loads, multiplies element-wise (the product rule, the node-level products) and stores are the same eight columns.  Weights sit in
 // registers in A-fragment order (packed once per call).  Rows are requested one tile ahead (member ids two), unconditionally and with clamped indices - a branch around a
 // request makes the compiler wait for everything at the join.
+#include <cassert>
+
 #include "narrow.hpp"
 
 namespace {
@@ -260,6 +262,13 @@ __global__ __launch_bounds__(kBlockThreads) void pack_members_narrow_kernel(cons
     if (idx >= nblk * 2 * 8 * kWave) return;
     const int lane = idx & 63, s = (idx >> 6) & 7, nt = idx >> 9;
     packed[idx] = w[static_cast<int64_t>(ncol(lane >> 4, s)) * ld_w + (3 + (nt >> 1)) * ND + 16 * (nt & 1) + (lane & 15)];
+}
+// its image: the packed blocks (one float per thread of the pack kernel), 16 floats that keep the dump regions off their cache line, a dump region per tile range
+constexpr int members_narrow_items(int nblk) { return nblk * 2 * 8 * kWave; }
+struct MembersNarrowImage { float* packed; float* dump; int64_t floats; };
+inline MembersNarrowImage members_narrow_image(float* base, int order) {
+    const int64_t o_dump = members_narrow_items(order == 3 ? 4 : 3) + 16;
+    return {base, carve(base, o_dump), o_dump + static_cast<int64_t>(kNarrowMemberRanges) * kNarrowDumpFloats};
 }
 
 template <int CTRL>
@@ -755,8 +764,9 @@ void launch_node_fwd_narrow(int order, const float* h, int64_t ld_h, const float
     const NarrowTiles plan = narrow_tiles(type_begin, 2048);
     if (plan.tile_prefix[3] == 0) return;
     const int grid = grid_for_waves(plan.wave_prefix[3]);
-    if (order == 3) hipLaunchKernelGGL(node_interact_fwd_narrow_kernel<3>, dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, packed, plan, out, ld_out);
-    else hipLaunchKernelGGL(node_interact_fwd_narrow_kernel<2>, dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, packed, plan, out, ld_out);
+    dispatch_order(order, [&](auto o) {
+        hipLaunchKernelGGL(node_interact_fwd_narrow_kernel<decltype(o)::value>, dim3(grid), dim3(kBlockThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, packed, plan, out, ld_out);
+    });
 }
 
 int64_t narrow_node_weight_floats(int order) { return static_cast<int64_t>(kNarrowWeightRanges) * ND * (order == 3 ? 4 : 3) * ND; }
@@ -784,16 +794,15 @@ void launch_node_weight_narrow(int order, const float* h, int64_t ld_h, const fl
     }
     plan.range_prefix[3] = acc;
     const int nblk = order == 3 ? 4 : 3;
-    if (acc > 0) {
-        if (order == 3) hipLaunchKernelGGL(node_interact_weight_narrow_kernel<4>, dim3(acc), dim3(kBlockThreads), 0, s, h, ld_h, sums, ld_s, dy, ld_dy, dy_scale, plan, slabs);
-        else hipLaunchKernelGGL(node_interact_weight_narrow_kernel<3>, dim3(acc), dim3(kBlockThreads), 0, s, h, ld_h, sums, ld_s, dy, ld_dy, dy_scale, plan, slabs);
-    }
+    if (acc > 0)
+        dispatch_nblk(order, [&](auto blocks) {
+            hipLaunchKernelGGL(node_interact_weight_narrow_kernel<decltype(blocks)::value>, dim3(acc), dim3(kBlockThreads), 0, s, h, ld_h, sums, ld_s, dy, ld_dy, dy_scale, plan, slabs);
+        });
     const int total_w = ND * nblk * ND;
     hipLaunchKernelGGL(narrow_weight_reduce_kernel, dim3((total_w + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, plan, nblk, dw, ld_dw);
 }
 
-static int64_t narrow_members_packed(int order) { return static_cast<int64_t>(order == 3 ? 4 : 3) * 2 * 8 * kWave; }
-int64_t narrow_members_floats(int order) { return narrow_members_packed(order) + 16 + static_cast<int64_t>(kNarrowMemberRanges) * kNarrowDumpFloats; }      // the packed weights + a dump region per range
+int64_t narrow_members_floats(int order) { return members_narrow_image(nullptr, order).floats; }
 
 bool narrow_members_ok(int dim, int order, const float* g2, int64_t ld_h, int64_t ld_d, const float* dsrc) {
     return dim == ND && (order == 2 || order == 3) && ld_h % 4 == 0 && ld_d % 4 == 0 && ld_h < (int64_t{1} << 31) && ld_d < (int64_t{1} << 31) && aligned16(g2) && aligned16(dsrc);
@@ -802,16 +811,15 @@ bool narrow_members_ok(int dim, int order, const float* g2, int64_t ld_h, int64_
 namespace {
 struct MembersNarrowCall {
     int order;
-    const float* h; int64_t ld_h; const int32_t* i3; float* packed;
+    const float* h; int64_t ld_h; const int32_t* i3; MembersNarrowImage image;
     const EdgeCotangent& cot; float* g2; int64_t n_edges; const UserReduced& ur; int n_ranges; hipStream_t s;
 };
 
 template <int NBLK, bool GATHER, bool STORE>
 void launch_members_narrow_kernel(const MembersNarrowCall& c) {
-    float* dump = c.packed + narrow_members_packed(c.order) + 16;
-    hipLaunchKernelGGL((members_narrow_kernel<NBLK, GATHER, STORE>), dim3(grid_for_waves(c.n_ranges)), dim3(kBlockThreads), 0, c.s, c.h, c.ld_h, c.i3, c.packed, c.cot.src, c.cot.ld,
+    hipLaunchKernelGGL((members_narrow_kernel<NBLK, GATHER, STORE>), dim3(grid_for_waves(c.n_ranges)), dim3(kBlockThreads), 0, c.s, c.h, c.ld_h, c.i3, c.image.packed, c.cot.src, c.cot.ld,
                        GATHER ? c.cot.scale : nullptr, STORE ? c.cot.store : nullptr, STORE ? c.cot.ld_store : int64_t{0}, c.g2, c.n_edges, c.ur.dh, c.ur.ld_dh, c.ur.bnd_val,
-                       c.ur.bnd_user, c.n_ranges, dump);
+                       c.ur.bnd_user, c.n_ranges, c.image.dump);
 }
 
 struct MembersNarrow {
@@ -824,14 +832,15 @@ struct MembersNarrow {
 };
 }  // namespace
 
-void launch_members_narrow(int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, float* packed, const EdgeCotangent& cot, float* g2,
+void launch_members_narrow(int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, Region planes, const EdgeCotangent& cot, float* g2,
                            int64_t n_edges, const UserReduced& ur, hipStream_t s) {
+    const MembersNarrowImage image = members_narrow_image(planes.p, order);
+    assert(image.floats <= planes.floats);
     const int nblk = order == 3 ? 4 : 3;
-    const int items = nblk * 2 * 8 * kWave;
-    hipLaunchKernelGGL(pack_members_narrow_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, nblk, packed);
+    hipLaunchKernelGGL(pack_members_narrow_kernel, dim3((members_narrow_items(nblk) + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, nblk, image.packed);
     const int64_t n_tiles = (n_edges + NT - 1) / NT;
     const int n_ranges = static_cast<int>(std::min<int64_t>(n_tiles, kNarrowMemberRanges));
-    dispatch_nblk<MembersNarrow>(MembersNarrowCall{order, h, ld_h, i3, packed, cot, g2, n_edges, ur, n_ranges, s});
+    dispatch_nblk<MembersNarrow>(MembersNarrowCall{order, h, ld_h, i3, image, cot, g2, n_edges, ur, n_ranges, s});
     const int per_block = kBlockThreads / ND;
     hipLaunchKernelGGL(narrow_boundary_fixup_kernel, dim3((2 * n_ranges + per_block - 1) / per_block), dim3(kBlockThreads), 0, s, ur.bnd_val, ur.bnd_user, 2 * n_ranges, ur.dh,
                        ur.ld_dh);
@@ -852,34 +861,32 @@ void launch_row_gemm_narrow(int dim, TypedRows in, int64_t ld_in, const float* w
     pack_linear_narrow(dim, w, ld_w, w_type_stride, transpose, pk, s);
     const int grid = grid_for_waves(plan.wave_prefix[3]);
     const int single = w_type_stride == 0 ? 1 : 0;
-#define IHG_NARROW_RG(D, ACC) hipLaunchKernelGGL((row_gemm_narrow_kernel<D, ACC>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, single, bias, bias_mask, bias_type_stride, plan, out, ld_out)
-    if (dim == 32) {
-        if (accumulate) IHG_NARROW_RG(32, true);
-        else IHG_NARROW_RG(32, false);
-    } else {
-        if (accumulate) IHG_NARROW_RG(64, true);
-        else IHG_NARROW_RG(64, false);
-    }
-#undef IHG_NARROW_RG
+    auto launch = [&](auto width, auto acc) {
+        hipLaunchKernelGGL((row_gemm_narrow_kernel<decltype(width)::value, decltype(acc)::value>), dim3(grid), dim3(kBlockThreads), 0, s, in, ld_in, pk, single, bias, bias_mask, bias_type_stride,
+                           plan, out, ld_out);
+    };
+    dispatch_width(dim, [&](auto width) {
+        if constexpr (decltype(width)::value <= 64) accumulate ? launch(width, std::true_type{}) : launch(width, std::false_type{});      // (narrow_linear_ok: 32 / 64)
+    });
 }
 
 int launch_dense_weight_narrow(int dim, const float* dout, int64_t ld_dout, TypedRows x, int64_t ld_x, const int64_t* type_begin, int n_types, float* slabs, float* bias_slabs,
                                const float* w, int64_t ld_w, int64_t w_type_stride, const TypedRowsOut* dx, int64_t ld_dx, int dx_accumulate, float* pk, hipStream_t s) {
     const NarrowTiles plan = narrow_tiles(type_begin);
-    const int n_slabs = 256;                                             // = dense.hip's kDenseSlabs: the workspace holds that many per type
+    const int n_slabs = kDenseSlabs;
     const int single = n_types == 1 ? 1 : 0;
     const TypedRowsOut dxr = dx != nullptr ? *dx : typed_rows_out(nullptr);
     if (dx != nullptr) pack_linear_narrow(dim, w, ld_w, w_type_stride, 1, pk, s);
-#define IHG_NARROW_DW(D, DXF, ACC) hipLaunchKernelGGL((dense_weight_grad_narrow_kernel<D, DXF, ACC>), dim3(n_slabs, 1, n_types), dim3(kBlockThreads), 0, s, dout, ld_dout, x, ld_x, plan, single, slabs, bias_slabs, pk, dxr, ld_dx)
-    if (dim == 32) {
-        if (dx == nullptr) IHG_NARROW_DW(32, false, false);
-        else if (dx_accumulate) IHG_NARROW_DW(32, true, true);
-        else IHG_NARROW_DW(32, true, false);
-    } else {
-        if (dx == nullptr) IHG_NARROW_DW(64, false, false);
-        else if (dx_accumulate) IHG_NARROW_DW(64, true, true);
-        else IHG_NARROW_DW(64, true, false);
-    }
-#undef IHG_NARROW_DW
+    auto launch = [&](auto width, auto with_dx, auto acc) {
+        hipLaunchKernelGGL((dense_weight_grad_narrow_kernel<decltype(width)::value, decltype(with_dx)::value, decltype(acc)::value>), dim3(n_slabs, 1, n_types), dim3(kBlockThreads), 0, s, dout,
+                           ld_dout, x, ld_x, plan, single, slabs, bias_slabs, pk, dxr, ld_dx);
+    };
+    dispatch_width(dim, [&](auto width) {
+        if constexpr (decltype(width)::value <= 64) {                    // (narrow_linear_ok: 32 / 64)
+            if (dx == nullptr) launch(width, std::false_type{}, std::false_type{});
+            else if (dx_accumulate) launch(width, std::true_type{}, std::true_type{});
+            else launch(width, std::true_type{}, std::false_type{});
+        }
+    });
     return n_slabs;
 }

@@ -19,6 +19,7 @@
 constexpr int kNarrowDim = 32;
 constexpr int kNarrowMemberRanges = 2048;      // contiguous tile ranges of the member-gradient kernel (one per wave: 256 CUs x 8 waves); two boundary entries each
 constexpr int kNarrowWeightRanges = 512;       // row ranges (= slabs) of the node-level weight-gradient kernel
+constexpr int kDenseSlabs = 256;               // weight / bias slabs per node type in the node-level linear maps' workspace (dense.hip), which launch_dense_weight_narrow fills too
 
 // node-level forward: out = scale * (sum over a node's hyperedges of their features) from h and the pair sums; packed: narrow_node_fwd_floats() floats of workspace
 IHG_INTERNAL int64_t narrow_node_fwd_floats();
@@ -33,11 +34,11 @@ IHG_INTERNAL void launch_node_weight_narrow(int order, const float* h, int64_t l
                                             const int64_t* type_begin, float* slabs, float* dw, int64_t ld_dw, hipStream_t s);
 
 // member gradients, user slot reduced on chip (g2 is [E, 2, d]; hyperedges numbered by user; `ur` and `cot`: interact_args.hpp).  The cotangents are fp32 rows or a
-// node-level cotangent [N, d] that the kernel gathers and sums itself, leaving the rows in cot.store where there is one (no planes at this width).  packed:
-// narrow_members_floats(order) floats of workspace; the boundary table holds 2 * kNarrowMemberRanges entries.  The boundary runs are added up by the launch itself.
+// node-level cotangent [N, d] that the kernel gathers and sums itself, leaving the rows in cot.store where there is one (no planes at this width).  planes: the
+// workspace's plane region, narrow_members_floats(order) floats (packed weights, pad, a dump region per range); the boundary table holds 2 * kNarrowMemberRanges entries.  The boundary runs are added up by the launch itself.
 IHG_INTERNAL int64_t narrow_members_floats(int order);
 IHG_INTERNAL bool narrow_members_ok(int dim, int order, const float* g2, int64_t ld_h, int64_t ld_d, const float* dsrc);
-IHG_INTERNAL void launch_members_narrow(int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, float* packed, const EdgeCotangent& cot, float* g2,
+IHG_INTERNAL void launch_members_narrow(int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, Region planes, const EdgeCotangent& cot, float* g2,
                                         int64_t n_edges, const UserReduced& ur, hipStream_t s);
 
 // node-level linear maps (ihg_node_linear_*) at dim 32 and 64: forward / input gradient as one stream over the rows; weight + bias gradient (and, dx != nullptr, the input gradient

@@ -54,6 +54,11 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_members_kernel(cons
     wsp[(static_cast<int64_t>(idx >> 6) * 2 + 0) * kWave + lane] = hi;
     wsp[(static_cast<int64_t>(idx >> 6) * 2 + 1) * kWave + lane] = lo;
 }
+// its image: the planes (one thread of the pack kernel = one v4u of either plane: d^2 v4u), then the scales wsc[4][d] and their inverses winv[4][d]
+constexpr int member_plane_items(int d) { return (d / 32) * 4 * (d / 32) * 2 * kWave; }
+constexpr int64_t member_plane_floats(int d) { return 2LL * member_plane_items(d) * 4 + 2 * 4 * d; }
+struct MemberPlanes { v4u* wsp; float* wsc; float* winv; };
+inline MemberPlanes member_planes(float* base, int d) { return {carve<v4u>(base, 0), carve(base, member_plane_floats(d) - 8 * d), carve(base, member_plane_floats(d) - 4 * d)}; }
 
 // Timeline probe of the member-gradient kernel (an ablation build's: -DIHG_ABL_M_TRACE; tools/phase_trace.py): lane 0 of matrix wave 0 and of service wave 4 of one
 // workgroup stamp the clock at marks inside 1,024 phases; ihg_ablation_trace() copies the stamps out.
@@ -678,6 +683,9 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_fwd_kernel(const fl
 #pragma unroll
     for (int p = 0; p < 3; ++p) wsp[(static_cast<int64_t>(idx >> 6) * 3 + p) * kWave + lane] = pl.p[p];
 }
+// its image: one thread of the pack kernel = one v4u of each of the three planes
+constexpr int fwd_plane_items(int d) { return (d / 64) * 4 * 4 * (d / 32) * kWave; }
+constexpr int64_t fwd_plane_floats(int d) { return 3LL * fwd_plane_items(d) * 4; }
 
 // D = 128: two output-column halves per tile sequence (both form and split every product).  D = 64: one workgroup, no duplicated work.
 // NBLK = 3 (order 2): matrix wave 3 has no block and only keeps the barriers.
@@ -862,6 +870,10 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_fwd_kpass_kernel(co
 #pragma unroll
     for (int p = 0; p < 3; ++p) wkp[(static_cast<int64_t>(idx >> 6) * 3 + p) * kWave + lane] = pl.p[p];
 }
+// its image: passes x column halves of kKpPassV4 v4u (one thread of the pack kernel = one v4u of each of the three planes)
+constexpr int kpass_passes(int d) { return d == 128 ? 2 : 4; }
+constexpr int kpass_plane_items(int d) { return kpass_passes(d) * (d / 128) * (kKpPassV4 / 3); }
+constexpr int64_t kpass_plane_floats(int d) { return 3LL * kpass_plane_items(d) * 4; }
 
 // D: feature width (128: all columns in one workgroup, tiles of 32; 256: column halves, tiles of 16);
 // NB: product blocks of this pass (d = 128: 2, or 1 for the second pass of order 2; d = 256: 1); B0: the pass's first block;
@@ -1250,8 +1262,11 @@ __global__ __launch_bounds__(kSplitThreads) void interact_bwd_weight_split_ws_ke
 
 }  // namespace
 
-// floats of workspace for the weight planes of one direction: laid out for four blocks at either order
-int64_t split_plane_floats(int dim, int order) { return (dim == 64 || dim == 128 || dim == 256) && (order == 2 || order == 3) ? (3LL * 4 * dim * dim) / 2 : 0; }
+// The planes region of one direction holds one image at a time - the member planes (backward), or the forward planes of the width's kernel - and is the largest of
+// them: the forward's, three bf16 per weight of four block slots at either order
+constexpr int64_t plane_region_floats(int d) { return std::max(member_plane_floats(d), d == 64 ? fwd_plane_floats(d) : kpass_plane_floats(d)); }
+static_assert(plane_region_floats(64) == 6 * 64 * 64 && plane_region_floats(128) == 6 * 128 * 128 && plane_region_floats(256) == 6 * 256 * 256, "the documented workspace sizes");
+int64_t split_plane_floats(int dim, int order) { return (dim == 64 || dim == 128 || dim == 256) && (order == 2 || order == 3) ? plane_region_floats(dim) : 0; }
 
 
 // the translation unit the ablation macros reach (tools/ab_variant.sh): include/ihgnn_hip.h
@@ -1309,22 +1324,19 @@ struct MembersSplit {
 };
 }  // namespace
 
-void launch_members_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, void* planes, const EdgeCotangent& cot, float* g,
+void launch_members_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* w, int64_t ld_w, Region planes, const EdgeCotangent& cot, float* g,
                           int64_t n_edges, const UserReduced* ur, int* n_boundary_entries, hipStream_t s) {
-    v4u* wsp = static_cast<v4u*>(planes);
+    assert(member_plane_floats(dim) <= planes.floats);
+    const MemberPlanes pl = member_planes(planes.p, dim);
     const int nblk = order == 3 ? 4 : 3;
-    const int items = (dim / 32) * 4 * (dim / 32) * 2 * kWave;
-    // the planes (2 fp16 per weight: 4 d^2 dwords) are followed by the weight columns' scales and their inverses ([4][d] floats each)
-    float* wsc = reinterpret_cast<float*>(wsp) + 4LL * dim * dim;
-    float* winv = wsc + 4 * dim;
     hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(nblk) * dim)), dim3(kBlockThreads), 0, s, w + 3 * dim, ld_w, int64_t{dim}, nblk, dim, 1,
-                       wsc, winv);
-    hipLaunchKernelGGL(pack_planes_members_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, wsc, wsp);
-    const MembersSplitCall call{order, h, ld_h, i3, wsp, winv, cot, g, n_edges, ur, s};
+                       pl.wsc, pl.winv);
+    hipLaunchKernelGGL(pack_planes_members_kernel, dim3((member_plane_items(dim) + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, pl.wsc, pl.wsp);
+    const MembersSplitCall call{order, h, ld_h, i3, pl.wsp, pl.winv, cot, g, n_edges, ur, s};
     if (dim == 256) dispatch_nblk<MembersSplit<256>>(call);
     else if (dim == 64) dispatch_nblk<MembersSplit<64>>(call);
     else dispatch_nblk<MembersSplit<128>>(call);
-    if (n_boundary_entries != nullptr) *n_boundary_entries = 2 * (dim == 64 ? 256 : (dim == 128 ? kSplitRanges : 32));     // two per tile range (256 workgroups / column parts: 256, 128, 32 ranges)
+    if (n_boundary_entries != nullptr) *n_boundary_entries = 2 * split_ranges(dim);      // two per tile range
 }
 
 bool split_weight_ok(int dim, int order, int64_t ld_h, int64_t ld_dout, const float* dout) {
@@ -1333,22 +1345,14 @@ bool split_weight_ok(int dim, int order, int64_t ld_h, int64_t ld_dout, const fl
 
 int launch_weight_split(int dim, int order, const float* h, int64_t ld_h, const int32_t* i3, const float* dout, int64_t ld_dout, float* slabs, int64_t n_edges,
                         hipStream_t s) {
-#define IHG_WEIGHT(D)                                                                                                                                   \
-    {                                                                                                                                                   \
-        if (order == 3) hipLaunchKernelGGL((interact_bwd_weight_split_ws_kernel<D, 4>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges); \
-        else hipLaunchKernelGGL((interact_bwd_weight_split_ws_kernel<D, 3>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges);           \
-    }
-    if (dim == 256) {
-        IHG_WEIGHT(256)
-        return 32;
-    }
-    if (dim == 64) {
-        IHG_WEIGHT(64)
-        return 256;
-    }
-    IHG_WEIGHT(128)
-#undef IHG_WEIGHT
-    return kSplitRanges;                                                 // slabs written (every range writes one, empty ranges zeros)
+    dispatch_width(dim, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        if constexpr (D != 32)                                           // (split_weight_ok: 64 / 128 / 256)
+            dispatch_nblk(order, [&](auto nblk) {
+                hipLaunchKernelGGL((interact_bwd_weight_split_ws_kernel<D, decltype(nblk)::value>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, i3, dout, ld_dout, slabs, n_edges);
+            });
+    });
+    return split_ranges(dim);                                            // slabs written (every range writes one, empty ranges zeros)
 }
 
 // orders 2 and 3 at d = 64 / 128 / 256
@@ -1357,39 +1361,30 @@ bool split_fwd_ok(int dim, int order, const float* p, int64_t ld_p, const float*
            ld_ok(ld_p) && ld_out % 4 == 0 && aligned16(p) && aligned16(out) && ld_ok(ld_h);
 }
 
-void launch_fwd_split(int dim, int order, const float* h, int64_t ld_h, const float* p, int64_t ld_p, const int32_t* i3, const float* w, int64_t ld_w, void* planes,
+void launch_fwd_split(int dim, int order, const float* h, int64_t ld_h, const float* p, int64_t ld_p, const int32_t* i3, const float* w, int64_t ld_w, Region planes,
                       float* out, int64_t ld_out, int64_t n_edges, hipStream_t s) {
-    v4u* wsp = static_cast<v4u*>(planes);
+    v4u* wsp = reinterpret_cast<v4u*>(planes.p);
+    const int nblk = order == 3 ? 4 : 3;
     // d = 128 / 256: passes over the contraction index, every product formed once (the column-half kernel formed them twice; a chunked form that streamed the
     // weight planes at d = 256 filled the CU's L2 port: both removed); d = 64: one workgroup holds the whole weight block
     if (dim == 128 || dim == 256) {
-        const int passes = dim == 128 ? 2 : 4, halves = dim / 128;
-        hipLaunchKernelGGL(pack_planes_fwd_kpass_kernel, dim3((passes * halves * 4 * 2 * 8 * kWave + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w,
-                           dim, order == 3 ? 4 : 3, wsp);
-        const int64_t chunk = n_edges;
-#define IHG_KPASS(D, NB, B0, ACC, PASS) \
-    hipLaunchKernelGGL((interact_fwd_split_kpass_kernel<D, NB, B0, ACC>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3 + 3 * e0, wsp + (PASS) * halves * kKpPassV4, \
-                       out + e0 * ld_out, ld_out, std::min<int64_t>(chunk, n_edges - e0))
-        for (int64_t e0 = 0; e0 < n_edges; e0 += chunk) {
-            if (dim == 128) {
-                IHG_KPASS(128, 2, 0, false, 0);
-                if (order == 3) IHG_KPASS(128, 2, 2, true, 1);
-                else IHG_KPASS(128, 1, 2, true, 1);
-            } else {
-                IHG_KPASS(256, 1, 0, false, 0);
-                IHG_KPASS(256, 1, 1, true, 1);
-                IHG_KPASS(256, 1, 2, true, 2);
-                IHG_KPASS(256, 1, 3, true, 3);
-            }
-        }
-#undef IHG_KPASS
+        assert(kpass_plane_floats(dim) <= planes.floats);
+        hipLaunchKernelGGL(pack_planes_fwd_kpass_kernel, dim3((kpass_plane_items(dim) + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, wsp);
+        // the passes in launch order, <D, blocks, first block, accumulate>: pass k reads the k-th (pass, column halves) piece of the image
+        using Kernel = void (*)(const float*, int64_t, const float*, int64_t, const int32_t*, const v4u*, float*, int64_t, int64_t);
+        static const Kernel kPasses128[2][2] = {{interact_fwd_split_kpass_kernel<128, 2, 0, false>, interact_fwd_split_kpass_kernel<128, 1, 2, true>},       // order 2
+                                                {interact_fwd_split_kpass_kernel<128, 2, 0, false>, interact_fwd_split_kpass_kernel<128, 2, 2, true>}};      // order 3
+        static const Kernel kPasses256[4] = {interact_fwd_split_kpass_kernel<256, 1, 0, false>, interact_fwd_split_kpass_kernel<256, 1, 1, true>,
+                                             interact_fwd_split_kpass_kernel<256, 1, 2, true>, interact_fwd_split_kpass_kernel<256, 1, 3, true>};
+        const Kernel* passes = dim == 128 ? kPasses128[order - 2] : kPasses256;
+        for (int pass = 0; pass < kpass_passes(dim); ++pass)
+            hipLaunchKernelGGL(passes[pass], dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp + pass * (dim / 128) * kKpPassV4, out, ld_out, n_edges);
         return;
     }
-    {
-        const int items = (dim / 64) * 4 * 4 * (dim / 32) * kWave;
-        hipLaunchKernelGGL(pack_planes_fwd_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, order == 3 ? 4 : 3, wsp);
-        if (order == 3) hipLaunchKernelGGL((interact_fwd_split_ws_kernel<64, 4>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges);
-        else hipLaunchKernelGGL((interact_fwd_split_ws_kernel<64, 3>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges);
-    }
+    assert(fwd_plane_floats(dim) <= planes.floats);
+    hipLaunchKernelGGL(pack_planes_fwd_kernel, dim3((fwd_plane_items(dim) + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, nblk, wsp);
+    dispatch_nblk(order, [&](auto blocks) {
+        hipLaunchKernelGGL((interact_fwd_split_ws_kernel<64, decltype(blocks)::value>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, p, ld_p, i3, wsp, out, ld_out, n_edges);
+    });
 }
 

@@ -2,6 +2,7 @@
 // split_node.hip: the node-level contractions and linear maps): wave roles and their issue priority, the three-bf16 and two-fp16 operand splits, the
 // transposed-read fragment helpers, row tiles by node type.  Everything here is inline device code in an anonymous namespace.
 #pragma once
+#include <cassert>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -12,12 +13,13 @@
 
 namespace {
 
-typedef short v8s __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef short v8s __attribute__((ext_vector_type(8)));       // (v4u, the 16-byte unit of every plane image: split.hpp)
 
 constexpr int kSplitTE = 32;            // hyperedges per tile
-constexpr int kSplitRanges = 128;       // contiguous tile ranges at d = 128 (x 2 column halves = 256 workgroups, one per CU)
 constexpr int kSplitThreads = 512;
+// Contiguous tile ranges of the 256-workgroup kernels (member gradients, weight gradients per hyperedge and per node): one workgroup per CU, and a range's column parts
+// (1 at d = 64, 2 at d = 128, 8 at d = 256) are neighbours on one XCD.  A range writes one weight-gradient slab and, user-reduced, two boundary-table entries.
+constexpr int split_ranges(int dim) { return dim == 64 ? 256 : (dim == 128 ? 128 : 32); }
 
 // Issue priority of the two wave roles (s_setprio, 0 .. 3; A/B: tools/ab_variant.sh NAME -DIHG_SERVICE_PRIO=n -DIHG_MATRIX_PRIO=m).  The
 // service waves are the second-dispatched half of the workgroup - the arbitration loser at equal priority (oldest first).

@@ -87,6 +87,7 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_node_fwd_kernel(con
 }
 
 constexpr int kNodePassV4 = 4 * 2 * 8 * 2 * kWave;                      // v4u of one (type, pass)'s planes
+constexpr int kNodeFwdItems128 = 3 * 4 * kNodePassV4 / 2;               // threads of the pack kernel: each writes one v4u of either plane
 
 // ------------------------------------------------------------------------------------------------
 // The node-level contraction at d = 128: FOUR passes over the contraction index ({deg h}, {S_a, h S_a}, {S_b, h S_b}, {S_ab, h S_ab}) as ONE launch that touches
@@ -445,6 +446,7 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_node_fwd256_kernel(
     wnx[(static_cast<int64_t>(idx >> 6) * 2 + 0) * kWave + lane] = hi;
     wnx[(static_cast<int64_t>(idx >> 6) * 2 + 1) * kWave + lane] = lo;
 }
+constexpr int node_fwd_items256(int order) { return 3 * (order == 3 ? 14 : 12) * 4 * 4 * 4 * kWave; }       // threads of the pack kernel: each writes one v4u of either plane
 
 template <int ORDER>
 __global__ __launch_bounds__(kSplitThreads) void node_interact_fwd_grouped256_kernel(const float* __restrict__ h, int64_t ld_h, const float* __restrict__ sums, int64_t ld_s,
@@ -759,6 +761,10 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_node_fwd_q_kernel(c
     }
     wnq[(static_cast<int64_t>(idx >> 6) * 2 + 0) * kWave + lane] = hi;
     wnq[(static_cast<int64_t>(idx >> 6) * 2 + 1) * kWave + lane] = lo;
+}
+constexpr int node_fwd_q_items(int d) {                                  // threads of the pack kernel: each writes one v4u of either plane
+    const int bpp = 512 / d, n_pass = (7 + bpp - 1) / bpp, parts = d / 64;
+    return 3 * n_pass * parts * 4 * 16 * kWave;
 }
 
 template <int D, int PASS, bool ACC, bool FINAL>
@@ -1278,6 +1284,10 @@ __global__ __launch_bounds__(kBlockThreads) void pack_planes_dense_h2_kernel(con
     pk[(static_cast<int64_t>(idx >> 6) * 2 + 0) * kWave + lane] = hi;
     pk[(static_cast<int64_t>(idx >> 6) * 2 + 1) * kWave + lane] = lo;
 }
+// its image: the planes (one thread of the pack kernel = one v4u of either plane), then the output columns' scales wsc[n_types][d] and their inverses winv[n_types][d]
+constexpr int dense_h2_items(int d, int n_types) { return n_types * (d / 16) * (d / 32) * kWave; }
+constexpr int64_t dense_h2_floats(int d, int n_types) { return 2LL * dense_h2_items(d, n_types) * 4 + 2 * n_types * d; }
+struct DenseH2Planes { const v4u* pk; int64_t pk_type_stride; const float* winv; };      // as the kernels take them (pk_type_stride in v4u; one weight for all types: 0)
 
 // D = 128: one workgroup covers all columns, two workgroups per CU.  D = 256: a workgroup covers a column HALF (64 weight registers per
 // wave), the two halves of a tile sequence are two workgroups on one XCD (the second read of a row hits that L2), one workgroup per CU.
@@ -1794,7 +1804,23 @@ __global__ __launch_bounds__(kSplitThreads) void dense_weight_grad_split_kernel(
 
 }  // namespace
 
+// room for three bf16 planes of the three types' weights; the two-fp16 image with its scales is the region's one tenant
 int64_t split_dense_plane_floats(int dim) { return dim == 128 || dim == 256 ? (3LL * 3 * dim * dim) / 2 : 0; }
+static_assert(dense_h2_floats(128, 3) <= (3LL * 3 * 128 * 128) / 2 && dense_h2_floats(256, 3) <= (3LL * 3 * 256 * 256) / 2, "the two-fp16 image fits the planes region");
+
+// The weight operand of out = in W_t^T / in W_t as the split kernels read it: its image laid out in `planes` (split_dense_plane_floats(dim) floats) and filled
+static DenseH2Planes prepare_dense_h2_planes(void* planes, int dim, const float* w, int64_t ld_w, int64_t w_type_stride, int n_types, int transpose, hipStream_t s) {
+    assert(dense_h2_floats(dim, n_types) <= split_dense_plane_floats(dim));
+    const int items = dense_h2_items(dim, n_types);
+    v4u* pk = static_cast<v4u*>(planes);
+    float* wsc = carve(planes, 2LL * items * 4);
+    float* winv = wsc + n_types * dim;
+    hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(n_types) * dim)), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim, transpose,
+                       wsc, winv);
+    hipLaunchKernelGGL(pack_planes_dense_h2_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim,
+                       transpose, wsc, pk);
+    return {pk, n_types == 1 ? int64_t{0} : int64_t{dense_h2_items(dim, 1)} * 2, winv};
+}
 
 bool split_row_gemm_ok(int dim, const float* out, int64_t ld_out, const float* bias, int64_t bias_type_stride) {
     return split_arith_enabled() && (dim == 128 || dim == 256) && aligned16(out) && ld_out % 4 == 0 && (bias == nullptr || (aligned16(bias) && bias_type_stride % 4 == 0));
@@ -1814,28 +1840,18 @@ static RowTiles row_tiles(const int64_t* type_begin, int rows_per_tile) {
 
 void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w, int64_t ld_w, int64_t w_type_stride, int transpose, const float* bias,
                            int bias_mask, int64_t bias_type_stride, const int64_t* type_begin, TypedRowsOut out, int64_t ld_out, void* planes, hipStream_t s, int accumulate, int activation) {
-    const int n_types = w_type_stride == 0 ? 1 : 3;
-    v4u* pk = static_cast<v4u*>(planes);
-    const int items = n_types * (dim / 16) * (dim / 32) * kWave;
-    // two fp16 planes of the scaled weights, followed by the output columns' scales and their inverses ([n_types][dim] floats each)
-    float* wsc = reinterpret_cast<float*>(pk + static_cast<int64_t>(items) * 2);
-    float* winv = wsc + 3 * dim;
-    hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(n_types) * dim)), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim, transpose,
-                       wsc, winv);
-    hipLaunchKernelGGL(pack_planes_dense_h2_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim,
-                       transpose, wsc, pk);
+    const DenseH2Planes wp = prepare_dense_h2_planes(planes, dim, w, ld_w, w_type_stride, w_type_stride == 0 ? 1 : 3, transpose, s);
     const RowTiles plan = row_tiles(type_begin, 32);
     if (plan.tile_prefix[3] == 0) return;
-    const int64_t pk_type_stride = n_types == 1 ? int64_t{0} : static_cast<int64_t>(dim / 16) * (dim / 32) * 2 * kWave;
     // ACC: out += ; ACT: out = act(...) (never accumulating).  d = 128: a workgroup per tile up to 256; d = 256: tile sequences, a multiple of 8, so that both halves of one land on one XCD
     auto launch = [&](auto acc, auto act) {
         constexpr bool ACC = decltype(acc)::value;
         constexpr int ACT = decltype(act)::value;
         const int tiles = plan.tile_prefix[3];
         if (dim == 128)
-            hipLaunchKernelGGL((row_gemm_split_kernel<128, ACC, ACT>), dim3(std::min(tiles, 256)), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride, plan, out, ld_out);
+            hipLaunchKernelGGL((row_gemm_split_kernel<128, ACC, ACT>), dim3(std::min(tiles, 256)), dim3(512), 0, s, in, ld_in, wp.pk, wp.pk_type_stride, wp.winv, bias, bias_mask, bias_type_stride, plan, out, ld_out);
         else
-            hipLaunchKernelGGL((row_gemm_split_kernel<256, ACC, ACT>), dim3(2 * std::min((tiles + 7) / 8 * 8, 256)), dim3(512), 0, s, in, ld_in, pk, pk_type_stride, winv, bias, bias_mask, bias_type_stride,
+            hipLaunchKernelGGL((row_gemm_split_kernel<256, ACC, ACT>), dim3(2 * std::min((tiles + 7) / 8 * 8, 256)), dim3(512), 0, s, in, ld_in, wp.pk, wp.pk_type_stride, wp.winv, bias, bias_mask, bias_type_stride,
                                plan, out, ld_out);
     };
     if (activation != 0) dispatch_act(activation, [&](auto act) { launch(std::false_type{}, act); });
@@ -1843,15 +1859,16 @@ void launch_row_gemm_split(int dim, TypedRows in, int64_t ld_in, const float* w,
     else launch(std::false_type{}, std::integral_constant<int, 0>{});
 }
 
-// node-level forward of the interactive layer: node_interact_fwd_grouped_kernel (d = 128), node_interact_fwd_grouped256_kernel (d = 256), node_interact_fwd_q_kernel (d = 64)
-static int64_t node_fwd_q_v4(int dim) {                                  // v4u of the q kernel's planes
-    const int bpp = 512 / dim, n_pass = (7 + bpp - 1) / bpp, parts = dim / 64;
-    return 3LL * n_pass * parts * 4 * 16 * 2 * kWave;
-}
+// node-level forward of the interactive layer: node_interact_fwd_grouped_kernel (d = 128), node_interact_fwd_grouped256_kernel (d = 256), node_interact_fwd_q_kernel (d = 64).
+// The planes part of its image is the width's pack kernel's output; at d = 256 it keeps the size of the four-launch form's image (the q kernel's at that width, no longer
+// instantiated), which the grouped kernel's 14 passes fit.
+constexpr int64_t node_fwd_plane_v4(int d) { return 2LL * (d == 128 ? kNodeFwdItems128 : node_fwd_q_items(d)); }
+static_assert(2LL * node_fwd_items256(3) <= node_fwd_plane_v4(256) && node_fwd_items256(2) <= node_fwd_items256(3), "the d = 256 planes fit their region at either order");
 
-int64_t split_node_fwd_plane_floats(int dim) {
-    if (dim != 64 && dim != 128 && dim != 256) return 0;
-    return (dim == 128 ? 3LL * 4 * kNodePassV4 : node_fwd_q_v4(dim)) * 4 + 2 * 3 * dim;     // two fp16 planes per weight + the weight rows' scales and inverses
+NodeFwdPlanes split_node_fwd_planes(void* base, int dim) {
+    if (dim != 64 && dim != 128 && dim != 256) return {nullptr, nullptr, nullptr, 0};
+    const int64_t o_wsc = node_fwd_plane_v4(dim) * 4;
+    return {carve<v4u>(base, 0), carve(base, o_wsc), carve(base, o_wsc + 3 * dim), o_wsc + 2 * 3 * dim};
 }
 
 bool split_node_fwd_ok(int dim, int order, int64_t ld_h, int64_t ld_s, const float* out, int64_t ld_out, const float* bias) {
@@ -1859,69 +1876,56 @@ bool split_node_fwd_ok(int dim, int order, int64_t ld_h, int64_t ld_s, const flo
            (bias == nullptr || aligned16(bias));
 }
 
-void launch_node_fwd_split(int dim, int order, const float* h, int64_t ld_h, const float* sums, int64_t ld_s, const float* deg, const float* scale, const float* bias,
-                           const float* w, int64_t ld_w, const int64_t* type_begin, float* out, int64_t ld_out, void* planes, hipStream_t s) {
-    v4u* wnp = static_cast<v4u*>(planes);
-    if (dim == 128) {
-        // the planes (2 fp16 per weight) are followed by the weight rows' scales and their inverses ([3][128] floats each)
-        float* wsc = reinterpret_cast<float*>(wnp + 3LL * 4 * kNodePassV4);
-        float* winv = wsc + 3 * 128;
-        hipLaunchKernelGGL(node_fwd_weight_scales_kernel, dim3(grid_for_waves(3 * 128)), dim3(kBlockThreads), 0, s, w, ld_w, 128, order, wsc, winv);
-        hipLaunchKernelGGL(pack_planes_node_fwd_kernel, dim3((3 * 4 * 4 * 2 * 8 * kWave + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, order, wsc, wnp);
-        const RowTiles plan = row_tiles(type_begin, 32);
-        if (plan.tile_prefix[3] == 0) return;
-        {
-            NodeGroups groups;
-            groups.tiles = plan;
-            int acc = 0;
-            for (int t = 0; t < 3; ++t) {
-                groups.group_prefix[t] = acc;
-                acc += (plan.tile_prefix[t + 1] - plan.tile_prefix[t] + kNodeGroupTiles - 1) / kNodeGroupTiles;
-            }
-            groups.group_prefix[3] = acc;
-            const int grid = std::min(acc, 256);
-            if (order == 3) hipLaunchKernelGGL(node_interact_fwd_grouped_kernel<3>, dim3(grid), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, wnp, winv, groups, out, ld_out);
-            else hipLaunchKernelGGL(node_interact_fwd_grouped_kernel<2>, dim3(grid), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, wnp, winv, groups, out, ld_out);
-            return;
-        }
+// groups of `tiles_per_group` consecutive tiles of one node type
+static NodeGroups node_groups(const RowTiles& tiles, int tiles_per_group) {
+    NodeGroups groups;
+    groups.tiles = tiles;
+    int acc = 0;
+    for (int t = 0; t < 3; ++t) {
+        groups.group_prefix[t] = acc;
+        acc += (tiles.tile_prefix[t + 1] - tiles.tile_prefix[t] + tiles_per_group - 1) / tiles_per_group;
     }
-    const int items = static_cast<int>(node_fwd_q_v4(dim) / 2);
-    float* wsc = reinterpret_cast<float*>(wnp + node_fwd_q_v4(dim));
-    float* winv = wsc + 3 * dim;
-    hipLaunchKernelGGL(node_fwd_weight_scales_kernel, dim3(grid_for_waves(3 * dim)), dim3(kBlockThreads), 0, s, w, ld_w, dim, order, wsc, winv);
-    if (dim == 256) {
-        // one launch: fourteen (order 2: twelve) passes of 128 contraction values over groups of four 32-row tiles
-        const int passes = order == 3 ? 14 : 12;
-        const int pack_items = 3 * passes * 4 * 4 * 4 * kWave;
-        if (order == 3) hipLaunchKernelGGL(pack_planes_node_fwd256_kernel<3>, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, wsc, wnp);
-        else hipLaunchKernelGGL(pack_planes_node_fwd256_kernel<2>, dim3((pack_items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, wsc, wnp);
-        const RowTiles tiles = row_tiles(type_begin, 32);
-        if (tiles.tile_prefix[3] == 0) return;
-        NodeGroups groups;
-        groups.tiles = tiles;
-        int acc = 0;
-        for (int t = 0; t < 3; ++t) {
-            groups.group_prefix[t] = acc;
-            acc += (tiles.tile_prefix[t + 1] - tiles.tile_prefix[t] + kNodeGroupTiles256 - 1) / kNodeGroupTiles256;
-        }
-        groups.group_prefix[3] = acc;
-        const int grid = std::min(acc, 256);
-        if (order == 3) hipLaunchKernelGGL(node_interact_fwd_grouped256_kernel<3>, dim3(grid), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, wnp, winv, groups, out, ld_out);
-        else hipLaunchKernelGGL(node_interact_fwd_grouped256_kernel<2>, dim3(grid), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, wnp, winv, groups, out, ld_out);
+    groups.group_prefix[3] = acc;
+    return groups;
+}
+
+// the weight rows' scales, then the planes of the width's kernel
+static void prepare_node_fwd_planes(int dim, int order, const float* w, int64_t ld_w, const NodeFwdPlanes& ws, hipStream_t s) {
+    const auto blocks = [](int items) { return dim3((items + kBlockThreads - 1) / kBlockThreads); };
+    hipLaunchKernelGGL(node_fwd_weight_scales_kernel, dim3(grid_for_waves(3 * dim)), dim3(kBlockThreads), 0, s, w, ld_w, dim, order, ws.wsc, ws.winv);
+    if (dim == 128)
+        hipLaunchKernelGGL(pack_planes_node_fwd_kernel, blocks(kNodeFwdItems128), dim3(kBlockThreads), 0, s, w, ld_w, order, ws.wsc, ws.planes);
+    else if (dim == 256)
+        dispatch_order(order, [&](auto o) {
+            hipLaunchKernelGGL(pack_planes_node_fwd256_kernel<decltype(o)::value>, blocks(node_fwd_items256(order)), dim3(kBlockThreads), 0, s, w, ld_w, ws.wsc, ws.planes);
+        });
+    else
+        hipLaunchKernelGGL(pack_planes_node_fwd_q_kernel, blocks(node_fwd_q_items(dim)), dim3(kBlockThreads), 0, s, w, ld_w, dim, order, ws.wsc, ws.planes);
+}
+
+void launch_node_fwd_split(int dim, int order, const float* h, int64_t ld_h, const float* sums, int64_t ld_s, const float* deg, const float* scale, const float* bias,
+                           const float* w, int64_t ld_w, const int64_t* type_begin, float* out, int64_t ld_out, const NodeFwdPlanes& ws, hipStream_t s) {
+    prepare_node_fwd_planes(dim, order, w, ld_w, ws, s);
+    const RowTiles plan = row_tiles(type_begin, dim == 64 ? 16 : 32);
+    if (plan.tile_prefix[3] == 0) return;
+    if (dim == 64) {                                                     // one column part, one pass
+        const int n_ranges = std::min((plan.tile_prefix[3] + 7) / 8 * 8, 256);
+        hipLaunchKernelGGL((node_interact_fwd_q_kernel<64, 0, false, true>), dim3(n_ranges), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, ws.planes, ws.winv, plan, out, ld_out);
         return;
     }
-    hipLaunchKernelGGL(pack_planes_node_fwd_q_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, dim, order, wsc, wnp);
-    const RowTiles plan = row_tiles(type_begin, 16);
-    if (plan.tile_prefix[3] == 0) return;
-    const int n_ranges = std::min((plan.tile_prefix[3] + 7) / 8 * 8, 256);              // (d = 64: one column part, one pass)
-    hipLaunchKernelGGL((node_interact_fwd_q_kernel<64, 0, false, true>), dim3(n_ranges), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, wnp, winv, plan, out, ld_out);
+    // one launch: four passes of 256 contraction values over groups of eight tiles; d = 256: fourteen (order 2: twelve) passes of 128 values over groups of four
+    const NodeGroups groups = node_groups(plan, dim == 128 ? kNodeGroupTiles : kNodeGroupTiles256);
+    const int grid = std::min(groups.group_prefix[3], 256);
+    dispatch_order(order, [&](auto o) {
+        constexpr int ORDER = decltype(o)::value;
+        const auto kernel = dim == 128 ? node_interact_fwd_grouped_kernel<ORDER> : node_interact_fwd_grouped256_kernel<ORDER>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, deg, scale, bias, ws.planes, ws.winv, groups, out, ld_out);
+    });
 }
 
 // node-level weight gradients of the product blocks (d = 64 / 128 / 256): see node_interact_weight_split_kernel
-static int node_weight_ranges(int dim) { return dim == 64 ? 256 : (dim == 128 ? 128 : 32); }
-
 int64_t split_node_weight_slab_floats(int dim, int order) {
-    return dim == 64 || dim == 128 || dim == 256 ? static_cast<int64_t>(node_weight_ranges(dim)) * dim * (order == 3 ? 4 : 3) * dim : 0;
+    return dim == 64 || dim == 128 || dim == 256 ? static_cast<int64_t>(split_ranges(dim)) * dim * (order == 3 ? 4 : 3) * dim : 0;     // one slab per tile range
 }
 
 bool split_node_weight_ok(int dim, int order, int64_t ld_h, int64_t ld_s, int64_t ld_dy, const float* dy) {
@@ -1938,7 +1942,7 @@ void launch_node_weight_split(int dim, int order, const float* h, int64_t ld_h, 
         total += tiles[t];
     }
     // tile ranges by type in proportion to the tiles, every non-empty type at least one, `ranges` in all at most
-    const int ranges = node_weight_ranges(dim);
+    const int ranges = split_ranges(dim);
     int acc = 0;
     for (int t = 0; t < 3; ++t) {
         int n = tiles[t] == 0 ? 0 : static_cast<int>(std::max<int64_t>(1, tiles[t] * (ranges - 2) / std::max<int64_t>(total, 1)));
@@ -1948,15 +1952,13 @@ void launch_node_weight_split(int dim, int order, const float* h, int64_t ld_h, 
     }
     plan.range_prefix[3] = acc;
     const int nblk = order == 3 ? 4 : 3;
-#define IHG_NODE_WEIGHT(D)                                                                                                                                   \
-    {                                                                                                                                                        \
-        if (order == 3) hipLaunchKernelGGL((node_interact_weight_split_kernel<D, 4>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, dy, ld_dy, dy_scale, plan, slabs); \
-        else hipLaunchKernelGGL((node_interact_weight_split_kernel<D, 3>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, dy, ld_dy, dy_scale, plan, slabs);           \
-    }
-    if (dim == 64) IHG_NODE_WEIGHT(64)
-    else if (dim == 128) IHG_NODE_WEIGHT(128)
-    else IHG_NODE_WEIGHT(256)
-#undef IHG_NODE_WEIGHT
+    dispatch_width(dim, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        if constexpr (D != 32)                                           // (split_node_weight_ok: 64 / 128 / 256)
+            dispatch_nblk(order, [&](auto blocks) {
+                hipLaunchKernelGGL((node_interact_weight_split_kernel<D, decltype(blocks)::value>), dim3(256), dim3(kSplitThreads), 0, s, h, ld_h, sums, ld_s, dy, ld_dy, dy_scale, plan, slabs);
+            });
+    });
     const int total_w = dim * nblk * dim;
     hipLaunchKernelGGL(node_weight_reduce_kernel, dim3((total_w + kWave - 1) / kWave), dim3(kBlockThreads), 0, s, slabs, plan, dim, nblk, dw, ld_dw);
 }
@@ -1978,29 +1980,19 @@ int launch_dense_weight_split(int dim, const float* dout, int64_t ld_dout, Typed
                            bias_slabs, static_cast<const v4u*>(nullptr), int64_t{0}, static_cast<const float*>(nullptr), typed_rows_out(nullptr), int64_t{0});
         return n_seq;
     }
-    // the fused input gradient's operands (dx_rows != nullptr), told to the kernel only then: planes of W for out = in W - two fp16 planes per weight, then the output
-    // columns' scales and their inverses ([types][128] floats each)
+    // the fused input gradient's operands (dx_rows != nullptr), told to the kernel only then: the planes of W for out = in W
     const int n_seq = 256;
-    const v4u* pk = nullptr;
-    const float* winv = nullptr;
-    int64_t pk_type_stride = 0;
+    DenseH2Planes wp{nullptr, 0, nullptr};
     TypedRowsOut dx = typed_rows_out(nullptr);
     if (dx_rows != nullptr) {
-        v4u* pkw = static_cast<v4u*>(planes);
-        float* wsc = reinterpret_cast<float*>(pkw + static_cast<int64_t>(n_types) * 8 * 4 * 2 * kWave);
-        const int items = n_types * 8 * 4 * kWave;
-        hipLaunchKernelGGL(dense_weight_scales_kernel, dim3(grid_for_waves(static_cast<int64_t>(n_types) * dim)), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types, dim, 1,
-                           wsc, wsc + n_types * dim);
-        hipLaunchKernelGGL(pack_planes_dense_h2_kernel, dim3((items + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, s, w, ld_w, w_type_stride, n_types,
-                           dim, 1, wsc, pkw);
-        pk = pkw, winv = wsc + n_types * dim, dx = *dx_rows;
-        pk_type_stride = single_weight ? int64_t{0} : int64_t{8 * 4 * 2 * kWave};
+        wp = prepare_dense_h2_planes(planes, dim, w, ld_w, w_type_stride, n_types, 1, s);
+        dx = *dx_rows;
     } else {
         ld_dx = 0;
     }
     auto launch = [&](auto with_dx, auto acc) {
         hipLaunchKernelGGL((dense_weight_grad_split_kernel<128, decltype(with_dx)::value, decltype(acc)::value>), dim3(n_seq, 1, n_types), dim3(kSplitThreads), 0, s, dout, ld_dout, x, ld_x, plan,
-                           single_weight, slabs, bias_slabs, pk, pk_type_stride, winv, dx, ld_dx);
+                           single_weight, slabs, bias_slabs, wp.pk, wp.pk_type_stride, wp.winv, dx, ld_dx);
     };
     if (dx_rows == nullptr) launch(std::false_type{}, std::false_type{});
     else if (dx_accumulate) launch(std::true_type{}, std::true_type{});

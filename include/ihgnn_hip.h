@@ -243,6 +243,10 @@ int ihg_bag_mean_bwd(const float* dout, int64_t ld_dout, const int32_t* word_ptr
  * dw == NULL (here and in ihg_interact_bwd_user_reduced): member gradients only - the caller takes the product blocks' weight gradients from
  * ihg_node_interact_bwd_weight.
  */
+/* The forward's workspace, in floats and in this order (B = 3 product blocks at order 2, 4 at order 3; 0 bytes unless dim is 32 / 64 / 128 / 256 and order 2 / 3;
+ * n_edges does not enter):
+ *   B dim^2              the product blocks of w in fp32 MFMA fragment order
+ *   6 dim^2 (dim >= 64)  planes: the split kernel's weight image - three bf16 planes of four block slots at either order */
 int64_t ihg_interact_fwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t order);
 
 int ihg_interact_fwd(const float* h, int64_t ld_h, const float* p, int64_t ld_p, const int32_t* i3,
@@ -250,6 +254,14 @@ int ihg_interact_fwd(const float* h, int64_t ld_h, const float* p, int64_t ld_p,
                      float* out, int64_t ld_out, void* workspace, int64_t workspace_bytes,
                      int64_t n_edges, int32_t dim, ihg_stream_t stream);
 
+/* The backward's workspace (all ihg_interact_bwd* entry points), in floats and in this order (B, the widths and n_edges as above):
+ *   B dim^2              the product blocks of w in fp32 MFMA fragment order
+ *   S B dim^2            weight-gradient slabs: S = 512 at dim 32 / 64, 256 at dim 128, 32 at dim 256
+ *   2 R dim              boundary runs of the user-reduced forms, values: two per tile range, sized for R = 256 ranges (dim 32: 2,048)
+ *   2 R dim              the same for the users' first-order gradient (ihg_interact_bwd_gathered_first_order)
+ *   2 R                  their users (int32)
+ *   6 dim^2 (dim >= 64)  planes: the member kernel's weight image (two fp16 planes of four block slots, the weight columns' scales and inverses: 4 dim^2 + 8 dim of it)
+ *   1,024 B + 16 + 2,048 x 320 (dim 32)   the narrow member kernel's image: packed blocks, padding, a dump region per tile range */
 int64_t ihg_interact_bwd_workspace_bytes(int64_t n_edges, int32_t dim, int32_t order);
 
 int ihg_interact_bwd(const float* h, int64_t ld_h, const int32_t* i3,
@@ -336,6 +348,9 @@ int ihg_node_pair_sums(const float* h, int64_t ld_h, const int32_t* pair_ptr, co
                        int64_t n_segments, const int32_t* heavy_rows, const int32_t* heavy_segptr, int64_t n_heavy, float* partials,
                        const float* pair_weight, ihg_stream_t stream);
 int32_t ihg_node_interact_fwd_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_sums, int64_t ld_out);
+/* The node-level forward's workspace is one weight image, in floats (0 bytes at any other dim):
+ *   dim 32:              3 x 7 x 1,024: every node type's seven blocks in fp32 MFMA fragment order
+ *   dim 64 / 128 / 256:  24 dim^2 (two fp16 planes of eight block slots per node type) | 3 dim (the weight rows' scales) | 3 dim (their inverses) */
 int64_t ihg_node_interact_fwd_workspace_bytes(int32_t dim);
 int ihg_node_interact_fwd(const float* h, int64_t ld_h, const float* sums, int64_t ld_sums, const float* degree, const float* out_scale, const float* bias,
                           const float* w, int64_t ld_w, int32_t order, const int64_t* type_begin, float* out, int64_t ld_out, void* workspace,
@@ -348,6 +363,8 @@ int ihg_node_interact_fwd(const float* h, int64_t ld_h, const float* sums, int64
  *   with dw == NULL (member gradients only).  Available where ihg_node_interact_bwd_weight_supported says so (dim 64 / 128 / 256, split arithmetic on: IHG_INTERACT_ARITH != f32).
  */
 int32_t ihg_node_interact_bwd_weight_supported(int32_t dim, int32_t order, int64_t ld_h, int64_t ld_sums, int64_t ld_dy);
+/* Its workspace is one region, in floats: R slabs of dim x B dim (B = 3 at order 2, 4 at order 3), one per row range of the width's kernel -
+ * R = 512 at dim 32, 256 at dim 64, 128 at dim 128, 32 at dim 256 (0 bytes at any other dim) */
 int64_t ihg_node_interact_bwd_weight_workspace_bytes(int32_t dim, int32_t order);
 int ihg_node_interact_bwd_weight(const float* h, int64_t ld_h, const float* sums, int64_t ld_sums, const float* dy, int64_t ld_dy, const float* dy_scale, int32_t order,
                                  const int64_t* type_begin, float* dw, int64_t ld_dw, void* workspace, int64_t workspace_bytes, int32_t dim, ihg_stream_t stream);

@@ -551,6 +551,38 @@ def test_node_linear_workspace_bytes_arithmetic():
         assert int(lib.ihg_node_linear_workspace_bytes(d)) >= 4 * 3 * 64 * (d * d + d)
 
 
+def test_interactive_layer_workspace_bytes_arithmetic():
+    """The four workspaces of the interactive layer: each ``*_workspace_bytes`` is the sum of the regions include/ihgnn_hip.h names for it, in floats, and the number the
+    library returned before the layouts were written as one function each (recorded from that build)."""
+    lib = _lib.load()
+    recorded = {   # (dim, order): forward, backward, node-level forward, node-level weight gradient
+        (32, 2): (12288, 10002496, 86016, 6291456), (32, 3): (16384, 12107840, 86016, 8388608),
+        (64, 2): (147456, 25577472, 394752, 12582912), (64, 3): (163840, 33982464, 394752, 16777216),
+        (128, 2): (589824, 51447808, 1575936, 25165824), (128, 3): (655360, 68290560, 1575936, 33554432),
+        (256, 2): (2359296, 28575744, 6297600, 25165824), (256, 3): (2621440, 37226496, 6297600, 33554432),
+        (12, 2): (0, 0, 0, 0), (12, 3): (0, 0, 0, 0)}
+    for (d, order), expected in recorded.items():
+        got = (int(lib.ihg_interact_fwd_workspace_bytes(1000, d, order)), int(lib.ihg_interact_bwd_workspace_bytes(1000, d, order)),
+               int(lib.ihg_node_interact_fwd_workspace_bytes(d)), int(lib.ihg_node_interact_bwd_weight_workspace_bytes(d, order)))
+        assert got == expected, (d, order)
+        if d == 12:
+            continue
+        blocks = 3 if order == 2 else 4
+        fragments = blocks * d * d
+        planes = 6 * d * d if d >= 64 else 0
+        fwd = fragments + planes
+        slabs = {32: 512, 64: 512, 128: 256, 256: 32}[d]
+        ranges = 2048 if d == 32 else 256
+        member_image = planes if d >= 64 else 1024 * blocks + 16 + 2048 * 320
+        assert d < 64 or 4 * d * d + 8 * d <= planes                    # what the member kernel's planes, scales and inverses take of the region
+        bwd = fragments + slabs * fragments + 2 * ranges * d + 2 * ranges * d + 2 * ranges + member_image
+        node_fwd = 3 * 7 * 1024 if d == 32 else 24 * d * d + 3 * d + 3 * d
+        node_weight = {32: 512, 64: 256, 128: 128, 256: 32}[d] * d * blocks * d
+        assert got == (4 * fwd, 4 * bwd, 4 * node_fwd, 4 * node_weight), (d, order)
+    # the sizes do not depend on the number of hyperedges
+    assert int(lib.ihg_interact_bwd_workspace_bytes(1, 128, 3)) == int(lib.ihg_interact_bwd_workspace_bytes(10 ** 9, 128, 3)) == recorded[(128, 3)][1]
+
+
 def test_missing_library_is_a_hard_error(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libihgnn_hip.so')
