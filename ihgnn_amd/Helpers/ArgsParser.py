@@ -32,7 +32,7 @@ _FLAGS = (
     ('epoch_start_test', ('--epoch_start_test', '--est'), int, 0, 'first epoch to test at (0 = driver default 10)'),
     ('epoch_test_frequency', ('--epoch_test_frequency', '--etf'), int, 0, 'test every this many epochs'),
     ('dataset', ('--dataset', '--ds'), str, '', 'dataset sub-directory under the data root'),
-    ('model', ('--model',), str, '', 'model type (RawGnn)'),
+    ('model', ('--model',), str, '', 'model type (RawGnn | Srrl)'),
     ('gnn', ('--gnn',), str, '', 'GNN layer type: IHGNN | HGCN | GCN | GAT'),
     ('gnns', ('--gnns',), int, 0, 'number of GNN layers (0 = driver default 2)'),
     ('feature_order', ('--feature_order', '--fo'), int, 0, 'interaction order 1 | 2 | 3 (0 = driver default 3)'),

@@ -44,6 +44,11 @@ class Gs:
     class Evaluation:
         extra_cutoffs = ()               # not in the reference (which reports @10 only): further cutoffs K in 11..128 (--cutoffs), HR / NDCG / MAP @K beside the @10 triple
 
+    class Srrl:                          # the Srrl baseline (GlobalSettings.py:87-91)
+        KG_loss = True                   # train the KG embeddings (srrl_steps KG steps per epoch) and feed them to the PS model through g_u / g_i
+        uni_weight = False               # True: every positive weighs the same in the KG loss; False: sqrt(1 / frequency of its (user, query))
+        regularization = 0               # != 0: adds the tables' squared norms to the REPORTED loss only (formed from .weight.data: no gradient)
+
     class Dataset:
         user_history_limit = 500
 

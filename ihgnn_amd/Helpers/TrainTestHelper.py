@@ -1,4 +1,4 @@
-"""Epoch loops of the RawGnn branch (reference ``Helpers/TrainTestHelper.py:12-159``).
+"""Epoch loops: the RawGnn branch (reference ``Helpers/TrainTestHelper.py:12-159``) and the Srrl branch (``:160-257``: KG steps, then the PS epoch).
 
 Differences that do not change results: the running loss stays on the GPU and is read back once per epoch
 (the reference syncs with ``loss.item()`` every step, ``TrainTestHelper.py:133``), and in a multi-process run
@@ -124,6 +124,69 @@ def _record_mode(record_step) -> str:
     raise ValueError(f'record_step: on | off | auto, got {record_step!r}')
 
 
+def srrl_kg_step(model, optimizer, batch, device: torch.device) -> torch.Tensor:
+    """One KG step of the Srrl baseline (reference ``Helpers/TrainTestHelper.py:169-214``) on a batch of ``SrrlDatasetKG.collate_fn``; -> the loss (on the device)."""
+    from .. import ops
+    positive, negative, weight, mode, true_tail, true_head, true_query = batch
+    positive, negative, weight = positive.to(device), negative.to(device), weight.to(device)
+    true_tail, true_head, true_query = true_tail.to(device), true_head.to(device), true_query.to(device)
+    optimizer.zero_grad()
+    negative_score = model.trainkg((positive, negative, true_tail, true_head, true_query), mode=mode, positive_mode=False)
+    positive_score = model.trainkg((positive, true_tail, true_head, true_query), mode=mode, positive_mode=True)
+    loss = ops.kg_loss(positive_score.view(-1), negative_score, None if Gs.Srrl.uni_weight else weight)
+    reported = loss.detach()
+    if Gs.Srrl.regularization != 0.0:
+        # as in the reference (TrainTestHelper.py:203-210) the term is formed from .weight.data: it changes the reported loss only and carries no gradient
+        kg = model.KG
+        squares = sum(t.weight.data.norm(p=2) ** 2 for t in (kg.embedding_user, kg.embedding_bag_vocabulary, kg.embedding_item))
+        reported = reported + Gs.Srrl.regularization * (Gs.Srrl.regularization * squares)
+    ops.backward(loss)
+    optimizer.step()
+    return reported
+
+
+def srrl_ps_step(model, optimizer, batch, device: torch.device) -> torch.Tensor:
+    """One PS step of the Srrl baseline (reference ``Helpers/TrainTestHelper.py:227-248``) on a batch of ``GraphDataset.collate_fn``; -> the loss (on the device)."""
+    from .. import ops
+    p_u, p_q, p_i, p_f, n_u, n_q, n_i, n_f = batch
+    users, queries, items = (torch.cat(pair).to(device) for pair in ((p_u, n_u), (p_q, n_q), (p_i, n_i)))
+    labels = torch.cat([p_f, n_f]).float().to(device)
+    optimizer.zero_grad()
+    loss = model.bce_loss(users, queries, items, labels)
+    reported = loss.detach()
+    if Gs.Srrl.regularization != 0.0:
+        # (TrainTestHelper.py:237-244: from .weight.data as well - the reported loss only)
+        squares = sum(t.weight.data.norm(p=2) ** 2 for t in (model.PS.embedding_user, model.KG.embedding_bag_vocabulary, model.PS.embedding_item))
+        reported = reported + Gs.Srrl.regularization * (Gs.Srrl.regularization * squares)
+    ops.backward(loss)
+    optimizer.step()
+    return reported
+
+
+def train_srrl_and_get_avg_loss(model, optimizer, dataloader_train, pc: ProcessController, device: torch.device) -> Tuple[float, float]:
+    """One epoch of the Srrl baseline (reference ``Helpers/TrainTestHelper.py:160-257``): ``model.srrl_steps`` KG steps from ``model.train_iterator_KG`` (under
+    ``Gs.Srrl.KG_loss``), then the PS epoch over ``dataloader_train``; -> (average PS loss, seconds).  The losses stay on the device and are read once per phase."""
+    started = time.time()
+    model.train()
+    if Gs.Srrl.KG_loss:
+        kg_started = time.time()
+        kg_sum = torch.zeros((), dtype=torch.float32, device=device)
+        for _ in range(model.srrl_steps):
+            kg_sum += srrl_kg_step(model, optimizer, model.train_iterator_KG.next(), device)
+        IOHelper.LogPrint(f'[Epoch KG {pc.CurrentEpoch:<2d}] avg loss  KG->  {kg_sum.item() / max(model.srrl_steps, 1):<.4f} in {time.time() - kg_started:<.2f}s'
+                          f' (remaining {pc.GetRemainingTimeString()}).')
+    ps_started = time.time()
+    ps_sum = torch.zeros((), dtype=torch.float32, device=device)
+    batches = 0
+    for batch in dataloader_train:
+        ps_sum += srrl_ps_step(model, optimizer, batch, device)
+        batches += 1
+    avg_loss = ps_sum.item() / max(batches, 1)
+    IOHelper.LogPrint(f'[Epoch PS {pc.CurrentEpoch:<2d}] avg loss {avg_loss:<.4f}  <-PS  in {time.time() - ps_started:<.2f}s (remaining {pc.GetRemainingTimeString()}).')
+    # (no learning-rate schedule: adjust_learning_rate is the RawGnn branch's, TrainTestHelper.py:155)
+    return avg_loss, time.time() - started
+
+
 def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.Module, dataset_train: GraphDataset,
                            dataloader_train, pc: ProcessController, device: torch.device,
                            grad_sync=None, record_step='auto') -> Tuple[float, float]:
@@ -132,6 +195,11 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
     bound by the host's launch rate, i.e. on small graphs); other batch sizes - the epoch's last batch - run eagerly.  ``'auto'`` (default): the first steps of the
     first epoch run eagerly, steps 4 - 7 are timed, and the step is recorded when they took less than ``AUTO_RECORD_BELOW_MS`` each; ``'on'`` / ``'off'`` decide
     without measuring.  A model the recording refuses (a parameter without gradient) trains eagerly, with one log line."""
+    from ..Models.Srrl import Srrl
+    if isinstance(model, Srrl):
+        if grad_sync is not None or _record_mode(record_step) == 'on':
+            raise NotImplementedError('the Srrl baseline trains in one process, eagerly: no gradient exchange, no recorded step')
+        return train_srrl_and_get_avg_loss(model, optimizer, dataloader_train, pc, device)
     started = time.time()
     loss_sum = torch.zeros((), dtype=torch.float32, device=device)
     batches = positives = 0

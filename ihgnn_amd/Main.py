@@ -1,7 +1,7 @@
 """Training / evaluation driver: ``python -m ihgnn_amd.Main --ds <dataset> [...]``.
 
 Same flags, defaults, call sequence, result-directory naming, checkpoint and metrics files as the reference's
-``Main.py`` (lines 20-325), restricted to the RawGnn model with IHGNN / HGCN layers, and written as a function
+``Main.py`` (lines 20-325): the RawGnn model with its GNN layers and the Srrl baseline (``--model Srrl``), written as a function
 so tests can drive it.  Launched under ``torchrun`` it trains data-parallel (one process per GPU, RCCL).
 """
 import os
@@ -22,12 +22,14 @@ from .Helpers.IOHelper import IOHelper
 from .Helpers.Metrics import Metrics, MetricsCollection
 from .Helpers.ProcessController import ProcessController
 from .Helpers.TrainTestHelper import print_network_parameters, test_and_get_avg_metrics, train_and_get_avg_loss
-from .Models import GATLayer, GCNLayer, HGCNLayer, HemPredictionLayer, IHGNNLayer, RawGnn, parse_gnn_layer, parse_model_type
+from .Models import GATLayer, GCNLayer, HGCNLayer, HemPredictionLayer, IHGNNLayer, RawGnn, Srrl, parse_gnn_layer, parse_model_type
 
 DEFAULT_DATASET = 'AlibabaAir/Complete5Core/'
 
 
-def result_directory(dataset_name: str, layers: int, layer_type: type, order: int, emb: int) -> str:
+def result_directory(dataset_name: str, layers: int, layer_type: type, order: int, emb: int, model_type: type = RawGnn) -> str:
+    if model_type is Srrl:                                   # (Main.py:80-86: no layer part for a model without layers)
+        return os.path.join('Results', '-'.join(dataset_name.strip('/').split('/') + ['Srrl', f'emb{emb}']))
     parts = dataset_name.strip('/').split('/') + ['RawGnn', f'{layers}{layer_type.__name__}']
     if layer_type is IHGNNLayer:
         parts.append(f'O{order}')
@@ -63,6 +65,41 @@ def apply_sampling_settings(args) -> None:
     Gs.negative_sample_size = Gs.random_negative_sample_size + Gs.non_random_negative_sample_size
 
 
+def check_srrl_settings(args, world: int) -> None:
+    """``--model Srrl``: what cannot apply is refused before anything is built."""
+    from . import ops
+    if world > 1:
+        raise NotImplementedError('--model Srrl trains in a single process: the gradient exchanges of ihgnn_amd.distributed have not been run with it')
+    if getattr(args, 'record_step', 'auto') in (True, 'on', '1', 'yes'):
+        raise NotImplementedError('--model Srrl trains eagerly: --record_step on records the RawGnn step (auto stays eager)')
+    if getattr(args, 'device_sampling', False):
+        raise NotImplementedError('--model Srrl draws its batches on the host (SrrlDatasetKG): --device_sampling does not apply')
+    if getattr(args, 'phase2', False):
+        raise ValueError('--phase2 is the IHGNN layer\'s phase-2 attention; --model Srrl has no layers')
+    widest = ops.cat_linear_max_width()
+    if 2 * Gs.embedding_size > widest:
+        # every block of the model concatenates two rows of the embedding width: said here, not by the first forward's launch
+        raise ValueError(f'--model Srrl: --emb {Gs.embedding_size} makes concatenated rows of {2 * Gs.embedding_size} floats, beyond the {widest} the block kernels take '
+                         f'(ihg_cat_linear_max_width()); use --emb {widest // 2} or less')
+    batch_rows = Gs.batch_size * (1 + Gs.negative_sample_size)
+    if batch_rows > ops.SCATTER_CHUNK_ROWS:
+        # the row gradients of a batch reach the embedding tables through ihg_batch_combine, whose launch takes ihg_batch_scatter_max_rows() rows: said here, not
+        # in the middle of the first backward
+        raise ValueError(f'--model Srrl: a batch of {Gs.batch_size} x (1 + {Gs.negative_sample_size}) = {batch_rows} rows is beyond the {ops.SCATTER_CHUNK_ROWS} rows of one '
+                         'deterministic scatter launch; use a smaller batch')
+
+
+def build_srrl(dataset_train, device):
+    """The Srrl model with its three KG loaders and the KG steps per epoch (Main.py:169-187)."""
+    from .SrrlDataset import MODES, MetaPaths, OneShotIterator, SrrlDatasetKG
+    meta_paths = MetaPaths(dataset_train)
+    loaders = [DataLoader(SrrlDatasetKG(meta_paths, Gs.negative_sample_size, mode), Gs.batch_size, True, collate_fn=SrrlDatasetKG.collate_fn) for mode in MODES]
+    model = Srrl(dataset=dataset_train, embedding_size=Gs.embedding_size, prediction_layer_type=None, lambda_muq=Gs.lambda_muq_for_hem).to(device)
+    model.srrl_steps = -(-len(meta_paths.positive_interactions) // Gs.batch_size)
+    model.train_iterator_KG = OneShotIterator(*loaders)
+    return model
+
+
 def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     args = parse_args(argv)
     rank, local_rank, world = ihg_dist.init_from_env()
@@ -80,8 +117,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     start_test = args.epoch_start_test or 10
     test_every = args.epoch_test_frequency or start_test
     dataset_name = args.dataset or DEFAULT_DATASET
-    if (parse_model_type[args.model] or RawGnn) is not RawGnn:
-        raise NotImplementedError('only the RawGnn model is part of this build')
+    model_type = parse_model_type[args.model] or RawGnn
     layer_type = parse_gnn_layer[args.gnn] or IHGNNLayer
     if layer_type not in (IHGNNLayer, HGCNLayer, GCNLayer, GATLayer):
         raise NotImplementedError(f'{layer_type.__name__} is outside the MI355X hypergraph path')
@@ -96,6 +132,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     apply_prediction_settings(args)
     apply_evaluation_settings(args)
     apply_sampling_settings(args)
+    if model_type is Srrl:
+        check_srrl_settings(args, world)
     if args.device == 'cpu':
         raise RuntimeError('ihgnn_amd has no CPU path: the hypergraph kernels are HIP-only')
     device = torch.device(f'cuda:{args.device}' if args.device else f'cuda:{local_rank}')
@@ -103,7 +141,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
 
     root = IOHelper.GetFirstLineContent('./dataset_dir.txt') if os.path.exists('./dataset_dir.txt') else './Data/'
     data_dir = os.path.join(root, dataset_name)
-    result_dir = result_directory(dataset_name, layer_count, layer_type, order, Gs.embedding_size)
+    result_dir = result_directory(dataset_name, layer_count, layer_type, order, Gs.embedding_size, model_type)
     os.makedirs(result_dir, exist_ok=True)
     stamp = time.strftime('%y%m%d-%H%M%S', time.localtime())
     fn_metrics = os.path.join(result_dir, f'{stamp}_metrics.txt')
@@ -116,7 +154,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
 
     say(f'device {device} | ranks {world} | batch {Gs.batch_size} | lr {Gs.learning_rate} | emb {Gs.embedding_size} | '
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}')
-    say(f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | '
+    say((f'model Srrl | dataset {dataset_name} | KG loss {Gs.Srrl.KG_loss} | uniform KG weights {Gs.Srrl.uni_weight} | ' if model_type is Srrl else
+         f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | ') +
         f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
         f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | validation {Gs.use_valid_dataset}')
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
@@ -144,9 +183,12 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     dataloader_valid = TestSearchLogDataLoader(os.path.join(data_dir, 'valid_data.csv'), dataset_train, device)
     dataloader_test = TestSearchLogDataLoader(os.path.join(data_dir, 'test_data.csv'), dataset_train, device)
 
-    model = RawGnn(device=device, dataset=dataset_train, embedding_size=Gs.embedding_size, gnn_layer_type=layer_type,
-                   gnn_layer_count=layer_count, predictions=HemPredictionLayer, lambda_muq=Gs.lambda_muq_for_hem,
-                   feature_interaction_order=order, phase2_attention=phase2).to(device)
+    if model_type is Srrl:
+        model = build_srrl(dataset_train, device)
+    else:
+        model = RawGnn(device=device, dataset=dataset_train, embedding_size=Gs.embedding_size, gnn_layer_type=layer_type,
+                       gnn_layer_count=layer_count, predictions=HemPredictionLayer, lambda_muq=Gs.lambda_muq_for_hem,
+                       feature_interaction_order=order, phase2_attention=phase2).to(device)
     loss_function = nn.BCEWithLogitsLoss().to(device)
     from .optim import Adam
     grad_sync = None

@@ -60,3 +60,32 @@ class FeatureInteractor(nn.Module):
         if self.max_order == 1:
             return ops.edge_gather_sum(hoisted, layout)
         return ops.interact(node_features, hoisted, self._operands(node_features)[0], layout, self.max_order)
+
+
+class Aggregation(nn.Module):
+    """``nn.Sequential(nn.Linear(input_dim, output_dim), nn.LeakyReLU())`` on ``F.normalize(cat(a, b), dim=-1)`` (reference ``Models/CommonLayers.py:18-26`` with the
+    concatenation and normalisation every caller in ``Models/Srrl.py`` puts in front of it): one launch of the block kernel (``ops.cat_linear``).  State-dict keys
+    ``aggregation.0.weight`` / ``.bias``, default ``nn.Linear`` initialisation."""
+
+    def __init__(self, input_dim: int, output_dim: int):
+        super().__init__()
+        self.aggregation = nn.Sequential(nn.Linear(input_dim, output_dim), nn.LeakyReLU())
+
+    def forward(self, a: Tensor, b: Optional[Tensor] = None, **sources) -> Tensor:
+        """``sources``: ``idx_a``, ``rep_a``, ``idx_b``, ``rep_b`` of ``ops.cat_linear``."""
+        linear = self.aggregation[0]
+        return ops.cat_linear(a, b, linear.weight, linear.bias, leaky=True, **sources)
+
+
+class MLP(nn.Module):
+    """``nn.Sequential(nn.Linear(input_dim, input_dim), nn.LeakyReLU(), nn.Linear(input_dim, output_dim))`` on ``F.normalize(cat(a, b), dim=-1)`` (reference
+    ``Models/CommonLayers.py:7-16``): the block kernel, then the same kernel as a plain Linear.  State-dict keys ``mlp.0.*`` and ``mlp.2.*``."""
+
+    def __init__(self, input_dim: int, output_dim: int):
+        super().__init__()
+        self.mlp = nn.Sequential(nn.Linear(input_dim, input_dim), nn.LeakyReLU(), nn.Linear(input_dim, output_dim))
+
+    def forward(self, a: Tensor, b: Optional[Tensor] = None, **sources) -> Tensor:
+        first, last = self.mlp[0], self.mlp[2]
+        hidden = ops.cat_linear(a, b, first.weight, first.bias, leaky=True, **sources)
+        return ops.cat_linear(hidden, None, last.weight, last.bias, normalize=False)

@@ -6,9 +6,10 @@ from .EmbeddingLayers import EmbeddingLayer
 from .GnnLayers import GATLayer, GCNLayer, HGCNLayer, IHGNNLayer
 from .PredictionLayers import HemPredictionLayer
 from .RawGnn import RawGnn
+from .Srrl import Srrl
 
-PpsModel = Union[RawGnn]
-PpsModelTypes = [RawGnn]
+PpsModel = Union[RawGnn, Srrl]
+PpsModelTypes = [RawGnn, Srrl]
 GnnLayer = Union[GCNLayer, GATLayer, HGCNLayer, IHGNNLayer]
 GnnLayerTypes = [GCNLayer, GATLayer, HGCNLayer, IHGNNLayer]
 

@@ -168,7 +168,20 @@ SIGNATURES = {
     'ihg_phase2_edges_bwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
     'ihg_phase2_add_rows': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
     'ihg_phase2_finish_bwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    # the Srrl baseline (csrc/srrl.hip): a source of the block is (base, ld, width, idx, rep)
+    'ihg_cat_linear_max_width': (c_int32, []),
+    'ihg_cat_linear_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
+    'ihg_cat_linear_fwd': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32,
+                                          c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'ihg_cat_linear_bwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64,
+                                          c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                          c_void_p, c_int64, c_void_p]),
+    'ihg_rows_dot_fwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    'ihg_rows_dot_bwd': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
+    'ihg_kg_loss': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'ihg_rows_topk': (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
 }
+ACT_NONE, ACT_LEAKY_RELU = 0, 3
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -14,6 +14,9 @@ interact     (K5+K6)   ihg_interact_fwd            ihg_interact_bwd + 4x ihg_nod
 gat_attention          ihg_gat_attention_fwd + K7  ihg_gat_scores_bwd, K7, ihg_gat_finish_bwd
 hyper_attention        ihg_phase2_attention_fwd    ihg_phase2_scores_bwd, ihg_phase2_edges_bwd, (K7,) ihg_phase2_finish_bwd
                        + K7
+cat_linear (Srrl)      ihg_cat_linear_fwd          ihg_cat_linear_bwd (+ ihg_batch_combine / ihg_batch_rows_add for a gathered source)
+rows_dot (Srrl)        ihg_rows_dot_fwd            ihg_rows_dot_bwd
+kg_loss (Srrl)         ihg_kg_loss                 (its gradients come from the forward launch)
 """
 from __future__ import annotations
 
@@ -1903,3 +1906,232 @@ def hem_bce_loss(layers, rows: Tensor, items: Tensor, labels: Tensor, bias: Tens
     if rows_upper is not None and holder is not None and holder.row_map is None:
         raise ValueError('rows_upper comes with holder.row_map (the layout\'s public -> own node map)')
     return _HemBceLoss.apply(rows, items, labels, bias, float(lam), int(item_row_offset), holder, tables, rows_upper, bool(cosine), *layers)
+
+
+# ---------------------------------------------------------------------------------------------
+# the Srrl baseline (Models/Srrl.py): block = F.normalize(cat(a, b)) -> Linear -> LeakyReLU, row dots, KG loss, dense top-k
+# ---------------------------------------------------------------------------------------------
+def _gpu(t: Tensor, name: str) -> Tensor:
+    if not t.is_cuda:
+        raise _lib.IhgnnHipError(f'{name} must be a GPU tensor: ihgnn_amd has no CPU path (got device {t.device})')
+    return t
+
+
+def _index(idx: Optional[Tensor], name: str) -> Optional[Tensor]:
+    if idx is None:
+        return None
+    _gpu(idx, name)
+    return idx.to(torch.int64).contiguous()
+
+
+def scatter_row_gradients(rowgrad: Tensor, idx: Tensor, n_rows: int) -> Tensor:
+    """``zeros [n_rows, w]`` with ``out[idx[k]] += rowgrad[k]``: the rows of equal destination are combined in batch order (``ihg_batch_combine``), then added
+    (``ihg_batch_rows_add``) - no atomics, at most ``SCATTER_CHUNK_ROWS`` rows per launch.  ``rowgrad`` is used up (combined in place)."""
+    lib = _lib.load()
+    _gpu(rowgrad, 'rowgrad')
+    width = int(rowgrad.shape[1])
+    dense = torch.zeros(n_rows, width, dtype=torch.float32, device=rowgrad.device)
+    n = int(idx.shape[0])
+    for lo in range(0, n, SCATTER_CHUNK_ROWS):
+        hi = min(lo + SCATTER_CHUNK_ROWS, n)
+        part, rows = rowgrad[lo:hi], idx[lo:hi]
+        leader = torch.empty(hi - lo, dtype=torch.int32, device=rowgrad.device)
+        with profiler.kernel('batch_combine', hi - lo, width):
+            _lib.check(lib.ihg_batch_combine(_ptr(part), _ld(rowgrad), width, _ptr(rows), hi - lo, 0, _ptr(leader), _stream()), 'ihg_batch_combine')
+        with profiler.kernel('batch_rows_add', hi - lo, width):
+            _lib.check(lib.ihg_batch_rows_add(_ptr(part), _ld(rowgrad), width, _ptr(rows), _ptr(leader), hi - lo, _ptr(dense), _ld(dense), None, 0, 0, _stream()),
+                       'ihg_batch_rows_add')
+    return dense
+
+
+def _cat_source(t: Optional[Tensor], idx: Optional[Tensor], rep: int):
+    """The five arguments of one source of the block."""
+    if t is None:
+        return (None, 0, 0, None, 1)
+    return (_ptr(t), _ld(t), int(t.shape[1]), _ptr(idx), int(rep))
+
+
+def _source_groups(t: Tensor, idx: Optional[Tensor]) -> int:
+    return int(t.shape[0]) if idx is None else int(idx.shape[0])
+
+
+class _CatLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a: Tensor, b: Optional[Tensor], w: Tensor, bias: Optional[Tensor], idx_a: Optional[Tensor], rep_a: int, idx_b: Optional[Tensor], rep_b: int,
+                normalize: bool, activation: int) -> Tensor:
+        lib = _lib.load()
+        a = _rows(a.detach(), 'a')
+        b = None if b is None else _rows(b.detach(), 'b')
+        wd = _rows(w.detach(), 'w')
+        bd = None if bias is None else _gpu(bias.detach(), 'bias').contiguous()
+        idx_a, idx_b = _index(idx_a, 'idx_a'), _index(idx_b, 'idx_b')
+        n_rows = _source_groups(a, idx_a) * rep_a
+        if b is not None and _source_groups(b, idx_b) * rep_b != n_rows:
+            raise ValueError(f'cat_linear: {n_rows} rows of a against {_source_groups(b, idx_b) * rep_b} of b')
+        m = int(wd.shape[0])
+        out = torch.empty(n_rows, m, dtype=torch.float32, device=a.device)
+        inv_norm = torch.empty(n_rows, dtype=torch.float32, device=a.device) if normalize else None
+        with profiler.kernel('cat_linear_fwd', n_rows, m):
+            _lib.check(lib.ihg_cat_linear_fwd(*_cat_source(a, idx_a, rep_a), *_cat_source(b, idx_b, rep_b), _ptr(wd), _ld(wd), _ptr(bd), m, int(normalize), activation,
+                                              _ptr(out), m, _ptr(inv_norm), n_rows, _stream()), 'ihg_cat_linear_fwd')
+        ctx.save_for_backward(a, b, wd, idx_a, idx_b, inv_norm, out)      # (out through save_for_backward: an attribute would tie the node to its own output)
+        ctx.args = (rep_a, rep_b, normalize, activation, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        lib = _lib.load()
+        a, b, w, idx_a, idx_b, inv_norm, out = ctx.saved_tensors
+        rep_a, rep_b, normalize, activation, has_bias = ctx.args
+        need_a, need_b = ctx.needs_input_grad[0], b is not None and ctx.needs_input_grad[1]
+        dy = _rows(dy, 'dy')
+        n_rows, m = int(out.shape[0]), int(out.shape[1])
+        wa, wb = int(a.shape[1]), 0 if b is None else int(b.shape[1])
+        dw = torch.empty_like(w, memory_format=torch.contiguous_format)
+        dbias = torch.empty(m, dtype=torch.float32, device=w.device) if has_bias else None
+        da = torch.empty(n_rows // rep_a, wa, dtype=torch.float32, device=w.device) if need_a else None
+        db = torch.empty(n_rows // rep_b, wb, dtype=torch.float32, device=w.device) if need_b else None
+        ws = _workspace(int(lib.ihg_cat_linear_workspace_bytes(n_rows, wa + wb, m)), w.device)
+        with profiler.kernel('cat_linear_bwd', n_rows, m):
+            _lib.check(lib.ihg_cat_linear_bwd(_ptr(dy), _ld(dy), _ptr(out), m, *_cat_source(a, idx_a, rep_a), *_cat_source(b, idx_b, rep_b), _ptr(inv_norm), _ptr(w), _ld(w), m,
+                                              int(normalize), activation, _ptr(dw), wa + wb, _ptr(dbias), _ptr(da), wa, _ptr(db), wb, n_rows, _ptr(ws), ws.numel() * 4,
+                                              _stream()), 'ihg_cat_linear_bwd')
+        if need_a and idx_a is not None:
+            da = scatter_row_gradients(da, idx_a, int(a.shape[0]))
+        if need_b and idx_b is not None:
+            db = scatter_row_gradients(db, idx_b, int(b.shape[0]))
+        return da, db, dw, dbias, None, None, None, None, None, None
+
+
+def cat_linear_max_width() -> int:
+    """The widest concatenated row, and the widest output row, ``cat_linear`` takes (256)."""
+    return int(_lib.load().ihg_cat_linear_max_width())
+
+
+def cat_linear(a: Tensor, b: Optional[Tensor], w: Tensor, bias: Optional[Tensor], idx_a: Optional[Tensor] = None, rep_a: int = 1, idx_b: Optional[Tensor] = None,
+               rep_b: int = 1, normalize: bool = True, leaky: bool = False) -> Tensor:
+    """``act(F.normalize(cat(a[idx_a].repeat_interleave(rep_a), b[idx_b].repeat_interleave(rep_b)), dim=-1) @ w.T + bias)`` as one launch, ``[rows, m]``; its backward is one
+    call too (``ihg_cat_linear_bwd``), and a gathered source's gradient reaches its table through the deterministic batch-row scatter.  ``b`` may be ``None``;
+    ``normalize=False`` is a plain Linear; ``leaky``: ``nn.LeakyReLU()``."""
+    if w.dim() != 2 or w.shape[1] != a.shape[1] + (0 if b is None else b.shape[1]):
+        raise ValueError(f'cat_linear: weight {tuple(w.shape)} against sources of width {a.shape[1]} + {0 if b is None else b.shape[1]}')
+    return _CatLinear.apply(a, b, w, bias, idx_a, int(rep_a), idx_b, int(rep_b), bool(normalize), _lib.ACT_LEAKY_RELU if leaky else _lib.ACT_NONE)
+
+
+class _RowsDot(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, y: Tensor, rep: int) -> Tensor:
+        lib = _lib.load()
+        x, y = _rows(x.detach(), 'x'), _rows(y.detach(), 'y')
+        n_rows, width = int(x.shape[0]), int(x.shape[1])
+        if int(y.shape[0]) * rep != n_rows or int(y.shape[1]) != width:
+            raise ValueError(f'rows_dot: x {tuple(x.shape)} against y {tuple(y.shape)} repeated {rep} times')
+        s = torch.empty(n_rows, dtype=torch.float32, device=x.device)
+        with profiler.kernel('rows_dot_fwd', n_rows, width):
+            _lib.check(lib.ihg_rows_dot_fwd(_ptr(x), _ld(x), _ptr(y), _ld(y), rep, _ptr(s), n_rows, width, _stream()), 'ihg_rows_dot_fwd')
+        ctx.save_for_backward(x, y)
+        ctx.rep = rep
+        return s
+
+    @staticmethod
+    def backward(ctx, ds: Tensor):
+        lib = _lib.load()
+        x, y = ctx.saved_tensors
+        rep = ctx.rep
+        ds = ds.contiguous()
+        n_rows, width = int(x.shape[0]), int(x.shape[1])
+        dx = torch.empty(n_rows, width, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        dy = torch.empty(n_rows // rep, width, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[1] else None
+        with profiler.kernel('rows_dot_bwd', n_rows, width):
+            _lib.check(lib.ihg_rows_dot_bwd(_ptr(ds), _ptr(x), _ld(x), _ptr(y), _ld(y), rep, _ptr(dx), width, _ptr(dy), width, n_rows, width, _stream()), 'ihg_rows_dot_bwd')
+        return dx, dy, None
+
+
+def rows_dot(x: Tensor, y: Tensor, rep: int = 1) -> Tensor:
+    """``(x * y.repeat_interleave(rep, 0)).sum(-1)``: the KG scores of ``Models/Srrl.py`` with their broadcast over the negatives, ``[rows]``."""
+    return _RowsDot.apply(x, y, int(rep))
+
+
+class _KgLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos: Tensor, neg: Tensor, weight: Optional[Tensor]) -> Tensor:
+        lib = _lib.load()
+        pos = _gpu(pos.detach(), 'pos').contiguous().view(-1)
+        neg = _rows(neg.detach(), 'neg')
+        weight = None if weight is None else _gpu(weight, 'weight').to(torch.float32).contiguous()
+        batch, k = int(neg.shape[0]), int(neg.shape[1])
+        if int(pos.shape[0]) != batch or (weight is not None and int(weight.shape[0]) != batch):
+            raise ValueError(f'kg_loss: pos {tuple(pos.shape)}, neg {tuple(neg.shape)}')
+        loss = torch.empty((), dtype=torch.float32, device=pos.device)
+        dpos = torch.empty(batch, dtype=torch.float32, device=pos.device)
+        dneg = torch.empty(batch, k, dtype=torch.float32, device=pos.device)
+        with profiler.kernel('kg_loss', batch, k):
+            _lib.check(lib.ihg_kg_loss(_ptr(pos), _ptr(neg), _ld(neg), _ptr(weight), batch, k, _ptr(loss), _ptr(dpos), _ptr(dneg), k, _stream()), 'ihg_kg_loss')
+        ctx.save_for_backward(dpos, dneg)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss: Tensor):
+        dpos, dneg = ctx.saved_tensors
+        return dpos * grad_loss, dneg * grad_loss, None
+
+
+def kg_loss(pos: Tensor, neg: Tensor, weight: Optional[Tensor] = None) -> Tensor:
+    """The KG loss of ``Helpers/TrainTestHelper.py:185-201``: ``(-sum w logsigmoid(pos) / sum w - sum w logsigmoid(-neg).mean(1) / sum w) / 2`` with its gradient, one launch;
+    ``weight=None``: uniform (``Gs.Srrl.uni_weight``).  ``pos [B]``, ``neg [B, k]``."""
+    return _KgLoss.apply(pos, neg, weight)
+
+
+def rows_topk(scores: Tensor, k: int):
+    """The ``k`` best entries of every row of a dense ``[C, I]`` score matrix, best first, equal scores in ascending item id (``score_topk``'s order):
+    ``(items [C, k] int64, scores [C, k])``, ``-1`` / ``-inf`` beyond ``I`` entries."""
+    lib = _lib.load()
+    scores = _rows(scores.detach(), 'scores')
+    n_rows, n_items = int(scores.shape[0]), int(scores.shape[1])
+    items = torch.empty(n_rows, max(int(k), 0), dtype=torch.int64, device=scores.device)
+    top = torch.empty(n_rows, max(int(k), 0), dtype=torch.float32, device=scores.device)
+    with profiler.kernel('rows_topk', n_rows, int(k)):
+        _lib.check(lib.ihg_rows_topk(_ptr(scores), _ld(scores), n_rows, n_items, int(k), _ptr(items), _ptr(top), _stream()), 'ihg_rows_topk')
+    return items, top
+
+
+class _BceWithLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores: Tensor, labels: Tensor) -> Tensor:
+        lib = _lib.load()
+        scores = _gpu(scores.detach(), 'scores').contiguous()
+        labels = _gpu(labels, 'labels').to(torch.float32).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=scores.device)
+        dscores = torch.empty_like(scores)
+        with profiler.kernel('bce_with_logits', int(scores.numel()), 1):
+            _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), int(scores.numel()), _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
+        ctx.save_for_backward(dscores)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss: Tensor):
+        return ctx.saved_tensors[0] * grad_loss, None
+
+
+def bce_with_logits(scores: Tensor, labels: Tensor) -> Tensor:
+    """``nn.BCEWithLogitsLoss()(scores, labels)`` with its gradient from the one launch of ``ihg_bce_with_logits``."""
+    return _BceWithLogits.apply(scores, labels)
+
+
+class _GatherRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table: Tensor, idx: Tensor) -> Tensor:
+        _gpu(table, 'table')
+        idx = _index(idx, 'idx')
+        ctx.save_for_backward(idx)
+        ctx.n_rows = int(table.shape[0])
+        return table.detach().index_select(0, idx)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        return scatter_row_gradients(_rows(grad, 'grad').clone(), ctx.saved_tensors[0], ctx.n_rows), None
+
+
+def gather_rows(table: Tensor, idx: Tensor) -> Tensor:
+    """``table[idx]`` whose backward is the deterministic batch-row scatter (``scatter_row_gradients``) instead of autograd's atomic ``index_put_``."""
+    return _GatherRows.apply(table, idx)

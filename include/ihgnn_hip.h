@@ -737,6 +737,51 @@ int ihg_batch_node_rows(const int64_t* users, const int64_t* queries, const int6
                         int64_t* rows, int32_t* rows32, ihg_stream_t stream);
 int ihg_zero_rows(float* base, int64_t ld, int32_t dim, const int64_t* rows, int64_t n, ihg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DEVICE: the Srrl baseline (Models/Srrl.py, csrc/srrl.hip).  Every module of that model is one block
+ *     F.normalize(cat(a, b), dim=-1) -> nn.Linear -> optional nn.LeakyReLU()          (Aggregation: one block; MLP: one block, then a plain Linear)
+ *   ihg_cat_linear_fwd   out[r] = act(w n(cat(a[ia(r)], b[ib(r)])) + bias), r < n_rows.  A source is a row table (base, ld, width), an optional int64 index vector and a
+ *                        repeat factor rep >= 1: row r reads table row idx[r / rep] (idx NULL: row r / rep) - the `expand` of a [B, 1, .] operand over k negatives, or one
+ *                        user / query row over all items at evaluation.  n_rows must be whole groups of both repeat factors.  width_b == 0: a single source.
+ *                        Index entries must name rows of their table: they are not checked.
+ *                        n(x) = x / max(|x|_2, 1e-12) (F.normalize) when `normalize` != 0, else x.  activation: IHG_ACT_NONE or IHG_ACT_LEAKY_RELU (slope 0.01).
+ *                        w [m, width_a + width_b] with row stride ld_w; out [n_rows, m] with any ld_out >= m.  With `normalize` the row's 1 / max(|x|, eps) goes to
+ *                        inv_norm [n_rows] for the backward.  The scale is applied to the row's products after the sum (w (x / n) = (w x) / n).
+ *   ihg_cat_linear_bwd   autograd's backward of the same block in one call: dz = dy * act'(y) formed as dy is loaded (act'(y) = y > 0 ? 1 : 0.01, no pre-activation stored),
+ *                        dw [m, K] and dbias [m] (NULL: skipped) as per-workgroup partials added in a fixed order (no atomics, bitwise reproducible), and the input
+ *                        gradient of F.normalize as autograd forms it - (dx^ - x^ (x^ . dx^)) / |x| above eps, dx^ / eps below (stored inverse norm = 1 / eps) - split
+ *                        into da [n_rows / rep_a, width_a] and db [n_rows / rep_b, width_b], the rep rows of a group added in ascending order.  Either may be NULL.
+ *                        These are ROW gradients: a gathered source lands in its table through ihg_batch_combine + ihg_batch_rows_add.
+ *                        n_rows == 0: dw and dbias are zeroed.  workspace: ihg_cat_linear_workspace_bytes(n_rows, width_a + width_b, m) bytes, 16-byte aligned.
+ *   Widths: width_a + width_b = 64 / 128 (d = 32 / 64) with both sources' rows and the weight's rows on 16-byte boundaries run on the matrix cores in exact fp32
+ *   (v_mfma_f32_32x32x2_f32; the backward for m <= 128); every other width up to ihg_cat_linear_max_width() = 256, alignment or m: the any-width kernels, one thread
+ *   per output element, rows staged in LDS 16 at a time, sums in index order.
+ *   No allocation and no synchronisation inside the library.
+ *   ihg_rows_dot_fwd     s[r] = sum_c x[r, c] y[r / rep, c]                                 (Models/Srrl.py:209, 221, 233 with their broadcast)
+ *   ihg_rows_dot_bwd     dx[r] = ds[r] y[r / rep], dy[g] = sum_{r in g} ds[r] x[r] in ascending r; either NULL: skipped
+ *   ihg_kg_loss          the KG loss of Helpers/TrainTestHelper.py:185-201 in one launch: pos [batch], neg [batch, k], weight [batch] or NULL (Gs.Srrl.uni_weight):
+ *                        loss = (-sum w logsigmoid(pos) / sum w - sum w mean_k logsigmoid(-neg) / sum w) / 2, with dpos [batch] and dneg [batch, k]; fixed-order sums
+ *   ihg_rows_topk        per row of a dense fp32 score matrix [n_rows, n_items] (row stride ld): the k <= 128 best (item, score) pairs, best first, equal scores in
+ *                        ascending item id (ihg_score_topk's order); items [n_rows, k] int64, top_scores [n_rows, k]; beyond n_items entries: -1 / -inf.  A NaN is not ranked.
+ */
+#define IHG_ACT_NONE          0
+#define IHG_ACT_LEAKY_RELU    3   /* nn.LeakyReLU(): the block kernels of the Srrl baseline only */
+int32_t ihg_cat_linear_max_width(void);
+int64_t ihg_cat_linear_workspace_bytes(int64_t n_rows, int32_t width, int32_t m);      /* -1: a width beyond ihg_cat_linear_max_width() */
+int ihg_cat_linear_fwd(const float* a, int64_t ld_a, int32_t width_a, const int64_t* idx_a, int64_t rep_a, const float* b, int64_t ld_b, int32_t width_b, const int64_t* idx_b,
+                       int64_t rep_b, const float* w, int64_t ld_w, const float* bias, int32_t m, int32_t normalize, int32_t activation, float* out, int64_t ld_out,
+                       float* inv_norm, int64_t n_rows, ihg_stream_t stream);
+int ihg_cat_linear_bwd(const float* dy, int64_t ld_dy, const float* y, int64_t ld_y, const float* a, int64_t ld_a, int32_t width_a, const int64_t* idx_a, int64_t rep_a,
+                       const float* b, int64_t ld_b, int32_t width_b, const int64_t* idx_b, int64_t rep_b, const float* inv_norm, const float* w, int64_t ld_w, int32_t m,
+                       int32_t normalize, int32_t activation, float* dw, int64_t ld_dw, float* dbias, float* da, int64_t ld_da, float* db, int64_t ld_db, int64_t n_rows,
+                       void* workspace, int64_t workspace_bytes, ihg_stream_t stream);
+int ihg_rows_dot_fwd(const float* x, int64_t ld_x, const float* y, int64_t ld_y, int64_t rep, float* s, int64_t n_rows, int32_t width, ihg_stream_t stream);
+int ihg_rows_dot_bwd(const float* ds, const float* x, int64_t ld_x, const float* y, int64_t ld_y, int64_t rep, float* dx, int64_t ld_dx, float* dy, int64_t ld_dy, int64_t n_rows,
+                     int32_t width, ihg_stream_t stream);
+int ihg_kg_loss(const float* pos, const float* neg, int64_t ld_neg, const float* weight, int64_t batch, int32_t k, float* loss, float* dpos, float* dneg, int64_t ld_dneg,
+                ihg_stream_t stream);
+int ihg_rows_topk(const float* scores, int64_t ld, int64_t n_rows, int64_t n_items, int32_t k, int64_t* items, float* top_scores, ihg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
