@@ -79,6 +79,18 @@ class EmbeddingLayer(nn.Module):
         queries = ops.bag_mean(self.embedding_bag_vocabulary.weight, self.dataset.bag_layout, *self._transform())
         return queries if query_indices is None else queries[query_indices]
 
+    def embed_bags(self, words, offsets) -> Tensor:
+        """``[C, d]``: the layer-0 rows of ``C`` queries given by their words - ``words`` flat 0-based word ids as ``GraphDataset`` reads them from
+        ``queries_multihot.txt``, ``offsets`` the start of every bag (``nn.EmbeddingBag``'s input) - through the kernels of ``embed_query`` over an ad-hoc
+        ``ops.BagLayout``: the bag mean, then the query transform where there is one.  An empty bag gives a zero row, or ``act(b)`` under the transform, as in
+        training; a bag that equals a training query's words gives that query's X0 row bit for bit."""
+        import numpy as np
+        words = np.asarray(words.cpu() if isinstance(words, Tensor) else words, dtype=np.int64).reshape(-1)
+        offsets = np.asarray(offsets.cpu() if isinstance(offsets, Tensor) else offsets, dtype=np.int64).reshape(-1)
+        table = self.embedding_bag_vocabulary.weight
+        bag = ops.BagLayout(words + 1, offsets, int(table.shape[0]), table.device)      # (stored id = index + 1: row 0 is padding)
+        return ops.bag_mean(table, bag, *self._transform())
+
     @staticmethod
     def create_embedding(num_embeddings: int, embedding_dimension: int, padding_idx: Optional[int] = None) -> nn.Embedding:
         table = nn.Embedding(num_embeddings, embedding_dimension, padding_idx=padding_idx)

@@ -278,6 +278,79 @@ class RawGnn(nn.Module):
         return ops.score_topk(features, user_indices, query_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph,
                               head.items_bias, head.lambda_muq, k, cosine=Gs.Prediction.use_cosine_similarity)
 
+    def _check_search_inputs(self, users, queries, words, offsets, candidates):
+        """The host-side checks of ``search``, before anything is launched (a tensor that already lives on the device is taken as checked: reading it back would
+        stall the stream the answer is waited on).  Returns ``(words, offsets)`` as int64 numpy arrays (``None, None`` with ``queries``)."""
+        import numpy as np
+        ds = self.dataset
+        for layer in self.gnns:
+            if getattr(getattr(layer, 'graph', None), 'self_loops', False):
+                # (with a self connection an isolated node's layer output is its own transformed row, not zero: an unseen query has rows above layer 0)
+                raise NotImplementedError('RawGnn.search scores an unseen query as an isolated node with zero layer outputs; a pairwise graph with self connections gives it others')
+
+        def on_host(t):
+            if t is None or (isinstance(t, Tensor) and t.is_cuda):
+                return None
+            return np.asarray(t.detach() if isinstance(t, Tensor) else t)
+
+        if (queries is None) == (words is None):
+            raise ValueError('RawGnn.search: give exactly one of queries= and words= (with offsets=)')
+        if (words is None) != (offsets is None):
+            raise ValueError('RawGnn.search: words= and offsets= go together')
+        u = on_host(users)
+        if u is not None and u.size and (u.min() < -1 or u.max() >= ds.user_count):
+            raise ValueError(f'RawGnn.search: user outside [-1, {ds.user_count}) (-1: no user)')
+        n_pairs = int(users.shape[0]) if hasattr(users, 'shape') else len(users)
+        q = on_host(queries)
+        if q is not None and q.size and (q.min() < 0 or q.max() >= ds.query_count):
+            raise ValueError(f'RawGnn.search: query outside [0, {ds.query_count})')
+        if queries is not None and (int(queries.shape[0]) if hasattr(queries, 'shape') else len(queries)) != n_pairs:
+            raise ValueError('RawGnn.search: one query per user')
+        c = on_host(candidates)
+        if c is not None and c.dtype != np.bool_ and c.size and (c.min() < 0 or c.max() >= ds.item_count):
+            raise ValueError(f'RawGnn.search: candidate item id outside [0, {ds.item_count})')
+        if c is not None and c.dtype == np.bool_ and c.shape != (ds.item_count,):
+            raise ValueError(f'RawGnn.search: a candidate mask is a bool tensor of [{ds.item_count}]')
+        if words is None:
+            return None, None
+        w = np.asarray(words.detach().cpu() if isinstance(words, Tensor) else words, dtype=np.int64).reshape(-1)
+        o = np.asarray(offsets.detach().cpu() if isinstance(offsets, Tensor) else offsets, dtype=np.int64).reshape(-1)
+        if w.size and (w.min() < 0 or w.max() >= ds.vocab_size):
+            raise ValueError(f'RawGnn.search: word id outside [0, {ds.vocab_size})')
+        if o.size != n_pairs:
+            raise ValueError(f'RawGnn.search: {o.size} bags for {n_pairs} users')
+        if o.size and (o[0] != 0 or np.any(np.diff(o) < 0) or o[-1] > w.size):
+            raise ValueError('RawGnn.search: offsets start at 0, do not decrease and stay within the words')
+        return w, o
+
+    @torch.no_grad()
+    def search(self, users, *, queries=None, words=None, offsets=None, k: int = 10, candidates=None):
+        """``(items [C, k] int32, scores [C, k])``: ``top_items`` for a search as it arrives.  ``users`` int64 ``[C]``, ``-1`` = nobody logged in: the head's
+        ``user_feature is None`` branch (``PredictionLayers.py:34-37``), the mixed row is the query row.  The query is EITHER ``queries`` (training query indices) OR
+        ``words`` with ``offsets`` (flat 0-based word ids and the start of every bag, as for ``nn.EmbeddingBag``): a query the graph has not seen is an isolated node -
+        its layer-0 row is ``EmbeddingLayer.embed_bags`` of its words, every layer output above is exactly zero (``Graph.py:120``) - scored as if appended to
+        ``queries_multihot.txt`` with no interaction.  A bag that happens to equal a training query's words is still scored this way (its layer-0 row equals that
+        query's, bit for bit; its upper rows are zero).  ``candidates``: a bool ``[I]`` mask or int64 item ids - only these are ranked; with fewer than ``k`` of them
+        the rest of a row is ``-1``.  Features, head and ``k`` as in ``top_items``; no retraining, no new parameter, no ``[C, I]`` matrix."""
+        from .. import ops
+        w, o = self._check_search_inputs(users, queries, words, offsets, candidates)
+        ds, head = self.dataset, self.prediction_layer
+        if k < 1 or k > ops.score_topk_max_k():
+            raise ValueError(f'RawGnn.search ranks 1 to {ops.score_topk_max_k()} items per pair, got k = {k}')
+        k = min(k, ds.item_count)
+        features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
+        users = torch.as_tensor(users, dtype=torch.int64)
+        query_rows = None
+        if w is not None:
+            query_rows = self.embeddings.embed_bags(w, o)
+        else:
+            queries = torch.as_tensor(queries, dtype=torch.int64)
+        if candidates is not None and not isinstance(candidates, Tensor):
+            candidates = torch.as_tensor(candidates)
+        items, scores, _ = ops.search_topk(features, users, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
+                                           queries=queries, query_rows=query_rows, candidates=candidates, cosine=Gs.Prediction.use_cosine_similarity)
+        return items, scores
+
     def save_features_for_test(self) -> None:
         """Cache one propagation for the evaluation loop (call under ``torch.no_grad()``)."""
         self._saved_output_feature = self.propagate()

@@ -146,6 +146,10 @@ SIGNATURES = {
     'ihg_score_topk_deep_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     'ihg_score_topk_deep': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
                                            c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    # answering a search (csrc/eval.hip): ihg_score_topk_deep with (queries | query_rows, ld_q, q_dim), the candidate mask words and users < 0 = no user
+    'ihg_search_topk_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    'ihg_search_topk': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_float,
+                                       c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     'ihg_zero_floats': (ctypes.c_int, [c_void_p, c_int64, c_void_p]),
     'ihg_mark_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_batch_node_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -84,11 +84,33 @@ __device__ __forceinline__ void eval_split8(const float (&x)[8], v4u& hi, v4u& l
 // aux[item].x = inverse scale / max(||a||, 1e-8) - the hot loop of score_topk_kernel multiplies by it as it does by the plain inverse scale.
 constexpr float kEvalCosineEps = 1e-8f;
 
-template <bool COSINE = false>
+// What ihg_search_topk adds to the deep call (an empty struct for every other instantiation, as DeepArgs<false>): an external query row per pair, the candidate
+// mask and the ranks a complete pair has, formed on the device (search_target_kernel) where the mask decides it.
+template <bool SEARCH>
+struct SearchArgs {};
+template <>
+struct SearchArgs<true> {
+    const float* query_rows;                                                // [n_pairs, q_dim] (row stride ld_q), columns q_dim.. count as zero and are never read; null: `queries`
+    int64_t ld_q;
+    int q_dim;
+    const uint32_t* item_mask;                                              // bit i % 32 of word i / 32: item i is a candidate; null: every item
+    const int32_t* target;                                                  // min(k, candidates)
+};
+
+// SEARCH: an item outside the mask gets aux = {0, -inf} and nothing else - whatever its stale planes multiply to, its score is -inf or NaN, which ranks before no
+// list entry (not even the empty (-FLT_MAX, INT_MAX)) and after no boundary: the hot loop of score_topk_kernel is the same code with or without a mask.
+template <bool COSINE = false, bool SEARCH = false>
 __global__ __launch_bounds__(kBlockThreads) void score_prepare_kernel(const float* __restrict__ feat, int64_t ld, int dim, int ksteps, int64_t item_row0, int64_t n_items,
-                                                                      const float* __restrict__ bias, v4u* __restrict__ frag, float2* __restrict__ aux) {
+                                                                      const float* __restrict__ bias, v4u* __restrict__ frag, float2* __restrict__ aux,
+                                                                      [[maybe_unused]] const SearchArgs<SEARCH> search) {
     const int lane = threadIdx.x & 63;
     for (int64_t item = global_wave_id(); item < n_items; item += global_wave_count()) {
+        if constexpr (SEARCH) {
+            if (search.item_mask != nullptr && ((search.item_mask[item >> 5] >> (item & 31)) & 1u) == 0) {      // (wave-uniform)
+                if (lane == 0) aux[item] = make_float2(0.f, -__builtin_inff());
+                continue;
+            }
+        }
         const float* row = feat + (item_row0 + item) * ld;
         float m = 0.f;
         [[maybe_unused]] float ss = 0.f;
@@ -141,15 +163,20 @@ struct DeepArgs<true> {
     int target;                                                             // min(k, n_items): the ranks a complete pair has
 };
 
-template <int PB, bool COSINE = false, bool DEEP = false>
+// SEARCH (ihg_search_topk; always with DEEP): the query row of a pair may come from `search.query_rows` (zero past q_dim), users[c] < 0 names no user - the mixed
+// row is the query row itself (PredictionLayers.py:34-37, user_feature is None) - and the ranks of a complete pair are read from `search.target`.
+template <int PB, bool COSINE = false, bool DEEP = false, bool SEARCH = false>
 __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
     const float* __restrict__ feat, int64_t ld, int dim, int ksteps, const v4u* __restrict__ frag, const float2* __restrict__ aux, int64_t n_items,
     const int64_t* __restrict__ users, const int64_t* __restrict__ queries, int64_t query_row0, float lam, int64_t n_pairs,
-    float* __restrict__ part_val, int32_t* __restrict__ part_idx, [[maybe_unused]] const DeepArgs<DEEP> deep) {
+    float* __restrict__ part_val, int32_t* __restrict__ part_idx, [[maybe_unused]] const DeepArgs<DEEP> deep, [[maybe_unused]] const SearchArgs<SEARCH> search) {
+    static_assert(DEEP || !SEARCH, "the search arguments ride on the deep passes");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];    // mixed planes: [32 PB][hi: 2 dp bytes | lo: 2 dp bytes | 16 bytes of padding], then pinv[32 PB]
     if constexpr (DEEP) {                                                   // every wave asks the same question of the same (read-only) state: no barrier
         const int64_t pr = static_cast<int64_t>(blockIdx.x) * (32 * PB) + (threadIdx.x & 63);
-        const bool open = (threadIdx.x & 63) < 32 * PB && pr < n_pairs && deep.state[pr].count < deep.target;
+        int target;
+        if constexpr (SEARCH) target = *search.target; else target = deep.target;
+        const bool open = (threadIdx.x & 63) < 32 * PB && pr < n_pairs && deep.state[pr].count < target;
         if (__ballot(open) == 0) return;
     }
     const int dp = 16 * ksteps;
@@ -162,12 +189,36 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
     for (int r = wave; r < 32 * PB; r += kEvalThreads / kWave) {
         int64_t pr = pair0 + r;
         pr = pr < n_pairs ? pr : n_pairs - 1;
-        const float* qrow = feat + (queries[pr] + query_row0) * ld;
-        const float* urow = feat + users[pr] * ld;
+        const float* qrow;
+        const float* urow;
+        [[maybe_unused]] int qd = dim;                                      // the columns the query row has in memory
+        [[maybe_unused]] bool anon = false;                                 // (wave-uniform: one wave per row)
+        if constexpr (SEARCH) {
+            if (search.query_rows != nullptr) {
+                qrow = search.query_rows + pr * search.ld_q;
+                qd = search.q_dim;
+            } else {
+                qrow = feat + (queries[pr] + query_row0) * ld;
+            }
+            anon = users[pr] < 0;
+            urow = feat + (anon ? 0 : users[pr]) * ld;                      // (never read for an anonymous pair; row 0 is there whatever happens)
+        } else {
+            qrow = feat + (queries[pr] + query_row0) * ld;
+            urow = feat + users[pr] * ld;
+        }
+        const auto mixed = [&](int c) -> float {
+            if constexpr (SEARCH) {
+                const float q = c < qd ? qrow[c] : 0.f;
+                if (anon) return q;
+                return lam * q + (1.f - lam) * urow[c];
+            } else {
+                return lam * qrow[c] + (1.f - lam) * urow[c];
+            }
+        };
         float m = 0.f;
         [[maybe_unused]] float ss = 0.f;
         for (int c = lane; c < dim; c += kWave) {
-            const float v = lam * qrow[c] + (1.f - lam) * urow[c];
+            const float v = mixed(c);
             m = fmaxf(m, fabsf(v));
             if constexpr (COSINE) ss += v * v;
         }
@@ -186,7 +237,7 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int c = 8 * chunk + i;
-                x[i] = c < dim ? (lam * qrow[c] + (1.f - lam) * urow[c]) * sc : 0.f;
+                x[i] = c < dim ? mixed(c) * sc : 0.f;
             }
             v4u hi, lo;
             eval_split8(x, hi, lo);
@@ -359,10 +410,13 @@ __global__ __launch_bounds__(kBlockThreads) void deep_init_kernel(DeepState* __r
 
 // one wave per incomplete pair.  Lane l owns lists l, l + 64, ...: the head of each in registers (statically indexed: no scratch), the best head of the wave by
 // shuffles, and the one lane that owned it loads its list's next entry - one load per emitted rank, where k full scans of the candidates would be k x n_lists x 10.
+// SEARCH: `target` is read from search.target (min(k, candidates), formed on the device)
+template <bool SEARCH = false>
 __global__ __launch_bounds__(kBlockThreads) void merge_deep_kernel(const float* __restrict__ part_val, const int32_t* __restrict__ part_idx, int64_t n_pairs, int n_lists, int k,
                                                                     int target, DeepState* __restrict__ state, float* __restrict__ out_val, int32_t* __restrict__ out_idx,
-                                                                    int32_t* __restrict__ passes) {
+                                                                    int32_t* __restrict__ passes, [[maybe_unused]] const SearchArgs<SEARCH> search) {
     const int lane = threadIdx.x & 63;
+    if constexpr (SEARCH) target = *search.target;
     for (int64_t pair = global_wave_id(); pair < n_pairs; pair += global_wave_count()) {
         const DeepState st = state[pair];
         if (st.count >= target) continue;                                   // complete (wave-uniform): its lists are stale and its output is final
@@ -497,7 +551,7 @@ int score_topk_launch(const char* what, const float* features, int64_t ld, int32
     float2* aux = reinterpret_cast<float2*>(static_cast<unsigned char*>(workspace) + eval_frag_bytes(n_items, dim));
     float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
     int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
-    hipLaunchKernelGGL(score_prepare_kernel<COSINE>, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux);
+    hipLaunchKernelGGL(score_prepare_kernel<COSINE>, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux, SearchArgs<false>{});
     static bool attr_set[64] = {};                           // per device ordinal: the opt-in to > 64 KB of LDS belongs to the device's code object
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
@@ -510,10 +564,10 @@ int score_topk_launch(const char* what, const float* features, int64_t ld, int32
     const size_t lds = eval_lds_bytes(dim, pb);
     if (pb == 2)
         hipLaunchKernelGGL((score_topk_kernel<2, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{});
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{});
     else
         hipLaunchKernelGGL((score_topk_kernel<1, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{});
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{});
     hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs,
                        static_cast<int>(n_lists * kTopMax), k, top_scores, top_items);
     return check_launch(what);
@@ -521,10 +575,37 @@ int score_topk_launch(const char* what, const float* features, int64_t ld, int32
 
 inline int64_t eval_lists(int64_t n_pairs, int64_t n_items, int dim) { return static_cast<int64_t>(eval_slices(n_pairs, n_items, dim)) * kEvalWavesPerBlock * 2; }
 
-template <bool COSINE>
+// once per ihg_search_topk call, one workgroup: *target = min(k, the candidates among the first n_items bits of the mask) - the deep kernels read it where the plain
+// deep call passes min(k, n_items) by value - and passes[c] = 0 (with no candidate no pass finds a pair incomplete, and merge_deep_kernel writes nothing)
+__global__ __launch_bounds__(kBlockThreads) void search_target_kernel(const uint32_t* __restrict__ item_mask, int64_t n_items, int k, int32_t* __restrict__ target,
+                                                                      int32_t* __restrict__ passes, int64_t n_pairs) {
+    __shared__ int part[kWavesPerBlock];
+    const int tid = threadIdx.x;
+    if (passes != nullptr)
+        for (int64_t c = tid; c < n_pairs; c += kBlockThreads) passes[c] = 0;
+    int64_t count = n_items;
+    if (item_mask != nullptr) {
+        const int64_t n_words = (n_items + 31) / 32;
+        int mine = 0;                                                        // (at most k + 31 bits matter, but the words are few: 3,750 at 120,000 items)
+        for (int64_t w = tid; w < n_words; w += kBlockThreads) {
+            uint32_t bits = item_mask[w];
+            if (w == n_words - 1 && (n_items & 31) != 0) bits &= (1u << (n_items & 31)) - 1u;      // bits at or past n_items are ignored
+            mine += __popc(bits);
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
+        if ((tid & 63) == 0) part[tid >> 6] = mine;
+        __syncthreads();
+        count = 0;
+        for (int w = 0; w < kWavesPerBlock; ++w) count += part[w];
+    }
+    if (tid == 0) *target = static_cast<int32_t>(count < k ? count : k);
+}
+
+template <bool COSINE, bool SEARCH = false>
 int score_topk_deep_launch(const char* what, const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                            const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
-                           int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t* passes, ihg_stream_t stream) {
+                           int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t* passes, ihg_stream_t stream, SearchArgs<SEARCH> search = {}) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
     const int slices = eval_slices(n_pairs, n_items, dim);
@@ -534,16 +615,21 @@ int score_topk_deep_launch(const char* what, const float* features, int64_t ld, 
     float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
     int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
     DeepState* state = reinterpret_cast<DeepState*>(part_idx + n_pairs * n_lists * kTopMax);
-    const int target = static_cast<int>(std::min<int64_t>(k, n_items));
-    hipLaunchKernelGGL(score_prepare_kernel<COSINE>, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux);
+    const int target = static_cast<int>(std::min<int64_t>(k, n_items));           // (SEARCH: the most a mask leaves - the passes launched; the kernels read search.target)
+    if constexpr (SEARCH) {
+        int32_t* target_cell = reinterpret_cast<int32_t*>(state + n_pairs);
+        hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, search.item_mask, n_items, k, target_cell, passes, n_pairs);
+        search.target = target_cell;
+    }
+    hipLaunchKernelGGL((score_prepare_kernel<COSINE, SEARCH>), dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux, search);
     hipLaunchKernelGGL(deep_init_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n_pairs * k + kBlockThreads - 1) / kBlockThreads, 4096))), dim3(kBlockThreads), 0, s, state, n_pairs,
                        k, top_scores, top_items);
     static bool attr_set[64] = {};                           // per device ordinal, as in score_topk_launch
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
     if (device < 0 || device >= 64 || !attr_set[device]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE, true, SEARCH>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE, true, SEARCH>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
         if (device >= 0 && device < 64) attr_set[device] = true;
     }
     const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
@@ -552,13 +638,13 @@ int score_topk_deep_launch(const char* what, const float* features, int64_t ld, 
     const int n_passes = (target + kTopMax - 1) / kTopMax;
     for (int pass = 0; pass < n_passes; ++pass) {
         if (pb == 2)
-            hipLaunchKernelGGL((score_topk_kernel<2, COSINE, true>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
-                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep);
+            hipLaunchKernelGGL((score_topk_kernel<2, COSINE, true, SEARCH>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
+                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search);
         else
-            hipLaunchKernelGGL((score_topk_kernel<1, COSINE, true>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
-                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep);
-        hipLaunchKernelGGL(merge_deep_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs, static_cast<int>(n_lists), k, target, state, top_scores,
-                           top_items, passes);
+            hipLaunchKernelGGL((score_topk_kernel<1, COSINE, true, SEARCH>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
+                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search);
+        hipLaunchKernelGGL(merge_deep_kernel<SEARCH>, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs, static_cast<int>(n_lists), k, target, state, top_scores,
+                           top_items, passes, search);
     }
     return check_launch(what);
 }
@@ -617,6 +703,33 @@ int ihg_score_topk_deep(const float* features, int64_t ld, int32_t dim, int64_t 
                                                       workspace_bytes, passes, stream)
                        : score_topk_deep_launch<false>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace,
                                                        workspace_bytes, passes, stream);
+}
+
+int64_t ihg_search_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) {
+    const int64_t deep = ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k);
+    return deep == 0 ? 0 : deep + 16;                                       // + the cell of search_target_kernel
+}
+
+int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
+                    const int64_t* users, const int64_t* queries, const float* query_rows, int64_t ld_q, int32_t q_dim, const uint32_t* item_mask,
+                    float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes,
+                    int32_t cosine, int32_t* passes, ihg_stream_t stream) {
+    const char* what = "ihg_search_topk";
+    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kDeepMax);
+    if ((queries == nullptr) == (query_rows == nullptr)) return fail(IHG_ERR_INVALID, "%s: exactly one of queries and query_rows", what);
+    if (query_rows != nullptr && (q_dim < 1 || q_dim > dim || ld_q < q_dim)) return fail(IHG_ERR_INVALID, "%s: 1 <= q_dim <= dim and ld_q >= q_dim", what);
+    if (n_pairs == 0) return IHG_OK;
+    if (features == nullptr || item_bias == nullptr || users == nullptr || top_scores == nullptr || top_items == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
+    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
+    if (eval_lists(n_pairs, n_items, dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", what);
+    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k))
+        return fail(IHG_ERR_INVALID, "%s: workspace too small", what);
+    const SearchArgs<true> search{query_rows, ld_q, q_dim, item_mask, nullptr};
+    return cosine != 0 ? score_topk_deep_launch<true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
+                                                            workspace, workspace_bytes, passes, stream, search)
+                       : score_topk_deep_launch<false, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
+                                                             workspace, workspace_bytes, passes, stream, search);
 }
 
 }  // extern "C"

@@ -615,6 +615,7 @@ class PairLayout:
                                           cap, ctypes.byref(nnz)), 'ihg_build_pair_csr')
         k = int(nnz.value)
         self.device = device
+        self.self_loops = bool(self_loops)                    # (with them an isolated node's layer outputs are not zero: RawGnn.search asks)
         self.csr = Csr(rowptr, cols[:k], device, heavy_threshold)
         self.values_host = vals[:k].copy()
         self.values = torch.from_numpy(self.values_host).to(device)

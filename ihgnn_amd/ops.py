@@ -1858,6 +1858,67 @@ def score_topk_deep(features: Tensor, users: Tensor, queries: Tensor, query_row0
     return top_items, top_scores, passes
 
 
+def pack_item_mask(candidates: Tensor, n_items: int) -> Tensor:
+    """The candidate filter as ``ihg_search_topk`` reads it: ``ceil(n_items / 32)`` words (int32 holding the uint32 bits) on the device of ``candidates``, bit
+    ``i % 32`` of word ``i // 32`` set where item ``i`` is a candidate.  ``candidates`` is a bool ``[n_items]`` tensor or an int64 tensor of item ids (in any order,
+    repeats allowed; in ``[0, n_items)`` - the caller's to check where they live on the device).  Torch ops only: no host read."""
+    n_items = int(n_items)
+    if candidates.dtype == torch.bool:
+        if candidates.dim() != 1 or int(candidates.shape[0]) != n_items:
+            raise ValueError(f'a candidate mask is a bool tensor of [{n_items}], got {tuple(candidates.shape)}')
+        flags = candidates
+    elif candidates.dtype in (torch.int64, torch.int32):
+        ids = candidates.reshape(-1).to(torch.int64)
+        if not ids.is_cuda and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_items):
+            raise ValueError(f'candidate item id outside [0, {n_items})')
+        flags = torch.zeros(n_items, dtype=torch.bool, device=ids.device).index_fill_(0, ids, True)
+    else:
+        raise TypeError(f'candidates: a bool mask or integer item ids, got {candidates.dtype}')
+    n_words = (n_items + 31) // 32
+    bits = torch.zeros(n_words * 32, dtype=torch.int64, device=flags.device)
+    bits[:n_items] = flags.to(torch.int64)
+    words = (bits.view(n_words, 32) << torch.arange(32, dtype=torch.int64, device=flags.device)).sum(1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def search_topk(features: Tensor, users: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int, *, queries: Optional[Tensor] = None,
+                query_rows: Optional[Tensor] = None, candidates: Optional[Tensor] = None, cosine: bool = False):
+    """``score_topk_deep`` for a search (``ihg_search_topk``): ``(top_items [C, k] int32, top_scores [C, k], passes [C] int32)``.  Exactly one of ``queries`` (int64
+    ``[C]`` query indices) and ``query_rows`` (float32 ``[C, q]``, ``q <= D``: the rows of queries that are not in the graph - columns ``q ..`` count as zero);
+    ``users[c] < 0``: no user, the mixed row is the query row; ``candidates`` (``pack_item_mask``'s input): only these items are ranked, a pair is complete at
+    ``min(k, candidates)`` and the rest of its row is the ``-1`` tail."""
+    lib = _lib.load()
+    if not score_topk_supported(features):
+        raise _lib.IhgnnHipError(f'ihg_search_topk needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
+    if (queries is None) == (query_rows is None):
+        raise ValueError('search_topk: give exactly one of queries and query_rows')
+    n_pairs = int(users.shape[0])
+    n_items = int(features.shape[0]) - int(item_row0)
+    dim = int(features.shape[1])
+    users = users.to(device=features.device, dtype=torch.int64).contiguous()
+    ld_q = q_dim = 0
+    if queries is not None:
+        queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
+        source = int(queries.shape[0])
+    else:
+        query_rows = _rows(query_rows, 'query_rows')
+        source, q_dim, ld_q = int(query_rows.shape[0]), int(query_rows.shape[1]), _ld(query_rows)
+    if source != n_pairs:
+        raise ValueError(f'search_topk: {n_pairs} users but {source} queries')
+    mask = None if candidates is None else pack_item_mask(candidates.to(features.device), n_items)
+    bias = item_bias.detach().to(torch.float32).contiguous()
+    width = max(int(k), 0)
+    top_scores = torch.empty(n_pairs, width, dtype=torch.float32, device=features.device)
+    top_items = torch.empty(n_pairs, width, dtype=torch.int32, device=features.device)
+    passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
+    ws = _workspace(int(lib.ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
+    with profiler.kernel('search_topk_cosine' if cosine else 'search_topk', n_pairs, dim):
+        _lib.check(lib.ihg_search_topk(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), _ptr(query_rows),
+                                       ld_q, q_dim, _ptr(mask), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)),
+                                       _ptr(passes), _stream()), 'ihg_search_topk')
+    return top_items, top_scores, passes
+
+
 def batch_node_rows(users: Tensor, queries: Tensor, items: Tensor, query_row0: int, item_row0: int) -> Tensor:
     """``torch.cat([users, queries + query_row0, items + item_row0])`` (``RawGnn.py:128-131``): the global node rows of a batch, int64 ``[3 B]``, one launch."""
     lib = _lib.load()

@@ -648,6 +648,31 @@ int ihg_score_topk_deep(const float* features, int64_t ld, int32_t dim, int64_t 
                         ihg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE: answering a search.  ihg_search_topk is ihg_score_topk_deep - its outputs, tie order, -1 tail, 1 <= k <= 128, width limit, `cosine` and `passes`; no host
+ * read, no allocation, no atomics, a stream capture holds it - with three additions, each what the model itself computes:
+ *   query source   exactly one of `queries` ([n_pairs] node indices, as in ihg_score_topk) and `query_rows` is non-null.  query_rows is a [n_pairs, q_dim] float32
+ *                  matrix (row stride ld_q >= q_dim, 1 <= q_dim <= dim): the query row of pair c is query_rows[c] in columns 0 .. q_dim and ZERO in columns
+ *                  q_dim .. dim, which are never read from memory - a query that is not in the training graph is an isolated node: its layer-0 row is its words'
+ *                  bag mean (or the query transform of it) and every layer output above is exactly zero (Helpers/Graph.py:120)
+ *   no user        users[c] < 0: the mixed row of pair c is its query row itself, not lambda times it (the head's `user_feature is None` branch,
+ *                  Models/PredictionLayers.py:34-37); under the cosine head its norm is the query row's
+ *   candidates     item_mask: NULL (every item) or ceil(n_items / 32) uint32 words on the device, shared by all pairs; bit i % 32 of word i / 32 says that item i is
+ *                  a candidate, bits at or past n_items are ignored.  An item that is no candidate never appears in the output; a pair is complete at
+ *                  min(k, candidates), a count formed on the device inside the call, so complete pairs still let their workgroups return at once and
+ *                  passes[c] <= ceil(min(k, candidates) / 10) (0 with no candidate: every output row is then the -1 tail).  The mask is applied where the item
+ *                  rows are prepared, once per call: the scoring loop is that of ihg_score_topk_deep, and an all-ones mask returns the bits of a NULL mask.
+ * With `queries`, no negative user and no mask the call returns the bits of ihg_score_topk_deep; with query_rows, those of ihg_score_topk_deep on a feature matrix
+ * that has the rows appended (zero above q_dim) as further query rows.
+ * IHG_ERR_INVALID before anything is launched: both or neither of queries / query_rows, q_dim outside 1 .. dim, ld_q < q_dim, k outside 1 .. 128, a workspace
+ * smaller than ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k) (that of ihg_score_topk_deep + 16 bytes).  n_pairs == 0 returns IHG_OK.
+ */
+int64_t ihg_search_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k);
+int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
+                    const float* item_bias, const int64_t* users, const int64_t* queries, const float* query_rows, int64_t ld_q, int32_t q_dim,
+                    const uint32_t* item_mask, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores, int32_t* top_items,
+                    void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes, ihg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE: the attention of the GAT baseline over the pairwise graph (csrc/gat.hip).  Replaces GATLayer.forward after its transform
  * (Models/GnnLayers.py:98-115: the [nnz, 2, d] row gather, feature_aggregate, dgl.ops.edge_softmax and dgl.ops.u_mul_e_sum) and autograd's backward of it.
  * Graph: the symmetric CSR of the pairwise adjacency (ihg_build_pair_csr) - entry p of row v with column u = ids[p] is the edge u -> v, so row v lists
