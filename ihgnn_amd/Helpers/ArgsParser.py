@@ -48,7 +48,7 @@ _FLAGS = (
     # not in the reference's command line: its driver hard-codes phase2_attention=False (Main.py:57)
     ('phase2', ('--phase2',), 'flag', False, 'IHGNN layers with phase-2 attention: attention weights over a node\'s hyperedges instead of their mean (Gs.Gnn.gat_head / gat_activation)'),
     # not in the reference's command line: there one edits Gs.Query in Helpers/GlobalSettings.py:68-76
-    ('query_transform', ('--query_transform',), str, Gsv.mean, 'query transform: mean | activation (nn.Linear + --query_activation on the bag mean; Gs.Query.transform)'),
+    ('query_transform', ('--query_transform',), str, Gsv.mean, 'query transform: mean | activation (nn.Linear + --query_activation on the bag mean) | gru (nn.GRU over the words in order, its last state; Gs.Query.transform)'),
     ('query_activation', ('--query_activation',), str, 'relu', 'activation of --query_transform activation: relu | tanh (Gs.Query.transform_activation)'),
     # not in the reference's command line: there one edits Gs.Prediction in Helpers/GlobalSettings.py
     ('cosine', ('--cosine',), 'flag', False, 'score with the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity) instead of the dot product'),
@@ -61,7 +61,7 @@ _FLAGS = (
 )
 
 
-_CHOICES = {'query_transform': (Gsv.mean, Gsv.activation), 'query_activation': ('relu', 'tanh')}
+_CHOICES = {'query_transform': (Gsv.mean, Gsv.activation, Gsv.gru), 'query_activation': ('relu', 'tanh')}
 
 
 class ConsoleArgs:

@@ -7,6 +7,7 @@ import torch.nn as nn
 
 class Gsv:
     mean, activation, rnn = 'mean', 'activation', 'rnn'
+    gru = 'gru'      # the recurrent query model that runs here (nn.GRU over the words in order); rnn stays the reference's refused placeholder
     concat, product = 'concatenation', 'product'
     graph_uqi, graph_only_uq, graph_only_ui, graph_only_qi = 'uqi', 'uq', 'ui', 'qi'
 
@@ -35,7 +36,7 @@ class Gs:
         gat_activation = (nn.LeakyReLU, 'leaky_relu')      # or (nn.ReLU, 'relu'), (nn.Tanh, 'tanh')
 
     class Query:
-        transform = Gsv.mean             # or Gsv.activation: nn.Linear(d, d) + transform_activation on the bag mean (EmbeddingLayers.py:37-44); Gsv.rnn raises, as in the reference
+        transform = Gsv.mean             # or Gsv.activation: nn.Linear(d, d) + transform_activation on the bag mean (EmbeddingLayers.py:37-44); Gsv.gru: nn.GRU(d, d) over the words in file order, its last state; Gsv.rnn raises, as in the reference
         transform_activation = nn.ReLU   # or nn.Tanh (the reference's other assignment, GlobalSettings.py:74-76)
 
     class Prediction:

@@ -76,6 +76,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise NotImplementedError('--model Srrl draws its batches on the host (SrrlDatasetKG): --device_sampling does not apply')
     if getattr(args, 'phase2', False):
         raise ValueError('--phase2 is the IHGNN layer\'s phase-2 attention; --model Srrl has no layers')
+    if getattr(args, 'query_transform', Gsv.mean) == Gsv.gru:
+        raise NotImplementedError('--model Srrl embeds its queries by the bag mean or the activation transform: --query_transform gru has not been built for it')
     widest = ops.cat_linear_max_width()
     if 2 * Gs.embedding_size > widest:
         # every block of the model concatenates two rows of the embedding width: said here, not by the first forward's launch

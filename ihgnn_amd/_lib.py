@@ -184,6 +184,13 @@ SIGNATURES = {
     'ihg_rows_dot_bwd': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
     'ihg_kg_loss': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'ihg_rows_topk': (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    # the GRU query encoder (csrc/recurrent.hip)
+    'ihg_gru_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32]),
+    'ihg_gru_saved_bytes': (c_int64, [c_int64, c_int32]),
+    'ihg_gru_fwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                   c_void_p, c_int64, c_int32, c_void_p]),
+    'ihg_gru_bwd': (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 ACT_NONE, ACT_LEAKY_RELU = 0, 3
 

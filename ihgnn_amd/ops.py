@@ -10,6 +10,7 @@ edge_gather_sum  (K5)  ihg_edge_gather_sum         ihg_node_segment_sum   (its t
 node_segment_sum (K7)  ihg_node_segment_sum         ihg_edge_gather_sum    (its transpose)
 bag_mean         (K2)  ihg_bag_mean_fwd            ihg_bag_mean_bwd
  + query transform     ihg_rows_linear_act_fwd     ihg_rows_linear_act_bwd  (in front of ihg_bag_mean_bwd)
+ or the GRU encoder    ihg_gru_fwd                 ihg_gru_bwd              (instead of the bag mean: QueryTransform('gru', ...))
 interact     (K5+K6)   ihg_interact_fwd            ihg_interact_bwd + 4x ihg_node_segment_sum
 gat_attention          ihg_gat_attention_fwd + K7  ihg_gat_scores_bwd, K7, ihg_gat_finish_bwd
 hyper_attention        ihg_phase2_attention_fwd    ihg_phase2_scores_bwd, ihg_phase2_edges_bwd, (K7,) ihg_phase2_finish_bwd
@@ -691,6 +692,14 @@ class BagLayout:
             self.bags.ids = self.words_of.ids = torch.zeros(1, dtype=torch.int32, device=device)
         lens = np.diff(ptr.astype(np.int64)).astype(np.float32)
         self.bag_len = torch.from_numpy(lens).to(device)
+        # for the recurrent encoder (ihg_gru_fwd / ihg_gru_bwd): the bags by decreasing length, ties in bag order (None: they already are) - a workgroup takes 32
+        # neighbours of that order and runs to the longest of them -, and every word's positions in `words`, ascending: word w's are
+        # word_positions[words_of.ptr[w] : words_of.ptr[w + 1]] (the per-occurrence gradients are summed over them in that order)
+        self.n_words = int(words.shape[0])
+        by_length = np.argsort(-lens, kind='stable').astype(np.int32)
+        self.length_order = None if np.array_equal(by_length, np.arange(self.n_bags, dtype=np.int32)) else torch.from_numpy(by_length).to(device)
+        positions = np.argsort(words, kind='stable').astype(np.int32)
+        self.word_positions = torch.from_numpy(positions if positions.size else np.zeros(1, np.int32)).to(device)
         inv = np.where(lens > 0, 1.0 / np.maximum(lens, 1), 0).astype(np.float32)
         self.inv_len = torch.from_numpy(inv).to(device)
 
@@ -713,10 +722,119 @@ def _query_transform_operands(wq: Optional[Tensor], bq: Optional[Tensor], dim: i
     return _rows(wq, 'query transform weight'), bq.contiguous()
 
 
-def _query_rows_forward(word_table: Tensor, bag: BagLayout, wq: Optional[Tensor], bq: Optional[Tensor], act: int, out: Tensor) -> Optional[Tensor]:
-    """The query rows of X0 into ``out`` (``[Q, d]``, any row stride - a row block of X0 or of a column slice of the feature matrix): the bag means ``m`` of the
-    queries' words (``ihg_bag_mean_fwd``), or - with a transform ``wq``, ``bq``, ``act`` (``Gs.Query.transform == 'activation'``) - ``act(m wq^T + bq)``
-    (``ihg_rows_linear_act_fwd``; an empty bag gives ``act(bq)``).  Returns ``m`` then (the transform's backward reads it; outside autograd the caller drops it), else ``None``."""
+class QueryTransform:
+    """What turns a query's words into its row of X0 (``Gs.Query.transform``), for every producer of those rows: its ``kind`` and its parameter ``tensors`` -
+    ``'mean'``: the bag mean, no tensors; ``'activation'``: ``act(mean wq^T + bq)``, tensors ``(wq [d, d], bq [d])`` and ``act`` the library's activation code;
+    ``'gru'``: the last state of ``nn.GRU(d, d)`` over the words in order, tensors ``(weight_ih_l0 [3d, d], weight_hh_l0 [3d, d], bias_ih_l0 [3d], bias_hh_l0 [3d])``.
+    The tensors travel through the producers' autograd functions as trailing arguments, so each returns one gradient per tensor."""
+    MEAN, ACTIVATION, GRU = 'mean', 'activation', 'gru'
+
+    def __init__(self, kind: str = 'mean', tensors=(), activation: Optional[str] = None, act: Optional[int] = None):
+        if kind not in (self.MEAN, self.ACTIVATION, self.GRU):
+            raise ValueError(f'query transform: unknown kind {kind!r} (mean, activation or gru)')
+        self.kind, self.tensors = kind, tuple(tensors)
+        if len(self.tensors) != {self.MEAN: 0, self.ACTIVATION: 2, self.GRU: 4}[kind]:
+            raise ValueError(f'query transform {kind!r}: {len(self.tensors)} tensors given')
+        self.act = 0 if kind != self.ACTIVATION else (act if act is not None else _query_activation(activation))
+
+    @classmethod
+    def of(cls, wq: Optional[Tensor], bq: Optional[Tensor], activation=None) -> 'QueryTransform':
+        """The ``(wq, bq, activation)`` spelling of the mean / activation transforms (``activation``: a name of ``QUERY_ACTIVATIONS`` or the library's code)."""
+        if isinstance(wq, cls):
+            return wq
+        if wq is None:
+            return cls()
+        return cls(cls.ACTIVATION, (wq, bq), **({'act': int(activation)} if isinstance(activation, int) else {'activation': activation}))
+
+    def operands(self, tensors, dim: int):
+        """``tensors`` (this transform's, as an autograd function received them) checked against the width and laid out as the library takes them."""
+        if self.kind == self.MEAN:
+            return ()
+        if self.kind == self.ACTIVATION:
+            return _query_transform_operands(tensors[0], tensors[1], dim)
+        w_ih, w_hh, b_ih, b_hh = tensors
+        if any(tuple(w.shape) != (3 * dim, dim) for w in (w_ih, w_hh)) or any(tuple(b.shape) != (3 * dim,) for b in (b_ih, b_hh)):
+            raise ValueError(f'the GRU query transform takes two [{3 * dim}, {dim}] weights and two [{3 * dim}] biases, got {[tuple(t.shape) for t in tensors]}')
+        return tuple(t.contiguous() for t in tensors)
+
+
+def _tape(*tensors) -> bool:
+    """True when autograd records the op that is about to run on ``tensors``: its backward will ask for what the forward keeps."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _gru_width(dim: int) -> int:
+    """The width the GRU kernels run a ``dim``-wide encoder at: the next tiled one.  Zero columns / rows appended to every operand change nothing: a padded unit has
+    ``r = z = 1/2``, ``n = tanh(0) = 0`` and stays ``h = 0`` from ``h_0 = 0``, and contributes exact zeros to every other unit's sums."""
+    if dim < 1 or dim > FAST_WIDTHS[-1]:
+        raise ValueError(f'the GRU query transform runs at embedding widths 1 .. {FAST_WIDTHS[-1]}, got {dim}')
+    return next(wd for wd in FAST_WIDTHS if wd >= dim)
+
+
+def _pad_gates(w: Tensor, dim: int, width: int) -> Tensor:
+    """``[3 d, d]`` (or ``[3 d]``) of the gates r, z, n as ``[3 width, width]`` (``[3 width]``): every gate's block in the top-left of its own zero block."""
+    if dim == width:
+        return w
+    if w.dim() == 1:
+        return torch.nn.functional.pad(w.reshape(3, dim), (0, width - dim)).reshape(-1)
+    return torch.nn.functional.pad(w.reshape(3, dim, dim), (0, width - dim, 0, width - dim)).reshape(3 * width, width)
+
+
+def _gru_rows_forward(word_table: Tensor, bag: BagLayout, params, out: Tensor, keep: bool):
+    """``ihg_gru_fwd`` into ``out``; returns what ``_gru_rows_backward`` reads - the saved gates and states and the operands at the kernels' width - or ``()``."""
+    lib = _lib.load()
+    q, dim = bag.n_bags, int(word_table.shape[1])
+    width = _gru_width(dim)
+    dev = word_table.device
+    table = pad_columns(word_table, width).contiguous()
+    w_ih, w_hh, b_ih, b_hh = (_pad_gates(t, dim, width) for t in params)
+    dest = out if width == dim else torch.empty(q, width, dtype=torch.float32, device=dev)
+    saved = torch.empty(int(lib.ihg_gru_saved_bytes(bag.n_words, width)) // 4, dtype=torch.float32, device=dev) if keep and q > 0 and bag.n_words > 0 else None
+    if q > 0:
+        with profiler.kernel('query_gru_fwd', q, width):
+            _lib.check(lib.ihg_gru_fwd(_ptr(table), _ld(table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.length_order), q, bag.n_words, _ptr(w_ih), _ptr(w_hh),
+                                       _ptr(b_ih), _ptr(b_hh), _ptr(dest), _ld(dest), _ptr(saved), None, 0, width, _stream()), 'ihg_gru_fwd')
+    if dest is not out:
+        out.copy_(dest[:, :dim])
+    if not keep:
+        return ()
+    return (saved if saved is not None else torch.empty(0, dtype=torch.float32, device=dev), table, w_ih, w_hh)
+
+
+def _gru_rows_backward(d_query: Tensor, bag: BagLayout, state):
+    """``(d word table, (d w_ih, d w_hh, d b_ih, d b_hh))`` from the complete cotangent of the query rows (``ihg_gru_bwd``); rows and columns of the padding are dropped."""
+    lib = _lib.load()
+    saved, table, w_ih, w_hh = state
+    q, dim, width = bag.n_bags, int(d_query.shape[1]), int(table.shape[1])
+    dev = d_query.device
+    if width != dim:
+        d_query = pad_columns(d_query, width)
+    d_table = torch.empty(bag.table_rows, width, dtype=torch.float32, device=dev)
+    dw_ih, dw_hh = torch.empty(3 * width, width, dtype=torch.float32, device=dev), torch.empty(3 * width, width, dtype=torch.float32, device=dev)
+    db_ih, db_hh = torch.empty(3 * width, dtype=torch.float32, device=dev), torch.empty(3 * width, dtype=torch.float32, device=dev)
+    ws = _workspace(int(lib.ihg_gru_workspace_bytes(q, bag.n_words, width)), dev)
+    with profiler.kernel('query_gru_bwd', q, width):
+        _lib.check(lib.ihg_gru_bwd(_ptr(d_query), _ld(d_query), _ptr(table), _ld(table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.length_order), q, bag.n_words,
+                                   _ptr(bag.words_of.ptr), _ptr(bag.word_positions), bag.table_rows, _ptr(w_ih), _ptr(w_hh), _ptr(saved) if saved.numel() else None,
+                                   _ptr(d_table), _ptr(dw_ih), _ptr(dw_hh), _ptr(db_ih), _ptr(db_hh), _ptr(ws), ws.numel() * 4, width, _stream()), 'ihg_gru_bwd')
+    if width != dim:
+        d_table = d_table[:, :dim].contiguous()
+        dw_ih, dw_hh = (w.reshape(3, width, width)[:, :dim, :dim].reshape(3 * dim, dim) for w in (dw_ih, dw_hh))
+        db_ih, db_hh = (b.reshape(3, width)[:, :dim].reshape(-1) for b in (db_ih, db_hh))
+    return d_table, (dw_ih, dw_hh, db_ih, db_hh)
+
+
+def _query_rows_forward(word_table: Tensor, bag: BagLayout, transform, bq: Optional[Tensor] = None, act: int = 0, out: Optional[Tensor] = None, keep: bool = True):
+    """The query rows of X0 into ``out`` (``[Q, d]``, any row stride - a row block of X0 or of a column slice of the feature matrix) under ``transform``, a
+    ``QueryTransform`` with its tensors as the library takes them (or the ``wq, bq, act`` spelling of the first two kinds): the bag means ``m`` of the queries' words
+    (``ihg_bag_mean_fwd``); with ``'activation'`` ``act(m wq^T + bq)`` (``ihg_rows_linear_act_fwd``; an empty bag gives ``act(bq)``); with ``'gru'`` the encoder's last state
+    (``ihg_gru_fwd``; an empty bag gives a zero row).  Returns the tensors the backward of that kind reads beside ``out`` - ``()``, ``(m,)``, or the GRU's saved state and
+    operands, which ``keep=False`` (outside autograd: search, the evaluation cache) does not store."""
+    qt = QueryTransform.of(transform, bq, int(act))
+    if qt.kind == QueryTransform.GRU:
+        return _gru_rows_forward(word_table, bag, qt.tensors, out, keep)
+    wq, bq = qt.tensors if qt.kind == QueryTransform.ACTIVATION else (None, None)
+    act = qt.act
     lib = _lib.load()
     q, dim = bag.n_bags, int(word_table.shape[1])
     means = out if wq is None else torch.empty(q, dim, dtype=torch.float32, device=word_table.device)
@@ -725,62 +843,74 @@ def _query_rows_forward(word_table: Tensor, bag: BagLayout, wq: Optional[Tensor]
             _lib.check(lib.ihg_bag_mean_fwd(_ptr(word_table), _ld(word_table), _ptr(bag.bags.ptr), _ptr(bag.bags.ids), _ptr(bag.bag_len),
                                             _ptr(means), _ld(means), q, dim, _stream()), 'ihg_bag_mean_fwd')
     if wq is None:
-        return None
+        return ()
     if q > 0:
         ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), word_table.device)
         with profiler.kernel('query_transform_fwd', q, dim):
             _lib.check(lib.ihg_rows_linear_act_fwd(_ptr(means), dim, _ptr(wq), int(wq.stride(0)), _ptr(bq), act, _ptr(out), _ld(out), q, _ptr(ws), ws.numel() * 4, dim,
                                                    _stream()), 'ihg_rows_linear_act_fwd')
-    return means
+    return (means,)
 
 
-def _query_rows_backward(d_query: Tensor, bag: BagLayout, means: Optional[Tensor], y: Optional[Tensor], wq: Optional[Tensor], act: int):
-    """``(d word table, d wq, d bq)`` from the COMPLETE cotangent ``d_query`` of the query rows (``[Q, d]``, any row stride): the transform's backward
-    (``ihg_rows_linear_act_bwd`` on ``d_query`` and the rows ``y`` themselves: ``dz = d_query * act'(y)`` is never stored), then the bag mean's."""
+def _query_rows_backward(d_query: Tensor, bag: BagLayout, qt: QueryTransform, state, y: Optional[Tensor]):
+    """``(d word table, gradients of the transform's tensors)`` from the COMPLETE cotangent ``d_query`` of the query rows (``[Q, d]``, any row stride) and what the
+    forward returned (``state``) - ``'activation'``: the transform's backward (``ihg_rows_linear_act_bwd`` on ``d_query`` and the rows ``y`` themselves:
+    ``dz = d_query * act'(y)`` is never stored; ``state[1]`` = ``wq``), then the bag mean's; ``'gru'``: ``ihg_gru_bwd``."""
+    if qt.kind == QueryTransform.GRU:
+        return _gru_rows_backward(d_query, bag, state)
     lib = _lib.load()
     q, dim = bag.n_bags, int(d_query.shape[1])
-    dwq = dbq = None
-    if wq is not None:
+    grads = ()
+    if qt.kind == QueryTransform.ACTIVATION:
+        means, wq = state
         dm = torch.empty(q, dim, dtype=torch.float32, device=d_query.device)
         dwq, dbq = torch.empty_like(wq), torch.empty(dim, dtype=torch.float32, device=d_query.device)
         ws = _workspace(int(lib.ihg_node_linear_workspace_bytes(dim)), d_query.device)
         with profiler.kernel('query_transform_bwd', q, dim):
-            _lib.check(lib.ihg_rows_linear_act_bwd(_ptr(d_query), _ld(d_query), _ptr(y), _ld(y), _ptr(means), dim, _ptr(wq), int(wq.stride(0)), act,
+            _lib.check(lib.ihg_rows_linear_act_bwd(_ptr(d_query), _ld(d_query), _ptr(y), _ld(y), _ptr(means), dim, _ptr(wq), int(wq.stride(0)), qt.act,
                                                    _ptr(dwq), int(dwq.stride(0)), _ptr(dbq), _ptr(dm), dim, q, _ptr(ws), ws.numel() * 4, dim, _stream()),
                        'ihg_rows_linear_act_bwd')
-        d_query = dm
+        d_query, grads = dm, (dwq, dbq)
     d_word = torch.empty(bag.table_rows, dim, dtype=torch.float32, device=d_query.device)
     with profiler.kernel('bag_mean_bwd', bag.table_rows, dim):
         _lib.check(lib.ihg_bag_mean_bwd(_ptr(d_query), _ld(d_query), _ptr(bag.words_of.ptr), _ptr(bag.words_of.ids), _ptr(bag.inv_len), _ptr(d_word), dim,
                                         bag.table_rows, dim, _stream()), 'ihg_bag_mean_bwd')
-    return d_word, dwq, dbq
+    return d_word, grads
+
+
+def _transform_state(qt: QueryTransform, state, params):
+    """What a producer saves for ``_query_rows_backward`` beside its own tensors: ``'activation'``: the bag means and ``wq``; ``'gru'``: what its forward returned."""
+    return (state[0], params[0]) if qt.kind == QueryTransform.ACTIVATION else tuple(state)
 
 
 class _BagMean(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, table: Tensor, bag: BagLayout, wq: Optional[Tensor], bq: Optional[Tensor], act: int) -> Tensor:
+    def forward(ctx, table: Tensor, bag: BagLayout, qt: QueryTransform, keep: bool, *params: Tensor) -> Tensor:
         table = _rows(table, 'table')
         dim = int(table.shape[1])
-        wq, bq = _query_transform_operands(wq, bq, dim)
+        params = qt.operands(params, dim)
         out = torch.empty(bag.n_bags, dim, dtype=torch.float32, device=table.device)
-        means = _query_rows_forward(table, bag, wq, bq, act, out)
-        ctx.bag, ctx.act, ctx.transform = bag, act, wq is not None
-        if wq is not None:
-            ctx.save_for_backward(means, out, wq)
+        state = _query_rows_forward(table, bag, QueryTransform(qt.kind, params, act=qt.act), out=out, keep=keep)
+        ctx.bag, ctx.qt = bag, qt
+        if qt.kind != QueryTransform.MEAN:
+            ctx.save_for_backward(out, *_transform_state(qt, state, params))
         return out
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
         grad_out = _rows(grad_out, 'grad_out')
-        means, y, wq = ctx.saved_tensors if ctx.transform else (None, None, None)
-        dtable, dwq, dbq = _query_rows_backward(grad_out, ctx.bag, means, y, wq, ctx.act)
-        return dtable, None, dwq, dbq, None
+        y, state = (ctx.saved_tensors[0], ctx.saved_tensors[1:]) if ctx.qt.kind != QueryTransform.MEAN else (None, ())
+        dtable, grads = _query_rows_backward(grad_out, ctx.bag, ctx.qt, state, y)
+        return (dtable, None, None, None) + tuple(grads)
 
 
-def bag_mean(table: Tensor, bag: BagLayout, wq: Optional[Tensor] = None, bq: Optional[Tensor] = None, activation: Optional[str] = None) -> Tensor:
+def bag_mean(table: Tensor, bag: BagLayout, wq: Optional[Tensor] = None, bq: Optional[Tensor] = None, activation: Optional[str] = None,
+             transform: Optional[QueryTransform] = None) -> Tensor:
     """``nn.EmbeddingBag(mode='mean')`` over every query: ``[V+1,d] -> [Q,d]``; with ``wq [d,d]``, ``bq [d]`` and ``activation`` ('relu' | 'tanh') the reference's
-    ``query_transform`` on top (``Models/EmbeddingLayers.py:40-44, 83-84``): ``act(mean wq^T + bq)``."""
-    return _BagMean.apply(table, bag, wq, bq, _query_activation(activation) if wq is not None else 0)
+    ``query_transform`` on top (``Models/EmbeddingLayers.py:40-44, 83-84``): ``act(mean wq^T + bq)``.  ``transform``: any ``QueryTransform`` instead of that triple - with
+    ``'gru'`` the rows are the GRU encoder's last states over the words in order, not a function of the mean."""
+    qt = transform if transform is not None else QueryTransform.of(wq, bq, activation)
+    return _BagMean.apply(table, bag, qt, _tape(table, *qt.tensors), *qt.tensors)
 
 
 class _EmbedAllNodes(torch.autograd.Function):
@@ -788,21 +918,20 @@ class _EmbedAllNodes(torch.autograd.Function):
     kernel writes its rows in place), with a backward that hands each table its gradient without a full-size zero fill."""
 
     @staticmethod
-    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor], wq: Optional[Tensor], bq: Optional[Tensor],
-                act: int) -> Tensor:
+    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor], qt: QueryTransform, keep: bool, *params: Tensor) -> Tensor:
         word_table = _rows(word_table, 'word table')
         u, q, i = int(user_table.shape[0]) - 1, bag.n_bags, int(item_table.shape[0]) - 1
         dim = int(word_table.shape[1])
-        wq, bq = _query_transform_operands(wq, bq, dim)
-        x = _check_out(out, user_table, item_table, word_table, wq, bq)
+        params = qt.operands(params, dim)
+        x = _check_out(out, user_table, item_table, word_table, *params)
         if x is None:
             x = torch.empty(u + q + i, dim, dtype=torch.float32, device=word_table.device)
         x[:u].copy_(user_table[1:])
         x[u + q:].copy_(item_table[1:])
-        means = _query_rows_forward(word_table, bag, wq, bq, act, x[u:u + q])
-        ctx.bag, ctx.counts, ctx.act, ctx.transform = bag, (u, q, i), act, wq is not None
-        if wq is not None and out is None:
-            ctx.save_for_backward(means, x, wq)
+        state = _query_rows_forward(word_table, bag, QueryTransform(qt.kind, params, act=qt.act), out=x[u:u + q], keep=keep and out is None)
+        ctx.bag, ctx.counts, ctx.qt = bag, (u, q, i), qt
+        if qt.kind != QueryTransform.MEAN and out is None:
+            ctx.save_for_backward(x, *_transform_state(qt, state, params))
         return x
 
     @staticmethod
@@ -816,16 +945,17 @@ class _EmbedAllNodes(torch.autograd.Function):
         d_item = torch.empty(i + 1, dim, dtype=torch.float32, device=grad.device)
         d_item[0].zero_()
         d_item[1:].copy_(grad[u + q:])
-        means, x, wq = ctx.saved_tensors if ctx.transform else (None, None, None)
-        d_word, dwq, dbq = _query_rows_backward(grad[u:u + q], bag, means, x[u:u + q] if x is not None else None, wq, ctx.act)
-        return d_user, d_item, d_word, None, None, dwq, dbq, None
+        x, state = (ctx.saved_tensors[0], ctx.saved_tensors[1:]) if ctx.qt.kind != QueryTransform.MEAN else (None, ())
+        d_word, grads = _query_rows_backward(grad[u:u + q], bag, ctx.qt, state, x[u:u + q] if x is not None else None)
+        return (d_user, d_item, d_word, None, None, None, None) + tuple(grads)
 
 
 def embed_all_nodes(user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: BagLayout, out: Optional[Tensor] = None, wq: Optional[Tensor] = None,
-                    bq: Optional[Tensor] = None, activation: Optional[str] = None) -> Tensor:
+                    bq: Optional[Tensor] = None, activation: Optional[str] = None, transform: Optional[QueryTransform] = None) -> Tensor:
     """The full-graph input features ``EmbeddingLayer(None, None, None)`` concatenated (``RawGnn.py:112-113``): ``[U+Q+I, d]``
-    from the ``[U+1, d]`` / ``[I+1, d]`` tables (row 0 = padding) and the ``[V+1, d]`` word table; ``wq``, ``bq``, ``activation``: the query transform, as in ``bag_mean``."""
-    return _EmbedAllNodes.apply(user_table, item_table, word_table, bag, out, wq, bq, _query_activation(activation) if wq is not None else 0)
+    from the ``[U+1, d]`` / ``[I+1, d]`` tables (row 0 = padding) and the ``[V+1, d]`` word table; ``wq``, ``bq``, ``activation`` / ``transform``: the query transform, as in ``bag_mean``."""
+    qt = transform if transform is not None else QueryTransform.of(wq, bq, activation)
+    return _EmbedAllNodes.apply(user_table, item_table, word_table, bag, out, qt, _tape(user_table, item_table, word_table, *qt.tensors), *qt.tensors)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -933,10 +1063,10 @@ class NodeTables:
     Stands in for the ``[N, d]`` tensor between ``EmbeddingLayer.node_tables()`` and the first layer; ``node_linear`` resolves it (bag means, autograd token)."""
 
     def __init__(self, user_table: Tensor, item_table: Tensor, word_table: Tensor, bag: 'BagLayout', holder: 'TailGradients', wq: Optional[Tensor] = None,
-                 bq: Optional[Tensor] = None, activation: Optional[str] = None):
+                 bq: Optional[Tensor] = None, activation: Optional[str] = None, transform: Optional[QueryTransform] = None):
         self.user_table, self.item_table, self.word_table, self.bag, self.holder = user_table, item_table, word_table, bag, holder
-        self.wq, self.bq = _query_transform_operands(wq, bq, int(user_table.shape[1]))          # the query transform (Gs.Query.transform == 'activation'), or None
-        self.act = _query_activation(activation) if wq is not None else 0
+        qt = transform if transform is not None else QueryTransform.of(wq, bq, activation)
+        self.transform = QueryTransform(qt.kind, qt.operands(qt.tensors, int(user_table.shape[1])), act=qt.act)      # the query transform (Gs.Query.transform), its tensors as the library takes them
         self.query_rows: Optional[Tensor] = None        # [Q, d] query rows of X0 (bag means, transformed where a transform is set), set by the first node_linear
         self.token: Optional[Tensor] = None             # carries the autograd edge from the batch tail to that op
         self.dim = int(user_table.shape[1])
@@ -968,13 +1098,13 @@ class _LinearFromTables(torch.autograd.Function):
     there (this op is also the tap of layer 0), then the bag-mean backward."""
 
     @staticmethod
-    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, w: Tensor, bias: Optional[Tensor], wq: Optional[Tensor], bq: Optional[Tensor],
-                nodes: NodeTables, layout: IncidenceLayout, typed: bool, bias_mask: int):
+    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, w: Tensor, bias: Optional[Tensor], nodes: NodeTables, layout: IncidenceLayout, typed: bool,
+                bias_mask: int, keep: bool, *params: Tensor):
         lib = _lib.load()
-        bag, dim = nodes.bag, nodes.dim
+        bag, dim, qt = nodes.bag, nodes.dim, nodes.transform
         n = nodes.shape[0]
         query_rows = torch.empty(bag.n_bags, dim, dtype=torch.float32, device=word_table.device)
-        means = _query_rows_forward(word_table, bag, wq, bq, nodes.act, query_rows)
+        state = _query_rows_forward(word_table, bag, qt, out=query_rows, keep=keep)
         nodes.query_rows, nodes.layout = query_rows, layout
         nodes.token = torch.empty(1, dtype=torch.float32, device=word_table.device)
         out = torch.empty(n, dim, dtype=torch.float32, device=word_table.device)
@@ -983,8 +1113,7 @@ class _LinearFromTables(torch.autograd.Function):
         with profiler.kernel('node_linear_fwd', n, dim):
             _lib.check(lib.ihg_node_linear_fwd_typed(nodes.row_pointers(), dim, _ptr(w), int(w.stride(0)), dim if typed else 0, _ptr(bias), bias_mask, dim if per_type_bias else 0,
                                                      _type_begin(layout), _ptr(out), dim, _ptr(ws), ws.numel() * 4, dim, _stream()), 'ihg_node_linear_fwd_typed')
-        ctx.transform = wq is not None
-        ctx.save_for_backward(user_table, item_table, w, query_rows, *((means, wq) if ctx.transform else ()))
+        ctx.save_for_backward(user_table, item_table, w, query_rows, *_transform_state(qt, state, params))
         ctx.nodes, ctx.layout, ctx.typed, ctx.bias_mask, ctx.has_bias, ctx.per_type_bias = nodes, layout, typed, bias_mask, bias is not None, per_type_bias
         ctx.mark_non_differentiable(query_rows)
         ctx.set_materialize_grads(False)                     # (the token's and the bag means' gradients are never read: no zero tensors made for them)
@@ -994,7 +1123,7 @@ class _LinearFromTables(torch.autograd.Function):
     def backward(ctx, grad_out: Tensor, _grad_token, _grad_rows):
         lib = _lib.load()
         user_table, item_table, w, query_rows = ctx.saved_tensors[:4]
-        means, wq = ctx.saved_tensors[4:] if ctx.transform else (None, None)
+        state = ctx.saved_tensors[4:]
         nodes, layout = ctx.nodes, ctx.layout
         bag, dim = nodes.bag, nodes.dim
         if grad_out is None:
@@ -1017,8 +1146,8 @@ class _LinearFromTables(torch.autograd.Function):
         if holder is not None and holder.rowgrad is not None:              # the batch tail's gradient of the layer-0 rows: this op is their tap
             holder.put_into_typed(dx_rows, dim, layout, 0, dim)
         # d_query is complete now (layer 0's input gradient + the batch tail's layer-0 rows): the query transform's backward, then the bag mean's
-        d_word, dwq, dbq = _query_rows_backward(d_query, bag, means, query_rows, wq, nodes.act)
-        return d_user, d_item, d_word, dw, dbias, dwq, dbq, None, None, None, None
+        d_word, grads = _query_rows_backward(d_query, bag, nodes.transform, state, query_rows)
+        return (d_user, d_item, d_word, dw, dbias, None, None, None, None, None) + tuple(grads)
 
 
 class _GatherActiveNodes(torch.autograd.Function):
@@ -1028,11 +1157,11 @@ class _GatherActiveNodes(torch.autograd.Function):
     gradients - dense ``[U + 1, d]`` / ``[I + 1, d]`` / ``[V + 1, d]`` tensors whose rows are zero for nodes that are neither active nor in the batch."""
 
     @staticmethod
-    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, wq: Optional[Tensor], bq: Optional[Tensor], nodes: NodeTables, layout: IncidenceLayout):
-        bag, dim = nodes.bag, nodes.dim
+    def forward(ctx, user_table: Tensor, item_table: Tensor, word_table: Tensor, nodes: NodeTables, layout: IncidenceLayout, keep: bool, *params: Tensor):
+        bag, dim, qt = nodes.bag, nodes.dim, nodes.transform
         u_pub, q_pub = layout.public_user_count, layout.public_query_count
         query_rows = torch.empty(bag.n_bags, dim, dtype=torch.float32, device=word_table.device)
-        means = _query_rows_forward(word_table, bag, wq, bq, nodes.act, query_rows)
+        state = _query_rows_forward(word_table, bag, qt, out=query_rows, keep=keep)
         nodes.query_rows, nodes.layout = query_rows, layout
         nodes._public_type_begin = (ctypes.c_int64 * 4)(0, u_pub, u_pub + q_pub, layout.public_node_count)
         nodes.token = torch.empty(1, dtype=torch.float32, device=word_table.device)
@@ -1046,8 +1175,7 @@ class _GatherActiveNodes(torch.autograd.Function):
         torch.index_select(user_table, 0, picks[0], out=x[:ua])
         torch.index_select(query_rows, 0, picks[1], out=x[ua:ua + qa])
         torch.index_select(item_table, 0, picks[2], out=x[ua + qa:])
-        ctx.transform = wq is not None
-        ctx.save_for_backward(user_table, item_table, *((means, query_rows, wq) if ctx.transform else ()))
+        ctx.save_for_backward(user_table, item_table, query_rows, *_transform_state(qt, state, params))
         ctx.nodes, ctx.layout, ctx.picks = nodes, layout, picks
         ctx.mark_non_differentiable(query_rows)
         ctx.set_materialize_grads(False)
@@ -1055,8 +1183,8 @@ class _GatherActiveNodes(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_x: Tensor, _grad_token, _grad_rows):
-        user_table, item_table = ctx.saved_tensors[:2]
-        means, query_rows, wq = ctx.saved_tensors[2:] if ctx.transform else (None, None, None)
+        user_table, item_table, query_rows = ctx.saved_tensors[:3]
+        state = ctx.saved_tensors[3:]
         nodes, layout, picks = ctx.nodes, ctx.layout, ctx.picks
         bag, dim = nodes.bag, nodes.dim
         if grad_x is None:
@@ -1073,8 +1201,8 @@ class _GatherActiveNodes(torch.autograd.Function):
             step = dim * 4
             dx_rows = (ctypes.c_void_p * 3)(d_user.data_ptr() + step, d_query.data_ptr(), d_item.data_ptr() + step)
             holder.put_into_typed(dx_rows, dim, layout, 0, dim, type_begin=nodes._public_type_begin)
-        d_word, dwq, dbq = _query_rows_backward(d_query, bag, means, query_rows, wq, nodes.act)      # (on the complete d_query, as in _LinearFromTables)
-        return d_user, d_item, d_word, dwq, dbq, None, None
+        d_word, grads = _query_rows_backward(d_query, bag, nodes.transform, state, query_rows)      # (on the complete d_query, as in _LinearFromTables)
+        return (d_user, d_item, d_word, None, None, None) + tuple(grads)
 
 
 def gather_active_nodes(nodes: NodeTables, layout: IncidenceLayout) -> Tensor:
@@ -1083,7 +1211,9 @@ def gather_active_nodes(nodes: NodeTables, layout: IncidenceLayout) -> Tensor:
         raise ValueError('gather_active_nodes is for a layout that leaves the isolated nodes out')
     if nodes.query_rows is not None:
         raise RuntimeError('NodeTables: the input features were already consumed (one per forward)')
-    x, _token, _rows_q = _GatherActiveNodes.apply(nodes.user_table, nodes.item_table, nodes.word_table, nodes.wq, nodes.bq, nodes, layout)
+    params = nodes.transform.tensors
+    x, _token, _rows_q = _GatherActiveNodes.apply(nodes.user_table, nodes.item_table, nodes.word_table, nodes, layout,
+                                                  _tape(nodes.user_table, nodes.item_table, nodes.word_table, *params), *params)
     return x
 
 
@@ -1094,7 +1224,9 @@ def node_linear(x, w: Tensor, bias: Optional[Tensor], layout: IncidenceLayout, t
     if isinstance(x, NodeTables):
         if x.query_rows is not None:
             raise RuntimeError('NodeTables: the input features were already consumed by a node-level transform (one per forward)')
-        out, _token, _rows_q = _LinearFromTables.apply(x.user_table, x.item_table, x.word_table, w, bias, x.wq, x.bq, x, layout, bool(typed), int(bias_mask))
+        params = x.transform.tensors
+        out, _token, _rows_q = _LinearFromTables.apply(x.user_table, x.item_table, x.word_table, w, bias, x, layout, bool(typed), int(bias_mask),
+                                                       _tape(x.user_table, x.item_table, x.word_table, w, bias, *params), *params)
         return out
     return _NodeLinear.apply(x, w, bias, _type_begin(layout), bool(typed), int(bias_mask))
 

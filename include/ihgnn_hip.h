@@ -807,6 +807,33 @@ int ihg_kg_loss(const float* pos, const float* neg, int64_t ld_neg, const float*
                 ihg_stream_t stream);
 int ihg_rows_topk(const float* scores, int64_t ld, int64_t n_rows, int64_t n_items, int32_t k, int64_t* items, float* top_scores, ihg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DEVICE: the GRU query encoder (csrc/recurrent.hip; Gs.Query.transform == 'gru').  For bag q with word rows x_1 .. x_T of `table` in the order of `words`, h_0 = 0:
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z = sigmoid(W_iz x + b_iz + W_hz h + b_hz), n = tanh(W_in x + b_in + r * (W_hn h + b_hn)), h' = (1 - z) n + z h
+ * (torch.nn.GRU: w_ih / w_hh [3 dim, dim] contiguous, b_ih / b_hh [3 dim], gate order r, z, n) and out[q] = h_T; an empty bag gives a zero row and no gradient.
+ * fp32 throughout (v_mfma_f32_16x16x4_f32).  dim is 32, 64, 128 or 256: a caller with another width appends zero columns / rows to every operand, which is exact.
+ * A workgroup owns 32 bags that are adjacent in `bag_order` (bags by decreasing length; NULL: as they are numbered) and runs its own time loop to its longest member: the
+ * launch count does not depend on the bag lengths - one launch forwards, four backwards - and nothing synchronises; results do not depend on bag_order.
+ *   ihg_gru_fwd   out [n_bags, dim] with any row stride ld_out >= dim and no alignment asked of it (a row block of X0, a column slice of the feature matrix).  `saved`
+ *                 (ihg_gru_saved_bytes(n_words, dim) bytes, 16-byte aligned; NULL outside autograd: nothing is stored): r, z, n, W_hn h + b_hn and h_{t-1} of every
+ *                 word occurrence - 5 n_words dim floats.  `workspace` is not read today (kept for an input projection hoisted to the vocabulary rows).
+ *   ihg_gru_bwd   from the COMPLETE cotangent d_query [n_bags, dim] (any row stride): d_table [n_table_rows, dim] contiguous, every row written - the sum over the
+ *                 word's positions in position order (word_ptr [n_table_rows + 1], word_pos [n_words]: ihg_node_segment_sum over the per-occurrence gradients) -,
+ *                 dw_ih, dw_hh [3 dim, dim], db_ih, db_hh [3 dim]: summed over fixed slabs of occurrences and the slabs in slab order.  No float atomics: two runs
+ *                 give the same bits.  `workspace`: ihg_gru_workspace_bytes(n_bags, n_words, dim) bytes, 16-byte aligned.
+ * IHG_ERR_INVALID / IHG_ERR_WORKSPACE have launched nothing.  n_bags == 0 or n_words == 0: IHG_OK - the forward writes zero rows, the backward zeroes all five gradients.
+ * The two *_bytes calls take any 1 <= dim <= 256 (the size at the next tiled width) and answer -1 beyond.
+ */
+int64_t ihg_gru_workspace_bytes(int64_t n_bags, int64_t n_words, int32_t dim);
+int64_t ihg_gru_saved_bytes(int64_t n_words, int32_t dim);
+int ihg_gru_fwd(const float* table, int64_t ld_table, const int32_t* bag_ptr, const int32_t* words, const int32_t* bag_order, int64_t n_bags, int64_t n_words,
+                const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* out, int64_t ld_out, float* saved, void* workspace,
+                int64_t workspace_bytes, int32_t dim, ihg_stream_t stream);
+int ihg_gru_bwd(const float* d_query, int64_t ld_dq, const float* table, int64_t ld_table, const int32_t* bag_ptr, const int32_t* words, const int32_t* bag_order,
+                int64_t n_bags, int64_t n_words, const int32_t* word_ptr, const int32_t* word_pos, int64_t n_table_rows, const float* w_ih, const float* w_hh,
+                const float* saved, float* d_table, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, void* workspace, int64_t workspace_bytes, int32_t dim,
+                ihg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
