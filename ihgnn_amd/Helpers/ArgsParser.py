@@ -54,6 +54,9 @@ _FLAGS = (
     ('cosine', ('--cosine',), 'flag', False, 'score with the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity) instead of the dot product'),
     # not in the reference, which reports @10 only (Metrics.py:60-63)
     ('cutoffs', ('--cutoffs',), cutoff_list, '', 'further metric cutoffs, e.g. 20,50,100 (each in 11..128): HR / NDCG / MAP @K beside the @10 triple, from one ranking at the largest (Gs.Evaluation.extra_cutoffs)'),
+    # not in the reference, which trains on nn.BCEWithLogitsLoss only (Main.py:191)
+    ('loss', ('--loss',), str, 'bce', 'training objective: bce (the reference\'s point-wise loss) | bpr (pairwise: every positive against each of its negatives) | '
+                                      'softmax (the positive against its own negatives; Gs.Training.loss)'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '
@@ -61,7 +64,8 @@ _FLAGS = (
 )
 
 
-_CHOICES = {'query_transform': (Gsv.mean, Gsv.activation, Gsv.gru), 'query_activation': ('relu', 'tanh')}
+LOSSES = ('bce', 'bpr', 'softmax')
+_CHOICES = {'query_transform': (Gsv.mean, Gsv.activation, Gsv.gru), 'query_activation': ('relu', 'tanh'), 'loss': LOSSES}
 
 
 class ConsoleArgs:

@@ -42,6 +42,9 @@ class Gs:
     class Prediction:
         use_cosine_similarity = False
 
+    class Training:
+        loss = 'bce'                     # not in the reference (whose only objective is nn.BCEWithLogitsLoss over a positive and its negatives): 'bpr' | 'softmax' (--loss) train on a ranking loss of every positive against its own negatives
+
     class Evaluation:
         extra_cutoffs = ()               # not in the reference (which reports @10 only): further cutoffs K in 11..128 (--cutoffs), HR / NDCG / MAP @K beside the @10 triple
 

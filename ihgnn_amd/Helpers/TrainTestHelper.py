@@ -194,7 +194,10 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
     process, fused loss, the HIP Adam): batches of the common size run as replays of ONE recorded step (``ihgnn_amd.captured_step``: worth it where the step is
     bound by the host's launch rate, i.e. on small graphs); other batch sizes - the epoch's last batch - run eagerly.  ``'auto'`` (default): the first steps of the
     first epoch run eagerly, steps 4 - 7 are timed, and the step is recorded when they took less than ``AUTO_RECORD_BELOW_MS`` each; ``'on'`` / ``'off'`` decide
-    without measuring.  A model the recording refuses (a parameter without gradient) trains eagerly, with one log line."""
+    without measuring.  A model the recording refuses (a parameter without gradient) trains eagerly, with one log line.
+
+    ``Gs.Training.loss`` other than ``'bce'`` (``--loss bpr | softmax``): a step is ``model.ranking_loss`` over the batch's groups (every positive with its own negatives)
+    where the fused batch tail runs, ``ops.ranking_loss`` on the model's scores where it does not; ``loss_function`` and the labels are then not used."""
     from ..Models.Srrl import Srrl
     if isinstance(model, Srrl):
         if grad_sync is not None or _record_mode(record_step) == 'on':
@@ -220,13 +223,19 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
         positives += len(p_u)
         users, queries, items = torch.cat([p_u, n_u]), torch.cat([p_q, n_q]), torch.cat([p_i, n_i])
         flags = torch.cat([p_f, n_f]).float()
-        fused = getattr(model, 'supports_fused_loss', None) and model.supports_fused_loss(loss_function)
+        kind = Gs.Training.loss                             # read per step, as the model reads its head
+        ranking = kind != 'bce'
+        if ranking:
+            fused = getattr(model, 'supports_fused_tail', None) and model.supports_fused_tail()
+        else:
+            fused = getattr(model, 'supports_fused_loss', None) and model.supports_fused_loss(loss_function)
         if decision and fused:
             recorded = getattr(model, '_recorded_step', None)
             if recorded is None or recorded.optimizer is not optimizer or recorded.stale():     # (stale: a hyper-parameter baked into the recording changed)
                 from ..captured_step import CapturedTrainingStep
                 try:
-                    recorded = model._recorded_step = CapturedTrainingStep(model, optimizer, int(users.shape[0]), warmup_batch=(users, queries, items, flags))
+                    recorded = model._recorded_step = CapturedTrainingStep(model, optimizer, int(users.shape[0]), warmup_batch=(users, queries, items, flags),
+                                                                                  positives=len(p_u) if ranking else None)
                 except (ValueError, RuntimeError) as refused:
                     # ValueError: the recording's own refusal (a parameter without gradient, ...); RuntimeError: the stream capture failed (an op that synchronises,
                     # an allocation the capture cannot hold) - under 'auto' nobody asked for a recording, so either way the run goes on eagerly; under 'on' a
@@ -237,8 +246,8 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
                     recorded, decision = None, False
                     model._recorded_step, model._record_decision, model._record_refused = None, False, True
                     optimizer.zero_grad(set_to_none=True)
-            if recorded is not None and recorded.batch_rows == int(users.shape[0]):
-                loss_sum += recorded.step(users, queries, items, flags)
+            if recorded is not None and recorded.batch_rows == int(users.shape[0]) and (not ranking or recorded.positives == len(p_u)):
+                loss_sum += recorded.step(users, queries, items, flags, positives=len(p_u))
                 batches += 1
                 continue
         # auto: a few eager steps are timed (the step alone, device drained on both sides - not the loader's work between steps) once the allocator and the workspaces are warm
@@ -251,7 +260,12 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
         cotangent = getattr(grad_sync, 'mode', None) == 'cotangent'
         if cotangent and not fused:
             raise RuntimeError('--grad_sync cotangent exchanges the fused batch tail\'s row gradients: it needs the HIP model and a plain BCEWithLogitsLoss (use bucketed / sharded)')
-        if fused:
+        if ranking and fused:
+            loss = model.ranking_loss(users, queries, items, positives=len(p_u), kind=kind, cotangent_sync=grad_sync if cotangent else None)
+        elif ranking:
+            from .. import ops
+            loss = ops.ranking_loss(model(users, queries, items), len(p_u), kind)
+        elif fused:
             loss = model.bce_loss(users, queries, items, flags, cotangent_sync=grad_sync) if cotangent else model.bce_loss(users, queries, items, flags)
         else:
             loss = loss_function(model(users, queries, items), flags)

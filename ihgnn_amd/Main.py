@@ -54,6 +54,15 @@ def apply_evaluation_settings(args) -> None:
     Gs.Evaluation.extra_cutoffs = tuple(getattr(args, 'cutoffs', ()) or ())
 
 
+def apply_training_settings(args) -> None:
+    """``--loss`` -> ``Gs.Training.loss``, assigned both ways like the head above (not in the reference, which trains on ``nn.BCEWithLogitsLoss`` only)."""
+    from .Helpers.ArgsParser import LOSSES
+    loss = getattr(args, 'loss', 'bce') or 'bce'
+    if loss not in LOSSES:
+        raise ValueError(f'--loss: one of {", ".join(LOSSES)}, got {loss!r}')
+    Gs.Training.loss = loss
+
+
 def apply_sampling_settings(args) -> None:
     """``--logged_negatives N`` -> ``Gs.non_random_negative_sample_size`` (0: the setting stays as it is) and the sum ``Gs.negative_sample_size``, which the class
     body evaluates once and which would go stale (not in the reference's command line: one edits ``Helpers/GlobalSettings.py`` there)."""
@@ -76,6 +85,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise NotImplementedError('--model Srrl draws its batches on the host (SrrlDatasetKG): --device_sampling does not apply')
     if getattr(args, 'phase2', False):
         raise ValueError('--phase2 is the IHGNN layer\'s phase-2 attention; --model Srrl has no layers')
+    if (getattr(args, 'loss', 'bce') or 'bce') != 'bce':
+        raise NotImplementedError('--model Srrl trains its PS half on the BCE, as the reference does: --loss bpr / softmax have not been built for it')
     if getattr(args, 'query_transform', Gsv.mean) == Gsv.gru:
         raise NotImplementedError('--model Srrl embeds its queries by the bag mean or the activation transform: --query_transform gru has not been built for it')
     widest = ops.cat_linear_max_width()
@@ -134,6 +145,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     apply_prediction_settings(args)
     apply_evaluation_settings(args)
     apply_sampling_settings(args)
+    apply_training_settings(args)
     if model_type is Srrl:
         check_srrl_settings(args, world)
     if args.device == 'cpu':
@@ -159,7 +171,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     say((f'model Srrl | dataset {dataset_name} | KG loss {Gs.Srrl.KG_loss} | uniform KG weights {Gs.Srrl.uni_weight} | ' if model_type is Srrl else
          f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | ') +
         f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
-        f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | validation {Gs.use_valid_dataset}')
+        f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | loss {Gs.Training.loss} | validation {Gs.use_valid_dataset}')
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
 
     dataset_train = GraphDataset(

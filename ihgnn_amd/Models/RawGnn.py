@@ -220,6 +220,22 @@ class RawGnn(nn.Module):
         MEAN of all ranks' losses - the ranks exchange the batch rows' cotangents (not the dense gradients) and every rank runs the propagation backward on their
         union; the layers are told the union of the ranks' batch rows (where the last layer's output is read / its cotangent is non-zero).  A COLLECTIVE: every
         rank calls it, with batches of the same size."""
+        return self._fused_loss(user_indices, query_indices, item_indices, labels, None, cotangent_sync)
+
+    def ranking_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, positives: int, kind: Optional[str] = None, cotangent_sync=None) -> Tensor:
+        """``ops.ranking_loss(self(u, q, i), positives, kind)`` through the fused batch tail: ``bce_loss`` with the BPR (``'bpr'``) or sampled-softmax (``'softmax'``)
+        loss of every positive against its own negatives in place of the BCE.  The batch is ``positives`` positives followed by the ``k`` negatives of each (the negatives
+        of positive ``p`` at rows ``P + p k ..``: ``collate_fn``'s layout); no labels.  ``kind=None`` reads ``Gs.Training.loss`` at every call, as the head flag is
+        read; ``'bce'`` needs labels and is ``bce_loss``'s.  ``cotangent_sync``: as in ``bce_loss`` (every rank's groups stay its own: the exchange moves row gradients)."""
+        from .. import ops
+        kind = Gs.Training.loss if kind is None else kind
+        if kind == 'bce':
+            raise ValueError('RawGnn.ranking_loss: the BCE needs labels - use bce_loss (Gs.Training.loss is \'bce\')')
+        objective = ops.ranking_objective(int(item_indices.shape[0]), positives, kind)
+        return self._fused_loss(user_indices, query_indices, item_indices, None, objective, cotangent_sync)
+
+    def _fused_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, labels: Optional[Tensor], objective, cotangent_sync) -> Tensor:
+        """The training loss through the fused batch tail: the BCE over ``labels`` (``objective`` None) or a ranking loss (``ops.ranking_objective``'s pair)."""
         from .. import ops
         ds, head = self.dataset, self.prediction_layer
         cosine = bool(Gs.Prediction.use_cosine_similarity)       # read at every call, as the reference's head does (PredictionLayers.py:38)
@@ -233,18 +249,27 @@ class RawGnn(nn.Module):
         compact = self._compact_layout()
         if compact is not None and holder is None:
             # (no gradient wanted: the public matrices, the plain tail)
-            return nn.functional.binary_cross_entropy_with_logits(
-                ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, cosine=cosine), labels.float())
+            scores = ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, cosine=cosine)
+            if objective is not None:
+                return ops.ranking_loss(scores, *objective)
+            return nn.functional.binary_cross_entropy_with_logits(scores, labels.float())
         if compact is not None:
             holder.row_map = compact.node_map
         layers = self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer)
+        rows_upper = compact.compact_rows(rows) if compact is not None else None
+        if objective is not None:
+            return ops.hem_ranking_loss(layers, rows, item_indices, *objective, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
+                                        rows_upper=rows_upper, cosine=cosine)
         return ops.hem_bce_loss(layers, rows, item_indices, labels, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
-                                rows_upper=compact.compact_rows(rows) if compact is not None else None, cosine=cosine)
+                                rows_upper=rows_upper, cosine=cosine)
 
     def supports_fused_loss(self, loss_function) -> bool:
         return (isinstance(loss_function, nn.BCEWithLogitsLoss) and loss_function.reduction == 'mean' and loss_function.weight is None
-                and loss_function.pos_weight is None and self._saved_output_feature is None
-                and len(self.gnns) + 1 <= 8 and next(self.parameters()).is_cuda)
+                and loss_function.pos_weight is None and self.supports_fused_tail())
+
+    def supports_fused_tail(self) -> bool:
+        """The fused batch tail (``bce_loss`` / ``ranking_loss``) runs on this model as it stands."""
+        return self._saved_output_feature is None and len(self.gnns) + 1 <= 8 and next(self.parameters()).is_cuda
 
     def score_all_items(self, user_indices: Tensor, query_indices: Tensor) -> Tensor:
         """Scores of ``C`` (user, query) pairs against every item as a dense ``[C, I]`` matrix (torch; a checker for tests and

@@ -104,6 +104,7 @@ SIGNATURES = {
     'ihg_hem_score_bwd': (ctypes.c_int, [POINTER(c_void_p), c_int32, c_int64, c_int32, c_void_p, c_void_p, c_float, c_float,
                                          c_void_p, c_int64, c_int64, c_void_p]),
     'ihg_bce_with_logits': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'ihg_ranking_loss': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     'ihg_batch_scatter_workspace_bytes': (c_int64, [c_int64]),
     'ihg_batch_scatter_max_rows': (c_int32, []),
     'ihg_batch_scatter_add': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int64,
@@ -193,6 +194,7 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 ACT_NONE, ACT_LEAKY_RELU = 0, 3
+LOSS_KINDS = {'bpr': 1, 'softmax': 2}      # IHG_LOSS_BPR / IHG_LOSS_SOFTMAX
 
 _lib: Optional[ctypes.CDLL] = None
 

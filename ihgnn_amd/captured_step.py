@@ -3,7 +3,7 @@
 A step of the hot path is ~85 kernel launches issued from Python through ctypes.  At the BASELINE workloads from C2 up the GPU is
 the bound (the kernels of a C3 step add up to the step's wall time: profiles/r3), so recording buys nothing there; on small graphs
 (config C1: 20,000 hyperedges, every kernel a few microseconds) the step is bound by the host's launch rate, and a replay removes
-that.  What is recorded: forward (``RawGnn.bce_loss``), backward, and the Adam update with its two step-dependent scalars read from
+that.  What is recorded: forward (``RawGnn.bce_loss``, or ``RawGnn.ranking_loss`` under ``Gs.Training.loss`` = bpr / softmax), backward, and the Adam update with its two step-dependent scalars read from
 device memory (``ihg_adam_step_device_scalars``).  Per replay the host copies the batch into the static input buffers, refreshes the two
 Adam scalars and launches the graph.  Single process only (a recorded RCCL exchange is not attempted).
 """
@@ -19,15 +19,25 @@ class CapturedTrainingStep:
 
         loss = model.bce_loss(users, queries, items, labels); loss.backward(); optimizer.step(); optimizer.zero_grad()
 
-    for batches of ``batch_rows`` rows.  The learning rate may change between calls (it enters through the device scalars)."""
+    for batches of ``batch_rows`` rows.  The learning rate may change between calls (it enters through the device scalars).  Under a ranking loss (``Gs.Training.loss``
+    other than ``'bce'``, read when the step is recorded) the recorded forward is ``model.ranking_loss(users, queries, items, positives)``: ``positives`` is then
+    required, and the labels are carried but not read."""
 
-    def __init__(self, model, optimizer: Adam, batch_rows: int, warmup_batch=None):
+    def __init__(self, model, optimizer: Adam, batch_rows: int, warmup_batch=None, positives=None):
         if not isinstance(optimizer, Adam):
             raise TypeError('CapturedTrainingStep records ihgnn_amd.optim.Adam')
         if any(getattr(layer, 'attention_phase2', False) for layer in getattr(model, 'gnns', ())):
             # (a ValueError: the training loop then goes on eagerly with one log line, TrainTestHelper.train_and_get_avg_loss)
             raise ValueError('CapturedTrainingStep: a model with phase-2 attention is not recorded (its step has not been replayed against the eager one)')
         self.model, self.optimizer, self.batch_rows = model, optimizer, int(batch_rows)
+        from .Helpers.GlobalSettings import Gs
+        self.loss_kind = Gs.Training.loss
+        self.positives = None if positives is None else int(positives)
+        if self.loss_kind != 'bce':
+            if self.positives is None:
+                raise ValueError(f'CapturedTrainingStep: Gs.Training.loss = {self.loss_kind!r} needs positives= (the batch is P positives followed by the negatives of each)')
+            from . import ops
+            ops.ranking_objective(self.batch_rows, self.positives, self.loss_kind)      # the host check, before anything is recorded
         dev = next(model.parameters()).device
         self.users = torch.zeros(batch_rows, dtype=torch.int64, device=dev)
         self.queries = torch.zeros(batch_rows, dtype=torch.int64, device=dev)
@@ -64,7 +74,10 @@ class CapturedTrainingStep:
             try:
                 for module, name, p in slots:
                     module._parameters[name] = aliases[id(p)]
-                loss = model.bce_loss(self.users, self.queries, self.items, self.labels)
+                if self.loss_kind != 'bce':
+                    loss = model.ranking_loss(self.users, self.queries, self.items, self.positives, self.loss_kind)
+                else:
+                    loss = model.bce_loss(self.users, self.queries, self.items, self.labels)
             finally:
                 for module, name, p in slots:
                     module._parameters[name] = p
@@ -102,8 +115,9 @@ class CapturedTrainingStep:
         recording holds the kernels of the head that was set) a replay cannot change any more (cheap: compared at every ``step()``)."""
         from .Helpers.GlobalSettings import Gs
         group = self.optimizer.param_groups[0]
+        loss = Gs.Training.loss                             # (read at every call, like the head: the recording holds the loss launch that was set - and its group count)
         return (tuple(group['betas']), float(group['eps']), float(group['weight_decay']), bool(self.model.batch_rows_only_last_layer),
-                bool(Gs.Prediction.use_cosine_similarity))
+                bool(Gs.Prediction.use_cosine_similarity), loss, self.positives if loss != 'bce' else None)
 
     def _baked_settings(self):
         """Everything a replay cannot change any more: the recording holds the kernels these settings selected.  Only the learning rate is
@@ -118,12 +132,13 @@ class CapturedTrainingStep:
 
     def stale(self, full: bool = False) -> bool:
         """True when a setting that is baked into the recording has changed since: the caller must record a new step (``TrainTestHelper`` does) - replaying would
-        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer`` and the scoring head - five values, what
-        every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
+        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer``, the scoring head, the loss kind and (under a ranking loss) the number of
+        positives - seven values, what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
         epoch, not per replay on the launch-bound path the recording exists for)."""
         if full:
             return self._baked != self._baked_settings()
-        return self._baked[:5] != self._baked_hyperparameters()
+        now = self._baked_hyperparameters()
+        return self._baked[:len(now)] != now
 
     TABLE_STEPS = 2048
 
@@ -138,11 +153,13 @@ class CapturedTrainingStep:
             self._table, self._table_first, self._table_lr = table.to(self.scalars.device), t, group['lr']
         self.scalars.copy_(self._table[t - self._table_first], non_blocking=True)
 
-    def step(self, users, queries, items, labels):
+    def step(self, users, queries, items, labels, positives=None):
         if users.shape[0] != self.batch_rows:
             raise ValueError(f'this step was recorded for batches of {self.batch_rows} rows, got {users.shape[0]}')
+        if positives is not None and self.loss_kind != 'bce' and int(positives) != self.positives:
+            raise ValueError(f'this step was recorded for batches of {self.positives} positives, got {positives}')
         if self.stale():
-            raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay, batch_rows_only_last_layer or the scoring head - the values '
+            raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay, batch_rows_only_last_layer, the scoring head or the loss - the values '
                                'every step() compares; the IHG_* environment and the switches of ihgnn_amd.ops are compared by stale(full=True), which the training loop '
                                'asks once per epoch); record a new step')
         self.users.copy_(users, non_blocking=True)

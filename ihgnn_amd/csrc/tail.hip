@@ -187,6 +187,59 @@ __global__ __launch_bounds__(kScatterThreads) void bce_with_logits_kernel(const 
     if (threadIdx.x == 0) *loss = part[0] * inv_n;
 }
 
+// Ranking losses over a batch laid out as P positives followed by P*k negatives, the negatives of positive p at P + p*k .. P + (p+1)*k - 1 (collate_fn,
+// device_batches, ihg_device_batch), and d loss / d scores, one workgroup, no atomics.
+//   BPR      x_pj = s_pj - s_p;  loss = (1 / (P k)) sum_p sum_j softplus(x_pj);  ds_pj = sigmoid(x_pj) / (P k);  ds_p = -sum_j ds_pj
+//   SOFTMAX  m_p = max(s_p, s_pj);  e_p = exp(s_p - m_p), e_pj = exp(s_pj - m_p);  N_p = sum_j e_pj;  Z_p = e_p + N_p;
+//            loss = (1 / P) sum_p ((m_p - s_p) + log Z_p);  ds_pj = (e_pj / Z_p) / P;  ds_p = -(N_p / Z_p) / P   (= (e_p / Z_p - 1) / P without its cancellation)
+// A THREAD OWNS A GROUP and loops over its k negatives, j ascending; a thread takes groups threadIdx.x, threadIdx.x + 1024, ... in that order and adds their loss
+// terms to its own partial sum, and the 1,024 partial sums go through bce_with_logits_kernel's tree.  Chosen over a sub-wave of lanes per group: at the working
+// point (100 groups of 10) the launch is the cost either way, k is arbitrary (a lane width would have to loop as well), and sums in plain j order need no
+// cross-lane step whose order depends on a lane width - so every sum's order is a function of (P, k) alone and the results are bitwise repeatable.
+constexpr int kLossBpr = IHG_LOSS_BPR, kLossSoftmax = IHG_LOSS_SOFTMAX;
+
+template <int KIND>
+__global__ __launch_bounds__(kScatterThreads) void ranking_loss_kernel(const float* __restrict__ scores, int positives, int k, float* __restrict__ loss,
+                                                                       float* __restrict__ dscores) {
+    __shared__ float part[kScatterThreads];
+    float acc = 0.f;
+    const float inv_p = 1.f / static_cast<float>(positives);
+    const float inv_n = 1.f / static_cast<float>(static_cast<int64_t>(positives) * k);
+    for (int p = threadIdx.x; p < positives; p += kScatterThreads) {
+        const float sp = scores[p];
+        const int64_t first = positives + static_cast<int64_t>(p) * k;      // (< positives * (1 + k) <= INT32_MAX: checked by the entry)
+        if constexpr (KIND == kLossBpr) {
+            float dsum = 0.f;
+            for (int j = 0; j < k; ++j) {
+                const float x = scores[first + j] - sp;
+                const float e = expf(-fabsf(x));
+                acc += fmaxf(x, 0.f) + log1pf(e);
+                const float sig = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+                const float d = sig * inv_n;
+                dscores[first + j] = d;
+                dsum += d;
+            }
+            dscores[p] = -dsum;
+        } else {
+            float m = sp;
+            for (int j = 0; j < k; ++j) m = fmaxf(m, scores[first + j]);
+            float negatives = 0.f;
+            for (int j = 0; j < k; ++j) negatives += expf(scores[first + j] - m);
+            const float z = expf(sp - m) + negatives;
+            acc += (m - sp) + logf(z);
+            for (int j = 0; j < k; ++j) dscores[first + j] = expf(scores[first + j] - m) / z * inv_p;      // (the same expf of the same argument as above: the same bits)
+            dscores[p] = -(negatives / z) * inv_p;
+        }
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = kScatterThreads / 2; off > 0; off >>= 1) {
+        if (static_cast<int>(threadIdx.x) < off) part[threadIdx.x] += part[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = part[0] * (KIND == kLossBpr ? inv_n : inv_p);
+}
+
 // Deterministic scatter-add of a small batch of rows into a large dense matrix: dense[rows[k], :] += rowgrad[k, :], duplicates
 // summed in batch order, no atomics, no sort.  One wave per batch position k: it scans rows[0..k) for an earlier occurrence of
 // its destination (ballot over 64 ids at a time; the id array is a few KB and cache-resident) and retires if there is one;
@@ -620,6 +673,17 @@ int ihg_bce_with_logits(const float* scores, const float* labels, int64_t n, flo
         return fail(IHG_ERR_INVALID, "ihg_bce_with_logits: bad argument");
     hipLaunchKernelGGL(bce_with_logits_kernel, dim3(1), dim3(kScatterThreads), 0, static_cast<hipStream_t>(stream), scores, labels, static_cast<int>(n), loss, dscores);
     return check_launch("ihg_bce_with_logits");
+}
+
+int ihg_ranking_loss(const float* scores, int64_t positives, int32_t k, int32_t kind, float* loss, float* dscores, ihg_stream_t stream) {
+    if (scores == nullptr || loss == nullptr || dscores == nullptr) return fail(IHG_ERR_INVALID, "ihg_ranking_loss: null pointer");
+    if (positives < 1 || k < 1) return fail(IHG_ERR_INVALID, "ihg_ranking_loss: need positives >= 1 and k >= 1, got %lld and %d", (long long)positives, k);
+    if (kind != kLossBpr && kind != kLossSoftmax) return fail(IHG_ERR_INVALID, "ihg_ranking_loss: kind is IHG_LOSS_BPR (1) or IHG_LOSS_SOFTMAX (2), got %d", kind);
+    if (positives > INT32_MAX / (static_cast<int64_t>(k) + 1))
+        return fail(IHG_ERR_INVALID, "ihg_ranking_loss: positives * (1 + k) = %lld * %lld is beyond INT32_MAX scores", (long long)positives, (long long)k + 1);
+    const auto kernel = kind == kLossBpr ? ranking_loss_kernel<kLossBpr> : ranking_loss_kernel<kLossSoftmax>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(kScatterThreads), 0, static_cast<hipStream_t>(stream), scores, static_cast<int>(positives), static_cast<int>(k), loss, dscores);
+    return check_launch("ihg_ranking_loss");
 }
 
 

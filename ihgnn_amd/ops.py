@@ -1859,8 +1859,9 @@ class _HemBceLoss(torch.autograd.Function):
     returned here); without one they are returned dense."""
 
     @staticmethod
-    def forward(ctx, rows: Tensor, items: Tensor, labels: Tensor, bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, cosine: bool,
-                *layers: Tensor) -> Tensor:
+    def forward(ctx, rows: Tensor, items: Tensor, labels: Optional[Tensor], bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, cosine: bool,
+                objective, *layers: Tensor) -> Tensor:
+        # objective: None = the BCE over ``labels``; (positives, kind) = a ranking loss (``ihg_ranking_loss``; no labels are read) - the one launch that differs
         # tables (a resolved NodeTables): layer 0 is the embedding tables in place; layers[0] is then its token (the autograd edge), not a matrix
         # rows_upper (a layout without the isolated nodes): layer 0 is in the public numbering (rows), the layers above are in the layout's (rows_upper; -1: zero row)
         lib = _lib.load()
@@ -1869,10 +1870,15 @@ class _HemBceLoss(torch.autograd.Function):
         scores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         dscores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         loss = torch.empty((), dtype=torch.float32, device=bias.device)
-        labels = labels.to(torch.float32).contiguous()
+        if objective is None:
+            labels = labels.to(torch.float32).contiguous()
         with profiler.kernel('hem_cosine_fwd' if cosine else 'hem_score_fwd', batch, dim):
             stats = _hem_forward(real, tables, rows, rows_upper, items, bias, lam, cosine, scores)
-            _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), batch, _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
+            if objective is None:
+                _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), batch, _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
+            else:
+                positives, kind = objective
+                _lib.check(lib.ihg_ranking_loss(_ptr(scores), positives, batch // positives - 1, kind, _ptr(loss), _ptr(dscores), _stream()), 'ihg_ranking_loss')
         ctx.save_for_backward(rows, items, bias, dscores, *real)
         ctx.rows_upper, ctx.stats = rows_upper, stats
         ctx.lam, ctx.offset, ctx.holder, ctx.tables = float(lam), int(item_row_offset), holder, tables
@@ -1887,7 +1893,7 @@ class _HemBceLoss(torch.autograd.Function):
             if tables is not None or ctx.rows_upper is not None:
                 raise _lib.IhgnnHipError('hem_bce_loss over NodeTables / a compact layout needs a TailGradients holder')
             dbias, grads = _hem_backward(layers, rows, items, bias, ctx.lam, dscores * grad_loss, 1.0, ctx.offset, ctx.stats)
-            return (None, None, None, dbias, None, None, None, None, None, None) + grads
+            return (None, None, None, dbias, None, None, None, None, None, None, None) + grads
         holder = ctx.holder
         rowgrad = _hem_row_gradients(layers, rows, items, bias, ctx.lam, dscores, holder.grad_scale, tables, grad_loss.contiguous(), ctx.rows_upper, ctx.stats)     # d loss stays on the device: no host read, no multiply launch
         width = _tail_shape(layers, tables)[2]
@@ -1918,7 +1924,7 @@ class _HemBceLoss(torch.autograd.Function):
         placeholders = tuple(_zero_like_expanded(x.shape, x.device) for x in layers)
         if tables is not None:
             placeholders = (_zero_like_expanded(ctx.token_shape, bias.device),) + placeholders
-        return (None, None, None, dbias, None, None, None, None, None, None) + placeholders
+        return (None, None, None, dbias, None, None, None, None, None, None, None) + placeholders
 
 
 def score_topk_max_width() -> int:
@@ -2089,16 +2095,43 @@ def hem_bce_loss(layers, rows: Tensor, items: Tensor, labels: Tensor, bias: Tens
     tail halves of ``tap`` outputs made with this holder, and their gradients travel through it (see ``TailGradients``).  ``rows_upper`` (with ``holder.row_map``): the
     layers above layer 0 are numbered by the layout's own node ids (a layout without the isolated nodes): their rows of the batch, -1 = isolated = zero.  ``layers[0]`` may be a
     ``NodeTables`` (resolved by the first layer's transform): the head reads its layer-0 rows from the embedding tables in place.  ``cosine``: as in ``hem_score``."""
+    return _hem_loss('hem_bce_loss', layers, rows, items, labels, None, bias, lam, item_row_offset, holder, rows_upper, cosine)
+
+
+def _hem_loss(what: str, layers, rows: Tensor, items: Tensor, labels: Optional[Tensor], objective, bias: Tensor, lam: float, item_row_offset: int,
+              holder: Optional[TailGradients], rows_upper: Optional[Tensor], cosine: bool) -> Tensor:
+    """The fused batch tail under either objective (``_HemBceLoss``: ``objective`` None = BCE over ``labels``, else ``(positives, kind)``)."""
     tables = None
     layers = list(layers)
     if layers and isinstance(layers[0], NodeTables):
         tables = layers[0]
         if tables.query_rows is None or tables.token is None:
-            raise RuntimeError('hem_bce_loss: the NodeTables were not consumed by a node-level transform (a model without layers?)')
+            raise RuntimeError(f'{what}: the NodeTables were not consumed by a node-level transform (a model without layers?)')
         layers[0] = tables.token
     if rows_upper is not None and holder is not None and holder.row_map is None:
         raise ValueError('rows_upper comes with holder.row_map (the layout\'s public -> own node map)')
-    return _HemBceLoss.apply(rows, items, labels, bias, float(lam), int(item_row_offset), holder, tables, rows_upper, bool(cosine), *layers)
+    return _HemBceLoss.apply(rows, items, labels, bias, float(lam), int(item_row_offset), holder, tables, rows_upper, bool(cosine), objective, *layers)
+
+
+def ranking_objective(batch_rows: int, positives: int, kind) -> tuple:
+    """``(positives, kind code)`` of a ranking loss over a batch of ``batch_rows`` scores, checked on the host before anything is launched: the batch is ``positives``
+    positives followed by the same number ``k >= 1`` of negatives for each (``B % positives == 0`` and ``B / positives - 1 >= 1``), ``kind`` is ``'bpr'`` or
+    ``'softmax'`` (or ``IHG_LOSS_BPR`` / ``IHG_LOSS_SOFTMAX``)."""
+    code = _lib.LOSS_KINDS.get(kind, kind)
+    if code not in _lib.LOSS_KINDS.values() or isinstance(code, bool):
+        raise ValueError(f'ranking loss: kind is one of {sorted(_lib.LOSS_KINDS)}, got {kind!r}')
+    batch_rows, positives = int(batch_rows), int(positives)
+    if positives < 1 or batch_rows % positives != 0 or batch_rows // positives - 1 < 1:
+        raise ValueError(f'ranking loss: a batch is P positives followed by P * k negatives, k >= 1: {batch_rows} rows cannot be split into {positives} groups')
+    return positives, int(code)
+
+
+def hem_ranking_loss(layers, rows: Tensor, items: Tensor, positives: int, kind, bias: Tensor, lam: float, item_row_offset: int,
+                     holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
+    """``ranking_loss(hem_score(...), positives, kind)`` as one differentiable op (scalar): ``hem_bce_loss`` with ``ihg_ranking_loss`` as its loss launch and no labels.
+    The batch rows are ``positives`` positives followed by the ``k`` negatives of each (``collate_fn``'s layout); every other argument as in ``hem_bce_loss``."""
+    objective = ranking_objective(int(items.shape[0]), positives, kind)
+    return _hem_loss('hem_ranking_loss', layers, rows, items, None, objective, bias, lam, item_row_offset, holder, rows_upper, cosine)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2309,6 +2342,33 @@ class _BceWithLogits(torch.autograd.Function):
 def bce_with_logits(scores: Tensor, labels: Tensor) -> Tensor:
     """``nn.BCEWithLogitsLoss()(scores, labels)`` with its gradient from the one launch of ``ihg_bce_with_logits``."""
     return _BceWithLogits.apply(scores, labels)
+
+
+class _RankingLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores: Tensor, positives: int, kind: int) -> Tensor:
+        lib = _lib.load()
+        scores = _gpu(scores.detach(), 'scores').to(torch.float32).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=scores.device)
+        dscores = torch.empty_like(scores)
+        with profiler.kernel('ranking_loss', int(scores.numel()), 1):
+            _lib.check(lib.ihg_ranking_loss(_ptr(scores), positives, int(scores.numel()) // positives - 1, kind, _ptr(loss), _ptr(dscores), _stream()), 'ihg_ranking_loss')
+        ctx.save_for_backward(dscores)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss: Tensor):
+        return ctx.saved_tensors[0] * grad_loss, None, None
+
+
+def ranking_loss(scores: Tensor, positives: int, kind) -> Tensor:
+    """The BPR (``kind='bpr'``) or sampled-softmax (``'softmax'``) loss of ``scores`` ``[P (1 + k)]`` - ``positives = P`` positives followed by the ``k`` negatives of
+    each, ``collate_fn``'s layout - with its gradient from the one launch of ``ihg_ranking_loss``: the sibling of ``bce_with_logits`` where the fused tail
+    (``hem_ranking_loss``) does not apply."""
+    if scores.dim() != 1:
+        raise ValueError(f'ranking_loss takes the scores of a batch as a vector, got {tuple(scores.shape)}')
+    positives, code = ranking_objective(int(scores.shape[0]), positives, kind)
+    return _RankingLoss.apply(scores, positives, code)
 
 
 class _GatherRows(torch.autograd.Function):

@@ -437,6 +437,15 @@ int ihg_hem_score_bwd(const float* const* layers, int32_t n_layers, int64_t ld, 
                       const int64_t* rows, const float* dscores, float grad_scale, float lambda_muq,
                       float* rowgrad, int64_t ld_rowgrad, int64_t batch, ihg_stream_t stream);
 int ihg_bce_with_logits(const float* scores, const float* labels, int64_t n, float* loss, float* dscores, ihg_stream_t stream);
+/* Ranking losses (not in the reference, whose only objective is the BCE above) over scores [positives * (1 + k)] laid out as the batches are: the positives first, then
+ * the k negatives of positive p at positives + p * k ..; loss and dscores [positives * (1 + k)] = d loss / d scores in one launch, no atomics, every sum in a fixed order
+ * (bitwise repeatable).  A negative that equals its positive is a group member like any other.
+ *   IHG_LOSS_BPR      mean over the positives * k pairs of softplus(s_pj - s_p)
+ *   IHG_LOSS_SOFTMAX  mean over the positives of -log softmax(s_p, s_p1 .. s_pk)[0]: the positive against its own k negatives
+ * Any positives >= 1 and k >= 1 with positives * (1 + k) <= INT32_MAX. */
+#define IHG_LOSS_BPR 1
+#define IHG_LOSS_SOFTMAX 2
+int ihg_ranking_loss(const float* scores, int64_t positives, int32_t k, int32_t kind, float* loss, float* dscores, ihg_stream_t stream);
 int64_t ihg_batch_scatter_workspace_bytes(int64_t n_rows);      /* 0, or -1 if n_rows > ihg_batch_scatter_max_rows() (caller scatters in row chunks) */
 int32_t ihg_batch_scatter_max_rows(void);                        /* 32768: rows of one ihg_batch_scatter_add / ihg_batch_combine launch (its id list lives in LDS: <= 16384 rows in 64 KiB,
                                                                     beyond that - the union of the ranks' batches under the cotangent exchange - a 128 KiB instance) */

@@ -1,0 +1,355 @@
+"""GPU: the ranking losses through the model (``RawGnn.ranking_loss`` over the fused batch tail, ``ops.ranking_loss`` on the module path, the compact layout, tables read
+in place, the recorded step, two ranks, the driver), case by case as ``tests/test_cosine_head.py`` holds the cosine head.
+
+Bars: RTOL = 1e-5 of the reference tensor's largest magnitude and 2e-6 on the loss - what ``tests/test_gpu_parity.py`` holds the fused BCE step to against its module
+path (``test_fused_bce_tail_equals_unfused_path``): the two routes differ in nothing but ``d loss / d scores``; RTOL_SUM = 2e-6 where two of our own paths differ
+by summation order only."""
+import functools
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import loss_reference as R
+from conftest import REPO
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-5
+RTOL_SUM = 2e-6
+KINDS = ('bpr', 'softmax')
+
+
+def dev():
+    return torch.device('cuda:0')
+
+
+def rel(a, b):
+    a, b = (t.detach().cpu().double().numpy() if torch.is_tensor(t) else np.asarray(t, np.float64) for t in (a, b))
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+class setting:
+    """``Gs.Prediction.use_cosine_similarity`` and ``Gs.Training.loss`` for the block, put back after it."""
+
+    def __init__(self, cosine=False, loss='bce'):
+        self.new = (bool(cosine), loss)
+
+    def __enter__(self):
+        from ihgnn_amd.Helpers.GlobalSettings import Gs
+        self.old = (Gs.Prediction.use_cosine_similarity, Gs.Training.loss)
+        Gs.Prediction.use_cosine_similarity, Gs.Training.loss = self.new
+
+    def __exit__(self, *exc):
+        from ihgnn_amd.Helpers.GlobalSettings import Gs
+        Gs.Prediction.use_cosine_similarity, Gs.Training.loss = self.old
+
+
+def layer_type(gnn):
+    from ihgnn_amd.Models import GATLayer, GCNLayer, HGCNLayer, IHGNNLayer
+    return {'ihgnn': IHGNNLayer, 'hgcn': HGCNLayer, 'gcn': GCNLayer, 'gat': GATLayer}[gnn]
+
+
+def build_model(ds, gnn, d=32, L=2):
+    from ihgnn_amd.Models import HemPredictionLayer, RawGnn
+    return RawGnn(dev(), ds, d, layer_type(gnn), L, 3 if gnn == 'ihgnn' else 1, False, HemPredictionLayer, 0.5).to(dev())
+
+
+@functools.lru_cache(maxsize=None)
+def workload():
+    from ihgnn_amd import synth
+    return synth.draw(60, 20, 80, 25, 500)
+
+
+def dataset_of(w, triples=None, pairwise=False):
+    from ihgnn_amd.Dataset import GraphDataset
+    from ihgnn_amd.Helpers.Graph import Pps2DGraph, PpsHyperGraph
+    return GraphDataset.from_arrays(w.user_count, w.query_count, w.item_count, w.vocab_size, w.bag_words, w.bag_offsets, w.triples if triples is None else triples,
+                                    graph_type=Pps2DGraph if pairwise else PpsHyperGraph, device=dev())
+
+
+def step_gradients(m, batch, positives, kind=None):
+    m.zero_grad(set_to_none=True)
+    loss = m.ranking_loss(*batch, positives, kind)
+    loss.backward()
+    return loss.detach().clone(), {k: p.grad.detach().clone() for k, p in m.named_parameters()}
+
+
+def module_path_gradients(m, batch, positives, kind, float64):
+    """The module path: ``ops.ranking_loss`` on the model's scores, or (``float64``) the torch composition of the formulas in float64 on those scores."""
+    from ihgnn_amd import ops
+    m.zero_grad(set_to_none=True)
+    scores = m(*batch)
+    loss = R.torch_loss(kind, scores.double(), positives) if float64 else ops.ranking_loss(scores, positives, kind)
+    loss.backward()
+    return loss.detach().clone(), {k: p.grad.detach().clone() for k, p in m.named_parameters()}
+
+
+# ---------------------------------------------------------------------------------------------
+# routes agree
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('cosine', [False, True])
+@pytest.mark.parametrize('gnn', ['ihgnn', 'hgcn', 'gcn', 'gat'])
+def test_fused_tail_equals_the_module_path(gnn, cosine, kind):
+    """``model.ranking_loss`` against ``ops.ranking_loss(model(u, q, i), P, kind)`` and against the float64 composition of the formulas on the module path's scores:
+    the loss to 2e-6, every parameter gradient to RTOL."""
+    from ihgnn_amd import profiler
+    ds = dataset_of(workload(), pairwise=gnn in ('gcn', 'gat'))
+    u, q, i, _ = next(iter(ds.sample_batches(40, 1, seed=9)))
+    batch, P = (u, q, i), 40
+    torch.manual_seed(11)
+    with setting(cosine=cosine):
+        m = build_model(ds, gnn)
+        assert m.supports_fused_tail()
+        profiler.start()
+        try:
+            l0, g0 = step_gradients(m, batch, P, kind)
+        finally:
+            profiler.stop()
+        assert ('hem_cosine_fwd' if cosine else 'hem_score_fwd') in profiler.summary()
+        l1, g1 = module_path_gradients(m, batch, P, kind, False)
+        l2, g2 = module_path_gradients(m, batch, P, kind, True)
+        with setting(cosine=cosine, loss=kind):                                  # kind=None reads the setting at the call: the same step
+            l3, g3 = step_gradients(m, batch, P)
+        with pytest.raises(ValueError, match='bce_loss'):                        # (the setting is 'bce' again)
+            m.ranking_loss(*batch, P)
+    print(f'{gnn} cosine={cosine} {kind}: loss {l0.item():.7f} module path {l1.item():.7f} float64 {l2.item():.7f}')
+    assert abs(l0.item() - l1.item()) <= 2e-6 * abs(l1.item()) and abs(l0.item() - l2.item()) <= 2e-6 * abs(l2.item())
+    assert torch.equal(l0, l3)
+    for k in g0:
+        assert torch.equal(g0[k], g3[k]), k
+        assert rel(g0[k], g1[k]) <= RTOL and rel(g0[k], g2[k]) <= RTOL, (k, rel(g0[k], g1[k]), rel(g0[k], g2[k]))
+
+
+# ---------------------------------------------------------------------------------------------
+# compact layout, tables in place
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('cosine', [False, True])
+def test_compact_layout_with_isolated_batch_nodes(kind, cosine, monkeypatch):
+    """Two thirds of every node type in no hyperedge; the batch names isolated users, queries and items.  Under ``IHG_COMPACT_NODES=1`` loss and every gradient equal the
+    every-node-a-row layout's to RTOL_SUM and the float64 composition on the plain layout's module path to RTOL."""
+    from ihgnn_amd import layout as layout_mod
+    w = workload()
+    g = np.random.default_rng(4)
+    counts = (w.user_count, w.query_count, w.item_count)
+    live = [g.choice(n, n // 3, replace=False) for n in counts]
+    triples = np.stack([g.choice(live[k], 400) for k in range(3)], 1)
+    P, k = 30, 2
+    pu, pq = (g.integers(0, n, P) for n in counts[:2])
+    u, q = (torch.from_numpy(np.concatenate([p, np.repeat(p, k)])) for p in (pu, pq))
+    i = torch.from_numpy(g.integers(0, counts[2], P * (1 + k)))
+    for ids, alive in zip((u, q, i), live):
+        assert len(set(ids.tolist()) - set(alive.tolist())) >= 1 and len(set(ids.tolist()) & set(alive.tolist())) >= 1
+    batch = tuple(t.to(dev()) for t in (u, q, i))
+    results, models = {}, {}
+    with setting(cosine=cosine):
+        for compact in (False, True):
+            monkeypatch.setattr(layout_mod, 'COMPACT_NODES', '1' if compact else '0')
+            ds = dataset_of(w, triples)
+            assert bool(getattr(ds.hypergraph.layout, 'compact', False)) == compact
+            torch.manual_seed(7)
+            models[compact] = build_model(ds, 'ihgnn')
+        models[True].load_state_dict(models[False].state_dict())
+        for compact in (False, True):
+            results[compact] = step_gradients(models[compact], batch, P, kind)
+        with torch.no_grad():                                                    # no gradient wanted: the plain tail on the public matrices, the same loss
+            quiet = models[True].ranking_loss(*batch, P, kind)
+        l64, g64 = module_path_gradients(models[False], batch, P, kind, True)
+    (l0, g0), (l1, g1) = results[False], results[True]
+    assert abs(l1.item() - l0.item()) <= RTOL_SUM * abs(l0.item()) and abs(l1.item() - l64.item()) <= 2e-6 * abs(l64.item())
+    assert abs(quiet.item() - l0.item()) <= RTOL_SUM * abs(l0.item())
+    for name in g0:
+        assert rel(g1[name], g0[name]) <= RTOL_SUM and rel(g1[name], g64[name]) <= RTOL and rel(g0[name], g64[name]) <= RTOL, name
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('cosine', [False, True])
+def test_tables_in_place_and_batch_rows_only(kind, cosine):
+    """One step with the embedding tables read in place against X0 assembled (``IHG_NODE_TABLES`` 1 / 0) and with the last layer evaluated at the batch rows only against
+    everywhere: loss and every gradient to RTOL_SUM."""
+    from ihgnn_amd import ops
+    ds = dataset_of(workload())
+    u, q, i, _ = next(iter(ds.sample_batches(40, 1, seed=9)))
+    torch.manual_seed(11)
+    runs = {}
+    with setting(cosine=cosine):
+        m = build_model(ds, 'ihgnn', d=64)
+        for tables, rows_only in ((True, True), (False, True), (True, False)):
+            ops.NODE_TABLES, m.batch_rows_only_last_layer = tables, rows_only
+            try:
+                runs[tables, rows_only] = step_gradients(m, (u, q, i), 40, kind)
+            finally:
+                ops.NODE_TABLES, m.batch_rows_only_last_layer = True, True
+    l0, g0 = runs[True, True]
+    for other in ((False, True), (True, False)):
+        l1, g1 = runs[other]
+        assert abs(l1.item() - l0.item()) <= RTOL_SUM * abs(l0.item())
+        for name in g0:
+            assert rel(g1[name], g0[name]) <= RTOL_SUM, (other, name, rel(g1[name], g0[name]))
+
+
+# ---------------------------------------------------------------------------------------------
+# recorded step
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('kind', KINDS)
+def test_recorded_step_equals_the_eager_step_and_notices_a_flip(kind):
+    """Four replays of a step recorded under the ranking loss equal four eager steps bit for bit, in the loss and in every parameter; the loss is baked into the
+    recording - after ``Gs.Training.loss`` flips, ``stale()`` says so and ``step()`` refuses."""
+    from ihgnn_amd import synth
+    from ihgnn_amd.captured_step import CapturedTrainingStep
+    from ihgnn_amd.Helpers.GlobalSettings import Gs
+    from ihgnn_amd.optim import Adam
+    ds = dataset_of(synth.draw(300, 40, 200, 50, 4000, seed=21, distribution='powerlaw'))
+    batches = list(ds.sample_batches(100, 4, seed=5))
+    kept_step = []
+
+    def run(recorded):
+        torch.manual_seed(7)
+        m = build_model(ds, 'ihgnn', d=64)
+        opt = Adam(m.parameters(), 1e-3, weight_decay=0)
+        step = CapturedTrainingStep(m, opt, batches[0][0].shape[0], warmup_batch=batches[0], positives=100) if recorded else None
+        losses = []
+        for u, q, i, y in batches:
+            if recorded:
+                losses.append(step.step(u, q, i, y, positives=100).clone())
+            else:
+                loss = m.ranking_loss(u, q, i, 100)
+                loss.backward(); opt.step(); opt.zero_grad()
+                losses.append(loss.detach().clone())
+        kept_step.append(step)
+        return losses, {k: v.clone() for k, v in m.state_dict().items()}
+
+    with setting(loss=kind):
+        l0, p0 = run(False)
+        l1, p1 = run(True)
+        step = kept_step[-1]
+        assert not step.stale() and not step.stale(full=True)
+        with pytest.raises(ValueError, match='positives'):
+            step.step(*batches[0], positives=50)
+        with pytest.raises(ValueError, match='positives'):
+            CapturedTrainingStep(step.model, step.optimizer, 1100)
+        Gs.Training.loss = 'bce'
+        assert step.stale() and step.stale(full=True)
+        with pytest.raises(RuntimeError, match='baked into the recording'):
+            step.step(*batches[0])
+        Gs.Training.loss = 'softmax' if kind == 'bpr' else 'bpr'
+        assert step.stale()
+        Gs.Training.loss = kind
+        assert not step.stale()
+        # the BCE step on the same model and batches is a different step: the comparison below is not vacuous
+        torch.manual_seed(7)
+        other = build_model(ds, 'ihgnn', d=64).bce_loss(*batches[0]).item()
+    print(f'{kind}: eager losses {[x.item() for x in l0]}, replayed {[x.item() for x in l1]}')
+    for a, b in zip(l0, l1):
+        assert torch.equal(a, b)
+    for name in p0:
+        assert torch.equal(p1[name], p0[name]), name
+    assert abs(other - l0[0].item()) > 1e-3 * abs(l0[0].item())
+
+
+# ---------------------------------------------------------------------------------------------
+# the training loop
+# ---------------------------------------------------------------------------------------------
+def test_training_loop_takes_the_ranking_step(monkeypatch):
+    """``train_and_get_avg_loss`` under ``Gs.Training.loss = 'bpr'``: the fused step where the fused tail runs (``model.ranking_loss`` is called, ``bce_loss`` is not), the
+    module path with ``ops.ranking_loss`` where it does not, and the same average loss either way to 1e-4."""
+    from torch.utils.data import DataLoader
+    from ihgnn_amd import ops
+    from ihgnn_amd.Dataset import GraphDataset
+    from ihgnn_amd.Helpers.ProcessController import ProcessController
+    from ihgnn_amd.Helpers.TrainTestHelper import train_and_get_avg_loss
+    from ihgnn_amd.Models import RawGnn
+    from ihgnn_amd.optim import Adam
+    import random
+    ds = dataset_of(workload())
+    calls = {'ranking': 0, 'bce': 0, 'op': 0}
+    real_ranking, real_op = RawGnn.ranking_loss, ops.ranking_loss
+    monkeypatch.setattr(RawGnn, 'ranking_loss', lambda self, *a, **k: (calls.__setitem__('ranking', calls['ranking'] + 1), real_ranking(self, *a, **k))[1])
+    monkeypatch.setattr(RawGnn, 'bce_loss', lambda self, *a, **k: calls.__setitem__('bce', calls['bce'] + 1))
+    monkeypatch.setattr(ops, 'ranking_loss', lambda *a, **k: (calls.__setitem__('op', calls['op'] + 1), real_op(*a, **k))[1])
+    averages = []
+    with setting(loss='bpr'):
+        for fused in (True, False):
+            random.seed(3); torch.manual_seed(3)
+            m = build_model(ds, 'ihgnn')
+            if not fused:
+                monkeypatch.setattr(m, 'supports_fused_tail', lambda: False, raising=False)
+            opt = Adam(m.parameters(), 1e-3, weight_decay=0)
+            loader = DataLoader(ds, 100, shuffle=False, collate_fn=GraphDataset.collate_fn)
+            pc = ProcessController(1, 1, 10, 10, None, None)
+            next(iter(pc))
+            avg, _ = train_and_get_avg_loss(m, opt, torch.nn.BCEWithLogitsLoss(), ds, loader, pc, dev(), record_step='off')
+            averages.append(avg)
+            assert calls['bce'] == 0 and len(loader) >= 4 and (calls['ranking'] == len(loader) and calls['op'] == 0 if fused else calls['op'] == len(loader)), calls
+            calls.update(ranking=0, op=0)
+    # (not a parity bar - the routes are held to one in test_fused_tail_equals_the_module_path: the same batches through both routes train alike)
+    assert np.isfinite(averages).all() and abs(averages[0] - averages[1]) <= 1e-4 * abs(averages[1]), averages
+
+
+def test_forty_bpr_steps_raise_the_margin():
+    """A sanity check of sign and grouping, not a quality claim: forty ``bpr`` steps at lr 1e-2 on a 200-interaction graph raise the mean of ``s_p - s_pj`` over a fixed
+    held batch."""
+    from ihgnn_amd import synth
+    from ihgnn_amd.optim import Adam
+    ds = dataset_of(synth.draw(40, 12, 50, 20, 200, seed=2))
+    held = next(iter(ds.sample_batches(50, 1, seed=77)))[:3]
+    torch.manual_seed(2)
+    m = build_model(ds, 'ihgnn')
+    opt = Adam(m.parameters(), 1e-2, weight_decay=0)
+
+    def margin():
+        with torch.no_grad():
+            s = m(*held)
+        return float((s[:50, None] - s[50:].view(50, -1)).mean())
+
+    before = margin()
+    for u, q, i, _ in ds.sample_batches(50, 40, seed=1):
+        loss = m.ranking_loss(u, q, i, 50, 'bpr')
+        loss.backward(); opt.step(); opt.zero_grad()
+    after = margin()
+    print(f'mean margin of the held batch {before:.4f} -> {after:.4f}')
+    assert np.isfinite(after) and after > before
+
+
+# ---------------------------------------------------------------------------------------------
+# two ranks, the driver (child processes, each under its own time limit)
+# ---------------------------------------------------------------------------------------------
+def test_two_ranks_exchange_the_bpr_cotangents():
+    """``tools/two_rank_check.py --sync cotangent --loss bpr`` as a child process: two replicas on GPU 0 over gloo, each with its own groups, exchange the row gradients,
+    stay bitwise identical and equal the one-rank run on the union batch [positives of rank 0; positives of rank 1; negatives of rank 0; negatives of rank 1] by
+    the tool's own bar."""
+    r = subprocess.run([sys.executable, 'tools/two_rank_check.py', '--ranks', '2', '--sync', 'cotangent', '--backend', 'gloo', '--device', '0', '--loss', 'bpr',
+                        '--child_timeout', '300'], cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and 'OK' in r.stdout and 'DIVERGED' not in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize('loader', ['device_sampling', 'dataloader'])
+def test_driver_trains_on_the_softmax_loss(loader, tmp_path):
+    """``python -m ihgnn_amd.Main ... --loss softmax --logged_negatives 2`` in a child process, batches drawn on the device or by the ``DataLoader``: two epochs on a tiny
+    corpus with logged negatives; the log names the loss, the average loss is finite and decreases, metrics are written."""
+    from ihgnn_amd import synth
+    w = synth.draw(60, 20, 80, 25, 2000, seed=4, eval_logs=30)
+    g = np.random.default_rng(6)
+    rows = [(u, q, [i] + [int(x) for x in g.integers(0, w.item_count, 2)], [1, 0, 0]) for u, q, i in w.triples.tolist()]
+    synth.write_files(w, str(tmp_path / 'Data' / 'Synth' / 'Tiny'), train_rows=rows)
+    command = [sys.executable, '-m', 'ihgnn_amd.Main', '--ds', 'Synth/Tiny/', '--gnn', 'IHGNN', '--gnns', '2', '--fo', '3', '--emb', '32', '--seed', '3', '--loss', 'softmax',
+               '--logged_negatives', '2', '--ec', '2', '--est', '1', '--etf', '1', '--sm'] + (['--device_sampling'] if loader == 'device_sampling' else [])
+    r = subprocess.run(command, cwd=str(tmp_path), capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get('PYTHONPATH', '')))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = tmp_path / 'Results' / 'Synth-Tiny-RawGnn-2IHGNNLayer-O3-emb32'
+    logs = [f for f in os.listdir(out) if f.endswith('_train_log.txt')]
+    metrics = [f for f in os.listdir(out) if f.endswith('_metrics.txt')]
+    assert len(logs) == 1 and len(metrics) == 1
+    log = open(out / logs[0], encoding='utf-8').read()
+    assert '| loss softmax |' in log and 'negatives 10/2' in log
+    losses = [float(x) for x in re.findall(r'average loss \S*?(\d+\.\d+)', log)]
+    assert len(losses) == 2 and np.isfinite(losses).all() and losses[1] < losses[0], losses
+    text = open(out / metrics[0], encoding='utf-8').read()
+    assert 'Epoch 1 Avg loss' in text and 'Epoch 2 Avg loss' in text and 'Best' in text

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """N ranks of the HIP model == 1 rank on the union batch, runnable on ONE GPU.
 
-    python tools/two_rank_check.py [--ranks 2] [--sync flat|bucketed|sharded|cotangent] [--device 0] [--backend gloo] [--cosine]
+    python tools/two_rank_check.py [--ranks 2] [--sync flat|bucketed|sharded|cotangent] [--device 0] [--backend gloo] [--cosine] [--loss bpr|softmax]
 
 The parent starts the rank processes before touching the GPU (as bench.py does).  Every rank builds the same RawGnn replica on
 GPU `--device` (RCCL refuses two ranks on one GPU, so the single-GPU form uses gloo; on a multi-GPU node pass `--backend nccl
@@ -34,6 +34,10 @@ def main():
                     'replicas are compared with each other: bitwise, under the cotangent exchange')
     ap.add_argument('--batch', type=int, default=64, help='batch rows per rank (8 ranks x 700: the union of the ranks\' 3 B batch rows exceeds 16,384 - the wide instance of the combine kernel)')
     ap.add_argument('--cosine', action='store_true', help='the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity): its row gradients travel in the same layout')
+    ap.add_argument('--loss', default='bce', choices=('bce', 'bpr', 'softmax'), help='a ranking loss (RawGnn.ranking_loss): a rank\'s batch is batch / (1 + negatives) positives followed by the '
+                    'negatives of each, and the one-rank run sees the union as [positives of rank 0; positives of rank 1; ...; negatives of rank 0; negatives of rank 1; ...] - every group\'s rows contiguous')
+    ap.add_argument('--negatives', type=int, default=3, help='negatives per positive under --loss bpr | softmax (batch must be a multiple of 1 + negatives)')
+    ap.add_argument('--child_timeout', type=float, default=None, help='seconds each rank process may take (default: no limit); a rank past it is killed, with the others, and the check fails')
     args = ap.parse_args()
     if 'WORLD_SIZE' not in os.environ:
         import socket
@@ -44,7 +48,15 @@ def main():
                                  env=dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(args.ranks), MASTER_ADDR='127.0.0.1',
                                           MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0',
                                           **({'IHG_FORCE_COLLECTIVES': '1'} if args.ranks == 1 else {}))) for r in range(args.ranks)]
-        codes = [k.wait() for k in kids]
+        codes = []
+        for k in kids:
+            try:
+                codes.append(k.wait(timeout=args.child_timeout))
+            except subprocess.TimeoutExpired:
+                for other in kids:
+                    other.kill()
+                print(f'two_rank_check: a rank process ran past {args.child_timeout} s', flush=True)
+                raise SystemExit(124)
         raise SystemExit(max(abs(c) for c in codes))
 
     import numpy as np
@@ -89,10 +101,21 @@ def main():
     opt = sync.optimizer(1e-3) if sync.owns_optimizer else Adam(model.parameters(), 1e-3)
     rows = ihg_dist.shard_range(B, rank, world)
     sl = slice(rows.start, rows.stop)
+    ranking = args.loss != 'bce'
+    if ranking:
+        # the union batch is P positives then P k negatives; this rank owns positives [rank P_r, (rank + 1) P_r) and their negatives
+        assert args.batch % (1 + args.negatives) == 0, 'batch must be a multiple of 1 + negatives'
+        p_r, k = args.batch // (1 + args.negatives), args.negatives
+        sl = torch.cat([torch.arange(rank * p_r, (rank + 1) * p_r), world * p_r + torch.arange(rank * p_r * k, (rank + 1) * p_r * k)]).to(dev)
+
+    def loss_of(m, sel, positives, cotangent_sync=None):
+        if ranking:
+            return m.ranking_loss(u[sel], q[sel], i[sel], positives, args.loss, cotangent_sync=cotangent_sync)
+        return m.bce_loss(u[sel], q[sel], i[sel], y[sel], cotangent_sync=cotangent_sync) if cotangent_sync is not None else m.bce_loss(u[sel], q[sel], i[sel], y[sel])
     assert world > 1 or sync.distributed, 'a one-rank run must be forced through the collectives (IHG_FORCE_COLLECTIVES=1)'
     cotangent = getattr(sync, 'mode', None) == 'cotangent'  # the ranks exchange the batch rows' cotangents inside the backward; no dense gradient exchange
     for step in range(args.steps):
-        (model.bce_loss(u[sl], q[sl], i[sl], y[sl], cotangent_sync=sync) if cotangent else model.bce_loss(u[sl], q[sl], i[sl], y[sl])).backward()
+        loss_of(model, sl, p_r if ranking else None, sync if cotangent else None).backward()
         if cotangent:
             assert sync.sent_bytes == 3 * (rows.stop - rows.start) * (8 + 4 * (args.dim * 3 + 4)), sync.sent_bytes
         sync.average_gradients()
@@ -125,7 +148,7 @@ def main():
         alone = replica()
         opt1 = Adam(alone.parameters(), 1e-3)
         for _ in range(2):
-            alone.bce_loss(u, q, i, y).backward()
+            loss_of(alone, slice(0, B), world * p_r if ranking else None).backward()
             opt1.step(); opt1.zero_grad()
         worst = 0.0
         for (name, a), (_, b) in zip(model.state_dict().items(), alone.state_dict().items()):
