@@ -301,7 +301,8 @@ class GraphDataset(Dataset):
         """One epoch of training batches produced ON THE DEVICE: the positives are a device-side permutation of the hyperedges
         (this rank's share of it when ``world_size`` > 1), the ``rand_neg_sample_size`` negatives of every positive come from
         ``ihg_sample_negatives`` (distinct within a sample, uniform over the catalogue, may hit the positive - the semantics of
-        ``random.sample(range(I), k)``, ``Dataset.py:107-109``).  Yields the 8-tuple of ``collate_fn`` (positives then negatives;
+        ``random.sample(range(I), k)``, ``Dataset.py:107-109``; more than ``SAMPLE_MAX`` of them - a pool of candidates for hard negatives - from
+        ``ihg_sample_pool``, the same stream continued).  Yields the 8-tuple of ``collate_fn`` (positives then negatives;
         users, queries, items, flags) with no host -> device copy and no host-side sampling per step.
 
         With ``nonrand_neg_sample_size`` > 0 a batch is ONE launch, ``ihg_device_batch``: it gathers the positives, draws every
@@ -358,8 +359,9 @@ class GraphDataset(Dataset):
             lo = hi
             n = int(pos.shape[0])
             neg_items = torch.empty(n, k, dtype=torch.int64, device=dev)
-            _lib.check(lib.ihg_sample_negatives(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, ctypes.c_void_p(neg_items.data_ptr()), stream),
-                       'ihg_sample_negatives')
+            # (beyond SAMPLE_MAX draws - a pool of candidates, --hard_negatives - the same stream from ihg_sample_pool; up to SAMPLE_MAX the launch batches always had)
+            draw, name = (lib.ihg_sample_pool, 'ihg_sample_pool') if k > self.SAMPLE_MAX else (lib.ihg_sample_negatives, 'ihg_sample_negatives')
+            _lib.check(draw(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, ctypes.c_void_p(neg_items.data_ptr()), stream), name)
             ones = torch.ones(n, dtype=torch.int64, device=dev)
             yield (pos[:, 0], pos[:, 1], pos[:, 2], ones, pos[:, 0].repeat_interleave(k), pos[:, 1].repeat_interleave(k),
                    neg_items.reshape(-1), torch.zeros(n * k, dtype=torch.int64, device=dev))

@@ -57,6 +57,9 @@ _FLAGS = (
     # not in the reference, which trains on nn.BCEWithLogitsLoss only (Main.py:191)
     ('loss', ('--loss',), str, 'bce', 'training objective: bce (the reference\'s point-wise loss) | bpr (pairwise: every positive against each of its negatives) | '
                                       'softmax (the positive against its own negatives; Gs.Training.loss)'),
+    # not in the reference, whose negatives are uniform draws (and a pair's logged ones): dynamic negative sampling
+    ('hard_negatives', ('--hard_negatives',), int, 0, 'hard negatives: draw a pool of M random candidates per positive and train on the Gs.random_negative_sample_size of them that the '
+                                                      'current model scores highest (Gs.Training.negative_pool; 0 = off; needs random_negative_sample_size < M <= 256, no --logged_negatives)'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '

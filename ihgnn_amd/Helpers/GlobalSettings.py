@@ -44,6 +44,7 @@ class Gs:
 
     class Training:
         loss = 'bce'                     # not in the reference (whose only objective is nn.BCEWithLogitsLoss over a positive and its negatives): 'bpr' | 'softmax' (--loss) train on a ranking loss of every positive against its own negatives
+        negative_pool = 0                # not in the reference: M > 0 (--hard_negatives M) draws a pool of M random candidates per positive and trains on the random_negative_sample_size of them that the model scores highest; 0 = off
 
     class Evaluation:
         extra_cutoffs = ()               # not in the reference (which reports @10 only): further cutoffs K in 11..128 (--cutoffs), HR / NDCG / MAP @K beside the @10 triple

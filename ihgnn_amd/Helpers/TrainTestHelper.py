@@ -197,7 +197,11 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
     without measuring.  A model the recording refuses (a parameter without gradient) trains eagerly, with one log line.
 
     ``Gs.Training.loss`` other than ``'bce'`` (``--loss bpr | softmax``): a step is ``model.ranking_loss`` over the batch's groups (every positive with its own negatives)
-    where the fused batch tail runs, ``ops.ranking_loss`` on the model's scores where it does not; ``loss_function`` and the labels are then not used."""
+    where the fused batch tail runs, ``ops.ranking_loss`` on the model's scores where it does not; ``loss_function`` and the labels are then not used.
+
+    ``Gs.Training.negative_pool`` = M > 0 (``--hard_negatives M``; the loader draws M candidates per positive): a step is ``model.hard_negative_loss`` - the objective
+    ``Gs.Training.loss`` names, ``'bce'`` included, over every positive and the ``Gs.random_negative_sample_size`` candidates of its pool that score highest - where the
+    fused tail runs, ``ops.hard_negative_loss`` on the model's scores where it does not; the labels are not used either."""
     from ..Models.Srrl import Srrl
     if isinstance(model, Srrl):
         if grad_sync is not None or _record_mode(record_step) == 'on':
@@ -224,7 +228,12 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
         users, queries, items = torch.cat([p_u, n_u]), torch.cat([p_q, n_q]), torch.cat([p_i, n_i])
         flags = torch.cat([p_f, n_f]).float()
         kind = Gs.Training.loss                             # read per step, as the model reads its head
-        ranking = kind != 'bce'
+        pool = Gs.Training.negative_pool                    # (the loader drew this many candidates per positive; the step keeps the best random_negative_sample_size)
+        keep = Gs.random_negative_sample_size
+        ranking = kind != 'bce' or bool(pool)               # a step over groups: no labels, no loss_function
+        if pool and len(n_u) != pool * len(p_u):
+            raise ValueError(f'Gs.Training.negative_pool = {pool}, but the loader drew {len(n_u)} negatives for {len(p_u)} positives: build the dataset with '
+                             'random_negative_sample_size = the pool size (Main does)')
         if ranking:
             fused = getattr(model, 'supports_fused_tail', None) and model.supports_fused_tail()
         else:
@@ -260,7 +269,12 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
         cotangent = getattr(grad_sync, 'mode', None) == 'cotangent'
         if cotangent and not fused:
             raise RuntimeError('--grad_sync cotangent exchanges the fused batch tail\'s row gradients: it needs the HIP model and a plain BCEWithLogitsLoss (use bucketed / sharded)')
-        if ranking and fused:
+        if pool and fused:
+            loss = model.hard_negative_loss(users, queries, items, positives=len(p_u), keep=keep, kind=kind, cotangent_sync=grad_sync if cotangent else None)
+        elif pool:
+            from .. import ops
+            loss = ops.hard_negative_loss(model(users, queries, items), len(p_u), keep, kind)
+        elif ranking and fused:
             loss = model.ranking_loss(users, queries, items, positives=len(p_u), kind=kind, cotangent_sync=grad_sync if cotangent else None)
         elif ranking:
             from .. import ops

@@ -55,12 +55,25 @@ def apply_evaluation_settings(args) -> None:
 
 
 def apply_training_settings(args) -> None:
-    """``--loss`` -> ``Gs.Training.loss``, assigned both ways like the head above (not in the reference, which trains on ``nn.BCEWithLogitsLoss`` only)."""
+    """``--loss`` -> ``Gs.Training.loss`` and ``--hard_negatives M`` -> ``Gs.Training.negative_pool``, assigned both ways like the head above (not in the reference, which
+    trains on ``nn.BCEWithLogitsLoss`` over uniform negatives only).  A pool needs ``Gs.random_negative_sample_size < M <= 256`` and no logged negatives (the pool is
+    random-only); called after ``apply_sampling_settings``."""
+    from . import _lib
     from .Helpers.ArgsParser import LOSSES
     loss = getattr(args, 'loss', 'bce') or 'bce'
     if loss not in LOSSES:
         raise ValueError(f'--loss: one of {", ".join(LOSSES)}, got {loss!r}')
+    pool = int(getattr(args, 'hard_negatives', 0) or 0)
+    if pool < 0:
+        raise ValueError(f'--hard_negatives takes a pool size >= 0 (0 = off), got {pool}')
+    if pool:
+        if not Gs.random_negative_sample_size < pool <= _lib.POOL_MAX:
+            raise ValueError(f'--hard_negatives {pool}: the pool must be larger than the {Gs.random_negative_sample_size} negatives kept of it '
+                             f'(Gs.random_negative_sample_size) and at most {_lib.POOL_MAX}')
+        if int(getattr(args, 'logged_negatives', 0) or 0) > 0 or Gs.non_random_negative_sample_size > 0:
+            raise ValueError('--hard_negatives draws its pool from the catalogue only: it does not go with --logged_negatives (Gs.non_random_negative_sample_size > 0)')
     Gs.Training.loss = loss
+    Gs.Training.negative_pool = pool
 
 
 def apply_sampling_settings(args) -> None:
@@ -87,6 +100,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise ValueError('--phase2 is the IHGNN layer\'s phase-2 attention; --model Srrl has no layers')
     if (getattr(args, 'loss', 'bce') or 'bce') != 'bce':
         raise NotImplementedError('--model Srrl trains its PS half on the BCE, as the reference does: --loss bpr / softmax have not been built for it')
+    if int(getattr(args, 'hard_negatives', 0) or 0) > 0:
+        raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --hard_negatives has not been built for it')
     if getattr(args, 'query_transform', Gsv.mean) == Gsv.gru:
         raise NotImplementedError('--model Srrl embeds its queries by the bag mean or the activation transform: --query_transform gru has not been built for it')
     widest = ops.cat_linear_max_width()
@@ -166,8 +181,16 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         IOHelper.quiet = True
     say = IOHelper.LogPrint if chief else (lambda *a, **k: None)
 
+    pool = Gs.Training.negative_pool
+    per_positive = pool or Gs.random_negative_sample_size + Gs.non_random_negative_sample_size      # negative rows a batch carries per positive
     say(f'device {device} | ranks {world} | batch {Gs.batch_size} | lr {Gs.learning_rate} | emb {Gs.embedding_size} | '
-        f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}')
+        f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}' +
+        (f' | hard negatives: the best {Gs.random_negative_sample_size} of a pool of {pool}' if pool else ''))
+    if pool:
+        from . import ops
+        if 3 * Gs.batch_size * (1 + pool) > ops.SCATTER_CHUNK_ROWS:
+            say(f'a batch of {Gs.batch_size} x (1 + {pool}) rows has {3 * Gs.batch_size * (1 + pool)} row gradients, beyond the {ops.SCATTER_CHUNK_ROWS} of one combine launch: '
+                'the step runs on the chunked scatter paths')
     say((f'model Srrl | dataset {dataset_name} | KG loss {Gs.Srrl.KG_loss} | uniform KG weights {Gs.Srrl.uni_weight} | ' if model_type is Srrl else
          f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | ') +
         f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
@@ -179,7 +202,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         fn_queries_multihot=os.path.join(data_dir, 'queries_multihot.txt'),
         fn_train_data=os.path.join(data_dir, 'train_data.csv'),
         graph_type=Pps2DGraph if layer_type in (GCNLayer, GATLayer) else PpsHyperGraph,
-        random_negative_sample_size=Gs.random_negative_sample_size,
+        random_negative_sample_size=pool or Gs.random_negative_sample_size,      # (a pool: the loaders draw M candidates per positive, the step keeps the best of them)
         non_random_negative_sample_size=Gs.non_random_negative_sample_size,
         device=device)
     if args.device_sampling:
@@ -212,7 +235,7 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         # sharded exchange owns it.
         mode = args.grad_sync
         if mode in ('auto', '', None):
-            batch_rows = Gs.batch_size * (1 + Gs.random_negative_sample_size + Gs.non_random_negative_sample_size)
+            batch_rows = Gs.batch_size * (1 + per_positive)
             mode = ihg_dist.choose_gradient_sync(4 * sum(p.numel() for p in model.parameters()), world, model.supports_fused_loss(loss_function),
                                                  ihg_dist.cotangent_bytes_per_rank(batch_rows, model.compute_width * (layer_count + 1)))
             say(f'gradient exchange: {mode}')

@@ -234,8 +234,23 @@ class RawGnn(nn.Module):
         objective = ops.ranking_objective(int(item_indices.shape[0]), positives, kind)
         return self._fused_loss(user_indices, query_indices, item_indices, None, objective, cotangent_sync)
 
+    def hard_negative_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, positives: int, keep: int, kind: Optional[str] = None,
+                           cotangent_sync=None, return_selected: bool = False):
+        """``ops.hard_negative_loss(self(u, q, i), positives, keep, kind)`` through the fused batch tail: the batch is ``positives`` positives followed by the ``M`` pool
+        candidates of each (the candidates of positive ``p`` at rows ``P + p M ..``: ``collate_fn``'s layout with M in place of k), the ``keep`` candidates of a pool that
+        the model scores highest are the positive's negatives, and the loss is ``bce_loss``'s (``'bce'``: labels 1 / 0) or ``ranking_loss``'s (``'bpr'`` / ``'softmax'``)
+        over the positive and those.  The pool rows are ordinary batch rows; the rows of the other candidates get zero row gradients.  ``kind=None`` reads
+        ``Gs.Training.loss`` at every call.  ``return_selected``: also the ``[P, keep]`` pool positions of the negatives, best first (int64, detached).
+        ``cotangent_sync``: as in ``bce_loss``."""
+        from .. import ops
+        kind = Gs.Training.loss if kind is None else kind
+        objective = ops.hard_negative_objective(int(item_indices.shape[0]), positives, keep, kind)
+        loss = self._fused_loss(user_indices, query_indices, item_indices, None, objective, cotangent_sync)
+        return (loss, objective.selected.to(torch.int64)) if return_selected else loss
+
     def _fused_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, labels: Optional[Tensor], objective, cotangent_sync) -> Tensor:
-        """The training loss through the fused batch tail: the BCE over ``labels`` (``objective`` None) or a ranking loss (``ops.ranking_objective``'s pair)."""
+        """The training loss through the fused batch tail: the BCE over ``labels`` (``objective`` None), a ranking loss (``ops.ranking_objective``'s pair) or the
+        hard-negative objective (``ops.hard_negative_objective``'s)."""
         from .. import ops
         ds, head = self.dataset, self.prediction_layer
         cosine = bool(Gs.Prediction.use_cosine_similarity)       # read at every call, as the reference's head does (PredictionLayers.py:38)
@@ -250,6 +265,8 @@ class RawGnn(nn.Module):
         if compact is not None and holder is None:
             # (no gradient wanted: the public matrices, the plain tail)
             scores = ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, cosine=cosine)
+            if isinstance(objective, ops.HardNegatives):
+                return ops._HardNegativeLoss.apply(scores, objective)
             if objective is not None:
                 return ops.ranking_loss(scores, *objective)
             return nn.functional.binary_cross_entropy_with_logits(scores, labels.float())
@@ -257,6 +274,9 @@ class RawGnn(nn.Module):
             holder.row_map = compact.node_map
         layers = self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer)
         rows_upper = compact.compact_rows(rows) if compact is not None else None
+        if isinstance(objective, ops.HardNegatives):
+            return ops.hem_hard_negative_loss(layers, rows, item_indices, objective, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
+                                              rows_upper=rows_upper, cosine=cosine)
         if objective is not None:
             return ops.hem_ranking_loss(layers, rows, item_indices, *objective, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
                                         rows_upper=rows_upper, cosine=cosine)

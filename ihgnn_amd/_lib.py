@@ -105,6 +105,7 @@ SIGNATURES = {
                                          c_void_p, c_int64, c_int64, c_void_p]),
     'ihg_bce_with_logits': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'ihg_ranking_loss': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    'ihg_hard_negative_loss': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ihg_batch_scatter_workspace_bytes': (c_int64, [c_int64]),
     'ihg_batch_scatter_max_rows': (c_int32, []),
     'ihg_batch_scatter_add': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int64,
@@ -116,6 +117,7 @@ SIGNATURES = {
     'ihg_adam_step_device_scalars': (ctypes.c_int, [c_void_p, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
     'ihg_batch_combine': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     'ihg_sample_negatives': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    'ihg_sample_pool': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     'ihg_device_batch': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                         c_void_p, c_void_p]),
     'ihg_score_topk_max_dim': (c_int32, []),
@@ -195,6 +197,8 @@ SIGNATURES = {
 }
 ACT_NONE, ACT_LEAKY_RELU = 0, 3
 LOSS_KINDS = {'bpr': 1, 'softmax': 2}      # IHG_LOSS_BPR / IHG_LOSS_SOFTMAX
+HARD_NEGATIVE_KINDS = {'bce': 0, **LOSS_KINDS}      # ihg_hard_negative_loss also takes IHG_LOSS_BCE
+POOL_MAX = 256                             # candidates per positive: ihg_sample_pool's m, ihg_hard_negative_loss's pool
 
 _lib: Optional[ctypes.CDLL] = None
 

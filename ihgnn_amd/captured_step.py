@@ -3,7 +3,7 @@
 A step of the hot path is ~85 kernel launches issued from Python through ctypes.  At the BASELINE workloads from C2 up the GPU is
 the bound (the kernels of a C3 step add up to the step's wall time: profiles/r3), so recording buys nothing there; on small graphs
 (config C1: 20,000 hyperedges, every kernel a few microseconds) the step is bound by the host's launch rate, and a replay removes
-that.  What is recorded: forward (``RawGnn.bce_loss``, or ``RawGnn.ranking_loss`` under ``Gs.Training.loss`` = bpr / softmax), backward, and the Adam update with its two step-dependent scalars read from
+that.  What is recorded: forward (``RawGnn.bce_loss``, ``RawGnn.ranking_loss`` under ``Gs.Training.loss`` = bpr / softmax, or ``RawGnn.hard_negative_loss`` under ``Gs.Training.negative_pool`` > 0), backward, and the Adam update with its two step-dependent scalars read from
 device memory (``ihg_adam_step_device_scalars``).  Per replay the host copies the batch into the static input buffers, refreshes the two
 Adam scalars and launches the graph.  Single process only (a recorded RCCL exchange is not attempted).
 """
@@ -21,7 +21,8 @@ class CapturedTrainingStep:
 
     for batches of ``batch_rows`` rows.  The learning rate may change between calls (it enters through the device scalars).  Under a ranking loss (``Gs.Training.loss``
     other than ``'bce'``, read when the step is recorded) the recorded forward is ``model.ranking_loss(users, queries, items, positives)``: ``positives`` is then
-    required, and the labels are carried but not read."""
+    required, and the labels are carried but not read.  With ``Gs.Training.negative_pool`` set (read then too) it is
+    ``model.hard_negative_loss(users, queries, items, positives, Gs.random_negative_sample_size)`` under any loss, ``positives`` required as well."""
 
     def __init__(self, model, optimizer: Adam, batch_rows: int, warmup_batch=None, positives=None):
         if not isinstance(optimizer, Adam):
@@ -32,12 +33,21 @@ class CapturedTrainingStep:
         self.model, self.optimizer, self.batch_rows = model, optimizer, int(batch_rows)
         from .Helpers.GlobalSettings import Gs
         self.loss_kind = Gs.Training.loss
+        self.pool = int(Gs.Training.negative_pool)          # hard negatives (read when the step is recorded, like the loss): the batch carries a pool per positive ...
+        self.keep = int(Gs.random_negative_sample_size) if self.pool else None      # ... of which the step keeps this many
         self.positives = None if positives is None else int(positives)
-        if self.loss_kind != 'bce':
+        if self.loss_kind != 'bce' or self.pool:
             if self.positives is None:
-                raise ValueError(f'CapturedTrainingStep: Gs.Training.loss = {self.loss_kind!r} needs positives= (the batch is P positives followed by the negatives of each)')
+                raise ValueError(f'CapturedTrainingStep: Gs.Training.loss = {self.loss_kind!r}' + (f' with a pool of {self.pool}' if self.pool else '') +
+                                 ' needs positives= (the batch is P positives followed by the negatives of each)')
             from . import ops
-            ops.ranking_objective(self.batch_rows, self.positives, self.loss_kind)      # the host check, before anything is recorded
+            # the host check, before anything is recorded
+            if self.pool:
+                objective = ops.hard_negative_objective(self.batch_rows, self.positives, self.keep, self.loss_kind)
+                if objective.pool != self.pool:
+                    raise ValueError(f'CapturedTrainingStep: Gs.Training.negative_pool = {self.pool}, but {self.batch_rows} rows over {self.positives} positives carry a pool of {objective.pool}')
+            else:
+                ops.ranking_objective(self.batch_rows, self.positives, self.loss_kind)
         dev = next(model.parameters()).device
         self.users = torch.zeros(batch_rows, dtype=torch.int64, device=dev)
         self.queries = torch.zeros(batch_rows, dtype=torch.int64, device=dev)
@@ -74,7 +84,9 @@ class CapturedTrainingStep:
             try:
                 for module, name, p in slots:
                     module._parameters[name] = aliases[id(p)]
-                if self.loss_kind != 'bce':
+                if self.pool:
+                    loss = model.hard_negative_loss(self.users, self.queries, self.items, self.positives, self.keep, self.loss_kind)
+                elif self.loss_kind != 'bce':
                     loss = model.ranking_loss(self.users, self.queries, self.items, self.positives, self.loss_kind)
                 else:
                     loss = model.bce_loss(self.users, self.queries, self.items, self.labels)
@@ -116,8 +128,9 @@ class CapturedTrainingStep:
         from .Helpers.GlobalSettings import Gs
         group = self.optimizer.param_groups[0]
         loss = Gs.Training.loss                             # (read at every call, like the head: the recording holds the loss launch that was set - and its group count)
+        pool = int(Gs.Training.negative_pool)               # (and the pool with its kept count: the recording holds ihg_hard_negative_loss's launch, or does not)
         return (tuple(group['betas']), float(group['eps']), float(group['weight_decay']), bool(self.model.batch_rows_only_last_layer),
-                bool(Gs.Prediction.use_cosine_similarity), loss, self.positives if loss != 'bce' else None)
+                bool(Gs.Prediction.use_cosine_similarity), loss, self.positives if loss != 'bce' or pool else None, pool, int(Gs.random_negative_sample_size) if pool else None)
 
     def _baked_settings(self):
         """Everything a replay cannot change any more: the recording holds the kernels these settings selected.  Only the learning rate is
@@ -132,8 +145,8 @@ class CapturedTrainingStep:
 
     def stale(self, full: bool = False) -> bool:
         """True when a setting that is baked into the recording has changed since: the caller must record a new step (``TrainTestHelper`` does) - replaying would
-        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer``, the scoring head, the loss kind and (under a ranking loss) the number of
-        positives - seven values, what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
+        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer``, the scoring head, the loss kind, (under a ranking loss or a pool) the number of
+        positives, and the hard-negative pool with its kept count - nine values, what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
         epoch, not per replay on the launch-bound path the recording exists for)."""
         if full:
             return self._baked != self._baked_settings()
@@ -156,7 +169,7 @@ class CapturedTrainingStep:
     def step(self, users, queries, items, labels, positives=None):
         if users.shape[0] != self.batch_rows:
             raise ValueError(f'this step was recorded for batches of {self.batch_rows} rows, got {users.shape[0]}')
-        if positives is not None and self.loss_kind != 'bce' and int(positives) != self.positives:
+        if positives is not None and (self.loss_kind != 'bce' or self.pool) and int(positives) != self.positives:
             raise ValueError(f'this step was recorded for batches of {self.positives} positives, got {positives}')
         if self.stale():
             raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay, batch_rows_only_last_layer, the scoring head or the loss - the values '

@@ -240,6 +240,147 @@ __global__ __launch_bounds__(kScatterThreads) void ranking_loss_kernel(const flo
     if (threadIdx.x == 0) *loss = part[0] * (KIND == kLossBpr ? inv_n : inv_p);
 }
 
+// Hard negatives (dynamic negative sampling): a batch of P positives followed by the M pool candidates of positive p at P + p*M .. P + (p+1)*M - 1; the k candidates of a
+// group that come first by (score descending, pool position ascending) are its negatives, and the loss is bce_with_logits_kernel's (KIND = IHG_LOSS_BCE: labels 1 / 0, mean
+// over P (1 + k)) or ranking_loss_kernel's over the positive and those k.  Score order is the order of the monotone uint32 key of the float's bits (score_key): a strict
+// total order over every bit pattern, so with the position as the tie-break the M ranks of a group are a permutation of 0 .. M-1 and exactly k candidates have rank < k,
+// NaNs or not.
+// A WAVE OWNS A GROUP (wave w of the one workgroup takes groups w, w + 16, ...; every wave makes the same number of trips, so the barriers below are met by all):
+//   1. lane l owns candidates l, l + 64, .. (at most 4): their keys go to LDS, and the lane counts over all M keys how many come before each of its own - the rank;
+//   2. rank < k: selected[p][rank] = the candidate's pool position, and its score goes to LDS slot `rank`;
+//   3. the group's sums run over the slots in RANK order - lane l adds slots l, l + 64, .. ascending, then the xor butterfly 32, 16, .. 1 - so their order is a function of k
+//      alone, whichever lanes held the selected candidates;
+//   4. every lane writes dscores of its own candidates (the same function of the same arguments as in 3: the same bits), +0.0 where the rank is >= k.
+// A wave adds its groups' terms in trip order; the 16 partial sums go through a four-level tree.  No atomics; two launches on the same input agree bit for bit.
+constexpr int kLossBce = IHG_LOSS_BCE;
+constexpr int kPoolMax = 256;
+constexpr int kLossWaves = kScatterThreads / kWave;
+
+__device__ __forceinline__ uint32_t score_key(float s) {
+    const uint32_t bits = __float_as_uint(s);
+    return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// softplus(x) and sigmoid(x) as bce_with_logits_kernel / ranking_loss_kernel form them
+__device__ __forceinline__ float softplus_term(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigmoid_of(float x) {
+    const float e = expf(-fabsf(x));
+    return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+
+// rank[t] += how many of keys[0 .. pool) come before the lane's candidate t (key own[t] at pool position lane + 64 t): a greater key, or the same key at a lower position.
+// OWNED = the candidates a lane holds (1 up to a pool of 64, 2 up to 128, else 4): a pool of 50 pays for one comparison per key, not four; the key loads of four
+// rounds are issued together (every lane reads the same address: a broadcast).
+template <int OWNED>
+__device__ __forceinline__ void count_before(const uint32_t* keys, int pool, int lane, const uint32_t (&own)[4], int (&rank)[4]) {
+#pragma unroll 4
+    for (int j = 0; j < pool; ++j) {
+        const uint32_t other = keys[j];
+#pragma unroll
+        for (int t = 0; t < OWNED; ++t) rank[t] += (other > own[t] || (other == own[t] && j < lane + t * kWave)) ? 1 : 0;
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kScatterThreads) void hard_negative_loss_kernel(const float* __restrict__ scores, int positives, int pool, int keep, float* __restrict__ loss,
+                                                                             float* __restrict__ dscores, int32_t* __restrict__ selected) {
+    __shared__ uint32_t keys[kLossWaves][kPoolMax];
+    __shared__ float kept[kLossWaves][kPoolMax];
+    __shared__ float part[kLossWaves];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int owned = (pool + kWave - 1) / kWave;                           // candidates per lane, <= 4
+    const float inv_p = 1.f / static_cast<float>(positives);
+    const float inv_n = 1.f / static_cast<float>(static_cast<int64_t>(positives) * (KIND == kLossBce ? keep + 1 : keep));
+    float acc = 0.f;
+    for (int first = 0; first < positives; first += kLossWaves) {
+        const int p = first + wave;
+        const bool active = p < positives;
+        const int64_t base = positives + static_cast<int64_t>(active ? p : 0) * pool;      // (< positives * (1 + pool) <= INT32_MAX: checked by the entry)
+        float mine[4] = {0.f, 0.f, 0.f, 0.f};
+        if (active) {
+            for (int t = 0; t < owned; ++t) {
+                const int c = lane + t * kWave;
+                if (c < pool) {
+                    mine[t] = scores[base + c];
+                    keys[wave][c] = score_key(mine[t]);
+                }
+            }
+        }
+        __syncthreads();
+        int rank[4] = {0, 0, 0, 0};
+        if (active) {
+            uint32_t own[4] = {0u, 0u, 0u, 0u};
+            for (int t = 0; t < owned; ++t) own[t] = (lane + t * kWave < pool) ? keys[wave][lane + t * kWave] : 0u;
+            if (owned == 1) count_before<1>(keys[wave], pool, lane, own, rank);
+            else if (owned == 2) count_before<2>(keys[wave], pool, lane, own, rank);
+            else count_before<4>(keys[wave], pool, lane, own, rank);
+            for (int t = 0; t < owned; ++t) {
+                const int c = lane + t * kWave;
+                if (c < pool && rank[t] < keep) {
+                    selected[static_cast<int64_t>(p) * keep + rank[t]] = c;
+                    kept[wave][rank[t]] = mine[t];
+                }
+            }
+        }
+        __syncthreads();
+        if (active) {
+            const float sp = scores[p];
+            if constexpr (KIND == kLossSoftmax) {
+                float m = sp;
+                for (int r = lane; r < keep; r += kWave) m = fmaxf(m, kept[wave][r]);
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+                float negatives = 0.f;
+                for (int r = lane; r < keep; r += kWave) negatives += expf(kept[wave][r] - m);
+                negatives = wave_sum(negatives);
+                const float z = expf(sp - m) + negatives;
+                acc += (m - sp) + logf(z);
+                for (int t = 0; t < owned; ++t) {
+                    const int c = lane + t * kWave;
+                    if (c < pool) dscores[base + c] = rank[t] < keep ? expf(mine[t] - m) / z * inv_p : 0.f;
+                }
+                if (lane == 0) dscores[p] = -(negatives / z) * inv_p;
+            } else if constexpr (KIND == kLossBpr) {
+                float terms = 0.f, dsum = 0.f;
+                for (int r = lane; r < keep; r += kWave) {
+                    const float x = kept[wave][r] - sp;
+                    terms += softplus_term(x);
+                    dsum += sigmoid_of(x) * inv_n;
+                }
+                acc += wave_sum(terms);
+                dsum = wave_sum(dsum);
+                for (int t = 0; t < owned; ++t) {
+                    const int c = lane + t * kWave;
+                    if (c < pool) dscores[base + c] = rank[t] < keep ? sigmoid_of(mine[t] - sp) * inv_n : 0.f;
+                }
+                if (lane == 0) dscores[p] = -dsum;
+            } else {
+                float terms = 0.f;
+                for (int r = lane; r < keep; r += kWave) terms += softplus_term(kept[wave][r]);      // label 0: max(s, 0) + log1p(exp(-|s|))
+                acc += wave_sum(terms) + ((fmaxf(sp, 0.f) - sp) + log1pf(expf(-fabsf(sp))));          // label 1: max(s, 0) - s + log1p(exp(-|s|)), the positive added last
+                for (int t = 0; t < owned; ++t) {
+                    const int c = lane + t * kWave;
+                    if (c < pool) dscores[base + c] = rank[t] < keep ? sigmoid_of(mine[t]) * inv_n : 0.f;
+                }
+                if (lane == 0) dscores[p] = (sigmoid_of(sp) - 1.f) * inv_n;
+            }
+        }
+    }
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    for (int off = kLossWaves / 2; off > 0; off >>= 1) {
+        if (static_cast<int>(threadIdx.x) < off) part[threadIdx.x] += part[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = part[0] * (KIND == kLossSoftmax ? inv_p : inv_n);
+}
+
 // Deterministic scatter-add of a small batch of rows into a large dense matrix: dense[rows[k], :] += rowgrad[k, :], duplicates
 // summed in batch order, no atomics, no sort.  One wave per batch position k: it scans rows[0..k) for an earlier occurrence of
 // its destination (ballot over 64 ids at a time; the id array is a few KB and cache-resident) and retires if there is one;
@@ -494,6 +635,39 @@ __global__ __launch_bounds__(kBlockThreads) void sample_negatives_kernel(uint64_
     }
 }
 
+// draw_distinct continued past kSampleMax (ihg_sample_pool): a WORKGROUP OF ONE WAVE per row.  Attempts are taken 64 at a time, lane j taking attempt base + j; a lane's
+// value is fresh iff it is not in the accepted list (LDS) and no EARLIER lane of the chunk holds it - an earlier lane with the same value is either accepted or itself a
+// repeat of an accepted value, so this is the sequential rule.  Slots come from the ballot's prefix count, cut at m: the first m accepted values in attempt order.
+// The loop ends like draw_distinct's: m <= n_items values are there to be found (m = n_items = 256 takes about thirty chunks).
+constexpr int kPoolDraws = 256;
+
+__global__ __launch_bounds__(kWave) void sample_pool_kernel(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int m, int64_t* __restrict__ out) {
+    __shared__ int64_t accepted[kPoolDraws];
+    __shared__ int64_t chunk[kWave];
+    const int lane = threadIdx.x;
+    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const uint64_t key = sample_row_key(seed, counter, row);
+        int count = 0;                                                   // accepted so far: the same in every lane (it follows from ballots)
+        for (uint64_t base = 0; count < m; base += kWave) {
+            const uint64_t r = mix64(key + (base + lane) * 0x2545F4914F6CDD1Dull);
+            const int64_t value = static_cast<int64_t>(__umul64hi(r, static_cast<uint64_t>(n_items)));
+            chunk[lane] = value;
+            __syncthreads();                                             // (one wave: the chunk, and the list as the last round left it, are visible)
+            bool fresh = true;
+            for (int j = 0; j < count; ++j) fresh = fresh && accepted[j] != value;
+            for (int j = 0; j < kWave; ++j) fresh = fresh && (j >= lane || chunk[j] != value);
+            const unsigned long long mask = __ballot(fresh);
+            const int slot = count + __popcll(mask & ((1ull << lane) - 1ull));
+            if (fresh && slot < m) {
+                accepted[slot] = value;
+                out[row * m + slot] = value;
+            }
+            count += __popcll(mask);
+            __syncthreads();
+        }
+    }
+}
+
 // One thread per positive writes its column of the pack and the k = k_rand + k_logged columns of its negatives (header: ihg_device_batch).
 __global__ __launch_bounds__(kBlockThreads) void device_batch_kernel(uint64_t seed, uint64_t counter, const int64_t* __restrict__ pos_triples,
                                                                      const int64_t* __restrict__ edge_ids, int64_t n, const int32_t* __restrict__ pair_of_edge,
@@ -549,6 +723,16 @@ int ihg_sample_negatives(uint64_t seed, uint64_t counter, int64_t n_rows, int64_
     const int grid = static_cast<int>(std::min<int64_t>((n_rows + kBlockThreads - 1) / kBlockThreads, kMaxBlocks));
     hipLaunchKernelGGL(sample_negatives_kernel, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, k, out);
     return check_launch("ihg_sample_negatives");
+}
+
+int ihg_sample_pool(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, int64_t* out, ihg_stream_t stream) {
+    if (n_rows < 0 || n_items <= 0 || m < 1 || m > kPoolDraws || m > n_items)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool: need 1 <= m <= min(%d, n_items), got m = %d and n_items = %lld", kPoolDraws, m, (long long)n_items);
+    if (n_rows == 0) return IHG_OK;
+    if (out == nullptr) return fail(IHG_ERR_INVALID, "ihg_sample_pool: null pointer");
+    const int grid = static_cast<int>(std::min<int64_t>(n_rows, static_cast<int64_t>(kMaxBlocks) * kWavesPerBlock));
+    hipLaunchKernelGGL(sample_pool_kernel, dim3(grid), dim3(kWave), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, static_cast<int>(m), out);
+    return check_launch("ihg_sample_pool");
 }
 
 int ihg_device_batch(uint64_t seed, uint64_t counter, const int64_t* pos_triples, const int64_t* edge_ids, int64_t n, const int32_t* pair_of_edge,
@@ -684,6 +868,22 @@ int ihg_ranking_loss(const float* scores, int64_t positives, int32_t k, int32_t 
     const auto kernel = kind == kLossBpr ? ranking_loss_kernel<kLossBpr> : ranking_loss_kernel<kLossSoftmax>;
     hipLaunchKernelGGL(kernel, dim3(1), dim3(kScatterThreads), 0, static_cast<hipStream_t>(stream), scores, static_cast<int>(positives), static_cast<int>(k), loss, dscores);
     return check_launch("ihg_ranking_loss");
+}
+
+int ihg_hard_negative_loss(const float* scores, int64_t positives, int32_t pool, int32_t keep, int32_t kind, float* loss, float* dscores, int32_t* selected,
+                           ihg_stream_t stream) {
+    if (scores == nullptr || loss == nullptr || dscores == nullptr || selected == nullptr) return fail(IHG_ERR_INVALID, "ihg_hard_negative_loss: null pointer");
+    if (positives < 1) return fail(IHG_ERR_INVALID, "ihg_hard_negative_loss: need positives >= 1, got %lld", (long long)positives);
+    if (keep < 1 || keep > pool || pool > kPoolMax)
+        return fail(IHG_ERR_INVALID, "ihg_hard_negative_loss: need 1 <= keep <= pool <= %d, got keep = %d and pool = %d", kPoolMax, keep, pool);
+    if (kind != kLossBce && kind != kLossBpr && kind != kLossSoftmax)
+        return fail(IHG_ERR_INVALID, "ihg_hard_negative_loss: kind is IHG_LOSS_BCE (0), IHG_LOSS_BPR (1) or IHG_LOSS_SOFTMAX (2), got %d", kind);
+    if (positives > INT32_MAX / (static_cast<int64_t>(pool) + 1))
+        return fail(IHG_ERR_INVALID, "ihg_hard_negative_loss: positives * (1 + pool) = %lld * %lld is beyond INT32_MAX scores", (long long)positives, (long long)pool + 1);
+    const auto kernel = kind == kLossBce ? hard_negative_loss_kernel<kLossBce> : kind == kLossBpr ? hard_negative_loss_kernel<kLossBpr> : hard_negative_loss_kernel<kLossSoftmax>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(kScatterThreads), 0, static_cast<hipStream_t>(stream), scores, static_cast<int>(positives), static_cast<int>(pool),
+                       static_cast<int>(keep), loss, dscores, selected);
+    return check_launch("ihg_hard_negative_loss");
 }
 
 

@@ -1861,7 +1861,8 @@ class _HemBceLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rows: Tensor, items: Tensor, labels: Optional[Tensor], bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, cosine: bool,
                 objective, *layers: Tensor) -> Tensor:
-        # objective: None = the BCE over ``labels``; (positives, kind) = a ranking loss (``ihg_ranking_loss``; no labels are read) - the one launch that differs
+        # objective: None = the BCE over ``labels``; (positives, kind) = a ranking loss (``ihg_ranking_loss``; no labels are read); a ``HardNegatives`` = the objective over
+        # every positive and the best ``keep`` of its pool (``ihg_hard_negative_loss``; no labels either) - the one launch that differs
         # tables (a resolved NodeTables): layer 0 is the embedding tables in place; layers[0] is then its token (the autograd edge), not a matrix
         # rows_upper (a layout without the isolated nodes): layer 0 is in the public numbering (rows), the layers above are in the layout's (rows_upper; -1: zero row)
         lib = _lib.load()
@@ -1876,6 +1877,8 @@ class _HemBceLoss(torch.autograd.Function):
             stats = _hem_forward(real, tables, rows, rows_upper, items, bias, lam, cosine, scores)
             if objective is None:
                 _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), batch, _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
+            elif isinstance(objective, HardNegatives):
+                objective.launch(scores, loss, dscores)
             else:
                 positives, kind = objective
                 _lib.check(lib.ihg_ranking_loss(_ptr(scores), positives, batch // positives - 1, kind, _ptr(loss), _ptr(dscores), _stream()), 'ihg_ranking_loss')
@@ -2126,6 +2129,58 @@ def ranking_objective(batch_rows: int, positives: int, kind) -> tuple:
     return positives, int(code)
 
 
+class HardNegatives:
+    """The objective over every positive and the best ``keep`` candidates of its pool (``ihg_hard_negative_loss``): what ``hard_negative_objective`` checked, and after
+    the launch ``selected`` - int32 ``[positives, keep]``, the pool positions of every group's negatives, best first."""
+    __slots__ = ('positives', 'pool', 'keep', 'kind', 'selected')
+
+    def __init__(self, positives: int, pool: int, keep: int, kind: int):
+        self.positives, self.pool, self.keep, self.kind, self.selected = positives, pool, keep, kind, None
+
+    def launch(self, scores: Tensor, loss: Tensor, dscores: Tensor) -> None:
+        self.selected = torch.empty(self.positives, self.keep, dtype=torch.int32, device=scores.device)
+        _lib.check(_lib.load().ihg_hard_negative_loss(_ptr(scores), self.positives, self.pool, self.keep, self.kind, _ptr(loss), _ptr(dscores), _ptr(self.selected),
+                                                      _stream()), 'ihg_hard_negative_loss')
+
+
+def hard_negative_objective(batch_rows: int, positives: int, keep: int, kind) -> HardNegatives:
+    """The hard-negative objective over a batch of ``batch_rows`` scores, checked on the host before anything is launched: the batch is ``positives`` positives followed by
+    the same number ``M`` of pool candidates for each (``B % positives == 0``, the candidates of positive ``p`` at rows ``P + p M ..``), ``1 <= keep <= M <= 256``, ``kind``
+    is ``'bce'``, ``'bpr'`` or ``'softmax'`` (or ``IHG_LOSS_BCE`` / ``IHG_LOSS_BPR`` / ``IHG_LOSS_SOFTMAX``)."""
+    kinds = _lib.HARD_NEGATIVE_KINDS
+    code = kinds.get(kind, kind) if isinstance(kind, str) else kind
+    if isinstance(code, bool) or not isinstance(code, int) or code not in kinds.values():
+        raise ValueError(f'hard negatives: kind is one of {sorted(kinds)}, got {kind!r}')
+    batch_rows, positives, keep = int(batch_rows), int(positives), int(keep)
+    if positives < 1 or batch_rows % positives != 0 or batch_rows // positives - 1 < 1:
+        raise ValueError(f'hard negatives: a batch is P positives followed by P * M pool candidates, M >= 1: {batch_rows} rows cannot be split into {positives} groups')
+    pool = batch_rows // positives - 1
+    if not 1 <= keep <= pool <= _lib.POOL_MAX:
+        raise ValueError(f'hard negatives: need 1 <= keep <= pool <= {_lib.POOL_MAX}, got keep = {keep} of a pool of {pool}')
+    return HardNegatives(positives, pool, keep, int(code))
+
+
+def hem_hard_negative_loss(layers, rows: Tensor, items: Tensor, objective: HardNegatives, bias: Tensor, lam: float, item_row_offset: int,
+                           holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
+    """``hard_negative_loss(hem_score(...), positives, keep, kind)`` as one differentiable op (scalar): ``hem_bce_loss`` with ``ihg_hard_negative_loss`` as its loss launch
+    and no labels.  ``objective`` is ``hard_negative_objective``'s and holds ``selected`` afterwards.  The pool rows are ordinary batch rows; the rows of the candidates
+    that are not selected get zero row gradients.  Every other argument as in ``hem_bce_loss``."""
+    if objective.positives * (1 + objective.pool) != int(items.shape[0]):
+        raise ValueError(f'hard negatives: the objective was made for {objective.positives * (1 + objective.pool)} rows, the batch has {int(items.shape[0])}')
+    return _hem_loss('hem_hard_negative_loss', layers, rows, items, None, objective, bias, lam, item_row_offset, holder, rows_upper, cosine)
+
+
+def sample_pool(seed: int, counter: int, n_rows: int, n_items: int, m: int, device=None) -> Tensor:
+    """``[n_rows, m]`` int64: ``m`` distinct items below ``n_items`` per row, ``1 <= m <= min(256, n_items)`` - ``ihg_sample_negatives``' stream continued past 16 draws
+    (``ihg_sample_pool``: the first ``c`` columns are what ``m = c`` gives)."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty(max(int(n_rows), 0), max(int(m), 0), dtype=torch.int64, device=device)
+    mask = (1 << 64) - 1
+    with profiler.kernel('sample_pool', int(n_rows), int(m)):
+        _lib.check(_lib.load().ihg_sample_pool(int(seed) & mask, int(counter) & mask, int(n_rows), int(n_items), int(m), _ptr(out), _stream()), 'ihg_sample_pool')
+    return out
+
+
 def hem_ranking_loss(layers, rows: Tensor, items: Tensor, positives: int, kind, bias: Tensor, lam: float, item_row_offset: int,
                      holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
     """``ranking_loss(hem_score(...), positives, kind)`` as one differentiable op (scalar): ``hem_bce_loss`` with ``ihg_ranking_loss`` as its loss launch and no labels.
@@ -2369,6 +2424,34 @@ def ranking_loss(scores: Tensor, positives: int, kind) -> Tensor:
         raise ValueError(f'ranking_loss takes the scores of a batch as a vector, got {tuple(scores.shape)}')
     positives, code = ranking_objective(int(scores.shape[0]), positives, kind)
     return _RankingLoss.apply(scores, positives, code)
+
+
+class _HardNegativeLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores: Tensor, objective: HardNegatives) -> Tensor:
+        scores = _gpu(scores.detach(), 'scores').to(torch.float32).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=scores.device)
+        dscores = torch.empty_like(scores)
+        with profiler.kernel('hard_negative_loss', int(scores.numel()), 1):
+            objective.launch(scores, loss, dscores)
+        ctx.save_for_backward(dscores)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss: Tensor):
+        return ctx.saved_tensors[0] * grad_loss, None
+
+
+def hard_negative_loss(scores: Tensor, positives: int, keep: int, kind, return_selected: bool = False):
+    """The loss ``kind`` (``'bce'``, ``'bpr'``, ``'softmax'``) of ``scores`` ``[P (1 + M)]`` - ``positives = P`` positives followed by the ``M`` pool candidates of each -
+    over every positive and the ``keep`` candidates of its pool that score highest (ties: the lower pool position), with its gradient - exactly zero on the other
+    candidates - from the one launch of ``ihg_hard_negative_loss``: the sibling of ``ranking_loss`` where the fused tail (``hem_hard_negative_loss``) does not apply.
+    ``return_selected``: also the ``[P, keep]`` pool positions of the negatives, best first (int64, detached)."""
+    if scores.dim() != 1:
+        raise ValueError(f'hard_negative_loss takes the scores of a batch as a vector, got {tuple(scores.shape)}')
+    objective = hard_negative_objective(int(scores.shape[0]), positives, keep, kind)
+    loss = _HardNegativeLoss.apply(scores, objective)
+    return (loss, objective.selected.to(torch.int64)) if return_selected else loss
 
 
 class _GatherRows(torch.autograd.Function):

@@ -446,6 +446,20 @@ int ihg_bce_with_logits(const float* scores, const float* labels, int64_t n, flo
 #define IHG_LOSS_BPR 1
 #define IHG_LOSS_SOFTMAX 2
 int ihg_ranking_loss(const float* scores, int64_t positives, int32_t k, int32_t kind, float* loss, float* dscores, ihg_stream_t stream);
+/* Hard negatives (dynamic negative sampling; not in the reference): scores [positives * (1 + pool)] are the positives followed by the `pool` candidates of positive p at
+ * positives + p * pool ..; the `keep` candidates of a group that come first by (score descending, pool position ascending) are its negatives.  Score order is the order of
+ * the monotone uint32 key of the float's bits - sign bit set: ~bits, otherwise bits | 0x80000000 - a strict total order over every bit pattern: a positive-sign NaN sorts
+ * above +inf, a negative-sign NaN below -inf, -0.0 below +0.0.  Exactly `keep` candidates are selected per group whatever the input, NaN included.
+ * One launch writes
+ *   selected [positives, keep] int32: selected[p][r] = the pool position 0 .. pool-1 of group p's r-th best;
+ *   loss: the objective over every positive and its selected negatives - IHG_LOSS_BCE: ihg_bce_with_logits with labels 1 / 0, mean over positives * (1 + keep);
+ *         IHG_LOSS_BPR / IHG_LOSS_SOFTMAX: ihg_ranking_loss with k = keep (means over positives * keep / over positives);
+ *   dscores [positives * (1 + pool)] = d loss / d scores, EVERY entry: exactly +0.0 on a candidate that is not selected.
+ * No atomics; every sum runs in an order that is a function of (positives, pool, keep) alone, so two launches on the same input agree bit for bit.
+ * 1 <= keep <= pool <= 256, positives >= 1, positives * (1 + pool) <= INT32_MAX; IHG_ERR_INVALID has launched nothing. */
+#define IHG_LOSS_BCE 0
+int ihg_hard_negative_loss(const float* scores, int64_t positives, int32_t pool, int32_t keep, int32_t kind, float* loss, float* dscores, int32_t* selected,
+                           ihg_stream_t stream);
 int64_t ihg_batch_scatter_workspace_bytes(int64_t n_rows);      /* 0, or -1 if n_rows > ihg_batch_scatter_max_rows() (caller scatters in row chunks) */
 int32_t ihg_batch_scatter_max_rows(void);                        /* 32768: rows of one ihg_batch_scatter_add / ihg_batch_combine launch (its id list lives in LDS: <= 16384 rows in 64 KiB,
                                                                     beyond that - the union of the ranks' batches under the cotangent exchange - a 128 KiB instance) */
@@ -532,6 +546,12 @@ int ihg_adam_step_device_scalars(const ihg_adam_tensor* tensors, int32_t n_tenso
  * Not the reference's Mersenne-Twister stream - same distribution, different draws.  k <= 16.
  */
 int ihg_sample_negatives(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t k, int64_t* out, ihg_stream_t stream);
+/* The same draw continued past 16, for a pool of candidates per positive: out [n_rows, m] int64, m DISTINCT values below n_items per row, 1 <= m <= min(256, n_items).
+ * Row r's stream is ihg_sample_negatives' key(seed, counter, r); attempts are counted from 0, attempt a yields umulhi(mix64(key + a * 0x2545F4914F6CDD1D), n_items), an
+ * attempt is accepted iff its value differs from every value accepted before it, and the first m accepted values, in attempt order, are the row.  So the first c columns
+ * of a call with m are what a call with c gives, and for c <= 16 they are ihg_sample_negatives' bits.  IHG_ERR_INVALID (m out of range, a null `out` with rows to write)
+ * has launched nothing; n_rows == 0 returns IHG_OK. */
+int ihg_sample_pool(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, int64_t* out, ihg_stream_t stream);
 
 /* DEVICE: one whole training batch in one launch, logged negatives included.  Replaces, for the n positives `edge_ids` of pos_triples [E, 3]
  * (user, query, item), GraphDataset.__getitem__ + collate_fn (Dataset.py:107-119, 282-291).  pack is the [4, n (1 + k)] array collate_fn builds, k = k_rand + k_logged,
