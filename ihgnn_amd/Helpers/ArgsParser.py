@@ -1,5 +1,6 @@
 """Command line of the driver: the reference's flags, aliases and defaults (``Helpers/ArgsParser.py:49-96``)."""
 import argparse
+import math
 from typing import Optional, Sequence
 
 from .GlobalSettings import Gsv
@@ -21,6 +22,26 @@ def cutoff_list(text: str):
             raise argparse.ArgumentTypeError(f'--cutoffs: every cutoff must be in {MIN_EXTRA_CUTOFF}..{MAX_EXTRA_CUTOFF} (@10 is always reported), got {value}')
         out.add(value)
     return tuple(sorted(out))
+
+
+def checked_clip_norm(value) -> float:
+    """The bound of ``--clip_grad_norm`` / ``Gs.Training.clip_grad_norm``: a finite float >= 0 (0 = off), or a ``ValueError`` - the one check the parser and the
+    driver's settings share."""
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f'--clip_grad_norm takes a number, got {value!r}')
+    if not math.isfinite(value) or value < 0:
+        raise ValueError(f'--clip_grad_norm takes a finite bound >= 0 (0 = off), got {value}')
+    return value
+
+
+def clip_norm(text: str) -> float:
+    """``checked_clip_norm`` as an argparse type."""
+    try:
+        return checked_clip_norm(text)
+    except ValueError as refused:
+        raise argparse.ArgumentTypeError(str(refused))
 
 
 # (dest, flags, kind, default, help); kind is a type or 'flag'
@@ -60,6 +81,9 @@ _FLAGS = (
     # not in the reference, whose negatives are uniform draws (and a pair's logged ones): dynamic negative sampling
     ('hard_negatives', ('--hard_negatives',), int, 0, 'hard negatives: draw a pool of M random candidates per positive and train on the Gs.random_negative_sample_size of them that the '
                                                       'current model scores highest (Gs.Training.negative_pool; 0 = off; needs random_negative_sample_size < M <= 256, no --logged_negatives)'),
+    # not in the reference, whose step has no gradient clipping
+    ('clip_grad_norm', ('--clip_grad_norm',), clip_norm, 0.0, 'clip every step\'s gradient to this global L2 norm, as torch.nn.utils.clip_grad_norm_ before Adam (Gs.Training.clip_grad_norm; '
+                                                             '0 = off); the epoch log then shows the largest norm and the number of clipped steps'),
     ('grad_sync', ('--grad_sync',), str, 'auto', 'gradient exchange under torchrun: auto | cotangent (batch-row cotangents: no dense exchange) | flat | bucketed | sharded (ihgnn_amd.distributed)'),
     ('seed', ('--seed',), int, -1, 'seed torch / random / numpy before the model is built (the reference seeds nothing, Main.py: -1 leaves the generators alone)'),
     ('record_step', ('--record_step',), 'optional', 'auto', 'replay the training step as one recorded hipGraph (single process): auto (default: when an eager step measures launch-bound, '

@@ -44,6 +44,7 @@ class Gs:
 
     class Training:
         loss = 'bce'                     # not in the reference (whose only objective is nn.BCEWithLogitsLoss over a positive and its negatives): 'bpr' | 'softmax' (--loss) train on a ranking loss of every positive against its own negatives
+        clip_grad_norm = 0.0             # not in the reference (whose step has no clipping): X > 0 (--clip_grad_norm X) scales every step's gradient so that its global L2 norm is at most X, as torch.nn.utils.clip_grad_norm_ does; 0 = off
         negative_pool = 0                # not in the reference: M > 0 (--hard_negatives M) draws a pool of M random candidates per positive and trains on the random_negative_sample_size of them that the model scores highest; 0 = off
 
     class Evaluation:

@@ -124,6 +124,15 @@ def _record_mode(record_step) -> str:
     raise ValueError(f'record_step: on | off | auto, got {record_step!r}')
 
 
+def log_clip_statistics(optimizer) -> None:
+    """With gradient clipping on (``optimizer.max_grad_norm``): one line with the epoch's largest gradient norm and how many of its steps were scaled down - one host
+    read of the three floats the clip launch keeps on the device.  Off: no line."""
+    if getattr(optimizer, 'max_grad_norm', None) is None or not hasattr(optimizer, 'clip_statistics'):
+        return
+    largest, clipped, steps = optimizer.clip_statistics(reset=True)
+    IOHelper.LogPrint(f'grad norm max {largest:<.4g} | clipped {clipped} of {steps} steps (max_grad_norm {optimizer.max_grad_norm:g})')
+
+
 def srrl_kg_step(model, optimizer, batch, device: torch.device) -> torch.Tensor:
     """One KG step of the Srrl baseline (reference ``Helpers/TrainTestHelper.py:169-214``) on a batch of ``SrrlDatasetKG.collate_fn``; -> the loss (on the device)."""
     from .. import ops
@@ -183,6 +192,7 @@ def train_srrl_and_get_avg_loss(model, optimizer, dataloader_train, pc: ProcessC
         batches += 1
     avg_loss = ps_sum.item() / max(batches, 1)
     IOHelper.LogPrint(f'[Epoch PS {pc.CurrentEpoch:<2d}] avg loss {avg_loss:<.4f}  <-PS  in {time.time() - ps_started:<.2f}s (remaining {pc.GetRemainingTimeString()}).')
+    log_clip_statistics(optimizer)                           # (the KG steps and the PS steps of the epoch together: one optimizer takes both)
     # (no learning-rate schedule: adjust_learning_rate is the RawGnn branch's, TrainTestHelper.py:155)
     return avg_loss, time.time() - started
 
@@ -326,6 +336,7 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
     IOHelper.LogPrint(f'[Epoch \033[0;44m{pc.CurrentEpoch:>2d}/{pc.EndEpoch - 1}\033[0m] average loss '
                       f'\033[0;45m{avg_loss:<.4f}\033[0m on {positives} interactions in {seconds:<.2f} s '
                       f'(remaining {pc.GetRemainingTimeString()}).')
+    log_clip_statistics(optimizer)
     if Gs.adjust_learning_rate and avg_loss < 0.008 and Gs.learning_rate > 0.0004:
         Gs.learning_rate *= 0.98
         for group in optimizer.param_groups:

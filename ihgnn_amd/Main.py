@@ -55,11 +55,11 @@ def apply_evaluation_settings(args) -> None:
 
 
 def apply_training_settings(args) -> None:
-    """``--loss`` -> ``Gs.Training.loss`` and ``--hard_negatives M`` -> ``Gs.Training.negative_pool``, assigned both ways like the head above (not in the reference, which
+    """``--loss`` -> ``Gs.Training.loss``, ``--hard_negatives M`` -> ``Gs.Training.negative_pool`` and ``--clip_grad_norm X`` -> ``Gs.Training.clip_grad_norm``, assigned both ways like the head above (not in the reference, which
     trains on ``nn.BCEWithLogitsLoss`` over uniform negatives only).  A pool needs ``Gs.random_negative_sample_size < M <= 256`` and no logged negatives (the pool is
     random-only); called after ``apply_sampling_settings``."""
     from . import _lib
-    from .Helpers.ArgsParser import LOSSES
+    from .Helpers.ArgsParser import LOSSES, checked_clip_norm
     loss = getattr(args, 'loss', 'bce') or 'bce'
     if loss not in LOSSES:
         raise ValueError(f'--loss: one of {", ".join(LOSSES)}, got {loss!r}')
@@ -72,8 +72,10 @@ def apply_training_settings(args) -> None:
                              f'(Gs.random_negative_sample_size) and at most {_lib.POOL_MAX}')
         if int(getattr(args, 'logged_negatives', 0) or 0) > 0 or Gs.non_random_negative_sample_size > 0:
             raise ValueError('--hard_negatives draws its pool from the catalogue only: it does not go with --logged_negatives (Gs.non_random_negative_sample_size > 0)')
+    clip = checked_clip_norm(getattr(args, 'clip_grad_norm', 0.0) or 0.0)      # (a caller that builds its own args: the parser's check)
     Gs.Training.loss = loss
     Gs.Training.negative_pool = pool
+    Gs.Training.clip_grad_norm = clip
 
 
 def apply_sampling_settings(args) -> None:
@@ -185,7 +187,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     per_positive = pool or Gs.random_negative_sample_size + Gs.non_random_negative_sample_size      # negative rows a batch carries per positive
     say(f'device {device} | ranks {world} | batch {Gs.batch_size} | lr {Gs.learning_rate} | emb {Gs.embedding_size} | '
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}' +
-        (f' | hard negatives: the best {Gs.random_negative_sample_size} of a pool of {pool}' if pool else ''))
+        (f' | hard negatives: the best {Gs.random_negative_sample_size} of a pool of {pool}' if pool else '') +
+        (f' | clip grad norm {Gs.Training.clip_grad_norm:g}' if Gs.Training.clip_grad_norm else ''))
     if pool:
         from . import ops
         if 3 * Gs.batch_size * (1 + pool) > ops.SCATTER_CHUNK_ROWS:
@@ -241,10 +244,11 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
             say(f'gradient exchange: {mode}')
         grad_sync = ihg_dist.make_gradient_sync(model, mode)
         grad_sync.broadcast_parameters(0)
+    max_grad_norm = Gs.Training.clip_grad_norm or None       # (0 = off: the optimizer then launches what it launches without the keyword)
     if grad_sync is not None and grad_sync.owns_optimizer:
-        optimizer = grad_sync.optimizer(Gs.learning_rate, Gs.weight_decay)
+        optimizer = grad_sync.optimizer(Gs.learning_rate, Gs.weight_decay, max_grad_norm=max_grad_norm)
     else:
-        optimizer = Adam(model.parameters(), Gs.learning_rate, weight_decay=Gs.weight_decay)      # torch.optim.Adam's rule (Main.py:192), one launch
+        optimizer = Adam(model.parameters(), Gs.learning_rate, weight_decay=Gs.weight_decay, max_grad_norm=max_grad_norm)      # torch.optim.Adam's rule (Main.py:192), one launch
 
     epoch_start = 1
     if args.checkpoint:

@@ -115,6 +115,11 @@ SIGNATURES = {
                                                    c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_adam_step': (ctypes.c_int, [c_void_p, c_int32, c_float, c_float, c_float, c_float, c_float, c_int64, c_void_p]),
     'ihg_adam_step_device_scalars': (ctypes.c_int, [c_void_p, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    'ihg_grad_sqnorm_workspace_bytes': (c_int64, [c_void_p, c_int32]),
+    'ihg_grad_sqnorm': (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    'ihg_clip_record': (ctypes.c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    'ihg_adam_step_clipped': (ctypes.c_int, [c_void_p, c_int32, c_float, c_float, c_float, c_float, c_float, c_int64, c_void_p, c_void_p]),
+    'ihg_adam_step_clipped_device_scalars': (ctypes.c_int, [c_void_p, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     'ihg_batch_combine': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     'ihg_sample_negatives': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     'ihg_sample_pool': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),

@@ -4,7 +4,8 @@ A step of the hot path is ~85 kernel launches issued from Python through ctypes.
 the bound (the kernels of a C3 step add up to the step's wall time: profiles/r3), so recording buys nothing there; on small graphs
 (config C1: 20,000 hyperedges, every kernel a few microseconds) the step is bound by the host's launch rate, and a replay removes
 that.  What is recorded: forward (``RawGnn.bce_loss``, ``RawGnn.ranking_loss`` under ``Gs.Training.loss`` = bpr / softmax, or ``RawGnn.hard_negative_loss`` under ``Gs.Training.negative_pool`` > 0), backward, and the Adam update with its two step-dependent scalars read from
-device memory (``ihg_adam_step_device_scalars``).  Per replay the host copies the batch into the static input buffers, refreshes the two
+device memory (``ihg_adam_step_device_scalars``; with ``optimizer.max_grad_norm`` set, the gradient norm and the clip record in front of the clipped update - the
+optimizer's clip statistics advance with every replay).  Per replay the host copies the batch into the static input buffers, refreshes the two
 Adam scalars and launches the graph.  Single process only (a recorded RCCL exchange is not attempted).
 """
 from __future__ import annotations
@@ -129,8 +130,10 @@ class CapturedTrainingStep:
         group = self.optimizer.param_groups[0]
         loss = Gs.Training.loss                             # (read at every call, like the head: the recording holds the loss launch that was set - and its group count)
         pool = int(Gs.Training.negative_pool)               # (and the pool with its kept count: the recording holds ihg_hard_negative_loss's launch, or does not)
+        # (max_grad_norm: the recording holds the norm and clip-record launches with the bound as a launch argument, or does not hold them)
         return (tuple(group['betas']), float(group['eps']), float(group['weight_decay']), bool(self.model.batch_rows_only_last_layer),
-                bool(Gs.Prediction.use_cosine_similarity), loss, self.positives if loss != 'bce' or pool else None, pool, int(Gs.random_negative_sample_size) if pool else None)
+                bool(Gs.Prediction.use_cosine_similarity), loss, self.positives if loss != 'bce' or pool else None, pool, int(Gs.random_negative_sample_size) if pool else None,
+                self.optimizer.max_grad_norm)
 
     def _baked_settings(self):
         """Everything a replay cannot change any more: the recording holds the kernels these settings selected.  Only the learning rate is
@@ -146,7 +149,7 @@ class CapturedTrainingStep:
     def stale(self, full: bool = False) -> bool:
         """True when a setting that is baked into the recording has changed since: the caller must record a new step (``TrainTestHelper`` does) - replaying would
         silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer``, the scoring head, the loss kind, (under a ranking loss or a pool) the number of
-        positives, and the hard-negative pool with its kept count - nine values, what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
+        positives, the hard-negative pool with its kept count, and the optimizer's ``max_grad_norm`` - ten values, what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
         epoch, not per replay on the launch-bound path the recording exists for)."""
         if full:
             return self._baked != self._baked_settings()
@@ -172,7 +175,7 @@ class CapturedTrainingStep:
         if positives is not None and (self.loss_kind != 'bce' or self.pool) and int(positives) != self.positives:
             raise ValueError(f'this step was recorded for batches of {self.positives} positives, got {positives}')
         if self.stale():
-            raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay, batch_rows_only_last_layer, the scoring head or the loss - the values '
+            raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay / max_grad_norm, batch_rows_only_last_layer, the scoring head or the loss - the values '
                                'every step() compares; the IHG_* environment and the switches of ihgnn_amd.ops are compared by stale(full=True), which the training loop '
                                'asks once per epoch); record a new step')
         self.users.copy_(users, non_blocking=True)

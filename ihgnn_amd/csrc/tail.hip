@@ -536,22 +536,34 @@ struct AdamTable {
     int n_tensors;
 };
 
+// kClip: g <- g * coef first (torch.nn.utils.clip_grad_norm_ scales the gradient before Adam adds the weight-decay term); the gradient in memory is not rewritten
+template <bool kClip>
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float beta1, float beta2, float eps, float weight_decay,
-                                            float step_size, float bias2_sqrt) {
-    g = weight_decay != 0.f ? g + weight_decay * p : g;
+                                            float step_size, float bias2_sqrt, float coef) {
+    if (kClip) {
+#pragma clang fp contract(off)                               // a product of its own: fused into the decay term's sum, coef = 1 would not give the unclipped instance's bits
+        g = g * coef;
+    }
+    // (the decay term as the one fma the unclipped instance has always been contracted to - written out, so that the clipped instance cannot pair its product
+    // with g * coef in a packed multiply and round it).  That the unclipped instance is bit for bit what `g + weight_decay * p` compiled to rests on the build
+    // keeping hipcc's default -ffp-contract (fast-honor-pragmas): under -ffp-contract=off the old form rounded the product and this one does not.
+    g = weight_decay != 0.f ? fmaf(weight_decay, p, g) : g;
     m = m + (g - m) * (1.f - beta1);                        // torch's lerp form
     v = beta2 * v + (1.f - beta2) * g * g;
     const float denom = sqrtf(v) / bias2_sqrt + eps;
     p = p - step_size * (m / denom);
 }
 
-// `scalars` != nullptr: {step_size, bias2_sqrt} are read from device memory at launch time (a captured launch replays with the step's own values)
+// `scalars` != nullptr: {step_size, bias2_sqrt} are read from device memory at launch time (a captured launch replays with the step's own values).
+// kClip: `clip` = {norm, coef} on the device (clip_record_kernel), every gradient is multiplied by coef as it is read.
+template <bool kClip>
 __global__ __launch_bounds__(kBlockThreads) void adam_kernel(AdamTable tab, float beta1, float beta2, float eps, float weight_decay, float step_size,
-                                                             float bias2_sqrt, const float* __restrict__ scalars) {
+                                                             float bias2_sqrt, const float* __restrict__ scalars, const float* __restrict__ clip) {
     if (scalars != nullptr) {
         step_size = scalars[0];
         bias2_sqrt = scalars[1];
     }
+    const float coef = kClip ? clip[1] : 1.f;
     const int64_t total_chunks = tab.chunk_begin[tab.n_tensors];
     for (int64_t chunk = blockIdx.x; chunk < total_chunks; chunk += gridDim.x) {
         int t = 0;
@@ -572,7 +584,7 @@ __global__ __launch_bounds__(kBlockThreads) void adam_kernel(AdamTable tab, floa
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     float pc = pv[c], mc = mv[c], vc = vv[c];
-                    adam_update(pc, gv[c], mc, vc, beta1, beta2, eps, weight_decay, step_size, bias2_sqrt);
+                    adam_update<kClip>(pc, gv[c], mc, vc, beta1, beta2, eps, weight_decay, step_size, bias2_sqrt, coef);
                     pv[c] = pc; mv[c] = mc; vv[c] = vc;
                 }
                 *reinterpret_cast<v4f*>(p + i) = pv;
@@ -581,8 +593,94 @@ __global__ __launch_bounds__(kBlockThreads) void adam_kernel(AdamTable tab, floa
             }
         } else {
             for (int64_t i = base + threadIdx.x; i < base + kAdamChunk && i < n; i += kBlockThreads)
-                adam_update(p[i], g[i], m[i], v[i], beta1, beta2, eps, weight_decay, step_size, bias2_sqrt);
+                adam_update<kClip>(p[i], g[i], m[i], v[i], beta1, beta2, eps, weight_decay, step_size, bias2_sqrt, coef);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Global gradient norm for clipping (torch.nn.utils.clip_grad_norm_, norm_type 2), over the table Adam takes.  One double per kAdamChunk elements: thread t adds the
+// squares of elements (t + 256 k) 4 + c, k = 0 .. 3, c = 0 .. 3 of its chunk in that order (a float's square is exact in double), six xor-shuffle steps add the lanes,
+// thread 0 adds the four waves in order.  A chunk's partial depends on the chunk alone - not on the grid, not on the pointer's alignment (the scalar path walks the same
+// elements in the same order) - so the sum is bitwise repeatable; no atomics.
+// ------------------------------------------------------------------------------------------------
+struct GradNormTable {
+    const float* grad[kAdamMaxTensors];
+    int64_t chunk_begin[kAdamMaxTensors + 1];
+    int64_t count[kAdamMaxTensors];
+    int n_tensors;
+};
+
+__device__ __forceinline__ double block_sum_fixed_order(double acc) {        // every thread of the workgroup calls; the result is valid in thread 0
+    __shared__ double waves[kWavesPerBlock];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double total = 0.0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) total += waves[w];
+    }
+    __syncthreads();                                         // (the next trip writes `waves` again)
+    return total;
+}
+
+__global__ __launch_bounds__(kBlockThreads) void grad_sqnorm_partial_kernel(GradNormTable tab, double* __restrict__ partials) {
+    const int64_t total_chunks = tab.chunk_begin[tab.n_tensors];
+    for (int64_t chunk = blockIdx.x; chunk < total_chunks; chunk += gridDim.x) {
+        int t = 0;
+        while (chunk >= tab.chunk_begin[t + 1]) ++t;
+        const int64_t base = (chunk - tab.chunk_begin[t]) * kAdamChunk;
+        const int64_t n = tab.count[t];
+        const float* __restrict__ g = tab.grad[t];
+        double acc = 0.0;
+        if ((reinterpret_cast<uintptr_t>(g) & 15) == 0 && base + kAdamChunk <= n) {
+#pragma unroll
+            for (int k = 0; k < kAdamChunk / (4 * kBlockThreads); ++k) {
+                const v4f gv = *reinterpret_cast<const v4f*>(g + base + (threadIdx.x + k * kBlockThreads) * 4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const double x = static_cast<double>(gv[c]);
+                    acc += x * x;
+                }
+            }
+        } else {
+            for (int k = 0; k < kAdamChunk / (4 * kBlockThreads); ++k) {
+                const int64_t i = base + (threadIdx.x + k * kBlockThreads) * 4;
+                for (int c = 0; c < 4 && i + c < n; ++c) {
+                    const double x = static_cast<double>(g[i + c]);
+                    acc += x * x;
+                }
+            }
+        }
+        const double total = block_sum_fixed_order(acc);
+        if (threadIdx.x == 0) partials[chunk] = total;
+    }
+}
+
+// one workgroup: thread t adds partials t, t + 256, ... in order, then the same wave and LDS tree
+__global__ __launch_bounds__(kBlockThreads) void grad_sqnorm_finish_kernel(const double* __restrict__ partials, int64_t n_partials, double* __restrict__ sum) {
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n_partials; i += kBlockThreads) acc += partials[i];
+    const double total = block_sum_fixed_order(acc);
+    if (threadIdx.x == 0) *sum = total;
+}
+
+// clip = {norm, coef}: norm = (float) sqrt(sum), coef = min(max_norm / (norm + 1e-6), 1) as torch.clamp(max=1) takes it - a NaN stays a NaN (fminf would return 1).
+// stats (optional) = {largest norm so far, steps with coef < 1, steps}.  One thread, plain stores.
+__global__ void clip_record_kernel(const double* __restrict__ sum, float max_norm, float* __restrict__ clip, float* __restrict__ stats) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float norm = static_cast<float>(sqrt(*sum));
+    float coef = max_norm / (norm + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;
+    clip[0] = norm;
+    clip[1] = coef;
+    if (stats != nullptr) {
+        const float seen = stats[0];
+        stats[0] = norm > seen ? norm : seen;
+        stats[1] = stats[1] + (coef < 1.f ? 1.f : 0.f);
+        stats[2] = stats[2] + 1.f;
     }
 }
 
@@ -989,7 +1087,7 @@ int ihg_batch_node_rows(const int64_t* users, const int64_t* queries, const int6
 }
 
 static int adam_launch(const char* what, const ihg_adam_tensor* tensors, int32_t n_tensors, float beta1, float beta2, float eps, float weight_decay, float step_size,
-                       float bias2_sqrt, const float* scalars, ihg_stream_t stream) {
+                       float bias2_sqrt, const float* scalars, const float* clip, ihg_stream_t stream) {
     for (int t = 0; t < n_tensors; ++t) {                    // every tensor is checked before the first launch: a refused call has updated nothing
         const ihg_adam_tensor& a = tensors[t];
         if (a.count < 0 || (a.count > 0 && (a.param == nullptr || a.grad == nullptr || a.exp_avg == nullptr || a.exp_avg_sq == nullptr)))
@@ -1013,8 +1111,12 @@ static int adam_launch(const char* what, const ihg_adam_tensor* tensors, int32_t
         tab.n_tensors = used;
         if (used == 0) continue;
         const int grid = static_cast<int>(std::min<int64_t>(chunks, 256 * 16));
-        hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), tab, beta1, beta2, eps, weight_decay,
-                           step_size, bias2_sqrt, scalars);
+        if (clip != nullptr)
+            hipLaunchKernelGGL(adam_kernel<true>, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), tab, beta1, beta2, eps, weight_decay,
+                               step_size, bias2_sqrt, scalars, clip);
+        else
+            hipLaunchKernelGGL(adam_kernel<false>, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), tab, beta1, beta2, eps, weight_decay,
+                               step_size, bias2_sqrt, scalars, clip);
         launched = true;
     }
     return launched ? check_launch(what) : IHG_OK;           // (only empty tensors: nothing was launched, the runtime is not asked)
@@ -1026,12 +1128,91 @@ int ihg_adam_step(const ihg_adam_tensor* tensors, int32_t n_tensors, float lr, f
     const double bias1 = 1.0 - std::pow(static_cast<double>(beta1), static_cast<double>(step));
     const double bias2 = 1.0 - std::pow(static_cast<double>(beta2), static_cast<double>(step));
     return adam_launch("ihg_adam_step", tensors, n_tensors, beta1, beta2, eps, weight_decay, static_cast<float>(static_cast<double>(lr) / bias1),
-                       static_cast<float>(std::sqrt(bias2)), nullptr, stream);
+                       static_cast<float>(std::sqrt(bias2)), nullptr, nullptr, stream);
 }
 
 int ihg_adam_step_device_scalars(const ihg_adam_tensor* tensors, int32_t n_tensors, float beta1, float beta2, float eps, float weight_decay,
                                  const float* step_scalars, ihg_stream_t stream) {
     if (n_tensors < 0 || (n_tensors > 0 && tensors == nullptr) || step_scalars == nullptr) return fail(IHG_ERR_INVALID, "ihg_adam_step_device_scalars: bad argument");
-    return adam_launch("ihg_adam_step_device_scalars", tensors, n_tensors, beta1, beta2, eps, weight_decay, 0.f, 1.f, step_scalars, stream);
+    return adam_launch("ihg_adam_step_device_scalars", tensors, n_tensors, beta1, beta2, eps, weight_decay, 0.f, 1.f, step_scalars, nullptr, stream);
+}
+
+int ihg_adam_step_clipped(const ihg_adam_tensor* tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          int64_t step, const float* clip, ihg_stream_t stream) {
+    if (n_tensors < 0 || (n_tensors > 0 && tensors == nullptr) || step < 1 || clip == nullptr) return fail(IHG_ERR_INVALID, "ihg_adam_step_clipped: bad argument");
+    const double bias1 = 1.0 - std::pow(static_cast<double>(beta1), static_cast<double>(step));
+    const double bias2 = 1.0 - std::pow(static_cast<double>(beta2), static_cast<double>(step));
+    return adam_launch("ihg_adam_step_clipped", tensors, n_tensors, beta1, beta2, eps, weight_decay, static_cast<float>(static_cast<double>(lr) / bias1),
+                       static_cast<float>(std::sqrt(bias2)), nullptr, clip, stream);
+}
+
+int ihg_adam_step_clipped_device_scalars(const ihg_adam_tensor* tensors, int32_t n_tensors, float beta1, float beta2, float eps, float weight_decay,
+                                         const float* step_scalars, const float* clip, ihg_stream_t stream) {
+    if (n_tensors < 0 || (n_tensors > 0 && tensors == nullptr) || step_scalars == nullptr || clip == nullptr)
+        return fail(IHG_ERR_INVALID, "ihg_adam_step_clipped_device_scalars: bad argument");
+    return adam_launch("ihg_adam_step_clipped_device_scalars", tensors, n_tensors, beta1, beta2, eps, weight_decay, 0.f, 1.f, step_scalars, clip, stream);
+}
+
+// chunks of the non-empty tensors, or -1 for a bad table (a negative count, a gradient missing where count > 0)
+static int64_t grad_sqnorm_chunks(const char* what, const ihg_adam_tensor* tensors, int32_t n_tensors) {
+    if (n_tensors < 0 || (n_tensors > 0 && tensors == nullptr)) {
+        fail(IHG_ERR_INVALID, "%s: bad argument", what);
+        return -1;
+    }
+    int64_t chunks = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        if (tensors[t].count < 0 || (tensors[t].count > 0 && tensors[t].grad == nullptr)) {
+            fail(IHG_ERR_INVALID, "%s: tensor %d has a null gradient or a negative count", what, t);
+            return -1;
+        }
+        chunks += (tensors[t].count + kAdamChunk - 1) / kAdamChunk;
+    }
+    return chunks;
+}
+
+int64_t ihg_grad_sqnorm_workspace_bytes(const ihg_adam_tensor* tensors, int32_t n_tensors) {
+    const int64_t chunks = grad_sqnorm_chunks("ihg_grad_sqnorm_workspace_bytes", tensors, n_tensors);
+    return chunks < 0 ? -1 : chunks * static_cast<int64_t>(sizeof(double));
+}
+
+int ihg_grad_sqnorm(const ihg_adam_tensor* tensors, int32_t n_tensors, void* workspace, int64_t workspace_bytes, double* sum, ihg_stream_t stream) {
+    const int64_t total = grad_sqnorm_chunks("ihg_grad_sqnorm", tensors, n_tensors);
+    if (total < 0) return IHG_ERR_INVALID;
+    if (sum == nullptr || (reinterpret_cast<uintptr_t>(sum) & 7) != 0) return fail(IHG_ERR_INVALID, "ihg_grad_sqnorm: sum is null or not 8-byte aligned");
+    if (total > 0 && (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0))
+        return fail(IHG_ERR_INVALID, "ihg_grad_sqnorm: workspace is null or not 8-byte aligned");
+    if (workspace_bytes < total * static_cast<int64_t>(sizeof(double)))
+        return fail(IHG_ERR_WORKSPACE, "ihg_grad_sqnorm: workspace too small (%lld bytes, %lld needed)", (long long)workspace_bytes, (long long)(total * sizeof(double)));
+    double* partials = static_cast<double*>(workspace);
+    int64_t done = 0;                                        // chunks of the launches so far: the numbering goes on through the workspace
+    for (int t = 0; t < n_tensors;) {
+        GradNormTable tab{};
+        int64_t chunks = 0;
+        int used = 0;
+        for (; t < n_tensors && used < kAdamMaxTensors; ++t) {
+            const ihg_adam_tensor& a = tensors[t];
+            if (a.count == 0) continue;
+            tab.grad[used] = a.grad;
+            tab.count[used] = a.count;
+            tab.chunk_begin[used] = chunks;
+            chunks += (a.count + kAdamChunk - 1) / kAdamChunk;
+            ++used;
+        }
+        tab.chunk_begin[used] = chunks;
+        tab.n_tensors = used;
+        if (used == 0) continue;
+        const int grid = static_cast<int>(std::min<int64_t>(chunks, 256 * 16));
+        hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3(grid), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), tab, partials + done);
+        done += chunks;
+    }
+    hipLaunchKernelGGL(grad_sqnorm_finish_kernel, dim3(1), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), partials, done, sum);      // (no chunks: sum = 0)
+    return check_launch("ihg_grad_sqnorm");
+}
+
+int ihg_clip_record(const double* sum, float max_norm, float* clip, float* stats, ihg_stream_t stream) {
+    if (sum == nullptr || clip == nullptr || (reinterpret_cast<uintptr_t>(sum) & 7) != 0) return fail(IHG_ERR_INVALID, "ihg_clip_record: null pointer or unaligned sum");
+    if (!(max_norm >= 0.f)) return fail(IHG_ERR_INVALID, "ihg_clip_record: max_norm must be >= 0 (inf allowed), got %g", static_cast<double>(max_norm));
+    hipLaunchKernelGGL(clip_record_kernel, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), sum, max_norm, clip, stats);
+    return check_launch("ihg_clip_record");
 }
 }  // extern "C"

@@ -201,22 +201,63 @@ class BucketedGradientSync(GradientSync):
 
 
 class _ShardOptimizer:
-    def __init__(self, sync: 'ShardedGradientSync', lr: float, weight_decay: float):
+    def __init__(self, sync: 'ShardedGradientSync', lr: float, weight_decay: float, max_grad_norm: Optional[float] = None):
         self.sync = sync
         shard = torch.nn.Parameter(sync.param_shard)
         shard.grad = sync.grad_shard
         self.shard = shard
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         if shard.is_cuda:
             from .optim import Adam
-            self.inner = Adam([shard], lr, weight_decay=weight_decay)
+            self.inner = Adam([shard], lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+            if max_grad_norm is not None and sync.distributed:
+                # the global norm: every rank adds the squares of its shard of the averaged gradient (the padding entries are zero), ONE double is all-reduced between
+                # the norm and the clip record, and every rank forms the same record
+                self.inner._sum_reduce = lambda total: dist.all_reduce(total, op=dist.ReduceOp.SUM, group=sync.group)
         else:
             self.inner = torch.optim.Adam([shard], lr, weight_decay=weight_decay)
         self.param_groups = self.inner.param_groups
+        self._host_stats = torch.zeros(3)                    # (the CPU form, which the gloo tests run: largest norm, clipped steps, steps)
+        self._host_record = None                             # ... and its (norm, coef) of the last step
+
+    def _clipped_on_the_host(self) -> torch.Tensor:
+        """The CPU form of the clipped step (``torch.optim.Adam`` inside, which takes no coefficient): the same global norm from the ranks' sums of squares, and the
+        scaled gradient as a NEW tensor - ``grad_shard`` keeps its values, as ``.grad`` does on the GPU.  The statistics are kept as the clip launch keeps them."""
+        grad = self.sync.grad_shard
+        total = grad.double().pow(2).sum().reshape(1)
+        if self.sync.distributed:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.sync.group)
+        norm = total.sqrt().float()
+        coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+        stats = self._host_stats
+        stats[0] = torch.where(norm[0] > stats[0], norm[0], stats[0])
+        stats[1] += (coef[0] < 1.0).float()
+        stats[2] += 1.0
+        self._host_record = torch.cat([norm, coef])
+        return grad * coef
 
     def step(self):
         self.shard.grad = self.sync.grad_shard
-        self.inner.step()
+        if self.max_grad_norm is not None and not self.shard.is_cuda:
+            self.shard.grad = self._clipped_on_the_host()
+            self.inner.step()
+            self.shard.grad = self.sync.grad_shard
+        else:
+            self.inner.step()
         self.sync.gather_parameters()
+
+    @property
+    def grad_norm(self):
+        return self.inner.grad_norm if self.shard.is_cuda else self._host_record
+
+    def clip_statistics(self, reset: bool = True):
+        """``(largest gradient norm, clipped steps, steps)`` since the last reset, as ``ihgnn_amd.optim.Adam.clip_statistics``."""
+        if self.shard.is_cuda:
+            return self.inner.clip_statistics(reset)
+        largest, clipped, steps = self._host_stats.tolist()
+        if reset:
+            self._host_stats.zero_()
+        return largest, int(clipped), int(steps)
 
     def zero_grad(self, set_to_none: bool = False):
         self.sync.zero_grad()
@@ -308,7 +349,15 @@ class _ShardOptimizer:
         if not inner['state']:                               # no step taken yet: let the inner optimizer create its buffers
             self.shard.grad = torch.zeros_like(self.shard)
             saved = self.shard.detach().clone()
-            self.inner.step()
+            # (this step only creates the buffers: it is not one of the run's, so it clips nothing, counts nothing and - loading stays a local call - reduces nothing)
+            bound = getattr(self.inner, 'max_grad_norm', None)
+            if bound is not None:
+                self.inner.max_grad_norm = None
+            try:
+                self.inner.step()
+            finally:
+                if bound is not None:
+                    self.inner.max_grad_norm = bound
             with torch.no_grad():
                 self.shard.copy_(saved)
             inner = self.inner.state_dict()
@@ -356,8 +405,8 @@ class ShardedGradientSync(GradientSync):
         self.param_shard = self.flat_params[self.shard_range[0]:self.shard_range[1]]
         self.grad_shard = torch.zeros(share, dtype=ref.dtype, device=ref.device)
 
-    def optimizer(self, lr: float, weight_decay: float = 0.0) -> _ShardOptimizer:
-        return _ShardOptimizer(self, lr, weight_decay)
+    def optimizer(self, lr: float, weight_decay: float = 0.0, max_grad_norm: Optional[float] = None) -> _ShardOptimizer:
+        return _ShardOptimizer(self, lr, weight_decay, max_grad_norm)
 
     def average_gradients(self):
         self._reattach()

@@ -539,6 +539,28 @@ int ihg_adam_step(const ihg_adam_tensor* tensors, int32_t n_tensors, float lr, f
 int ihg_adam_step_device_scalars(const ihg_adam_tensor* tensors, int32_t n_tensors, float beta1, float beta2, float eps, float weight_decay,
                                  const float* step_scalars, ihg_stream_t stream);
 
+/* Clipping by the global L2 norm of the gradients, torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False) followed by Adam.step()
+ * (nothing in the reference, whose step has no clipping), in three launches around the table Adam takes:
+ *
+ *   ihg_grad_sqnorm   *sum (a DEVICE double) = sum of grad^2 over every tensor of the table (it reads `grad` and `count` only).  One partial per 4,096 elements of a
+ *                     tensor in `workspace` (ihg_grad_sqnorm_workspace_bytes(tensors, n_tensors) = 8 bytes per chunk, 8-byte aligned; -1 for a bad table), every
+ *                     element squared and added in double in a fixed order, the partials added in a fixed order by one workgroup: no atomics, the same bits on
+ *                     every call whatever the grid, and a float's square never overflows.  An empty table gives 0.
+ *   ihg_clip_record   clip[0] = norm = (float) sqrt(*sum); clip[1] = coef = max_norm / (norm + 1e-6f), at most 1 (a NaN stays a NaN, as torch.clamp(max=1) leaves
+ *                     it).  `stats` (may be null), three floats the caller zeroes once: the largest norm so far, the calls with coef < 1, the calls.  max_norm >= 0;
+ *                     +inf is allowed (coef = 1 unless the norm is inf or NaN).  Separate from the sum so that ranks that hold shards of the gradient can add their
+ *                     sums in between.
+ *   ihg_adam_step_clipped / _clipped_device_scalars   ihg_adam_step / ihg_adam_step_device_scalars on g * clip[1] (the product is formed before the weight-decay
+ *                     term, the order torch gives).  `grad` itself is NOT rewritten - the one difference from torch; the scaled gradient is grad * clip[1].
+ *                     With clip[1] == 1 the result is bit for bit the unclipped entry's. */
+int64_t ihg_grad_sqnorm_workspace_bytes(const ihg_adam_tensor* tensors, int32_t n_tensors);
+int ihg_grad_sqnorm(const ihg_adam_tensor* tensors, int32_t n_tensors, void* workspace, int64_t workspace_bytes, double* sum, ihg_stream_t stream);
+int ihg_clip_record(const double* sum, float max_norm, float* clip, float* stats, ihg_stream_t stream);
+int ihg_adam_step_clipped(const ihg_adam_tensor* tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int64_t step, const float* clip, ihg_stream_t stream);
+int ihg_adam_step_clipped_device_scalars(const ihg_adam_tensor* tensors, int32_t n_tensors, float beta1, float beta2, float eps, float weight_decay,
+                                         const float* step_scalars, const float* clip, ihg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DEVICE: negative sampling of a training batch.  Replaces `random.sample(range(item_count), k)` per positive in
  * GraphDataset.__getitem__ (Dataset.py:107-109): out[row][0..k) = k DISTINCT item ids, uniform over [0, n_items), the positive
