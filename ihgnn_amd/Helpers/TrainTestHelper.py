@@ -206,12 +206,9 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
     first epoch run eagerly, steps 4 - 7 are timed, and the step is recorded when they took less than ``AUTO_RECORD_BELOW_MS`` each; ``'on'`` / ``'off'`` decide
     without measuring.  A model the recording refuses (a parameter without gradient) trains eagerly, with one log line.
 
-    ``Gs.Training.loss`` other than ``'bce'`` (``--loss bpr | softmax``): a step is ``model.ranking_loss`` over the batch's groups (every positive with its own negatives)
-    where the fused batch tail runs, ``ops.ranking_loss`` on the model's scores where it does not; ``loss_function`` and the labels are then not used.
-
-    ``Gs.Training.negative_pool`` = M > 0 (``--hard_negatives M``; the loader draws M candidates per positive): a step is ``model.hard_negative_loss`` - the objective
-    ``Gs.Training.loss`` names, ``'bce'`` included, over every positive and the ``Gs.random_negative_sample_size`` candidates of its pool that score highest - where the
-    fused tail runs, ``ops.hard_negative_loss`` on the model's scores where it does not; the labels are not used either."""
+    The objective of every step is ``ops.training_objective``'s (the settings ``--loss`` and ``--hard_negatives M`` write): a step is ``model.training_loss`` where the
+    fused batch tail runs; where it does not, ``ops.objective_loss`` on the model's scores under an objective over groups (a ranking loss of every positive against
+    its own negatives, or any loss over the best of a pool of M candidates: ``loss_function`` and the labels are then not used) and ``loss_function`` otherwise."""
     from ..Models.Srrl import Srrl
     if isinstance(model, Srrl):
         if grad_sync is not None or _record_mode(record_step) == 'on':
@@ -224,6 +221,7 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
     if hasattr(sampler, 'set_epoch'):
         sampler.set_epoch(pc.CurrentEpoch)                  # data parallel: a fresh shared permutation per epoch (ShardedBatchSampler)
     mode = _record_mode(record_step)
+    from .. import ops
     from ..optim import Adam as _HipAdam
     can_record = mode != 'off' and grad_sync is None and device.type == 'cuda' and isinstance(optimizer, _HipAdam)
     decision = getattr(model, '_record_decision', None) if can_record else False       # None: undecided (auto, still measuring); True / False
@@ -237,14 +235,8 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
         positives += len(p_u)
         users, queries, items = torch.cat([p_u, n_u]), torch.cat([p_q, n_q]), torch.cat([p_i, n_i])
         flags = torch.cat([p_f, n_f]).float()
-        kind = Gs.Training.loss                             # read per step, as the model reads its head
-        pool = Gs.Training.negative_pool                    # (the loader drew this many candidates per positive; the step keeps the best random_negative_sample_size)
-        keep = Gs.random_negative_sample_size
-        ranking = kind != 'bce' or bool(pool)               # a step over groups: no labels, no loss_function
-        if pool and len(n_u) != pool * len(p_u):
-            raise ValueError(f'Gs.Training.negative_pool = {pool}, but the loader drew {len(n_u)} negatives for {len(p_u)} positives: build the dataset with '
-                             'random_negative_sample_size = the pool size (Main does)')
-        if ranking:
+        objective = ops.training_objective(len(users), len(p_u))      # the settings are read per step, as the model reads its head; grouped: no labels, no loss_function
+        if objective.grouped:
             fused = getattr(model, 'supports_fused_tail', None) and model.supports_fused_tail()
         else:
             fused = getattr(model, 'supports_fused_loss', None) and model.supports_fused_loss(loss_function)
@@ -254,7 +246,7 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
                 from ..captured_step import CapturedTrainingStep
                 try:
                     recorded = model._recorded_step = CapturedTrainingStep(model, optimizer, int(users.shape[0]), warmup_batch=(users, queries, items, flags),
-                                                                                  positives=len(p_u) if ranking else None)
+                                                                                  positives=objective.positives)
                 except (ValueError, RuntimeError) as refused:
                     # ValueError: the recording's own refusal (a parameter without gradient, ...); RuntimeError: the stream capture failed (an op that synchronises,
                     # an allocation the capture cannot hold) - under 'auto' nobody asked for a recording, so either way the run goes on eagerly; under 'on' a
@@ -265,7 +257,7 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
                     recorded, decision = None, False
                     model._recorded_step, model._record_decision, model._record_refused = None, False, True
                     optimizer.zero_grad(set_to_none=True)
-            if recorded is not None and recorded.batch_rows == int(users.shape[0]) and (not ranking or recorded.positives == len(p_u)):
+            if recorded is not None and recorded.batch_rows == int(users.shape[0]) and (not objective.grouped or recorded.positives == objective.positives):
                 loss_sum += recorded.step(users, queries, items, flags, positives=len(p_u))
                 batches += 1
                 continue
@@ -279,23 +271,14 @@ def train_and_get_avg_loss(model, optimizer: optim.Optimizer, loss_function: nn.
         cotangent = getattr(grad_sync, 'mode', None) == 'cotangent'
         if cotangent and not fused:
             raise RuntimeError('--grad_sync cotangent exchanges the fused batch tail\'s row gradients: it needs the HIP model and a plain BCEWithLogitsLoss (use bucketed / sharded)')
-        if pool and fused:
-            loss = model.hard_negative_loss(users, queries, items, positives=len(p_u), keep=keep, kind=kind, cotangent_sync=grad_sync if cotangent else None)
-        elif pool:
-            from .. import ops
-            loss = ops.hard_negative_loss(model(users, queries, items), len(p_u), keep, kind)
-        elif ranking and fused:
-            loss = model.ranking_loss(users, queries, items, positives=len(p_u), kind=kind, cotangent_sync=grad_sync if cotangent else None)
-        elif ranking:
-            from .. import ops
-            loss = ops.ranking_loss(model(users, queries, items), len(p_u), kind)
-        elif fused:
-            loss = model.bce_loss(users, queries, items, flags, cotangent_sync=grad_sync) if cotangent else model.bce_loss(users, queries, items, flags)
+        if fused:
+            loss = model.training_loss(users, queries, items, objective, flags, cotangent_sync=grad_sync if cotangent else None)
+        elif objective.grouped:
+            loss = ops.objective_loss(model(users, queries, items), objective)
         else:
             loss = loss_function(model(users, queries, items), flags)
         loss_sum += loss.detach()
         if loss.is_cuda:
-            from .. import ops
             ops.backward(loss)                               # loss.backward() with a cached root gradient (no fill launch per step)
         else:
             loss.backward()

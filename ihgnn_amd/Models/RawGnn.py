@@ -220,7 +220,8 @@ class RawGnn(nn.Module):
         MEAN of all ranks' losses - the ranks exchange the batch rows' cotangents (not the dense gradients) and every rank runs the propagation backward on their
         union; the layers are told the union of the ranks' batch rows (where the last layer's output is read / its cotangent is non-zero).  A COLLECTIVE: every
         rank calls it, with batches of the same size."""
-        return self._fused_loss(user_indices, query_indices, item_indices, labels, None, cotangent_sync)
+        from .. import ops
+        return self.training_loss(user_indices, query_indices, item_indices, ops.bce_objective(), labels, cotangent_sync)
 
     def ranking_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, positives: int, kind: Optional[str] = None, cotangent_sync=None) -> Tensor:
         """``ops.ranking_loss(self(u, q, i), positives, kind)`` through the fused batch tail: ``bce_loss`` with the BPR (``'bpr'``) or sampled-softmax (``'softmax'``)
@@ -232,7 +233,7 @@ class RawGnn(nn.Module):
         if kind == 'bce':
             raise ValueError('RawGnn.ranking_loss: the BCE needs labels - use bce_loss (Gs.Training.loss is \'bce\')')
         objective = ops.ranking_objective(int(item_indices.shape[0]), positives, kind)
-        return self._fused_loss(user_indices, query_indices, item_indices, None, objective, cotangent_sync)
+        return self.training_loss(user_indices, query_indices, item_indices, objective, cotangent_sync=cotangent_sync)
 
     def hard_negative_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, positives: int, keep: int, kind: Optional[str] = None,
                            cotangent_sync=None, return_selected: bool = False):
@@ -245,12 +246,13 @@ class RawGnn(nn.Module):
         from .. import ops
         kind = Gs.Training.loss if kind is None else kind
         objective = ops.hard_negative_objective(int(item_indices.shape[0]), positives, keep, kind)
-        loss = self._fused_loss(user_indices, query_indices, item_indices, None, objective, cotangent_sync)
+        loss = self.training_loss(user_indices, query_indices, item_indices, objective, cotangent_sync=cotangent_sync)
         return (loss, objective.selected.to(torch.int64)) if return_selected else loss
 
-    def _fused_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, labels: Optional[Tensor], objective, cotangent_sync) -> Tensor:
-        """The training loss through the fused batch tail: the BCE over ``labels`` (``objective`` None), a ranking loss (``ops.ranking_objective``'s pair) or the
-        hard-negative objective (``ops.hard_negative_objective``'s)."""
+    def training_loss(self, user_indices: Tensor, query_indices: Tensor, item_indices: Tensor, objective, labels: Optional[Tensor] = None, cotangent_sync=None) -> Tensor:
+        """The training loss of a batch under ``objective`` (an ``ops.Objective``: the BCE over ``labels``, a ranking loss, or either over hard negatives - after which it
+        holds ``selected``) through the fused batch tail: the shared body of ``bce_loss``, ``ranking_loss`` and ``hard_negative_loss``, and what the training loops call.
+        ``cotangent_sync``: as in ``bce_loss``."""
         from .. import ops
         ds, head = self.dataset, self.prediction_layer
         cosine = bool(Gs.Prediction.use_cosine_similarity)       # read at every call, as the reference's head does (PredictionLayers.py:38)
@@ -265,23 +267,16 @@ class RawGnn(nn.Module):
         if compact is not None and holder is None:
             # (no gradient wanted: the public matrices, the plain tail)
             scores = ops.hem_score(self.propagate_layers(), rows, item_indices, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, cosine=cosine)
-            if isinstance(objective, ops.HardNegatives):
-                return ops._HardNegativeLoss.apply(scores, objective)
-            if objective is not None:
-                return ops.ranking_loss(scores, *objective)
+            if objective.grouped:
+                return ops.objective_loss(scores, objective)
+            # (the plain BCE of this route has always been torch's: an evaluation loss computed here keeps its bits only with this call, not with the HIP launch)
             return nn.functional.binary_cross_entropy_with_logits(scores, labels.float())
         if compact is not None:
             holder.row_map = compact.node_map
         layers = self.propagate_layers(holder, read_rows, self.batch_rows_only_last_layer)
         rows_upper = compact.compact_rows(rows) if compact is not None else None
-        if isinstance(objective, ops.HardNegatives):
-            return ops.hem_hard_negative_loss(layers, rows, item_indices, objective, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
-                                              rows_upper=rows_upper, cosine=cosine)
-        if objective is not None:
-            return ops.hem_ranking_loss(layers, rows, item_indices, *objective, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
-                                        rows_upper=rows_upper, cosine=cosine)
-        return ops.hem_bce_loss(layers, rows, item_indices, labels, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
-                                rows_upper=rows_upper, cosine=cosine)
+        return ops.hem_loss(layers, rows, item_indices, objective, head.items_bias, head.lambda_muq, ds.item_start_index_in_graph, holder,
+                            rows_upper=rows_upper, cosine=cosine, labels=labels)
 
     def supports_fused_loss(self, loss_function) -> bool:
         return (isinstance(loss_function, nn.BCEWithLogitsLoss) and loss_function.reduction == 'mean' and loss_function.weight is None

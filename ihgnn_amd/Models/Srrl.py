@@ -126,6 +126,12 @@ class Srrl(nn.Module):
         """``nn.BCEWithLogitsLoss()(self(uids, queries, items), labels)`` with the loss and its gradient from one launch."""
         return ops.bce_with_logits(self(uids, queries, items), labels)
 
+    def training_loss(self, uids: Tensor, queries: Tensor, items: Tensor, objective, labels: Optional[Tensor] = None, cotangent_sync=None) -> Tensor:
+        """``RawGnn.training_loss``'s signature; the baseline trains on the BCE over ``labels`` alone, in one process (``Main.check_srrl_settings`` refuses the rest)."""
+        if objective.grouped or cotangent_sync is not None:
+            raise NotImplementedError('the Srrl baseline trains on the BCE in one process: no --loss bpr | softmax, no --hard_negatives, no gradient exchange')
+        return self.bce_loss(uids, queries, items, labels)
+
     def save_features_for_test(self) -> None:
         """Evaluation (no gradient): keeps the tables, and what does not depend on the (user, query) pair - ``g_i`` over all items."""
         self._saved_u_ps, self._saved_i_ps = self.PS.embed_user(), self.PS.embed_item()

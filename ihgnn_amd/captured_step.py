@@ -3,7 +3,7 @@
 A step of the hot path is ~85 kernel launches issued from Python through ctypes.  At the BASELINE workloads from C2 up the GPU is
 the bound (the kernels of a C3 step add up to the step's wall time: profiles/r3), so recording buys nothing there; on small graphs
 (config C1: 20,000 hyperedges, every kernel a few microseconds) the step is bound by the host's launch rate, and a replay removes
-that.  What is recorded: forward (``RawGnn.bce_loss``, ``RawGnn.ranking_loss`` under ``Gs.Training.loss`` = bpr / softmax, or ``RawGnn.hard_negative_loss`` under ``Gs.Training.negative_pool`` > 0), backward, and the Adam update with its two step-dependent scalars read from
+that.  What is recorded: forward (``RawGnn.training_loss`` under the objective the settings name, ``ops.training_objective``), backward, and the Adam update with its two step-dependent scalars read from
 device memory (``ihg_adam_step_device_scalars``; with ``optimizer.max_grad_norm`` set, the gradient norm and the clip record in front of the clipped update - the
 optimizer's clip statistics advance with every replay).  Per replay the host copies the batch into the static input buffers, refreshes the two
 Adam scalars and launches the graph.  Single process only (a recorded RCCL exchange is not attempted).
@@ -20,10 +20,10 @@ class CapturedTrainingStep:
 
         loss = model.bce_loss(users, queries, items, labels); loss.backward(); optimizer.step(); optimizer.zero_grad()
 
-    for batches of ``batch_rows`` rows.  The learning rate may change between calls (it enters through the device scalars).  Under a ranking loss (``Gs.Training.loss``
-    other than ``'bce'``, read when the step is recorded) the recorded forward is ``model.ranking_loss(users, queries, items, positives)``: ``positives`` is then
-    required, and the labels are carried but not read.  With ``Gs.Training.negative_pool`` set (read then too) it is
-    ``model.hard_negative_loss(users, queries, items, positives, Gs.random_negative_sample_size)`` under any loss, ``positives`` required as well."""
+    for batches of ``batch_rows`` rows.  The learning rate may change between calls (it enters through the device scalars).  The objective is ``ops.training_objective``'s,
+    read when the step is recorded: under a loss over groups (``--loss bpr | softmax``, or any loss with ``--hard_negatives M``) the recorded forward is what
+    ``model.ranking_loss(users, queries, items, positives)`` / ``model.hard_negative_loss(users, queries, items, positives, Gs.random_negative_sample_size)`` run;
+    ``positives`` is then required, and the labels are carried but not read."""
 
     def __init__(self, model, optimizer: Adam, batch_rows: int, warmup_batch=None, positives=None):
         if not isinstance(optimizer, Adam):
@@ -32,23 +32,13 @@ class CapturedTrainingStep:
             # (a ValueError: the training loop then goes on eagerly with one log line, TrainTestHelper.train_and_get_avg_loss)
             raise ValueError('CapturedTrainingStep: a model with phase-2 attention is not recorded (its step has not been replayed against the eager one)')
         self.model, self.optimizer, self.batch_rows = model, optimizer, int(batch_rows)
-        from .Helpers.GlobalSettings import Gs
-        self.loss_kind = Gs.Training.loss
-        self.pool = int(Gs.Training.negative_pool)          # hard negatives (read when the step is recorded, like the loss): the batch carries a pool per positive ...
-        self.keep = int(Gs.random_negative_sample_size) if self.pool else None      # ... of which the step keeps this many
         self.positives = None if positives is None else int(positives)
-        if self.loss_kind != 'bce' or self.pool:
-            if self.positives is None:
-                raise ValueError(f'CapturedTrainingStep: Gs.Training.loss = {self.loss_kind!r}' + (f' with a pool of {self.pool}' if self.pool else '') +
-                                 ' needs positives= (the batch is P positives followed by the negatives of each)')
-            from . import ops
-            # the host check, before anything is recorded
-            if self.pool:
-                objective = ops.hard_negative_objective(self.batch_rows, self.positives, self.keep, self.loss_kind)
-                if objective.pool != self.pool:
-                    raise ValueError(f'CapturedTrainingStep: Gs.Training.negative_pool = {self.pool}, but {self.batch_rows} rows over {self.positives} positives carry a pool of {objective.pool}')
-            else:
-                ops.ranking_objective(self.batch_rows, self.positives, self.loss_kind)
+        from . import _lib, ops
+        # the objective the settings name when the step is recorded - the host check, before anything is recorded (every forward below makes its own: a launch writes into it)
+        self.objective = objective = ops.training_objective(self.batch_rows, self.positives)
+        self.loss_kind = next(name for name, code in _lib.HARD_NEGATIVE_KINDS.items() if code == objective.kind)
+        # hard negatives: the batch carries a pool per positive, of which the step keeps this many
+        self.pool, self.keep = (objective.pool, objective.keep) if objective.hard else (0, None)
         dev = next(model.parameters()).device
         self.users = torch.zeros(batch_rows, dtype=torch.int64, device=dev)
         self.queries = torch.zeros(batch_rows, dtype=torch.int64, device=dev)
@@ -85,12 +75,7 @@ class CapturedTrainingStep:
             try:
                 for module, name, p in slots:
                     module._parameters[name] = aliases[id(p)]
-                if self.pool:
-                    loss = model.hard_negative_loss(self.users, self.queries, self.items, self.positives, self.keep, self.loss_kind)
-                elif self.loss_kind != 'bce':
-                    loss = model.ranking_loss(self.users, self.queries, self.items, self.positives, self.loss_kind)
-                else:
-                    loss = model.bce_loss(self.users, self.queries, self.items, self.labels)
+                loss = model.training_loss(self.users, self.queries, self.items, ops.training_objective(self.batch_rows, self.positives), self.labels)
             finally:
                 for module, name, p in slots:
                     module._parameters[name] = p
@@ -127,13 +112,16 @@ class CapturedTrainingStep:
         """The optimizer's hyper-parameters, the model attribute and the scoring head (``Gs.Prediction.use_cosine_similarity``: the model reads it at every call, the
         recording holds the kernels of the head that was set) a replay cannot change any more (cheap: compared at every ``step()``)."""
         from .Helpers.GlobalSettings import Gs
+        from . import ops
         group = self.optimizer.param_groups[0]
-        loss = Gs.Training.loss                             # (read at every call, like the head: the recording holds the loss launch that was set - and its group count)
-        pool = int(Gs.Training.negative_pool)               # (and the pool with its kept count: the recording holds ihg_hard_negative_loss's launch, or does not)
+        try:
+            # (read at every call, like the head: the recording holds the loss launch that was set, with its group count, its pool and its kept count)
+            objective = ops.training_objective(self.batch_rows, self.positives).key()
+        except ValueError:
+            objective = None                                 # the settings now name an objective these batches cannot carry: not the recorded one
         # (max_grad_norm: the recording holds the norm and clip-record launches with the bound as a launch argument, or does not hold them)
         return (tuple(group['betas']), float(group['eps']), float(group['weight_decay']), bool(self.model.batch_rows_only_last_layer),
-                bool(Gs.Prediction.use_cosine_similarity), loss, self.positives if loss != 'bce' or pool else None, pool, int(Gs.random_negative_sample_size) if pool else None,
-                self.optimizer.max_grad_norm)
+                bool(Gs.Prediction.use_cosine_similarity), objective, self.optimizer.max_grad_norm)
 
     def _baked_settings(self):
         """Everything a replay cannot change any more: the recording holds the kernels these settings selected.  Only the learning rate is
@@ -148,8 +136,9 @@ class CapturedTrainingStep:
 
     def stale(self, full: bool = False) -> bool:
         """True when a setting that is baked into the recording has changed since: the caller must record a new step (``TrainTestHelper`` does) - replaying would
-        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer``, the scoring head, the loss kind, (under a ranking loss or a pool) the number of
-        positives, the hard-negative pool with its kept count, and the optimizer's ``max_grad_norm`` - ten values, what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
+        silently ignore the change.  The default compares Adam's betas / eps / weight decay, ``batch_rows_only_last_layer``, the scoring head, the objective
+        (``ops.training_objective(...).key()``: the loss kind, under a loss over groups the number of positives and of negatives each, the kept count of a pool) and the
+        optimizer's ``max_grad_norm`` - what every ``step()`` checks; ``full=True`` also the ``IHG_*`` environment and the path switches of ``ihgnn_amd.ops`` (a sort over the environment: for the caller to ask once per
         epoch, not per replay on the launch-bound path the recording exists for)."""
         if full:
             return self._baked != self._baked_settings()
@@ -172,7 +161,7 @@ class CapturedTrainingStep:
     def step(self, users, queries, items, labels, positives=None):
         if users.shape[0] != self.batch_rows:
             raise ValueError(f'this step was recorded for batches of {self.batch_rows} rows, got {users.shape[0]}')
-        if positives is not None and (self.loss_kind != 'bce' or self.pool) and int(positives) != self.positives:
+        if positives is not None and self.objective.grouped and int(positives) != self.positives:
             raise ValueError(f'this step was recorded for batches of {self.positives} positives, got {positives}')
         if self.stale():
             raise RuntimeError('CapturedTrainingStep: a setting baked into the recording changed (Adam betas / eps / weight_decay / max_grad_norm, batch_rows_only_last_layer, the scoring head or the loss - the values '

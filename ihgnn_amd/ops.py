@@ -1860,28 +1860,20 @@ class _HemBceLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows: Tensor, items: Tensor, labels: Optional[Tensor], bias: Tensor, lam: float, item_row_offset: int, holder, tables, rows_upper, cosine: bool,
-                objective, *layers: Tensor) -> Tensor:
-        # objective: None = the BCE over ``labels``; (positives, kind) = a ranking loss (``ihg_ranking_loss``; no labels are read); a ``HardNegatives`` = the objective over
-        # every positive and the best ``keep`` of its pool (``ihg_hard_negative_loss``; no labels either) - the one launch that differs
+                objective: 'Objective', *layers: Tensor) -> Tensor:
+        # objective: which loss launch follows the scores (``Objective.launch``: the one launch that differs); ``labels`` are read by the plain BCE only
         # tables (a resolved NodeTables): layer 0 is the embedding tables in place; layers[0] is then its token (the autograd edge), not a matrix
         # rows_upper (a layout without the isolated nodes): layer 0 is in the public numbering (rows), the layers above are in the layout's (rows_upper; -1: zero row)
-        lib = _lib.load()
         real = _same_layout(layers[1:] if tables is not None else layers)
         batch, dim = int(items.shape[0]), _tail_shape(real, tables)[1]
         scores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         dscores = torch.empty(batch, dtype=torch.float32, device=bias.device)
         loss = torch.empty((), dtype=torch.float32, device=bias.device)
-        if objective is None:
+        if not objective.grouped:
             labels = labels.to(torch.float32).contiguous()
         with profiler.kernel('hem_cosine_fwd' if cosine else 'hem_score_fwd', batch, dim):
             stats = _hem_forward(real, tables, rows, rows_upper, items, bias, lam, cosine, scores)
-            if objective is None:
-                _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), batch, _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
-            elif isinstance(objective, HardNegatives):
-                objective.launch(scores, loss, dscores)
-            else:
-                positives, kind = objective
-                _lib.check(lib.ihg_ranking_loss(_ptr(scores), positives, batch // positives - 1, kind, _ptr(loss), _ptr(dscores), _stream()), 'ihg_ranking_loss')
+            objective.launch(scores, labels, loss, dscores)
         ctx.save_for_backward(rows, items, bias, dscores, *real)
         ctx.rows_upper, ctx.stats = rows_upper, stats
         ctx.lam, ctx.offset, ctx.holder, ctx.tables = float(lam), int(item_row_offset), holder, tables
@@ -2098,76 +2090,133 @@ def hem_bce_loss(layers, rows: Tensor, items: Tensor, labels: Tensor, bias: Tens
     tail halves of ``tap`` outputs made with this holder, and their gradients travel through it (see ``TailGradients``).  ``rows_upper`` (with ``holder.row_map``): the
     layers above layer 0 are numbered by the layout's own node ids (a layout without the isolated nodes): their rows of the batch, -1 = isolated = zero.  ``layers[0]`` may be a
     ``NodeTables`` (resolved by the first layer's transform): the head reads its layer-0 rows from the embedding tables in place.  ``cosine``: as in ``hem_score``."""
-    return _hem_loss('hem_bce_loss', layers, rows, items, labels, None, bias, lam, item_row_offset, holder, rows_upper, cosine)
+    return hem_loss(layers, rows, items, bce_objective(), bias, lam, item_row_offset, holder, rows_upper, cosine, labels)
 
 
-def _hem_loss(what: str, layers, rows: Tensor, items: Tensor, labels: Optional[Tensor], objective, bias: Tensor, lam: float, item_row_offset: int,
-              holder: Optional[TailGradients], rows_upper: Optional[Tensor], cosine: bool) -> Tensor:
-    """The fused batch tail under either objective (``_HemBceLoss``: ``objective`` None = BCE over ``labels``, else ``(positives, kind)``)."""
+def hem_loss(layers, rows: Tensor, items: Tensor, objective: Objective, bias: Tensor, lam: float, item_row_offset: int,
+             holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False, labels: Optional[Tensor] = None) -> Tensor:
+    """``objective_loss(hem_score(...), objective, labels)`` as one differentiable op (scalar): the fused batch tail under any ``Objective`` - its launch is the one that
+    differs.  ``labels`` are read by the plain BCE only; every other argument as in ``hem_bce_loss``."""
+    objective.check_rows(int(items.shape[0]))
     tables = None
     layers = list(layers)
     if layers and isinstance(layers[0], NodeTables):
         tables = layers[0]
         if tables.query_rows is None or tables.token is None:
-            raise RuntimeError(f'{what}: the NodeTables were not consumed by a node-level transform (a model without layers?)')
+            raise RuntimeError('hem_loss: the NodeTables were not consumed by a node-level transform (a model without layers?)')
         layers[0] = tables.token
     if rows_upper is not None and holder is not None and holder.row_map is None:
         raise ValueError('rows_upper comes with holder.row_map (the layout\'s public -> own node map)')
     return _HemBceLoss.apply(rows, items, labels, bias, float(lam), int(item_row_offset), holder, tables, rows_upper, bool(cosine), objective, *layers)
 
 
-def ranking_objective(batch_rows: int, positives: int, kind) -> tuple:
-    """``(positives, kind code)`` of a ranking loss over a batch of ``batch_rows`` scores, checked on the host before anything is launched: the batch is ``positives``
-    positives followed by the same number ``k >= 1`` of negatives for each (``B % positives == 0`` and ``B / positives - 1 >= 1``), ``kind`` is ``'bpr'`` or
-    ``'softmax'`` (or ``IHG_LOSS_BPR`` / ``IHG_LOSS_SOFTMAX``)."""
-    code = _lib.LOSS_KINDS.get(kind, kind)
-    if code not in _lib.LOSS_KINDS.values() or isinstance(code, bool):
-        raise ValueError(f'ranking loss: kind is one of {sorted(_lib.LOSS_KINDS)}, got {kind!r}')
+class Objective:
+    """The training objective of a batch of scores, checked on the host before anything is launched - the one description every layer passes on, from the training loop
+    to the loss launch.  ``positives`` None: the BCE over labels (``kind`` is ``IHG_LOSS_BCE``).  Otherwise the batch is ``positives`` positives followed by the same
+    number ``pool >= 1`` of negatives for each (``B % positives == 0``; those of positive ``p`` at rows ``P + p pool ..``), and neither labels nor a loss function are
+    read: with ``keep`` None a ranking loss over all of them (``kind`` ``'bpr'`` / ``'softmax'``, or ``IHG_LOSS_BPR`` / ``IHG_LOSS_SOFTMAX``), else the loss ``kind``
+    (``'bce'`` / ``IHG_LOSS_BCE`` too) over every positive and the ``keep`` candidates of its pool that score highest, ``1 <= keep <= pool <= 256``; the launch then leaves
+    ``selected`` - int32 ``[positives, keep]``, the pool positions of every group's negatives, best first - so an ``Objective`` is made per call."""
+    __slots__ = ('kind', 'positives', 'pool', 'keep', 'selected')
+
+    def __init__(self, kind='bce', batch_rows: Optional[int] = None, positives: Optional[int] = None, keep: Optional[int] = None):
+        self.selected = None
+        if positives is None:
+            if kind not in ('bce', _lib.HARD_NEGATIVE_KINDS['bce']) or isinstance(kind, bool) or keep is not None:
+                raise ValueError(f'objective: kind {kind!r}' + (f' over the best {keep}' if keep is not None else '') + ' is a loss over groups: it needs positives')
+            self.kind, self.positives, self.pool, self.keep = _lib.HARD_NEGATIVE_KINDS['bce'], None, None, None
+            return
+        what, kinds = ('ranking loss', _lib.LOSS_KINDS) if keep is None else ('hard negatives', _lib.HARD_NEGATIVE_KINDS)
+        code = kinds.get(kind, kind) if isinstance(kind, str) else kind
+        if isinstance(code, bool) or not isinstance(code, int) or code not in kinds.values():
+            raise ValueError(f'{what}: kind is one of {sorted(kinds)}, got {kind!r}')
+        batch_rows, positives = int(batch_rows), int(positives)
+        if positives < 1 or batch_rows % positives != 0 or batch_rows // positives - 1 < 1:
+            raise ValueError(f'{what}: a batch is P positives followed by the same number >= 1 of negatives (or pool candidates) for each: {batch_rows} rows cannot be '
+                             f'split into {positives} groups')
+        pool = batch_rows // positives - 1
+        if keep is not None:
+            keep = int(keep)
+            if not 1 <= keep <= pool <= _lib.POOL_MAX:
+                raise ValueError(f'hard negatives: need 1 <= keep <= pool <= {_lib.POOL_MAX}, got keep = {keep} of a pool of {pool}')
+        self.kind, self.positives, self.pool, self.keep = code, positives, pool, keep
+
+    @property
+    def grouped(self) -> bool:
+        """A loss over groups: no labels and no ``loss_function`` are needed."""
+        return self.positives is not None
+
+    @property
+    def hard(self) -> bool:
+        return self.keep is not None
+
+    @property
+    def label(self) -> str:
+        """The profiler's name of the loss launch on the module path."""
+        return 'hard_negative_loss' if self.hard else 'ranking_loss' if self.grouped else 'bce_with_logits'
+
+    def key(self) -> tuple:
+        """What a recording of the step holds of the objective (``CapturedTrainingStep`` compares it at every replay)."""
+        return self.kind, self.positives, self.pool, self.keep
+
+    def check_rows(self, batch_rows: int) -> None:
+        if self.grouped and self.positives * (1 + self.pool) != batch_rows:
+            raise ValueError(f'objective: made for {self.positives * (1 + self.pool)} rows, the batch has {batch_rows}')
+
+    def launch(self, scores: Tensor, labels: Optional[Tensor], loss: Tensor, dscores: Tensor) -> None:
+        """The loss launch: ``loss`` and ``dscores`` (d loss / d scores) of the float32 ``scores``; ``labels`` (float32) are read by the plain BCE only."""
+        lib = _lib.load()
+        if self.hard:
+            self.selected = torch.empty(self.positives, self.keep, dtype=torch.int32, device=scores.device)
+            _lib.check(lib.ihg_hard_negative_loss(_ptr(scores), self.positives, self.pool, self.keep, self.kind, _ptr(loss), _ptr(dscores), _ptr(self.selected), _stream()),
+                       'ihg_hard_negative_loss')
+        elif self.grouped:
+            _lib.check(lib.ihg_ranking_loss(_ptr(scores), self.positives, self.pool, self.kind, _ptr(loss), _ptr(dscores), _stream()), 'ihg_ranking_loss')
+        else:
+            _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), int(scores.numel()), _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
+
+
+def bce_objective() -> Objective:
+    """The BCE over the batch's labels."""
+    return Objective()
+
+
+def ranking_objective(batch_rows: int, positives: int, kind) -> Objective:
+    """The ranking loss ``kind`` (``'bpr'`` / ``'softmax'``) over a batch of ``batch_rows`` scores in ``positives`` groups."""
+    return Objective(kind, batch_rows, positives)
+
+
+def hard_negative_objective(batch_rows: int, positives: int, keep: int, kind) -> Objective:
+    """The loss ``kind`` (``'bce'`` / ``'bpr'`` / ``'softmax'``) over every positive and the best ``keep`` of its pool, for a batch of ``batch_rows`` scores in
+    ``positives`` groups."""
+    return Objective(kind, batch_rows, positives, int(keep))
+
+
+def training_objective(batch_rows: int, positives: Optional[int]) -> Objective:
+    """The objective the settings name for a batch of ``batch_rows`` rows of which the first ``positives`` are the positives - the one reader of ``Gs.Training.loss``,
+    ``Gs.Training.negative_pool`` (M > 0: the loader drew M candidates per positive) and ``Gs.random_negative_sample_size`` (of which a step then keeps this many) for
+    the choice of a step; read at every call, as the model reads its head.  The plain BCE does not look at ``positives``."""
+    from .Helpers.GlobalSettings import Gs
+    kind, pool = Gs.Training.loss, int(Gs.Training.negative_pool)
+    if kind == 'bce' and not pool:
+        return bce_objective()
+    if positives is None:
+        raise ValueError(f'Gs.Training.loss = {kind!r}' + (f' with a pool of {pool}' if pool else '') +
+                         ' needs positives= (the batch is P positives followed by the negatives of each)')
     batch_rows, positives = int(batch_rows), int(positives)
-    if positives < 1 or batch_rows % positives != 0 or batch_rows // positives - 1 < 1:
-        raise ValueError(f'ranking loss: a batch is P positives followed by P * k negatives, k >= 1: {batch_rows} rows cannot be split into {positives} groups')
-    return positives, int(code)
+    if pool and batch_rows != positives * (1 + pool):
+        raise ValueError(f'Gs.Training.negative_pool = {pool}, but the loader drew {batch_rows - positives} negatives for {positives} positives ({batch_rows} rows over '
+                         f'{positives} positives carry a pool of {(batch_rows - positives) / max(positives, 1):g}): build the dataset with '
+                         'random_negative_sample_size = the pool size (Main does)')
+    return Objective(kind, batch_rows, positives, int(Gs.random_negative_sample_size) if pool else None)
 
 
-class HardNegatives:
-    """The objective over every positive and the best ``keep`` candidates of its pool (``ihg_hard_negative_loss``): what ``hard_negative_objective`` checked, and after
-    the launch ``selected`` - int32 ``[positives, keep]``, the pool positions of every group's negatives, best first."""
-    __slots__ = ('positives', 'pool', 'keep', 'kind', 'selected')
-
-    def __init__(self, positives: int, pool: int, keep: int, kind: int):
-        self.positives, self.pool, self.keep, self.kind, self.selected = positives, pool, keep, kind, None
-
-    def launch(self, scores: Tensor, loss: Tensor, dscores: Tensor) -> None:
-        self.selected = torch.empty(self.positives, self.keep, dtype=torch.int32, device=scores.device)
-        _lib.check(_lib.load().ihg_hard_negative_loss(_ptr(scores), self.positives, self.pool, self.keep, self.kind, _ptr(loss), _ptr(dscores), _ptr(self.selected),
-                                                      _stream()), 'ihg_hard_negative_loss')
-
-
-def hard_negative_objective(batch_rows: int, positives: int, keep: int, kind) -> HardNegatives:
-    """The hard-negative objective over a batch of ``batch_rows`` scores, checked on the host before anything is launched: the batch is ``positives`` positives followed by
-    the same number ``M`` of pool candidates for each (``B % positives == 0``, the candidates of positive ``p`` at rows ``P + p M ..``), ``1 <= keep <= M <= 256``, ``kind``
-    is ``'bce'``, ``'bpr'`` or ``'softmax'`` (or ``IHG_LOSS_BCE`` / ``IHG_LOSS_BPR`` / ``IHG_LOSS_SOFTMAX``)."""
-    kinds = _lib.HARD_NEGATIVE_KINDS
-    code = kinds.get(kind, kind) if isinstance(kind, str) else kind
-    if isinstance(code, bool) or not isinstance(code, int) or code not in kinds.values():
-        raise ValueError(f'hard negatives: kind is one of {sorted(kinds)}, got {kind!r}')
-    batch_rows, positives, keep = int(batch_rows), int(positives), int(keep)
-    if positives < 1 or batch_rows % positives != 0 or batch_rows // positives - 1 < 1:
-        raise ValueError(f'hard negatives: a batch is P positives followed by P * M pool candidates, M >= 1: {batch_rows} rows cannot be split into {positives} groups')
-    pool = batch_rows // positives - 1
-    if not 1 <= keep <= pool <= _lib.POOL_MAX:
-        raise ValueError(f'hard negatives: need 1 <= keep <= pool <= {_lib.POOL_MAX}, got keep = {keep} of a pool of {pool}')
-    return HardNegatives(positives, pool, keep, int(code))
-
-
-def hem_hard_negative_loss(layers, rows: Tensor, items: Tensor, objective: HardNegatives, bias: Tensor, lam: float, item_row_offset: int,
+def hem_hard_negative_loss(layers, rows: Tensor, items: Tensor, objective: Objective, bias: Tensor, lam: float, item_row_offset: int,
                            holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
     """``hard_negative_loss(hem_score(...), positives, keep, kind)`` as one differentiable op (scalar): ``hem_bce_loss`` with ``ihg_hard_negative_loss`` as its loss launch
     and no labels.  ``objective`` is ``hard_negative_objective``'s and holds ``selected`` afterwards.  The pool rows are ordinary batch rows; the rows of the candidates
     that are not selected get zero row gradients.  Every other argument as in ``hem_bce_loss``."""
-    if objective.positives * (1 + objective.pool) != int(items.shape[0]):
-        raise ValueError(f'hard negatives: the objective was made for {objective.positives * (1 + objective.pool)} rows, the batch has {int(items.shape[0])}')
-    return _hem_loss('hem_hard_negative_loss', layers, rows, items, None, objective, bias, lam, item_row_offset, holder, rows_upper, cosine)
+    return hem_loss(layers, rows, items, objective, bias, lam, item_row_offset, holder, rows_upper, cosine)
 
 
 def sample_pool(seed: int, counter: int, n_rows: int, n_items: int, m: int, device=None) -> Tensor:
@@ -2185,8 +2234,7 @@ def hem_ranking_loss(layers, rows: Tensor, items: Tensor, positives: int, kind, 
                      holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
     """``ranking_loss(hem_score(...), positives, kind)`` as one differentiable op (scalar): ``hem_bce_loss`` with ``ihg_ranking_loss`` as its loss launch and no labels.
     The batch rows are ``positives`` positives followed by the ``k`` negatives of each (``collate_fn``'s layout); every other argument as in ``hem_bce_loss``."""
-    objective = ranking_objective(int(items.shape[0]), positives, kind)
-    return _hem_loss('hem_ranking_loss', layers, rows, items, None, objective, bias, lam, item_row_offset, holder, rows_upper, cosine)
+    return hem_loss(layers, rows, items, ranking_objective(int(items.shape[0]), positives, kind), bias, lam, item_row_offset, holder, rows_upper, cosine)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2376,38 +2424,16 @@ def rows_topk(scores: Tensor, k: int):
     return items, top
 
 
-class _BceWithLogits(torch.autograd.Function):
+class _ScoreLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scores: Tensor, labels: Tensor) -> Tensor:
-        lib = _lib.load()
-        scores = _gpu(scores.detach(), 'scores').contiguous()
-        labels = _gpu(labels, 'labels').to(torch.float32).contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=scores.device)
-        dscores = torch.empty_like(scores)
-        with profiler.kernel('bce_with_logits', int(scores.numel()), 1):
-            _lib.check(lib.ihg_bce_with_logits(_ptr(scores), _ptr(labels), int(scores.numel()), _ptr(loss), _ptr(dscores), _stream()), 'ihg_bce_with_logits')
-        ctx.save_for_backward(dscores)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss: Tensor):
-        return ctx.saved_tensors[0] * grad_loss, None
-
-
-def bce_with_logits(scores: Tensor, labels: Tensor) -> Tensor:
-    """``nn.BCEWithLogitsLoss()(scores, labels)`` with its gradient from the one launch of ``ihg_bce_with_logits``."""
-    return _BceWithLogits.apply(scores, labels)
-
-
-class _RankingLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores: Tensor, positives: int, kind: int) -> Tensor:
-        lib = _lib.load()
+    def forward(ctx, scores: Tensor, objective: Objective, labels: Optional[Tensor]) -> Tensor:
         scores = _gpu(scores.detach(), 'scores').to(torch.float32).contiguous()
+        if not objective.grouped:
+            labels = _gpu(labels, 'labels').to(torch.float32).contiguous()
         loss = torch.empty((), dtype=torch.float32, device=scores.device)
         dscores = torch.empty_like(scores)
-        with profiler.kernel('ranking_loss', int(scores.numel()), 1):
-            _lib.check(lib.ihg_ranking_loss(_ptr(scores), positives, int(scores.numel()) // positives - 1, kind, _ptr(loss), _ptr(dscores), _stream()), 'ihg_ranking_loss')
+        with profiler.kernel(objective.label, int(scores.numel()), 1):
+            objective.launch(scores, labels, loss, dscores)
         ctx.save_for_backward(dscores)
         return loss
 
@@ -2416,30 +2442,30 @@ class _RankingLoss(torch.autograd.Function):
         return ctx.saved_tensors[0] * grad_loss, None, None
 
 
+def _score_vector(scores: Tensor, what: str) -> int:
+    if scores.dim() != 1:
+        raise ValueError(f'{what} takes the scores of a batch as a vector, got {tuple(scores.shape)}')
+    return int(scores.shape[0])
+
+
+def objective_loss(scores: Tensor, objective: Objective, labels: Optional[Tensor] = None) -> Tensor:
+    """The loss of ``scores`` under ``objective`` (``labels``: the plain BCE's) with its gradient from the objective's one launch: the module path, where the fused tail
+    (``hem_loss``) does not apply."""
+    if objective.grouped:
+        objective.check_rows(_score_vector(scores, 'objective_loss'))
+    return _ScoreLoss.apply(scores, objective, labels)
+
+
+def bce_with_logits(scores: Tensor, labels: Tensor) -> Tensor:
+    """``nn.BCEWithLogitsLoss()(scores, labels)`` with its gradient from the one launch of ``ihg_bce_with_logits``."""
+    return objective_loss(scores, bce_objective(), labels)
+
+
 def ranking_loss(scores: Tensor, positives: int, kind) -> Tensor:
     """The BPR (``kind='bpr'``) or sampled-softmax (``'softmax'``) loss of ``scores`` ``[P (1 + k)]`` - ``positives = P`` positives followed by the ``k`` negatives of
     each, ``collate_fn``'s layout - with its gradient from the one launch of ``ihg_ranking_loss``: the sibling of ``bce_with_logits`` where the fused tail
     (``hem_ranking_loss``) does not apply."""
-    if scores.dim() != 1:
-        raise ValueError(f'ranking_loss takes the scores of a batch as a vector, got {tuple(scores.shape)}')
-    positives, code = ranking_objective(int(scores.shape[0]), positives, kind)
-    return _RankingLoss.apply(scores, positives, code)
-
-
-class _HardNegativeLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores: Tensor, objective: HardNegatives) -> Tensor:
-        scores = _gpu(scores.detach(), 'scores').to(torch.float32).contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=scores.device)
-        dscores = torch.empty_like(scores)
-        with profiler.kernel('hard_negative_loss', int(scores.numel()), 1):
-            objective.launch(scores, loss, dscores)
-        ctx.save_for_backward(dscores)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss: Tensor):
-        return ctx.saved_tensors[0] * grad_loss, None
+    return objective_loss(scores, ranking_objective(_score_vector(scores, 'ranking_loss'), positives, kind))
 
 
 def hard_negative_loss(scores: Tensor, positives: int, keep: int, kind, return_selected: bool = False):
@@ -2447,10 +2473,8 @@ def hard_negative_loss(scores: Tensor, positives: int, keep: int, kind, return_s
     over every positive and the ``keep`` candidates of its pool that score highest (ties: the lower pool position), with its gradient - exactly zero on the other
     candidates - from the one launch of ``ihg_hard_negative_loss``: the sibling of ``ranking_loss`` where the fused tail (``hem_hard_negative_loss``) does not apply.
     ``return_selected``: also the ``[P, keep]`` pool positions of the negatives, best first (int64, detached)."""
-    if scores.dim() != 1:
-        raise ValueError(f'hard_negative_loss takes the scores of a batch as a vector, got {tuple(scores.shape)}')
-    objective = hard_negative_objective(int(scores.shape[0]), positives, keep, kind)
-    loss = _HardNegativeLoss.apply(scores, objective)
+    objective = hard_negative_objective(_score_vector(scores, 'hard_negative_loss'), positives, keep, kind)
+    loss = objective_loss(scores, objective)
     return (loss, objective.selected.to(torch.int64)) if return_selected else loss
 
 

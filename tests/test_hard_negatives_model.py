@@ -285,11 +285,13 @@ def test_recorded_step_equals_the_eager_step_and_notices_a_flip():
 # the training loop, the device loader
 # ---------------------------------------------------------------------------------------------
 def test_training_loop_takes_the_hard_negative_step(monkeypatch):
-    """``train_and_get_avg_loss`` under ``Gs.Training.negative_pool``: the fused step where the fused tail runs (``model.hard_negative_loss`` is called, ``bce_loss`` and
-    ``ranking_loss`` are not), the module path with ``ops.hard_negative_loss`` where it does not, and the same average loss either way to 1e-4."""
+    """``train_and_get_avg_loss`` under ``Gs.Training.negative_pool``: the fused step where the fused tail runs (``model.training_loss`` is called under the hard-negative
+    objective and no other; the per-objective methods are not the loop's route), the module path with ``ops.objective_loss`` where it does not, and the same average
+    loss either way to 1e-4."""
     from torch.utils.data import DataLoader
-    from ihgnn_amd import ops
+    from ihgnn_amd import _lib, ops
     from ihgnn_amd.Dataset import GraphDataset
+    from ihgnn_amd.Helpers.GlobalSettings import Gs
     from ihgnn_amd.Helpers.ProcessController import ProcessController
     from ihgnn_amd.Helpers.TrainTestHelper import train_and_get_avg_loss
     from ihgnn_amd.Models import RawGnn
@@ -297,12 +299,24 @@ def test_training_loop_takes_the_hard_negative_step(monkeypatch):
     import random
     ds = dataset_of(workload())
     ds.rand_neg_sample_size = M                                                  # (Main builds the dataset with the pool size)
-    calls = {'hard': 0, 'other': 0, 'op': 0}
-    real_hard, real_op = RawGnn.hard_negative_loss, ops.hard_negative_loss
-    monkeypatch.setattr(RawGnn, 'hard_negative_loss', lambda self, *a, **k: (calls.__setitem__('hard', calls['hard'] + 1), real_hard(self, *a, **k))[1])
-    monkeypatch.setattr(RawGnn, 'bce_loss', lambda self, *a, **k: calls.__setitem__('other', calls['other'] + 1))
-    monkeypatch.setattr(RawGnn, 'ranking_loss', lambda self, *a, **k: calls.__setitem__('other', calls['other'] + 1))
-    monkeypatch.setattr(ops, 'hard_negative_loss', lambda *a, **k: (calls.__setitem__('op', calls['op'] + 1), real_op(*a, **k))[1])
+    calls = {'hard': 0, 'other': 0, 'op': 0}                                      # calls of model.training_loss, of a per-objective method, of ops.objective_loss
+    seen = []                                                                    # the objective of every one of them
+    real_loss, real_op = RawGnn.training_loss, ops.objective_loss
+
+    def model_loss(self, users, queries, items, objective, *a, **k):
+        calls['hard'] += 1
+        seen.append(objective)
+        return real_loss(self, users, queries, items, objective, *a, **k)
+
+    def op_loss(scores, objective, *a, **k):
+        calls['op'] += 1
+        seen.append(objective)
+        return real_op(scores, objective, *a, **k)
+
+    monkeypatch.setattr(RawGnn, 'training_loss', model_loss)
+    monkeypatch.setattr(ops, 'objective_loss', op_loss)
+    for name in ('bce_loss', 'ranking_loss', 'hard_negative_loss'):
+        monkeypatch.setattr(RawGnn, name, lambda self, *a, **k: calls.__setitem__('other', calls['other'] + 1))
     averages = []
     with setting(loss='bce', pool=M):
         for fused in (True, False):
@@ -317,7 +331,11 @@ def test_training_loop_takes_the_hard_negative_step(monkeypatch):
             avg, _ = train_and_get_avg_loss(m, opt, torch.nn.BCEWithLogitsLoss(), ds, loader, pc, dev(), record_step='off')
             averages.append(avg)
             assert calls['other'] == 0 and len(loader) >= 4 and (calls['hard'] == len(loader) and calls['op'] == 0 if fused else calls['op'] == len(loader)), calls
+            # no other objective ran: every step's is the BCE over 100 positives and the best ten of their 24 candidates each
+            keep = Gs.random_negative_sample_size
+            assert len(seen) == len(loader) and all((o.kind, o.positives, o.pool, o.keep) == (_lib.HARD_NEGATIVE_KINDS['bce'], 100, M, keep) for o in seen), [o.key() for o in seen]
             calls.update(hard=0, op=0)
+            seen.clear()
         ds.rand_neg_sample_size = 10                                             # a loader that draws no pool is refused, not trained on
         with pytest.raises(ValueError, match='negative_pool'):
             train_and_get_avg_loss(m, opt, torch.nn.BCEWithLogitsLoss(), ds, loader, pc, dev(), record_step='off')

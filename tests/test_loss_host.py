@@ -99,8 +99,9 @@ def test_srrl_refuses_a_ranking_loss():
 def test_grouping_is_checked_on_the_host():
     """``B % positives == 0`` and ``B / positives - 1 >= 1``, before any launch: CPU tensors get as far as the check and no further."""
     from ihgnn_amd import _lib, ops
-    assert ops.ranking_objective(1100, 100, 'bpr') == (100, 1) and ops.ranking_objective(1600, 100, 'softmax') == (100, 2)
-    assert ops.ranking_objective(4, 2, _lib.LOSS_KINDS['softmax']) == (2, 2)
+    for args, pair, pool in (((1100, 100, 'bpr'), (100, 1), 10), ((1600, 100, 'softmax'), (100, 2), 15), ((4, 2, _lib.LOSS_KINDS['softmax']), (2, 2), 1)):
+        o = ops.ranking_objective(*args)
+        assert (o.positives, o.kind) == pair and o.pool == pool and o.keep is None
     for rows, positives in ((1100, 99), (100, 100), (7, 0), (7, -1), (3, 2)):
         with pytest.raises(ValueError, match='rows'):
             ops.ranking_objective(rows, positives, 'bpr')

@@ -257,10 +257,11 @@ def test_recorded_step_equals_the_eager_step_and_notices_a_flip(kind):
 # the training loop
 # ---------------------------------------------------------------------------------------------
 def test_training_loop_takes_the_ranking_step(monkeypatch):
-    """``train_and_get_avg_loss`` under ``Gs.Training.loss = 'bpr'``: the fused step where the fused tail runs (``model.ranking_loss`` is called, ``bce_loss`` is not), the
-    module path with ``ops.ranking_loss`` where it does not, and the same average loss either way to 1e-4."""
+    """``train_and_get_avg_loss`` under ``Gs.Training.loss = 'bpr'``: the fused step where the fused tail runs (``model.training_loss`` is called under the bpr objective
+    and no other; the per-objective methods are not the loop's route), the module path with ``ops.objective_loss`` where it does not, and the same average loss
+    either way to 1e-4."""
     from torch.utils.data import DataLoader
-    from ihgnn_amd import ops
+    from ihgnn_amd import _lib, ops
     from ihgnn_amd.Dataset import GraphDataset
     from ihgnn_amd.Helpers.ProcessController import ProcessController
     from ihgnn_amd.Helpers.TrainTestHelper import train_and_get_avg_loss
@@ -268,11 +269,24 @@ def test_training_loop_takes_the_ranking_step(monkeypatch):
     from ihgnn_amd.optim import Adam
     import random
     ds = dataset_of(workload())
-    calls = {'ranking': 0, 'bce': 0, 'op': 0}
-    real_ranking, real_op = RawGnn.ranking_loss, ops.ranking_loss
-    monkeypatch.setattr(RawGnn, 'ranking_loss', lambda self, *a, **k: (calls.__setitem__('ranking', calls['ranking'] + 1), real_ranking(self, *a, **k))[1])
-    monkeypatch.setattr(RawGnn, 'bce_loss', lambda self, *a, **k: calls.__setitem__('bce', calls['bce'] + 1))
-    monkeypatch.setattr(ops, 'ranking_loss', lambda *a, **k: (calls.__setitem__('op', calls['op'] + 1), real_op(*a, **k))[1])
+    calls = {'ranking': 0, 'bce': 0, 'op': 0}                                     # calls of model.training_loss, of a per-objective method, of ops.objective_loss
+    seen = []                                                                    # the objective of every one of them
+    real_loss, real_op = RawGnn.training_loss, ops.objective_loss
+
+    def model_loss(self, users, queries, items, objective, *a, **k):
+        calls['ranking'] += 1
+        seen.append(objective)
+        return real_loss(self, users, queries, items, objective, *a, **k)
+
+    def op_loss(scores, objective, *a, **k):
+        calls['op'] += 1
+        seen.append(objective)
+        return real_op(scores, objective, *a, **k)
+
+    monkeypatch.setattr(RawGnn, 'training_loss', model_loss)
+    monkeypatch.setattr(ops, 'objective_loss', op_loss)
+    for name in ('bce_loss', 'ranking_loss', 'hard_negative_loss'):
+        monkeypatch.setattr(RawGnn, name, lambda self, *a, **k: calls.__setitem__('bce', calls['bce'] + 1))
     averages = []
     with setting(loss='bpr'):
         for fused in (True, False):
@@ -287,7 +301,10 @@ def test_training_loop_takes_the_ranking_step(monkeypatch):
             avg, _ = train_and_get_avg_loss(m, opt, torch.nn.BCEWithLogitsLoss(), ds, loader, pc, dev(), record_step='off')
             averages.append(avg)
             assert calls['bce'] == 0 and len(loader) >= 4 and (calls['ranking'] == len(loader) and calls['op'] == 0 if fused else calls['op'] == len(loader)), calls
+            # no other objective ran: every step's is the bpr loss of 100 positives against their ten negatives each
+            assert len(seen) == len(loader) and all((o.kind, o.positives, o.pool, o.keep) == (_lib.LOSS_KINDS['bpr'], 100, 10, None) for o in seen), [o.key() for o in seen]
             calls.update(ranking=0, op=0)
+            seen.clear()
     # (not a parity bar - the routes are held to one in test_fused_tail_equals_the_module_path: the same batches through both routes train alike)
     assert np.isfinite(averages).all() and abs(averages[0] - averages[1]) <= 1e-4 * abs(averages[1]), averages
 
