@@ -203,6 +203,24 @@ class GraphDataset(Dataset):
         return self._neg_lists
 
     @property
+    def user_item_lists(self) -> Tuple[np.ndarray, np.ndarray]:
+        """What every user interacted with in training, as the search kernels read exclusion lists: ``(ptr [U + 1] int64, items int32)`` where
+        ``items[ptr[u]:ptr[u + 1]]`` are user ``u``'s distinct items of ``pos_triples``, ascending; empty for a user without a positive.  Built once."""
+        if getattr(self, '_user_items', None) is None:
+            keys = np.unique(self.pos_triples[:, 0].astype(np.int64) * self.item_count + self.pos_triples[:, 2])
+            ptr = np.searchsorted(keys, np.arange(self.user_count + 1, dtype=np.int64) * self.item_count).astype(np.int64)
+            self._user_items = (ptr, np.ascontiguousarray(keys % self.item_count, np.int32))
+        return self._user_items
+
+    def user_item_lists_on(self, device) -> Tuple[Tensor, Tensor]:
+        """``user_item_lists`` as tensors on ``device``, copied there once."""
+        device = torch.device(device)
+        cached = getattr(self, '_user_items_device', None)
+        if cached is None or cached[0].device.type != device.type or (device.index is not None and cached[0].device.index != device.index):
+            cached = self._user_items_device = tuple(torch.from_numpy(a).to(device) for a in self.user_item_lists)
+        return cached
+
+    @property
     def pos_interactions(self) -> List[PosInteraction]:
         if self._pos_interactions is None:
             if self.search_logs is not None:

@@ -75,6 +75,9 @@ _FLAGS = (
     ('cosine', ('--cosine',), 'flag', False, 'score with the cosine-similarity HEM head (Gs.Prediction.use_cosine_similarity) instead of the dot product'),
     # not in the reference, which reports @10 only (Metrics.py:60-63)
     ('cutoffs', ('--cutoffs',), cutoff_list, '', 'further metric cutoffs, e.g. 20,50,100 (each in 11..128): HR / NDCG / MAP @K beside the @10 triple, from one ranking at the largest (Gs.Evaluation.extra_cutoffs)'),
+    # not in the reference, which ranks every item of the catalogue for every test log
+    ('filter_seen', ('--filter_seen',), 'flag', False, 'evaluate under the "filter seen" protocol: rank each test log without the items its user interacted with in training '
+                                                       '(the log\'s own positives stay rankable; Gs.Evaluation.filter_seen)'),
     # not in the reference, which trains on nn.BCEWithLogitsLoss only (Main.py:191)
     ('loss', ('--loss',), str, 'bce', 'training objective: bce (the reference\'s point-wise loss) | bpr (pairwise: every positive against each of its negatives) | '
                                       'softmax (the positive against its own negatives; Gs.Training.loss)'),

@@ -31,11 +31,25 @@ def print_network_parameters(module: nn.Module, name_filter: Optional[str] = Non
                               f'std={p.std().item():<7.3f} | absmean={p.abs().mean().item():<7.3f}')
 
 
-def _evaluate_batched(model, logs, item_count: int, device: torch.device, indices) -> List[Tuple[int, Metrics]]:
+def seen_lists_for_logs(logs, indices, ptr, items) -> Tuple[List[int], List[int]]:
+    """The items each of the logs ``indices`` is ranked WITHOUT under ``Gs.Evaluation.filter_seen``: its user's training items (run ``user`` of the lists
+    ``(ptr, items)``, ``GraphDataset.user_item_lists``) except the log's own interacted items - a test positive that was also bought in training stays
+    rankable, it is not turned into a guaranteed miss.  Returns ``(offsets [len(indices) + 1], flat item ids)``, each run ascending."""
+    offsets, flat = [0], []
+    for i in indices:
+        user, _, interacted = logs[i][0], logs[i][1], logs[i][2]
+        keep = set(int(x) for x in interacted)
+        flat.extend(x for x in (int(v) for v in items[int(ptr[user]):int(ptr[user + 1])]) if x not in keep)
+        offsets.append(len(flat))
+    return offsets, flat
+
+
+def _evaluate_batched(model, logs, item_count: int, device: torch.device, indices, seen=None) -> List[Tuple[int, Metrics]]:
     """Top-10 of many searches per launch (``ihg_score_topk`` / ``ihg_score_topk_cosine``, whichever head ``Gs.Prediction.use_cosine_similarity`` names: scores on
     the matrix cores, running top-10 in registers, no ``[C, I]`` matrix), one D2H copy per chunk (the reference scores one log at a time and syncs on every one,
     ``TrainTestHelper.py:58-67``, ``Metrics.py:60-61``).  With ``Gs.Evaluation.extra_cutoffs`` the ONE ranking per chunk is as deep as the largest cutoff
-    (``ihg_score_topk_deep``) and every cutoff's metrics are read from a prefix of it."""
+    (``ihg_score_topk_deep``) and every cutoff's metrics are read from a prefix of it.  ``seen`` (``GraphDataset.user_item_lists`` under
+    ``Gs.Evaluation.filter_seen``): every log is ranked without ``seen_lists_for_logs``' items, per-search lists built on the host per chunk."""
     out: List[Tuple[int, Metrics]] = []
     chunk = 8192
     extras = tuple(Gs.Evaluation.extra_cutoffs)
@@ -43,7 +57,11 @@ def _evaluate_batched(model, logs, item_count: int, device: torch.device, indice
     for lo in range(0, len(indices), chunk):
         part = indices[lo:lo + chunk]
         uq = torch.tensor([(logs[i][0], logs[i][1]) for i in part], dtype=torch.long, device=device)
-        top = model.top_items(uq[:, 0], uq[:, 1], k)[0].tolist()          # HIP kernel: fp32-MFMA scores reduced to a running top-10 on chip
+        if seen is not None:
+            offsets, flat = seen_lists_for_logs(logs, part, *seen)
+            top = model.top_items(uq[:, 0], uq[:, 1], k, exclude=(torch.tensor(offsets, dtype=torch.int64), torch.tensor(flat, dtype=torch.int64)))[0].tolist()
+        else:
+            top = model.top_items(uq[:, 0], uq[:, 1], k)[0].tolist()      # HIP kernel: fp32-MFMA scores reduced to a running top-10 on chip
         for i, row in zip(part, top):
             _, _, items, flags, all_1 = logs[i]
             out.append((i, Metrics.at_cutoffs(row, items, flags, all_1, extras)))
@@ -70,7 +88,8 @@ def test_and_get_avg_metrics(model, dataset_train: GraphDataset, dataloader: Tes
         model.save_features_for_test()
         try:
             if hasattr(model, 'top_items'):
-                scored = _evaluate_batched(model, logs, dataset_train.item_count, device, mine)
+                filtered = bool(Gs.Evaluation.filter_seen)
+                scored = _evaluate_batched(model, logs, dataset_train.item_count, device, mine, dataset_train.user_item_lists if filtered else None)
             else:
                 scored = []
                 for i in mine:
@@ -102,7 +121,8 @@ def test_and_get_avg_metrics(model, dataset_train: GraphDataset, dataloader: Tes
         user_avgs = [None if row[3] < 0.5 else Metrics(row[0], row[1], row[2]).divide_and_get_new(int(round(row[3])))
                      for row in table.tolist()]
     seconds = time.time() - started
-    IOHelper.LogPrint(f'evaluation done in {seconds:<.2f} s over {counted} usable search logs.')
+    IOHelper.LogPrint(f'evaluation done in {seconds:<.2f} s over {counted} usable search logs' +
+                      (', each ranked without its user\'s training items.' if hasattr(model, 'top_items') and Gs.Evaluation.filter_seen else '.'))
     IOHelper.LogPrint(average.to_string(highlight=True), put_time_in_single_line=True)
     IOHelper.LogPrint()
     return user_avgs, average, seconds

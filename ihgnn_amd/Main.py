@@ -50,8 +50,10 @@ def apply_prediction_settings(args) -> None:
 
 
 def apply_evaluation_settings(args) -> None:
-    """``--cutoffs`` -> ``Gs.Evaluation.extra_cutoffs``, assigned both ways like the head above (not in the reference, which reports @10 only)."""
+    """``--cutoffs`` -> ``Gs.Evaluation.extra_cutoffs`` and ``--filter_seen`` -> ``Gs.Evaluation.filter_seen``, assigned both ways like the head above (not in the
+    reference, which reports @10 only, over the whole catalogue)."""
     Gs.Evaluation.extra_cutoffs = tuple(getattr(args, 'cutoffs', ()) or ())
+    Gs.Evaluation.filter_seen = bool(getattr(args, 'filter_seen', False))
 
 
 def apply_training_settings(args) -> None:
@@ -104,6 +106,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise NotImplementedError('--model Srrl trains its PS half on the BCE, as the reference does: --loss bpr / softmax have not been built for it')
     if int(getattr(args, 'hard_negatives', 0) or 0) > 0:
         raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --hard_negatives has not been built for it')
+    if getattr(args, 'filter_seen', False):
+        raise NotImplementedError('--model Srrl ranks the whole catalogue: --filter_seen has not been built for its scoring kernels')
     if getattr(args, 'query_transform', Gsv.mean) == Gsv.gru:
         raise NotImplementedError('--model Srrl embeds its queries by the bag mean or the activation transform: --query_transform gru has not been built for it')
     widest = ops.cat_linear_max_width()
@@ -197,7 +201,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     say((f'model Srrl | dataset {dataset_name} | KG loss {Gs.Srrl.KG_loss} | uniform KG weights {Gs.Srrl.uni_weight} | ' if model_type is Srrl else
          f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | ') +
         f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
-        f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | loss {Gs.Training.loss} | validation {Gs.use_valid_dataset}')
+        f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | loss {Gs.Training.loss} | validation {Gs.use_valid_dataset}' +
+        (' | evaluation filtered: without the user\'s training items' if Gs.Evaluation.filter_seen else ''))
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
 
     dataset_train = GraphDataset(

@@ -303,22 +303,29 @@ class RawGnn(nn.Module):
             item_feature = item_feature / item_feature.norm(dim=1, keepdim=True).clamp_min(1e-8)
         return torch.addmm(head.items_bias.unsqueeze(0), mixed, item_feature.t())
 
-    def top_items(self, user_indices: Tensor, query_indices: Tensor, k: int = 10):
+    def top_items(self, user_indices: Tensor, query_indices: Tensor, k: int = 10, exclude=None):
         """``(items [C, k] int32, scores [C, k])``: the ``k`` best items of each (user, query) pair over the whole catalogue, best
         first - what ``Metrics.calculate_on_all_items`` keeps of ``forward(u, q, None)`` (``Metrics.py:60-61``) - from the fused
         HIP scoring + running top-k kernel; the ``[C, I]`` scores are never stored.  Ties: ascending item id.  ``k`` up to ``ops.score_topk_max_k()`` = 128
         (beyond ten the kernel runs in passes, ``ops.score_topk_deep``; the reference itself stops at ten).  No torch path: any feature width
-        ``d (L + 1)`` up to ``MAX_SCORED_WIDTH`` (checked at construction).  Scores with the head that ``Gs.Prediction.use_cosine_similarity`` names."""
+        ``d (L + 1)`` up to ``MAX_SCORED_WIDTH`` (checked at construction).  Scores with the head that ``Gs.Prediction.use_cosine_similarity`` names.
+        ``exclude=(offsets [C + 1], items)``: pair ``c`` is ranked without ``items[offsets[c]:offsets[c + 1]]`` (any order, repeats allowed) - the scores of the
+        other items are the same bits, and a row with fewer than ``k`` items left ends in ``-1``."""
         from .. import ops
         features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
         ds, head = self.dataset, self.prediction_layer
         if k > ops.score_topk_max_k():
             raise ValueError(f'RawGnn.top_items ranks at most {ops.score_topk_max_k()} items per pair, got k = {k}')
         k = min(k, ds.item_count)
+        if exclude is not None:
+            lists = ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
+            items, scores, _ = ops.search_topk(features, user_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
+                                               queries=query_indices, cosine=Gs.Prediction.use_cosine_similarity, exclude=lists)
+            return items, scores
         return ops.score_topk(features, user_indices, query_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph,
                               head.items_bias, head.lambda_muq, k, cosine=Gs.Prediction.use_cosine_similarity)
 
-    def _check_search_inputs(self, users, queries, words, offsets, candidates):
+    def _check_search_inputs(self, users, queries, words, offsets, candidates, exclude=None, exclude_seen=False):
         """The host-side checks of ``search``, before anything is launched (a tensor that already lives on the device is taken as checked: reading it back would
         stall the stream the answer is waited on).  Returns ``(words, offsets)`` as int64 numpy arrays (``None, None`` with ``queries``)."""
         import numpy as np
@@ -351,6 +358,18 @@ class RawGnn(nn.Module):
             raise ValueError(f'RawGnn.search: candidate item id outside [0, {ds.item_count})')
         if c is not None and c.dtype == np.bool_ and c.shape != (ds.item_count,):
             raise ValueError(f'RawGnn.search: a candidate mask is a bool tensor of [{ds.item_count}]')
+        if exclude is not None and exclude_seen:
+            raise ValueError('RawGnn.search: give exclude= or exclude_seen=True, not both')
+        if exclude is not None:
+            if not isinstance(exclude, (tuple, list)) or len(exclude) != 2:
+                raise ValueError('RawGnn.search: exclude= is (offsets [C + 1], items)')
+            eo, ei = on_host(exclude[0]), on_host(exclude[1])
+            if eo is not None and (eo.ndim != 1 or eo.size != n_pairs + 1):
+                raise ValueError(f'RawGnn.search: exclude= needs {n_pairs + 1} offsets for {n_pairs} searches')
+            if eo is not None and ei is not None and (eo[0] != 0 or np.any(np.diff(eo) < 0) or eo[-1] != ei.size):
+                raise ValueError('RawGnn.search: the offsets of exclude= start at 0, do not decrease and end at the number of items')
+            if ei is not None and ei.size and (ei.min() < 0 or ei.max() >= ds.item_count):
+                raise ValueError(f'RawGnn.search: excluded item id outside [0, {ds.item_count})')
         if words is None:
             return None, None
         w = np.asarray(words.detach().cpu() if isinstance(words, Tensor) else words, dtype=np.int64).reshape(-1)
@@ -364,16 +383,20 @@ class RawGnn(nn.Module):
         return w, o
 
     @torch.no_grad()
-    def search(self, users, *, queries=None, words=None, offsets=None, k: int = 10, candidates=None):
+    def search(self, users, *, queries=None, words=None, offsets=None, k: int = 10, candidates=None, exclude=None, exclude_seen: bool = False):
         """``(items [C, k] int32, scores [C, k])``: ``top_items`` for a search as it arrives.  ``users`` int64 ``[C]``, ``-1`` = nobody logged in: the head's
         ``user_feature is None`` branch (``PredictionLayers.py:34-37``), the mixed row is the query row.  The query is EITHER ``queries`` (training query indices) OR
         ``words`` with ``offsets`` (flat 0-based word ids and the start of every bag, as for ``nn.EmbeddingBag``): a query the graph has not seen is an isolated node -
         its layer-0 row is ``EmbeddingLayer.embed_bags`` of its words, every layer output above is exactly zero (``Graph.py:120``) - scored as if appended to
         ``queries_multihot.txt`` with no interaction.  A bag that happens to equal a training query's words is still scored this way (its layer-0 row equals that
         query's, bit for bit; its upper rows are zero).  ``candidates``: a bool ``[I]`` mask or int64 item ids - only these are ranked; with fewer than ``k`` of them
-        the rest of a row is ``-1``.  Features, head and ``k`` as in ``top_items``; no retraining, no new parameter, no ``[C, I]`` matrix."""
+        the rest of a row is ``-1``.  ``exclude=(offsets [C + 1], items)``: search ``c`` is answered without ``items[offsets[c]:offsets[c + 1]]`` (any order,
+        repeats allowed), a different set per search where ``candidates`` is one for all.  ``exclude_seen=True``: every search of a logged-in user is answered
+        without the items that user interacted with in training (``GraphDataset.user_item_lists``, one copy on the device shared by all searches; ``-1`` excludes
+        nothing).  Both compose with everything else, and the scores of the items that remain do not change by a bit.
+        Features, head and ``k`` as in ``top_items``; no retraining, no new parameter, no ``[C, I]`` matrix."""
         from .. import ops
-        w, o = self._check_search_inputs(users, queries, words, offsets, candidates)
+        w, o = self._check_search_inputs(users, queries, words, offsets, candidates, exclude, exclude_seen)
         ds, head = self.dataset, self.prediction_layer
         if k < 1 or k > ops.score_topk_max_k():
             raise ValueError(f'RawGnn.search ranks 1 to {ops.score_topk_max_k()} items per pair, got k = {k}')
@@ -387,8 +410,14 @@ class RawGnn(nn.Module):
             queries = torch.as_tensor(queries, dtype=torch.int64)
         if candidates is not None and not isinstance(candidates, Tensor):
             candidates = torch.as_tensor(candidates)
+        lists = rows = None
+        if exclude_seen:
+            lists, rows = ds.user_item_lists_on(features.device), users         # (a user IS the row of the shared lists; -1 names none)
+        elif exclude is not None:
+            lists = ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
         items, scores, _ = ops.search_topk(features, users, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
-                                           queries=queries, query_rows=query_rows, candidates=candidates, cosine=Gs.Prediction.use_cosine_similarity)
+                                           queries=queries, query_rows=query_rows, candidates=candidates, cosine=Gs.Prediction.use_cosine_similarity,
+                                           exclude=lists, exclude_rows=rows)
         return items, scores
 
     def save_features_for_test(self) -> None:

@@ -1,9 +1,10 @@
-"""Answer searches with a trained model: ``python -m ihgnn_amd.Search --ds <dataset> --cp <checkpoint | latest> [--k K] [--candidates FILE] < searches``.
+"""Answer searches with a trained model: ``python -m ihgnn_amd.Search --ds <dataset> --cp <checkpoint | latest> [--k K] [--candidates FILE] [--exclude_seen] < searches``.
 
 The model is described by the driver's own flags (``--ds --gnn --gnns --fo --emb --cosine --query_transform --query_activation --device``, ``Helpers/ArgsParser.py``)
 and built as ``Main.py`` builds it; ``--cp`` is a checkpoint file (a path, or a name inside the run's result directory) or ``latest``.  Every line of the standard
 input is one search, ``user<TAB>w1 w2 ...``: the user's index (``-1``: nobody is logged in) and the query's 0-based word ids as ``queries_multihot.txt`` holds them -
-the query need not be one the model was trained on (``RawGnn.search``).  ``--candidates FILE`` (one item id per line) restricts every search to these items.
+the query need not be one the model was trained on (``RawGnn.search``).  ``--candidates FILE`` (one item id per line) restricts every search to these items;
+``--exclude_seen`` answers every search of a logged-in user without the items that user interacted with in training.
 Output: one line per search, ``item:score`` pairs, best first.  One process; the features are propagated once and the searches are answered in batches.
 """
 import os
@@ -72,6 +73,8 @@ def main(argv: Optional[Sequence[str]] = None, lines=None, out=None) -> int:
     parser.description = 'answer searches with a trained IHGNN model'
     parser.add_argument('--k', dest='k', type=int, default=10, help='items returned per search (1..128)')
     parser.add_argument('--candidates', dest='candidates', type=str, default='', help='a file of item ids, one per line: only these items are ranked')
+    parser.add_argument('--exclude_seen', dest='exclude_seen', action='store_true', default=False,
+                        help='leave out, for every search of a logged-in user, the items that user interacted with in training')
     ns = parser.parse_args(argv)
     args = ConsoleArgs(ns)
     if args.device == 'cpu':
@@ -93,7 +96,7 @@ def main(argv: Optional[Sequence[str]] = None, lines=None, out=None) -> int:
             users = torch.tensor([u for u, _ in batch], dtype=torch.int64)
             offsets = np.cumsum([0] + [len(w) for _, w in batch[:-1]]).astype(np.int64)
             words = np.asarray([w for _, bag in batch for w in bag], np.int64)
-            items, scores = model.search(users, words=words, offsets=offsets, k=ns.k, candidates=candidates)
+            items, scores = model.search(users, words=words, offsets=offsets, k=ns.k, candidates=candidates, exclude_seen=ns.exclude_seen)
             for row_i, row_s in zip(items.cpu().tolist(), scores.cpu().tolist()):
                 out.write(format_answer(row_i, row_s) + '\n')
             batch.clear()

@@ -158,6 +158,11 @@ SIGNATURES = {
     'ihg_search_topk_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     'ihg_search_topk': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_float,
                                        c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    # ... that leaves out a list of items per pair: ihg_search_topk with (excl_ptr, excl_items, excl_row, n_excl_rows) after the mask
+    'ihg_search_topk_excluding_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    'ihg_search_topk_excluding': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                                 c_void_p]),
     'ihg_zero_floats': (ctypes.c_int, [c_void_p, c_int64, c_void_p]),
     'ihg_mark_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_batch_node_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

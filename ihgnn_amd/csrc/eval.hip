@@ -94,7 +94,30 @@ struct SearchArgs<true> {
     int64_t ld_q;
     int q_dim;
     const uint32_t* item_mask;                                              // bit i % 32 of word i / 32: item i is a candidate; null: every item
-    const int32_t* target;                                                  // min(k, candidates)
+    const int32_t* target;                                                  // min(k, candidates); EXCL: [n_pairs], min(k, the candidates of pair c that it does not exclude)
+};
+
+// What ihg_search_topk_excluding adds to the search call (an empty struct for every other instantiation): per pair a strictly ascending run of item ids that are
+// never ranked for it.  A lane owns one pair per pair tile and meets that pair's items in ascending id order - within a tile (8 r4 + 4 half + x) and from tile to
+// tile - so it follows the run with a cursor: the cost is that of the run, not of pairs x items.
+template <bool EXCL>
+struct ExclArgs {};
+template <>
+struct ExclArgs<true> {
+    const int64_t* ptr;                                                     // [rows + 1]
+    const int32_t* items;                                                   // [ptr[rows]]
+    const int64_t* row;                                                     // [n_pairs]: the run of pair c, < 0: none; null: run c
+};
+
+// the cursor of one lane into the run of one pair: `next` is the run's first id not yet passed (INT_MAX: spent, or no run)
+struct ExclCursor {
+    const int32_t* at;
+    const int32_t* end;
+    int next;
+    __device__ __forceinline__ void step() {
+        ++at;
+        next = at < end ? *at : INT_MAX;
+    }
 };
 
 // SEARCH: an item outside the mask gets aux = {0, -inf} and nothing else - whatever its stale planes multiply to, its score is -inf or NaN, which ranks before no
@@ -165,17 +188,23 @@ struct DeepArgs<true> {
 
 // SEARCH (ihg_search_topk; always with DEEP): the query row of a pair may come from `search.query_rows` (zero past q_dim), users[c] < 0 names no user - the mixed
 // row is the query row itself (PredictionLayers.py:34-37, user_feature is None) - and the ranks of a complete pair are read from `search.target`.
-template <int PB, bool COSINE = false, bool DEEP = false, bool SEARCH = false>
+// EXCL (ihg_search_topk_excluding; always with SEARCH): search.target is per pair, and an item of the pair's run never enters the lane's list.  Its score is
+// computed like every other (one expression, one item order: the scores that remain are the bits of ihg_search_topk); exclusion only gates the insert.
+template <int PB, bool COSINE = false, bool DEEP = false, bool SEARCH = false, bool EXCL = false>
 __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
     const float* __restrict__ feat, int64_t ld, int dim, int ksteps, const v4u* __restrict__ frag, const float2* __restrict__ aux, int64_t n_items,
     const int64_t* __restrict__ users, const int64_t* __restrict__ queries, int64_t query_row0, float lam, int64_t n_pairs,
-    float* __restrict__ part_val, int32_t* __restrict__ part_idx, [[maybe_unused]] const DeepArgs<DEEP> deep, [[maybe_unused]] const SearchArgs<SEARCH> search) {
+    float* __restrict__ part_val, int32_t* __restrict__ part_idx, [[maybe_unused]] const DeepArgs<DEEP> deep, [[maybe_unused]] const SearchArgs<SEARCH> search,
+    [[maybe_unused]] const ExclArgs<EXCL> excl) {
     static_assert(DEEP || !SEARCH, "the search arguments ride on the deep passes");
+    static_assert(SEARCH || !EXCL, "the exclusion lists ride on the search arguments");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];    // mixed planes: [32 PB][hi: 2 dp bytes | lo: 2 dp bytes | 16 bytes of padding], then pinv[32 PB]
     if constexpr (DEEP) {                                                   // every wave asks the same question of the same (read-only) state: no barrier
         const int64_t pr = static_cast<int64_t>(blockIdx.x) * (32 * PB) + (threadIdx.x & 63);
         int target;
-        if constexpr (SEARCH) target = *search.target; else target = deep.target;
+        if constexpr (EXCL) target = search.target[pr < n_pairs ? pr : 0];
+        else if constexpr (SEARCH) target = *search.target;
+        else target = deep.target;
         const bool open = (threadIdx.x & 63) < 32 * PB && pr < n_pairs && deep.state[pr].count < target;
         if (__ballot(open) == 0) return;
     }
@@ -275,6 +304,31 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
             b_idx[pb] = deep.state[pr].b_idx;
         }
     }
+    // EXCL: the cursor starts at the run's first id at or past this wave's first item (a lower bound, once per wave run); pairs past the end, which repeat the
+    // last pair and write nothing, follow no run
+    [[maybe_unused]] ExclCursor cur[PB];
+    if constexpr (EXCL) {
+#pragma unroll
+        for (int pb = 0; pb < PB; ++pb) {
+            const int64_t pr = pair0 + 32 * pb + n31;
+            int64_t lo = 0, hi = 0;
+            if (pr < n_pairs && tile_begin < tile_end) {
+                const int64_t row = excl.row != nullptr ? excl.row[pr] : pr;
+                if (row >= 0) {
+                    lo = excl.ptr[row];
+                    hi = excl.ptr[row + 1];
+                }
+            }
+            cur[pb].end = excl.items + hi;
+            const int64_t first = tile_begin * 32;
+            while (lo < hi) {
+                const int64_t mid = lo + (hi - lo) / 2;
+                if (excl.items[mid] < first) lo = mid + 1; else hi = mid;
+            }
+            cur[pb].at = excl.items + lo;
+            cur[pb].next = cur[pb].at < cur[pb].end ? *cur[pb].at : INT_MAX;
+        }
+    }
 
     constexpr int PF = 4;                                                   // k-steps of item fragments in flight
     for (int64_t tile = tile_begin; tile < tile_end; ++tile) {
@@ -317,13 +371,33 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
             float2 ax[4];
 #pragma unroll
             for (int x = 0; x < 4; ++x) ax[x] = i0 + x < n_items ? aux[i0 + x] : make_float2(0.f, 0.f);
+            // EXCL: bit x of skip[pb] = item i0 + x is in the pair's run.  The ids of the other lane half (and of other waves' tiles) are stepped over; a lane
+            // whose run has nothing before i0 + 4 - every lane of a call without lists - pays the one comparison
+            [[maybe_unused]] unsigned skip[PB];
+            if constexpr (EXCL) {
+#pragma unroll
+                for (int pb = 0; pb < PB; ++pb) {
+                    skip[pb] = 0u;
+                    if (cur[pb].next < i0 + 4) {
+                        while (cur[pb].next < i0) cur[pb].step();
+                        while (cur[pb].next < i0 + 4) {
+                            skip[pb] |= 1u << (cur[pb].next - static_cast<int>(i0));
+                            cur[pb].step();
+                        }
+                    }
+                }
+            }
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
                 const int i = static_cast<int>(i0 + x);
 #pragma unroll
                 for (int pb = 0; pb < PB; ++pb) {
                     const float s = acc[pb][4 * r4 + x] * (ax[x].x * my_pinv[pb]) + ax[x].y;
-                    if constexpr (DEEP) {
+                    if constexpr (EXCL) {
+                        if (i0 + x < n_items && ((skip[pb] >> x) & 1u) == 0 && ranks_before(b_val[pb], b_idx[pb], s, i) &&
+                            ranks_before(s, i, top[pb].val[kTopMax - 1], top[pb].idx[kTopMax - 1]))
+                            top[pb].insert(s, i);
+                    } else if constexpr (DEEP) {
                         if (i0 + x < n_items && ranks_before(b_val[pb], b_idx[pb], s, i) && ranks_before(s, i, top[pb].val[kTopMax - 1], top[pb].idx[kTopMax - 1])) top[pb].insert(s, i);
                     } else {
                         if (i0 + x < n_items && ranks_before(s, i, top[pb].val[kTopMax - 1], top[pb].idx[kTopMax - 1])) top[pb].insert(s, i);
@@ -410,14 +484,18 @@ __global__ __launch_bounds__(kBlockThreads) void deep_init_kernel(DeepState* __r
 
 // one wave per incomplete pair.  Lane l owns lists l, l + 64, ...: the head of each in registers (statically indexed: no scratch), the best head of the wave by
 // shuffles, and the one lane that owned it loads its list's next entry - one load per emitted rank, where k full scans of the candidates would be k x n_lists x 10.
-// SEARCH: `target` is read from search.target (min(k, candidates), formed on the device)
-template <bool SEARCH = false>
+// SEARCH: `target` is read from search.target (min(k, candidates), formed on the device); EXCL: from search.target[pair].  An excluded item is in no list, so the
+// lists are exact over the pair's remaining candidates down to t and the argument above holds for them: a pair short of target[pair] still gains ten ranks or all
+// that is left, and the ceil(min(k, n_items) / 10) passes the host launches are at least ceil(target[pair] / 10).  Past the last rank the row keeps deep_init's tail.
+template <bool SEARCH = false, bool EXCL = false>
 __global__ __launch_bounds__(kBlockThreads) void merge_deep_kernel(const float* __restrict__ part_val, const int32_t* __restrict__ part_idx, int64_t n_pairs, int n_lists, int k,
                                                                     int target, DeepState* __restrict__ state, float* __restrict__ out_val, int32_t* __restrict__ out_idx,
                                                                     int32_t* __restrict__ passes, [[maybe_unused]] const SearchArgs<SEARCH> search) {
+    static_assert(SEARCH || !EXCL, "the per-pair target rides on the search arguments");
     const int lane = threadIdx.x & 63;
-    if constexpr (SEARCH) target = *search.target;
+    if constexpr (SEARCH && !EXCL) target = *search.target;
     for (int64_t pair = global_wave_id(); pair < n_pairs; pair += global_wave_count()) {
+        if constexpr (EXCL) target = search.target[pair];
         const DeepState st = state[pair];
         if (st.count >= target) continue;                                   // complete (wave-uniform): its lists are stale and its output is final
         const float* pv = part_val + pair * n_lists * kTopMax;
@@ -564,10 +642,10 @@ int score_topk_launch(const char* what, const float* features, int64_t ld, int32
     const size_t lds = eval_lds_bytes(dim, pb);
     if (pb == 2)
         hipLaunchKernelGGL((score_topk_kernel<2, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{});
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{}, ExclArgs<false>{});
     else
         hipLaunchKernelGGL((score_topk_kernel<1, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{});
+                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{}, ExclArgs<false>{});
     hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs,
                        static_cast<int>(n_lists * kTopMax), k, top_scores, top_items);
     return check_launch(what);
@@ -602,10 +680,35 @@ __global__ __launch_bounds__(kBlockThreads) void search_target_kernel(const uint
     if (tid == 0) *target = static_cast<int32_t>(count < k ? count : k);
 }
 
-template <bool COSINE, bool SEARCH = false>
+// once per ihg_search_topk_excluding call, after search_target_kernel has left the candidates' count in *n_candidates (its k = INT_MAX), one wave per pair:
+// target[c] = min(k, candidates - the ids of the pair's run that are candidates) - an excluded id that the mask already removes is not subtracted twice, and the
+// run is strictly ascending, so no id is counted twice either.  An id outside [0, n_items) is the caller's breach of contract; it is skipped here, not read through.
+__global__ __launch_bounds__(kBlockThreads) void exclude_target_kernel(const uint32_t* __restrict__ item_mask, int64_t n_items, int k, const int32_t* __restrict__ n_candidates,
+                                                                       const ExclArgs<true> excl, int32_t* __restrict__ target, int64_t n_pairs) {
+    const int lane = threadIdx.x & 63;
+    const int candidates = *n_candidates;
+    for (int64_t pair = global_wave_id(); pair < n_pairs; pair += global_wave_count()) {
+        const int64_t row = excl.row != nullptr ? excl.row[pair] : pair;    // (wave-uniform)
+        int hits = 0;
+        if (row >= 0) {
+            const int64_t end = excl.ptr[row + 1];
+            for (int64_t e = excl.ptr[row] + lane; e < end; e += kWave) {
+                const int64_t i = excl.items[e];
+                if (i >= 0 && i < n_items && (item_mask == nullptr || ((item_mask[i >> 5] >> (i & 31)) & 1u) != 0)) ++hits;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) hits += __shfl_xor(hits, off);
+        const int left = candidates - hits;
+        if (lane == 0) target[pair] = left < k ? left : k;
+    }
+}
+
+template <bool COSINE, bool SEARCH = false, bool EXCL = false>
 int score_topk_deep_launch(const char* what, const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                            const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
-                           int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t* passes, ihg_stream_t stream, SearchArgs<SEARCH> search = {}) {
+                           int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t* passes, ihg_stream_t stream, SearchArgs<SEARCH> search = {},
+                           ExclArgs<EXCL> excl = {}) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
     const int slices = eval_slices(n_pairs, n_items, dim);
@@ -618,8 +721,14 @@ int score_topk_deep_launch(const char* what, const float* features, int64_t ld, 
     const int target = static_cast<int>(std::min<int64_t>(k, n_items));           // (SEARCH: the most a mask leaves - the passes launched; the kernels read search.target)
     if constexpr (SEARCH) {
         int32_t* target_cell = reinterpret_cast<int32_t*>(state + n_pairs);
-        hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, search.item_mask, n_items, k, target_cell, passes, n_pairs);
-        search.target = target_cell;
+        if constexpr (EXCL) {                                               // the cell holds the candidates' count itself, and the 16 bytes after it begin target[n_pairs]
+            hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, search.item_mask, n_items, INT_MAX, target_cell, passes, n_pairs);
+            hipLaunchKernelGGL(exclude_target_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, search.item_mask, n_items, k, target_cell, excl, target_cell + 4, n_pairs);
+            search.target = target_cell + 4;
+        } else {
+            hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, search.item_mask, n_items, k, target_cell, passes, n_pairs);
+            search.target = target_cell;
+        }
     }
     hipLaunchKernelGGL((score_prepare_kernel<COSINE, SEARCH>), dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux, search);
     hipLaunchKernelGGL(deep_init_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n_pairs * k + kBlockThreads - 1) / kBlockThreads, 4096))), dim3(kBlockThreads), 0, s, state, n_pairs,
@@ -628,8 +737,8 @@ int score_topk_deep_launch(const char* what, const float* features, int64_t ld, 
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
     if (device < 0 || device >= 64 || !attr_set[device]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE, true, SEARCH>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE, true, SEARCH>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE, true, SEARCH, EXCL>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE, true, SEARCH, EXCL>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
         if (device >= 0 && device < 64) attr_set[device] = true;
     }
     const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
@@ -638,12 +747,12 @@ int score_topk_deep_launch(const char* what, const float* features, int64_t ld, 
     const int n_passes = (target + kTopMax - 1) / kTopMax;
     for (int pass = 0; pass < n_passes; ++pass) {
         if (pb == 2)
-            hipLaunchKernelGGL((score_topk_kernel<2, COSINE, true, SEARCH>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
-                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search);
+            hipLaunchKernelGGL((score_topk_kernel<2, COSINE, true, SEARCH, EXCL>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
+                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search, excl);
         else
-            hipLaunchKernelGGL((score_topk_kernel<1, COSINE, true, SEARCH>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
-                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search);
-        hipLaunchKernelGGL(merge_deep_kernel<SEARCH>, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs, static_cast<int>(n_lists), k, target, state, top_scores,
+            hipLaunchKernelGGL((score_topk_kernel<1, COSINE, true, SEARCH, EXCL>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
+                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search, excl);
+        hipLaunchKernelGGL((merge_deep_kernel<SEARCH, EXCL>), dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs, static_cast<int>(n_lists), k, target, state, top_scores,
                            top_items, passes, search);
     }
     return check_launch(what);
@@ -730,6 +839,44 @@ int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t quer
                                                             workspace, workspace_bytes, passes, stream, search)
                        : score_topk_deep_launch<false, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
                                                              workspace, workspace_bytes, passes, stream, search);
+}
+
+int64_t ihg_search_topk_excluding_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) {
+    const int64_t search = ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k);
+    return search == 0 ? 0 : search + (n_pairs * 4 + 15) / 16 * 16;         // + target[n_pairs] of exclude_target_kernel
+}
+
+int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
+                              const int64_t* users, const int64_t* queries, const float* query_rows, int64_t ld_q, int32_t q_dim, const uint32_t* item_mask,
+                              const int64_t* excl_ptr, const int32_t* excl_items, const int64_t* excl_row, int64_t n_excl_rows, float lambda_muq, int64_t n_pairs,
+                              int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes,
+                              ihg_stream_t stream) {
+    const char* what = "ihg_search_topk_excluding";
+    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kDeepMax);
+    if ((queries == nullptr) == (query_rows == nullptr)) return fail(IHG_ERR_INVALID, "%s: exactly one of queries and query_rows", what);
+    if (query_rows != nullptr && (q_dim < 1 || q_dim > dim || ld_q < q_dim)) return fail(IHG_ERR_INVALID, "%s: 1 <= q_dim <= dim and ld_q >= q_dim", what);
+    if ((excl_ptr == nullptr) != (excl_items == nullptr)) return fail(IHG_ERR_INVALID, "%s: excl_ptr and excl_items go together", what);
+    if (excl_ptr == nullptr && excl_row != nullptr) return fail(IHG_ERR_INVALID, "%s: excl_row without lists", what);
+    if (excl_ptr != nullptr && (n_excl_rows < 1 || (excl_row == nullptr && n_excl_rows != n_pairs && n_pairs > 0)))
+        return fail(IHG_ERR_INVALID, "%s: n_excl_rows >= 1, and == n_pairs without excl_row", what);
+    if (n_pairs == 0) return IHG_OK;
+    if (features == nullptr || item_bias == nullptr || users == nullptr || top_scores == nullptr || top_items == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
+    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
+    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
+    if (eval_lists(n_pairs, n_items, dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", what);
+    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, k))
+        return fail(IHG_ERR_INVALID, "%s: workspace too small", what);
+    const SearchArgs<true> search{query_rows, ld_q, q_dim, item_mask, nullptr};
+    if (excl_ptr == nullptr)                                                // no lists: the launches of ihg_search_topk
+        return cosine != 0 ? score_topk_deep_launch<true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
+                                                                workspace, workspace_bytes, passes, stream, search)
+                           : score_topk_deep_launch<false, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
+                                                                 workspace, workspace_bytes, passes, stream, search);
+    const ExclArgs<true> excl{excl_ptr, excl_items, excl_row};
+    return cosine != 0 ? score_topk_deep_launch<true, true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores,
+                                                                  top_items, workspace, workspace_bytes, passes, stream, search, excl)
+                       : score_topk_deep_launch<false, true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores,
+                                                                   top_items, workspace, workspace_bytes, passes, stream, search, excl);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import ctypes
 import os as _os
-from typing import Optional, Union
+from typing import Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -2014,12 +2014,41 @@ def pack_item_mask(candidates: Tensor, n_items: int) -> Tensor:
     return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
 
 
+def exclusion_lists(offsets: Tensor, items: Tensor, n_items: int) -> Tuple[Tensor, Tensor]:
+    """Per-row item lists as ``ihg_search_topk_excluding`` reads them: ``(ptr int64 [R + 1], items int32)`` with every run strictly ascending.  Input: ``offsets``
+    ``[R + 1]`` (non-decreasing, from 0 to ``len(items)``) and the flat ids of the rows, in any order, repeats allowed, in ``[0, n_items)``.  One sort of the keys
+    ``row * n_items + id`` orders every run and brings repeats together; the new offsets are a search for each row's first key.  Torch ops on the tensors' own
+    device, so it serves host tensors as well; the range of host tensors is checked here, that of device tensors is the caller's."""
+    n_items = int(n_items)
+    offsets = offsets.reshape(-1).to(torch.int64)
+    ids = items.reshape(-1).to(device=offsets.device, dtype=torch.int64)
+    if offsets.numel() < 1:
+        raise ValueError('exclusion_lists: offsets holds at least the leading 0')
+    n_rows = int(offsets.shape[0]) - 1
+    if not offsets.is_cuda:
+        if int(offsets[0]) != 0 or int(offsets[-1]) != ids.numel() or bool((offsets[1:] < offsets[:-1]).any()):
+            raise ValueError(f'exclusion_lists: offsets run from 0 to the {ids.numel()} ids without decreasing')
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_items):
+            raise ValueError(f'excluded item id outside [0, {n_items})')
+    rows = torch.repeat_interleave(torch.arange(n_rows, dtype=torch.int64, device=offsets.device), offsets[1:] - offsets[:-1], output_size=int(ids.shape[0]))
+    keys = torch.unique(rows * n_items + ids)                               # (sorted)
+    ptr = torch.searchsorted(keys, torch.arange(n_rows + 1, dtype=torch.int64, device=offsets.device) * n_items)
+    return ptr, (keys % n_items).to(torch.int32)
+
+
 def search_topk(features: Tensor, users: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int, *, queries: Optional[Tensor] = None,
-                query_rows: Optional[Tensor] = None, candidates: Optional[Tensor] = None, cosine: bool = False):
+                query_rows: Optional[Tensor] = None, candidates: Optional[Tensor] = None, cosine: bool = False,
+                exclude: Optional[Tuple[Tensor, Tensor]] = None, exclude_rows: Optional[Tensor] = None):
     """``score_topk_deep`` for a search (``ihg_search_topk``): ``(top_items [C, k] int32, top_scores [C, k], passes [C] int32)``.  Exactly one of ``queries`` (int64
     ``[C]`` query indices) and ``query_rows`` (float32 ``[C, q]``, ``q <= D``: the rows of queries that are not in the graph - columns ``q ..`` count as zero);
     ``users[c] < 0``: no user, the mixed row is the query row; ``candidates`` (``pack_item_mask``'s input): only these items are ranked, a pair is complete at
-    ``min(k, candidates)`` and the rest of its row is the ``-1`` tail."""
+    ``min(k, candidates)`` and the rest of its row is the ``-1`` tail.
+    ``exclude`` (``ihg_search_topk_excluding``): per-search lists of items that are never ranked, ``(ptr [R + 1], items)``.  int32 ``items`` are taken as
+    ``exclusion_lists`` returned them (every run strictly ascending); items of any other integer type are raw (any order, repeats) and go through it first.
+    ``exclude_rows`` (int64 ``[C]``): search ``c`` leaves out run ``exclude_rows[c]``, nothing where that is negative; without it search ``c`` leaves out run ``c``
+    and ``R = C``.  A search is then complete at ``min(k, its candidates that it does not exclude)``.  Without ``exclude`` the call is ``ihg_search_topk``'s."""
+    if exclude is None and exclude_rows is not None:
+        raise ValueError('search_topk: exclude_rows without exclude')
     lib = _lib.load()
     if not score_topk_supported(features):
         raise _lib.IhgnnHipError(f'ihg_search_topk needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
@@ -2044,11 +2073,33 @@ def search_topk(features: Tensor, users: Tensor, query_row0: int, item_row0: int
     top_scores = torch.empty(n_pairs, width, dtype=torch.float32, device=features.device)
     top_items = torch.empty(n_pairs, width, dtype=torch.int32, device=features.device)
     passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
-    ws = _workspace(int(lib.ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
-    with profiler.kernel('search_topk_cosine' if cosine else 'search_topk', n_pairs, dim):
-        _lib.check(lib.ihg_search_topk(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), _ptr(query_rows),
-                                       ld_q, q_dim, _ptr(mask), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)),
-                                       _ptr(passes), _stream()), 'ihg_search_topk')
+    if exclude is None:
+        ws = _workspace(int(lib.ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
+        with profiler.kernel('search_topk_cosine' if cosine else 'search_topk', n_pairs, dim):
+            _lib.check(lib.ihg_search_topk(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), _ptr(query_rows),
+                                           ld_q, q_dim, _ptr(mask), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)),
+                                           _ptr(passes), _stream()), 'ihg_search_topk')
+        return top_items, top_scores, passes
+    ptr, ids = exclude
+    if ids.dtype != torch.int32:
+        ptr, ids = exclusion_lists(ptr, ids, n_items)
+    ptr = ptr.to(device=features.device, dtype=torch.int64).contiguous()
+    ids = ids.to(device=features.device).contiguous()
+    if ids.numel() == 0:
+        ids = ids.new_zeros(1)                                              # (an empty tensor has no address, and the entry point takes a null list for "no lists")
+    n_rows = int(ptr.shape[0]) - 1
+    if exclude_rows is not None:
+        exclude_rows = exclude_rows.to(device=features.device, dtype=torch.int64).contiguous()
+        if exclude_rows.dim() != 1 or int(exclude_rows.shape[0]) != n_pairs:
+            raise ValueError(f'search_topk: {n_pairs} searches but exclude_rows of {tuple(exclude_rows.shape)}')
+    elif n_rows != n_pairs:
+        raise ValueError(f'search_topk: {n_pairs} searches but {n_rows} exclusion lists (exclude_rows= maps searches to shared lists)')
+    ws = _workspace(int(lib.ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
+    with profiler.kernel('search_topk_excluding_cosine' if cosine else 'search_topk_excluding', n_pairs, dim):
+        _lib.check(lib.ihg_search_topk_excluding(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries),
+                                                 _ptr(query_rows), ld_q, q_dim, _ptr(mask), _ptr(ptr), _ptr(ids), _ptr(exclude_rows), n_rows, float(lam), n_pairs, int(k),
+                                                 _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)), _ptr(passes), _stream()),
+                   'ihg_search_topk_excluding')
     return top_items, top_scores, passes
 
 

@@ -724,6 +724,34 @@ int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t quer
                     void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes, ihg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE: a search that leaves out a different item set per pair ("not what this user already bought").  ihg_search_topk_excluding is ihg_search_topk - every
+ * argument, output, tie order, -1 tail and limit - plus per-pair exclusion lists in CSR form:
+ *   excl_ptr     int64 [n_excl_rows + 1], non-decreasing, excl_ptr[0] = 0
+ *   excl_items   int32 [excl_ptr[n_excl_rows]]: run r is excl_items[excl_ptr[r] .. excl_ptr[r + 1]), STRICTLY ASCENDING, ids in [0, n_items)
+ *   excl_row     int64 [n_pairs] or NULL: pair c leaves out run excl_row[c]; a negative entry leaves out nothing.  NULL: pair c leaves out run c, and
+ *                n_excl_rows == n_pairs.  With excl_row one CSR of "items per user" serves any batch of searches without a copy per search.
+ * An item of its pair's run is never ranked for that pair.  Pair c is complete at target_c = min(k, |candidates minus its run|) - an excluded id that item_mask
+ * already removes is not subtracted twice - and the rest of its row is the (-FLT_MAX, -1) tail; passes[c] <= ceil(target_c / 10).  target_c is formed on the
+ * device (two small launches per call, none per pass, no host read); the call still launches ceil(min(k, n_items) / 10) passes: an excluded item is in no lane's
+ * list, so the lists stay exact over what remains and an incomplete pair still gains ten ranks per pass, or all that is left.
+ * The scores of the items that remain are the bits of ihg_search_topk: the scoring loop computes every score with the same expression in the same item order, and
+ * exclusion only decides whether a score may enter a lane's list - each lane follows the run of its pair with a cursor as its item ids ascend, so the cost grows
+ * with the lists, not with pairs x items, and the memory is that of the lists plus 4 bytes per pair.  A pair whose run is empty gets the row ihg_search_topk
+ * returns for it; with excl_ptr == NULL (then excl_items and excl_row are NULL too) the call launches what ihg_search_topk launches.
+ * CONTRACT: the order inside a run, the range of the ids and of excl_row's entries (< n_excl_rows) live on the device and are the caller's to keep
+ * (ops.exclusion_lists builds such lists); a run that is not strictly ascending gives a wrong ranking, not a fault.
+ * IHG_ERR_INVALID before anything is launched, in ihg_search_topk's order: its size checks, its query-source checks, then excl_ptr without excl_items or the
+ * reverse, excl_row without lists, n_excl_rows < 1 with lists (or != n_pairs with lists and no excl_row), then its null-pointer, width and list checks, then a
+ * workspace smaller than ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, k) (that of ihg_search_topk + 4 bytes per pair, rounded up to 16).
+ */
+int64_t ihg_search_topk_excluding_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k);
+int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
+                              const float* item_bias, const int64_t* users, const int64_t* queries, const float* query_rows, int64_t ld_q, int32_t q_dim,
+                              const uint32_t* item_mask, const int64_t* excl_ptr, const int32_t* excl_items, const int64_t* excl_row, int64_t n_excl_rows,
+                              float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes,
+                              int32_t cosine, int32_t* passes, ihg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE: the attention of the GAT baseline over the pairwise graph (csrc/gat.hip).  Replaces GATLayer.forward after its transform
  * (Models/GnnLayers.py:98-115: the [nnz, 2, d] row gather, feature_aggregate, dgl.ops.edge_softmax and dgl.ops.u_mul_e_sum) and autograd's backward of it.
  * Graph: the symmetric CSR of the pairwise adjacency (ihg_build_pair_csr) - entry p of row v with column u = ids[p] is the edge u -> v, so row v lists
