@@ -44,6 +44,28 @@ def clip_norm(text: str) -> float:
         raise argparse.ArgumentTypeError(str(refused))
 
 
+def checked_candidate_count(value, item_count=None) -> int:
+    """The N of ``--eval_candidates`` / ``Gs.Evaluation.sampled_candidates``: an integer >= 0 (0 = off) and, once the catalogue is known, below its size - or a
+    ``ValueError``; the one check the parser and the driver share."""
+    try:
+        number = int(value)
+    except (TypeError, ValueError):
+        raise ValueError(f'--eval_candidates takes an integer, got {value!r}')
+    if number < 0:
+        raise ValueError(f'--eval_candidates takes a count >= 0 (0 = off), got {number}')
+    if item_count is not None and number >= int(item_count):
+        raise ValueError(f'--eval_candidates {number}: the catalogue has {int(item_count)} items - draw fewer than that (0 ranks the whole catalogue)')
+    return number
+
+
+def candidate_count(text: str) -> int:
+    """``checked_candidate_count`` as an argparse type."""
+    try:
+        return checked_candidate_count(text)
+    except ValueError as refused:
+        raise argparse.ArgumentTypeError(str(refused))
+
+
 # (dest, flags, kind, default, help); kind is a type or 'flag'
 _FLAGS = (
     ('checkpoint', ('--checkpoint', '--cp'), str, '', 'checkpoint file inside the result dir, or "latest"; empty = fresh start'),
@@ -78,6 +100,10 @@ _FLAGS = (
     # not in the reference, which ranks every item of the catalogue for every test log
     ('filter_seen', ('--filter_seen',), 'flag', False, 'evaluate under the "filter seen" protocol: rank each test log without the items its user interacted with in training '
                                                        '(the log\'s own positives stay rankable; Gs.Evaluation.filter_seen)'),
+    # not in the reference: the sampled-metrics protocol much of the literature reports (the positive ranked among 99 or 999 drawn items)
+    ('eval_candidates', ('--eval_candidates',), candidate_count, 0, 'evaluate on sampled candidates: rank each test log among its own logged items plus N items drawn uniformly without '
+                                                                   'replacement from the rest of the catalogue (Gs.Evaluation.sampled_candidates; 0 = off: the whole catalogue). '
+                                                                   'Sampled metrics are not comparable with whole-catalogue ones'),
     # not in the reference, which trains on nn.BCEWithLogitsLoss only (Main.py:191)
     ('loss', ('--loss',), str, 'bce', 'training objective: bce (the reference\'s point-wise loss) | bpr (pairwise: every positive against each of its negatives) | '
                                       'softmax (the positive against its own negatives; Gs.Training.loss)'),

@@ -50,6 +50,8 @@ class Gs:
     class Evaluation:
         extra_cutoffs = ()               # not in the reference (which reports @10 only): further cutoffs K in 11..128 (--cutoffs), HR / NDCG / MAP @K beside the @10 triple
         filter_seen = False              # not in the reference (which ranks the whole catalogue): True (--filter_seen) ranks every test log without the items its user interacted with in training, the log's own positives kept
+        sampled_candidates = 0           # not in the reference: N > 0 (--eval_candidates N) ranks every test log among its own logged items plus N items drawn uniformly from the rest of the catalogue (the sampled-metrics protocol; not comparable with whole-catalogue metrics)
+        candidate_seed = 0               # the seed of those draws: log i draws from numpy's default_rng([candidate_seed, i]), whatever the rank or the chunk it is evaluated in
 
     class Srrl:                          # the Srrl baseline (GlobalSettings.py:87-91)
         KG_loss = True                   # train the KG embeddings (srrl_steps KG steps per epoch) and feed them to the PS model through g_u / g_i

@@ -44,12 +44,64 @@ def seen_lists_for_logs(logs, indices, ptr, items) -> Tuple[List[int], List[int]
     return offsets, flat
 
 
-def _evaluate_batched(model, logs, item_count: int, device: torch.device, indices, seen=None) -> List[Tuple[int, Metrics]]:
+def sampled_candidate_set(index: int, own_items, item_count: int, count: int, seed: int = 0):
+    """The set test log ``index`` is ranked among under ``Gs.Evaluation.sampled_candidates = count``: its own logged items plus ``count`` items drawn uniformly without
+    replacement from the rest of the catalogue - int32, ascending.  The rule depends on the log's index alone, so every epoch, every rank and every chunking sees the
+    same set: ``default_rng([seed, index])`` draws ``min(count + len(own), I)`` distinct ids in one call, the log's own are dropped from the draw and the first
+    ``count`` of the rest are kept (all of them - the whole catalogue - when fewer remain)."""
+    import numpy as np
+    own = np.unique(np.asarray(own_items, np.int64))
+    rng = np.random.default_rng([int(seed), int(index)])
+    draw = rng.choice(int(item_count), size=min(int(count) + len(own), int(item_count)), replace=False, shuffle=False)
+    drawn = draw[~np.isin(draw, own)][:int(count)]
+    return np.union1d(own, drawn).astype(np.int32)
+
+
+class SampledCandidates:
+    """The sets of the logs ``indices`` as ONE CSR (``ptr`` int64 ``[len + 1]``, ``items`` int32, every run ascending: what ``ops.search_candidates`` takes as
+    prepared), built once and kept beside the test logs (``for_loader``)."""
+
+    def __init__(self, logs, indices, item_count: int, count: int, seed: int = 0):
+        import numpy as np
+        self.indices = np.asarray(list(indices), np.int64)
+        runs = [sampled_candidate_set(int(i), logs[int(i)][2], item_count, count, seed) for i in self.indices]
+        self.ptr = np.zeros(len(runs) + 1, np.int64)
+        np.cumsum([len(r) for r in runs], out=self.ptr[1:])
+        self.items = np.concatenate(runs).astype(np.int32) if runs else np.zeros(0, np.int32)
+        self._position = {int(i): p for p, i in enumerate(self.indices.tolist())}
+
+    def lists_for(self, part) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(offsets int64 [len(part) + 1], items int32)`` of the logs ``part``, in that order."""
+        import numpy as np
+        pos = np.asarray([self._position[int(i)] for i in part], np.int64)
+        lengths = self.ptr[pos + 1] - self.ptr[pos]
+        offsets = np.zeros(len(pos) + 1, np.int64)
+        np.cumsum(lengths, out=offsets[1:])
+        if len(pos) and np.array_equal(pos, np.arange(pos[0], pos[0] + len(pos))):      # a contiguous share: one slice
+            flat = self.items[self.ptr[pos[0]]:self.ptr[pos[-1] + 1]]
+        else:
+            flat = np.concatenate([self.items[self.ptr[p]:self.ptr[p + 1]] for p in pos]) if len(pos) else np.zeros(0, np.int32)
+        return torch.from_numpy(offsets), torch.from_numpy(np.ascontiguousarray(flat, np.int32))
+
+    @staticmethod
+    def for_loader(dataloader, indices, item_count: int, count: int, seed: int = 0) -> 'SampledCandidates':
+        """The sets of this rank's share of ``dataloader.logs``, built at the first evaluation and reused by every later one."""
+        key = (int(count), int(seed), int(item_count), len(indices), int(indices[0]) if len(indices) else -1)
+        cached = getattr(dataloader, '_sampled_candidates', None)
+        if cached is None or cached[0] != key:
+            cached = (key, SampledCandidates(dataloader.logs, indices, item_count, count, seed))
+            dataloader._sampled_candidates = cached
+        return cached[1]
+
+
+def _evaluate_batched(model, logs, item_count: int, device: torch.device, indices, seen=None, sampled: Optional[SampledCandidates] = None) -> List[Tuple[int, Metrics]]:
     """Top-10 of many searches per launch (``ihg_score_topk`` / ``ihg_score_topk_cosine``, whichever head ``Gs.Prediction.use_cosine_similarity`` names: scores on
     the matrix cores, running top-10 in registers, no ``[C, I]`` matrix), one D2H copy per chunk (the reference scores one log at a time and syncs on every one,
     ``TrainTestHelper.py:58-67``, ``Metrics.py:60-61``).  With ``Gs.Evaluation.extra_cutoffs`` the ONE ranking per chunk is as deep as the largest cutoff
     (``ihg_score_topk_deep``) and every cutoff's metrics are read from a prefix of it.  ``seen`` (``GraphDataset.user_item_lists`` under
-    ``Gs.Evaluation.filter_seen``): every log is ranked without ``seen_lists_for_logs``' items, per-search lists built on the host per chunk."""
+    ``Gs.Evaluation.filter_seen``): every log is ranked without ``seen_lists_for_logs``' items, per-search lists built on the host per chunk.  ``sampled``
+    (``Gs.Evaluation.sampled_candidates``): every log is ranked among ITS set only, by the list kernels (``top_items(..., candidate_lists=)``: the work is the sets'
+    size, not the catalogue's); composes with ``seen``."""
     out: List[Tuple[int, Metrics]] = []
     chunk = 8192
     extras = tuple(Gs.Evaluation.extra_cutoffs)
@@ -57,7 +109,13 @@ def _evaluate_batched(model, logs, item_count: int, device: torch.device, indice
     for lo in range(0, len(indices), chunk):
         part = indices[lo:lo + chunk]
         uq = torch.tensor([(logs[i][0], logs[i][1]) for i in part], dtype=torch.long, device=device)
-        if seen is not None:
+        if sampled is not None:
+            exclude = None
+            if seen is not None:
+                offsets, flat = seen_lists_for_logs(logs, part, *seen)
+                exclude = (torch.tensor(offsets, dtype=torch.int64), torch.tensor(flat, dtype=torch.int64))
+            top = model.top_items(uq[:, 0], uq[:, 1], k, exclude=exclude, candidate_lists=sampled.lists_for(part))[0].tolist()
+        elif seen is not None:
             offsets, flat = seen_lists_for_logs(logs, part, *seen)
             top = model.top_items(uq[:, 0], uq[:, 1], k, exclude=(torch.tensor(offsets, dtype=torch.int64), torch.tensor(flat, dtype=torch.int64)))[0].tolist()
         else:
@@ -89,7 +147,11 @@ def test_and_get_avg_metrics(model, dataset_train: GraphDataset, dataloader: Tes
         try:
             if hasattr(model, 'top_items'):
                 filtered = bool(Gs.Evaluation.filter_seen)
-                scored = _evaluate_batched(model, logs, dataset_train.item_count, device, mine, dataset_train.user_item_lists if filtered else None)
+                drawn = int(Gs.Evaluation.sampled_candidates)
+                if drawn < 0 or drawn >= dataset_train.item_count:
+                    raise ValueError(f'Gs.Evaluation.sampled_candidates = {drawn}: 0 (off) or a count below the {dataset_train.item_count} items of the catalogue')
+                sampled = SampledCandidates.for_loader(dataloader, mine, dataset_train.item_count, drawn, int(Gs.Evaluation.candidate_seed)) if drawn else None
+                scored = _evaluate_batched(model, logs, dataset_train.item_count, device, mine, dataset_train.user_item_lists if filtered else None, sampled)
             else:
                 scored = []
                 for i in mine:
@@ -122,6 +184,7 @@ def test_and_get_avg_metrics(model, dataset_train: GraphDataset, dataloader: Tes
                      for row in table.tolist()]
     seconds = time.time() - started
     IOHelper.LogPrint(f'evaluation done in {seconds:<.2f} s over {counted} usable search logs' +
+                      (f', each ranked among its own items and {int(Gs.Evaluation.sampled_candidates)} sampled ones' if hasattr(model, 'top_items') and Gs.Evaluation.sampled_candidates else '') +
                       (', each ranked without its user\'s training items.' if hasattr(model, 'top_items') and Gs.Evaluation.filter_seen else '.'))
     IOHelper.LogPrint(average.to_string(highlight=True), put_time_in_single_line=True)
     IOHelper.LogPrint()

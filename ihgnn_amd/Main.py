@@ -50,10 +50,13 @@ def apply_prediction_settings(args) -> None:
 
 
 def apply_evaluation_settings(args) -> None:
-    """``--cutoffs`` -> ``Gs.Evaluation.extra_cutoffs`` and ``--filter_seen`` -> ``Gs.Evaluation.filter_seen``, assigned both ways like the head above (not in the
+    """``--cutoffs`` -> ``Gs.Evaluation.extra_cutoffs``, ``--filter_seen`` -> ``Gs.Evaluation.filter_seen`` and ``--eval_candidates N`` ->
+    ``Gs.Evaluation.sampled_candidates``, assigned both ways like the head above (not in the
     reference, which reports @10 only, over the whole catalogue)."""
     Gs.Evaluation.extra_cutoffs = tuple(getattr(args, 'cutoffs', ()) or ())
     Gs.Evaluation.filter_seen = bool(getattr(args, 'filter_seen', False))
+    from .Helpers.ArgsParser import checked_candidate_count
+    Gs.Evaluation.sampled_candidates = checked_candidate_count(getattr(args, 'eval_candidates', 0) or 0)      # (a caller that builds its own args: the parser's check)
 
 
 def apply_training_settings(args) -> None:
@@ -108,6 +111,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --hard_negatives has not been built for it')
     if getattr(args, 'filter_seen', False):
         raise NotImplementedError('--model Srrl ranks the whole catalogue: --filter_seen has not been built for its scoring kernels')
+    if int(getattr(args, 'eval_candidates', 0) or 0) > 0:
+        raise NotImplementedError('--model Srrl ranks the whole catalogue: --eval_candidates has not been built for its scoring kernels')
     if getattr(args, 'query_transform', Gsv.mean) == Gsv.gru:
         raise NotImplementedError('--model Srrl embeds its queries by the bag mean or the activation transform: --query_transform gru has not been built for it')
     widest = ops.cat_linear_max_width()
@@ -202,7 +207,9 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
          f'model RawGnn | dataset {dataset_name} | {layer_count} x {layer_type.__name__} | order {order}{" + phase-2 attention" if phase2 else ""} | ') +
         f'query transform {Gs.Query.transform}{" (" + Gs.Query.transform_activation.__name__ + ")" if Gs.Query.transform == Gsv.activation else ""} | '
         f'head {"cosine similarity" if Gs.Prediction.use_cosine_similarity else "dot product"} | loss {Gs.Training.loss} | validation {Gs.use_valid_dataset}' +
-        (' | evaluation filtered: without the user\'s training items' if Gs.Evaluation.filter_seen else ''))
+        (' | evaluation filtered: without the user\'s training items' if Gs.Evaluation.filter_seen else '') +
+        (f' | evaluation sampled: each log among its own items and {Gs.Evaluation.sampled_candidates} drawn ones (not comparable with whole-catalogue metrics)'
+         if Gs.Evaluation.sampled_candidates else ''))
     say(f'store metrics {args.storemetrics} | store checkpoint {args.storecheckpoint} | load {args.checkpoint or False}\n')
 
     dataset_train = GraphDataset(
@@ -225,6 +232,9 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         dataloader_train = DataLoader(dataset_train, batch_sampler=sampler, collate_fn=GraphDataset.collate_fn)
     else:
         dataloader_train = DataLoader(dataset_train, Gs.batch_size, shuffle=True, collate_fn=GraphDataset.collate_fn)
+    if Gs.Evaluation.sampled_candidates:
+        from .Helpers.ArgsParser import checked_candidate_count
+        checked_candidate_count(Gs.Evaluation.sampled_candidates, dataset_train.item_count)      # (N >= I is refused here, where the catalogue is known)
     dataloader_valid = TestSearchLogDataLoader(os.path.join(data_dir, 'valid_data.csv'), dataset_train, device)
     dataloader_test = TestSearchLogDataLoader(os.path.join(data_dir, 'test_data.csv'), dataset_train, device)
 

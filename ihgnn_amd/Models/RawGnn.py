@@ -303,20 +303,29 @@ class RawGnn(nn.Module):
             item_feature = item_feature / item_feature.norm(dim=1, keepdim=True).clamp_min(1e-8)
         return torch.addmm(head.items_bias.unsqueeze(0), mixed, item_feature.t())
 
-    def top_items(self, user_indices: Tensor, query_indices: Tensor, k: int = 10, exclude=None):
+    def top_items(self, user_indices: Tensor, query_indices: Tensor, k: int = 10, exclude=None, candidate_lists=None):
         """``(items [C, k] int32, scores [C, k])``: the ``k`` best items of each (user, query) pair over the whole catalogue, best
         first - what ``Metrics.calculate_on_all_items`` keeps of ``forward(u, q, None)`` (``Metrics.py:60-61``) - from the fused
         HIP scoring + running top-k kernel; the ``[C, I]`` scores are never stored.  Ties: ascending item id.  ``k`` up to ``ops.score_topk_max_k()`` = 128
         (beyond ten the kernel runs in passes, ``ops.score_topk_deep``; the reference itself stops at ten).  No torch path: any feature width
         ``d (L + 1)`` up to ``MAX_SCORED_WIDTH`` (checked at construction).  Scores with the head that ``Gs.Prediction.use_cosine_similarity`` names.
         ``exclude=(offsets [C + 1], items)``: pair ``c`` is ranked without ``items[offsets[c]:offsets[c + 1]]`` (any order, repeats allowed) - the scores of the
-        other items are the same bits, and a row with fewer than ``k`` items left ends in ``-1``."""
+        other items are the same bits, and a row with fewer than ``k`` items left ends in ``-1``.
+        ``candidate_lists=(offsets [C + 1], items)``: pair ``c`` is ranked among ``items[offsets[c]:offsets[c + 1]]`` only (any order, repeats allowed; int32 items
+        are taken as ``ops.candidate_lists`` returned them) by the list kernels (``ops.search_candidates``): only the listed rows are read, and the scores are plain
+        float32 sums, close to but not the bits of the whole-catalogue kernels'.  Composes with ``exclude``."""
         from .. import ops
         features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
         ds, head = self.dataset, self.prediction_layer
         if k > ops.score_topk_max_k():
             raise ValueError(f'RawGnn.top_items ranks at most {ops.score_topk_max_k()} items per pair, got k = {k}')
         k = min(k, ds.item_count)
+        if candidate_lists is not None:
+            lists = None if exclude is None else ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
+            items, scores, _ = ops.search_candidates(features, user_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq,
+                                                     k, lists=(torch.as_tensor(candidate_lists[0]), torch.as_tensor(candidate_lists[1])), queries=query_indices,
+                                                     exclude=lists, cosine=Gs.Prediction.use_cosine_similarity)
+            return items, scores
         if exclude is not None:
             lists = ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
             items, scores, _ = ops.search_topk(features, user_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
@@ -325,7 +334,7 @@ class RawGnn(nn.Module):
         return ops.score_topk(features, user_indices, query_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph,
                               head.items_bias, head.lambda_muq, k, cosine=Gs.Prediction.use_cosine_similarity)
 
-    def _check_search_inputs(self, users, queries, words, offsets, candidates, exclude=None, exclude_seen=False):
+    def _check_search_inputs(self, users, queries, words, offsets, candidates, exclude=None, exclude_seen=False, candidate_lists=None):
         """The host-side checks of ``search``, before anything is launched (a tensor that already lives on the device is taken as checked: reading it back would
         stall the stream the answer is waited on).  Returns ``(words, offsets)`` as int64 numpy arrays (``None, None`` with ``queries``)."""
         import numpy as np
@@ -370,6 +379,16 @@ class RawGnn(nn.Module):
                 raise ValueError('RawGnn.search: the offsets of exclude= start at 0, do not decrease and end at the number of items')
             if ei is not None and ei.size and (ei.min() < 0 or ei.max() >= ds.item_count):
                 raise ValueError(f'RawGnn.search: excluded item id outside [0, {ds.item_count})')
+        if candidate_lists is not None:
+            if not isinstance(candidate_lists, (tuple, list)) or len(candidate_lists) != 2:
+                raise ValueError('RawGnn.search: candidate_lists= is (offsets [C + 1], items)')
+            co, ci = on_host(candidate_lists[0]), on_host(candidate_lists[1])
+            if co is not None and (co.ndim != 1 or co.size != n_pairs + 1):
+                raise ValueError(f'RawGnn.search: candidate_lists= needs {n_pairs + 1} offsets for {n_pairs} searches')
+            if co is not None and ci is not None and (co[0] != 0 or np.any(np.diff(co) < 0) or co[-1] != ci.size):
+                raise ValueError('RawGnn.search: the offsets of candidate_lists= start at 0, do not decrease and end at the number of items')
+            if ci is not None and ci.size and (ci.min() < 0 or ci.max() >= ds.item_count):
+                raise ValueError(f'RawGnn.search: listed candidate item id outside [0, {ds.item_count})')
         if words is None:
             return None, None
         w = np.asarray(words.detach().cpu() if isinstance(words, Tensor) else words, dtype=np.int64).reshape(-1)
@@ -383,7 +402,8 @@ class RawGnn(nn.Module):
         return w, o
 
     @torch.no_grad()
-    def search(self, users, *, queries=None, words=None, offsets=None, k: int = 10, candidates=None, exclude=None, exclude_seen: bool = False):
+    def search(self, users, *, queries=None, words=None, offsets=None, k: int = 10, candidates=None, exclude=None, exclude_seen: bool = False, candidate_lists=None,
+               return_list_scores: bool = False):
         """``(items [C, k] int32, scores [C, k])``: ``top_items`` for a search as it arrives.  ``users`` int64 ``[C]``, ``-1`` = nobody logged in: the head's
         ``user_feature is None`` branch (``PredictionLayers.py:34-37``), the mixed row is the query row.  The query is EITHER ``queries`` (training query indices) OR
         ``words`` with ``offsets`` (flat 0-based word ids and the start of every bag, as for ``nn.EmbeddingBag``): a query the graph has not seen is an isolated node -
@@ -394,9 +414,17 @@ class RawGnn(nn.Module):
         repeats allowed), a different set per search where ``candidates`` is one for all.  ``exclude_seen=True``: every search of a logged-in user is answered
         without the items that user interacted with in training (``GraphDataset.user_item_lists``, one copy on the device shared by all searches; ``-1`` excludes
         nothing).  Both compose with everything else, and the scores of the items that remain do not change by a bit.
+        ``candidate_lists=(offsets [C + 1], items)``: a different SHORTLIST per search - search ``c`` ranks ``items[offsets[c]:offsets[c + 1]]`` only (any order,
+        repeats allowed; int32 items are taken as ``ops.candidate_lists`` returned them), what a first retrieval stage hands over for re-ranking.  The list kernels
+        (``ops.search_candidates``) read only the listed item rows, so the cost is the lists' length, not the catalogue's; their scores are plain float32 sums,
+        within a derived bound of the float64 score but NOT the bits of the whole-catalogue call.  Composes with ``queries`` / ``words``, ``-1`` users, ``candidates``,
+        ``exclude`` / ``exclude_seen`` and both heads; a search ranks ``min(k, what its list, the mask and its exclusions leave)`` items, then ``-1``.  Without the
+        keyword the call takes the whole-catalogue path and returns its bits.
         Features, head and ``k`` as in ``top_items``; no retraining, no new parameter, no ``[C, I]`` matrix."""
         from .. import ops
-        w, o = self._check_search_inputs(users, queries, words, offsets, candidates, exclude, exclude_seen)
+        w, o = self._check_search_inputs(users, queries, words, offsets, candidates, exclude, exclude_seen, candidate_lists)
+        if return_list_scores and candidate_lists is None:
+            raise ValueError('RawGnn.search: return_list_scores needs candidate_lists=')
         ds, head = self.dataset, self.prediction_layer
         if k < 1 or k > ops.score_topk_max_k():
             raise ValueError(f'RawGnn.search ranks 1 to {ops.score_topk_max_k()} items per pair, got k = {k}')
@@ -415,10 +443,28 @@ class RawGnn(nn.Module):
             lists, rows = ds.user_item_lists_on(features.device), users         # (a user IS the row of the shared lists; -1 names none)
         elif exclude is not None:
             lists = ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
+        if candidate_lists is not None:
+            shortlists = (torch.as_tensor(candidate_lists[0]), torch.as_tensor(candidate_lists[1]))
+            if shortlists[1].dtype != torch.int32:
+                shortlists = ops.candidate_lists(shortlists[0], shortlists[1], ds.item_count)
+            out = ops.search_candidates(features, users, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
+                                        lists=shortlists, queries=queries, query_rows=query_rows, candidates=candidates, exclude=lists, exclude_rows=rows,
+                                        cosine=Gs.Prediction.use_cosine_similarity, return_scores=return_list_scores)
+            if return_list_scores:
+                return out[0], out[1], (shortlists[0], shortlists[1], out[3])
+            return out[0], out[1]
         items, scores, _ = ops.search_topk(features, users, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
                                            queries=queries, query_rows=query_rows, candidates=candidates, cosine=Gs.Prediction.use_cosine_similarity,
                                            exclude=lists, exclude_rows=rows)
         return items, scores
+
+    @torch.no_grad()
+    def score_candidates(self, users, *, candidate_lists, queries=None, words=None, offsets=None):
+        """``(ptr [C + 1], items int32, scores float32)``: the score of EVERY candidate of every search at its slot in the sorted lists (``ops.candidate_lists`` of
+        ``candidate_lists=(offsets [C + 1], items)``: each run ascending, repeats removed) - for callers who blend the model's score with a first-stage score.  The
+        launch is ``search``'s with ``candidate_lists=``; ``users`` / ``queries`` / ``words`` with ``offsets`` as there."""
+        _, _, listed = self.search(users, queries=queries, words=words, offsets=offsets, k=1, candidate_lists=candidate_lists, return_list_scores=True)
+        return listed
 
     def save_features_for_test(self) -> None:
         """Cache one propagation for the evaluation loop (call under ``torch.no_grad()``)."""

@@ -1,10 +1,12 @@
-"""Answer searches with a trained model: ``python -m ihgnn_amd.Search --ds <dataset> --cp <checkpoint | latest> [--k K] [--candidates FILE] [--exclude_seen] < searches``.
+"""Answer searches with a trained model: ``python -m ihgnn_amd.Search --ds <dataset> --cp <checkpoint | latest> [--k K] [--candidates FILE] [--exclude_seen] [--shortlists] < searches``.
 
 The model is described by the driver's own flags (``--ds --gnn --gnns --fo --emb --cosine --query_transform --query_activation --device``, ``Helpers/ArgsParser.py``)
 and built as ``Main.py`` builds it; ``--cp`` is a checkpoint file (a path, or a name inside the run's result directory) or ``latest``.  Every line of the standard
 input is one search, ``user<TAB>w1 w2 ...``: the user's index (``-1``: nobody is logged in) and the query's 0-based word ids as ``queries_multihot.txt`` holds them -
 the query need not be one the model was trained on (``RawGnn.search``).  ``--candidates FILE`` (one item id per line) restricts every search to these items;
-``--exclude_seen`` answers every search of a logged-in user without the items that user interacted with in training.
+``--exclude_seen`` answers every search of a logged-in user without the items that user interacted with in training.  ``--shortlists``: every line is
+``user<TAB>w1 w2 ...<TAB>i1 i2 ...`` and the search is ranked over those item ids only (``RawGnn.search(candidate_lists=)``: the shortlist of a first retrieval
+stage; an empty third field gives an empty output line); both other flags compose with it.
 Output: one line per search, ``item:score`` pairs, best first.  One process; the features are propagated once and the searches are answered in batches.
 """
 import os
@@ -29,6 +31,16 @@ def parse_search_line(line: str):
     """``'user<TAB>w1 w2 ...'`` -> ``(user, [word ids])``; the words may be missing (an empty bag)."""
     head, _, tail = line.rstrip('\n').partition('\t')
     return int(head), [int(w) for w in tail.split()]
+
+
+def parse_shortlist_line(line: str):
+    """``'user<TAB>w1 w2 ...<TAB>i1 i2 ...'`` -> ``(user, [word ids], [item ids])`` (``--shortlists``); the words and the items may be missing (an empty bag, an
+    empty shortlist: nothing to rank)."""
+    fields = line.rstrip('\n').split('\t')
+    if len(fields) > 3:
+        raise ValueError(f'a shortlist line is user<TAB>words<TAB>items, got {len(fields)} fields')
+    fields += [''] * (3 - len(fields))
+    return int(fields[0]), [int(w) for w in fields[1].split()], [int(i) for i in fields[2].split()]
 
 
 def format_answer(items, scores) -> str:
@@ -75,6 +87,8 @@ def main(argv: Optional[Sequence[str]] = None, lines=None, out=None) -> int:
     parser.add_argument('--candidates', dest='candidates', type=str, default='', help='a file of item ids, one per line: only these items are ranked')
     parser.add_argument('--exclude_seen', dest='exclude_seen', action='store_true', default=False,
                         help='leave out, for every search of a logged-in user, the items that user interacted with in training')
+    parser.add_argument('--shortlists', dest='shortlists', action='store_true', default=False,
+                        help='every input line carries a third field, the item ids to rank for that search (user<TAB>words<TAB>i1 i2 ...): re-rank a shortlist')
     ns = parser.parse_args(argv)
     args = ConsoleArgs(ns)
     if args.device == 'cpu':
@@ -93,10 +107,13 @@ def main(argv: Optional[Sequence[str]] = None, lines=None, out=None) -> int:
         batch = []
 
         def answer():
-            users = torch.tensor([u for u, _ in batch], dtype=torch.int64)
-            offsets = np.cumsum([0] + [len(w) for _, w in batch[:-1]]).astype(np.int64)
-            words = np.asarray([w for _, bag in batch for w in bag], np.int64)
-            items, scores = model.search(users, words=words, offsets=offsets, k=ns.k, candidates=candidates, exclude_seen=ns.exclude_seen)
+            users = torch.tensor([b[0] for b in batch], dtype=torch.int64)
+            offsets = np.cumsum([0] + [len(b[1]) for b in batch[:-1]]).astype(np.int64)
+            words = np.asarray([w for b in batch for w in b[1]], np.int64)
+            shortlists = None
+            if ns.shortlists:
+                shortlists = (np.cumsum([0] + [len(b[2]) for b in batch]).astype(np.int64), np.asarray([i for b in batch for i in b[2]], np.int64))
+            items, scores = model.search(users, words=words, offsets=offsets, k=ns.k, candidates=candidates, exclude_seen=ns.exclude_seen, candidate_lists=shortlists)
             for row_i, row_s in zip(items.cpu().tolist(), scores.cpu().tolist()):
                 out.write(format_answer(row_i, row_s) + '\n')
             batch.clear()
@@ -104,7 +121,7 @@ def main(argv: Optional[Sequence[str]] = None, lines=None, out=None) -> int:
         for line in lines:
             if not line.strip():
                 continue
-            batch.append(parse_search_line(line))
+            batch.append(parse_shortlist_line(line) if ns.shortlists else parse_search_line(line))
             if len(batch) == BATCH:
                 answer()
         if batch:

@@ -163,6 +163,12 @@ SIGNATURES = {
     'ihg_search_topk_excluding': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                                  c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                                  c_void_p]),
+    # re-ranking a shortlist per search (csrc/candidates.hip): ihg_search_topk_excluding's sources, then (cand_ptr, cand_items, cand_row, n_cand_rows, total), and all_scores
+    'ihg_search_candidates_max_dim': (c_int32, []),
+    'ihg_search_candidates_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    'ihg_search_candidates': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_int64, c_int32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     'ihg_zero_floats': (ctypes.c_int, [c_void_p, c_int64, c_void_p]),
     'ihg_mark_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_batch_node_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -10,7 +10,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(CSRC, 'libihgnn_hip.so')
-SOURCES = [os.path.join(CSRC, name) for name in ('host.hip', 'aggregate.hip', 'interact.hip', 'split_arith.hip', 'split_node.hip', 'narrow.hip', 'dense.hip', 'tail.hip', 'eval.hip', 'gat.hip', 'phase2.hip', 'srrl.hip', 'recurrent.hip')]
+SOURCES = [os.path.join(CSRC, name) for name in ('host.hip', 'aggregate.hip', 'interact.hip', 'split_arith.hip', 'split_node.hip', 'narrow.hip', 'dense.hip', 'tail.hip', 'eval.hip', 'candidates.hip', 'gat.hip', 'phase2.hip', 'srrl.hip', 'recurrent.hip')]
 HEADERS = [os.path.join(REPO, 'include', 'ihgnn_hip.h'), os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'interact_args.hpp'), os.path.join(CSRC, 'split.hpp'), os.path.join(CSRC, 'split_common.hpp'), os.path.join(CSRC, 'ablate.hpp'), os.path.join(CSRC, 'narrow.hpp'), os.path.join(CSRC, 'attention.hpp'), os.path.join(CSRC, 'worklist.hpp')]
 ARCH = 'gfx950'
 

@@ -2014,26 +2014,39 @@ def pack_item_mask(candidates: Tensor, n_items: int) -> Tensor:
     return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
 
 
+def _sorted_unique_lists(what: str, which: str, offsets: Tensor, items: Tensor, n_items: int) -> Tuple[Tensor, Tensor]:
+    """The one-sort construction behind ``exclusion_lists`` and ``candidate_lists``: one sort of the keys ``row * n_items + id`` orders every run and brings repeats
+    together; the new offsets are a search for each row's first key.  ``what`` / ``which`` only word the messages."""
+    n_items = int(n_items)
+    offsets = offsets.reshape(-1).to(torch.int64)
+    ids = items.reshape(-1).to(device=offsets.device, dtype=torch.int64)
+    if offsets.numel() < 1:
+        raise ValueError(f'{what}: offsets holds at least the leading 0')
+    n_rows = int(offsets.shape[0]) - 1
+    if not offsets.is_cuda:
+        if int(offsets[0]) != 0 or int(offsets[-1]) != ids.numel() or bool((offsets[1:] < offsets[:-1]).any()):
+            raise ValueError(f'{what}: offsets run from 0 to the {ids.numel()} ids without decreasing')
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_items):
+            raise ValueError(f'{which} item id outside [0, {n_items})')
+    rows = torch.repeat_interleave(torch.arange(n_rows, dtype=torch.int64, device=offsets.device), offsets[1:] - offsets[:-1], output_size=int(ids.shape[0]))
+    keys = torch.unique(rows * n_items + ids)                               # (sorted)
+    ptr = torch.searchsorted(keys, torch.arange(n_rows + 1, dtype=torch.int64, device=offsets.device) * n_items)
+    return ptr, (keys % n_items).to(torch.int32)
+
+
 def exclusion_lists(offsets: Tensor, items: Tensor, n_items: int) -> Tuple[Tensor, Tensor]:
     """Per-row item lists as ``ihg_search_topk_excluding`` reads them: ``(ptr int64 [R + 1], items int32)`` with every run strictly ascending.  Input: ``offsets``
     ``[R + 1]`` (non-decreasing, from 0 to ``len(items)``) and the flat ids of the rows, in any order, repeats allowed, in ``[0, n_items)``.  One sort of the keys
     ``row * n_items + id`` orders every run and brings repeats together; the new offsets are a search for each row's first key.  Torch ops on the tensors' own
     device, so it serves host tensors as well; the range of host tensors is checked here, that of device tensors is the caller's."""
-    n_items = int(n_items)
-    offsets = offsets.reshape(-1).to(torch.int64)
-    ids = items.reshape(-1).to(device=offsets.device, dtype=torch.int64)
-    if offsets.numel() < 1:
-        raise ValueError('exclusion_lists: offsets holds at least the leading 0')
-    n_rows = int(offsets.shape[0]) - 1
-    if not offsets.is_cuda:
-        if int(offsets[0]) != 0 or int(offsets[-1]) != ids.numel() or bool((offsets[1:] < offsets[:-1]).any()):
-            raise ValueError(f'exclusion_lists: offsets run from 0 to the {ids.numel()} ids without decreasing')
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_items):
-            raise ValueError(f'excluded item id outside [0, {n_items})')
-    rows = torch.repeat_interleave(torch.arange(n_rows, dtype=torch.int64, device=offsets.device), offsets[1:] - offsets[:-1], output_size=int(ids.shape[0]))
-    keys = torch.unique(rows * n_items + ids)                               # (sorted)
-    ptr = torch.searchsorted(keys, torch.arange(n_rows + 1, dtype=torch.int64, device=offsets.device) * n_items)
-    return ptr, (keys % n_items).to(torch.int32)
+    return _sorted_unique_lists('exclusion_lists', 'excluded', offsets, items, n_items)
+
+
+def candidate_lists(offsets: Tensor, items: Tensor, n_items: int) -> Tuple[Tensor, Tensor]:
+    """Per-search shortlists as ``ihg_search_candidates`` reads them: ``(ptr int64 [R + 1], items int32)`` with every run strictly ascending and free of repeats, from
+    raw lists (``offsets`` ``[R + 1]`` and the flat ids, in any order, repeats allowed, in ``[0, n_items)``).  The construction is ``exclusion_lists``'s; host tensors
+    are range-checked here, device tensors are the caller's to check."""
+    return _sorted_unique_lists('candidate_lists', 'candidate', offsets, items, n_items)
 
 
 def search_topk(features: Tensor, users: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int, *, queries: Optional[Tensor] = None,
@@ -2100,6 +2113,105 @@ def search_topk(features: Tensor, users: Tensor, query_row0: int, item_row0: int
                                                  _ptr(query_rows), ld_q, q_dim, _ptr(mask), _ptr(ptr), _ptr(ids), _ptr(exclude_rows), n_rows, float(lam), n_pairs, int(k),
                                                  _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)), _ptr(passes), _stream()),
                    'ihg_search_topk_excluding')
+    return top_items, top_scores, passes
+
+
+def search_candidates_max_width() -> int:
+    """The widest feature row ``ihg_search_candidates`` scores (2048): the LDS image of its mixed row, not the pair block of ``ihg_score_topk``."""
+    return int(_lib.load().ihg_search_candidates_max_dim())
+
+
+def search_candidates(features: Tensor, users: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int, *, lists: Tuple[Tensor, Tensor],
+                      list_rows: Optional[Tensor] = None, queries: Optional[Tensor] = None, query_rows: Optional[Tensor] = None, candidates: Optional[Tensor] = None,
+                      exclude: Optional[Tuple[Tensor, Tensor]] = None, exclude_rows: Optional[Tensor] = None, cosine: bool = False, return_scores: bool = False):
+    """Re-rank a shortlist per search (``ihg_search_candidates``): ``(top_items [C, k] int32, top_scores [C, k], passes [C] int32)``, and with ``return_scores`` the
+    float32 ``[total]`` score of every list entry at its slot in the sorted lists (``-inf`` where ``candidates`` or ``exclude`` removes the entry).  Only the listed
+    items are scored: the cost is the lists' total length times the width, with no pass over the catalogue.
+    ``lists`` = ``(ptr [R + 1], items)``: int32 ``items`` are taken as ``candidate_lists`` returned them (every run strictly ascending); items of any other integer type
+    are raw (any order, repeats) and go through it first.  ``list_rows`` (int64 ``[C]``): search ``c`` ranks run ``list_rows[c]``, nothing where that is negative;
+    without it search ``c`` ranks run ``c`` and ``R = C``.  ``users`` / ``queries`` / ``query_rows`` / ``candidates`` / ``exclude`` / ``exclude_rows`` / ``cosine`` are
+    ``search_topk``'s: a search ranks what is in its list, in ``candidates`` and not in its exclusion run, and is complete at ``min(k, that many)``.
+    The scores are plain float32 sums (a per-lane chain, then a tree) and NOT the bits of ``search_topk``, whose operands are two fp16 terms each; both are within their
+    bounds of the float64 score (``tests/candidates_reference.py``).  With ``return_scores`` and ``list_rows`` a run's slots hold the scores of the lowest-numbered search
+    that names it, so searches that share a run must be the same search: a host ``list_rows`` that names a run twice is refused, a device one is the caller's."""
+    if exclude is None and exclude_rows is not None:
+        raise ValueError('search_candidates: exclude_rows without exclude')
+    if not isinstance(lists, (tuple, list)) or len(lists) != 2:
+        raise ValueError('search_candidates: lists is (offsets, items)')
+    lib = _lib.load()
+    width = search_candidates_max_width()
+    if not (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1 and 0 < features.shape[1] <= width
+            and (features.shape[0] <= 1 or features.stride(0) >= features.shape[1])):
+        raise _lib.IhgnnHipError(f'ihg_search_candidates needs a float32 GPU feature matrix of width <= {width}, got {tuple(features.shape)} {features.dtype} on {features.device}')
+    if (queries is None) == (query_rows is None):
+        raise ValueError('search_candidates: give exactly one of queries and query_rows')
+    n_pairs = int(users.shape[0])
+    n_items = int(features.shape[0]) - int(item_row0)
+    dim = int(features.shape[1])
+    users = users.to(device=features.device, dtype=torch.int64).contiguous()
+    ld_q = q_dim = 0
+    if queries is not None:
+        queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
+        source = int(queries.shape[0])
+    else:
+        query_rows = _rows(query_rows, 'query_rows')
+        source, q_dim, ld_q = int(query_rows.shape[0]), int(query_rows.shape[1]), _ld(query_rows)
+    if source != n_pairs:
+        raise ValueError(f'search_candidates: {n_pairs} users but {source} queries')
+    cand_ptr, cand_ids = lists
+    if cand_ids.dtype != torch.int32:
+        cand_ptr, cand_ids = candidate_lists(cand_ptr, cand_ids, n_items)
+    cand_ptr = cand_ptr.reshape(-1).to(device=features.device, dtype=torch.int64).contiguous()
+    cand_ids = cand_ids.reshape(-1).to(device=features.device).contiguous()
+    total = int(cand_ids.shape[0])
+    n_runs = int(cand_ptr.shape[0]) - 1
+    if n_runs < 1 and n_pairs > 0:
+        raise ValueError('search_candidates: the offsets hold at least one run')
+    if list_rows is not None:
+        if list_rows.dim() != 1 or int(list_rows.shape[0]) != n_pairs:
+            raise ValueError(f'search_candidates: {n_pairs} searches but list_rows of {tuple(list_rows.shape)}')
+        if return_scores and not list_rows.is_cuda:
+            named = list_rows[list_rows >= 0]
+            if named.numel() != torch.unique(named).numel():
+                raise ValueError('search_candidates: return_scores with a list that two searches share (a slot holds one score)')
+        list_rows = list_rows.to(device=features.device, dtype=torch.int64).contiguous()
+    elif n_runs != n_pairs:
+        raise ValueError(f'search_candidates: {n_pairs} searches but {n_runs} candidate lists (list_rows= maps searches to shared lists)')
+    mask = None if candidates is None else pack_item_mask(candidates.to(features.device), n_items)
+    excl_ptr = excl_ids = None
+    n_excl = 0
+    if exclude is not None:
+        excl_ptr, excl_ids = exclude
+        if excl_ids.dtype != torch.int32:
+            excl_ptr, excl_ids = exclusion_lists(excl_ptr, excl_ids, n_items)
+        excl_ptr = excl_ptr.to(device=features.device, dtype=torch.int64).contiguous()
+        excl_ids = excl_ids.to(device=features.device).contiguous()
+        if excl_ids.numel() == 0:
+            excl_ids = excl_ids.new_zeros(1)
+        n_excl = int(excl_ptr.shape[0]) - 1
+        if exclude_rows is not None:
+            exclude_rows = exclude_rows.to(device=features.device, dtype=torch.int64).contiguous()
+            if exclude_rows.dim() != 1 or int(exclude_rows.shape[0]) != n_pairs:
+                raise ValueError(f'search_candidates: {n_pairs} searches but exclude_rows of {tuple(exclude_rows.shape)}')
+        elif n_excl != n_pairs:
+            raise ValueError(f'search_candidates: {n_pairs} searches but {n_excl} exclusion lists (exclude_rows= maps searches to shared lists)')
+    bias = item_bias.detach().to(torch.float32).contiguous()
+    depth = max(int(k), 0)
+    top_scores = torch.empty(n_pairs, depth, dtype=torch.float32, device=features.device)
+    top_items = torch.empty(n_pairs, depth, dtype=torch.int32, device=features.device)
+    passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
+    all_scores = torch.empty(total, dtype=torch.float32, device=features.device) if return_scores else None
+    if total == 0:
+        cand_ids = cand_ids.new_zeros(1)                                    # (an empty tensor has no address: the one-entry dummy of search_topk)
+    ws = _workspace(int(lib.ihg_search_candidates_workspace_bytes(n_pairs, total, dim, int(k))), features.device)
+    with profiler.kernel('search_candidates_cosine' if cosine else 'search_candidates', n_pairs, dim):
+        _lib.check(lib.ihg_search_candidates(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries),
+                                             _ptr(query_rows), ld_q, q_dim, _ptr(mask), _ptr(excl_ptr), _ptr(excl_ids), _ptr(exclude_rows), n_excl, _ptr(cand_ptr),
+                                             _ptr(cand_ids), _ptr(list_rows), n_runs, total, float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items),
+                                             _ptr(all_scores) if total else None, _ptr(ws), ws.numel() * 4, int(bool(cosine)), _ptr(passes), _stream()),
+                   'ihg_search_candidates')
+    if return_scores:
+        return top_items, top_scores, passes, all_scores
     return top_items, top_scores, passes
 
 

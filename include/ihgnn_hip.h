@@ -752,6 +752,45 @@ int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, in
                               int32_t cosine, int32_t* passes, ihg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE: re-ranking a shortlist per search (csrc/candidates.hip).  ihg_search_candidates takes what ihg_search_topk_excluding takes - the query source, users < 0,
+ * the item mask, the exclusion lists, lambda, 1 <= k <= 128, `cosine`, `passes`, the outputs' tie order (higher score first, equal scores by ascending item id) and
+ * their (-FLT_MAX, -1) tail - plus a CANDIDATE list per search in CSR form, and scores only the listed items: the work is sum_c |run_c| * dim, with no pass over the
+ * n_items item rows, no prepare pass and no memory proportional to n_items.
+ *   cand_ptr     int64 [n_cand_rows + 1], non-decreasing, cand_ptr[0] = 0, cand_ptr[n_cand_rows] = total
+ *   cand_items   int32 [total]: run r is cand_items[cand_ptr[r] .. cand_ptr[r + 1]), STRICTLY ASCENDING, ids in [0, n_items)
+ *   cand_row     int64 [n_pairs] or NULL: search c ranks run cand_row[c]; a negative or out-of-range entry is an empty run.  NULL: search c ranks run c, and
+ *                n_cand_rows == n_pairs
+ * An item is ranked for search c iff it is in run c, in item_mask (NULL: every item) and not in c's exclusion run.  Search c is complete at
+ * target_c = min(k, the items so admitted); the rest of its row is the tail; passes[c] = ceil(target_c / 10), the trips of its selecting wave (0 with nothing admitted).
+ *   all_scores   float32 [total] or NULL: the score of every list entry at its CSR slot, -inf (exactly) for an entry that the mask or the exclusion run removes, or
+ *                whose id is outside [0, n_items); the top-k is the stable ranking of these very floats.  With cand_row a run's slots are written for the
+ *                LOWEST-NUMBERED search that names it (a run that none names holds -inf): searches that share a run and differ in user or query need
+ *                all_scores == NULL, which the caller sees to (the rows live on the device).
+ * ARITHMETIC: plain fp32, NOT the bits of ihg_search_topk (two fp16 terms per operand on the matrix cores).  m = fma(lam, q, (1 - lam) u) (q alone for
+ * users[c] < 0, zero past q_dim for an external row) is formed once per (search, chunk of 256 ids); G = min(16, the power of two at or above ceil(dim / 4)) lanes
+ * own a candidate, lane g takes the four-column segments g, g + G, ... of the item row in one fma chain, a shuffle tree over G adds the partial sums, and
+ * score = dot + bias[item]; cosine: dot / (max(sqrt(sum a^2), 1e-8) * max(sqrt(sum m^2), 1e-8)) + bias[item], both sums in that same order.  A score of -inf or NaN
+ * is never ranked.  The result depends on no workspace byte and no launch order: two calls return equal bits.
+ * Launches: the runs' plan (a wave per search; with cand_row it compares each entry with those below it), the scan of the scoring units, the scoring pass (a wave per
+ * chunk of 256 ids of a run: a long run is spread over many waves) and the selecting pass (a wave per search).  A search that is not the first to name its run scores
+ * it in its selecting wave instead (a slot holds one search's score), so the memory stays that of the lists.
+ * ihg_search_candidates_max_dim() = 2048 is the widest row the mixed row's LDS image takes (the 1264 of the pair block of ihg_score_topk does not bind here).
+ * CONTRACT: the order inside a run and the offsets live on the device and are the caller's to keep (ops.candidate_lists builds such lists); a run that is not
+ * strictly ascending gives a wrong ranking, offsets outside [0, total] an empty run, an id outside [0, n_items) an entry that is never ranked - none of them a fault.
+ * IHG_ERR_INVALID before anything is launched: ihg_search_topk_excluding's size, query-source and exclusion-list checks, then total < 0, n_cand_rows < 1 (or
+ * != n_pairs without cand_row), then (n_pairs == 0 returns IHG_OK) a null pointer, dim > ihg_search_candidates_max_dim(), a workspace that is not 16-byte aligned or
+ * smaller than ihg_search_candidates_workspace_bytes(n_pairs, total, dim, k) = 4 total (rounded up to 16) + 8 (n_pairs + 1) (rounded up to 16) + 16 n_pairs.
+ */
+int32_t ihg_search_candidates_max_dim(void);
+int64_t ihg_search_candidates_workspace_bytes(int64_t n_pairs, int64_t total, int32_t dim, int32_t k);
+int ihg_search_candidates(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
+                          const float* item_bias, const int64_t* users, const int64_t* queries, const float* query_rows, int64_t ld_q, int32_t q_dim,
+                          const uint32_t* item_mask, const int64_t* excl_ptr, const int32_t* excl_items, const int64_t* excl_row, int64_t n_excl_rows,
+                          const int64_t* cand_ptr, const int32_t* cand_items, const int64_t* cand_row, int64_t n_cand_rows, int64_t total,
+                          float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores, int32_t* top_items, float* all_scores,
+                          void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes, ihg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE: the attention of the GAT baseline over the pairwise graph (csrc/gat.hip).  Replaces GATLayer.forward after its transform
  * (Models/GnnLayers.py:98-115: the [nnz, 2, d] row gather, feature_aggregate, dgl.ops.edge_softmax and dgl.ops.u_mul_e_sum) and autograd's backward of it.
  * Graph: the symmetric CSR of the pairwise adjacency (ihg_build_pair_csr) - entry p of row v with column u = ids[p] is the edge u -> v, so row v lists
