@@ -316,23 +316,28 @@ class RawGnn(nn.Module):
         float32 sums, close to but not the bits of the whole-catalogue kernels'.  Composes with ``exclude``."""
         from .. import ops
         features = self._saved_output_feature if self._saved_output_feature is not None else self.propagate()
-        ds, head = self.dataset, self.prediction_layer
+        ds = self.dataset
         if k > ops.score_topk_max_k():
             raise ValueError(f'RawGnn.top_items ranks at most {ops.score_topk_max_k()} items per pair, got k = {k}')
         k = min(k, ds.item_count)
-        if candidate_lists is not None:
-            lists = None if exclude is None else ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
-            items, scores, _ = ops.search_candidates(features, user_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq,
-                                                     k, lists=(torch.as_tensor(candidate_lists[0]), torch.as_tensor(candidate_lists[1])), queries=query_indices,
-                                                     exclude=lists, cosine=Gs.Prediction.use_cosine_similarity)
-            return items, scores
-        if exclude is not None:
-            lists = ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
-            items, scores, _ = ops.search_topk(features, user_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
-                                               queries=query_indices, cosine=Gs.Prediction.use_cosine_similarity, exclude=lists)
-            return items, scores
-        return ops.score_topk(features, user_indices, query_indices, ds.query_start_index_in_graph, ds.item_start_index_in_graph,
-                              head.items_bias, head.lambda_muq, k, cosine=Gs.Prediction.use_cosine_similarity)
+        lists = None if exclude is None else ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
+        shortlists = None if candidate_lists is None else (torch.as_tensor(candidate_lists[0]), torch.as_tensor(candidate_lists[1]))
+        return self._ranked(features, user_indices, k, queries=query_indices, exclude=lists, shortlists=shortlists, as_search=False)[:2]
+
+    def _ranked(self, features, users, k, *, queries=None, query_rows=None, candidates=None, exclude=None, exclude_rows=None, shortlists=None, return_scores=False,
+                as_search=True):
+        """The one place that picks the ranking call of ``top_items`` and ``search``: the list kernels with ``shortlists``, else the search entry points
+        (``as_search``, or with exclusion lists), else ``ihg_score_topk`` - the evaluation path of ``top_items`` without lists.  Returns what the call returns."""
+        from .. import ops
+        ds, head = self.dataset, self.prediction_layer
+        rows0, cosine = (ds.query_start_index_in_graph, ds.item_start_index_in_graph), Gs.Prediction.use_cosine_similarity
+        if shortlists is not None:
+            return ops.search_candidates(features, users, *rows0, head.items_bias, head.lambda_muq, k, lists=shortlists, queries=queries, query_rows=query_rows,
+                                         candidates=candidates, exclude=exclude, exclude_rows=exclude_rows, cosine=cosine, return_scores=return_scores)
+        if as_search or exclude is not None:
+            return ops.search_topk(features, users, *rows0, head.items_bias, head.lambda_muq, k, queries=queries, query_rows=query_rows, candidates=candidates, cosine=cosine,
+                                   exclude=exclude, exclude_rows=exclude_rows)
+        return ops.score_topk(features, users, queries, *rows0, head.items_bias, head.lambda_muq, k, cosine=cosine)
 
     def _check_search_inputs(self, users, queries, words, offsets, candidates, exclude=None, exclude_seen=False, candidate_lists=None):
         """The host-side checks of ``search``, before anything is launched (a tensor that already lives on the device is taken as checked: reading it back would
@@ -369,26 +374,22 @@ class RawGnn(nn.Module):
             raise ValueError(f'RawGnn.search: a candidate mask is a bool tensor of [{ds.item_count}]')
         if exclude is not None and exclude_seen:
             raise ValueError('RawGnn.search: give exclude= or exclude_seen=True, not both')
+        def check_lists(keyword, lists, which):
+            """``keyword=(offsets [C + 1], items)``; ``which`` words the id message"""
+            if not isinstance(lists, (tuple, list)) or len(lists) != 2:
+                raise ValueError(f'RawGnn.search: {keyword}= is (offsets [C + 1], items)')
+            o, i = on_host(lists[0]), on_host(lists[1])
+            if o is not None and (o.ndim != 1 or o.size != n_pairs + 1):
+                raise ValueError(f'RawGnn.search: {keyword}= needs {n_pairs + 1} offsets for {n_pairs} searches')
+            if o is not None and i is not None and (o[0] != 0 or np.any(np.diff(o) < 0) or o[-1] != i.size):
+                raise ValueError(f'RawGnn.search: the offsets of {keyword}= start at 0, do not decrease and end at the number of items')
+            if i is not None and i.size and (i.min() < 0 or i.max() >= ds.item_count):
+                raise ValueError(f'RawGnn.search: {which} item id outside [0, {ds.item_count})')
+
         if exclude is not None:
-            if not isinstance(exclude, (tuple, list)) or len(exclude) != 2:
-                raise ValueError('RawGnn.search: exclude= is (offsets [C + 1], items)')
-            eo, ei = on_host(exclude[0]), on_host(exclude[1])
-            if eo is not None and (eo.ndim != 1 or eo.size != n_pairs + 1):
-                raise ValueError(f'RawGnn.search: exclude= needs {n_pairs + 1} offsets for {n_pairs} searches')
-            if eo is not None and ei is not None and (eo[0] != 0 or np.any(np.diff(eo) < 0) or eo[-1] != ei.size):
-                raise ValueError('RawGnn.search: the offsets of exclude= start at 0, do not decrease and end at the number of items')
-            if ei is not None and ei.size and (ei.min() < 0 or ei.max() >= ds.item_count):
-                raise ValueError(f'RawGnn.search: excluded item id outside [0, {ds.item_count})')
+            check_lists('exclude', exclude, 'excluded')
         if candidate_lists is not None:
-            if not isinstance(candidate_lists, (tuple, list)) or len(candidate_lists) != 2:
-                raise ValueError('RawGnn.search: candidate_lists= is (offsets [C + 1], items)')
-            co, ci = on_host(candidate_lists[0]), on_host(candidate_lists[1])
-            if co is not None and (co.ndim != 1 or co.size != n_pairs + 1):
-                raise ValueError(f'RawGnn.search: candidate_lists= needs {n_pairs + 1} offsets for {n_pairs} searches')
-            if co is not None and ci is not None and (co[0] != 0 or np.any(np.diff(co) < 0) or co[-1] != ci.size):
-                raise ValueError('RawGnn.search: the offsets of candidate_lists= start at 0, do not decrease and end at the number of items')
-            if ci is not None and ci.size and (ci.min() < 0 or ci.max() >= ds.item_count):
-                raise ValueError(f'RawGnn.search: listed candidate item id outside [0, {ds.item_count})')
+            check_lists('candidate_lists', candidate_lists, 'listed candidate')
         if words is None:
             return None, None
         w = np.asarray(words.detach().cpu() if isinstance(words, Tensor) else words, dtype=np.int64).reshape(-1)
@@ -425,7 +426,7 @@ class RawGnn(nn.Module):
         w, o = self._check_search_inputs(users, queries, words, offsets, candidates, exclude, exclude_seen, candidate_lists)
         if return_list_scores and candidate_lists is None:
             raise ValueError('RawGnn.search: return_list_scores needs candidate_lists=')
-        ds, head = self.dataset, self.prediction_layer
+        ds = self.dataset
         if k < 1 or k > ops.score_topk_max_k():
             raise ValueError(f'RawGnn.search ranks 1 to {ops.score_topk_max_k()} items per pair, got k = {k}')
         k = min(k, ds.item_count)
@@ -443,20 +444,16 @@ class RawGnn(nn.Module):
             lists, rows = ds.user_item_lists_on(features.device), users         # (a user IS the row of the shared lists; -1 names none)
         elif exclude is not None:
             lists = ops.exclusion_lists(torch.as_tensor(exclude[0]), torch.as_tensor(exclude[1]), ds.item_count)
+        shortlists = None
         if candidate_lists is not None:
             shortlists = (torch.as_tensor(candidate_lists[0]), torch.as_tensor(candidate_lists[1]))
             if shortlists[1].dtype != torch.int32:
                 shortlists = ops.candidate_lists(shortlists[0], shortlists[1], ds.item_count)
-            out = ops.search_candidates(features, users, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
-                                        lists=shortlists, queries=queries, query_rows=query_rows, candidates=candidates, exclude=lists, exclude_rows=rows,
-                                        cosine=Gs.Prediction.use_cosine_similarity, return_scores=return_list_scores)
-            if return_list_scores:
-                return out[0], out[1], (shortlists[0], shortlists[1], out[3])
-            return out[0], out[1]
-        items, scores, _ = ops.search_topk(features, users, ds.query_start_index_in_graph, ds.item_start_index_in_graph, head.items_bias, head.lambda_muq, k,
-                                           queries=queries, query_rows=query_rows, candidates=candidates, cosine=Gs.Prediction.use_cosine_similarity,
-                                           exclude=lists, exclude_rows=rows)
-        return items, scores
+        out = self._ranked(features, users, k, queries=queries, query_rows=query_rows, candidates=candidates, exclude=lists, exclude_rows=rows, shortlists=shortlists,
+                           return_scores=return_list_scores)
+        if return_list_scores:
+            return out[0], out[1], (shortlists[0], shortlists[1], out[3])
+        return out[0], out[1]
 
     @torch.no_grad()
     def score_candidates(self, users, *, candidate_lists, queries=None, words=None, offsets=None):

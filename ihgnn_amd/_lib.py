@@ -30,6 +30,15 @@ SRC_SCALE_IN_ENTRIES = 0x800  # OR-ed into the mode of ihg_node_segment_sum: ent
 
 _i64p, _i32p, _f32p = POINTER(c_int64), POINTER(c_int32), POINTER(c_float)
 
+# The ranking entry points' argument groups (include/ihgnn_hip.h), from which their six signatures below are composed:
+_SCORE_HEAD = [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]      # features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries
+_SEARCH_SOURCES = [c_void_p, c_int64, c_int32, c_void_p]                                               # query_rows, ld_q, q_dim, item_mask
+_EXCLUSION = [c_void_p, c_void_p, c_void_p, c_int64]                                                   # excl_ptr, excl_items, excl_row, n_excl_rows
+_CANDIDATES = [c_void_p, c_void_p, c_void_p, c_int64, c_int64]                                         # cand_ptr, cand_items, cand_row, n_cand_rows, total
+_RANKED = [c_float, c_int64, c_int32, c_void_p, c_void_p]                                              # lambda_muq, n_pairs, k, top_scores, top_items
+_WORKSPACE = [c_void_p, c_int64]
+_DEEP_TAIL = [c_int32, c_void_p, c_void_p]                                                             # cosine, passes, stream
+
 # name -> (restype, argtypes); mirrors include/ihgnn_hip.h line by line.  Device pointers travel as
 # c_void_p (tensor.data_ptr()); host-side builders take real typed pointers.
 SIGNATURES = {
@@ -127,8 +136,7 @@ SIGNATURES = {
                                         c_void_p, c_void_p]),
     'ihg_score_topk_max_dim': (c_int32, []),
     'ihg_score_topk_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32]),
-    'ihg_score_topk': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
-                                      c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'ihg_score_topk': (ctypes.c_int, _SCORE_HEAD + _RANKED + _WORKSPACE + [c_void_p]),
     'ihg_batch_rows_add': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                           c_void_p]),
     # typed rows: the first row of every node type at its own address (host arrays of three device pointers)
@@ -147,28 +155,21 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_int64, c_void_p]),
     'ihg_hem_cosine_bwd': (ctypes.c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64, _i64p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                           c_void_p, c_int64, c_int64, c_void_p]),
-    'ihg_score_topk_cosine': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
-                                             c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'ihg_score_topk_cosine': (ctypes.c_int, _SCORE_HEAD + _RANKED + _WORKSPACE + [c_void_p]),
     # ranking deeper than ten (csrc/eval.hip): ihg_score_topk's arguments, then the head, then the optional per-pair pass counts
     'ihg_score_topk_max_k': (c_int32, []),
     'ihg_score_topk_deep_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    'ihg_score_topk_deep': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int64,
-                                           c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    'ihg_score_topk_deep': (ctypes.c_int, _SCORE_HEAD + _RANKED + _WORKSPACE + _DEEP_TAIL),
     # answering a search (csrc/eval.hip): ihg_score_topk_deep with (queries | query_rows, ld_q, q_dim), the candidate mask words and users < 0 = no user
     'ihg_search_topk_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    'ihg_search_topk': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_float,
-                                       c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    'ihg_search_topk': (ctypes.c_int, _SCORE_HEAD + _SEARCH_SOURCES + _RANKED + _WORKSPACE + _DEEP_TAIL),
     # ... that leaves out a list of items per pair: ihg_search_topk with (excl_ptr, excl_items, excl_row, n_excl_rows) after the mask
     'ihg_search_topk_excluding_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    'ihg_search_topk_excluding': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
-                                                 c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
-                                                 c_void_p]),
+    'ihg_search_topk_excluding': (ctypes.c_int, _SCORE_HEAD + _SEARCH_SOURCES + _EXCLUSION + _RANKED + _WORKSPACE + _DEEP_TAIL),
     # re-ranking a shortlist per search (csrc/candidates.hip): ihg_search_topk_excluding's sources, then (cand_ptr, cand_items, cand_row, n_cand_rows, total), and all_scores
     'ihg_search_candidates_max_dim': (c_int32, []),
     'ihg_search_candidates_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    'ihg_search_candidates': (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_int64, c_int32, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    'ihg_search_candidates': (ctypes.c_int, _SCORE_HEAD + _SEARCH_SOURCES + _EXCLUSION + _CANDIDATES + _RANKED + [c_void_p] + _WORKSPACE + _DEEP_TAIL),
     'ihg_zero_floats': (ctypes.c_int, [c_void_p, c_int64, c_void_p]),
     'ihg_mark_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     'ihg_batch_node_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -11,7 +11,7 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(CSRC, 'libihgnn_hip.so')
 SOURCES = [os.path.join(CSRC, name) for name in ('host.hip', 'aggregate.hip', 'interact.hip', 'split_arith.hip', 'split_node.hip', 'narrow.hip', 'dense.hip', 'tail.hip', 'eval.hip', 'candidates.hip', 'gat.hip', 'phase2.hip', 'srrl.hip', 'recurrent.hip')]
-HEADERS = [os.path.join(REPO, 'include', 'ihgnn_hip.h'), os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'interact_args.hpp'), os.path.join(CSRC, 'split.hpp'), os.path.join(CSRC, 'split_common.hpp'), os.path.join(CSRC, 'ablate.hpp'), os.path.join(CSRC, 'narrow.hpp'), os.path.join(CSRC, 'attention.hpp'), os.path.join(CSRC, 'worklist.hpp')]
+HEADERS = [os.path.join(REPO, 'include', 'ihgnn_hip.h'), os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'interact_args.hpp'), os.path.join(CSRC, 'split.hpp'), os.path.join(CSRC, 'split_common.hpp'), os.path.join(CSRC, 'ablate.hpp'), os.path.join(CSRC, 'narrow.hpp'), os.path.join(CSRC, 'attention.hpp'), os.path.join(CSRC, 'worklist.hpp'), os.path.join(CSRC, 'ranking.hpp')]
 ARCH = 'gfx950'
 
 

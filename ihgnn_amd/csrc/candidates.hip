@@ -15,59 +15,16 @@
 //   cand_select_kernel  a wave per search: every lane keeps a TopList of ten over its strided share of the run (entries that rank strictly after the search's
 //                       boundary), the wave emits the best ten of the 64 lists and moves the boundary: ceil(target / 10) trips.  A search that is not the owner of
 //                       its run has no stored scores (a slot holds one search's): its wave scores the run itself, chunk by chunk into LDS, with the same function.
-#include "common.hpp"
-
-#include <cfloat>
-#include <climits>
+// Host side: the call record, the argument checks and the list type are eval.hip's (ranking.hpp); cand_workspace lays the workspace out, cand_args fills the kernels' block.
+#include "ranking.hpp"
 
 namespace {
 
-constexpr int kCandTop = 10;                // list length kept per lane, ranks emitted per trip
 constexpr int kCandMaxK = 128;
 constexpr int kCandChunk = 256;             // ids per scoring unit
 constexpr int kCandMaxDim = 2048;           // the widest mixed row the LDS image takes
 constexpr int kCandRows = 4;                // item rows in flight per lane group
-constexpr float kCandCosineEps = 1e-8f;
 constexpr int kCandMaxGrid = 256 * 16;      // one-wave workgroups: 16 per CU, grid-stride beyond that
-
-__device__ __forceinline__ bool cand_ranks_before(float s, int i, float v, int j) { return s > v || (s == v && i < j); }
-
-struct CandTopList {
-    float val[kCandTop];
-    int idx[kCandTop];
-    __device__ void init() {
-#pragma unroll
-        for (int p = 0; p < kCandTop; ++p) {
-            val[p] = -FLT_MAX;
-            idx[p] = INT_MAX;
-        }
-    }
-    // sorted insert (best first); the caller has checked that (s, i) ranks before the last slot
-    __device__ void insert(float s, int i) {
-        val[kCandTop - 1] = s;
-        idx[kCandTop - 1] = i;
-#pragma unroll
-        for (int p = kCandTop - 1; p > 0; --p) {
-            const bool up = cand_ranks_before(val[p], idx[p], val[p - 1], idx[p - 1]);
-            const float v0 = val[p - 1], v1 = val[p];
-            const int i0 = idx[p - 1], i1 = idx[p];
-            val[p - 1] = up ? v1 : v0;
-            val[p] = up ? v0 : v1;
-            idx[p - 1] = up ? i1 : i0;
-            idx[p] = up ? i0 : i1;
-        }
-    }
-    // drop the head (statically indexed: no scratch)
-    __device__ void pop() {
-#pragma unroll
-        for (int p = 0; p + 1 < kCandTop; ++p) {
-            val[p] = val[p + 1];
-            idx[p] = idx[p + 1];
-        }
-        val[kCandTop - 1] = -FLT_MAX;
-        idx[kCandTop - 1] = INT_MAX;
-    }
-};
 
 // the run of a search as the kernels read it
 struct CandRun {
@@ -143,7 +100,7 @@ __device__ float cand_mixed_row(const CandArgs& a, int64_t c, float* __restrict_
         ss = fmaf(m.w, m.w, ss);
     }
     for (int off = a.group >> 1; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
-    return fmaxf(sqrtf(ss), kCandCosineEps);
+    return fmaxf(sqrtf(ss), kCosineEps);
 }
 
 __device__ __forceinline__ float4 cand_segment(const float* __restrict__ row, int s, int dim, bool vec) {
@@ -232,7 +189,7 @@ __device__ void cand_score_chunk(const CandArgs& a, const float* __restrict__ mr
                 if (e < n) {
                     float s = -__builtin_inff();
                     if (live[r]) {
-                        if constexpr (COSINE) s = dot[r] / (fmaxf(sqrtf(ss[r]), kCandCosineEps) * norm_m) + a.bias[item[r]];
+                        if constexpr (COSINE) s = dot[r] / (fmaxf(sqrtf(ss[r]), kCosineEps) * norm_m) + a.bias[item[r]];
                         else s = dot[r] + a.bias[item[r]];
                     }
                     out[e] = s;
@@ -335,7 +292,7 @@ __global__ __launch_bounds__(kWave) void cand_select_kernel(const CandArgs a, co
         float b_val = __builtin_inff();                                     // the boundary: the last rank emitted
         int b_idx = -1;
         while (run.len > 0) {
-            CandTopList top;
+            TopList top;
             top.init();
             int admitted = 0;
             for (int e0 = 0; e0 < run.len; e0 += kCandChunk) {
@@ -352,7 +309,7 @@ __global__ __launch_bounds__(kWave) void cand_select_kernel(const CandArgs a, co
                     if (s > -__builtin_inff()) {                              // (-inf: not admitted; a NaN score is never ranked either)
                         ++admitted;
                         const int i = ids[e0 + t];
-                        if (cand_ranks_before(b_val, b_idx, s, i) && cand_ranks_before(s, i, top.val[kCandTop - 1], top.idx[kCandTop - 1])) top.insert(s, i);
+                        if (ranks_before(b_val, b_idx, s, i) && ranks_before(s, i, top.val[kTopMax - 1], top.idx[kTopMax - 1])) top.insert(s, i);
                     }
                 }
             }
@@ -363,7 +320,7 @@ __global__ __launch_bounds__(kWave) void cand_select_kernel(const CandArgs a, co
             }
             if (target == 0) break;
             ++trips;
-            const int emit = target - count < kCandTop ? target - count : kCandTop;
+            const int emit = target - count < kTopMax ? target - count : kTopMax;
             int got = 0;
             for (int j = 0; j < emit; ++j) {
                 float wv = top.val[0];
@@ -372,7 +329,7 @@ __global__ __launch_bounds__(kWave) void cand_select_kernel(const CandArgs a, co
                 for (int off = 32; off >= 1; off >>= 1) {
                     const float ov = __shfl_xor(wv, off);
                     const int oi = __shfl_xor(wi, off);
-                    if (cand_ranks_before(ov, oi, wv, wi)) {
+                    if (ranks_before(ov, oi, wv, wi)) {
                         wv = ov;
                         wi = oi;
                     }
@@ -402,11 +359,39 @@ __global__ __launch_bounds__(kBlockThreads) void cand_fill_kernel(float* __restr
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlockThreads + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlockThreads) p[i] = v;
 }
 
-inline int64_t align16(int64_t n) { return (n + 15) / 16 * 16; }
-inline int64_t cand_scores_bytes(int64_t total) { return align16(total * 4); }
-inline int64_t cand_units_bytes(int64_t n_pairs) { return align16((n_pairs + 1) * 8); }
-
 inline int cand_grid(int64_t waves) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(waves, kCandMaxGrid))); }
+
+// The workspace, region after region: the scores of the list entries, float32 [total] | unit_begin, int64 [n_pairs + 1] (each rounded up to 16 bytes) |
+// runs, CandRun [n_pairs].  A null base answers the size query (`bytes`), the caller's pointer carves the regions.
+struct CandWorkspace {
+    float* scores;
+    int64_t* unit_begin;
+    CandRun* runs;
+    int64_t bytes;
+};
+inline CandWorkspace cand_workspace(void* base, int64_t n_pairs, int64_t total) {
+    WorkspaceCursor ws(base);
+    CandWorkspace w{};
+    w.scores = static_cast<float*>(ws.take(align16(total * 4)));
+    w.unit_begin = static_cast<int64_t*>(ws.take(align16((n_pairs + 1) * 8)));
+    w.runs = static_cast<CandRun*>(ws.take(n_pairs * static_cast<int64_t>(sizeof(CandRun))));
+    w.bytes = ws.at;
+    return w;
+}
+
+constexpr RankRules kSearchCandidates{"ihg_search_candidates", kCandMaxK, "1 <= ", true, kCandMaxDim, "is beyond the mixed row's storage", IHG_ERR_INVALID};
+
+// the kernels' argument block, from the record
+inline CandArgs cand_args(const RankCall& c, const int32_t* cand_items) {
+    CandArgs a;
+    a.feat = c.features, a.ld = c.ld, a.dim = c.dim, a.query_row0 = c.query_row0, a.item_row0 = c.item_row0, a.n_items = c.n_items, a.bias = c.item_bias;
+    a.group = cand_group_width(c.dim);
+    a.vec = (aligned16(c.features) && c.ld % 4 == 0) ? 1 : 0;
+    a.users = c.users, a.queries = c.queries, a.query_rows = c.query_rows, a.ld_q = c.ld_q, a.q_dim = c.q_dim, a.item_mask = c.item_mask;
+    a.excl_ptr = c.excl_ptr, a.excl_items = c.excl_items, a.excl_row = c.excl_row, a.n_excl_rows = c.n_excl_rows;
+    a.cand_items = cand_items, a.lam = c.lambda_muq;
+    return a;
+}
 
 }  // namespace
 
@@ -414,9 +399,10 @@ extern "C" {
 
 int32_t ihg_search_candidates_max_dim(void) { return kCandMaxDim; }
 
+// regions: scores [total] | unit_begin [n_pairs + 1] | runs [n_pairs]
 int64_t ihg_search_candidates_workspace_bytes(int64_t n_pairs, int64_t total, int32_t dim, int32_t k) {
     if (n_pairs <= 0 || total < 0 || dim <= 0 || dim > kCandMaxDim || k <= 0 || k > kCandMaxK) return 0;
-    return cand_scores_bytes(total) + cand_units_bytes(n_pairs) + n_pairs * static_cast<int64_t>(sizeof(CandRun));
+    return cand_workspace(nullptr, n_pairs, total).bytes;
 }
 
 int ihg_search_candidates(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
@@ -425,65 +411,36 @@ int ihg_search_candidates(const float* features, int64_t ld, int32_t dim, int64_
                           const int32_t* cand_items, const int64_t* cand_row, int64_t n_cand_rows, int64_t total, float lambda_muq, int64_t n_pairs, int32_t k,
                           float* top_scores, int32_t* top_items, float* all_scores, void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes,
                           ihg_stream_t stream) {
-    const char* what = "ihg_search_candidates";
-    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kCandMaxK || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kCandMaxK);
-    if ((queries == nullptr) == (query_rows == nullptr)) return fail(IHG_ERR_INVALID, "%s: exactly one of queries and query_rows", what);
-    if (query_rows != nullptr && (q_dim < 1 || q_dim > dim || ld_q < q_dim)) return fail(IHG_ERR_INVALID, "%s: 1 <= q_dim <= dim and ld_q >= q_dim", what);
-    if ((excl_ptr == nullptr) != (excl_items == nullptr)) return fail(IHG_ERR_INVALID, "%s: excl_ptr and excl_items go together", what);
-    if (excl_ptr == nullptr && excl_row != nullptr) return fail(IHG_ERR_INVALID, "%s: excl_row without lists", what);
-    if (excl_ptr != nullptr && (n_excl_rows < 1 || (excl_row == nullptr && n_excl_rows != n_pairs && n_pairs > 0)))
-        return fail(IHG_ERR_INVALID, "%s: n_excl_rows >= 1, and == n_pairs without excl_row", what);
+    RankCall c;
+    c.features = features, c.ld = ld, c.dim = dim, c.query_row0 = query_row0, c.item_row0 = item_row0, c.n_items = n_items, c.item_bias = item_bias;
+    c.users = users, c.queries = queries, c.query_rows = query_rows, c.ld_q = ld_q, c.q_dim = q_dim, c.item_mask = item_mask;
+    c.excl_ptr = excl_ptr, c.excl_items = excl_items, c.excl_row = excl_row, c.n_excl_rows = n_excl_rows;
+    c.lambda_muq = lambda_muq, c.n_pairs = n_pairs, c.k = k, c.top_scores = top_scores, c.top_items = top_items;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.cosine = cosine, c.passes = passes, c.stream = stream;
+    if (int rc = rank_check_call(c, kSearchCandidates)) return rc;
     if (total < 0 || (n_pairs > 0 && (n_cand_rows < 1 || (cand_row == nullptr && n_cand_rows != n_pairs))))
-        return fail(IHG_ERR_INVALID, "%s: total >= 0, n_cand_rows >= 1, and == n_pairs without cand_row", what);
+        return fail(IHG_ERR_INVALID, "%s: total >= 0, n_cand_rows >= 1, and == n_pairs without cand_row", kSearchCandidates.what);
     if (n_pairs == 0) return IHG_OK;
-    if (features == nullptr || item_bias == nullptr || users == nullptr || top_scores == nullptr || top_items == nullptr || cand_ptr == nullptr ||
-        (cand_items == nullptr && total > 0))
-        return fail(IHG_ERR_INVALID, "%s: null pointer", what);
-    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
-    if (dim > kCandMaxDim) return fail(IHG_ERR_INVALID, "%s: feature width %d is beyond the mixed row's storage (widest: %d)", what, dim, kCandMaxDim);
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_search_candidates_workspace_bytes(n_pairs, total, dim, k))
-        return fail(IHG_ERR_INVALID, "%s: workspace too small", what);
+    if (int rc = rank_check_pointers(c, kSearchCandidates, cand_ptr != nullptr && (cand_items != nullptr || total == 0))) return rc;
+    if (int rc = rank_check_workspace(c, kSearchCandidates, cand_workspace(nullptr, n_pairs, total).bytes)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    float* scores = all_scores != nullptr ? all_scores : reinterpret_cast<float*>(ws);
-    int64_t* unit_begin = reinterpret_cast<int64_t*>(ws + cand_scores_bytes(total));
-    CandRun* runs = reinterpret_cast<CandRun*>(ws + cand_scores_bytes(total) + cand_units_bytes(n_pairs));
-    CandArgs a;
-    a.feat = features;
-    a.ld = ld;
-    a.dim = dim;
-    a.group = cand_group_width(dim);
-    a.vec = (aligned16(features) && ld % 4 == 0) ? 1 : 0;
-    a.query_row0 = query_row0;
-    a.item_row0 = item_row0;
-    a.n_items = n_items;
-    a.bias = item_bias;
-    a.users = users;
-    a.queries = queries;
-    a.query_rows = query_rows;
-    a.ld_q = ld_q;
-    a.q_dim = q_dim;
-    a.item_mask = item_mask;
-    a.excl_ptr = excl_ptr;
-    a.excl_items = excl_items;
-    a.excl_row = excl_row;
-    a.n_excl_rows = n_excl_rows;
-    a.cand_items = cand_items;
-    a.lam = lambda_muq;
+    const CandWorkspace ws = cand_workspace(workspace, n_pairs, total);
+    float* scores = all_scores != nullptr ? all_scores : ws.scores;
+    const CandArgs a = cand_args(c, cand_items);
     if (all_scores != nullptr && cand_row != nullptr && total > 0)           // a run that no search names keeps -inf: every slot is written
         hipLaunchKernelGGL(cand_fill_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((total + kBlockThreads - 1) / kBlockThreads, kMaxBlocks))), dim3(kBlockThreads), 0, s,
                            all_scores, total, -__builtin_inff());
-    hipLaunchKernelGGL(cand_plan_kernel, dim3(cand_grid(n_pairs)), dim3(kWave), 0, s, cand_ptr, cand_row, n_cand_rows, total, n_pairs, runs);
-    hipLaunchKernelGGL(cand_units_kernel, dim3(1), dim3(kBlockThreads), 0, s, runs, n_pairs, unit_begin);
+    hipLaunchKernelGGL(cand_plan_kernel, dim3(cand_grid(n_pairs)), dim3(kWave), 0, s, cand_ptr, cand_row, n_cand_rows, total, n_pairs, ws.runs);
+    hipLaunchKernelGGL(cand_units_kernel, dim3(1), dim3(kBlockThreads), 0, s, ws.runs, n_pairs, ws.unit_begin);
     const int score_grid = cand_grid(total / kCandChunk + n_pairs);          // (the units are at most this many; the kernel reads their number on the device)
     if (cosine != 0) {
-        hipLaunchKernelGGL(cand_score_kernel<true>, dim3(score_grid), dim3(kWave), 0, s, a, runs, unit_begin, n_pairs, scores);
-        hipLaunchKernelGGL(cand_select_kernel<true>, dim3(cand_grid(n_pairs)), dim3(kWave), 0, s, a, runs, n_pairs, scores, k, top_scores, top_items, passes);
+        hipLaunchKernelGGL(cand_score_kernel<true>, dim3(score_grid), dim3(kWave), 0, s, a, ws.runs, ws.unit_begin, n_pairs, scores);
+        hipLaunchKernelGGL(cand_select_kernel<true>, dim3(cand_grid(n_pairs)), dim3(kWave), 0, s, a, ws.runs, n_pairs, scores, k, top_scores, top_items, passes);
     } else {
-        hipLaunchKernelGGL(cand_score_kernel<false>, dim3(score_grid), dim3(kWave), 0, s, a, runs, unit_begin, n_pairs, scores);
-        hipLaunchKernelGGL(cand_select_kernel<false>, dim3(cand_grid(n_pairs)), dim3(kWave), 0, s, a, runs, n_pairs, scores, k, top_scores, top_items, passes);
+        hipLaunchKernelGGL(cand_score_kernel<false>, dim3(score_grid), dim3(kWave), 0, s, a, ws.runs, ws.unit_begin, n_pairs, scores);
+        hipLaunchKernelGGL(cand_select_kernel<false>, dim3(cand_grid(n_pairs)), dim3(kWave), 0, s, a, ws.runs, n_pairs, scores, k, top_scores, top_items, passes);
     }
-    return check_launch(what);
+    return check_launch(kSearchCandidates.what);
 }
 
 }  // extern "C"

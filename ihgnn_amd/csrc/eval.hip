@@ -10,43 +10,11 @@
 // no cross-lane traffic in the loop.  The partial lists (2 lane halves x 4 waves x item slices per pair) are merged by a second,
 // tiny kernel.  Order: higher score first, equal scores by lower item index (= a stable descending sort; the reference's
 // torch.sort is unstable on ties).
-#include "common.hpp"
-
-#include <cfloat>
-#include <climits>
+// Entry points: ihg_score_topk / _cosine (k <= 10), ihg_score_topk_deep (k <= 128, in passes), ihg_search_topk (external query rows, no user, a candidate mask) and
+// ihg_search_topk_excluding (a run of excluded items per pair) - one kernel family by template flags, one host path at the end of this file.
+#include "ranking.hpp"
 
 namespace {
-
-constexpr int kTopMax = 10;                 // list length kept per lane (Metrics.py:60: top 10)
-
-__device__ __forceinline__ bool ranks_before(float s, int i, float v, int j) { return s > v || (s == v && i < j); }
-
-struct TopList {
-    float val[kTopMax];
-    int idx[kTopMax];
-    __device__ void init() {
-#pragma unroll
-        for (int p = 0; p < kTopMax; ++p) {
-            val[p] = -FLT_MAX;
-            idx[p] = INT_MAX;
-        }
-    }
-    // sorted insert (best first); the caller has checked that (s, i) ranks before the last slot
-    __device__ void insert(float s, int i) {
-        val[kTopMax - 1] = s;
-        idx[kTopMax - 1] = i;
-#pragma unroll
-        for (int p = kTopMax - 1; p > 0; --p) {
-            const bool up = ranks_before(val[p], idx[p], val[p - 1], idx[p - 1]);
-            const float v0 = val[p - 1], v1 = val[p];
-            const int i0 = idx[p - 1], i1 = idx[p];
-            val[p - 1] = up ? v1 : v0;
-            val[p] = up ? v0 : v1;
-            idx[p - 1] = up ? i1 : i0;
-            idx[p] = up ? i0 : i1;
-        }
-    }
-};
 
 // ------------------------------------------------------------------------------------------------
 // Arithmetic: fp32 through TWO fp16 terms (split_arith.hip has the scheme and its error analysis): every item row and every mixed row is multiplied by the power of
@@ -82,8 +50,7 @@ __device__ __forceinline__ void eval_split8(const float (&x)[8], v4u& hi, v4u& l
 // v_mfma_f32_32x32x16_f16), aux[item] = {inverse scale, bias}.  One wave per item row; columns past `dim` are zero.
 // COSINE (Gs.Prediction.use_cosine_similarity, PredictionLayers.py:38-40): the row's sum of squares is reduced beside its largest magnitude and
 // aux[item].x = inverse scale / max(||a||, 1e-8) - the hot loop of score_topk_kernel multiplies by it as it does by the plain inverse scale.
-constexpr float kEvalCosineEps = 1e-8f;
-
+//
 // What ihg_search_topk adds to the deep call (an empty struct for every other instantiation, as DeepArgs<false>): an external query row per pair, the candidate
 // mask and the ranks a complete pair has, formed on the device (search_target_kernel) where the mask decides it.
 template <bool SEARCH>
@@ -149,7 +116,7 @@ __global__ __launch_bounds__(kBlockThreads) void score_prepare_kernel(const floa
         if constexpr (COSINE) {
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
-            inv /= fmaxf(sqrtf(ss), kEvalCosineEps);
+            inv /= fmaxf(sqrtf(ss), kCosineEps);
         }
         if (lane == 0) aux[item] = make_float2(inv, bias[item]);
         const int64_t tile = item >> 5;
@@ -258,7 +225,7 @@ __global__ __launch_bounds__(kEvalThreads) void score_topk_kernel(
         if constexpr (COSINE) {                                             // pinv = inverse scale / max(||m||, eps): the cosine's other factor
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
-            inv /= fmaxf(sqrtf(ss), kEvalCosineEps);
+            inv /= fmaxf(sqrtf(ss), kCosineEps);
         }
         if (lane == 0) pinv[r] = inv;
         for (int chunk = lane; chunk < 2 * ksteps; chunk += kWave) {
@@ -591,68 +558,6 @@ __global__ __launch_bounds__(kBlockThreads) void merge_deep_kernel(const float* 
     }
 }
 
-constexpr int kEvalWavesPerBlock = kEvalThreads / kWave;
-
-inline int eval_ksteps(int dim) { return (dim + 15) / 16; }
-inline size_t eval_lds_bytes(int dim, int pb) { return static_cast<size_t>(32 * pb) * (4 * 16 * eval_ksteps(dim) + 16) + static_cast<size_t>(32 * pb) * sizeof(float); }
-inline int eval_pair_tiles(int dim) { return eval_lds_bytes(dim, 2) <= 160 * 1024 ? 2 : 1; }      // pair tiles of 32 per workgroup
-
-inline int eval_slices(int64_t n_pairs, int64_t n_items, int dim) {
-    const int64_t blocks = (n_pairs + 32 * eval_pair_tiles(dim) - 1) / (32 * eval_pair_tiles(dim));
-    const int64_t tiles = (n_items + 31) / 32;
-    int64_t slices = (512 + blocks - 1) / blocks;                           // ~2 workgroups per CU in all (one resident per CU: LDS)
-    const int64_t most = std::max<int64_t>(1, tiles / (kEvalWavesPerBlock * 4));    // at least 4 tiles per wave
-    slices = std::max<int64_t>(1, std::min<int64_t>({slices, most, 64}));
-    return static_cast<int>(slices);
-}
-
-inline int64_t eval_frag_bytes(int64_t n_items, int dim) { return ((n_items + 31) / 32) * eval_ksteps(dim) * 2 * kWave * 16; }
-inline int64_t eval_aux_bytes(int64_t n_items) { return ((n_items + 31) / 32) * 32 * 8; }
-
-template <bool COSINE>
-int score_topk_launch(const char* what, const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
-                   const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
-                   int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
-    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kTopMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (k <= %d)", what, kTopMax);
-    if (n_pairs == 0) return IHG_OK;
-    if (features == nullptr || item_bias == nullptr || users == nullptr || queries == nullptr || top_scores == nullptr || top_items == nullptr)
-        return fail(IHG_ERR_INVALID, "%s: null pointer", what);
-    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
-    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_score_topk_workspace_bytes(n_pairs, n_items, dim))
-        return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", what);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
-    const int slices = eval_slices(n_pairs, n_items, dim);
-    const int64_t n_lists = static_cast<int64_t>(slices) * kEvalWavesPerBlock * 2;
-    v4u* frag = static_cast<v4u*>(workspace);
-    float2* aux = reinterpret_cast<float2*>(static_cast<unsigned char*>(workspace) + eval_frag_bytes(n_items, dim));
-    float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
-    int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
-    hipLaunchKernelGGL(score_prepare_kernel<COSINE>, dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux, SearchArgs<false>{});
-    static bool attr_set[64] = {};                           // per device ordinal: the opt-in to > 64 KB of LDS belongs to the device's code object
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
-    if (device < 0 || device >= 64 || !attr_set[device]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (device >= 0 && device < 64) attr_set[device] = true;
-    }
-    const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
-    const size_t lds = eval_lds_bytes(dim, pb);
-    if (pb == 2)
-        hipLaunchKernelGGL((score_topk_kernel<2, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{}, ExclArgs<false>{});
-    else
-        hipLaunchKernelGGL((score_topk_kernel<1, COSINE>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users, queries,
-                           query_row0, lambda_muq, n_pairs, part_val, part_idx, DeepArgs<false>{}, SearchArgs<false>{}, ExclArgs<false>{});
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs,
-                       static_cast<int>(n_lists * kTopMax), k, top_scores, top_items);
-    return check_launch(what);
-}
-
-inline int64_t eval_lists(int64_t n_pairs, int64_t n_items, int dim) { return static_cast<int64_t>(eval_slices(n_pairs, n_items, dim)) * kEvalWavesPerBlock * 2; }
-
 // once per ihg_search_topk call, one workgroup: *target = min(k, the candidates among the first n_items bits of the mask) - the deep kernels read it where the plain
 // deep call passes min(k, n_items) by value - and passes[c] = 0 (with no candidate no pass finds a pair incomplete, and merge_deep_kernel writes nothing)
 __global__ __launch_bounds__(kBlockThreads) void search_target_kernel(const uint32_t* __restrict__ item_mask, int64_t n_items, int k, int32_t* __restrict__ target,
@@ -704,146 +609,210 @@ __global__ __launch_bounds__(kBlockThreads) void exclude_target_kernel(const uin
     }
 }
 
-template <bool COSINE, bool SEARCH = false, bool EXCL = false>
-int score_topk_deep_launch(const char* what, const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
-                           const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
-                           int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t* passes, ihg_stream_t stream, SearchArgs<SEARCH> search = {},
-                           ExclArgs<EXCL> excl = {}) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ksteps = eval_ksteps(dim), pb = eval_pair_tiles(dim);
-    const int slices = eval_slices(n_pairs, n_items, dim);
-    const int64_t n_lists = eval_lists(n_pairs, n_items, dim);
-    v4u* frag = static_cast<v4u*>(workspace);
-    float2* aux = reinterpret_cast<float2*>(static_cast<unsigned char*>(workspace) + eval_frag_bytes(n_items, dim));
-    float* part_val = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(aux) + eval_aux_bytes(n_items));
-    int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + n_pairs * n_lists * kTopMax);
-    DeepState* state = reinterpret_cast<DeepState*>(part_idx + n_pairs * n_lists * kTopMax);
-    const int target = static_cast<int>(std::min<int64_t>(k, n_items));           // (SEARCH: the most a mask leaves - the passes launched; the kernels read search.target)
-    if constexpr (SEARCH) {
-        int32_t* target_cell = reinterpret_cast<int32_t*>(state + n_pairs);
-        if constexpr (EXCL) {                                               // the cell holds the candidates' count itself, and the 16 bytes after it begin target[n_pairs]
-            hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, search.item_mask, n_items, INT_MAX, target_cell, passes, n_pairs);
-            hipLaunchKernelGGL(exclude_target_kernel, dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, search.item_mask, n_items, k, target_cell, excl, target_cell + 4, n_pairs);
-            search.target = target_cell + 4;
-        } else {
-            hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, search.item_mask, n_items, k, target_cell, passes, n_pairs);
-            search.target = target_cell;
-        }
-    }
-    hipLaunchKernelGGL((score_prepare_kernel<COSINE, SEARCH>), dim3(grid_for_waves(n_items)), dim3(kBlockThreads), 0, s, features, ld, dim, ksteps, item_row0, n_items, item_bias, frag, aux, search);
-    hipLaunchKernelGGL(deep_init_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n_pairs * k + kBlockThreads - 1) / kBlockThreads, 4096))), dim3(kBlockThreads), 0, s, state, n_pairs,
-                       k, top_scores, top_items);
-    static bool attr_set[64] = {};                           // per device ordinal, as in score_topk_launch
+// ------------------------------------------------------------------------------------------------
+// Host side.  Every entry point below fills a RankCall (ranking.hpp) and hands it to catalogue_rank with its rules and its shape: the shared front in the shared
+// order, the workspace from the one layout function (eval_workspace), and the launch routine of the call's (shape, head) out of one table.
+// ------------------------------------------------------------------------------------------------
+constexpr int kEvalWavesPerBlock = kEvalThreads / kWave;
+constexpr size_t kEvalLds = 160 * 1024;
+
+constexpr int eval_ksteps(int dim) { return (dim + 15) / 16; }
+constexpr size_t eval_lds_bytes(int dim, int pb) { return static_cast<size_t>(32 * pb) * (4 * 16 * eval_ksteps(dim) + 16) + static_cast<size_t>(32 * pb) * sizeof(float); }
+inline int eval_pair_tiles(int dim) { return eval_lds_bytes(dim, 2) <= kEvalLds ? 2 : 1; }      // pair tiles of 32 per workgroup
+// the widest feature row whose 32-pair block (two fp16 planes + the row pad + the pair scales) fits the 160 KB of LDS: 1264 (79 k-steps of 16)
+constexpr int eval_max_dim() {
+    int dim = 16;
+    while (eval_lds_bytes(dim + 16, 1) <= kEvalLds) dim += 16;
+    return dim;
+}
+
+inline int eval_slices(int64_t n_pairs, int64_t n_items, int dim) {
+    const int64_t blocks = (n_pairs + 32 * eval_pair_tiles(dim) - 1) / (32 * eval_pair_tiles(dim));
+    const int64_t tiles = (n_items + 31) / 32;
+    int64_t slices = (512 + blocks - 1) / blocks;                           // ~2 workgroups per CU in all (one resident per CU: LDS)
+    const int64_t most = std::max<int64_t>(1, tiles / (kEvalWavesPerBlock * 4));    // at least 4 tiles per wave
+    slices = std::max<int64_t>(1, std::min<int64_t>({slices, most, 64}));
+    return static_cast<int>(slices);
+}
+inline int64_t eval_lists(int64_t n_pairs, int64_t n_items, int dim) { return static_cast<int64_t>(eval_slices(n_pairs, n_items, dim)) * kEvalWavesPerBlock * 2; }
+
+// The workspace of every catalogue entry point, region after region: the item fragments | aux | the partial lists' values | their ids | deep: DeepState per pair |
+// search: the 16-byte cell of search_target_kernel | excluding: target[n_pairs] of exclude_target_kernel, rounded up to 16 bytes.  A search without lists reads its
+// ranks from the cell itself.  A null base answers the size query (`bytes`), the caller's pointer carves the regions: the two cannot drift.
+struct EvalWorkspace {
+    v4u* frag;
+    float2* aux;
+    float* part_val;
+    int32_t* part_idx;
+    DeepState* state;
+    int32_t *target_cell, *target;
+    int64_t bytes;
+};
+inline EvalWorkspace eval_workspace(void* base, int64_t n_pairs, int64_t n_items, int dim, bool deep, bool search, bool excluding) {
+    const int64_t tiles = (n_items + 31) / 32, entries = n_pairs * eval_lists(n_pairs, n_items, dim) * kTopMax;
+    WorkspaceCursor ws(base);
+    EvalWorkspace w{};
+    w.frag = static_cast<v4u*>(ws.take(tiles * eval_ksteps(dim) * 2 * kWave * 16));
+    w.aux = static_cast<float2*>(ws.take(tiles * 32 * 8));
+    w.part_val = static_cast<float*>(ws.take(entries * 4));
+    w.part_idx = static_cast<int32_t*>(ws.take(entries * 4));
+    if (deep) w.state = static_cast<DeepState*>(ws.take(n_pairs * static_cast<int64_t>(sizeof(DeepState))));
+    if (search) w.target = w.target_cell = static_cast<int32_t*>(ws.take(16));
+    if (excluding) w.target = static_cast<int32_t*>(ws.take(align16(n_pairs * 4)));
+    w.bytes = ws.at;
+    return w;
+}
+
+// The scoring kernel of a call: PB = 2 pair tiles per workgroup where their planes fit LDS, and the opt-in to more than 64 KB of it - once per device ordinal (it
+// belongs to the device's code object) and per instantiation: the flags are a static of this template, which is instantiated once per kernel pair.
+template <bool COSINE, bool DEEP, bool SEARCH, bool EXCL>
+auto score_topk_kernel_for(int pb) {
+    const auto one = score_topk_kernel<1, COSINE, DEEP, SEARCH, EXCL>, two = score_topk_kernel<2, COSINE, DEEP, SEARCH, EXCL>;
+    static bool attr_set[64] = {};
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) (void)hipGetLastError();
     if (device < 0 || device >= 64 || !attr_set[device]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<1, COSINE, true, SEARCH, EXCL>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>((score_topk_kernel<2, COSINE, true, SEARCH, EXCL>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+        for (const void* kernel : {reinterpret_cast<const void*>(one), reinterpret_cast<const void*>(two)})
+            if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kEvalLds) != hipSuccess) (void)hipGetLastError();
         if (device >= 0 && device < 64) attr_set[device] = true;
     }
-    const int64_t blocks = (n_pairs + 32 * pb - 1) / (32 * pb);
-    const size_t lds = eval_lds_bytes(dim, pb);
-    const DeepArgs<true> deep{state, target};
-    const int n_passes = (target + kTopMax - 1) / kTopMax;
+    return pb == 2 ? two : one;
+}
+
+// The launches of one call.  Plain (DEEP = false): prepare -> score -> merge_topk_kernel.  Deep: the targets (SEARCH: on the device) -> prepare -> deep_init ->
+// ceil(min(k, n_items) / 10) passes of (score, merge_deep_kernel).
+template <bool COSINE, bool DEEP, bool SEARCH, bool EXCL>
+int catalogue_launch(const char* what, const RankCall& c) {
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const int ksteps = eval_ksteps(c.dim), pb = eval_pair_tiles(c.dim);
+    const int slices = eval_slices(c.n_pairs, c.n_items, c.dim);
+    const int n_lists = static_cast<int>(eval_lists(c.n_pairs, c.n_items, c.dim));
+    const EvalWorkspace ws = eval_workspace(c.workspace, c.n_pairs, c.n_items, c.dim, DEEP, SEARCH, EXCL);
+    const int target = static_cast<int>(std::min<int64_t>(c.k, c.n_items));        // (SEARCH: the most a mask leaves - the passes launched; the kernels read search.target)
+    SearchArgs<SEARCH> search{};
+    ExclArgs<EXCL> excl{};
+    DeepArgs<DEEP> deep{};
+    if constexpr (SEARCH) {
+        search = SearchArgs<true>{c.query_rows, c.ld_q, c.q_dim, c.item_mask, ws.target};
+        // EXCL: the cell holds the candidates' count itself, and exclude_target_kernel forms target[n_pairs] from it
+        hipLaunchKernelGGL(search_target_kernel, dim3(1), dim3(kBlockThreads), 0, s, c.item_mask, c.n_items, EXCL ? INT_MAX : c.k, ws.target_cell, c.passes, c.n_pairs);
+        if constexpr (EXCL) {
+            excl = ExclArgs<true>{c.excl_ptr, c.excl_items, c.excl_row};
+            hipLaunchKernelGGL(exclude_target_kernel, dim3(grid_for_waves(c.n_pairs)), dim3(kBlockThreads), 0, s, c.item_mask, c.n_items, c.k, ws.target_cell, excl, ws.target, c.n_pairs);
+        }
+    }
+    hipLaunchKernelGGL((score_prepare_kernel<COSINE, SEARCH>), dim3(grid_for_waves(c.n_items)), dim3(kBlockThreads), 0, s, c.features, c.ld, c.dim, ksteps, c.item_row0, c.n_items, c.item_bias,
+                       ws.frag, ws.aux, search);
+    if constexpr (DEEP) {
+        deep = DeepArgs<true>{ws.state, target};
+        hipLaunchKernelGGL(deep_init_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((c.n_pairs * c.k + kBlockThreads - 1) / kBlockThreads, 4096))), dim3(kBlockThreads), 0, s, ws.state,
+                           c.n_pairs, c.k, c.top_scores, c.top_items);
+    }
+    const auto score = score_topk_kernel_for<COSINE, DEEP, SEARCH, EXCL>(pb);
+    const dim3 grid(static_cast<unsigned>((c.n_pairs + 32 * pb - 1) / (32 * pb)), slices);
+    const int n_passes = DEEP ? (target + kTopMax - 1) / kTopMax : 1;
     for (int pass = 0; pass < n_passes; ++pass) {
-        if (pb == 2)
-            hipLaunchKernelGGL((score_topk_kernel<2, COSINE, true, SEARCH, EXCL>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
-                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search, excl);
+        hipLaunchKernelGGL(score, grid, dim3(kEvalThreads), eval_lds_bytes(c.dim, pb), s, c.features, c.ld, c.dim, ksteps, ws.frag, ws.aux, c.n_items, c.users, c.queries, c.query_row0,
+                           c.lambda_muq, c.n_pairs, ws.part_val, ws.part_idx, deep, search, excl);
+        if constexpr (DEEP)
+            hipLaunchKernelGGL((merge_deep_kernel<SEARCH, EXCL>), dim3(grid_for_waves(c.n_pairs)), dim3(kBlockThreads), 0, s, ws.part_val, ws.part_idx, c.n_pairs, n_lists, c.k, target, ws.state,
+                               c.top_scores, c.top_items, c.passes, search);
         else
-            hipLaunchKernelGGL((score_topk_kernel<1, COSINE, true, SEARCH, EXCL>), dim3(static_cast<unsigned>(blocks), slices), dim3(kEvalThreads), lds, s, features, ld, dim, ksteps, frag, aux, n_items, users,
-                               queries, query_row0, lambda_muq, n_pairs, part_val, part_idx, deep, search, excl);
-        hipLaunchKernelGGL((merge_deep_kernel<SEARCH, EXCL>), dim3(grid_for_waves(n_pairs)), dim3(kBlockThreads), 0, s, part_val, part_idx, n_pairs, static_cast<int>(n_lists), k, target, state, top_scores,
-                           top_items, passes, search);
+            hipLaunchKernelGGL(merge_topk_kernel, dim3(grid_for_waves(c.n_pairs)), dim3(kBlockThreads), 0, s, ws.part_val, ws.part_idx, c.n_pairs, n_lists * kTopMax, c.k, c.top_scores,
+                               c.top_items);
     }
     return check_launch(what);
+}
+
+// An entry point is its rules for the front and the first of its launch shapes, which also says what regions its workspace has (kExcluding: target[n_pairs]; a call of
+// that entry without lists launches kSearch).
+enum CatalogueShape { kPlain, kDeep, kSearch, kExcluding };
+constexpr const char* kPairBlock = "does not fit the LDS pair block";
+constexpr RankRules kScoreTopk{"ihg_score_topk", kTopMax, "", false, eval_max_dim(), kPairBlock, IHG_ERR_WORKSPACE};
+constexpr RankRules kScoreTopkCosine{"ihg_score_topk_cosine", kTopMax, "", false, eval_max_dim(), kPairBlock, IHG_ERR_WORKSPACE};
+constexpr RankRules kScoreTopkDeep{"ihg_score_topk_deep", kDeepMax, "1 <= ", false, eval_max_dim(), kPairBlock, IHG_ERR_WORKSPACE};
+constexpr RankRules kSearchTopk{"ihg_search_topk", kDeepMax, "1 <= ", true, eval_max_dim(), kPairBlock, IHG_ERR_INVALID};
+constexpr RankRules kSearchTopkExcluding{"ihg_search_topk_excluding", kDeepMax, "1 <= ", true, eval_max_dim(), kPairBlock, IHG_ERR_INVALID};
+
+inline int64_t catalogue_workspace_bytes(CatalogueShape shape, int64_t n_pairs, int64_t n_items, int dim, int k) {
+    if (n_pairs <= 0 || n_items <= 0 || dim <= 0 || (shape != kPlain && (k <= 0 || k > kDeepMax))) return 0;
+    return eval_workspace(nullptr, n_pairs, n_items, dim, shape >= kDeep, shape >= kSearch, shape >= kExcluding).bytes;
+}
+
+// the run-time (shape, head) -> the template instance: the one dispatch
+using CatalogueLaunch = int (*)(const char*, const RankCall&);
+constexpr CatalogueLaunch kCatalogueLaunch[4][2] = {{catalogue_launch<false, false, false, false>, catalogue_launch<true, false, false, false>},
+                                                    {catalogue_launch<false, true, false, false>, catalogue_launch<true, true, false, false>},
+                                                    {catalogue_launch<false, true, true, false>, catalogue_launch<true, true, true, false>},
+                                                    {catalogue_launch<false, true, true, true>, catalogue_launch<true, true, true, true>}};
+
+int catalogue_rank(const RankCall& c, const RankRules& r, CatalogueShape shape) {
+    if (int rc = rank_check_call(c, r)) return rc;
+    if (c.n_pairs == 0) return IHG_OK;
+    if (int rc = rank_check_pointers(c, r)) return rc;
+    if (shape != kPlain && eval_lists(c.n_pairs, c.n_items, c.dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", r.what);
+    if (int rc = rank_check_workspace(c, r, catalogue_workspace_bytes(shape, c.n_pairs, c.n_items, c.dim, c.k))) return rc;
+    if (shape == kExcluding && c.excl_ptr == nullptr) shape = kSearch;      // no lists: the launches of ihg_search_topk
+    return kCatalogueLaunch[shape][c.cosine != 0](r.what, c);
 }
 
 }  // namespace
 
 extern "C" {
 
-// the widest feature row whose 32-pair block (two fp16 planes + the row pad + the pair scales) fits the 160 KB of LDS: 1264 (79 k-steps of 16)
-int32_t ihg_score_topk_max_dim(void) {
-    int dim = 16;
-    while (eval_lds_bytes(dim + 16, 1) <= 160 * 1024) dim += 16;
-    return dim;
-}
+int32_t ihg_score_topk_max_dim(void) { return eval_max_dim(); }
+int32_t ihg_score_topk_max_k(void) { return kDeepMax; }
 
-int64_t ihg_score_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim) {
-    if (n_pairs <= 0 || n_items <= 0 || dim <= 0) return 0;
-    const int64_t n_lists = static_cast<int64_t>(eval_slices(n_pairs, n_items, dim)) * kEvalWavesPerBlock * 2;
-    return eval_frag_bytes(n_items, dim) + eval_aux_bytes(n_items) + n_pairs * n_lists * kTopMax * 8;
-}
+// regions: fragments | aux | partial values | partial ids
+int64_t ihg_score_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim) { return catalogue_workspace_bytes(kPlain, n_pairs, n_items, dim, 0); }
+// ... | DeepState[n_pairs]
+int64_t ihg_score_topk_deep_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) { return catalogue_workspace_bytes(kDeep, n_pairs, n_items, dim, k); }
+// ... | the target cell (16 bytes)
+int64_t ihg_search_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) { return catalogue_workspace_bytes(kSearch, n_pairs, n_items, dim, k); }
+// ... | target[n_pairs] (rounded up to 16 bytes)
+int64_t ihg_search_topk_excluding_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) { return catalogue_workspace_bytes(kExcluding, n_pairs, n_items, dim, k); }
 
 int ihg_score_topk(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                    const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
                    int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
-    return score_topk_launch<false>("ihg_score_topk", features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace, workspace_bytes, stream);
+    RankCall c;
+    c.features = features, c.ld = ld, c.dim = dim, c.query_row0 = query_row0, c.item_row0 = item_row0, c.n_items = n_items, c.item_bias = item_bias;
+    c.users = users, c.queries = queries, c.lambda_muq = lambda_muq, c.n_pairs = n_pairs, c.k = k, c.top_scores = top_scores, c.top_items = top_items;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    return catalogue_rank(c, kScoreTopk, kPlain);
 }
 
 // the cosine head: the same kernels with the rows' inverse norms folded into the two scale factors (score_prepare_kernel<true>, score_topk_kernel<PB, true>)
 int ihg_score_topk_cosine(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                    const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
                    int32_t* top_items, void* workspace, int64_t workspace_bytes, ihg_stream_t stream) {
-    return score_topk_launch<true>("ihg_score_topk_cosine", features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace, workspace_bytes, stream);
-}
-
-int32_t ihg_score_topk_max_k(void) { return kDeepMax; }
-
-int64_t ihg_score_topk_deep_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) {
-    if (n_pairs <= 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax) return 0;
-    return ihg_score_topk_workspace_bytes(n_pairs, n_items, dim) + n_pairs * static_cast<int64_t>(sizeof(DeepState));
+    RankCall c;
+    c.features = features, c.ld = ld, c.dim = dim, c.query_row0 = query_row0, c.item_row0 = item_row0, c.n_items = n_items, c.item_bias = item_bias;
+    c.users = users, c.queries = queries, c.lambda_muq = lambda_muq, c.n_pairs = n_pairs, c.k = k, c.top_scores = top_scores, c.top_items = top_items;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.cosine = 1, c.stream = stream;
+    return catalogue_rank(c, kScoreTopkCosine, kPlain);
 }
 
 int ihg_score_topk_deep(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                         const int64_t* users, const int64_t* queries, float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores,
                         int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes, ihg_stream_t stream) {
-    const char* what = "ihg_score_topk_deep";
-    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kDeepMax);
-    if (n_pairs == 0) return IHG_OK;
-    if (features == nullptr || item_bias == nullptr || users == nullptr || queries == nullptr || top_scores == nullptr || top_items == nullptr)
-        return fail(IHG_ERR_INVALID, "%s: null pointer", what);
-    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
-    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
-    if (eval_lists(n_pairs, n_items, dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", what);
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k))
-        return fail(IHG_ERR_WORKSPACE, "%s: workspace too small", what);
-    return cosine != 0 ? score_topk_deep_launch<true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace,
-                                                      workspace_bytes, passes, stream)
-                       : score_topk_deep_launch<false>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items, workspace,
-                                                       workspace_bytes, passes, stream);
-}
-
-int64_t ihg_search_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) {
-    const int64_t deep = ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k);
-    return deep == 0 ? 0 : deep + 16;                                       // + the cell of search_target_kernel
+    RankCall c;
+    c.features = features, c.ld = ld, c.dim = dim, c.query_row0 = query_row0, c.item_row0 = item_row0, c.n_items = n_items, c.item_bias = item_bias;
+    c.users = users, c.queries = queries, c.lambda_muq = lambda_muq, c.n_pairs = n_pairs, c.k = k, c.top_scores = top_scores, c.top_items = top_items;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.cosine = cosine, c.passes = passes, c.stream = stream;
+    return catalogue_rank(c, kScoreTopkDeep, kDeep);
 }
 
 int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
                     const int64_t* users, const int64_t* queries, const float* query_rows, int64_t ld_q, int32_t q_dim, const uint32_t* item_mask,
                     float lambda_muq, int64_t n_pairs, int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes,
                     int32_t cosine, int32_t* passes, ihg_stream_t stream) {
-    const char* what = "ihg_search_topk";
-    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kDeepMax);
-    if ((queries == nullptr) == (query_rows == nullptr)) return fail(IHG_ERR_INVALID, "%s: exactly one of queries and query_rows", what);
-    if (query_rows != nullptr && (q_dim < 1 || q_dim > dim || ld_q < q_dim)) return fail(IHG_ERR_INVALID, "%s: 1 <= q_dim <= dim and ld_q >= q_dim", what);
-    if (n_pairs == 0) return IHG_OK;
-    if (features == nullptr || item_bias == nullptr || users == nullptr || top_scores == nullptr || top_items == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
-    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
-    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
-    if (eval_lists(n_pairs, n_items, dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", what);
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k))
-        return fail(IHG_ERR_INVALID, "%s: workspace too small", what);
-    const SearchArgs<true> search{query_rows, ld_q, q_dim, item_mask, nullptr};
-    return cosine != 0 ? score_topk_deep_launch<true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
-                                                            workspace, workspace_bytes, passes, stream, search)
-                       : score_topk_deep_launch<false, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
-                                                             workspace, workspace_bytes, passes, stream, search);
-}
-
-int64_t ihg_search_topk_excluding_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k) {
-    const int64_t search = ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k);
-    return search == 0 ? 0 : search + (n_pairs * 4 + 15) / 16 * 16;         // + target[n_pairs] of exclude_target_kernel
+    RankCall c;
+    c.features = features, c.ld = ld, c.dim = dim, c.query_row0 = query_row0, c.item_row0 = item_row0, c.n_items = n_items, c.item_bias = item_bias;
+    c.users = users, c.queries = queries, c.query_rows = query_rows, c.ld_q = ld_q, c.q_dim = q_dim, c.item_mask = item_mask;
+    c.lambda_muq = lambda_muq, c.n_pairs = n_pairs, c.k = k, c.top_scores = top_scores, c.top_items = top_items;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.cosine = cosine, c.passes = passes, c.stream = stream;
+    return catalogue_rank(c, kSearchTopk, kSearch);
 }
 
 int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items, const float* item_bias,
@@ -851,32 +820,13 @@ int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, in
                               const int64_t* excl_ptr, const int32_t* excl_items, const int64_t* excl_row, int64_t n_excl_rows, float lambda_muq, int64_t n_pairs,
                               int32_t k, float* top_scores, int32_t* top_items, void* workspace, int64_t workspace_bytes, int32_t cosine, int32_t* passes,
                               ihg_stream_t stream) {
-    const char* what = "ihg_search_topk_excluding";
-    if (n_pairs < 0 || n_items <= 0 || dim <= 0 || k <= 0 || k > kDeepMax || ld < dim) return fail(IHG_ERR_INVALID, "%s: bad size (1 <= k <= %d)", what, kDeepMax);
-    if ((queries == nullptr) == (query_rows == nullptr)) return fail(IHG_ERR_INVALID, "%s: exactly one of queries and query_rows", what);
-    if (query_rows != nullptr && (q_dim < 1 || q_dim > dim || ld_q < q_dim)) return fail(IHG_ERR_INVALID, "%s: 1 <= q_dim <= dim and ld_q >= q_dim", what);
-    if ((excl_ptr == nullptr) != (excl_items == nullptr)) return fail(IHG_ERR_INVALID, "%s: excl_ptr and excl_items go together", what);
-    if (excl_ptr == nullptr && excl_row != nullptr) return fail(IHG_ERR_INVALID, "%s: excl_row without lists", what);
-    if (excl_ptr != nullptr && (n_excl_rows < 1 || (excl_row == nullptr && n_excl_rows != n_pairs && n_pairs > 0)))
-        return fail(IHG_ERR_INVALID, "%s: n_excl_rows >= 1, and == n_pairs without excl_row", what);
-    if (n_pairs == 0) return IHG_OK;
-    if (features == nullptr || item_bias == nullptr || users == nullptr || top_scores == nullptr || top_items == nullptr) return fail(IHG_ERR_INVALID, "%s: null pointer", what);
-    if (n_items > INT_MAX - 64) return fail(IHG_ERR_INVALID, "%s: item ids are int32", what);
-    if (eval_lds_bytes(dim, 1) > 160 * 1024) return fail(IHG_ERR_INVALID, "%s: feature width %d does not fit the LDS pair block (widest: %d)", what, dim, ihg_score_topk_max_dim());
-    if (eval_lists(n_pairs, n_items, dim) > kWave * kDeepListsPerLane) return fail(IHG_ERR_INVALID, "%s: more partial lists than the merge holds", what);
-    if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, k))
-        return fail(IHG_ERR_INVALID, "%s: workspace too small", what);
-    const SearchArgs<true> search{query_rows, ld_q, q_dim, item_mask, nullptr};
-    if (excl_ptr == nullptr)                                                // no lists: the launches of ihg_search_topk
-        return cosine != 0 ? score_topk_deep_launch<true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
-                                                                workspace, workspace_bytes, passes, stream, search)
-                           : score_topk_deep_launch<false, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores, top_items,
-                                                                 workspace, workspace_bytes, passes, stream, search);
-    const ExclArgs<true> excl{excl_ptr, excl_items, excl_row};
-    return cosine != 0 ? score_topk_deep_launch<true, true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores,
-                                                                  top_items, workspace, workspace_bytes, passes, stream, search, excl)
-                       : score_topk_deep_launch<false, true, true>(what, features, ld, dim, query_row0, item_row0, n_items, item_bias, users, queries, lambda_muq, n_pairs, k, top_scores,
-                                                                   top_items, workspace, workspace_bytes, passes, stream, search, excl);
+    RankCall c;
+    c.features = features, c.ld = ld, c.dim = dim, c.query_row0 = query_row0, c.item_row0 = item_row0, c.n_items = n_items, c.item_bias = item_bias;
+    c.users = users, c.queries = queries, c.query_rows = query_rows, c.ld_q = ld_q, c.q_dim = q_dim, c.item_mask = item_mask;
+    c.excl_ptr = excl_ptr, c.excl_items = excl_items, c.excl_row = excl_row, c.n_excl_rows = n_excl_rows;
+    c.lambda_muq = lambda_muq, c.n_pairs = n_pairs, c.k = k, c.top_scores = top_scores, c.top_items = top_items;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.cosine = cosine, c.passes = passes, c.stream = stream;
+    return catalogue_rank(c, kSearchTopkExcluding, kExcluding);
 }
 
 }  // extern "C"

@@ -1927,10 +1927,70 @@ def score_topk_max_width() -> int:
     return int(_lib.load().ihg_score_topk_max_dim())
 
 
+def _scored_matrix(features: Tensor, width: int) -> bool:
+    """Float32 GPU rows of any width up to ``width``, any row stride: the feature matrix the ranking entry points take."""
+    return (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1 and 0 < features.shape[1] <= width
+            and (features.shape[0] <= 1 or features.stride(0) >= features.shape[1]))
+
+
 def score_topk_supported(features: Tensor) -> bool:
     """True when ``ihg_score_topk`` takes this feature matrix: float32 GPU rows of any width up to ``score_topk_max_width()`` (any row stride)."""
-    return (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1 and 0 < features.shape[1] <= score_topk_max_width()
-            and (features.shape[0] <= 1 or features.stride(0) >= features.shape[1]))
+    return _scored_matrix(features, score_topk_max_width())
+
+
+# The four public ranking functions below are these helpers and one library call each.
+def _rank_features(entry: str, features: Tensor, item_row0: int, item_bias: Tensor, width: int):
+    """The feature-matrix test of ``entry`` -> ``(n_items, dim, bias)``."""
+    if not _scored_matrix(features, width):
+        raise _lib.IhgnnHipError(f'{entry} needs a float32 GPU feature matrix of width <= {width}, got {tuple(features.shape)} {features.dtype} on {features.device}')
+    return int(features.shape[0]) - int(item_row0), int(features.shape[1]), item_bias.detach().to(torch.float32).contiguous()
+
+
+def _rank_pairs(what: Optional[str], features: Tensor, users: Tensor, queries: Optional[Tensor], query_rows: Optional[Tensor] = None):
+    """The pair sources on the features' device -> ``(users, queries, query_rows, ld_q, q_dim, n_pairs)``.  ``what`` names a search function: exactly one of
+    ``queries`` / ``query_rows``, one per user."""
+    if what is not None and (queries is None) == (query_rows is None):
+        raise ValueError(f'{what}: give exactly one of queries and query_rows')
+    n_pairs = int(users.shape[0])
+    users = users.to(device=features.device, dtype=torch.int64).contiguous()
+    ld_q = q_dim = 0
+    if queries is not None:
+        queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
+        source = int(queries.shape[0])
+    else:
+        query_rows = _rows(query_rows, 'query_rows')
+        source, q_dim, ld_q = int(query_rows.shape[0]), int(query_rows.shape[1]), _ld(query_rows)
+    if what is not None and source != n_pairs:
+        raise ValueError(f'{what}: {n_pairs} users but {source} queries')
+    return users, queries, query_rows, ld_q, q_dim, n_pairs
+
+
+def _rank_outputs(n_pairs: int, depth: int, device):
+    """``(top_items [C, depth] int32, top_scores [C, depth], passes [C] int32)``, uninitialised."""
+    return (torch.empty(n_pairs, depth, dtype=torch.int32, device=device), torch.empty(n_pairs, depth, dtype=torch.float32, device=device),
+            torch.empty(n_pairs, dtype=torch.int32, device=device))
+
+
+def _search_lists(what: str, lists, rows: Optional[Tensor], build, noun: str, rows_name: str, n_pairs: int, n_items: int, device, need_a_run: bool = False):
+    """Per-search lists as the entry points read them -> ``(ptr, ids, rows, n_runs, total)`` on ``device``.  ``lists = (ptr, items)``: int32 items are taken as
+    ``build`` (``exclusion_lists`` / ``candidate_lists``) returned them, any other integer type goes through it first.  ``rows`` (the ``rows_name=`` keyword) maps
+    searches to runs; without it there is one run per search.  An empty id tensor has no address, and a null list means "no lists": it becomes a one-entry dummy that
+    no offset reaches (``total`` stays 0)."""
+    ptr, ids = lists
+    if ids.dtype != torch.int32:
+        ptr, ids = build(ptr, ids, n_items)
+    ptr = ptr.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+    ids = ids.reshape(-1).to(device=device).contiguous()
+    n_runs, total = int(ptr.shape[0]) - 1, int(ids.shape[0])
+    if need_a_run and n_runs < 1 and n_pairs > 0:
+        raise ValueError(f'{what}: the offsets hold at least one run')
+    if rows is not None:
+        if rows.dim() != 1 or int(rows.shape[0]) != n_pairs:
+            raise ValueError(f'{what}: {n_pairs} searches but {rows_name} of {tuple(rows.shape)}')
+        rows = rows.to(device=device, dtype=torch.int64).contiguous()
+    elif n_runs != n_pairs:
+        raise ValueError(f'{what}: {n_pairs} searches but {n_runs} {noun} lists ({rows_name}= maps searches to shared lists)')
+    return ptr, (ids if total else ids.new_zeros(1)), rows, n_runs, total
 
 
 def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int, item_row0: int, item_bias: Tensor, lam: float, k: int = 10, cosine: bool = False):
@@ -1942,16 +2002,9 @@ def score_topk(features: Tensor, users: Tensor, queries: Tensor, query_row0: int
     if k > 10:
         return score_topk_deep(features, users, queries, query_row0, item_row0, item_bias, lam, k, cosine=cosine)[:2]
     lib = _lib.load()
-    if not score_topk_supported(features):
-        raise _lib.IhgnnHipError(f'ihg_score_topk needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
-    n_pairs = int(users.shape[0])
-    n_items = int(features.shape[0]) - int(item_row0)
-    dim = int(features.shape[1])
-    users = users.to(device=features.device, dtype=torch.int64).contiguous()
-    queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
-    bias = item_bias.detach().to(torch.float32).contiguous()
-    top_scores = torch.empty(n_pairs, k, dtype=torch.float32, device=features.device)
-    top_items = torch.empty(n_pairs, k, dtype=torch.int32, device=features.device)
+    n_items, dim, bias = _rank_features('ihg_score_topk', features, item_row0, item_bias, score_topk_max_width())
+    users, queries, _, _, _, n_pairs = _rank_pairs(None, features, users, queries)
+    top_items, top_scores, _ = _rank_outputs(n_pairs, k, features.device)
     ws = _workspace(int(lib.ihg_score_topk_workspace_bytes(n_pairs, n_items, dim)), features.device)
     name = 'score_topk_cosine' if cosine else 'score_topk'
     with profiler.kernel(name, n_pairs, dim):
@@ -1971,18 +2024,9 @@ def score_topk_deep(features: Tensor, users: Tensor, queries: Tensor, query_row0
     and the call runs in passes that each rank at least ten more items of every pair that is not complete yet (``include/ihgnn_hip.h`` has the scheme);
     ``passes[c]`` = the passes that found pair ``c`` incomplete, at most ``ceil(min(k, I) / 10)``.  Exact, with the tie order and the ``-1`` tail of ``score_topk``."""
     lib = _lib.load()
-    if not score_topk_supported(features):
-        raise _lib.IhgnnHipError(f'ihg_score_topk_deep needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
-    n_pairs = int(users.shape[0])
-    n_items = int(features.shape[0]) - int(item_row0)
-    dim = int(features.shape[1])
-    users = users.to(device=features.device, dtype=torch.int64).contiguous()
-    queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
-    bias = item_bias.detach().to(torch.float32).contiguous()
-    width = max(int(k), 0)
-    top_scores = torch.empty(n_pairs, width, dtype=torch.float32, device=features.device)
-    top_items = torch.empty(n_pairs, width, dtype=torch.int32, device=features.device)
-    passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
+    n_items, dim, bias = _rank_features('ihg_score_topk_deep', features, item_row0, item_bias, score_topk_max_width())
+    users, queries, _, _, _, n_pairs = _rank_pairs(None, features, users, queries)
+    top_items, top_scores, passes = _rank_outputs(n_pairs, max(int(k), 0), features.device)
     ws = _workspace(int(lib.ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
     with profiler.kernel('score_topk_deep_cosine' if cosine else 'score_topk_deep', n_pairs, dim):
         _lib.check(lib.ihg_score_topk_deep(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), float(lam),
@@ -2063,56 +2107,19 @@ def search_topk(features: Tensor, users: Tensor, query_row0: int, item_row0: int
     if exclude is None and exclude_rows is not None:
         raise ValueError('search_topk: exclude_rows without exclude')
     lib = _lib.load()
-    if not score_topk_supported(features):
-        raise _lib.IhgnnHipError(f'ihg_search_topk needs a float32 GPU feature matrix of width <= {score_topk_max_width()}, got {tuple(features.shape)} {features.dtype} on {features.device}')
-    if (queries is None) == (query_rows is None):
-        raise ValueError('search_topk: give exactly one of queries and query_rows')
-    n_pairs = int(users.shape[0])
-    n_items = int(features.shape[0]) - int(item_row0)
-    dim = int(features.shape[1])
-    users = users.to(device=features.device, dtype=torch.int64).contiguous()
-    ld_q = q_dim = 0
-    if queries is not None:
-        queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
-        source = int(queries.shape[0])
-    else:
-        query_rows = _rows(query_rows, 'query_rows')
-        source, q_dim, ld_q = int(query_rows.shape[0]), int(query_rows.shape[1]), _ld(query_rows)
-    if source != n_pairs:
-        raise ValueError(f'search_topk: {n_pairs} users but {source} queries')
+    n_items, dim, bias = _rank_features('ihg_search_topk', features, item_row0, item_bias, score_topk_max_width())
+    users, queries, query_rows, ld_q, q_dim, n_pairs = _rank_pairs('search_topk', features, users, queries, query_rows)
     mask = None if candidates is None else pack_item_mask(candidates.to(features.device), n_items)
-    bias = item_bias.detach().to(torch.float32).contiguous()
-    width = max(int(k), 0)
-    top_scores = torch.empty(n_pairs, width, dtype=torch.float32, device=features.device)
-    top_items = torch.empty(n_pairs, width, dtype=torch.int32, device=features.device)
-    passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
-    if exclude is None:
-        ws = _workspace(int(lib.ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
-        with profiler.kernel('search_topk_cosine' if cosine else 'search_topk', n_pairs, dim):
-            _lib.check(lib.ihg_search_topk(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), _ptr(query_rows),
-                                           ld_q, q_dim, _ptr(mask), float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)),
-                                           _ptr(passes), _stream()), 'ihg_search_topk')
-        return top_items, top_scores, passes
-    ptr, ids = exclude
-    if ids.dtype != torch.int32:
-        ptr, ids = exclusion_lists(ptr, ids, n_items)
-    ptr = ptr.to(device=features.device, dtype=torch.int64).contiguous()
-    ids = ids.to(device=features.device).contiguous()
-    if ids.numel() == 0:
-        ids = ids.new_zeros(1)                                              # (an empty tensor has no address, and the entry point takes a null list for "no lists")
-    n_rows = int(ptr.shape[0]) - 1
-    if exclude_rows is not None:
-        exclude_rows = exclude_rows.to(device=features.device, dtype=torch.int64).contiguous()
-        if exclude_rows.dim() != 1 or int(exclude_rows.shape[0]) != n_pairs:
-            raise ValueError(f'search_topk: {n_pairs} searches but exclude_rows of {tuple(exclude_rows.shape)}')
-    elif n_rows != n_pairs:
-        raise ValueError(f'search_topk: {n_pairs} searches but {n_rows} exclusion lists (exclude_rows= maps searches to shared lists)')
-    ws = _workspace(int(lib.ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, int(k))), features.device)
-    with profiler.kernel('search_topk_excluding_cosine' if cosine else 'search_topk_excluding', n_pairs, dim):
-        _lib.check(lib.ihg_search_topk_excluding(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries),
-                                                 _ptr(query_rows), ld_q, q_dim, _ptr(mask), _ptr(ptr), _ptr(ids), _ptr(exclude_rows), n_rows, float(lam), n_pairs, int(k),
-                                                 _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4, int(bool(cosine)), _ptr(passes), _stream()),
-                   'ihg_search_topk_excluding')
+    top_items, top_scores, passes = _rank_outputs(n_pairs, max(int(k), 0), features.device)
+    entry, lists = 'search_topk', ()
+    if exclude is not None:
+        ptr, ids, exclude_rows, n_rows, _ = _search_lists('search_topk', exclude, exclude_rows, exclusion_lists, 'exclusion', 'exclude_rows', n_pairs, n_items, features.device)
+        entry, lists = 'search_topk_excluding', (_ptr(ptr), _ptr(ids), _ptr(exclude_rows), n_rows)
+    ws = _workspace(int(getattr(lib, f'ihg_{entry}_workspace_bytes')(n_pairs, n_items, dim, int(k))), features.device)
+    with profiler.kernel(entry + '_cosine' if cosine else entry, n_pairs, dim):
+        _lib.check(getattr(lib, 'ihg_' + entry)(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries), _ptr(query_rows),
+                                                ld_q, q_dim, _ptr(mask), *lists, float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items), _ptr(ws), ws.numel() * 4,
+                                                int(bool(cosine)), _ptr(passes), _stream()), 'ihg_' + entry)
     return top_items, top_scores, passes
 
 
@@ -2139,75 +2146,24 @@ def search_candidates(features: Tensor, users: Tensor, query_row0: int, item_row
     if not isinstance(lists, (tuple, list)) or len(lists) != 2:
         raise ValueError('search_candidates: lists is (offsets, items)')
     lib = _lib.load()
-    width = search_candidates_max_width()
-    if not (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1 and 0 < features.shape[1] <= width
-            and (features.shape[0] <= 1 or features.stride(0) >= features.shape[1])):
-        raise _lib.IhgnnHipError(f'ihg_search_candidates needs a float32 GPU feature matrix of width <= {width}, got {tuple(features.shape)} {features.dtype} on {features.device}')
-    if (queries is None) == (query_rows is None):
-        raise ValueError('search_candidates: give exactly one of queries and query_rows')
-    n_pairs = int(users.shape[0])
-    n_items = int(features.shape[0]) - int(item_row0)
-    dim = int(features.shape[1])
-    users = users.to(device=features.device, dtype=torch.int64).contiguous()
-    ld_q = q_dim = 0
-    if queries is not None:
-        queries = queries.to(device=features.device, dtype=torch.int64).contiguous()
-        source = int(queries.shape[0])
-    else:
-        query_rows = _rows(query_rows, 'query_rows')
-        source, q_dim, ld_q = int(query_rows.shape[0]), int(query_rows.shape[1]), _ld(query_rows)
-    if source != n_pairs:
-        raise ValueError(f'search_candidates: {n_pairs} users but {source} queries')
-    cand_ptr, cand_ids = lists
-    if cand_ids.dtype != torch.int32:
-        cand_ptr, cand_ids = candidate_lists(cand_ptr, cand_ids, n_items)
-    cand_ptr = cand_ptr.reshape(-1).to(device=features.device, dtype=torch.int64).contiguous()
-    cand_ids = cand_ids.reshape(-1).to(device=features.device).contiguous()
-    total = int(cand_ids.shape[0])
-    n_runs = int(cand_ptr.shape[0]) - 1
-    if n_runs < 1 and n_pairs > 0:
-        raise ValueError('search_candidates: the offsets hold at least one run')
-    if list_rows is not None:
-        if list_rows.dim() != 1 or int(list_rows.shape[0]) != n_pairs:
-            raise ValueError(f'search_candidates: {n_pairs} searches but list_rows of {tuple(list_rows.shape)}')
-        if return_scores and not list_rows.is_cuda:
-            named = list_rows[list_rows >= 0]
-            if named.numel() != torch.unique(named).numel():
-                raise ValueError('search_candidates: return_scores with a list that two searches share (a slot holds one score)')
-        list_rows = list_rows.to(device=features.device, dtype=torch.int64).contiguous()
-    elif n_runs != n_pairs:
-        raise ValueError(f'search_candidates: {n_pairs} searches but {n_runs} candidate lists (list_rows= maps searches to shared lists)')
+    n_items, dim, bias = _rank_features('ihg_search_candidates', features, item_row0, item_bias, search_candidates_max_width())
+    users, queries, query_rows, ld_q, q_dim, n_pairs = _rank_pairs('search_candidates', features, users, queries, query_rows)
+    cand_ptr, cand_ids, cand_rows, n_runs, total = _search_lists('search_candidates', lists, list_rows, candidate_lists, 'candidate', 'list_rows', n_pairs, n_items,
+                                                                 features.device, need_a_run=True)
+    if return_scores and list_rows is not None and not list_rows.is_cuda:
+        named = list_rows[list_rows >= 0]
+        if named.numel() != torch.unique(named).numel():
+            raise ValueError('search_candidates: return_scores with a list that two searches share (a slot holds one score)')
     mask = None if candidates is None else pack_item_mask(candidates.to(features.device), n_items)
-    excl_ptr = excl_ids = None
-    n_excl = 0
-    if exclude is not None:
-        excl_ptr, excl_ids = exclude
-        if excl_ids.dtype != torch.int32:
-            excl_ptr, excl_ids = exclusion_lists(excl_ptr, excl_ids, n_items)
-        excl_ptr = excl_ptr.to(device=features.device, dtype=torch.int64).contiguous()
-        excl_ids = excl_ids.to(device=features.device).contiguous()
-        if excl_ids.numel() == 0:
-            excl_ids = excl_ids.new_zeros(1)
-        n_excl = int(excl_ptr.shape[0]) - 1
-        if exclude_rows is not None:
-            exclude_rows = exclude_rows.to(device=features.device, dtype=torch.int64).contiguous()
-            if exclude_rows.dim() != 1 or int(exclude_rows.shape[0]) != n_pairs:
-                raise ValueError(f'search_candidates: {n_pairs} searches but exclude_rows of {tuple(exclude_rows.shape)}')
-        elif n_excl != n_pairs:
-            raise ValueError(f'search_candidates: {n_pairs} searches but {n_excl} exclusion lists (exclude_rows= maps searches to shared lists)')
-    bias = item_bias.detach().to(torch.float32).contiguous()
-    depth = max(int(k), 0)
-    top_scores = torch.empty(n_pairs, depth, dtype=torch.float32, device=features.device)
-    top_items = torch.empty(n_pairs, depth, dtype=torch.int32, device=features.device)
-    passes = torch.empty(n_pairs, dtype=torch.int32, device=features.device)
+    excl_ptr, excl_ids, exclude_rows, n_excl, _ = (None, None, None, 0, 0) if exclude is None else _search_lists(
+        'search_candidates', exclude, exclude_rows, exclusion_lists, 'exclusion', 'exclude_rows', n_pairs, n_items, features.device)
+    top_items, top_scores, passes = _rank_outputs(n_pairs, max(int(k), 0), features.device)
     all_scores = torch.empty(total, dtype=torch.float32, device=features.device) if return_scores else None
-    if total == 0:
-        cand_ids = cand_ids.new_zeros(1)                                    # (an empty tensor has no address: the one-entry dummy of search_topk)
     ws = _workspace(int(lib.ihg_search_candidates_workspace_bytes(n_pairs, total, dim, int(k))), features.device)
     with profiler.kernel('search_candidates_cosine' if cosine else 'search_candidates', n_pairs, dim):
         _lib.check(lib.ihg_search_candidates(_ptr(features), _ld(features), dim, int(query_row0), int(item_row0), n_items, _ptr(bias), _ptr(users), _ptr(queries),
                                              _ptr(query_rows), ld_q, q_dim, _ptr(mask), _ptr(excl_ptr), _ptr(excl_ids), _ptr(exclude_rows), n_excl, _ptr(cand_ptr),
-                                             _ptr(cand_ids), _ptr(list_rows), n_runs, total, float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items),
+                                             _ptr(cand_ids), _ptr(cand_rows), n_runs, total, float(lam), n_pairs, int(k), _ptr(top_scores), _ptr(top_items),
                                              _ptr(all_scores) if total else None, _ptr(ws), ws.numel() * 4, int(bool(cosine)), _ptr(passes), _stream()),
                    'ihg_search_candidates')
     if return_scores:

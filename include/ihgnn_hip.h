@@ -608,7 +608,8 @@ int ihg_device_batch(uint64_t seed, uint64_t counter, const int64_t* pos_triples
  * multiplied by a power of two and taken apart into two fp16 terms (hi + lo, 22 significand bits); a product is three v_mfma_f32_32x32x16_f16 partial products
  * accumulated in fp32 (relative error <= 3 x 2^-22 per product, as accurate as the fp32 matrix instructions on these sums - tests/test_gpu_parity.py); the item rows are
  * split once per call into the workspace.
- * Workspace: ihg_score_topk_workspace_bytes(n_pairs, n_items, dim) bytes (the split item rows + partial lists).
+ * Workspace: ihg_score_topk_workspace_bytes(n_pairs, n_items, dim) bytes; regions in order: the split item rows (MFMA fragments) | aux, 8 bytes per item | the partial
+ * lists' scores | their item ids.  A workspace that is NULL, not 16-byte aligned or smaller answers IHG_ERR_WORKSPACE (so do ihg_score_topk_cosine and _deep).
  */
 int32_t ihg_score_topk_max_dim(void);
 int64_t ihg_score_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim);
@@ -689,7 +690,7 @@ int ihg_score_topk_cosine(const float* features, int64_t ld, int32_t dim, int64_
  * item id, or all equal, need 8 at k = 128.  Every pass computes bit-identical scores (one kernel, one item order), so the boundary comparison is exact under ties and
  * two calls return the same bits; k <= 10 returns the bits of ihg_score_topk / ihg_score_topk_cosine.
  *   passes (optional, [n_pairs] int32): passes[c] = the number of passes that found pair c incomplete.
- * Workspace: ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k) bytes (that of ihg_score_topk + 16 bytes per pair).
+ * Workspace: ihg_score_topk_deep_workspace_bytes(n_pairs, n_items, dim, k) bytes: the regions of ihg_score_topk | the pairs' state (count, boundary, passes), 16 bytes per pair.
  */
 int32_t ihg_score_topk_max_k(void);
 int64_t ihg_score_topk_deep_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k);
@@ -715,7 +716,8 @@ int ihg_score_topk_deep(const float* features, int64_t ld, int32_t dim, int64_t 
  * With `queries`, no negative user and no mask the call returns the bits of ihg_score_topk_deep; with query_rows, those of ihg_score_topk_deep on a feature matrix
  * that has the rows appended (zero above q_dim) as further query rows.
  * IHG_ERR_INVALID before anything is launched: both or neither of queries / query_rows, q_dim outside 1 .. dim, ld_q < q_dim, k outside 1 .. 128, a workspace
- * smaller than ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k) (that of ihg_score_topk_deep + 16 bytes).  n_pairs == 0 returns IHG_OK.
+ * smaller than ihg_search_topk_workspace_bytes(n_pairs, n_items, dim, k) (the regions of ihg_score_topk_deep | the 16-byte cell of the candidates' count) or not 16-byte aligned.  n_pairs == 0 with otherwise good sizes, query source (and lists)
+ * returns IHG_OK before any pointer is looked at; so it does for every ranking entry point.
  */
 int64_t ihg_search_topk_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k);
 int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
@@ -742,7 +744,7 @@ int ihg_search_topk(const float* features, int64_t ld, int32_t dim, int64_t quer
  * (ops.exclusion_lists builds such lists); a run that is not strictly ascending gives a wrong ranking, not a fault.
  * IHG_ERR_INVALID before anything is launched, in ihg_search_topk's order: its size checks, its query-source checks, then excl_ptr without excl_items or the
  * reverse, excl_row without lists, n_excl_rows < 1 with lists (or != n_pairs with lists and no excl_row), then its null-pointer, width and list checks, then a
- * workspace smaller than ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, k) (that of ihg_search_topk + 4 bytes per pair, rounded up to 16).
+ * workspace smaller than ihg_search_topk_excluding_workspace_bytes(n_pairs, n_items, dim, k) (the regions of ihg_search_topk | target_c, 4 bytes per pair, rounded up to 16).
  */
 int64_t ihg_search_topk_excluding_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t dim, int32_t k);
 int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, int64_t query_row0, int64_t item_row0, int64_t n_items,
@@ -779,7 +781,8 @@ int ihg_search_topk_excluding(const float* features, int64_t ld, int32_t dim, in
  * strictly ascending gives a wrong ranking, offsets outside [0, total] an empty run, an id outside [0, n_items) an entry that is never ranked - none of them a fault.
  * IHG_ERR_INVALID before anything is launched: ihg_search_topk_excluding's size, query-source and exclusion-list checks, then total < 0, n_cand_rows < 1 (or
  * != n_pairs without cand_row), then (n_pairs == 0 returns IHG_OK) a null pointer, dim > ihg_search_candidates_max_dim(), a workspace that is not 16-byte aligned or
- * smaller than ihg_search_candidates_workspace_bytes(n_pairs, total, dim, k) = 4 total (rounded up to 16) + 8 (n_pairs + 1) (rounded up to 16) + 16 n_pairs.
+ * smaller than ihg_search_candidates_workspace_bytes(n_pairs, total, dim, k) ; regions in order: the entries' scores, 4 total (rounded up to 16) | the scoring units' scan,
+ * 8 (n_pairs + 1) (rounded up to 16) | the searches' runs, 16 n_pairs.
  */
 int32_t ihg_search_candidates_max_dim(void);
 int64_t ihg_search_candidates_workspace_bytes(int64_t n_pairs, int64_t total, int32_t dim, int32_t k);
