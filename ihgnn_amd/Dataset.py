@@ -75,13 +75,13 @@ class GraphDataset(Dataset):
     SAMPLE_MAX = 16                    # negatives per positive the device sampler draws at most (kSampleMax of csrc/tail.hip)
 
     def __init__(self, fn_graph_info: str, fn_queries_multihot: str, fn_train_data: str, graph_type: type,
-                 random_negative_sample_size: int, non_random_negative_sample_size: int, device: torch.device):
+                 random_negative_sample_size: int, non_random_negative_sample_size: int, device: torch.device, filter_negatives: bool = False):
         super().__init__()
         counts = read_graph_info(fn_graph_info)                      # the three input files go through the native readers
         bag_words, bag_offsets = read_query_bags(fn_queries_multihot)
         n_logs, triples, negatives, rows = parse_search_logs(fn_train_data, with_rows=True)
         self._setup(counts, bag_words, bag_offsets, triples, graph_type,
-                    random_negative_sample_size, non_random_negative_sample_size, device)
+                    random_negative_sample_size, non_random_negative_sample_size, device, filter_negatives)
         self.pos_log = rows
         self._fn_train_data = fn_train_data
         self._search_logs = None
@@ -100,15 +100,16 @@ class GraphDataset(Dataset):
                     bag_words: np.ndarray, bag_offsets: np.ndarray, triples: np.ndarray,
                     graph_type: type = PpsHyperGraph, random_negative_sample_size: int = 10,
                     non_random_negative_sample_size: int = 0, device: torch.device = torch.device('cuda:0'),
-                    pos_log: Optional[np.ndarray] = None, neg_triples: Optional[np.ndarray] = None) -> 'GraphDataset':
+                    pos_log: Optional[np.ndarray] = None, neg_triples: Optional[np.ndarray] = None, filter_negatives: bool = False) -> 'GraphDataset':
         """In-memory construction (synthetic corpora): ``bag_words`` are 0-based word ids, ``triples`` 0-based per type;
         ``pos_log[e]`` = the search log hyperedge ``e`` came from (default: one log per positive); ``neg_triples`` ``[M, 3]`` = the logged
-        negatives (user, query, item), array order standing for file order (default: none)."""
+        negatives (user, query, item), array order standing for file order (default: none); ``filter_negatives``: random negatives are drawn outside what the
+        positive's user interacted with in training (``user_item_lists``; default off: uniform over the catalogue)."""
         self = cls.__new__(cls)
         Dataset.__init__(self)
         self._setup([user_count, query_count, item_count, vocab_size], np.asarray(bag_words, np.int64),
                     np.asarray(bag_offsets, np.int64), np.asarray(triples, np.int64).reshape(-1, 3), graph_type,
-                    random_negative_sample_size, non_random_negative_sample_size, device)
+                    random_negative_sample_size, non_random_negative_sample_size, device, filter_negatives)
         if pos_log is not None:
             self.pos_log = np.ascontiguousarray(pos_log, dtype=np.int64)
         self._fn_train_data = None
@@ -119,7 +120,7 @@ class GraphDataset(Dataset):
         return self
 
     def _setup(self, counts: Sequence[int], bag_words: np.ndarray, bag_offsets: np.ndarray, triples: np.ndarray,
-               graph_type: type, rand_neg: int, nonrand_neg: int, device: torch.device) -> None:
+               graph_type: type, rand_neg: int, nonrand_neg: int, device: torch.device, filter_negatives: bool = False) -> None:
         if graph_type not in (Pps2DGraph, PpsHyperGraph, PpsLogHyperGraph):
             raise AssertionError(f'unsupported graph type: {graph_type}')
         GraphDataset.device = device
@@ -127,6 +128,9 @@ class GraphDataset(Dataset):
         self.rand_neg_sample_size = rand_neg
         self.nonrand_neg_sample_size = nonrand_neg
         self.neg_sample_size = rand_neg + nonrand_neg
+        self.filter_negatives = bool(filter_negatives)
+        if self.filter_negatives and nonrand_neg:
+            raise ValueError('filter_negatives draws random negatives only: it does not go with logged negatives (non_random_negative_sample_size > 0)')
 
         self.user_count, self.query_count, self.item_count, self.vocab_size = (int(c) for c in counts)
         self.node_count = self.user_count + self.query_count + self.item_count
@@ -212,6 +216,22 @@ class GraphDataset(Dataset):
             self._user_items = (ptr, np.ascontiguousarray(keys % self.item_count, np.int32))
         return self._user_items
 
+    @property
+    def max_user_items(self) -> int:
+        """The longest run of ``user_item_lists``: the most distinct training items any one user has.  Computed once, on the host."""
+        if getattr(self, '_max_user_items', None) is None:
+            self._max_user_items = int(np.diff(self.user_item_lists[0]).max(initial=0))
+        return self._max_user_items
+
+    def user_item_set(self, user: int) -> frozenset:
+        """User ``user``'s run of ``user_item_lists`` as a set, built when first asked for (the host sampler's rejection test under ``filter_negatives``)."""
+        sets = self.__dict__.setdefault('_user_item_sets', {})
+        seen = sets.get(user)
+        if seen is None:
+            ptr, items = self.user_item_lists
+            seen = sets[user] = frozenset(items[ptr[user]:ptr[user + 1]].tolist()) if 0 <= user < self.user_count else frozenset()
+        return seen
+
     def user_item_lists_on(self, device) -> Tuple[Tensor, Tensor]:
         """``user_item_lists`` as tensors on ``device``, copied there once."""
         device = torch.device(device)
@@ -283,8 +303,19 @@ class GraphDataset(Dataset):
 
     def __getitem__(self, index: int) -> Sample:
         """One positive and its sampled negative items (``Dataset.py:107-119``): ``random.sample`` draws distinct
-        items per call and may hit the positive; logged negatives of the (user, query) pair come first if requested."""
+        items per call and may hit the positive; logged negatives of the (user, query) pair come first if requested.  Under ``filter_negatives``
+        (random negatives only) the items are ``random.randrange`` draws, kept while distinct and outside the user's training items."""
         u, q, i = (int(x) for x in self.pos_triples[index])
+        if self.filter_negatives:
+            seen, k = self.user_item_set(u), self.rand_neg_sample_size
+            if k + len(seen) > self.item_count:
+                raise ValueError(f'filter_negatives: user {u} has {len(seen)} of {self.item_count} items, which leaves fewer than {k} to draw')
+            drawn: List[int] = []
+            while len(drawn) < k:
+                item = random.randrange(self.item_count)
+                if item not in seen and item not in drawn:
+                    drawn.append(item)
+            return (u, q, i, 1), drawn
         want_logged = self.nonrand_neg_sample_size
         if want_logged == 0:
             return (u, q, i, 1), random.sample(range(self.item_count), self.rand_neg_sample_size)
@@ -321,7 +352,9 @@ class GraphDataset(Dataset):
         ``ihg_sample_negatives`` (distinct within a sample, uniform over the catalogue, may hit the positive - the semantics of
         ``random.sample(range(I), k)``, ``Dataset.py:107-109``; more than ``SAMPLE_MAX`` of them - a pool of candidates for hard negatives - from
         ``ihg_sample_pool``, the same stream continued).  Yields the 8-tuple of ``collate_fn`` (positives then negatives;
-        users, queries, items, flags) with no host -> device copy and no host-side sampling per step.
+        users, queries, items, flags) with no host -> device copy and no host-side sampling per step.  Under ``filter_negatives`` the negatives
+        come from ``ihg_sample_pool_excluding`` for every count: the same stream under the same keys with the items of the positive's user
+        (``user_item_lists_on``) deleted; permutation, positives and layout are the unflagged epoch's.
 
         With ``nonrand_neg_sample_size`` > 0 a batch is ONE launch, ``ihg_device_batch``: it gathers the positives, draws every
         positive's logged negatives from ``logged_negative_lists`` by the rule of ``__getitem__`` (``Dataset.py:110-119``) and its
@@ -345,6 +378,12 @@ class GraphDataset(Dataset):
                 # (a corpus without logged negatives: one unread int32, since an empty tensor has no address to pass)
                 self._neg_device = tuple(torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(dev) for a in self.logged_negative_lists)
             pair_of_edge, neg_ptr, neg_items = (ctypes.c_void_p(t.data_ptr()) for t in self._neg_device)
+        filtered = self.filter_negatives
+        if filtered:
+            from . import ops
+            if k + self.max_user_items > self.item_count:
+                raise ValueError(f'filter_negatives: a user has {self.max_user_items} of {self.item_count} items, which leaves fewer than {k} negatives to draw')
+            user_lists = self.user_item_lists_on(dev)
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed * 1_000_003 + epoch)
         order = torch.randperm(len(self), device=dev, generator=gen)[rank::world_size]
@@ -376,10 +415,14 @@ class GraphDataset(Dataset):
             pos = self._pos_device[order[lo:hi]]
             lo = hi
             n = int(pos.shape[0])
-            neg_items = torch.empty(n, k, dtype=torch.int64, device=dev)
-            # (beyond SAMPLE_MAX draws - a pool of candidates, --hard_negatives - the same stream from ihg_sample_pool; up to SAMPLE_MAX the launch batches always had)
-            draw, name = (lib.ihg_sample_pool, 'ihg_sample_pool') if k > self.SAMPLE_MAX else (lib.ihg_sample_negatives, 'ihg_sample_negatives')
-            _lib.check(draw(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, ctypes.c_void_p(neg_items.data_ptr()), stream), name)
+            if filtered:
+                # the same stream under the same keys, without what the positive's user has bought: one kernel for every k (ihg_sample_pool_excluding)
+                neg_items = ops.sample_pool_excluding(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, pos[:, 0], user_lists, self.max_user_items, device=dev)
+            else:
+                neg_items = torch.empty(n, k, dtype=torch.int64, device=dev)
+                # (beyond SAMPLE_MAX draws - a pool of candidates, --hard_negatives - the same stream from ihg_sample_pool; up to SAMPLE_MAX the launch batches always had)
+                draw, name = (lib.ihg_sample_pool, 'ihg_sample_pool') if k > self.SAMPLE_MAX else (lib.ihg_sample_negatives, 'ihg_sample_negatives')
+                _lib.check(draw(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, ctypes.c_void_p(neg_items.data_ptr()), stream), name)
             ones = torch.ones(n, dtype=torch.int64, device=dev)
             yield (pos[:, 0], pos[:, 1], pos[:, 2], ones, pos[:, 0].repeat_interleave(k), pos[:, 1].repeat_interleave(k),
                    neg_items.reshape(-1), torch.zeros(n * k, dtype=torch.int64, device=dev))

@@ -110,6 +110,10 @@ _FLAGS = (
     # not in the reference, whose negatives are uniform draws (and a pair's logged ones): dynamic negative sampling
     ('hard_negatives', ('--hard_negatives',), int, 0, 'hard negatives: draw a pool of M random candidates per positive and train on the Gs.random_negative_sample_size of them that the '
                                                       'current model scores highest (Gs.Training.negative_pool; 0 = off; needs random_negative_sample_size < M <= 256, no --logged_negatives)'),
+    # not in the reference, whose negatives may be items the same user bought under another query, or the positive itself
+    ('filter_negatives', ('--filter_negatives',), 'flag', False, 'filtered negatives: draw every random negative outside the items the positive\'s user interacted with in training '
+                                                                 '(Gs.Training.filter_negatives; with or without --device_sampling and --hard_negatives; no --logged_negatives, '
+                                                                 'and negatives per positive + the longest user history must stay within half the catalogue)'),
     # not in the reference, whose step has no gradient clipping
     ('clip_grad_norm', ('--clip_grad_norm',), clip_norm, 0.0, 'clip every step\'s gradient to this global L2 norm, as torch.nn.utils.clip_grad_norm_ before Adam (Gs.Training.clip_grad_norm; '
                                                              '0 = off); the epoch log then shows the largest norm and the number of clipped steps'),

@@ -60,9 +60,10 @@ def apply_evaluation_settings(args) -> None:
 
 
 def apply_training_settings(args) -> None:
-    """``--loss`` -> ``Gs.Training.loss``, ``--hard_negatives M`` -> ``Gs.Training.negative_pool`` and ``--clip_grad_norm X`` -> ``Gs.Training.clip_grad_norm``, assigned both ways like the head above (not in the reference, which
+    """``--loss`` -> ``Gs.Training.loss``, ``--hard_negatives M`` -> ``Gs.Training.negative_pool``, ``--clip_grad_norm X`` -> ``Gs.Training.clip_grad_norm`` and
+    ``--filter_negatives`` -> ``Gs.Training.filter_negatives``, assigned both ways like the head above (not in the reference, which
     trains on ``nn.BCEWithLogitsLoss`` over uniform negatives only).  A pool needs ``Gs.random_negative_sample_size < M <= 256`` and no logged negatives (the pool is
-    random-only); called after ``apply_sampling_settings``."""
+    random-only), and so do filtered negatives (the filter is on the random draws; on both loaders, so that they agree); called after ``apply_sampling_settings``."""
     from . import _lib
     from .Helpers.ArgsParser import LOSSES, checked_clip_norm
     loss = getattr(args, 'loss', 'bce') or 'bce'
@@ -77,10 +78,33 @@ def apply_training_settings(args) -> None:
                              f'(Gs.random_negative_sample_size) and at most {_lib.POOL_MAX}')
         if int(getattr(args, 'logged_negatives', 0) or 0) > 0 or Gs.non_random_negative_sample_size > 0:
             raise ValueError('--hard_negatives draws its pool from the catalogue only: it does not go with --logged_negatives (Gs.non_random_negative_sample_size > 0)')
+    filtered = bool(getattr(args, 'filter_negatives', False))
+    if filtered and (int(getattr(args, 'logged_negatives', 0) or 0) > 0 or Gs.non_random_negative_sample_size > 0):
+        raise ValueError('--filter_negatives filters the random draws only: it does not go with --logged_negatives (Gs.non_random_negative_sample_size > 0) yet, '
+                         'with or without --device_sampling')
     clip = checked_clip_norm(getattr(args, 'clip_grad_norm', 0.0) or 0.0)      # (a caller that builds its own args: the parser's check)
     Gs.Training.loss = loss
     Gs.Training.negative_pool = pool
+    Gs.Training.filter_negatives = filtered
     Gs.Training.clip_grad_norm = clip
+
+
+def own_item_share(dataset) -> float:
+    """The share of uniform draws that would have been an item of their own user: ``sum_u deg_u |seen_u| / (E I)`` with ``deg_u`` the positives of user ``u``, ``seen_u``
+    its run of ``user_item_lists``, ``E`` the positives and ``I`` the catalogue - what ``--filter_negatives`` removes.  Host arithmetic on ``pos_triples`` and the CSR."""
+    import numpy as np
+    ptr, _ = dataset.user_item_lists
+    degree = np.bincount(dataset.pos_triples[:, 0], minlength=dataset.user_count)[:dataset.user_count]
+    positives = max(len(dataset), 1)
+    return float((degree * np.diff(ptr)).sum()) / (positives * max(dataset.item_count, 1))
+
+
+def check_filtered_negatives(dataset, per_positive: int) -> None:
+    """``--filter_negatives`` on this dataset: the driver's policy is that the negatives of a positive and the longest user history together stay within half the catalogue,
+    so that a draw costs at most two attempts per item on average (the entry point itself only needs a solution to exist)."""
+    if per_positive + dataset.max_user_items > dataset.item_count // 2:
+        raise ValueError(f'--filter_negatives: {per_positive} negatives per positive + {dataset.max_user_items} items of the user with the longest history exceed half the '
+                         f'catalogue ({dataset.item_count} items): the filtered draw would spend most of its attempts on rejections; train without the flag')
 
 
 def apply_sampling_settings(args) -> None:
@@ -109,6 +133,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise NotImplementedError('--model Srrl trains its PS half on the BCE, as the reference does: --loss bpr / softmax have not been built for it')
     if int(getattr(args, 'hard_negatives', 0) or 0) > 0:
         raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --hard_negatives has not been built for it')
+    if getattr(args, 'filter_negatives', False):
+        raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --filter_negatives has not been built for it')
     if getattr(args, 'filter_seen', False):
         raise NotImplementedError('--model Srrl ranks the whole catalogue: --filter_seen has not been built for its scoring kernels')
     if int(getattr(args, 'eval_candidates', 0) or 0) > 0:
@@ -197,7 +223,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
     say(f'device {device} | ranks {world} | batch {Gs.batch_size} | lr {Gs.learning_rate} | emb {Gs.embedding_size} | '
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}' +
         (f' | hard negatives: the best {Gs.random_negative_sample_size} of a pool of {pool}' if pool else '') +
-        (f' | clip grad norm {Gs.Training.clip_grad_norm:g}' if Gs.Training.clip_grad_norm else ''))
+        (f' | clip grad norm {Gs.Training.clip_grad_norm:g}' if Gs.Training.clip_grad_norm else '') +
+        (' | negatives filtered: outside the user\'s training items' if Gs.Training.filter_negatives else ''))
     if pool:
         from . import ops
         if 3 * Gs.batch_size * (1 + pool) > ops.SCATTER_CHUNK_ROWS:
@@ -219,7 +246,11 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         graph_type=Pps2DGraph if layer_type in (GCNLayer, GATLayer) else PpsHyperGraph,
         random_negative_sample_size=pool or Gs.random_negative_sample_size,      # (a pool: the loaders draw M candidates per positive, the step keeps the best of them)
         non_random_negative_sample_size=Gs.non_random_negative_sample_size,
-        device=device)
+        device=device, filter_negatives=Gs.Training.filter_negatives)
+    if Gs.Training.filter_negatives:
+        check_filtered_negatives(dataset_train, per_positive)
+        say(f'filtered negatives: drawn outside the user\'s training items (longest history {dataset_train.max_user_items} items; '
+            f'{100 * own_item_share(dataset_train):.4f} % of uniform draws would have been an item of their own user)')
     if args.device_sampling:
         from .Dataset import DeviceBatchLoader
         dataloader_train = DeviceBatchLoader(dataset_train, Gs.batch_size, rank, world)

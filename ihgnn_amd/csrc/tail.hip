@@ -766,6 +766,50 @@ __global__ __launch_bounds__(kWave) void sample_pool_kernel(uint64_t seed, uint6
     }
 }
 
+// sample_pool_kernel with a per-row list of values that are never accepted (ihg_sample_pool_excluding): the same wave per row, the same chunks of 64 attempts.  A lane's
+// value is fresh iff it is not on the row's list (a binary search over the sorted int32 run, every lane for its own value), not in the accepted list and not held by an
+// EARLIER lane of the chunk.  An earlier lane with the same value is accepted, a repeat of an accepted value, or itself on the list - and then so is this lane's value,
+// which its own search has found: the sequential rule again.  With an empty list the search finds nothing and this is sample_pool_kernel to the bit.  A row whose list id
+// lies outside [0, n_lists) has an empty list, and list_ptr is not read for it.  The loop ends because the entry point has been promised m + (longest list) <= n_items.
+__global__ __launch_bounds__(kWave) void sample_pool_excluding_kernel(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int m,
+                                                                      const int64_t* __restrict__ list_of_row, int64_t n_lists, const int64_t* __restrict__ list_ptr,
+                                                                      const int32_t* __restrict__ list_items, int64_t* __restrict__ out) {
+    __shared__ int64_t accepted[kPoolDraws];
+    __shared__ int64_t chunk[kWave];
+    const int lane = threadIdx.x;
+    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const uint64_t key = sample_row_key(seed, counter, row);
+        const int64_t which = list_of_row[row];
+        const bool listed_row = which >= 0 && which < n_lists;
+        const int64_t first = listed_row ? list_ptr[which] : 0;
+        const int64_t len = listed_row ? list_ptr[which + 1] - first : 0;
+        const int32_t* const list = list_items + first;                  // list[0 .. len): ascending, distinct
+        int count = 0;                                                   // accepted so far: the same in every lane (it follows from ballots)
+        for (uint64_t base = 0; count < m; base += kWave) {
+            const uint64_t r = mix64(key + (base + lane) * 0x2545F4914F6CDD1Dull);
+            const int64_t value = static_cast<int64_t>(__umul64hi(r, static_cast<uint64_t>(n_items)));
+            chunk[lane] = value;
+            __syncthreads();                                             // (one wave: the chunk, and the list as the last round left it, are visible)
+            int64_t lo = 0, hi = len;                                    // the first entry >= value
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (static_cast<int64_t>(list[mid]) < value) lo = mid + 1; else hi = mid;
+            }
+            bool fresh = !(lo < len && static_cast<int64_t>(list[lo]) == value);
+            for (int j = 0; j < count; ++j) fresh = fresh && accepted[j] != value;
+            for (int j = 0; j < kWave; ++j) fresh = fresh && (j >= lane || chunk[j] != value);
+            const unsigned long long mask = __ballot(fresh);
+            const int slot = count + __popcll(mask & ((1ull << lane) - 1ull));
+            if (fresh && slot < m) {
+                accepted[slot] = value;
+                out[row * m + slot] = value;
+            }
+            count += __popcll(mask);
+            __syncthreads();
+        }
+    }
+}
+
 // One thread per positive writes its column of the pack and the k = k_rand + k_logged columns of its negatives (header: ihg_device_batch).
 __global__ __launch_bounds__(kBlockThreads) void device_batch_kernel(uint64_t seed, uint64_t counter, const int64_t* __restrict__ pos_triples,
                                                                      const int64_t* __restrict__ edge_ids, int64_t n, const int32_t* __restrict__ pair_of_edge,
@@ -831,6 +875,24 @@ int ihg_sample_pool(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_i
     const int grid = static_cast<int>(std::min<int64_t>(n_rows, static_cast<int64_t>(kMaxBlocks) * kWavesPerBlock));
     hipLaunchKernelGGL(sample_pool_kernel, dim3(grid), dim3(kWave), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, static_cast<int>(m), out);
     return check_launch("ihg_sample_pool");
+}
+
+int ihg_sample_pool_excluding(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, const int64_t* list_of_row, int64_t n_lists,
+                              const int64_t* list_ptr, const int32_t* list_items, int64_t max_list_len, int64_t* out, ihg_stream_t stream) {
+    if (n_rows < 0 || n_items <= 0 || m < 1 || m > kPoolDraws || m > n_items)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_excluding: need 1 <= m <= min(%d, n_items), got m = %d and n_items = %lld", kPoolDraws, m, (long long)n_items);
+    if (n_lists < 1 || max_list_len < 0)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_excluding: need n_lists >= 1 and max_list_len >= 0, got n_lists = %lld and max_list_len = %lld", (long long)n_lists,
+                    (long long)max_list_len);
+    if (max_list_len > n_items - m)                                      // (the row with the longest list would have fewer than m values to find: its loop would not end)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_excluding: need m + max_list_len <= n_items, got m = %d, max_list_len = %lld and n_items = %lld", m,
+                    (long long)max_list_len, (long long)n_items);
+    if (n_rows == 0) return IHG_OK;
+    if (list_of_row == nullptr || list_ptr == nullptr || list_items == nullptr || out == nullptr) return fail(IHG_ERR_INVALID, "ihg_sample_pool_excluding: null pointer");
+    const int grid = static_cast<int>(std::min<int64_t>(n_rows, static_cast<int64_t>(kMaxBlocks) * kWavesPerBlock));
+    hipLaunchKernelGGL(sample_pool_excluding_kernel, dim3(grid), dim3(kWave), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, static_cast<int>(m),
+                       list_of_row, n_lists, list_ptr, list_items, out);
+    return check_launch("ihg_sample_pool_excluding");
 }
 
 int ihg_device_batch(uint64_t seed, uint64_t counter, const int64_t* pos_triples, const int64_t* edge_ids, int64_t n, const int32_t* pair_of_edge,

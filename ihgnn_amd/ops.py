@@ -2349,6 +2349,38 @@ def sample_pool(seed: int, counter: int, n_rows: int, n_items: int, m: int, devi
     return out
 
 
+def sample_pool_excluding(seed: int, counter: int, n_rows: int, n_items: int, m: int, rows: Tensor, lists: Tuple[Tensor, Tensor], max_list_len: int,
+                          device=None) -> Tensor:
+    """``sample_pool`` without the items of a per-row list (``ihg_sample_pool_excluding``): ``[n_rows, m]`` int64, row ``r`` being row ``r`` of ``sample_pool``'s stream
+    with the values of list ``rows[r]`` deleted.  ``lists = (ptr int64 [R + 1], items int32)`` as ``exclusion_lists`` returns them (every run strictly ascending), on the
+    device; ``rows`` int64 ``[n_rows]`` names each row's run, a value outside ``[0, R)`` meaning none.  ``max_list_len`` is the longest run, known on the host (the
+    launch never reads it back): ``m + max_list_len <= n_items`` is what lets every row find its ``m`` values.  One kernel for every ``1 <= m <= 256``."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    ptr, ids = lists
+    n_rows = int(n_rows)
+    operands = (('rows', rows, torch.int64), ('lists[0]', ptr, torch.int64), ('lists[1]', ids, torch.int32))
+    for name, t, dtype in operands:
+        if t.dtype != dtype or t.dim() != 1:
+            raise TypeError(f'sample_pool_excluding: {name} must be a 1-D {dtype} tensor, got {tuple(t.shape)} {t.dtype}')
+    for name, t, _ in operands:
+        _gpu(t, f'sample_pool_excluding: {name}')
+        if device.index is not None and t.device.index != device.index:
+            raise ValueError(f'sample_pool_excluding: {name} is on {t.device}, the draw on {device}')
+    if int(rows.shape[0]) != max(n_rows, 0):
+        raise ValueError(f'sample_pool_excluding: {n_rows} rows but rows of {tuple(rows.shape)}')
+    if int(ptr.shape[0]) < 1:
+        raise ValueError('sample_pool_excluding: lists[0] holds at least the leading 0')
+    rows, ptr, ids = rows.contiguous(), ptr.contiguous(), ids.contiguous()
+    if not ids.numel():
+        ids = ids.new_zeros(1)                                                  # (an empty tensor has no address; no offset reaches this entry)
+    out = torch.empty(max(n_rows, 0), max(int(m), 0), dtype=torch.int64, device=device)
+    mask = (1 << 64) - 1
+    with profiler.kernel('sample_pool_excluding', n_rows, int(m)):
+        _lib.check(_lib.load().ihg_sample_pool_excluding(int(seed) & mask, int(counter) & mask, n_rows, int(n_items), int(m), _ptr(rows), int(ptr.shape[0]) - 1, _ptr(ptr),
+                                                         _ptr(ids), int(max_list_len), _ptr(out), _stream()), 'ihg_sample_pool_excluding')
+    return out
+
+
 def hem_ranking_loss(layers, rows: Tensor, items: Tensor, positives: int, kind, bias: Tensor, lam: float, item_row_offset: int,
                      holder: Optional[TailGradients] = None, rows_upper: Optional[Tensor] = None, cosine: bool = False) -> Tensor:
     """``ranking_loss(hem_score(...), positives, kind)`` as one differentiable op (scalar): ``hem_bce_loss`` with ``ihg_ranking_loss`` as its loss launch and no labels.

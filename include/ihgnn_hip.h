@@ -574,6 +574,18 @@ int ihg_sample_negatives(uint64_t seed, uint64_t counter, int64_t n_rows, int64_
  * of a call with m are what a call with c gives, and for c <= 16 they are ihg_sample_negatives' bits.  IHG_ERR_INVALID (m out of range, a null `out` with rows to write)
  * has launched nothing; n_rows == 0 returns IHG_OK. */
 int ihg_sample_pool(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, int64_t* out, ihg_stream_t stream);
+/* The pool draw with a per-row list of values that are never drawn (negatives outside what the row's user has bought): out [n_rows, m] int64.  Lists are a CSR in the
+ * layout of per-search exclusion lists: list l = list_items[list_ptr[l] .. list_ptr[l + 1]) (list_ptr int64 [n_lists + 1], list_items int32), every list ascending and
+ * distinct, values in [0, n_items).  Row r has list l = list_of_row[r] (int64 [n_rows]); an l outside [0, n_lists) means an empty list, and list_ptr is not read for it.
+ * Sequential definition: row r walks ihg_sample_negatives' stream - key(seed, counter, r), attempts counted from 0, attempt a yields
+ * umulhi(mix64(key + a * 0x2545F4914F6CDD1D), n_items); a value is accepted iff it is not in the row's list and differs from every value accepted before it; out[r][0..m)
+ * are the first m accepted values, in attempt order.  So row r is row r of the unfiltered stream with the listed values deleted; with all lists empty the output is
+ * ihg_sample_pool's bit for bit (for m <= 16: ihg_sample_negatives'); the first c columns of a call with m are what a call with c gives.  One kernel serves every m.
+ * max_list_len is the caller's promise that no list is longer, computed on the host from its copy of list_ptr and never read back from the device: the draw ends
+ * because m + max_list_len <= n_items leaves every row m values to find.  IHG_ERR_INVALID unless 1 <= m <= min(256, n_items), n_lists >= 1, max_list_len >= 0 and
+ * m + max_list_len <= n_items, and on a null pointer with rows to write: it has launched and written nothing.  n_rows == 0 returns IHG_OK and launches nothing. */
+int ihg_sample_pool_excluding(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, const int64_t* list_of_row, int64_t n_lists,
+                              const int64_t* list_ptr, const int32_t* list_items, int64_t max_list_len, int64_t* out, ihg_stream_t stream);
 
 /* DEVICE: one whole training batch in one launch, logged negatives included.  Replaces, for the n positives `edge_ids` of pos_triples [E, 3]
  * (user, query, item), GraphDataset.__getitem__ + collate_fn (Dataset.py:107-119, 282-291).  pack is the [4, n (1 + k)] array collate_fn builds, k = k_rand + k_logged,
