@@ -7,6 +7,7 @@ list-of-namedtuples view is built only if somebody asks for ``pos_interactions``
 """
 from __future__ import annotations
 
+import bisect
 import os
 import random
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
@@ -75,13 +76,14 @@ class GraphDataset(Dataset):
     SAMPLE_MAX = 16                    # negatives per positive the device sampler draws at most (kSampleMax of csrc/tail.hip)
 
     def __init__(self, fn_graph_info: str, fn_queries_multihot: str, fn_train_data: str, graph_type: type,
-                 random_negative_sample_size: int, non_random_negative_sample_size: int, device: torch.device, filter_negatives: bool = False):
+                 random_negative_sample_size: int, non_random_negative_sample_size: int, device: torch.device, filter_negatives: bool = False,
+                 popularity_power: float = 0.0):
         super().__init__()
         counts = read_graph_info(fn_graph_info)                      # the three input files go through the native readers
         bag_words, bag_offsets = read_query_bags(fn_queries_multihot)
         n_logs, triples, negatives, rows = parse_search_logs(fn_train_data, with_rows=True)
         self._setup(counts, bag_words, bag_offsets, triples, graph_type,
-                    random_negative_sample_size, non_random_negative_sample_size, device, filter_negatives)
+                    random_negative_sample_size, non_random_negative_sample_size, device, filter_negatives, popularity_power)
         self.pos_log = rows
         self._fn_train_data = fn_train_data
         self._search_logs = None
@@ -100,16 +102,18 @@ class GraphDataset(Dataset):
                     bag_words: np.ndarray, bag_offsets: np.ndarray, triples: np.ndarray,
                     graph_type: type = PpsHyperGraph, random_negative_sample_size: int = 10,
                     non_random_negative_sample_size: int = 0, device: torch.device = torch.device('cuda:0'),
-                    pos_log: Optional[np.ndarray] = None, neg_triples: Optional[np.ndarray] = None, filter_negatives: bool = False) -> 'GraphDataset':
+                    pos_log: Optional[np.ndarray] = None, neg_triples: Optional[np.ndarray] = None, filter_negatives: bool = False,
+                    popularity_power: float = 0.0) -> 'GraphDataset':
         """In-memory construction (synthetic corpora): ``bag_words`` are 0-based word ids, ``triples`` 0-based per type;
         ``pos_log[e]`` = the search log hyperedge ``e`` came from (default: one log per positive); ``neg_triples`` ``[M, 3]`` = the logged
         negatives (user, query, item), array order standing for file order (default: none); ``filter_negatives``: random negatives are drawn outside what the
-        positive's user interacted with in training (``user_item_lists``; default off: uniform over the catalogue)."""
+        positive's user interacted with in training (``user_item_lists``; default off: uniform over the catalogue); ``popularity_power`` alpha in (0, 1]: random negatives
+        fall on an item in proportion to its training frequency raised to alpha (``item_sampling_weights``; default 0 = off: uniform)."""
         self = cls.__new__(cls)
         Dataset.__init__(self)
         self._setup([user_count, query_count, item_count, vocab_size], np.asarray(bag_words, np.int64),
                     np.asarray(bag_offsets, np.int64), np.asarray(triples, np.int64).reshape(-1, 3), graph_type,
-                    random_negative_sample_size, non_random_negative_sample_size, device, filter_negatives)
+                    random_negative_sample_size, non_random_negative_sample_size, device, filter_negatives, popularity_power)
         if pos_log is not None:
             self.pos_log = np.ascontiguousarray(pos_log, dtype=np.int64)
         self._fn_train_data = None
@@ -120,7 +124,8 @@ class GraphDataset(Dataset):
         return self
 
     def _setup(self, counts: Sequence[int], bag_words: np.ndarray, bag_offsets: np.ndarray, triples: np.ndarray,
-               graph_type: type, rand_neg: int, nonrand_neg: int, device: torch.device, filter_negatives: bool = False) -> None:
+               graph_type: type, rand_neg: int, nonrand_neg: int, device: torch.device, filter_negatives: bool = False,
+               popularity_power: float = 0.0) -> None:
         if graph_type not in (Pps2DGraph, PpsHyperGraph, PpsLogHyperGraph):
             raise AssertionError(f'unsupported graph type: {graph_type}')
         GraphDataset.device = device
@@ -131,6 +136,12 @@ class GraphDataset(Dataset):
         self.filter_negatives = bool(filter_negatives)
         if self.filter_negatives and nonrand_neg:
             raise ValueError('filter_negatives draws random negatives only: it does not go with logged negatives (non_random_negative_sample_size > 0)')
+        self.popularity_power = float(popularity_power)
+        if not 0.0 <= self.popularity_power <= 1.0:                             # (also refuses a NaN)
+            raise ValueError(f'popularity_power must be in (0, 1], or 0 for uniform negatives, got {popularity_power}')
+        if self.popularity_power and nonrand_neg:
+            raise ValueError('popularity_power weights the random negatives of the pool draw only: it does not go with logged negatives '
+                             '(non_random_negative_sample_size > 0), whose random part is uniform')
 
         self.user_count, self.query_count, self.item_count, self.vocab_size = (int(c) for c in counts)
         self.node_count = self.user_count + self.query_count + self.item_count
@@ -232,6 +243,37 @@ class GraphDataset(Dataset):
             seen = sets[user] = frozenset(items[ptr[user]:ptr[user + 1]].tolist()) if 0 <= user < self.user_count else frozenset()
         return seen
 
+    @property
+    def item_sampling_weights(self) -> np.ndarray:
+        """The integer weights of the popularity-weighted draw, int64 ``[I]``: ``w_i = max(1, rint(2^32 ((c_i + 1) / (c_max + 1))^alpha))`` in float64, ``c_i`` the rows
+        of ``pos_triples`` whose item is ``i`` and alpha ``popularity_power`` (which must be > 0).  The ``+ 1`` keeps a never-bought item drawable; the most frequent item
+        has weight ``2^32``, so the sum is at most ``I 2^32``.  Built once, on the host."""
+        if not self.popularity_power:
+            raise ValueError('item_sampling_weights: the dataset was built with popularity_power = 0 (uniform negatives)')
+        if getattr(self, '_item_weights', None) is None:
+            counts = np.bincount(self.pos_triples[:, 2], minlength=self.item_count)[:self.item_count].astype(np.float64)
+            share = (counts + 1.0) / (counts.max(initial=0.0) + 1.0)
+            self._item_weights = np.maximum(1, np.rint(2.0 ** 32 * share ** self.popularity_power)).astype(np.int64)
+        return self._item_weights
+
+    @property
+    def item_sampling_cum(self) -> Tuple[List[int], int]:
+        """``(cum, total)`` on the host, ``cum`` a list of ``I + 1`` Python ints (what ``bisect`` reads on the ``DataLoader`` path): the running sum of
+        ``item_sampling_weights``, ``cum[0] = 0``, ``cum[I] = total``."""
+        if getattr(self, '_item_cum', None) is None:
+            cum = [0] + np.cumsum(self.item_sampling_weights).tolist()
+            self._item_cum = (cum, cum[-1])
+        return self._item_cum
+
+    def item_sampling_table_on(self, device) -> Tuple[Tensor, int]:
+        """``ops.item_sampling_table(item_sampling_weights)`` on ``device``, built and copied there once."""
+        from . import ops
+        device = torch.device(device)
+        cached = getattr(self, '_item_table_device', None)
+        if cached is None or cached[0].device.type != device.type or (device.index is not None and cached[0].device.index != device.index):
+            cached = self._item_table_device = ops.item_sampling_table(self.item_sampling_weights, device=device)
+        return cached
+
     def user_item_lists_on(self, device) -> Tuple[Tensor, Tensor]:
         """``user_item_lists`` as tensors on ``device``, copied there once."""
         device = torch.device(device)
@@ -306,6 +348,18 @@ class GraphDataset(Dataset):
         items per call and may hit the positive; logged negatives of the (user, query) pair come first if requested.  Under ``filter_negatives``
         (random negatives only) the items are ``random.randrange`` draws, kept while distinct and outside the user's training items."""
         u, q, i = (int(x) for x in self.pos_triples[index])
+        if self.popularity_power:
+            # a threshold below the sum of the weights, the item whose run of the running sum holds it: kept while distinct (and, filtered, outside the user's items)
+            seen, k = (self.user_item_set(u) if self.filter_negatives else frozenset()), self.rand_neg_sample_size
+            if k + len(seen) > self.item_count:
+                raise ValueError(f'popularity_power: user {u} has {len(seen)} of {self.item_count} items, which leaves fewer than {k} to draw')
+            cum, total = self.item_sampling_cum
+            drawn: List[int] = []
+            while len(drawn) < k:
+                item = bisect.bisect_right(cum, random.randrange(total)) - 1
+                if item not in seen and item not in drawn:
+                    drawn.append(item)
+            return (u, q, i, 1), drawn
         if self.filter_negatives:
             seen, k = self.user_item_set(u), self.rand_neg_sample_size
             if k + len(seen) > self.item_count:
@@ -354,7 +408,9 @@ class GraphDataset(Dataset):
         ``ihg_sample_pool``, the same stream continued).  Yields the 8-tuple of ``collate_fn`` (positives then negatives;
         users, queries, items, flags) with no host -> device copy and no host-side sampling per step.  Under ``filter_negatives`` the negatives
         come from ``ihg_sample_pool_excluding`` for every count: the same stream under the same keys with the items of the positive's user
-        (``user_item_lists_on``) deleted; permutation, positives and layout are the unflagged epoch's.
+        (``user_item_lists_on``) deleted; permutation, positives and layout are the unflagged epoch's.  With ``popularity_power`` > 0 they come from
+        ``ihg_sample_pool_weighted`` for every count, under the same keys again: every attempt falls on an item in proportion to ``item_sampling_weights``
+        (``item_sampling_table_on``), with the user's items deleted when ``filter_negatives`` is on as well.
 
         With ``nonrand_neg_sample_size`` > 0 a batch is ONE launch, ``ihg_device_batch``: it gathers the positives, draws every
         positive's logged negatives from ``logged_negative_lists`` by the rule of ``__getitem__`` (``Dataset.py:110-119``) and its
@@ -384,6 +440,12 @@ class GraphDataset(Dataset):
             if k + self.max_user_items > self.item_count:
                 raise ValueError(f'filter_negatives: a user has {self.max_user_items} of {self.item_count} items, which leaves fewer than {k} negatives to draw')
             user_lists = self.user_item_lists_on(dev)
+        weighted = bool(self.popularity_power)
+        if weighted:
+            from . import ops
+            if k > self.item_count:
+                raise ValueError(f'popularity_power: {k} distinct negatives per positive from a catalogue of {self.item_count} items')
+            table = self.item_sampling_table_on(dev)
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed * 1_000_003 + epoch)
         order = torch.randperm(len(self), device=dev, generator=gen)[rank::world_size]
@@ -415,7 +477,11 @@ class GraphDataset(Dataset):
             pos = self._pos_device[order[lo:hi]]
             lo = hi
             n = int(pos.shape[0])
-            if filtered:
+            if weighted:
+                # the same keys, every attempt falling on an item in proportion to its weight; filtered as below when that is on too (ihg_sample_pool_weighted, every k)
+                neg_items = ops.sample_pool_weighted(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, table, pos[:, 0] if filtered else None,
+                                                     user_lists if filtered else None, self.max_user_items if filtered else 0, device=dev)
+            elif filtered:
                 # the same stream under the same keys, without what the positive's user has bought: one kernel for every k (ihg_sample_pool_excluding)
                 neg_items = ops.sample_pool_excluding(seed * 7919 + rank, (epoch << 32) + b, n, self.item_count, k, pos[:, 0], user_lists, self.max_user_items, device=dev)
             else:

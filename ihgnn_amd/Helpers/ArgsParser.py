@@ -44,6 +44,29 @@ def clip_norm(text: str) -> float:
         raise argparse.ArgumentTypeError(str(refused))
 
 
+POPULARITY_POWER_DEFAULT = 0.75                          # a bare --popularity_negatives: the exponent of word2vec's and HEM's noise distribution
+
+
+def checked_popularity_power(value) -> float:
+    """The exponent of ``--popularity_negatives`` / ``Gs.Training.popularity_power``: 0 (off: uniform negatives) or a float in (0, 1], or a ``ValueError`` - the one check
+    the parser and the driver's settings share."""
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f'--popularity_negatives takes a number, got {value!r}')
+    if not 0.0 <= value <= 1.0:                             # (also refuses a NaN)
+        raise ValueError(f'--popularity_negatives takes an exponent in (0, 1] (0 = off: uniform negatives; a bare flag = {POPULARITY_POWER_DEFAULT}), got {value}')
+    return value
+
+
+def popularity_power(text: str) -> float:
+    """``checked_popularity_power`` as an argparse type."""
+    try:
+        return checked_popularity_power(text)
+    except ValueError as refused:
+        raise argparse.ArgumentTypeError(str(refused))
+
+
 def checked_candidate_count(value, item_count=None) -> int:
     """The N of ``--eval_candidates`` / ``Gs.Evaluation.sampled_candidates``: an integer >= 0 (0 = off) and, once the catalogue is known, below its size - or a
     ``ValueError``; the one check the parser and the driver share."""
@@ -66,7 +89,7 @@ def candidate_count(text: str) -> int:
         raise argparse.ArgumentTypeError(str(refused))
 
 
-# (dest, flags, kind, default, help); kind is a type or 'flag'
+# (dest, flags, kind, default, help); kind is a type, 'flag', 'optional' (auto | on | off) or ('optional', type, the bare flag's value)
 _FLAGS = (
     ('checkpoint', ('--checkpoint', '--cp'), str, '', 'checkpoint file inside the result dir, or "latest"; empty = fresh start'),
     ('storecheckpoint', ('--storecheckpoint', '--scp', '-c'), 'flag', False, 'write a checkpoint when the schedule says so'),
@@ -114,6 +137,10 @@ _FLAGS = (
     ('filter_negatives', ('--filter_negatives',), 'flag', False, 'filtered negatives: draw every random negative outside the items the positive\'s user interacted with in training '
                                                                  '(Gs.Training.filter_negatives; with or without --device_sampling and --hard_negatives; no --logged_negatives, '
                                                                  'and negatives per positive + the longest user history must stay within half the catalogue)'),
+    # not in the reference, whose negatives are uniform over the catalogue (HEM itself, like word2vec, draws its noise from the item frequency raised to 3/4)
+    ('popularity_negatives', ('--popularity_negatives',), ('optional', popularity_power, POPULARITY_POWER_DEFAULT), 0.0,
+     'popularity-weighted negatives: draw every random negative in proportion to its item\'s training frequency raised to A (Gs.Training.popularity_power; A in (0, 1], a bare '
+     'flag = 0.75, 0 = off: uniform; with or without --device_sampling, --hard_negatives and --filter_negatives; no --logged_negatives, no --model Srrl; no logQ correction)'),
     # not in the reference, whose step has no gradient clipping
     ('clip_grad_norm', ('--clip_grad_norm',), clip_norm, 0.0, 'clip every step\'s gradient to this global L2 norm, as torch.nn.utils.clip_grad_norm_ before Adam (Gs.Training.clip_grad_norm; '
                                                              '0 = off); the epoch log then shows the largest norm and the number of clipped steps'),
@@ -140,6 +167,8 @@ def build_parser() -> argparse.ArgumentParser:
     for dest, flags, kind, default, text in _FLAGS:
         if kind == 'flag':
             parser.add_argument(*flags, dest=dest, action='store_true', default=default, help=text)
+        elif isinstance(kind, tuple):                        # ('optional', type, value of the bare flag)
+            parser.add_argument(*flags, dest=dest, nargs='?', type=kind[1], const=kind[2], default=default, metavar='A', help=text)
         elif kind == 'optional':
             parser.add_argument(*flags, dest=dest, nargs='?', const='on', default=default, choices=('auto', 'on', 'off'), help=text)
         elif dest in _CHOICES:

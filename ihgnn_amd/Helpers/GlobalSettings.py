@@ -47,6 +47,7 @@ class Gs:
         clip_grad_norm = 0.0             # not in the reference (whose step has no clipping): X > 0 (--clip_grad_norm X) scales every step's gradient so that its global L2 norm is at most X, as torch.nn.utils.clip_grad_norm_ does; 0 = off
         negative_pool = 0                # not in the reference: M > 0 (--hard_negatives M) draws a pool of M random candidates per positive and trains on the random_negative_sample_size of them that the model scores highest; 0 = off
         filter_negatives = False         # not in the reference (whose negatives are uniform over the catalogue): True (--filter_negatives) draws every random negative outside the items the positive's user interacted with in training, the positive itself included
+        popularity_power = 0.0           # not in the reference (whose negatives are uniform over the catalogue): A in (0, 1] (--popularity_negatives [A], a bare flag = 0.75) draws every random negative in proportion to its item's training frequency raised to A; 0 = off
 
     class Evaluation:
         extra_cutoffs = ()               # not in the reference (which reports @10 only): further cutoffs K in 11..128 (--cutoffs), HR / NDCG / MAP @K beside the @10 triple

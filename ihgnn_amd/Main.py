@@ -61,11 +61,12 @@ def apply_evaluation_settings(args) -> None:
 
 def apply_training_settings(args) -> None:
     """``--loss`` -> ``Gs.Training.loss``, ``--hard_negatives M`` -> ``Gs.Training.negative_pool``, ``--clip_grad_norm X`` -> ``Gs.Training.clip_grad_norm`` and
-    ``--filter_negatives`` -> ``Gs.Training.filter_negatives``, assigned both ways like the head above (not in the reference, which
+    ``--filter_negatives`` -> ``Gs.Training.filter_negatives`` and ``--popularity_negatives [A]`` -> ``Gs.Training.popularity_power``, assigned both ways like the head above (not in the reference, which
     trains on ``nn.BCEWithLogitsLoss`` over uniform negatives only).  A pool needs ``Gs.random_negative_sample_size < M <= 256`` and no logged negatives (the pool is
-    random-only), and so do filtered negatives (the filter is on the random draws; on both loaders, so that they agree); called after ``apply_sampling_settings``."""
+    random-only), and so do filtered negatives (the filter is on the random draws; on both loaders, so that they agree) and popularity-weighted ones (the random part of
+    a batch with logged negatives is not weighted); called after ``apply_sampling_settings``."""
     from . import _lib
-    from .Helpers.ArgsParser import LOSSES, checked_clip_norm
+    from .Helpers.ArgsParser import LOSSES, checked_clip_norm, checked_popularity_power
     loss = getattr(args, 'loss', 'bce') or 'bce'
     if loss not in LOSSES:
         raise ValueError(f'--loss: one of {", ".join(LOSSES)}, got {loss!r}')
@@ -82,10 +83,15 @@ def apply_training_settings(args) -> None:
     if filtered and (int(getattr(args, 'logged_negatives', 0) or 0) > 0 or Gs.non_random_negative_sample_size > 0):
         raise ValueError('--filter_negatives filters the random draws only: it does not go with --logged_negatives (Gs.non_random_negative_sample_size > 0) yet, '
                          'with or without --device_sampling')
+    power = checked_popularity_power(getattr(args, 'popularity_negatives', 0.0) or 0.0)      # (a caller that builds its own args: the parser's check)
+    if power and (int(getattr(args, 'logged_negatives', 0) or 0) > 0 or Gs.non_random_negative_sample_size > 0):
+        raise ValueError('--popularity_negatives weights the draws of the pool kernels only: it does not go with --logged_negatives (Gs.non_random_negative_sample_size > 0), '
+                         'whose random part is uniform, with or without --device_sampling')
     clip = checked_clip_norm(getattr(args, 'clip_grad_norm', 0.0) or 0.0)      # (a caller that builds its own args: the parser's check)
     Gs.Training.loss = loss
     Gs.Training.negative_pool = pool
     Gs.Training.filter_negatives = filtered
+    Gs.Training.popularity_power = power
     Gs.Training.clip_grad_norm = clip
 
 
@@ -105,6 +111,47 @@ def check_filtered_negatives(dataset, per_positive: int) -> None:
     if per_positive + dataset.max_user_items > dataset.item_count // 2:
         raise ValueError(f'--filter_negatives: {per_positive} negatives per positive + {dataset.max_user_items} items of the user with the longest history exceed half the '
                          f'catalogue ({dataset.item_count} items): the filtered draw would spend most of its attempts on rejections; train without the flag')
+
+
+def popularity_shares(dataset) -> dict:
+    """What the popularity-weighted draw does on this dataset, for the startup log: ``head_share`` = the share of weighted draws that fall on the most popular 1 % of items
+    (at least one item; a uniform draw: ``uniform_head_share``), ``own_item_share`` = the share of weighted draws that would be an item of their own user, ``sum_u deg_u
+    w(seen_u) / (E total)`` - the weighted counterpart of ``own_item_share``, what ``--filter_negatives`` removes.  Host arithmetic on the weights and the CSR."""
+    import numpy as np
+    weights = dataset.item_sampling_weights
+    total = float(weights.sum())
+    head = max(1, dataset.item_count // 100)
+    ptr, items = dataset.user_item_lists
+    degree = np.bincount(dataset.pos_triples[:, 0], minlength=dataset.user_count)[:dataset.user_count]
+    return dict(head_items=head, head_share=float(np.sort(weights)[-head:].sum()) / total, uniform_head_share=head / dataset.item_count,
+                own_item_share=float((degree * _list_masses(weights, ptr, items)).sum()) / (max(len(dataset), 1) * total))
+
+
+def _list_masses(weights, ptr, items):
+    """float64 ``[U]``: the sum of ``weights`` over every run of the CSR ``(ptr, items)``, 0 for an empty run (``np.add.reduceat`` over the non-empty ones)."""
+    import numpy as np
+    masses = np.zeros(len(ptr) - 1, np.float64)
+    filled = np.flatnonzero(np.diff(ptr) > 0)
+    if len(filled):
+        masses[filled] = np.add.reduceat(weights[items].astype(np.float64), ptr[filled])
+    return masses
+
+
+def check_popularity_negatives(dataset, per_positive: int) -> None:
+    """``--popularity_negatives`` on this dataset: the driver's policy is that the mass a row can reject stays within half of the weights' sum, so that a draw costs at most
+    two attempts per item on average (the entry point itself only needs ``m + max_list_len <= n_items``).  That mass is the sum of the ``per_positive`` heaviest weights -
+    the most a row's own accepted values can hold - plus, under ``filter_negatives``, the largest sum of weights over any one user's list."""
+    import numpy as np
+    weights = dataset.item_sampling_weights
+    total = int(weights.sum())
+    mass = int(np.sort(weights)[-min(int(per_positive), len(weights)):].sum())
+    told = f'the {per_positive} heaviest items'
+    if dataset.filter_negatives:
+        mass += int(_list_masses(weights, *dataset.user_item_lists).max(initial=0.0))
+        told += ' + the heaviest user history'
+    if 2 * mass > total:
+        raise ValueError(f'--popularity_negatives: {told} weigh {mass}, more than half of all weights ({total}, {dataset.item_count} items): the weighted draw would spend most '
+                         'of its attempts on rejections; use a smaller exponent, fewer negatives per positive, or train without the flag')
 
 
 def apply_sampling_settings(args) -> None:
@@ -135,6 +182,8 @@ def check_srrl_settings(args, world: int) -> None:
         raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --hard_negatives has not been built for it')
     if getattr(args, 'filter_negatives', False):
         raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --filter_negatives has not been built for it')
+    if float(getattr(args, 'popularity_negatives', 0.0) or 0.0) > 0:
+        raise NotImplementedError('--model Srrl trains on uniform negatives, as the reference does: --popularity_negatives has not been built for it')
     if getattr(args, 'filter_seen', False):
         raise NotImplementedError('--model Srrl ranks the whole catalogue: --filter_seen has not been built for its scoring kernels')
     if int(getattr(args, 'eval_candidates', 0) or 0) > 0:
@@ -224,7 +273,8 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         f'L2 {Gs.weight_decay} | negatives {Gs.random_negative_sample_size}/{Gs.non_random_negative_sample_size}' +
         (f' | hard negatives: the best {Gs.random_negative_sample_size} of a pool of {pool}' if pool else '') +
         (f' | clip grad norm {Gs.Training.clip_grad_norm:g}' if Gs.Training.clip_grad_norm else '') +
-        (' | negatives filtered: outside the user\'s training items' if Gs.Training.filter_negatives else ''))
+        (' | negatives filtered: outside the user\'s training items' if Gs.Training.filter_negatives else '') +
+        (f' | negatives weighted: item frequency ^ {Gs.Training.popularity_power:g}' if Gs.Training.popularity_power else ''))
     if pool:
         from . import ops
         if 3 * Gs.batch_size * (1 + pool) > ops.SCATTER_CHUNK_ROWS:
@@ -246,11 +296,20 @@ def main(argv: Optional[Sequence[str]] = None) -> MetricsCollection:
         graph_type=Pps2DGraph if layer_type in (GCNLayer, GATLayer) else PpsHyperGraph,
         random_negative_sample_size=pool or Gs.random_negative_sample_size,      # (a pool: the loaders draw M candidates per positive, the step keeps the best of them)
         non_random_negative_sample_size=Gs.non_random_negative_sample_size,
-        device=device, filter_negatives=Gs.Training.filter_negatives)
+        device=device, filter_negatives=Gs.Training.filter_negatives, popularity_power=Gs.Training.popularity_power)
     if Gs.Training.filter_negatives:
         check_filtered_negatives(dataset_train, per_positive)
         say(f'filtered negatives: drawn outside the user\'s training items (longest history {dataset_train.max_user_items} items; '
             f'{100 * own_item_share(dataset_train):.4f} % of uniform draws would have been an item of their own user)')
+    if Gs.Training.popularity_power:
+        check_popularity_negatives(dataset_train, per_positive)
+        shares = popularity_shares(dataset_train)
+        uniform_own = own_item_share(dataset_train)
+        say(f'popularity-weighted negatives: item frequency ^ {Gs.Training.popularity_power:g}, no logQ correction; {100 * shares["head_share"]:.2f} % of draws fall on the '
+            f'{shares["head_items"]} most popular items (1 % of the catalogue; uniform: {100 * shares["uniform_head_share"]:.2f} %); '
+            f'{100 * shares["own_item_share"]:.4f} % of weighted draws would be an item of their own user (uniform: {100 * uniform_own:.4f} %)' +
+            (': removed by --filter_negatives' if Gs.Training.filter_negatives else
+             ' - add --filter_negatives to draw outside the user\'s items' if shares['own_item_share'] > uniform_own else ''))
     if args.device_sampling:
         from .Dataset import DeviceBatchLoader
         dataloader_train = DeviceBatchLoader(dataset_train, Gs.batch_size, rank, world)

@@ -134,6 +134,8 @@ SIGNATURES = {
     'ihg_sample_pool': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     'ihg_sample_pool_excluding': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                                  c_void_p]),
+    'ihg_sample_pool_weighted': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                                c_void_p, c_void_p]),
     'ihg_device_batch': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                         c_void_p, c_void_p]),
     'ihg_score_topk_max_dim': (c_int32, []),

@@ -810,6 +810,57 @@ __global__ __launch_bounds__(kWave) void sample_pool_excluding_kernel(uint64_t s
     }
 }
 
+// sample_pool_excluding_kernel with a weighted value (ihg_sample_pool_weighted): the same wave per row, the same chunks of 64 attempts, the same freshness rule.  The one
+// new step: a lane's 64 random bits become a threshold t = umulhi(r, total) in [0, total), and its value is the one i with cum[i] <= t < cum[i + 1] - a binary search over
+// cum [n_items + 1] that keeps cum[lo] <= t < cum[hi] from (0, n_items) on, so that every index it reads lies in [0, n_items] whatever the table holds.  With cum[i] = i
+// the search returns t itself and this is sample_pool_excluding_kernel to the bit.  list_of_row == nullptr (n_lists == 0): no row has a list and no list pointer is read.
+// The loop ends because cum is strictly ascending (every item can be drawn) and the entry point has been promised m + (longest list) <= n_items.
+__global__ __launch_bounds__(kWave) void sample_pool_weighted_kernel(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int m,
+                                                                     const int64_t* __restrict__ cum, uint64_t total, const int64_t* __restrict__ list_of_row,
+                                                                     int64_t n_lists, const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ list_items,
+                                                                     int64_t* __restrict__ out) {
+    __shared__ int64_t accepted[kPoolDraws];
+    __shared__ int64_t chunk[kWave];
+    const int lane = threadIdx.x;
+    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const uint64_t key = sample_row_key(seed, counter, row);
+        const int64_t which = list_of_row != nullptr ? list_of_row[row] : -1;
+        const bool listed_row = which >= 0 && which < n_lists;
+        const int64_t first = listed_row ? list_ptr[which] : 0;
+        const int64_t len = listed_row ? list_ptr[which + 1] - first : 0;
+        const int32_t* const list = list_items + first;                  // list[0 .. len): ascending, distinct (never read when len == 0)
+        int count = 0;                                                   // accepted so far: the same in every lane (it follows from ballots)
+        for (uint64_t base = 0; count < m; base += kWave) {
+            const uint64_t r = mix64(key + (base + lane) * 0x2545F4914F6CDD1Dull);
+            const int64_t t = static_cast<int64_t>(__umul64hi(r, total));                        // < total < 2^63
+            int64_t below = 0, above = n_items;                          // cum[below] <= t < cum[above]
+            while (above - below > 1) {
+                const int64_t mid = (below + above) >> 1;
+                if (cum[mid] <= t) below = mid; else above = mid;
+            }
+            const int64_t value = below;
+            chunk[lane] = value;
+            __syncthreads();                                             // (one wave: the chunk, and the list as the last round left it, are visible)
+            int64_t lo = 0, hi = len;                                    // the first entry >= value
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (static_cast<int64_t>(list[mid]) < value) lo = mid + 1; else hi = mid;
+            }
+            bool fresh = !(lo < len && static_cast<int64_t>(list[lo]) == value);
+            for (int j = 0; j < count; ++j) fresh = fresh && accepted[j] != value;
+            for (int j = 0; j < kWave; ++j) fresh = fresh && (j >= lane || chunk[j] != value);
+            const unsigned long long mask = __ballot(fresh);
+            const int slot = count + __popcll(mask & ((1ull << lane) - 1ull));
+            if (fresh && slot < m) {
+                accepted[slot] = value;
+                out[row * m + slot] = value;
+            }
+            count += __popcll(mask);
+            __syncthreads();
+        }
+    }
+}
+
 // One thread per positive writes its column of the pack and the k = k_rand + k_logged columns of its negatives (header: ihg_device_batch).
 __global__ __launch_bounds__(kBlockThreads) void device_batch_kernel(uint64_t seed, uint64_t counter, const int64_t* __restrict__ pos_triples,
                                                                      const int64_t* __restrict__ edge_ids, int64_t n, const int32_t* __restrict__ pair_of_edge,
@@ -893,6 +944,27 @@ int ihg_sample_pool_excluding(uint64_t seed, uint64_t counter, int64_t n_rows, i
     hipLaunchKernelGGL(sample_pool_excluding_kernel, dim3(grid), dim3(kWave), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, static_cast<int>(m),
                        list_of_row, n_lists, list_ptr, list_items, out);
     return check_launch("ihg_sample_pool_excluding");
+}
+
+int ihg_sample_pool_weighted(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, const int64_t* cum, int64_t total, const int64_t* list_of_row,
+                             int64_t n_lists, const int64_t* list_ptr, const int32_t* list_items, int64_t max_list_len, int64_t* out, ihg_stream_t stream) {
+    if (n_rows < 0 || n_items <= 0 || m < 1 || m > kPoolDraws || m > n_items)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_weighted: need 1 <= m <= min(%d, n_items), got m = %d and n_items = %lld", kPoolDraws, m, (long long)n_items);
+    if (total < n_items)                                                 // (every weight is >= 1; a total of 2^63 or more arrives here as a negative int64)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_weighted: need n_items <= total < 2^63, got total = %lld and n_items = %lld", (long long)total, (long long)n_items);
+    if (n_lists < 0 || max_list_len < 0)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_weighted: need n_lists >= 0 and max_list_len >= 0, got n_lists = %lld and max_list_len = %lld", (long long)n_lists,
+                    (long long)max_list_len);
+    if (max_list_len > n_items - m)                                      // (the row with the longest list would have fewer than m values to find: its loop would not end)
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_weighted: need m + max_list_len <= n_items, got m = %d, max_list_len = %lld and n_items = %lld", m,
+                    (long long)max_list_len, (long long)n_items);
+    if (n_rows == 0) return IHG_OK;
+    if (cum == nullptr || out == nullptr || (n_lists > 0 && (list_of_row == nullptr || list_ptr == nullptr || list_items == nullptr)))
+        return fail(IHG_ERR_INVALID, "ihg_sample_pool_weighted: null pointer");
+    const int grid = static_cast<int>(std::min<int64_t>(n_rows, static_cast<int64_t>(kMaxBlocks) * kWavesPerBlock));
+    hipLaunchKernelGGL(sample_pool_weighted_kernel, dim3(grid), dim3(kWave), 0, static_cast<hipStream_t>(stream), seed, counter, n_rows, n_items, static_cast<int>(m), cum,
+                       static_cast<uint64_t>(total), n_lists > 0 ? list_of_row : nullptr, n_lists, list_ptr, list_items, out);
+    return check_launch("ihg_sample_pool_weighted");
 }
 
 int ihg_device_batch(uint64_t seed, uint64_t counter, const int64_t* pos_triples, const int64_t* edge_ids, int64_t n, const int32_t* pair_of_edge,

@@ -25,6 +25,7 @@ import ctypes
 import os as _os
 from typing import Optional, Tuple, Union
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -2378,6 +2379,74 @@ def sample_pool_excluding(seed: int, counter: int, n_rows: int, n_items: int, m:
     with profiler.kernel('sample_pool_excluding', n_rows, int(m)):
         _lib.check(_lib.load().ihg_sample_pool_excluding(int(seed) & mask, int(counter) & mask, n_rows, int(n_items), int(m), _ptr(rows), int(ptr.shape[0]) - 1, _ptr(ptr),
                                                          _ptr(ids), int(max_list_len), _ptr(out), _stream()), 'ihg_sample_pool_excluding')
+    return out
+
+
+def item_sampling_table(weights, device=None) -> Tuple[Tensor, int]:
+    """The table ``ihg_sample_pool_weighted`` draws from: ``(cum, total)`` with ``cum`` int64 ``[I + 1]`` on the device, ``cum[0] = 0``, ``cum[i + 1] = cum[i] + weights[i]``,
+    and ``total = cum[I]`` as a Python int.  ``weights`` is int64 ``[I]``, a host array or tensor (the table then goes to ``device``, default the current GPU) or a device
+    tensor (the table stays beside it).  Every weight must be >= 1 and the sum below 2^63: this is the one place where the launch's promise of a strictly ascending
+    ``cum`` is checked - before anything is copied for host weights, with one read-back for device weights."""
+    w = weights if isinstance(weights, Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+    if w.dtype != torch.int64 or w.dim() != 1 or not w.numel():
+        raise TypeError(f'item_sampling_table: weights must be a non-empty 1-D int64 array, got {tuple(w.shape)} {w.dtype}')
+    if w.is_cuda and device is not None and torch.device(device).index not in (None, w.device.index):
+        raise ValueError(f'item_sampling_table: weights are on {w.device}, the table was asked for on {torch.device(device)}')
+    cum = torch.zeros(int(w.shape[0]) + 1, dtype=torch.int64, device=w.device)
+    torch.cumsum(w, 0, out=cum[1:])                                             # (int64 wraps: positive weights whose sum passes 2^63 show as a step down)
+    smallest, ascending = int(w.min()), bool((cum[1:] > cum[:-1]).all())
+    if smallest < 1:
+        raise ValueError(f'item_sampling_table: every weight must be >= 1 (an item of weight 0 can never be drawn, and the draw would not end once the others are used up), '
+                         f'got a smallest weight of {smallest}')
+    if not ascending:
+        raise ValueError('item_sampling_table: the weights sum to 2^63 or more; the thresholds of the draw are int64')
+    total = int(cum[-1])
+    if not cum.is_cuda:
+        cum = cum.to(torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device))
+    return cum, total
+
+
+def sample_pool_weighted(seed: int, counter: int, n_rows: int, n_items: int, m: int, table: Tuple[Tensor, int], rows: Optional[Tensor] = None,
+                         lists: Optional[Tuple[Tensor, Tensor]] = None, max_list_len: int = 0, device=None) -> Tensor:
+    """``sample_pool`` / ``sample_pool_excluding`` with item weights (``ihg_sample_pool_weighted``): ``[n_rows, m]`` int64, ``m`` distinct items per row, every attempt
+    falling on item ``i`` with probability ``weights[i] / total``.  ``table = (cum, total)`` is ``item_sampling_table``'s, on the device, ``cum`` of ``n_items + 1`` entries.
+    ``rows`` and ``lists`` are ``sample_pool_excluding``'s and come together or not at all (``None``: no row has a list); ``max_list_len`` is the longest run, known on the
+    host.  With weights all equal the output is ``sample_pool_excluding``'s / ``sample_pool``'s bit for bit.  One kernel for every ``1 <= m <= 256``."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    cum, total = table
+    n_rows = int(n_rows)
+    if (rows is None) != (lists is None):
+        raise ValueError('sample_pool_weighted: rows and lists come together (both None: no row has a list)')
+    ptr, ids = lists if lists is not None else (None, None)
+    operands = (('table[0]', cum, torch.int64),) + ((('rows', rows, torch.int64), ('lists[0]', ptr, torch.int64), ('lists[1]', ids, torch.int32)) if lists is not None else ())
+    for name, t, dtype in operands:
+        if not isinstance(t, Tensor) or t.dtype != dtype or t.dim() != 1:
+            raise TypeError(f'sample_pool_weighted: {name} must be a 1-D {dtype} tensor, got {tuple(t.shape)} {t.dtype}' if isinstance(t, Tensor) else
+                            f'sample_pool_weighted: {name} must be a 1-D {dtype} tensor, got {type(t).__name__}')
+    for name, t, _ in operands:
+        _gpu(t, f'sample_pool_weighted: {name}')
+        if device.index is not None and t.device.index != device.index:
+            raise ValueError(f'sample_pool_weighted: {name} is on {t.device}, the draw on {device}')
+    if int(cum.shape[0]) != int(n_items) + 1:
+        raise ValueError(f'sample_pool_weighted: a table of {int(cum.shape[0])} entries does not belong to {int(n_items)} items (item_sampling_table gives n_items + 1)')
+    cum = cum.contiguous()
+    n_lists = 0
+    if lists is not None:
+        if int(rows.shape[0]) != max(n_rows, 0):
+            raise ValueError(f'sample_pool_weighted: {n_rows} rows but rows of {tuple(rows.shape)}')
+        if int(ptr.shape[0]) < 1:
+            raise ValueError('sample_pool_weighted: lists[0] holds at least the leading 0')
+        rows, ptr, ids = rows.contiguous(), ptr.contiguous(), ids.contiguous()
+        if not ids.numel():
+            ids = ids.new_zeros(1)                                              # (an empty tensor has no address; no offset reaches this entry)
+        n_lists = int(ptr.shape[0]) - 1
+        if n_lists == 0:
+            rows = ptr = ids = None                                             # (no run at all: the launch's form without lists)
+    out = torch.empty(max(n_rows, 0), max(int(m), 0), dtype=torch.int64, device=device)
+    mask = (1 << 64) - 1
+    with profiler.kernel('sample_pool_weighted', n_rows, int(m)):
+        _lib.check(_lib.load().ihg_sample_pool_weighted(int(seed) & mask, int(counter) & mask, n_rows, int(n_items), int(m), _ptr(cum), int(total), _ptr(rows), n_lists,
+                                                        _ptr(ptr), _ptr(ids), int(max_list_len), _ptr(out), _stream()), 'ihg_sample_pool_weighted')
     return out
 
 

@@ -586,6 +586,22 @@ int ihg_sample_pool(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_i
  * m + max_list_len <= n_items, and on a null pointer with rows to write: it has launched and written nothing.  n_rows == 0 returns IHG_OK and launches nothing. */
 int ihg_sample_pool_excluding(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, const int64_t* list_of_row, int64_t n_lists,
                               const int64_t* list_ptr, const int32_t* list_items, int64_t max_list_len, int64_t* out, ihg_stream_t stream);
+/* The pool draw with item weights (popularity-weighted negatives), with or without the per-row lists of ihg_sample_pool_excluding: out [n_rows, m] int64.  cum is int64
+ * [n_items + 1], the running sum of integer item weights: cum[0] = 0, strictly ascending (every weight >= 1), cum[n_items] = total < 2^63.  The lists are the CSR of
+ * ihg_sample_pool_excluding with its list_of_row and its rule that an l outside [0, n_lists) means an empty list; with n_lists == 0 the three list pointers may be null
+ * and no row has a list.  Sequential definition: row r walks ihg_sample_negatives' stream - key(seed, counter, r), attempts counted from 0, attempt a yields the
+ * threshold t = umulhi(mix64(key + a * 0x2545F4914F6CDD1D), total), and its value is the one i with cum[i] <= t < cum[i + 1]; a value is accepted iff it is not in the
+ * row's list and differs from every value accepted before it; out[r][0..m) are the first m accepted values, in attempt order.  So item i is drawn with probability
+ * (cum[i + 1] - cum[i]) / total per attempt, and the first accepted value follows the weights renormalised over the complement of the row's list.  With cum[i] = i the
+ * output is ihg_sample_pool_excluding's bit for bit (no lists: ihg_sample_pool's; m <= 16: ihg_sample_negatives'), and so it is with every weight 2^32, because
+ * umulhi(r, I * 2^32) >> 32 == umulhi(r, I); the first c columns of a call with m are what a call with c gives.  One kernel serves every m.  total and max_list_len
+ * are the caller's promises, computed on the host and never read back from the device, and so is the strict ascent of cum, which this call cannot see: a table with a
+ * zero weight, or a longer list, may keep a row from ever finding its m values.  IHG_ERR_INVALID unless 1 <= m <= min(256, n_items), n_items <= total < 2^63,
+ * n_lists >= 0, max_list_len >= 0 and m + max_list_len <= n_items, and on a null pointer with rows to write (the list pointers only when n_lists > 0): it has launched
+ * and written nothing.  n_rows == 0 returns IHG_OK and launches nothing. */
+int ihg_sample_pool_weighted(uint64_t seed, uint64_t counter, int64_t n_rows, int64_t n_items, int32_t m, const int64_t* cum, int64_t total,
+                             const int64_t* list_of_row, int64_t n_lists, const int64_t* list_ptr, const int32_t* list_items, int64_t max_list_len,
+                             int64_t* out, ihg_stream_t stream);
 
 /* DEVICE: one whole training batch in one launch, logged negatives included.  Replaces, for the n positives `edge_ids` of pos_triples [E, 3]
  * (user, query, item), GraphDataset.__getitem__ + collate_fn (Dataset.py:107-119, 282-291).  pack is the [4, n (1 + k)] array collate_fn builds, k = k_rand + k_logged,
